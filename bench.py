@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py — end-to-end 640x480 inference throughput (img/s) + hough-vote kernel roofline.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up the headline configuration, runs W warm-up steps, times EXACTLY K steps in one region and prints the
+result line (`value`, `ms_per_step`, `config`).  `--full` adds everything else listed below (side measurements, other
+configurations, CPU baseline, rooflines, the `train` object) and repeats the K-step region until `--min-seconds` are
+covered.  `--dump-outputs DIR` writes what the headline's last timed step returned (DIR/<name>.npy, f32 or f64, a fixed
+seeded sample of the larger arrays, 64 MB at most); the inputs and the vote's sampler seeds are the same from run to run.
 
 N > 1: one process per GPU.  Started plainly (`python bench.py --gpus 8`) the script spawns its N ranks itself
 (fresh child processes with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set; the parent never touches a GPU and relays
@@ -25,7 +31,7 @@ frame's post-network stages follow on the same stream; every frame completes all
 four submissions later); `config.ms_per_frame_one_in_flight` is the latency with one frame in flight.  Weak scaling:
 every rank runs its own frames; `value` = N * B * K / max-over-ranks(time).
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full):
   roofline          the hough-vote launch sequence at the headline config, as the model's pipeline calls it (the aggregation
                     layer's mask bit words: fpc_ransac_voting_v3_bits): algorithmic bytes n_instances * 12*H*W per call /
                     HIP-event device time of 10 calls on cold inputs (graph replay), against the 8 TB/s HBM peak of MI355X_MICROARCH.md;
@@ -44,7 +50,7 @@ Extra objects on the JSON line:
   train             BASELINE.json configs[4] at batch 8 on this GPU (fastposecnn_amd/train_bench.py; 1-GPU runs)
   cpu_baseline      the same step on the host: torch-CPU backbone + the C oracle's post-network path (1 thread and the
                     job's CPU share), three samples each
-`value` is the MEDIAN of the repeated K-step timed regions (`repeats`, `ms_per_step_min_max`).  `scaling_measured` is true
+With --full `value` is the MEDIAN of the repeated K-step timed regions (`repeats`, `ms_per_step_min_max`).  `scaling_measured` is true
 exactly when this line comes from an N > 1 run; such a line also carries `per_rank_img_per_s`, `rccl_ranks_seen` (what an
 all-reduce of ones over the job's backend summed to), `collective_backend`, `cores_per_rank` (each rank pins itself to its
 own share of the host cores before touching the GPU) and `config.pose_gather.us_per_collective`.
@@ -67,6 +73,7 @@ HBM_PEAK_GBPS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29
 MFMA_F32_PEAK_TFLOPS = 157.3    # MI355X_MICROARCH.md: f32-input MFMA = f32 vector peak (155 measured)
 VALU_PEAK_WAVE_INSTR_PER_S = 1024 * 2.4e9 / 2      # 1024 SIMD-32 units, a wave64 instruction issues over 2 cycles (the guide)
 H, W = 480, 640
+METRIC = "img/s end-to-end 640x480 inference; hough-vote kernel HBM GB/s vs roofline"
 
 
 def parse(argv=None):
@@ -87,7 +94,10 @@ def parse(argv=None):
     ap.add_argument("--no-hn128", action="store_true", help="skip the hn=128 / 32-frame vote roofline")
     ap.add_argument("--no-plain-f32", action="store_true", help="skip the second streamed measurement with plain f32 matrix products")
     ap.add_argument("--no-train-line", action="store_true", help="skip the `train` object (configs[4] at B=8 on this GPU, 1-GPU runs only)")
-    ap.add_argument("--min-seconds", type=float, default=0.5, help="the K-step timed region is repeated until this much time is covered; `value` is the median repeat")
+    ap.add_argument("--full", action="store_true", help="also run every side measurement, configuration and baseline (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the headline's last timed step returned as DIR/<name>.npy")
+    ap.add_argument("--min-seconds", type=float, default=None, help="the K-step timed region is repeated until this much time is covered; "
+                                                                     "`value` is the median repeat (default 0.5 with --full, else 0: one region)")
     ap.add_argument("--gather-every", type=int, default=0, help="frames per pose all-gather on the side stream (0 = frames in flight)")
     ap.add_argument("--check-gather", action="store_true", help="N > 1: verify the gathered pose records against every rank's records rebuilt locally")
     ap.add_argument("--vote-only", action="store_true", help="time only the post-network stages (profiling aid)")
@@ -111,6 +121,8 @@ def parse(argv=None):
         args.steps = 20 if args.train else 300
     if args.warmup is None:
         args.warmup = 3 if args.train else 20
+    if args.min_seconds is None:
+        args.min_seconds = 0.5 if args.full else 0.0
     return args
 
 
@@ -214,6 +226,29 @@ def multi_rank_fields(dist, torch, world, rank, dev, local_s, units_per_rank, ba
 def median(xs):
     xs = sorted(xs)
     return xs[len(xs) // 2]
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, out):
+    """--dump-outputs: every tensor of forward()'s dict for the last timed step as path/<group>_<key>.npy — floating
+    tensors as f32, integer ones as f64 (exact).  An array larger than its share of DUMP_BYTES is replaced by the elements
+    at fixed indices (seed 0, sorted, drawn over the flattened tensor), gathered on the device; the same arguments give
+    the same shapes, hence the same indices, in every run."""
+    import numpy as np
+    import torch
+    arrays = [(f"{group}_{key}", t) for group, d in out.items() if isinstance(d, dict)
+              for key, t in d.items() if torch.is_tensor(t)]
+    cap = (DUMP_BYTES - (64 << 10) * len(arrays)) // (8 * max(1, len(arrays)))     # elements per array (8 bytes, npy headers aside)
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays:
+        flat = t.detach().reshape(-1)
+        if flat.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), cap))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = (flat.float() if flat.is_floating_point() and flat.dtype != torch.float64 else flat.double()).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a if t.numel() > cap else a.reshape(tuple(t.shape)))
 
 
 def cpu_baseline(model_cpu, image, cat_cpu, hn, inv_k, encoder):
@@ -482,9 +517,10 @@ def check_gather(model_gpu, gatherer, cat, Bq, world, rank, cap, dev):
 
 
 def run_inference(args, encoder, Bq, hn, steps, warmup, world, rank, dev, want_backbone=True, split_precision=None, coalesce=1, tune_trials=1,
-                  split_f16=None, split_f16_3p=None):
+                  split_f16=None, split_f16_3p=None, want_side=True, dump=None):
     """The timed hot path for one (encoder, batch) configuration.  Returns a dict of measurements and the objects
-    later sections reuse."""
+    later sections reuse.  want_side: the one-frame-in-flight latency and the serial collective timing after the timed
+    region; dump: a directory for what the last timed step returned (rank 0 writes it)."""
     import torch
     import torch.distributed as dist
     import fastposecnn_amd.lib as L
@@ -530,10 +566,14 @@ def run_inference(args, encoder, Bq, hn, steps, warmup, world, rank, dev, want_b
     # pose records of `gather_every` frames per RCCL all-gather, issued on a side stream: no frame waits for it
     gatherer = parallel.PoseGatherer(cap, every=args.gather_every or max(1, depth + 1), device=dev) if world > 1 else None
 
+    last = [None]                                             # what the latest collected step returned (--dump-outputs)
+
     def finish(ticket):
         out = {"aggregated": model_gpu.post_network_finish(ticket)} if args.vote_only else streamer.collect(ticket)
         if gatherer is not None:
             gatherer.add(out["aggregated"], rank * Bq)       # pack = one native launch; the collective follows on the side stream
+        if dump:
+            last[0] = out
         return out
 
     def step(pipelined=True):
@@ -574,6 +614,7 @@ def run_inference(args, encoder, Bq, hn, steps, warmup, world, rank, dev, want_b
     # EXACTLY `steps` steps between barrier + synchronize on both sides, max over ranks; the region is repeated until
     # `--min-seconds` are covered (20 steps are 16 ms, a quarter of it pipeline fill and drain) and the MEDIAN repeat is reported
     def timed_region():
+        torch.manual_seed(1 + rank)      # the vote's sampler seeds of the region's steps (drawn per submission): the same in every region and run
         barrier()
         t0 = time.perf_counter()
         for _ in range(steps):
@@ -602,31 +643,36 @@ def run_inference(args, encoder, Bq, hn, steps, warmup, world, rank, dev, want_b
             dts.append(timed_region())
             repeats += 1
     dt = median(dts)
+    if dump and rank == 0:
+        dump_outputs(dump, last[0])
+    last[0] = None
 
     # per-frame latency with ONE frame in flight (not the headline number)
-    nlat = max(5, min(steps, 20))
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(nlat):
-        step(pipelined=False)
-    torch.cuda.synchronize()
-    latency_ms = (time.perf_counter() - t1) / nlat * 1e3
+    latency_ms = None
+    if want_side:
+        nlat = max(5, min(steps, 20))
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(nlat):
+            step(pipelined=False)
+        torch.cuda.synchronize()
+        latency_ms = round((time.perf_counter() - t1) / nlat * 1e3, 4)
 
     pose_gather = None
     if gatherer is not None:
-        # one collective, issue -> complete, serial (nothing else in flight): the cost the side stream hides per round
-        ncol = gatherer.collectives
-        barrier()
-        t_c = time.perf_counter()
-        for _ in range(20):
-            gatherer.flush()
-            gatherer.latest()
-        us_col = (time.perf_counter() - t_c) / 20 * 1e6
-        pose_gather = {"frames_per_collective": gatherer.every, "collectives": ncol, "stream": "side", "record_bytes": 160,
-                       "capacity_per_frame": cap, "bytes_per_rank_per_collective": gatherer.every * (cap + 1) * 160,
-                       "us_per_collective": round(us_col, 1),
-                       "us_per_collective_note": "20 serial empty rounds after the timed region, issue -> host-visible completion; "
-                                                 "warmed by the warm-up steps' collectives; inside the timed region it runs on a side stream"}
+        pose_gather = {"frames_per_collective": gatherer.every, "collectives": gatherer.collectives, "stream": "side", "record_bytes": 160,
+                       "capacity_per_frame": cap, "bytes_per_rank_per_collective": gatherer.every * (cap + 1) * 160}
+        if want_side:
+            # one collective, issue -> complete, serial (nothing else in flight): the cost the side stream hides per round
+            barrier()
+            t_c = time.perf_counter()
+            for _ in range(20):
+                gatherer.flush()
+                gatherer.latest()
+            us_col = (time.perf_counter() - t_c) / 20 * 1e6
+            pose_gather["us_per_collective"] = round(us_col, 1)
+            pose_gather["us_per_collective_note"] = ("20 serial empty rounds after the timed region, issue -> host-visible completion; "
+                                                     "warmed by the warm-up steps' collectives; inside the timed region it runs on a side stream")
         if args.check_gather:
             pose_gather["verified"] = check_gather(model_gpu, gatherer, cat, Bq, world, rank, cap, dev)
     res = {"value": round(world * Bq * steps / dt, 3), "ms_per_step": round(dt / steps * 1e3, 4), "steps": steps, "warmup": warmup,
@@ -636,7 +682,7 @@ def run_inference(args, encoder, Bq, hn, steps, warmup, world, rank, dev, want_b
                        f"{len(streamer.models)} streams, hn={hn}, {n_inst} instances per step (vote-bench fixture), random-init weights",
            "global_batch": world * Bq, "frames_in_flight": 1 + depth, "net_streams": len(streamer.models), "stream_tune_mode": stream_tune,
            "tune_trials": tune_trials, "trial_rates_img_per_s": getattr(streamer, "trial_rates", []),
-           "ms_per_frame_one_in_flight": round(latency_ms, 4)}
+           "ms_per_frame_one_in_flight": latency_ms}
 
     # the same pipeline fed from HOST memory: decoded u8 frames -> pinned staging -> H2D -> preprocessing kernels -> network
     # (F/tools/dataset.py:249-262 on the device).  PCIe-inclusive, so never `value`.
@@ -816,6 +862,55 @@ def load_profile_json(name):
     return None
 
 
+def matrix_products_note():
+    """`config.matrix_products`: the product forms the engine's plans may use."""
+    if os.environ.get("FPC_SPLIT_PRECISION", "1") == "0":
+        return "plain f32 matrix products (v_mfma_f32_32x32x2_f32) everywhere: FPC_SPLIT_PRECISION=0"
+    return ("f32 operands, f32 accumulation, f32 results (dtype f32).  Where the autotuner finds it "
+            "faster a convolution's products run in SPLIT PRECISION on the 16-bit matrix instructions: (a) the "
+            "exact three-way bf16 split of both operands, six partial products on v_mfma_f32_32x32x16_bf16, "
+            "dropped terms < 2^-23 — any operand range; (b) round 6, 3x3 / stride-1 sites only "
+            "(csrc/wino_h2.hip, wino_h3.hip): two fp16 pieces per operand (22 significant bits) on "
+            "v_mfma_f32_32x32x16_f16 — all four piece products in two instructions per 8 channels, or (the "
+            "default where Cin is a multiple of 16) three of them in three instructions per 16 channels: the "
+            "dropped h2 g2 is <= 2^-22 of the term, the size of the two terms any two-piece form drops; "
+            "weights scaled by a power of two on the device, activations as they "
+            "come: 2^-22 relative for |v| >= 2^-3, 2^-25 absolute below, saturation beyond 1.3e5 — f32-level "
+            "for activations of ordinary scale, held to the same bars (2e-5 per convolution, 1e-4 of the "
+            "logits against float64 with EVERY eligible site forced onto it: tests/test_gpu_net.py).  "
+            "FPC_SPLIT_F16_3P=0 (HPARAM.ENGINE_SPLIT_F16_3P = False) keeps all four products — "
+            "`fp16_four_products`; FPC_SPLIT_F16=0 (HPARAM.ENGINE_SPLIT_F16 = False) keeps (a) only — `bf16x3_products`; "
+            "FPC_SPLIT_PRECISION=0 keeps every product on v_mfma_f32_32x32x2_f32")
+
+
+def plain_run(args, world, rank, dev, dist, backend, cores):
+    """The run without --full: the configuration a --full line reports at its top level (ResNet34, batch 32, for the default
+    invocation), its set-up, the W warm-up steps and ONE region of exactly K timed steps; the same top-level fields."""
+    import torch
+    promoted = args.promote and world == 1 and not args.no_config3
+    encoder, batch = ("resnet34", 32) if promoted else (args.encoder, args.batch)
+    res, _ = run_inference(args, encoder, batch, args.hn, args.steps, args.warmup, world, rank, dev, want_backbone=False,
+                           tune_trials=1 if promoted else args.tune_trials, want_side=False, dump=args.dump_outputs)
+    multi = (multi_rank_fields(dist, torch, world, rank, dev, res["local_s"], batch * args.steps, backend, cores)
+             if world > 1 else {"scaling_measured": False})
+    if rank == 0:
+        config = {"workload": res["workload"], "global_batch": res["global_batch"],
+                  "parallelism": f"image-sharded dp{world}" if world > 1 else "single GPU",
+                  "vote_only": bool(args.vote_only), "frames_in_flight": res["frames_in_flight"], "net_streams": res["net_streams"],
+                  "stream_tune_mode": res["stream_tune_mode"], "tune_trials": res["tune_trials"],
+                  "trial_rates_img_per_s": res["trial_rates_img_per_s"], "pose_gather": res["pose_gather"],
+                  "matrix_products": matrix_products_note(),
+                  "post_network_input": "synthetic vote-bench fixture (SURVEY.md 8d), not the random-weight network's output"}
+        if promoted:
+            config["baseline_config"] = "BASELINE.json configs[2] (per GPU also configs[3]'s share)"
+        print(json.dumps({"metric": METRIC, "value": res["value"], "unit": "img/s", "n_gpus": world, "steps": args.steps,
+                          "warmup": args.warmup, "ms_per_step": res["ms_per_step"], "higher_is_better": True, "scaling": "weak",
+                          **multi, "vs_baseline": None, "dtype": "f32", "data": "synthetic", "repeats": res["repeats"],
+                          "ms_per_step_min_max": res["ms_per_step_min_max"], "config": config}), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
 def promote_config3(line, c3, r3, args):
     """The default invocation's record: BASELINE.json configs[2] (ResNet34, batch 32 — the largest single-GPU configuration,
     and one rank's share of configs[3]) at the TOP level — value, ms_per_step, config, roofline, backbone, cpu_baseline —
@@ -909,8 +1004,12 @@ def main():
 
     from fastposecnn_amd import synth, _native
     _native.lib()      # fail loudly if the HIP library is missing
+    if not args.full:
+        return plain_run(args, world, rank, dev, dist, backend, cores)
 
-    res, ctx = run_inference(args, args.encoder, args.batch, args.hn, args.steps, args.warmup, world, rank, dev, tune_trials=args.tune_trials)
+    promoted = args.promote and world == 1 and not args.no_config3          # config 3's run below is the top-level record
+    res, ctx = run_inference(args, args.encoder, args.batch, args.hn, args.steps, args.warmup, world, rank, dev, tune_trials=args.tune_trials,
+                             dump=None if promoted else args.dump_outputs)
     multi = (multi_rank_fields(dist, torch, world, rank, dev, res["local_s"], args.batch * args.steps, backend, cores)
              if world > 1 else {"scaling_measured": False})
 
@@ -929,7 +1028,7 @@ def main():
                                   "built in round 4 and were slower (tools_dev/r4_vote_fused/README.md); since round 6 the RT assembly rides on "
                                   "the last of the four (fpc_ransac_voting_v3_pose)")
         line = {
-            "metric": "img/s end-to-end 640x480 inference; hough-vote kernel HBM GB/s vs roofline",
+            "metric": METRIC,
             "value": res["value"], "unit": "img/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": res["ms_per_step"], "higher_is_better": True,
             "scaling": "weak", **multi, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -941,23 +1040,7 @@ def main():
                        "stream_tune_mode": res.get("stream_tune_mode"), "tune_trials": res.get("tune_trials"),
                        "trial_rates_img_per_s": res.get("trial_rates_img_per_s"),
                        "pose_gather": res["pose_gather"],
-                       "matrix_products": ("f32 operands, f32 accumulation, f32 results (dtype f32).  Where the autotuner finds it "
-                                           "faster a convolution's products run in SPLIT PRECISION on the 16-bit matrix instructions: (a) the "
-                                           "exact three-way bf16 split of both operands, six partial products on v_mfma_f32_32x32x16_bf16, "
-                                           "dropped terms < 2^-23 — any operand range; (b) round 6, 3x3 / stride-1 sites only "
-                                           "(csrc/wino_h2.hip, wino_h3.hip): two fp16 pieces per operand (22 significant bits) on "
-                                           "v_mfma_f32_32x32x16_f16 — all four piece products in two instructions per 8 channels, or (the "
-                                           "default where Cin is a multiple of 16) three of them in three instructions per 16 channels: the "
-                                           "dropped h2 g2 is <= 2^-22 of the term, the size of the two terms any two-piece form drops; "
-                                           "weights scaled by a power of two on the device, activations as they "
-                                           "come: 2^-22 relative for |v| >= 2^-3, 2^-25 absolute below, saturation beyond 1.3e5 — f32-level "
-                                           "for activations of ordinary scale, held to the same bars (2e-5 per convolution, 1e-4 of the "
-                                           "logits against float64 with EVERY eligible site forced onto it: tests/test_gpu_net.py).  "
-                                           "FPC_SPLIT_F16_3P=0 (HPARAM.ENGINE_SPLIT_F16_3P = False) keeps all four products — "
-                                           "`fp16_four_products`; FPC_SPLIT_F16=0 (HPARAM.ENGINE_SPLIT_F16 = False) keeps (a) only — `bf16x3_products`; "
-                                           "FPC_SPLIT_PRECISION=0 keeps every product on v_mfma_f32_32x32x2_f32")
-                                          if os.environ.get("FPC_SPLIT_PRECISION", "1") != "0" else
-                                          "plain f32 matrix products (v_mfma_f32_32x32x2_f32) everywhere: FPC_SPLIT_PRECISION=0",
+                       "matrix_products": matrix_products_note(),
                        "post_network_input": "synthetic vote-bench fixture (SURVEY.md 8d), not the random-weight network's output",
                        "img_per_s_from_host_u8_frames": res.get("host_frames_img_per_s"), "host_frames": res.get("host_frames"),
                        "img_per_s_from_png_files": res.get("png_files_img_per_s"),
@@ -1030,7 +1113,7 @@ def main():
             torch.cuda.empty_cache()
             # promoted to the top level (the default invocation): EXACTLY the K timed steps and W warm-up steps asked for
             st, wu3 = (args.steps, args.warmup) if args.promote else (max(10, args.steps // 10), max(2, args.warmup // 5))
-            r3, ctx3 = run_inference(args, "resnet34", 32, args.hn, st, wu3, 1, 0, dev)
+            r3, ctx3 = run_inference(args, "resnet34", 32, args.hn, st, wu3, 1, 0, dev, dump=args.dump_outputs if args.promote else None)
             c3 = {"metric": "img/s end-to-end 640x480 inference", "value": r3["value"], "unit": "img/s",
                   "ms_per_step": r3["ms_per_step"], "steps": r3["steps"], "warmup": r3["warmup"], "dtype": "f32",
                   "config": {"workload": r3["workload"], "global_batch": 32, "frames_in_flight": r3["frames_in_flight"],

@@ -426,6 +426,35 @@ def test_bench_launches_its_own_ranks():
     assert out.returncode != 0
 
 
+def test_bench_dump_outputs_fixed_sample_within_budget(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs`: every tensor of forward()'s dict as <group>_<key>.npy in f32 (floating) or f64 (integer),
+    whole when it fits its share of the byte budget, else the same seeded sample in every run; the total stays in budget.
+    A plain run times exactly --steps steps in one region; --full repeats it for --min-seconds."""
+    import importlib
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4 << 20)
+    g = torch.Generator().manual_seed(0)
+    out = {"logits": {"mask": torch.randn((2, 7, 48, 64), generator=g)},
+           "categorical": {"mask": torch.randint(0, 7, (2, 96, 128), generator=g)},
+           "aggregated": {"class_ids": torch.arange(5), "instance_masks": torch.rand((5, 480, 640), generator=g),
+                          "RT": torch.randn((5, 4, 4), generator=g, dtype=torch.float64)}}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), out)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["aggregated_RT.npy", "aggregated_class_ids.npy", "aggregated_instance_masks.npy",
+                     "categorical_mask.npy", "logits_mask.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 4 << 20
+    got = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    assert all(np.array_equal(v, np.load(tmp_path / "b" / (k + ".npy"))) for k, v in got.items())
+    assert np.array_equal(got["logits_mask"], out["logits"]["mask"].numpy()) and got["logits_mask"].dtype == np.float32
+    assert np.array_equal(got["categorical_mask"], out["categorical"]["mask"].numpy()) and got["categorical_mask"].dtype == np.float64
+    assert got["aggregated_RT"].dtype == np.float64 and got["aggregated_class_ids"].dtype == np.float64
+    s = got["aggregated_instance_masks"]
+    assert s.ndim == 1 and 0 < s.size < out["aggregated"]["instance_masks"].numel() and s.dtype == np.float32
+    assert np.isin(s, out["aggregated"]["instance_masks"].numpy().ravel()).all()
+    assert bench.parse(["--steps", "7"]).min_seconds == 0 and bench.parse(["--full"]).min_seconds == 0.5
+
+
 def test_training_conv_helpers_fall_back_to_torch_on_cpu():
     """lib/train_conv.py on CPU tensors: plain torch results and gradients (the native kernels are GPU-only and are never
     substituted silently: the GPU tests assert that they ran)."""
