@@ -65,6 +65,7 @@ _SIGNATURES = {
     "fpc_png_decode": (_i, [_vp, _sz, _vp, _sz, _i]),
     "fpc_png_decode_batch": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_sz), _i, _vp, _i, _i, _i]),
     "fpc_net_create": (_i, [ctypes.c_char_p, _i, _i, _i, _i, ctypes.POINTER(_vp)]),
+    "fpc_net_create_encoder": (_i, [_i, ctypes.POINTER(_i), _i, _i, _i, _i, ctypes.POINTER(_vp)]),
     "fpc_net_destroy": (None, [_vp]),
     "fpc_net_set_graph": (_i, [_vp, _i]),
     "fpc_net_set_split_precision": (_i, [_vp, _i]),
@@ -80,6 +81,7 @@ _SIGNATURES = {
     "fpc_net_conv_plan": (_i, [_vp, _i, ctypes.POINTER(_i)]),
     "fpc_net_copy_plans": (_i, [_vp, _vp]),
     "fpc_net_force_winograd": (_i, [_vp, _i]),
+    "fpc_net_force_pointwise": (_i, [_vp, _i]),
     "fpc_net_flops": (_i, [_vp, ctypes.POINTER(ctypes.c_double)]),
     "fpc_net_tensor": (_i, [_vp, ctypes.c_char_p, ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i),
                             ctypes.POINTER(_i)]),

@@ -3,7 +3,8 @@
 // (F/lib/pose_regressor.py:709-743, 445-457) for inference.
 //
 // The graph is the one segmentation_models_pytorch builds for FastPoseCNN
-// (encoder = ResNet BasicBlock x {2,2,2,2} or {3,4,6,3}; four FPN decoders, merge "add";
+// (encoder = ResNet BasicBlock x {2,2,2,2} or {3,4,6,3}, or Bottleneck x {3,4,6,3} / {3,4,23,3} / {3,8,36,3} whose 1x1 sites
+// may run on k_conv1x1 (pointwise.hip); four FPN decoders, merge "add";
 // four 1x1 heads + x4 bilinear), see fastposecnn_amd/lib/backbone.py.  The plan owns no device
 // memory: packed weights, activations and split-K scratch live in one caller-provided workspace.
 // Launch order per frame (R18): stem conv, max-pool, 16 encoder convs (+3 downsample 1x1) with
@@ -43,6 +44,7 @@ struct ConvPlan {
     int bm = 64, bn = 64, nsplit = 1, mtiles = 1, ntiles = 1, wino = 0, bf3 = 0, fused = 0;
     int lat = 0;             // > 0: k_lateral1x1 with this many workgroups per 128-pixel tile (lateral.hip) instead of k_conv_igemm
     int stem = 0;            // > 0: k_stem7x7 (stem.hip), a persistent grid of this many workgroups (one per CU: 256)
+    int pw = 0;              // > 0: k_conv1x1 (pointwise.hip), variant pw - 1 (net_kernels.hpp: PwArgs::variant)
 };
 
 // the 7x7 / stride-2 / pad-3 stem in its row-per-K-step layout (NHWC4 image, 8 taps x 4 channels per kernel row, K = 224) with a
@@ -62,6 +64,20 @@ static bool lateral_ok(const ConvArgs& a, int groups) {
         return false;
     for (int g = 0; g < groups; ++g)
         if (a.p[g].in != a.p[0].in || a.p[g].scale || a.p[g].res || a.p[g].gn_part || ((a.p[g].up != nullptr) != (a.p[0].up != nullptr)))
+            return false;
+    return !(a.p[0].up && ((a.Ho | a.Wo) & 1));
+}
+
+// a 1x1 site k_conv1x1 takes: K a multiple of 64, Cout of 64, stride 1 or 2, channel-contiguous input shared by the groups,
+// no GroupNorm partials and the same epilogue operands in every group
+static bool pw_ok(const ConvArgs& a, int groups) {
+    if (a.Kh != 1 || a.Kw != 1 || a.pad != 0 || (a.stride != 1 && a.stride != 2) || a.generic != 0 || a.lanepx || a.Cin % 64 != 0 ||
+        a.Kpad != a.Cin || a.Cout % 64 != 0 || a.in_sc != 1)
+        return false;
+    for (int g = 0; g < groups; ++g)
+        if (a.p[g].in != a.p[0].in || a.p[g].gn_part || (a.p[g].scale != nullptr) != (a.p[0].scale != nullptr) ||
+            (a.p[g].shift != nullptr) != (a.p[0].shift != nullptr) || (a.p[g].res != nullptr) != (a.p[0].res != nullptr) ||
+            (a.p[g].up != nullptr) != (a.p[0].up != nullptr))
             return false;
     return !(a.p[0].up && ((a.Ho | a.Wo) & 1));
 }
@@ -129,7 +145,7 @@ using namespace fpc;
 struct fpc_net {
     int layers[4];
     int classes, B, H, W;
-    bool r34 = false;
+    int expansion = 1;            // 1: BasicBlock encoder, 4: Bottleneck (1x1, 3x3 with the stride, 1x1 x 4)
     std::vector<std::string> pnames;
     std::vector<int64_t> pnumel;
     std::vector<const float*> pptr;
@@ -144,7 +160,7 @@ struct fpc_net {
 
     // conv indices
     int c_stem = -1;
-    struct Block { int conv1, conv2, ds; };
+    struct Block { int conv1, conv2, ds, conv3 = -1; };      // conv3: Bottleneck only
     std::vector<Block> blocks[4];
     struct Dec {
         int lat[4];               // p5, p4, p3, p2 (1x1, bias)
@@ -157,6 +173,7 @@ struct fpc_net {
     // activations (float offsets)
     Act a_img4, a_stem, a_pool;
     std::vector<Act> a_blk_t[4], a_blk_y[4], a_blk_d[4];
+    std::vector<Act> a_blk_t2[4];  // Bottleneck: conv2's output (a_blk_t: conv1's); a stage's blocks share T1, T2 and two outputs
     Act a_p[4][4];                // [decoder][p5,p4,p3,p2]
     Act a_seg[4][7];              // pre-GroupNorm conv outputs
     Act a_up[4][3];               // s5.0 -> up, s5.1 -> up, s4.0 -> up
@@ -212,12 +229,33 @@ static const char* kHeadNames[4] = {"segmentation_head", "rotation_head", "trans
 
 static int conv_out(int x, int k, int s, int p) { return (x + 2 * p - k) / s + 1; }
 
+// the plan of `n` (layers and expansion set) for (classes, B, H, W); owns `n` (deleted on failure)
+static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** out);
+
 extern "C" int fpc_net_create(const char* encoder, int classes, int B, int H, int W, fpc_net_t** out) {
     if (!encoder || !out || classes < 2 || classes > 8 || B < 1 || H < 32 || W < 32 || H % 32 || W % 32) return FPC_EINVAL;
     fpc_net* n = new fpc_net();
     if (!strcmp(encoder, "resnet18")) { int l[4] = {2, 2, 2, 2}; memcpy(n->layers, l, sizeof(l)); }
-    else if (!strcmp(encoder, "resnet34")) { int l[4] = {3, 4, 6, 3}; memcpy(n->layers, l, sizeof(l)); n->r34 = true; }
+    else if (!strcmp(encoder, "resnet34")) { int l[4] = {3, 4, 6, 3}; memcpy(n->layers, l, sizeof(l)); }
     else { delete n; return FPC_EINVAL; }
+    return net_build(n, classes, B, H, W, out);
+}
+
+// An encoder by its descriptor: block 1 = BasicBlock, 4 = Bottleneck (torchvision's: the stride on the 3x3), layers4 = blocks per
+// stage.  (1, {2,2,2,2}) and (1, {3,4,6,3}) are the plans fpc_net_create builds for "resnet18" / "resnet34".
+extern "C" int fpc_net_create_encoder(int block, const int* layers4, int classes, int B, int H, int W, fpc_net_t** out) {
+    if (!layers4 || !out || (block != 1 && block != 4) || classes < 2 || classes > 8 || B < 1 || H < 32 || W < 32 || H % 32 ||
+        W % 32)
+        return FPC_EINVAL;
+    for (int L = 0; L < 4; ++L)
+        if (layers4[L] < 1 || layers4[L] > 64) return FPC_EINVAL;
+    fpc_net* n = new fpc_net();
+    memcpy(n->layers, layers4, sizeof(n->layers));
+    n->expansion = block;
+    return net_build(n, classes, B, H, W, out);
+}
+
+static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** out) {
     n->classes = classes; n->B = B; n->H = H; n->W = W;
     {   // merge + head in two passes (merge_split.hip) unless FPC_MERGE_SPLIT=0; read once, here
         const char* e = getenv("FPC_MERGE_SPLIT");
@@ -228,6 +266,7 @@ extern "C" int fpc_net_create(const char* encoder, int classes, int B, int H, in
     // ---- parameters + packed storage (persistent region first)
     n->c_stem = n->add_conv("encoder.conv1.weight", 3, 64, 7, 2, 3, "encoder.bn1", nullptr, 4, 8);     // NHWC4 pixels, 8 taps per row
     const int planes[4] = {64, 128, 256, 512};
+    const int e = n->expansion;
     int inpl = 64;
     for (int L = 0; L < 4; ++L)
         for (int bi = 0; bi < n->layers[L]; ++bi) {
@@ -235,6 +274,18 @@ extern "C" int fpc_net_create(const char* encoder, int classes, int B, int H, in
             fpc_net::Block blk;
             snprintf(buf, sizeof(buf), "encoder.layer%d.%d", L + 1, bi);
             std::string p(buf);
+            if (e == 4) {      // Bottleneck: 1x1 -> 3x3 (stride) -> 1x1 x 4, torchvision's parameter order
+                const int C = 4 * planes[L];
+                blk.conv1 = n->add_conv(p + ".conv1.weight", inpl, planes[L], 1, 1, 0, (p + ".bn1").c_str(), nullptr);
+                blk.conv2 = n->add_conv(p + ".conv2.weight", planes[L], planes[L], 3, stride, 1, (p + ".bn2").c_str(), nullptr);
+                blk.conv3 = n->add_conv(p + ".conv3.weight", planes[L], C, 1, 1, 0, (p + ".bn3").c_str(), nullptr);
+                blk.ds = -1;
+                if (stride != 1 || inpl != C)
+                    blk.ds = n->add_conv(p + ".downsample.0.weight", inpl, C, 1, stride, 0, (p + ".downsample.1").c_str(), nullptr);
+                inpl = C;
+                n->blocks[L].push_back(blk);
+                continue;
+            }
             blk.conv1 = n->add_conv(p + ".conv1.weight", inpl, planes[L], 3, stride, 1, (p + ".bn1").c_str(), nullptr);
             blk.conv2 = n->add_conv(p + ".conv2.weight", planes[L], planes[L], 3, 1, 1, (p + ".bn2").c_str(), nullptr);
             blk.ds = -1;
@@ -248,8 +299,8 @@ extern "C" int fpc_net_create(const char* encoder, int classes, int B, int H, in
     for (int d = 0; d < 4; ++d) {
         std::string D(kDecNames[d]);
         fpc_net::Dec& dc = n->dec[d];
-        dc.lat[0] = n->add_conv(D + ".p5.weight", 512, 256, 1, 1, 0, nullptr, (D + ".p5.bias").c_str());
-        const int skipc[3] = {256, 128, 64};
+        dc.lat[0] = n->add_conv(D + ".p5.weight", 512 * e, 256, 1, 1, 0, nullptr, (D + ".p5.bias").c_str());
+        const int skipc[3] = {256 * e, 128 * e, 64 * e};
         for (int i = 0; i < 3; ++i) {
             snprintf(buf, sizeof(buf), "%s.p%d.skip_conv", kDecNames[d], 4 - i);
             std::string p(buf);
@@ -288,8 +339,27 @@ extern "C" int fpc_net_create(const char* encoder, int classes, int B, int H, in
     {
         int h = hp, w = wp;
         for (int L = 0; L < 4; ++L) {
+            const int hin = h, win = w;
             if (L > 0) { h = conv_out(h, 3, 2, 1); w = conv_out(w, 3, 2, 1); }
             fh[L] = h; fw[L] = w;
+            if (e == 4) {
+                // only a block's output feeds the next block: the stage's blocks share conv1's output (block 0's, at the stage's
+                // input resolution, is the largest), conv2's, the downsample's and two outputs in turn (a block reads its
+                // predecessor's as input and residual); the last block's is the stage's feature map
+                const int C = 4 * planes[L];
+                const Act t1 = n->alloc_act(hin, win, planes[L]), t2 = n->alloc_act(h, w, planes[L]);
+                const Act y[2] = {n->alloc_act(h, w, C), n->alloc_act(h, w, C)};
+                const Act dd = n->alloc_act(h, w, C);
+                for (int bi = 0; bi < n->layers[L]; ++bi) {
+                    Act t = t1;
+                    if (bi > 0) { t.H = h; t.W = w; }
+                    n->a_blk_t[L].push_back(t);
+                    n->a_blk_t2[L].push_back(t2);
+                    n->a_blk_y[L].push_back(y[bi & 1]);
+                    n->a_blk_d[L].push_back(n->blocks[L][bi].ds >= 0 ? dd : Act());
+                }
+                continue;
+            }
             for (int bi = 0; bi < n->layers[L]; ++bi) {
                 n->a_blk_t[L].push_back(n->alloc_act(h, w, planes[L]));
                 n->a_blk_y[L].push_back(n->alloc_act(h, w, planes[L]));
@@ -329,7 +399,15 @@ extern "C" int fpc_net_create(const char* encoder, int classes, int B, int H, in
     };
     plan(n->c_stem, h1 * w1, 1);
     for (int L = 0; L < 4; ++L)
-        for (auto& blk : n->blocks[L]) {
+        for (size_t bi = 0; bi < n->blocks[L].size(); ++bi) {
+            const fpc_net::Block& blk = n->blocks[L][bi];
+            if (e == 4) {
+                plan(blk.conv1, n->a_blk_t[L][bi].H * n->a_blk_t[L][bi].W, 1);
+                plan(blk.conv2, fh[L] * fw[L], 1);
+                plan(blk.conv3, fh[L] * fw[L], 1);
+                if (blk.ds >= 0) plan(blk.ds, fh[L] * fw[L], 1);
+                continue;
+            }
             plan(blk.conv1, fh[L] * fw[L], 1);
             plan(blk.conv2, fh[L] * fw[L], 1);
             if (blk.ds >= 0) plan(blk.ds, fh[L] * fw[L], 1);
@@ -462,6 +540,24 @@ int launch_conv_plan(ConvArgs& a, const ConvPlan& p, int groups, hipStream_t s) 
         t.grid = p.stem;
         return launch_stem7x7(t, s);
     }
+    if (p.pw) {
+        if (!pw_ok(a, groups)) return FPC_EINVAL;
+        PwArgs w;
+        memset(&w, 0, sizeof(w));
+        w.in = a.p[0].in;
+        for (int g = 0; g < groups; ++g) {
+            // the three bf16 planes sit behind the f32 image (k_pack_weight_bf3)
+            w.wpl[g] = reinterpret_cast<const unsigned short*>(a.p[g].w + (size_t)a.Npad * a.Kpad);
+            w.out[g] = a.p[g].out; w.scale[g] = a.p[g].scale; w.shift[g] = a.p[g].shift; w.res[g] = a.p[g].res; w.up[g] = a.p[g].up;
+        }
+        w.in_sb = a.in_sb; w.in_sh = a.in_sh; w.in_sw = a.in_sw;
+        w.B = a.B; w.Ho = a.Ho; w.Wo = a.Wo; w.Cin = a.Cin; w.Cout = a.Cout; w.Npad = a.Npad; w.Kpad = a.Kpad; w.stride = a.stride;
+        w.groups = groups; w.relu = a.relu;
+        w.has_scale = a.p[0].scale != nullptr; w.has_shift = a.p[0].shift != nullptr;
+        w.has_res = a.p[0].res != nullptr; w.has_up = a.p[0].up != nullptr;
+        w.variant = p.pw - 1;
+        return launch_conv1x1(w, s);
+    }
     if (p.lat) {
         if (!lateral_ok(a, groups)) return FPC_EINVAL;
         LatArgs l;
@@ -536,6 +632,11 @@ int run_conv(fpc_net* n, ConvArgs& a, int groups, int ci, hipStream_t s) {
             for (int parts = 1; parts <= tiles; parts *= 2)
                 if (tiles % parts == 0) { ConvPlan lq; lq.lat = parts; cands.push_back(lq); }
         }
+        if (n->split_precision && n->expansion == 4 && pw_ok(a, groups)) {      // the 1x1 GEMM (bf16 x 3 planes), Bottleneck plans only
+            ConvPlan pq;
+            pq.pw = 1; cands.push_back(pq);
+            pq.pw = 2; cands.push_back(pq);
+        }
         if (a.wino_w[0] && !a.p[0].up) {
             ConvPlan wq;
             wq.wino = 1; cands.push_back(wq);
@@ -571,6 +672,7 @@ int run_conv(fpc_net* n, ConvArgs& a, int groups, int ci, hipStream_t s) {
             if (n->tune_mode >= 1) {
                 double nblk = q.stem ? 512.0      // (a persistent 512-thread, 86 KB workgroup per CU: the whole chip, whatever its grid)
                               : q.lat ? (double)cdiv(a.Ho * a.Wo, 128) * a.B * q.lat
+                              : q.pw ? (double)cdiv(a.B * a.Ho * a.Wo, pw_tile_pixels(q.pw - 1)) * (a.Cout / 64) * groups * q.pw      // (8-wave workgroups count twice)
                               : q.wino ? (double)cdiv(cdiv(a.Wo, 2), 8) * cdiv(cdiv(a.Ho, 2), (q.wino == 2 || q.wino == 4 || q.wino == 5 || q.wino == 7 || q.wino == 8 || q.wino == 9) ? 8 : 4) * a.B * (a.Cout / (q.wino == 6 ? 128 : 64)) * groups
                                      : (double)q.mtiles * q.ntiles * q.nsplit * a.B * groups;
                 double slots = 256.0 * ((q.wino == 2 || q.wino == 4 || q.wino == 5 || q.wino == 6 || q.wino == 7 || q.wino == 8 || q.wino == 9) ? 1.0 : 2.0);
@@ -626,6 +728,39 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
             const Act& T = n->a_blk_t[L][bi];
             const Act& Y = n->a_blk_y[L][bi];
             long long sb, sh, sw, sc;
+            if (n->expansion == 4) {
+                // Bottleneck: conv1 (1x1, BN + ReLU) -> conv2 (3x3 with the stride, BN + ReLU), the downsample (1x1, stride, BN),
+                // conv3 (1x1, BN + residual + ReLU)
+                const Act& T2 = n->a_blk_t2[L][bi];
+                nhwc(cur, sb, sh, sw, sc);
+                const PackedConv& c1 = n->convs[blk.conv1];
+                fill_conv_args(n, a, c1, n->cplan[blk.conv1], cur.H, cur.W, T.H, T.W, sb, sh, sw, sc, true, 0);
+                a.p[0] = ConvPtrs{ws + cur.off, ws + c1.w_off, ws + T.off, ws + c1.scale_off, ws + c1.shift_off, nullptr, nullptr, nullptr};
+                FPC_TRY(run_conv(n, a, 1, blk.conv1, s));
+                long long tb, th, tw, tc;
+                nhwc(T, tb, th, tw, tc);
+                const PackedConv& c2 = n->convs[blk.conv2];
+                fill_conv_args(n, a, c2, n->cplan[blk.conv2], T.H, T.W, T2.H, T2.W, tb, th, tw, tc, true, 0);
+                a.p[0] = ConvPtrs{ws + T.off, ws + c2.w_off, ws + T2.off, ws + c2.scale_off, ws + c2.shift_off, nullptr, nullptr, nullptr};
+                if (c2.wino_ok) a.wino_w[0] = ws + c2.wino_off;
+                FPC_TRY(run_conv(n, a, 1, blk.conv2, s));
+                const float* res = ws + cur.off;
+                if (blk.ds >= 0) {
+                    const PackedConv& cd = n->convs[blk.ds];
+                    const Act& D = n->a_blk_d[L][bi];
+                    fill_conv_args(n, a, cd, n->cplan[blk.ds], cur.H, cur.W, D.H, D.W, sb, sh, sw, sc, false, 0);
+                    a.p[0] = ConvPtrs{ws + cur.off, ws + cd.w_off, ws + D.off, ws + cd.scale_off, ws + cd.shift_off, nullptr, nullptr, nullptr};
+                    FPC_TRY(run_conv(n, a, 1, blk.ds, s));
+                    res = ws + D.off;
+                }
+                nhwc(T2, tb, th, tw, tc);
+                const PackedConv& c3 = n->convs[blk.conv3];
+                fill_conv_args(n, a, c3, n->cplan[blk.conv3], T2.H, T2.W, Y.H, Y.W, tb, th, tw, tc, true, 0);
+                a.p[0] = ConvPtrs{ws + T2.off, ws + c3.w_off, ws + Y.off, ws + c3.scale_off, ws + c3.shift_off, res, nullptr, nullptr};
+                FPC_TRY(run_conv(n, a, 1, blk.conv3, s));
+                cur = Y;
+                continue;
+            }
             nhwc(cur, sb, sh, sw, sc);
             const PackedConv& c1 = n->convs[blk.conv1];
             fill_conv_args(n, a, c1, n->cplan[blk.conv1], cur.H, cur.W, T.H, T.W, sb, sh, sw, sc, true, 0);
@@ -860,6 +995,7 @@ extern "C" int fpc_net_conv_plan(const fpc_net_t* n, int i, int* out5) {
     out5[0] = n->cplan[i].bm; out5[1] = n->cplan[i].bn; out5[2] = n->cplan[i].wino ? -n->cplan[i].wino : n->cplan[i].nsplit;
     if (n->cplan[i].lat) { out5[0] = 128; out5[1] = 32; out5[2] = 2000 + n->cplan[i].lat; }      // k_lateral1x1 (fpc_conv2d's hook value)
     if (n->cplan[i].stem) { out5[0] = 64; out5[1] = 64; out5[2] = 3000; }                        // k_stem7x7
+    if (n->cplan[i].pw) { out5[0] = pw_tile_pixels(n->cplan[i].pw - 1); out5[1] = 64; out5[2] = 4000 + n->cplan[i].pw - 1; }      // k_conv1x1
     out5[3] = n->convs[i].Cout; out5[4] = n->convs[i].K;
     return FPC_OK;
 }
@@ -876,6 +1012,30 @@ extern "C" int fpc_net_force_winograd(fpc_net_t* n, int form) {
         ConvPlan q = n->cplan[i];
         q.wino = form; q.lat = 0; q.stem = 0;
         n->cplan[i] = q;
+        ++changed;
+    }
+    if (n->graph_exec) { (void)hipGraphExecDestroy(n->graph_exec); n->graph_exec = nullptr; }
+    return changed;
+}
+
+// Every 1x1 site k_conv1x1 takes (Cin and Cout multiples of 64, no padding) -> k_conv1x1 (on = 1: the variant the site was
+// tuned to, else 64-pixel tiles) or back to the heuristic k_conv_igemm tiling (on = 0; sites already there are not counted).
+// Returns the number of sites changed, or a negative code.  Drops the recorded graph.
+extern "C" int fpc_net_force_pointwise(fpc_net_t* n, int on) {
+    if (!n || on < 0 || on > 1) return FPC_EINVAL;
+    int changed = 0;
+    for (size_t i = 0; i < n->convs.size(); ++i) {
+        const PackedConv& c = n->convs[i];
+        if (!n->c_groups[i] || c.Kh != 1 || c.pad != 0 || c.Cinp != c.Cin || c.Cin % 64 || c.Kpad != c.Cin || c.Cout % 64) continue;
+        if (on) {
+            if (n->cplan[i].pw) continue;
+            ConvPlan q;
+            q.pw = 1;
+            n->cplan[i] = q;
+        } else {
+            if (!n->cplan[i].pw) continue;
+            n->cplan[i] = plan_conv(n->c_howo[i], n->B, c.Cout, c.Kpad / kConvBK, n->c_groups[i]);
+        }
         ++changed;
     }
     if (n->graph_exec) { (void)hipGraphExecDestroy(n->graph_exec); n->graph_exec = nullptr; }
@@ -958,7 +1118,7 @@ extern "C" int fpc_conv2d_plan(int B, int Ho, int Wo, int Cin, int Cout, int Kh,
                                int* out4) {
     if (!out4) return FPC_EINVAL;
     int Kpad = cdiv(Cin * Kh * Kw, kConvBK) * kConvBK;
-    if (nsplit >= 2000) nsplit = 1;          // k_lateral1x1 / k_stem7x7: no split-K, no GroupNorm rows
+    if (nsplit >= 2000) nsplit = 1;          // k_lateral1x1 / k_stem7x7 / k_conv1x1: no split-K, no GroupNorm rows
     if (nsplit >= 1000) nsplit -= 1000;      // fpc_conv2d's split-precision / two-launch hooks do not change the tiling
     if (nsplit >= 100) nsplit -= 100;
     ConvPlan p = plan_conv(Ho * Wo, B, Cout, Kpad / kConvBK, 1, bm, bn, nsplit);
@@ -969,9 +1129,10 @@ extern "C" int fpc_conv2d_plan(int B, int Ho, int Wo, int Cin, int Cout, int Kh,
 
 namespace {
 // the hooks folded into fpc_conv2d's `nsplit` argument
-struct Conv2dRequest { int nsplit; bool bf3, two_launch, wino; int lat; bool stem; };
+struct Conv2dRequest { int nsplit; bool bf3, two_launch, wino; int lat; bool stem; int pw; };
 Conv2dRequest conv2d_request(int nsplit) {
-    Conv2dRequest r{nsplit, false, false, false, 0, false};
+    Conv2dRequest r{nsplit, false, false, false, 0, false, 0};
+    if (r.nsplit >= 4000) { r.pw = r.nsplit - 4000 + 1; r.bf3 = true; r.nsplit = 1; return r; }   // 4000 + variant = k_conv1x1 (pointwise.hip)
     if (r.nsplit == 3000) { r.stem = true; r.bf3 = true; r.nsplit = 1; return r; }                   // 3000 = k_stem7x7 (stem.hip): NHWC4 input
     if (r.nsplit >= 2000) { r.lat = r.nsplit - 2000; r.bf3 = true; r.nsplit = 1; return r; }      // 2000 + parts = k_lateral1x1 (lateral.hip)
     if (r.nsplit >= 1000) { r.bf3 = true; r.nsplit -= 1000; }          // 1000 + split = split-precision matrix products
@@ -1003,6 +1164,7 @@ ConvPlan conv2d_plan_for(int B, int Ho, int Wo, int Cin, int Cout, int Kh, int K
     if (r.two_launch) p.fused = 0;
     p.lat = r.lat;
     p.stem = r.stem ? 256 : 0;
+    p.pw = r.pw;
     return p;
 }
 }  // namespace
@@ -1098,6 +1260,6 @@ extern "C" int fpc_conv2d(const float* in, int64_t sb, int64_t sh, int64_t sw, i
     }
     a.bf3 = (p.bf3 && mode == 0) ? 1 : 0;
     if (p.bf3 && mode != 0) return FPC_EINVAL;
-    if (p.lat) return launch_conv_plan(a, p, 1, s);
+    if (p.lat || p.pw) return launch_conv_plan(a, p, 1, s);
     return run_conv(nullptr, a, 1, 0, s);
 }

@@ -55,6 +55,24 @@ struct LatArgs {
 };
 int launch_lateral1x1(const LatArgs& a, hipStream_t s);
 
+// 1x1 convolution as a GEMM over all output pixels of the batch (pointwise.hip, k_conv1x1): Cin a multiple of 64, Cout of 64,
+// stride 1 or 2, bf16 x 3 products on k_pack_weight_bf3's planes; the groups share the input (FPN laterals)
+struct PwArgs {
+    const float* in;                        // input row of output pixel (b, ho, wo): in + b in_sb + s ho in_sh + s wo in_sw (channels contiguous)
+    const unsigned short* wpl[kMaxGroup];   // k_pack_weight_bf3's planes: [3][Npad][Kpad] bf16
+    float* out[kMaxGroup];                  // [B * Ho * Wo][Cout]
+    const float* scale[kMaxGroup];          // folded BatchNorm multiplier or null
+    const float* shift[kMaxGroup];          // folded BatchNorm addend / conv bias or null
+    const float* res[kMaxGroup];            // residual [B * Ho * Wo][Cout] or null
+    const float* up[kMaxGroup];             // [B][Ho/2][Wo/2][Cout], nearest-x2 upsampled and added, or null
+    long long in_sb, in_sh, in_sw;
+    int B, Ho, Wo, Cin, Cout, Npad, Kpad, stride, groups, relu;
+    int has_scale, has_shift, has_res, has_up;   // the same for every group
+    int variant;                            // 0: 64-pixel tiles (4 waves), 1: 128-pixel tiles (8 waves)
+};
+int launch_conv1x1(const PwArgs& a, hipStream_t s);
+inline int pw_tile_pixels(int variant) { return variant == 0 ? 64 : 128; }
+
 // the 7x7 / stride-2 / pad-3 stem on the NHWC4 image as a weight-resident product (stem.hip)
 struct StemArgs {
     const float* in;             // [B][Hi][Wi][4] f32 (4th channel 0), contiguous

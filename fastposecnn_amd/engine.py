@@ -24,8 +24,13 @@ class NetEngine:
         self.B, self.H, self.W, self.device = B, H, W, device
         self.classes = model.classes
         h = ctypes.c_void_p()
-        enc = model.encoder.name.encode()
-        nat.check(L.fpc_net_create(enc, self.classes, B, H, W, ctypes.byref(h)), "fpc_net_create")
+        from fastposecnn_amd.lib import backbone
+        block, layers = backbone.encoder_layout(model.encoder.name)
+        if block == 1:      # the named nets, as always
+            nat.check(L.fpc_net_create(model.encoder.name.encode(), self.classes, B, H, W, ctypes.byref(h)), "fpc_net_create")
+        else:               # Bottleneck encoders by their descriptor
+            nat.check(L.fpc_net_create_encoder(block, (ctypes.c_int * 4)(*layers), self.classes, B, H, W, ctypes.byref(h)),
+                      "fpc_net_create_encoder")
         self._h = h
         self._names = [L.fpc_net_param_name(h, i).decode() for i in range(L.fpc_net_param_count(h))]
         nbytes = L.fpc_net_workspace_bytes(h)
@@ -99,6 +104,13 @@ class NetEngine:
         rc = self._lib.fpc_net_force_winograd(self._h, int(form))
         if rc < 0:
             nat.check(rc, "fpc_net_force_winograd")
+        return rc
+
+    def force_pointwise(self, on):
+        """Every eligible 1x1 site on k_conv1x1 (on = 1) or back on k_conv_igemm (on = 0); returns the number of sites changed."""
+        rc = self._lib.fpc_net_force_pointwise(self._h, int(on))
+        if rc < 0:
+            nat.check(rc, "fpc_net_force_pointwise")
         return rc
 
     def flops(self):

@@ -78,20 +78,57 @@ class BasicBlock(nn.Module):
         return self.relu(out + identity)
 
 
-_RESNET_LAYERS = {"resnet18": [2, 2, 2, 2], "resnet34": [3, 4, 6, 3]}
+class Bottleneck(nn.Module):
+    """torchvision's Bottleneck (ResNet V1.5, which smp's ResNetEncoder subclasses): 1x1 -> 3x3 (the stride) -> 1x1 x 4."""
+    expansion = 4
+
+    def __init__(self, inplanes, planes, stride=1, downsample=None):
+        super().__init__()
+        self.conv1 = Conv2d(inplanes, planes, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(planes)
+        self.conv2 = Conv2d(planes, planes, 3, stride, 1, bias=False)
+        self.bn2 = nn.BatchNorm2d(planes)
+        self.conv3 = Conv2d(planes, planes * self.expansion, 1, bias=False)
+        self.bn3 = nn.BatchNorm2d(planes * self.expansion)
+        self.relu = nn.ReLU(inplace=True)
+        self.downsample = downsample
+        self.stride = stride
+
+    def forward(self, x):
+        identity = x
+        out = self.relu(self.bn1(self.conv1(x)))
+        out = self.relu(self.bn2(self.conv2(out)))
+        out = self.bn3(self.conv3(out))
+        if self.downsample is not None:
+            identity = self.downsample(x)
+        return self.relu(out + identity)
+
+
+# name -> (block, blocks per stage), as torchvision / smp
+_RESNET_LAYERS = {"resnet18": (BasicBlock, [2, 2, 2, 2]), "resnet34": (BasicBlock, [3, 4, 6, 3]),
+                  "resnet50": (Bottleneck, [3, 4, 6, 3]), "resnet101": (Bottleneck, [3, 4, 23, 3]),
+                  "resnet152": (Bottleneck, [3, 8, 36, 3])}
+
+
+def encoder_layout(name):
+    """(block expansion, blocks per stage) of encoder `name`: the descriptor fpc_net_create_encoder takes."""
+    block, layers = _RESNET_LAYERS[name]
+    return block.expansion, list(layers)
 
 
 class ResNetEncoder(nn.Module):
-    """torchvision-style ResNet (BasicBlock) without avgpool/fc, returning 6 feature levels."""
+    """torchvision-style ResNet (BasicBlock or Bottleneck) without avgpool/fc, returning 6 feature levels."""
 
     def __init__(self, name="resnet18", in_channels=3, depth=5):
         super().__init__()
         if name not in _RESNET_LAYERS:
             raise KeyError(f"encoder {name!r} not available (have {sorted(_RESNET_LAYERS)})")
-        layers = _RESNET_LAYERS[name]
+        block, layers = _RESNET_LAYERS[name]
         self.name = name
         self._depth = depth
-        self.out_channels = (in_channels, 64, 64, 128, 256, 512)
+        self._block = block
+        e = block.expansion
+        self.out_channels = (in_channels, 64, 64 * e, 128 * e, 256 * e, 512 * e)
         self.inplanes = 64
         self.conv1 = Conv2d(in_channels, 64, 7, 2, 3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
@@ -109,14 +146,15 @@ class ResNetEncoder(nn.Module):
                 nn.init.constant_(m.bias, 0)
 
     def _make_layer(self, planes, blocks, stride=1):
+        block = self._block
         downsample = None
-        if stride != 1 or self.inplanes != planes:
-            downsample = nn.Sequential(Conv2d(self.inplanes, planes, 1, stride, bias=False),
-                                       nn.BatchNorm2d(planes))
-        layers = [BasicBlock(self.inplanes, planes, stride, downsample)]
-        self.inplanes = planes
+        if stride != 1 or self.inplanes != planes * block.expansion:
+            downsample = nn.Sequential(Conv2d(self.inplanes, planes * block.expansion, 1, stride, bias=False),
+                                       nn.BatchNorm2d(planes * block.expansion))
+        layers = [block(self.inplanes, planes, stride, downsample)]
+        self.inplanes = planes * block.expansion
         for _ in range(1, blocks):
-            layers.append(BasicBlock(self.inplanes, planes))
+            layers.append(block(self.inplanes, planes))
         return nn.Sequential(*layers)
 
     def forward(self, x):

@@ -43,6 +43,8 @@
 extern "C" {
 #endif
 
+/* 11 also covers the Bottleneck encoders (fpc_net_create_encoder, fpc_net_force_pointwise, fpc_conv2d's 4000 + variant):
+ * additions only, every earlier entry point keeps its behaviour. */
 #define FPC_ABI_VERSION 11
 
 #define FPC_OK 0
@@ -348,6 +350,11 @@ int fpc_lookahead_radam_step(float* p, const float* g, float* m, float* v, float
  *                    cat_mask i64 [B,H,W], cq [B,4,H,W], cs [B,3,H,W], cxy [B,2,H,W], cz [B,H,W]. */
 typedef struct fpc_net fpc_net_t;
 int fpc_net_create(const char* encoder, int classes, int B, int H, int W, fpc_net_t** out);
+/* The same plan for an encoder given by its descriptor: block 1 = BasicBlock, 4 = Bottleneck (torchvision's ResNet V1.5: the
+ * stride on the 3x3; ResNet-50 / 101 / 152 = {3,4,6,3} / {3,4,23,3} / {3,8,36,3}); layers4 = blocks per stage, 1..64 each.
+ * (1, {2,2,2,2}) and (1, {3,4,6,3}) give the parameter tables and workspaces of "resnet18" / "resnet34".  Same H / W / classes
+ * rules as fpc_net_create. */
+int fpc_net_create_encoder(int block, const int* layers4, int classes, int B, int H, int W, fpc_net_t** out);
 void fpc_net_destroy(fpc_net_t* net);
 int fpc_net_param_count(const fpc_net_t* net);
 const char* fpc_net_param_name(const fpc_net_t* net, int i);
@@ -403,6 +410,10 @@ int fpc_net_copy_plans(fpc_net_t* dst, const fpc_net_t* src);
  * their plan) — tests hold the whole network on ONE form (8: every eligible product on fp16 x 2 pieces) to the float64 bars.
  * Returns the number of sites changed or a negative code. */
 int fpc_net_force_winograd(fpc_net_t* net, int form);
+/* on = 1: every 1x1 site with Cin and Cout multiples of 64 on the 1x1 GEMM kernel (csrc/pointwise.hip, reported by
+ * fpc_net_conv_plan as 4000 + variant); on = 0: those sites back on the implicit-GEMM kernel's heuristic tiling.  Returns the
+ * number of sites changed or a negative code.  The autotuner offers the kernel itself in Bottleneck plans at split level >= 1. */
+int fpc_net_force_pointwise(fpc_net_t* net, int on);
 /* FLOP of one forward over the batch under the current plans: out3 = {2 x MACs of the direct convolutions (what the
  * reference's cuDNN path executes), multiply-add FLOP the plans execute (Winograd sites: / 2.25), Winograd share}. */
 int fpc_net_flops(const fpc_net_t* net, double* out3);
@@ -416,7 +427,9 @@ int fpc_net_tensor(const fpc_net_t* net, const char* name, const float** ptr, in
  * GroupNorm partials gn_part [B][P32][Cout][2]; bm/bn/nsplit = 0 -> chosen by the planner.
  * `nsplit` also selects the engine's other kernels for tests: -1..-5 Winograd forms (-5 split precision), 100 + k split-K
  * summed by a second launch, 1000 + k split-precision (bf16 x 3) products, 2000 + parts the pixel-resident FPN lateral
- * product (1x1, Cin 64 / 128, bias + `up` epilogue), 3000 the weight-resident 7x7 / s2 stem (Cin = 4: NHWC4 image). */
+ * product (1x1, Cin 64 / 128, bias + `up` epilogue), 3000 the weight-resident 7x7 / s2 stem (Cin = 4: NHWC4 image),
+ * 4000 + variant the 1x1 GEMM (pad 0, stride 1 / 2, Cin and Cout multiples of 64, channel stride 1, no GroupNorm partials;
+ * variant 0: 64-pixel tiles on 4 waves, 1: 128-pixel tiles on 8 waves; bf16 x 3 products). */
 size_t fpc_conv2d_workspace_bytes(int B, int Ho, int Wo, int Cin, int Cout, int Kh, int Kw);
 /* the exact need of one request (same bm / bn / nsplit as the fpc_conv2d call): <= the bound above, which reserves 32
  * split-K slices of the whole output; fpc_conv2d accepts either size */
