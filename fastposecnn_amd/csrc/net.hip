@@ -45,6 +45,7 @@ struct ConvPlan {
     int lat = 0;             // > 0: k_lateral1x1 with this many workgroups per 128-pixel tile (lateral.hip) instead of k_conv_igemm
     int stem = 0;            // > 0: k_stem7x7 (stem.hip), a persistent grid of this many workgroups (one per CU: 256)
     int pw = 0;              // > 0: k_conv1x1 (pointwise.hip), variant pw - 1 (net_kernels.hpp: PwArgs::variant)
+    int fold = 0;            // s2.0 with wino 9 only: the FPN p2 level folded into the launch (wino_h3.hip, FOLD); no p2 lateral runs
 };
 
 // the 7x7 / stride-2 / pad-3 stem in its row-per-K-step layout (NHWC4 image, 8 taps x 4 channels per kernel row, K = 224) with a
@@ -189,8 +190,14 @@ struct fpc_net {
     size_t zeros_off = 0;         // 64 zero floats (DMA source for out-of-image positions)
     size_t tickets_off = 0;       // kConvTickets zero ints: arrival counters of the fused split-K convolutions
 
+    // the FPN p2 fold of s2.0 (BasicBlock encoders: c2 has 64 channels): per decoder Wc = W L (OIHW), the h3 images of Wc and of W on
+    // one scale (wino_h3.hip: launch_wino_pack_h3_pair) and the border-class bias table
+    bool fold_ok = false;
+    size_t fold_wc_off[4] = {}, fold_img1_off[4] = {}, fold_img2_off[4] = {}, fold_tab_off[4] = {};
+
     // per-conv launch plans (index = conv id of decoder 0 for grouped ones)
     std::vector<ConvPlan> cplan;
+    std::vector<float> tune_score;       // the autotuner's best score per site (ms, or its throughput objective)
     std::vector<int> c_howo, c_groups;   // output pixels per image and launch multiplicity of every planned conv site (0: not a site)
 
     size_t bump = 0;
@@ -325,6 +332,14 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
         dc.p_head_w = n->add_param(std::string(kHeadNames[d]) + ".0.weight", (int64_t)head_ch[d] * 128);
         dc.p_head_b = n->add_param(std::string(kHeadNames[d]) + ".0.bias", head_ch[d]);
     }
+    n->fold_ok = e == 1;
+    if (n->fold_ok)
+        for (int d = 0; d < 4; ++d) {
+            n->fold_wc_off[d] = n->alloc((size_t)128 * 64 * 9);
+            n->fold_img1_off[d] = n->alloc((size_t)16 * 128 * 64 + 2);
+            n->fold_img2_off[d] = n->alloc((size_t)16 * 128 * 256 + 2);
+            n->fold_tab_off[d] = n->alloc((size_t)16 * 128);
+        }
     n->zeros_off = n->alloc(64);
     n->tickets_off = n->alloc(kConvTickets);
     n->packed_floats = n->bump;
@@ -384,6 +399,7 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
 
     // ---- conv plans (+ split-K scratch for the worst candidate, GroupNorm partials for the largest P32)
     n->cplan.resize(n->convs.size());
+    n->tune_score.assign(n->convs.size(), 0.f);
     n->c_howo.assign(n->convs.size(), 0);
     n->c_groups.assign(n->convs.size(), 0);
     auto plan = [&](int ci, int HoWo, int groups) {
@@ -501,6 +517,15 @@ extern "C" int fpc_net_load_params(fpc_net_t* n, const float* const* params, int
             if (rc) return rc;
         }
     }
+    if (n->fold_ok)
+        for (int d = 0; d < 4; ++d) {
+            const PackedConv &sc = n->convs[n->dec[d].seg[6]], &lc = n->convs[n->dec[d].lat[3]];
+            int rc = launch_fold_compose(n->pptr[sc.p_w], n->pptr[lc.p_w], n->pptr[lc.p_bias], n->ws + n->fold_wc_off[d],
+                                         n->ws + n->fold_tab_off[d], sc.Cout, sc.Cin, lc.Cin, s);
+            if (!rc) rc = launch_wino_pack_h3_pair(n->ws + n->fold_wc_off[d], n->ws + n->fold_img1_off[d], lc.Cin, n->pptr[sc.p_w],
+                                                   n->ws + n->fold_img2_off[d], sc.Cin, sc.Cout, s);
+            if (rc) return rc;
+        }
     n->loaded = true;
     return FPC_OK;
 }
@@ -590,6 +615,15 @@ int launch_conv_plan(ConvArgs& a, const ConvPlan& p, int groups, hipStream_t s) 
         w.B = a.B; w.H = a.Ho; w.W = a.Wo; w.Cin = a.Cin; w.Cout = a.Cout; w.relu = a.relu;
         w.waves = (p.wino == 2 || p.wino == 4 || p.wino == 5 || p.wino == 7 || p.wino == 8 || p.wino == 9) ? 8 : 4;
         w.tbx = cdiv(cdiv(a.Wo, 2), 8); w.tby = cdiv(cdiv(a.Ho, 2), w.waves);
+        if (p.fold) {      // c2 on Wc's image + up2(p3) on W's (the p2 input of .p[g] is not read)
+            if (p.wino != 9 || !a.fold_in) return FPC_EINVAL;
+            for (int g = 0; g < groups; ++g) {
+                w.in2[g] = a.fold_up[g]; w.w2[g] = a.fold_w2[g];
+                w.btab[g] = a.fold_tab[g];
+                w.p[g].in = a.fold_in; w.p[g].w = a.fold_w[g];
+            }
+            w.fold = 1; w.Cin2 = a.Cin; w.Cin = a.fold_cin;
+        }
         if (p.wino == 6) return a.Cout % 128 == 0 ? launch_conv_wino_c128(w, groups, s) : FPC_EINVAL;      // 8 x 4 tiles x 128 channels (wino128.hip)
         if (p.wino == 7) return launch_conv_wino_w4(w, groups, s);
         if (p.wino == 9) return launch_conv_wino_h3(w, groups, s);      // three fp16 piece products over pairs of K-steps (wino_h3.hip)
@@ -682,6 +716,24 @@ int run_conv(fpc_net* n, ConvArgs& a, int groups, int ci, hipStream_t s) {
                 score = ms * (float)(n->tune_mode == 2 ? share : sqrt(share));      // 2: latency x share = the launch's CU-time
             }
             if (score < best_ms) { best_ms = score; best = q; }
+        }
+        n->tune_score[ci] = best_ms;
+        // s2.0 with the FPN p2 level folded in (level 3, wino_h3.hip): it replaces the p2 lateral AND this site, so it must beat the sum
+        // of both best scores (the lateral's was taken earlier in this pass).  Same timing rule as above; the whole chip: score = ms.
+        if (n->split_precision >= 3 && a.fold_in && a.fold_lat_ms > 0.f) {
+            ConvPlan fq;
+            fq.wino = 9; fq.fold = 1;
+            int rc = launch_conv_plan(a, fq, groups, s);
+            if (rc && rc != FPC_EINVAL) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return rc; }
+            float ms = 1e30f;
+            for (int rep = 0; rep < 3 && !rc; ++rep) {
+                float t = 0.f;
+                bool timed = hipEventRecord(e0, s) == hipSuccess && launch_conv_plan(a, fq, groups, s) == FPC_OK &&
+                             hipEventRecord(e1, s) == hipSuccess && hipEventSynchronize(e1) == hipSuccess &&
+                             hipEventElapsedTime(&t, e0, e1) == hipSuccess;
+                if (timed && t < ms) ms = t;
+            }
+            if (ms < best_ms + a.fold_lat_ms) best = fq;
         }
         (void)hipEventDestroy(e0);
         (void)hipEventDestroy(e1);
@@ -788,8 +840,10 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
     }
 
     // ---- four decoders, grouped
-    // laterals: p5 = conv(c5); p4 = up2_nearest(p5) + conv(c4); p3; p2
+    // laterals: p5 = conv(c5); p4 = up2_nearest(p5) + conv(c4); p3; p2 (not where s2.0 folds it in, outside an autotuning pass)
+    const bool fold = n->cplan[n->dec[0].seg[6]].fold && !n->tuning;
     for (int i = 0; i < 4; ++i) {
+        if (i == 3 && fold) continue;
         const Act& src = feat[3 - i];
         long long sb, sh, sw, sc;
         nhwc(src, sb, sh, sw, sc);
@@ -817,6 +871,17 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
             a.p[d] = ConvPtrs{ws + in.off, ws + c.w_off, ws + n->a_seg[d][si].off, nullptr, nullptr, nullptr, nullptr,
                               ws + n->gn_part_off[d][si]};
             if (c.wino_ok) a.wino_w[d] = ws + c.wino_off;
+        }
+        if (si == 6 && n->fold_ok) {      // s2.0: what its fold reads instead of p2
+            a.fold_in = ws + feat[0].off;
+            a.fold_cin = feat[0].C;
+            for (int d = 0; d < 4; ++d) {
+                a.fold_w[d] = ws + n->fold_img1_off[d];
+                a.fold_w2[d] = ws + n->fold_img2_off[d];
+                a.fold_up[d] = ws + n->a_p[d][2].off;
+                a.fold_tab[d] = ws + n->fold_tab_off[d];
+            }
+            a.fold_lat_ms = n->tune_score[n->dec[0].lat[3]];
         }
         return run_conv(n, a, 4, ci0, s);
     };
@@ -988,7 +1053,8 @@ extern "C" int fpc_net_autotune_next(fpc_net_t* n, int mode) {
     return FPC_OK;
 }
 
-// Chosen tiling of convolution site `i` (0 <= i < fpc_net_conv_count): out5 = bm, bn, nsplit, Cout, K.
+// Chosen tiling of convolution site `i` (0 <= i < fpc_net_conv_count): out5 = bm, bn, nsplit, Cout, K.  nsplit 5000: the p2 lateral
+// site, folded into s2.0's launch (which reports -9).
 extern "C" int fpc_net_conv_count(const fpc_net_t* n) { return n ? (int)n->convs.size() : 0; }
 extern "C" int fpc_net_conv_plan(const fpc_net_t* n, int i, int* out5) {
     if (!n || !out5 || i < 0 || i >= (int)n->convs.size()) return FPC_EINVAL;
@@ -996,6 +1062,7 @@ extern "C" int fpc_net_conv_plan(const fpc_net_t* n, int i, int* out5) {
     if (n->cplan[i].lat) { out5[0] = 128; out5[1] = 32; out5[2] = 2000 + n->cplan[i].lat; }      // k_lateral1x1 (fpc_conv2d's hook value)
     if (n->cplan[i].stem) { out5[0] = 64; out5[1] = 64; out5[2] = 3000; }                        // k_stem7x7
     if (n->cplan[i].pw) { out5[0] = pw_tile_pixels(n->cplan[i].pw - 1); out5[1] = 64; out5[2] = 4000 + n->cplan[i].pw - 1; }      // k_conv1x1
+    if (n->fold_ok && i == n->dec[0].lat[3] && n->cplan[n->dec[0].seg[6]].fold) out5[2] = 5000;      // the p2 lateral, folded into s2.0
     out5[3] = n->convs[i].Cout; out5[4] = n->convs[i].K;
     return FPC_OK;
 }
@@ -1011,11 +1078,25 @@ extern "C" int fpc_net_force_winograd(fpc_net_t* n, int form) {
         if (!c.wino_ok || !n->c_groups[i] || (form == 6 && c.Cout % 128 != 0) || (form == 9 && c.Cin % 16 != 0)) continue;
         ConvPlan q = n->cplan[i];
         q.wino = form; q.lat = 0; q.stem = 0;
+        if (form != 9) q.fold = 0;      // (form 9 keeps s2.0's fold: it runs on that form)
         n->cplan[i] = q;
         ++changed;
     }
     if (n->graph_exec) { (void)hipGraphExecDestroy(n->graph_exec); n->graph_exec = nullptr; }
     return changed;
+}
+
+// s2.0 with the FPN p2 level folded in (on = 1; ResNet-18/34 plans) or back on its unfolded form 9 plan (on = 0).  Returns 1 when the
+// plan changed, 0 when it was already so, or a negative code.  Drops the recorded graph.
+extern "C" int fpc_net_force_fold(fpc_net_t* n, int on) {
+    if (!n || on < 0 || on > 1 || (on && !n->fold_ok)) return FPC_EINVAL;
+    ConvPlan& p = n->cplan[n->dec[0].seg[6]];
+    if (p.fold == on) return 0;
+    ConvPlan q;
+    q.wino = 9; q.fold = on;
+    p = q;
+    if (n->graph_exec) { (void)hipGraphExecDestroy(n->graph_exec); n->graph_exec = nullptr; }
+    return 1;
 }
 
 // Every 1x1 site k_conv1x1 takes (Cin and Cout multiples of 64, no padding) -> k_conv1x1 (on = 1: the variant the site was
@@ -1096,7 +1177,10 @@ extern "C" int fpc_net_tensor(const fpc_net_t* n, const char* name, const float*
     else if (name[0] == 'd' && name[1] >= '0' && name[1] <= '3' && name[2] == '.') {
         int d = name[1] - '0';
         const char* r = name + 3;
-        if (r[0] == 'p' && r[1] >= '2' && r[1] <= '5' && !r[2]) { t = n->a_p[d]['5' - r[1]]; ok = true; }
+        if (r[0] == 'p' && r[1] >= '2' && r[1] <= '5' && !r[2]) {
+            if (r[1] == '2' && n->cplan[n->dec[0].seg[6]].fold) return FPC_EINVAL;      // folded into s2.0: never written
+            t = n->a_p[d]['5' - r[1]]; ok = true;
+        }
         else if (!strncmp(r, "seg", 3) && r[3] >= '0' && r[3] <= '6' && !r[4]) { t = n->a_seg[d][r[3] - '0']; ok = true; }
         else if (!strcmp(r, "low")) { t = n->a_low[d]; ok = true; }
     }

@@ -39,6 +39,15 @@ struct ConvArgs {
                           // stem: Kw = 1, Cin = 32 virtual channels); horizontal padding is then per lane
     const float* wino_w[kMaxGroup];   // host side only: Winograd-packed weights per group (or null)
     const float* zeros;               // host side only: 64 zero floats for the all-DMA Winograd form (or null)
+    // host side only, the FPN p2 fold of s2.0 (ConvPlan::fold; null where the site cannot fold): c2, the h3 images of Wc and W, p3,
+    // bias table
+    const float* fold_in;
+    const float* fold_w[kMaxGroup];
+    const float* fold_w2[kMaxGroup];
+    const float* fold_up[kMaxGroup];
+    const float* fold_tab[kMaxGroup];
+    int fold_cin;
+    float fold_lat_ms;                // tuning: the p2 lateral's best score, the fold's time must beat lateral + s2.0
     void* dbg;                        // host side only: diagnostic stamp buffer for k_conv_wino (or null)
 };
 
@@ -152,6 +161,12 @@ struct WinoArgs {
     int groups;
     int waves;               // 4: 8x4 tile patch per workgroup; 8: 8x8 patch (512 threads)
     int B, H, W, Cin, Cout, relu, tbx, tby;   // tbx = ceil(ceil(W/2)/8), tby = ceil(ceil(H/2)/waves) tile patches
+    // k_conv_wino_h3 only, fold = 1 (FPN p2 folded into s2.0, wino_h3.hip): out = conv3x3(Wc, in) + conv3x3(W, up2_nearest(in2))
+    // + the border-class bias table; .p[g].in = c2 (Cin channels), .p[g].w = Wc's h3 image, in2 = p3 [B][H/2][W/2][Cin2]
+    const float* in2[kMaxGroup];
+    const float* w2[kMaxGroup];      // W's h3 image (Cin2 channels) with .p[g].w's scale (launch_wino_pack_h3_pair)
+    const float* btab[kMaxGroup];    // [4 row classes][4 column classes][Cout]: class bit 0 = first row / column, bit 1 = last
+    int fold, Cin2;
 };
 int launch_conv_wino(const WinoArgs& a, int groups, hipStream_t s);
 const float* zero_page();      // 64 zero floats in the code object (per device context), or null
@@ -173,6 +188,11 @@ int launch_absmax_bits(const float* w, long long n, unsigned* out_bits, hipStrea
 // 16 * Cout * Cin + 2 floats
 int launch_conv_wino_h3(const WinoArgs& a, int groups, hipStream_t s);
 int launch_wino_pack_h3(const float* w_oihw, float* packed, int Cout, int Cin, hipStream_t s);
+// the fold's weights: wc = W . L (OIHW [Cout][Cmid -> Cin][3][3], f64 sums) and the bias table conv3x3(W, bias . 1_inside) per border
+// class (WinoArgs::btab); W [Cout][Cmid][3][3], L the 1x1 lateral [Cmid][Cin], bias [Cmid]
+int launch_wino_pack_h3_pair(const float* w1, float* packed1, int Cin1, const float* w2, float* packed2, int Cin2, int Cout, hipStream_t s);
+int launch_fold_compose(const float* W, const float* L, const float* bias, float* wc, float* btab, int Cout, int Cmid, int Cin,
+                        hipStream_t s);
 int launch_conv(const ConvArgs& a, int groups, hipStream_t s);
 int launch_conv_splitk_epilogue(const ConvArgs& a, int groups, hipStream_t s);
 int launch_maxpool3x3s2(const float* in, float* out, int B, int Hi, int Wi, int C, int Ho, int Wo, hipStream_t s);

@@ -29,6 +29,7 @@
 // Reference: the 3x3 / stride-1 convolutions of F/lib/pose_regressor.py:709-743 (smp encoder + FPN decoder, not vendored).
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 #include "net_kernels.hpp"
 
 namespace fpc {
@@ -60,21 +61,36 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base) {
 __device__ __forceinline__ f32x4 fma_s4(float s, f32x4 b, f32x4 a) {
     return f32x4{__builtin_fmaf(s, b[0], a[0]), __builtin_fmaf(s, b[1], a[1]), __builtin_fmaf(s, b[2], a[2]), __builtin_fmaf(s, b[3], a[3])};
 }
+// a wave-uniform pointer in scalar registers (the staging asm takes its base as an "s" operand)
+__device__ __forceinline__ const float* sgpr_ptr(const float* p) {
+    const unsigned long long v = reinterpret_cast<unsigned long long>(p);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return reinterpret_cast<const float*>(((unsigned long long)hi << 32) | lo);
+}
 __device__ __forceinline__ f32x4 sub_s4(f32x4 a, f32x4 b) { return f32x4{a[0] - b[0], a[1] - b[1], a[2] - b[2], a[3] - b[3]}; }
 __device__ __forceinline__ f32x4 add_s4(f32x4 a, f32x4 b) { return f32x4{a[0] + b[0], a[1] + b[1], a[2] + b[2], a[3] + b[3]}; }
 
 }  // namespace
 
 // VAR (diagnostic, FPC_H3_VAR at launch): 1 = a piece's residual by conversion + subtraction instead of v_fma_mix_f32 (the same bits)
-template <int VAR>
+//
+// FOLD: the FPN p2 level folded into s2.0 (a.fold; p2 = L c2 + b + up2_nearest(p3) is never written).  By linearity
+//   conv3x3(W, p2) = conv3x3(W L, c2) + conv3x3(W, up2(p3)) + conv3x3(W, b 1_inside)
+// and the K loop runs twice into the same accumulators: phase 1 over c2 (64 channels) on the composed weights' image, phase 2 over
+// p3 on an image of W with the same power-of-two scale, the bias term comes from a table by border class in the epilogue.  Phase 2 stages the 18 x 18 region of the
+// UPSAMPLED image straight from p3 (each lane's DMA address is its low-resolution pixel): a tile's input rows 2i-1 .. 2i+2 are then
+// the low-resolution rows [a, b, b, c], and B^T [a, b, b, c] = [a-b, 2b, 0, b-c] with an exact 0 in floating point.  Transform row 2
+// and column 2 are zero: every wave skips its xi column 2 in phase 2 (operands, weight loads, matrix instructions), 36 of 48 matrix
+// instructions per pair.  Wave 2's row is zero too, but it still runs the loop (its products add exact zeros): a branch that gave it
+// only the staging made the compiler spill ~1 KB per wave at the phase boundary.
+template <int VAR, bool FOLD>
 __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[kLdsFloats];
     const long long t_entry = a.dbg ? clock64() : 0;
     const int t = threadIdx.x, lane = t & 63;
     const int wi = __builtin_amdgcn_readfirstlane(t >> 6);      // transform row of this wave (wave-uniform)
     const int li = lane & 31, lh = lane >> 5;
-    const int H = a.H, W = a.W, Cin = a.Cin, Cout = a.Cout, HW = H * W;
-    const int nkb = Cin >> 3;
+    const int H = a.H, W = a.W, Cout = a.Cout, HW = H * W;
     // weight slice (group, 64-channel block) fastest: fixed per XCD under round-robin dispatch (k_conv_wino)
     int bid = blockIdx.x;
     const int nnb = Cout / kBN;
@@ -90,18 +106,30 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
     const int ty0 = by * kTY, tx0 = bx * kTX;
     const int y_in0 = 2 * ty0 - 1, x_in0 = 2 * tx0 - 1;
 
-    const int npair = nkb >> 1;      // (the launcher refuses an odd number of K-steps)
-
     f32x16 acc[4][2][2];      // [xi column j][tile half mt][32-channel tile nt]; zeroed while the first operands are on their way
+    float inv_s = 1.f;        // 1 / (the power of two the weights of the LAST phase were scaled by)
+    long long t_issued = 0, t_landed = 0, t_synced = 0, c_begin = 0, r_begin = 0;
+    const bool stamp = a.dbg != nullptr;      // (the loop below never names `a`: a reference to the kernel argument puts it in scratch)
+
+    // The K loop over one input image `src` (Cs channels; up = 1: read as its nearest-x2 upsample) on the weight image `wimg`.
+    // PH 0: the whole loop (acc zeroed first); 1: fold phase 2 (xi column 2 skipped).  Every phase ends after a barrier with no
+    // staging in flight and the input ring free.
+    auto kloop = [&](auto ph, const float* src, const float* wimg, const int Cs, const int up) __attribute__((always_inline)) {
+    constexpr int PH = decltype(ph)::value;
+    constexpr bool SKIPC = PH == 1;
+    const int nkb = Cs >> 3;
+    const int npair = nkb >> 1;      // (the launcher refuses an odd number of K-steps)
     // ---- weights: buffer loads of this wave's fragments, per pair of K-steps one 16-byte B1 = {g1 even, g1 odd} and one B2 = {g2 even,
     // g2 odd} per (xi, 32-channel tile, lane)
-    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(reinterpret_cast<const char*>(P.w) + (size_t)nb * npair * kPairBytes);
-    const float inv_s = P.w[(size_t)nnb * npair * (kPairBytes / 4)];      // 1 / (the power of two the weights were scaled by)
+    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(reinterpret_cast<const char*>(wimg) + (size_t)nb * npair * kPairBytes);
+    inv_s = wimg[(size_t)nnb * npair * (kPairBytes / 4)];      // 1 / (the power of two the weights were scaled by)
     const int vo_u = lane * 16;
     int so_u = wi * 4 * 4096;      // this wave's four xi; + kPairBytes per pair
     u32x4 U1[4][2], U2[4][2];
-#define FPC_H3_LOAD_U1_AT(SO, J, NT) U1[J][NT] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_w, vo_u, (SO) + (J) * 4096 + (NT) * 2048, 0))
-#define FPC_H3_LOAD_U2_AT(SO, J, NT) U2[J][NT] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_w, vo_u, (SO) + (J) * 4096 + (NT) * 2048 + 1024, 0))
+    // (a fold phase 2 loads no fragment of xi column 2: 12 weight loads per pair instead of 16)
+#define FPC_H3_XI_LIVE(J) (!(SKIPC && (J) == 2))
+#define FPC_H3_LOAD_U1_AT(SO, J, NT) do { if (FPC_H3_XI_LIVE(J)) U1[J][NT] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_w, vo_u, (SO) + (J) * 4096 + (NT) * 2048, 0)); } while (0)
+#define FPC_H3_LOAD_U2_AT(SO, J, NT) do { if (FPC_H3_XI_LIVE(J)) U2[J][NT] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_w, vo_u, (SO) + (J) * 4096 + (NT) * 2048 + 1024, 0)); } while (0)
 #define FPC_H3_LOAD_U1(J, NT) FPC_H3_LOAD_U1_AT(so_u, J, NT)
 #define FPC_H3_LOAD_U2(J, NT) FPC_H3_LOAD_U2_AT(so_u, J, NT)
 #pragma unroll
@@ -113,7 +141,8 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
     // ---- input staging: LDS-DMA pieces (wave + 4 i), i < 5 (18 pieces).  The 16-byte unit a lane's data lands in decides the
     // global address it fetches (k_conv_wino, PERM): unit = (cell * 8 + block) * 16 + 4 * (qh & 3) + (ah & 3), cell = (ah >> 2) * 3 +
     // (qh >> 2), block = (ry & 1) * 4 + (rx & 1) * 2 + channel half, ah = ry >> 1, qh = rx >> 1 (0..8)
-    const float* isb = P.in + (size_t)b * HW * Cin;            // image base, + 8 floats per step
+    const int Hs = H >> up, Ws = W >> up;                      // the source image's own size
+    const float* isb = sgpr_ptr(src + (size_t)b * Hs * Ws * Cs);      // image base, + 8 floats per step
     unsigned ivo[5];
     bool iok[5];
 #pragma unroll
@@ -125,7 +154,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
         const int ry = 2 * ah + ((blk >> 2) & 1), rx = 2 * qh + ((blk >> 1) & 1);
         const int y = y_in0 + ry, x = x_in0 + rx;
         iok[i] = wi + 4 * i < kInPieces && ah <= kTY && qh <= kTX && y >= 0 && y < H && x >= 0 && x < W;
-        ivo[i] = iok[i] ? (unsigned)((((size_t)y * W + x) * Cin + 4 * hf) * sizeof(float)) : 0u;
+        ivo[i] = iok[i] ? (unsigned)((((size_t)(y >> up) * Ws + (x >> up)) * Cs + 4 * hf) * sizeof(float)) : 0u;
     }
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm"
@@ -192,13 +221,14 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc[j][mt][nt][r] = 0.f;
+                for (int r = 0; r < 16; ++r)
+                    if (PH == 0) acc[j][mt][nt][r] = 0.f;
 
-    const long long t_issued = a.dbg ? clock64() : 0;
+    t_issued = stamp ? clock64() : 0;
     asm volatile("s_waitcnt vmcnt(10)" ::: "memory");      // the weight fragments and step 0 (steps 1, 2 land under step 0's transform)
-    const long long t_landed = a.dbg ? clock64() : 0;
+    t_landed = stamp ? clock64() : 0;
     __syncthreads();
-    const long long t_synced = a.dbg ? clock64() : 0;
+    t_synced = stamp ? clock64() : 0;
 
     // operands as the matrix instructions take them: TA1[j][mt] = {h1 of the pair's even step, h1 of its odd step}, TA2[j][mt] = {h2
     // even, h2 odd} (four channels per piece and half); vn[mt][j]: the transformed values of the step whose pieces are being built
@@ -211,7 +241,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
     // reads them, as wino_w4.hip's items)
 #define FPC_H3_SPLIT_PAIR(J, MT, PAIR, HALF) FPC_H3_SPLIT_PAIR_V(vn, J, MT, PAIR, HALF)
 #define FPC_H3_SPLIT_PAIR_V(V, J, MT, PAIR, HALF)                                                             \
-    do {                                                                                                      \
+    if (FPC_H3_XI_LIVE(J)) do {                                                                               \
         const float x0_ = V[MT][J][2 * (PAIR)], x1_ = V[MT][J][2 * (PAIR) + 1];                               \
         const fp16x2 h_ = __builtin_amdgcn_cvt_pkrtz(x0_, x1_);                                               \
         /* x - h1 in ONE instruction: v_fma_mix_f32 reads the fp16 piece in place (m1 = -1 in a scalar register the compiler cannot  \
@@ -243,10 +273,10 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // steps 1 and 2
     __syncthreads();       // everybody's have landed; buffer 0 is refilled by the pieces of step 4, issued at the top of pair 0
 
-#define FPC_H3_MFMA(J, MT, NT, A, B) acc[J][MT][NT] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, A), __builtin_bit_cast(f16x8, B), acc[J][MT][NT], 0, 0, 0)
+#define FPC_H3_MFMA(J, MT, NT, A, B) do { if (FPC_H3_XI_LIVE(J)) acc[J][MT][NT] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, A), __builtin_bit_cast(f16x8, B), acc[J][MT][NT], 0, 0, 0); } while (0)
 #define FPC_H3_PIN4(V) asm volatile("" :: "v"(V))
 #define FPC_H3_SPLIT_Q(J, Q, HALF) do { if ((Q) == 0) FPC_H3_SPLIT_PAIR(J, 0, 0, HALF); if ((Q) == 1) FPC_H3_SPLIT_PAIR(J, 0, 1, HALF); if ((Q) == 2) FPC_H3_SPLIT_PAIR(J, 1, 0, HALF); if ((Q) == 3) FPC_H3_SPLIT_PAIR(J, 1, 1, HALF); } while (0)
-    const long long c_begin = a.dbg ? clock64() : 0, r_begin = a.dbg ? wall_clock64() : 0;
+    c_begin = stamp ? clock64() : 0; r_begin = stamp ? wall_clock64() : 0;
 #pragma unroll 1
     for (int p = 0; p < npair; ++p) {
         // ---- E: step 2p + 1's fragment reads and transform; the odd halves of xi 0 (xi 1-3 follow behind O's first matrix instructions).
@@ -324,7 +354,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
                         if (sl < 4) FPC_H3_SPLIT_Q(1, sl, 1);
                         if (sl >= 4 && sl < 8) FPC_H3_SPLIT_Q(2, sl - 4, 1);
                         if (sl >= 8 && sl < 12) FPC_H3_SPLIT_Q(3, sl - 8, 1);
-                        if (sl >= 12 && sl < 20) {
+                        if (sl >= 12 && sl < 20 && !(SKIPC && ((sl - 12) & 3) == 2)) {
                             const int m_ = (sl - 12) >> 2, jx = (sl - 12) & 3;
                             if (jx == 0) vn[m_][0] = sub_s4(e[m_][0], e[m_][2]);
                             if (jx == 1) vn[m_][1] = add_s4(e[m_][1], e[m_][2]);
@@ -340,7 +370,8 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
         __builtin_amdgcn_s_setprio(0);
         so_u += p + 2 < npair ? kPairBytes : 0;
         // this wave's ten pieces (issued before the pair's 16 weight loads, which stay in flight) have landed
-        asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+        if (PH == 0) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+        if (PH == 1) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
         __syncthreads();                                       // everybody's have; this pair's fragment reads are done
     }
 #undef FPC_H3_MFMA
@@ -353,15 +384,30 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
 #undef FPC_H3_LOAD_U2
 #undef FPC_H3_LOAD_U1_AT
 #undef FPC_H3_LOAD_U2_AT
+#undef FPC_H3_XI_LIVE
 #undef FPC_LDS_ADDR
 #pragma clang diagnostic pop
+    };      // kloop
+
+    if (!FOLD) {
+        kloop(std::integral_constant<int, 0>(), P.in, P.w, a.Cin, 0);
+    } else {
+        kloop(std::integral_constant<int, 0>(), P.in, P.w, a.Cin, 0);
+        // (both images carry ONE power-of-two scale, launch_wino_pack_h3_pair: phase 2 adds into the same scaled sums)
+        const float* w2 = a.w2[0];
+        const float* in2 = a.in2[0];
+        if (grp == 1) { w2 = a.w2[1]; in2 = a.in2[1]; }
+        if (grp == 2) { w2 = a.w2[2]; in2 = a.in2[2]; }
+        if (grp == 3) { w2 = a.w2[3]; in2 = a.in2[3]; }
+        kloop(std::integral_constant<int, 1>(), in2, w2, a.Cin2, 1);
+    }
     // (no staging is in flight here: a step past the last is never issued, every real step was waited for at the end of its pair; the
     // last pair's redundant weight reloads target registers, whose reuse the compiler guards itself)
     const long long t_kend = a.dbg ? clock64() : 0;
     if (a.dbg && lane == 0) {      // tools_dev/wino_stamps.py: shader-clock ticks and 100 MHz reference ticks of the K loop, entry -> loop
         long long* o = a.dbg + ((size_t)blockIdx.x * 4 + wi) * 8;
         o[0] = t_issued - t_entry; o[1] = t_landed - t_issued; o[2] = t_synced - t_landed;      // entry: set-up + issue | first operands land | barrier
-        o[3] = t_kend - c_begin; o[4] = wall_clock64() - r_begin; o[5] = nkb; o[6] = c_begin - t_entry;
+        o[3] = t_kend - c_begin; o[4] = wall_clock64() - r_begin; o[5] = a.Cin >> 3; o[6] = c_begin - t_entry;
     }
 
     // ---- output transform.  Column part inside the wave: z0 = m0 + m1 + m2, z1 = m1 - m2 - m3; row part across the four
@@ -372,6 +418,10 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
     const int n = nb * kBN + oq * 4;
     const f32x4 e_sc = P.scale ? *reinterpret_cast<const f32x4*>(P.scale + n) : f32x4{1.f, 1.f, 1.f, 1.f};
     const f32x4 e_sh = P.shift ? *reinterpret_cast<const f32x4*>(P.shift + n) : f32x4{0.f, 0.f, 0.f, 0.f};
+    const float* btab = a.btab[0];
+    if (grp == 1) btab = a.btab[1];
+    if (grp == 2) btab = a.btab[2];
+    if (grp == 3) btab = a.btab[3];
     // the residual of this thread's 4 x 4 outputs is requested BEFORE the output transform's barriers (one workgroup per CU: nothing
     // else hides that latency; k_conv_wino does the same)
     f32x4 e_res[4][4];
@@ -416,6 +466,10 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
                 const int y = 2 * oty + rr, x = 2 * otx + cc;
                 if (y >= H || x >= W) continue;
                 f32x4 val = (rr == 0 ? z[0][cc] + z[1][cc] + z[2][cc] : z[1][cc] - z[2][cc] - z[3][cc]) * inv_s;      // (a power of two: exact)
+                if (FOLD) {      // conv3x3(W, b 1_inside): by the output pixel's border class
+                    const int cls = (((y == 0) | ((y == H - 1) << 1)) << 2) | (x == 0) | ((x == W - 1) << 1);
+                    val += *reinterpret_cast<const f32x4*>(btab + (size_t)cls * Cout + n);
+                }
                 if (P.scale) val = val * e_sc;
                 val = val + e_sh;
                 const size_t o = ((size_t)b * HW + (size_t)y * W + x) * Cout + n;
@@ -508,9 +562,69 @@ int launch_conv_wino_h3(const WinoArgs& a, int groups, hipStream_t s) {
     if (a.tbx != cdiv(cdiv(a.W, 2), kTX) || a.tby != cdiv(cdiv(a.H, 2), kTY)) return FPC_EINVAL;
     const long long nblk = (long long)a.tbx * a.tby * a.B * (a.Cout / kBN) * groups;
     if (nblk < 1 || nblk >= (1LL << 31)) return FPC_EINVAL;
+    if (a.fold) {      // c2 + up2(p3): both phases pairs of K-steps, p2 exactly 2 x p3, the bias table and nothing else in the epilogue
+        if (a.Cin2 % 16 != 0 || (a.H | a.W) & 1 || (long long)(a.H / 2) * (a.W / 2) * a.Cin2 * (long long)sizeof(float) >= (1LL << 32) ||
+            (long long)(a.Cin2 >> 4) * kPairBytes >= (1LL << 31) || a.relu || a.dbg)
+            return FPC_EINVAL;
+        for (int g = 0; g < groups; ++g)
+            if (!a.in2[g] || !a.w2[g] || !a.btab[g] || a.p[g].scale || a.p[g].shift || a.p[g].res || a.p[g].up) return FPC_EINVAL;
+        hipLaunchKernelGGL((k_conv_wino_h3<0, true>), dim3((unsigned)nblk), dim3(256), 0, s, a);
+        return check_launch();
+    }
     static const int var = getenv("FPC_H3_VAR") ? atoi(getenv("FPC_H3_VAR")) : 0;      // diagnostic
-    if (var == 1) hipLaunchKernelGGL(k_conv_wino_h3<1>, dim3((unsigned)nblk), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k_conv_wino_h3<0>, dim3((unsigned)nblk), dim3(256), 0, s, a);
+    if (var == 1) hipLaunchKernelGGL((k_conv_wino_h3<1, false>), dim3((unsigned)nblk), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_conv_wino_h3<0, false>), dim3((unsigned)nblk), dim3(256), 0, s, a);
+    return check_launch();
+}
+
+// wc[o][k][tap] = sum_c W[o][c][tap] L[c][k]; btab[(rc * 4 + cc) * Cout + o] = sum over the taps a pixel of row class rc / column class
+// cc sees inside the image (bit 0: first row / column: no tap above / left; bit 1: last: none below / right) of sum_c W[o][c][tap] b[c].
+// f64 sums, rounded once.
+__global__ __launch_bounds__(256) void k_fold_compose(const float* __restrict__ w, const float* __restrict__ l, const float* __restrict__ bias,
+                                                      float* __restrict__ wc, float* __restrict__ btab, int Cout, int Cmid, int Cin) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    const int nw = Cout * Cin * 9;
+    if (g < nw) {
+        const int tap = g % 9, k = (g / 9) % Cin, o = g / (9 * Cin);
+        double acc = 0.0;
+        for (int c = 0; c < Cmid; ++c) acc += (double)w[((size_t)o * Cmid + c) * 9 + tap] * (double)l[(size_t)c * Cin + k];
+        wc[g] = (float)acc;
+    } else if (g < nw + 16 * Cout) {
+        const int o = (g - nw) % Cout, cls = (g - nw) / Cout, rc = cls >> 2, cc = cls & 3;
+        double acc = 0.0;
+        for (int ky = (rc & 1); ky < 3 - ((rc >> 1) & 1); ++ky)
+            for (int kx = (cc & 1); kx < 3 - ((cc >> 1) & 1); ++kx)
+                for (int c = 0; c < Cmid; ++c) acc += (double)w[((size_t)o * Cmid + c) * 9 + ky * 3 + kx] * (double)bias[c];
+        btab[(size_t)cls * Cout + o] = (float)acc;
+    }
+}
+
+int launch_fold_compose(const float* W, const float* L, const float* bias, float* wc, float* btab, int Cout, int Cmid, int Cin,
+                        hipStream_t s) {
+    if (!W || !L || !bias || !wc || !btab || Cout < 1 || Cmid < 1 || Cin < 1) return FPC_EINVAL;
+    const long long work = (long long)Cout * Cin * 9 + 16LL * Cout;
+    hipLaunchKernelGGL(k_fold_compose, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, s, W, L, bias, wc, btab, Cout, Cmid, Cin);
+    return check_launch();
+}
+
+// the fold's two images (Wc: Cin1 channels, W: Cin2) scaled by ONE power of two, from the larger max |w| of the two
+int launch_wino_pack_h3_pair(const float* w1, float* packed1, int Cin1, const float* w2, float* packed2, int Cin2, int Cout, hipStream_t s) {
+    if (Cin1 % 16 != 0 || Cin2 % 16 != 0 || Cout % kBN != 0 || ((uintptr_t)w1 & 15) || ((uintptr_t)w2 & 15)) return FPC_EINVAL;
+    float* tail1 = packed1 + (size_t)16 * Cout * Cin1;
+    float* tail2 = packed2 + (size_t)16 * Cout * Cin2;
+    if (hipMemsetAsync(tail1, 0, 2 * sizeof(float), s) != hipSuccess || hipMemsetAsync(tail2, 0, 2 * sizeof(float), s) != hipSuccess)
+        return FPC_ELAUNCH;
+    for (float* tail : {tail1, tail2}) {
+        int rc = launch_absmax_bits(w1, (long long)Cout * Cin1 * 9, reinterpret_cast<unsigned*>(tail) + 1, s);
+        if (!rc) rc = launch_absmax_bits(w2, (long long)Cout * Cin2 * 9, reinterpret_cast<unsigned*>(tail) + 1, s);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(k_wino_pack_h3, dim3((unsigned)std::min<long long>(((long long)Cout * Cin1 + 255) / 256, 4096)), dim3(256), 0, s, w1,
+                       reinterpret_cast<unsigned short*>(packed1), tail1, Cout, Cin1);
+    int rc = check_launch();
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_wino_pack_h3, dim3((unsigned)std::min<long long>(((long long)Cout * Cin2 + 255) / 256, 4096)), dim3(256), 0, s, w2,
+                       reinterpret_cast<unsigned short*>(packed2), tail2, Cout, Cin2);
     return check_launch();
 }
 

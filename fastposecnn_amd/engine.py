@@ -106,6 +106,13 @@ class NetEngine:
             nat.check(rc, "fpc_net_force_winograd")
         return rc
 
+    def force_fold(self, on):
+        """s2.0 with the FPN p2 level folded in (on = 1) or on plain form -9 (on = 0); returns 1 when the plan changed."""
+        rc = self._lib.fpc_net_force_fold(self._h, int(on))
+        if rc < 0:
+            nat.check(rc, "fpc_net_force_fold")
+        return rc
+
     def force_pointwise(self, on):
         """Every eligible 1x1 site on k_conv1x1 (on = 1) or back on k_conv_igemm (on = 0); returns the number of sites changed."""
         rc = self._lib.fpc_net_force_pointwise(self._h, int(on))

@@ -43,8 +43,8 @@
 extern "C" {
 #endif
 
-/* 11 also covers the Bottleneck encoders (fpc_net_create_encoder, fpc_net_force_pointwise, fpc_conv2d's 4000 + variant):
- * additions only, every earlier entry point keeps its behaviour. */
+/* 11 also covers the Bottleneck encoders (fpc_net_create_encoder, fpc_net_force_pointwise, fpc_conv2d's 4000 + variant) and
+ * the FPN p2 fold (fpc_net_force_fold): additions only, every earlier entry point keeps its behaviour. */
 #define FPC_ABI_VERSION 11
 
 #define FPC_OK 0
@@ -393,7 +393,10 @@ int fpc_net_autotune_next(fpc_net_t* net, int mode /* 0: minimise each conv's la
  * activations of ordinary scale (the tests hold it to the bars of every other form), NOT for tensors of tiny or huge values.  The
  * 3: additionally (and, where Cin is a multiple of 16, INSTEAD of -8) its three-product form (csrc/wino_h3.hip, reported as -9):
  * h1 g1 + h2 g1 + h1 g2 in three matrix instructions per 16 channels; the dropped h2 g2 is <= 2^-22 of the term — the size of the
- * two terms every two-piece form drops — and the same tests hold it to the same bars.
+ * two terms every two-piece form drops — and the same tests hold it to the same bars.  At this level the autotuner also times
+ * s2.0 with the FPN p2 level folded in (ResNet-18/34 encoders): conv3x3(W, L c2 + b + up2(p3)) as conv3x3(W L, c2) + conv3x3(W,
+ * up2(p3)) + a bias table by border class, in one launch that never writes p2; it is kept only when it beats the p2 lateral and
+ * s2.0 together.  s2.0 then reports -9 and the p2 lateral site nsplit = 5000 (no launch).
  * The Python front end uses 3 unless HPARAM.ENGINE_SPLIT_F16_3P (then 2) or HPARAM.ENGINE_SPLIT_F16 (then 1) is False. */
 int fpc_net_set_split_precision(fpc_net_t* net, int on);
 /* HIP graph replay (default 0).  1: after autotuning, the frame-invariant launches of fpc_net_forward (everything
@@ -414,11 +417,15 @@ int fpc_net_force_winograd(fpc_net_t* net, int form);
  * fpc_net_conv_plan as 4000 + variant); on = 0: those sites back on the implicit-GEMM kernel's heuristic tiling.  Returns the
  * number of sites changed or a negative code.  The autotuner offers the kernel itself in Bottleneck plans at split level >= 1. */
 int fpc_net_force_pointwise(fpc_net_t* net, int on);
+/* s2.0 with the FPN p2 level folded in (on = 1, ResNet-18/34 plans; see fpc_net_set_split_precision) or on plain form -9 (on = 0).
+ * Returns 1 when the plan changed, 0 when it already was so, or a negative code.  Drops the recorded graph. */
+int fpc_net_force_fold(fpc_net_t* net, int on);
 /* FLOP of one forward over the batch under the current plans: out3 = {2 x MACs of the direct convolutions (what the
  * reference's cuDNN path executes), multiply-add FLOP the plans execute (Winograd sites: / 2.25), Winograd share}. */
 int fpc_net_flops(const fpc_net_t* net, double* out3);
 /* Intermediate activations (NHWC f32 inside the workspace) for tests: "stem", "pool", "c2".."c5",
- * "d<k>.p5".."d<k>.p2", "d<k>.seg<i>" (pre-GroupNorm conv outputs), "d<k>.low" (low-res logits). */
+ * "d<k>.p5".."d<k>.p2", "d<k>.seg<i>" (pre-GroupNorm conv outputs), "d<k>.low" (low-res logits).  "d<k>.p2" is FPC_EINVAL
+ * while s2.0 runs with p2 folded in (fpc_net_set_split_precision): that tensor is never written. */
 int fpc_net_tensor(const fpc_net_t* net, const char* name, const float** ptr, int* H, int* W, int* C);
 
 /* Stand-alone convolution on the engine's implicit-GEMM kernel (tests / micro-benchmarks).
