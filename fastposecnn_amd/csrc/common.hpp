@@ -120,6 +120,21 @@ __device__ __forceinline__ void split_bf3(f32x4 v, u32x2& p1, u32x2& p2, u32x2& 
     p3 = u32x2{pack_hi16(q[0], q[1]), pack_hi16(q[2], q[3])};
 }
 
+typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
+
+// Two fp16 pieces of four activations (k_conv_igemm's three-product form, H3): h1 = fp16(x) by truncation, h2 = fp16(x - h1) with
+// the residual in ONE v_fma_mix_f32 (m1 = -1 in a scalar register, as wino_h3.hip).  x = h1 + h2 + r with |r| <= 2^-22 |x| while
+// h2 is normal (|x| >= 2^-3); below that the second piece is subnormal and x is kept to 2^-25 absolute; |x| > 131 008 saturates
+// (round-toward-zero conversions never give infinity).  p1 / p2 = {h1 x 4} / {h2 x 4} in K order.
+__device__ __forceinline__ void split_h2(f32x4 v, float m1, u32x2& p1, u32x2& p2) {
+    const float x0 = v[0], x1 = v[1], x2 = v[2], x3 = v[3];
+    const fp16x2 a = __builtin_amdgcn_cvt_pkrtz(x0, x1), b = __builtin_amdgcn_cvt_pkrtz(x2, x3);
+    const float r0 = __builtin_fmaf((float)a[0], m1, x0), r1 = __builtin_fmaf((float)a[1], m1, x1);
+    const float r2 = __builtin_fmaf((float)b[0], m1, x2), r3 = __builtin_fmaf((float)b[1], m1, x3);
+    p1 = u32x2{__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b)};
+    p2 = u32x2{__builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(r0, r1)), __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(r2, r3))};
+}
+
 __device__ __forceinline__ int wave_reduce_add(int v) {
 #pragma unroll
     for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_down(v, o, kWave);

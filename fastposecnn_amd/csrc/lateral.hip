@@ -14,6 +14,9 @@
 // A 32 x 32 accumulator register holds one output channel per lane for two pixels: stored as it stands, every store
 // instruction writes two full 128-byte lines (MI355X_MICROARCH.md: the full-rate store shape), the nearest-x2 addend is
 // fetched the same way before the tile's MFMAs.  Bound: HBM writes.
+// H3 (LatArgs::h3): k_conv_igemm's three-product form — the A fragments as two fp16 pieces (split_h2: 2/3 of the registers), the
+// weight tiles from k_pack_weight_h3's two planes, three v_mfma_f32_32x32x16_f16 per k-group, 1 / scale (a power of two) applied
+// before the bias.  (K = 256 on two pieces was tried for the p4 lateral: with its top-down addend the build spills 76 registers.)
 #include "net_kernels.hpp"
 
 namespace fpc {
@@ -21,12 +24,14 @@ namespace fpc {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
-template <int KG /* K / 16 */, bool UP /* top-down addend */>
+template <int KG /* K / 16 */, bool UP /* top-down addend */, bool H3 = false>
 __global__ __launch_bounds__(256, 2) void k_lateral1x1(const LatArgs a) {
     constexpr bool UP_AHEAD = KG == 4;      // K = 128 keeps 96 registers of A planes: its addends are fetched in their own iteration
-    constexpr int K = KG * 16, ROWB = K * 2, CPR = ROWB / 16, TILEB = 32 * ROWB, NLD = 3 * TILEB / 16 / 256;
-    __shared__ __attribute__((aligned(16))) unsigned char s_w[2][3 * TILEB];
+    constexpr int NPL = H3 ? 2 : 3;         // weight / activation planes
+    constexpr int K = KG * 16, ROWB = K * 2, CPR = ROWB / 16, TILEB = 32 * ROWB, NLD = NPL * TILEB / 16 / 256;
+    __shared__ __attribute__((aligned(16))) unsigned char s_w[2][NPL * TILEB];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, col = lane & 31, h = lane >> 5;
     const int HW = a.Ho * a.Wo, mt = (HW + 127) >> 7;
     // XCD-aware tile order: workgroups go to the 8 XCDs round-robin by id; with the grid a multiple of 8, XCD x = id % 8 takes the
@@ -51,8 +56,14 @@ __global__ __launch_bounds__(256, 2) void k_lateral1x1(const LatArgs a) {
             f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;
             if (rv) { v0 = *reinterpret_cast<const f32x4*>(ap + 16 * g); v1 = *reinterpret_cast<const f32x4*>(ap + 16 * g + 4); }
             u32x2 p1, p2, p3, q1, q2, q3;
-            split_bf3(v0, p1, p2, p3);
-            split_bf3(v1, q1, q2, q3);
+            if constexpr (H3) {
+                split_h2(v0, -1.f, p1, p2);
+                split_h2(v1, -1.f, q1, q2);
+                p3 = q3 = u32x2{0u, 0u};
+            } else {
+                split_bf3(v0, p1, p2, p3);
+                split_bf3(v1, q1, q2, q3);
+            }
             A1[g] = u32x4{p1[0], p1[1], q1[0], q1[1]};
             A2[g] = u32x4{p2[0], p2[1], q2[0], q2[1]};
             A3[g] = u32x4{p3[0], p3[1], q3[0], q3[1]};
@@ -111,6 +122,10 @@ __global__ __launch_bounds__(256, 2) void k_lateral1x1(const LatArgs a) {
             for (int i = 0; i < 16; ++i) upv[i] = up[uoff[i]];
         }
     };
+    // H3: 1 / scale of each group's weight image (behind its two planes)
+    float isc[kMaxGroup];
+#pragma unroll
+    for (int g = 0; g < kMaxGroup; ++g) isc[g] = (H3 && g < a.groups) ? reinterpret_cast<const float*>(a.wpl[g])[(size_t)a.Npad * K] : 1.f;
     const bool full = m * 128 + wv * 32 + 32 <= HW;      // wave-uniform: all 32 rows of this wave exist (every wave but a ragged map's last)
     float bias_c = 0.f, upc[16];
 #pragma unroll
@@ -135,6 +150,14 @@ __global__ __launch_bounds__(256, 2) void k_lateral1x1(const LatArgs a) {
 #pragma unroll
         for (int g = 0; g < KG; ++g) {
             const int o = ((2 * g + h) ^ swz(col)) << 4;
+            if constexpr (H3) {
+                const f16x8 g1 = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(sb + o));
+                const f16x8 g2 = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(sb + TILEB + o));
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, A2[g]), g1, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, A1[g]), g2, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, A1[g]), g1, acc, 0, 0, 0);
+                continue;
+            }
             const bf16x8 b1 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(sb + o));
             const bf16x8 b2 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(sb + TILEB + o));
             const bf16x8 b3 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(sb + 2 * TILEB + o));
@@ -144,6 +167,11 @@ __global__ __launch_bounds__(256, 2) void k_lateral1x1(const LatArgs a) {
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, A2[g]), b1, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, A1[g]), b2, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, A1[g]), b1, acc, 0, 0, 0);
+        }
+        if constexpr (H3) {      // (a power of two: exact)
+            const float inv = d == 0 ? isc[0] : d == 1 ? isc[1] : d == 2 ? isc[2] : isc[3];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[i] *= inv;
         }
         float* out = a.out[d] + img_out + (size_t)prow * a.Cout + c0 + col;
         if (full) {
@@ -200,6 +228,13 @@ int launch_lateral1x1(const LatArgs& a, hipStream_t s) {
     for (int g = 0; g < a.groups; ++g)
         if (b.bias_mask == 0u && a.shift[g]) return FPC_EINVAL;      // bias for all groups or for none
     const bool up = a.up[0] != nullptr;
+    if (a.h3) {
+        if (a.Kpad == 64 && up) hipLaunchKernelGGL((k_lateral1x1<4, true, true>), dim3((unsigned)grid), dim3(256), 0, s, b);
+        else if (a.Kpad == 64) hipLaunchKernelGGL((k_lateral1x1<4, false, true>), dim3((unsigned)grid), dim3(256), 0, s, b);
+        else if (up) hipLaunchKernelGGL((k_lateral1x1<8, true, true>), dim3((unsigned)grid), dim3(256), 0, s, b);
+        else hipLaunchKernelGGL((k_lateral1x1<8, false, true>), dim3((unsigned)grid), dim3(256), 0, s, b);
+        return check_launch();
+    }
     if (a.Kpad == 64 && up) hipLaunchKernelGGL((k_lateral1x1<4, true>), dim3((unsigned)grid), dim3(256), 0, s, b);
     else if (a.Kpad == 64) hipLaunchKernelGGL((k_lateral1x1<4, false>), dim3((unsigned)grid), dim3(256), 0, s, b);
     else if (up) hipLaunchKernelGGL((k_lateral1x1<8, true>), dim3((unsigned)grid), dim3(256), 0, s, b);

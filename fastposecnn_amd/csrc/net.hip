@@ -36,6 +36,9 @@ struct PackedConv {
     size_t w_off = 0, scale_off = 0, shift_off = 0;   // float offsets into the workspace
     size_t wino_off = 0;     // Winograd-packed copy (eligible convs only)
     bool wino_ok = false;    // 3x3, stride 1, pad 1, Cin % 8 == 0, Cout % 64 == 0
+    size_t h3_off = 0;       // k_pack_weight_h3's image (h3_ok sites only)
+    bool h3_ok = false;      // a candidate of k_conv_igemm's three-product form: the direct sites of ResNet-18/34 plans that do not
+                             // run on Winograd — the stride-2 3x3 and 1x1 convolutions and the p5 / p4 / p3 laterals
 };
 
 struct Act { size_t off = 0; int H = 0, W = 0, C = 0; };
@@ -46,6 +49,7 @@ struct ConvPlan {
     int stem = 0;            // > 0: k_stem7x7 (stem.hip), a persistent grid of this many workgroups (one per CU: 256)
     int pw = 0;              // > 0: k_conv1x1 (pointwise.hip), variant pw - 1 (net_kernels.hpp: PwArgs::variant)
     int fold = 0;            // s2.0 with wino 9 only: the FPN p2 level folded into the launch (wino_h3.hip, FOLD); no p2 lateral runs
+    int h3 = 0;              // k_conv_igemm on two fp16 pieces, three piece products (ConvArgs::h3; PackedConv::h3_ok sites)
 };
 
 // the 7x7 / stride-2 / pad-3 stem in its row-per-K-step layout (NHWC4 image, 8 taps x 4 channels per kernel row, K = 224) with a
@@ -192,6 +196,8 @@ struct fpc_net {
 
     // the FPN p2 fold of s2.0 (BasicBlock encoders: c2 has 64 channels): per decoder Wc = W L (OIHW), the h3 images of Wc and of W on
     // one scale (wino_h3.hip: launch_wino_pack_h3_pair) and the border-class bias table
+    bool h3_packed = false;               // the PackedConv::h3_ok images hold the current weights (split level 3, pack_h3_images)
+    hipStream_t load_stream = nullptr;    // stream of the last fpc_net_load_params
     bool fold_ok = false;
     size_t fold_wc_off[4] = {}, fold_img1_off[4] = {}, fold_img2_off[4] = {}, fold_tab_off[4] = {};
 
@@ -340,6 +346,18 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
             n->fold_img2_off[d] = n->alloc((size_t)16 * 128 * 256 + 2);
             n->fold_tab_off[d] = n->alloc((size_t)16 * 128);
         }
+    if (e == 1) {      // the three-product direct form's weight images, only where it is a candidate (not the p2 lateral: folded away)
+        std::vector<int> sites;
+        for (int L = 1; L < 4; ++L) { sites.push_back(n->blocks[L][0].conv1); if (n->blocks[L][0].ds >= 0) sites.push_back(n->blocks[L][0].ds); }
+        for (int d = 0; d < 4; ++d)
+            for (int i = 0; i < 3; ++i) sites.push_back(n->dec[d].lat[i]);
+        for (int ci : sites) {
+            PackedConv& c = n->convs[ci];
+            if (c.wino_ok || c.Cin % kConvBK != 0 || c.Cinp != c.Cin || c.Kh * c.Kw > 32) continue;
+            c.h3_ok = true;
+            c.h3_off = n->alloc(h3_packed_floats(c.Npad, c.Kpad));
+        }
+    }
     n->zeros_off = n->alloc(64);
     n->tickets_off = n->alloc(kConvTickets);
     n->packed_floats = n->bump;
@@ -457,11 +475,28 @@ extern "C" void fpc_net_destroy(fpc_net_t* n) {
 // 1: the next autotuning pass also times the split-precision (bf16 x 3, f32 accumulation) form of every direct
 // fast-path convolution and keeps it where it is faster.  Opt-in: the results then differ from the f32 product chain
 // by rounding (about 2^-24 relative per product, like a different f32 summation order), not bit for bit.
+// The three-product direct form's weight images (PackedConv::h3_ok): their room is reserved when the plan is built (the workspace
+// size is fixed before the split level is known), but they are packed only at level 3 — by fpc_net_load_params, or by raising the
+// level on a loaded plan (on the stream of the last load).
+static int pack_h3_images(fpc_net* n, hipStream_t s) {
+    for (const PackedConv& c : n->convs)
+        if (c.h3_ok) {
+            int rc = launch_pack_weight_h3(n->pptr[c.p_w], n->ws + c.h3_off, c.Cout, c.Cin, c.Cinp, c.Kh, c.Kw, c.Kwp, c.Npad, c.Kpad, s);
+            if (rc) return rc;
+        }
+    n->h3_packed = true;
+    return FPC_OK;
+}
+
 extern "C" int fpc_net_set_split_precision(fpc_net_t* n, int on) {
     if (!n) return FPC_EINVAL;
     n->split_precision = on < 0 ? 0 : (on > 3 ? 3 : on);      // 0: f32 products only, 1: + bf16 x 3 forms, 2: + the fp16 x 2 Winograd form, 3: + its three-product form
+    if (n->split_precision >= 3 && n->loaded && !n->h3_packed) return pack_h3_images(n, n->load_stream);
     return FPC_OK;
 }
+
+// 1 while a recorded graph replays the frame (fpc_net_set_graph, after the first frame that could be captured), else 0
+extern "C" int fpc_net_graph_recorded(const fpc_net_t* n) { return n && n->use_graph && n->graph_exec ? 1 : 0; }
 
 extern "C" int fpc_net_set_graph(fpc_net_t* n, int on) {
     if (!n) return FPC_EINVAL;
@@ -488,6 +523,9 @@ extern "C" int fpc_net_load_params(fpc_net_t* n, const float* const* params, int
     hipStream_t s = (hipStream_t)stream;
     n->ws = (float*)ws;
     n->pptr.assign(params, params + count);
+    n->load_stream = s;
+    n->h3_packed = false;
+    if (n->split_precision >= 3) { int rc = pack_h3_images(n, s); if (rc) return rc; }
     if (hipMemsetAsync(n->ws + n->zeros_off, 0, 64 * sizeof(float), s) != hipSuccess) return FPC_ELAUNCH;
     if (hipMemsetAsync(n->ws + n->tickets_off, 0, kConvTickets * sizeof(int), s) != hipSuccess) return FPC_ELAUNCH;
     for (const PackedConv& c : n->convs) {
@@ -589,12 +627,14 @@ int launch_conv_plan(ConvArgs& a, const ConvPlan& p, int groups, hipStream_t s) 
         memset(&l, 0, sizeof(l));
         l.in = a.p[0].in;
         for (int g = 0; g < groups; ++g) {
-            // the three bf16 planes sit behind the f32 image (k_pack_weight_bf3)
-            l.wpl[g] = reinterpret_cast<const unsigned short*>(a.p[g].w + (size_t)a.Npad * a.Kpad);
+            // the three bf16 planes sit behind the f32 image (k_pack_weight_bf3); h3: the site's k_pack_weight_h3 image
+            if (p.h3 && !a.h3_w[g]) return FPC_EINVAL;
+            l.wpl[g] = reinterpret_cast<const unsigned short*>(p.h3 ? a.h3_w[g] : a.p[g].w + (size_t)a.Npad * a.Kpad);
             l.out[g] = a.p[g].out; l.shift[g] = a.p[g].shift; l.up[g] = a.p[g].up;
         }
         l.B = a.B; l.Ho = a.Ho; l.Wo = a.Wo; l.Cout = a.Cout; l.Npad = a.Npad; l.Kpad = a.Kpad; l.groups = groups; l.relu = a.relu;
         l.parts = p.lat;
+        l.h3 = p.h3;
         return launch_lateral1x1(l, s);
     }
     if (p.wino) {
@@ -633,6 +673,19 @@ int launch_conv_plan(ConvArgs& a, const ConvPlan& p, int groups, hipStream_t s) 
     a.bm = p.bm; a.bn = p.bn; a.nsplit = p.nsplit; a.mtiles = p.mtiles; a.ntiles = p.ntiles; a.groups = groups;
     a.bf3 = (p.bf3 && a.generic == 0) ? 1 : 0;
     a.fused = (p.fused && p.nsplit > 1) ? 1 : 0;
+    a.h3 = 0;
+    if (p.h3) {      // the same launch on the site's k_pack_weight_h3 images (a is left as it was: the tuner reuses it)
+        if (a.generic != 0) return FPC_EINVAL;
+        ConvArgs h = a;
+        h.bf3 = 0; h.h3 = 1;
+        for (int g = 0; g < groups; ++g) {
+            if (!a.h3_w[g]) return FPC_EINVAL;
+            h.p[g].w = a.h3_w[g];
+        }
+        int rc = launch_conv(h, groups, s);
+        if (!rc && h.nsplit > 1 && !h.fused) rc = launch_conv_splitk_epilogue(h, groups, s);
+        return rc;
+    }
     int rc = launch_conv(a, groups, s);
     if (rc) return rc;
     if (a.nsplit > 1 && !a.fused) rc = launch_conv_splitk_epilogue(a, groups, s);
@@ -654,9 +707,12 @@ int run_conv(fpc_net* n, ConvArgs& a, int groups, int ci, hipStream_t s) {
         ConvPlan best = n->cplan[ci];
         size_t cap = n->splitk_floats;
         std::vector<ConvPlan> cands = conv_candidates(a.Ho * a.Wo, a.B, a.Cout, a.ksteps, groups);
+        const size_t nf = cands.size();
         if (n->split_precision && a.generic == 0) {          // the same tilings with split-precision matrix products
-            size_t nc = cands.size();
-            for (size_t i = 0; i < nc; ++i) { ConvPlan q = cands[i]; q.bf3 = 1; cands.push_back(q); }
+            for (size_t i = 0; i < nf; ++i) { ConvPlan q = cands[i]; q.bf3 = 1; cands.push_back(q); }
+        }
+        if (n->split_precision >= 3 && a.generic == 0 && a.h3_w[0]) {      // ... and with the three fp16 piece products (level 3)
+            for (size_t i = 0; i < nf; ++i) { ConvPlan q = cands[i]; q.h3 = 1; cands.push_back(q); }
         }
         if (n->split_precision && groups == 1 && stem_ok(a)) {   // weight-resident stem (bf16 x 3 planes), one workgroup per CU
             ConvPlan sq; sq.stem = 256; cands.push_back(sq);
@@ -664,7 +720,10 @@ int run_conv(fpc_net* n, ConvArgs& a, int groups, int ci, hipStream_t s) {
         if (n->split_precision && lateral_ok(a, groups)) {   // pixel-resident lateral product (bf16 x 3 planes)
             const int tiles = groups * (a.Cout / 32);
             for (int parts = 1; parts <= tiles; parts *= 2)
-                if (tiles % parts == 0) { ConvPlan lq; lq.lat = parts; cands.push_back(lq); }
+                if (tiles % parts == 0) {
+                    ConvPlan lq; lq.lat = parts; cands.push_back(lq);
+                    if (n->split_precision >= 3 && a.h3_w[0]) { lq.h3 = 1; cands.push_back(lq); }      // ... on two fp16 pieces
+                }
         }
         if (n->split_precision && n->expansion == 4 && pw_ok(a, groups)) {      // the 1x1 GEMM (bf16 x 3 planes), Bottleneck plans only
             ConvPlan pq;
@@ -818,6 +877,7 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
             fill_conv_args(n, a, c1, n->cplan[blk.conv1], cur.H, cur.W, T.H, T.W, sb, sh, sw, sc, true, 0);
             a.p[0] = ConvPtrs{ws + cur.off, ws + c1.w_off, ws + T.off, ws + c1.scale_off, ws + c1.shift_off, nullptr, nullptr, nullptr};
             if (c1.wino_ok) a.wino_w[0] = ws + c1.wino_off;
+            if (c1.h3_ok && n->h3_packed) a.h3_w[0] = ws + c1.h3_off;
             FPC_TRY(run_conv(n, a, 1, blk.conv1, s));
             const float* res = ws + cur.off;
             if (blk.ds >= 0) {
@@ -825,6 +885,7 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
                 const Act& D = n->a_blk_d[L][bi];
                 fill_conv_args(n, a, cd, n->cplan[blk.ds], cur.H, cur.W, D.H, D.W, sb, sh, sw, sc, false, 0);
                 a.p[0] = ConvPtrs{ws + cur.off, ws + cd.w_off, ws + D.off, ws + cd.scale_off, ws + cd.shift_off, nullptr, nullptr, nullptr};
+                if (cd.h3_ok && n->h3_packed) a.h3_w[0] = ws + cd.h3_off;
                 FPC_TRY(run_conv(n, a, 1, blk.ds, s));
                 res = ws + D.off;
             }
@@ -853,6 +914,7 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
             const PackedConv& c = n->convs[n->dec[d].lat[i]];
             a.p[d] = ConvPtrs{ws + src.off, ws + c.w_off, ws + n->a_p[d][i].off, nullptr, n->pptr[c.p_bias], nullptr,
                               i > 0 ? ws + n->a_p[d][i - 1].off : nullptr, nullptr};
+            if (c.h3_ok && n->h3_packed) a.h3_w[d] = ws + c.h3_off;
         }
         FPC_TRY(run_conv(n, a, 4, ci0, s));
     }
@@ -1062,6 +1124,8 @@ extern "C" int fpc_net_conv_plan(const fpc_net_t* n, int i, int* out5) {
     if (n->cplan[i].lat) { out5[0] = 128; out5[1] = 32; out5[2] = 2000 + n->cplan[i].lat; }      // k_lateral1x1 (fpc_conv2d's hook value)
     if (n->cplan[i].stem) { out5[0] = 64; out5[1] = 64; out5[2] = 3000; }                        // k_stem7x7
     if (n->cplan[i].pw) { out5[0] = pw_tile_pixels(n->cplan[i].pw - 1); out5[1] = 64; out5[2] = 4000 + n->cplan[i].pw - 1; }      // k_conv1x1
+    // the three-product form: k_conv_igemm 6000 + split (fused or not, as the plain tilings), k_lateral1x1 7000 + parts
+    if (n->cplan[i].h3) out5[2] = n->cplan[i].lat ? 7000 + n->cplan[i].lat : 6000 + n->cplan[i].nsplit;
     if (n->fold_ok && i == n->dec[0].lat[3] && n->cplan[n->dec[0].seg[6]].fold) out5[2] = 5000;      // the p2 lateral, folded into s2.0
     out5[3] = n->convs[i].Cout; out5[4] = n->convs[i].K;
     return FPC_OK;
@@ -1123,6 +1187,27 @@ extern "C" int fpc_net_force_pointwise(fpc_net_t* n, int on) {
     return changed;
 }
 
+// Every site with a k_pack_weight_h3 image (PackedConv::h3_ok; packed at split level 3 only) -> the three-product form (on = 1: a
+// k_lateral1x1 site on its two-piece build, any other on its own k_conv_igemm tiling or the heuristic one) or back to the heuristic
+// f32 tiling (on = 0; sites not on the form are not counted).  Returns the number of sites changed, or a negative code.  Drops the recorded graph.
+extern "C" int fpc_net_force_direct_h3(fpc_net_t* n, int on) {
+    if (!n || on < 0 || on > 1 || (on && !n->h3_packed)) return FPC_EINVAL;      // (the images are packed at split level 3 only)
+    int changed = 0;
+    for (size_t i = 0; i < n->convs.size(); ++i) {
+        const PackedConv& c = n->convs[i];
+        if (!c.h3_ok || !n->c_groups[i] || on == n->cplan[i].h3) continue;
+        const ConvPlan& p = n->cplan[i];
+        ConvPlan q = plan_conv(n->c_howo[i], n->B, c.Cout, c.Kpad / kConvBK, n->c_groups[i]);
+        if (on && !p.wino && !p.stem && !p.pw) q = p;      // (a k_lateral1x1 site stays on it, on two pieces)
+        q.bf3 = 0;
+        q.h3 = on;
+        n->cplan[i] = q;
+        ++changed;
+    }
+    if (n->graph_exec) { (void)hipGraphExecDestroy(n->graph_exec); n->graph_exec = nullptr; }
+    return changed;
+}
+
 // Plans of `src` -> `dst` (same encoder, classes, H, W; batch sizes may differ): runs a small batch on the tilings, split-K
 // factors and kernel forms a larger one was autotuned to (tests: the headline configuration's kernels against float64 on two
 // frames).  A plan whose split-K partials do not fit dst's workspace keeps dst's own.  Drops dst's recorded graph.
@@ -1138,6 +1223,7 @@ extern "C" int fpc_net_copy_plans(fpc_net_t* dst, const fpc_net_t* src) {
         const ConvPlan& q = src->cplan[i];
         if (splitk_floats_for(q, dst->c_groups[i] ? dst->c_groups[i] : 1, dst->B, dst->convs[i].Npad) > dst->splitk_floats) continue;
         if (q.nsplit > 1 && q.fused && !can_fuse(q, dst->c_groups[i] ? dst->c_groups[i] : 1, dst->B)) continue;
+        if (q.h3 && !dst->h3_packed) continue;      // dst is not at split level 3: no three-product images
         dst->cplan[i] = q;
     }
     dst->tuned = true;
@@ -1202,6 +1288,7 @@ extern "C" int fpc_conv2d_plan(int B, int Ho, int Wo, int Cin, int Cout, int Kh,
                                int* out4) {
     if (!out4) return FPC_EINVAL;
     int Kpad = cdiv(Cin * Kh * Kw, kConvBK) * kConvBK;
+    if (nsplit >= 6000 && nsplit < 6200) nsplit -= 6000;      // the three-product form keeps the tiling (100 + split: two launches)
     if (nsplit >= 2000) nsplit = 1;          // k_lateral1x1 / k_stem7x7 / k_conv1x1: no split-K, no GroupNorm rows
     if (nsplit >= 1000) nsplit -= 1000;      // fpc_conv2d's split-precision / two-launch hooks do not change the tiling
     if (nsplit >= 100) nsplit -= 100;
@@ -1213,9 +1300,15 @@ extern "C" int fpc_conv2d_plan(int B, int Ho, int Wo, int Cin, int Cout, int Kh,
 
 namespace {
 // the hooks folded into fpc_conv2d's `nsplit` argument
-struct Conv2dRequest { int nsplit; bool bf3, two_launch, wino; int lat; bool stem; int pw; };
+struct Conv2dRequest { int nsplit; bool bf3, two_launch, wino; int lat; bool stem; int pw; bool h3; };
 Conv2dRequest conv2d_request(int nsplit) {
-    Conv2dRequest r{nsplit, false, false, false, 0, false, 0};
+    Conv2dRequest r{nsplit, false, false, false, 0, false, 0, false};
+    if (r.nsplit >= 7000 && r.nsplit < 8000) { r.lat = r.nsplit - 7000; r.h3 = true; r.nsplit = 1; return r; }      // 7000 + parts = k_lateral1x1 on two fp16 pieces
+    if (r.nsplit >= 6000 && r.nsplit < 6200) {      // 6000 + split = k_conv_igemm's three-product form (fused split-K), 6100 + split: two launches
+        r.h3 = true; r.nsplit -= 6000;
+        if (r.nsplit >= 100) { r.two_launch = true; r.nsplit -= 100; }
+        return r;
+    }
     if (r.nsplit >= 4000) { r.pw = r.nsplit - 4000 + 1; r.bf3 = true; r.nsplit = 1; return r; }   // 4000 + variant = k_conv1x1 (pointwise.hip)
     if (r.nsplit == 3000) { r.stem = true; r.bf3 = true; r.nsplit = 1; return r; }                   // 3000 = k_stem7x7 (stem.hip): NHWC4 input
     if (r.nsplit >= 2000) { r.lat = r.nsplit - 2000; r.bf3 = true; r.nsplit = 1; return r; }      // 2000 + parts = k_lateral1x1 (lateral.hip)
@@ -1245,6 +1338,7 @@ ConvPlan conv2d_plan_for(int B, int Ho, int Wo, int Cin, int Cout, int Kh, int K
     const int Kpad = cdiv(Cin * Kh * Kw, kConvBK) * kConvBK;
     ConvPlan p = plan_conv(Ho * Wo, B, Cout, Kpad / kConvBK, 1, r.wino ? 0 : bm, bn, r.wino ? 1 : r.nsplit);
     p.bf3 = r.bf3 ? 1 : 0;
+    p.h3 = r.h3 ? 1 : 0;
     if (r.two_launch) p.fused = 0;
     p.lat = r.lat;
     p.stem = r.stem ? 256 : 0;
@@ -1298,8 +1392,10 @@ extern "C" int fpc_conv2d(const float* in, int64_t sb, int64_t sh, int64_t sw, i
     // (the split-precision forms — bf16 x 3 tiles, k_lateral1x1 — read only the planes behind the f32 image: it is not packed for them)
     static_assert(FPC_IGEMM_DMA_B, "the split-precision direct form stages its B rows from the bf16 planes by LDS-DMA; a build that loads "
                                    "them from the f32 image must pack that image here as well");
-    if (!wino && !p.bf3) FPC_TRY(launch_pack_weight(w_oihw, packed, Cout, Cin, Cin, Kh, Kw, Kw, c.Npad, c.Kpad, s));
+    // (the three-product form reads its own image at the start of the packed region: conv_packed_floats() > h3_packed_floats())
+    if (!wino && !p.bf3 && !p.h3) FPC_TRY(launch_pack_weight(w_oihw, packed, Cout, Cin, Cin, Kh, Kw, Kw, c.Npad, c.Kpad, s));
     if (!wino && p.bf3) FPC_TRY(launch_pack_weight_bf3(w_oihw, packed, Cout, Cin, Cin, Kh, Kw, Kw, c.Npad, c.Kpad, s));
+    if (!wino && p.h3) FPC_TRY(launch_pack_weight_h3(w_oihw, packed, Cout, Cin, Cin, Kh, Kw, Kw, c.Npad, c.Kpad, s));
     int mode = (sc == 1 && Cin % kConvBK == 0 && Kh * Kw <= 32 && ((int64_t)Hi + 2 * pad) * sh * 4 < ((int64_t)1 << 31)) ? 0
                : (sc == 1 && Cin % 4 == 0 && sw % 4 == 0 && sh % 4 == 0 && sb % 4 == 0 && ((uintptr_t)in & 15) == 0) ? 2 : 1;
     fpc_net tmp;
@@ -1340,6 +1436,11 @@ extern "C" int fpc_conv2d(const float* in, int64_t sb, int64_t sh, int64_t sw, i
             a.zeros = zp;
         }
         p.wino = -nsplit;
+        return launch_conv_plan(a, p, 1, s);
+    }
+    if (p.h3) {
+        if (mode != 0) return FPC_EINVAL;
+        a.h3_w[0] = packed;
         return launch_conv_plan(a, p, 1, s);
     }
     a.bf3 = (p.bf3 && mode == 0) ? 1 : 0;

@@ -14,6 +14,10 @@
 //                       K-step's global loads are in flight under the current step's MFMAs.
 //                       Epilogue: folded BatchNorm / bias, residual, FPN nearest-x2 add, ReLU,
 //                       GroupNorm partial sums.  Split-K writes raw partials instead.
+//                       Split forms (MODE 0): BF3, three bf16 planes per operand and six products per 16-deep k group
+//                       (fpc_conv2d's 1000 + split); H3, two fp16 planes and three products (6000 + split, 6100 + split with
+//                       the second-launch split-K sum) on k_pack_weight_h3's power-of-two-scaled weights — activations keep
+//                       2^-22 relative for |x| >= 2^-3, 2^-25 absolute below, and saturate (finite) beyond 1.3e5.
 //   k_conv_splitk_epilogue  fixed-order sum of the split-K partials + the same epilogue.
 //   k_maxpool3x3s2, k_gn_finalize, k_gn_relu_up2, k_merge_head, k_up4_compress: HBM-bound
 //                       streaming kernels, lanes along the contiguous (channel or x) axis.
@@ -27,8 +31,12 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
 
 // split_bf3 / pack_hi16: common.hpp (shared with conv_wgrad.hip)
+
+// split_h2: common.hpp (shared with lateral.hip)
 
 // raw buffer descriptor over [base, base + 2 GB): offsets are 32-bit, an offset >= 2^31 reads zeros without
 // touching memory (measured, tools_dev/dma_vs_mfma.hip) — the zero fill of the convolution padding
@@ -293,15 +301,20 @@ __device__ __forceinline__ void conv_epilogue(const ConvPtrs& P, const EpiGeom& 
 }
 
 // (the 128x128 tiling keeps 64 accumulator + 64 staging registers per lane: one workgroup per CU, no spills)
-template <int BM, int BN, int MODE, bool BF3 = false>
+// H3 (ConvArgs::h3): the three-product form on two fp16 pieces per operand (split_h2; weights: k_pack_weight_h3's planes)
+template <int BM, int BN, int MODE, bool BF3 = false, bool H3 = false>
 __global__ __launch_bounds__(256, (BM * BN >= 128 * 128) ? 1 : 2) void k_conv_igemm(const ConvArgs a) {
     constexpr int TM = BM / 64, TN = BN / 64;     // 32x32 tiles per wave
     constexpr int AR = BM / 32, BR = BN / 32;     // float4 rows staged per thread
-    constexpr bool DMAB = BF3 && FPC_IGEMM_DMA_B; // split precision: weight planes pre-split, staged by LDS-DMA
-    // f32 operands: 2 stages x (BM + BN) rows x 128 B;  split precision: 2 stages x 3 planes x (BM + BN) rows x 64 B
-    __shared__ __attribute__((aligned(16))) float lds[BF3 ? 2 * (BM + BN) * 48 : 2 * (BM + BN) * kLdsRow];
+    constexpr bool SPL = BF3 || H3;               // split operands in LDS planes
+    constexpr int NPL = H3 ? 2 : 3;               // planes per operand
+    constexpr int kPlB = NPL * 64;                // bytes of one operand row over its planes (one stage)
+    constexpr bool DMAB = SPL && FPC_IGEMM_DMA_B; // split precision: weight planes pre-split, staged by LDS-DMA
+    // f32 operands: 2 stages x (BM + BN) rows x 128 B;  split precision: 2 stages x NPL planes x (BM + BN) rows x 64 B
+    __shared__ __attribute__((aligned(16))) float lds[SPL ? 2 * (BM + BN) * (NPL * 16) : 2 * (BM + BN) * kLdsRow];
     __shared__ int s_last;
-    static_assert(!BF3 || MODE == 0, "split precision rides on the fast loader");
+    static_assert(!SPL || MODE == 0, "split precision rides on the fast loader");
+    static_assert(!(BF3 && H3) && (!H3 || DMAB), "one product form; H3 weights come by LDS-DMA only");
 #ifdef FPC_STAMP_IGEMM      // diagnostic build (tools_dev/igemm_stamps.py): phase stamps per wave into a.dbg
     const long long st0 = clock64();
 #endif
@@ -379,7 +392,8 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128) ? 1 : 2) void k_conv_ig
     // lane l -> row l >> 2, slot l & 3); 3 * BN / 16 pieces per K-step, piece q = wave + 4 i is plane q / (BN / 16), row
     // group q % (BN / 16).  The swizzle is the choice of the chunk each lane fetches.  SGPR base + 32-bit lane offset, the
     // base advances 64 B per K-step (see the Winograd kernel for why not a 64-bit lane address).
-    constexpr int kRG = BN / 16, kNPB = 3 * kRG / 4;
+    // (H3: the two fp16 planes start at P.w and 1 / s follows them)
+    constexpr int kRG = BN / 16, kNPB = NPL * kRG / 4;
     const int swave = __builtin_amdgcn_readfirstlane(wave);
     unsigned bvo[kNPB];
     const char* w3b = nullptr;
@@ -390,8 +404,11 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128) ? 1 : 2) void k_conv_ig
             const int r = rg * 16 + (lane >> 2), c = (lane & 3) ^ ((r >> 2) & 1);
             bvo[i] = (unsigned)((((size_t)pl * Npad + n0 + r) * Kpad + c * 8) * 2);
         }
-        w3b = reinterpret_cast<const char*>(P.w + (size_t)Npad * Kpad) + (size_t)ks0 * (kConvBK * 2);
+        w3b = reinterpret_cast<const char*>(P.w + (H3 ? 0 : (size_t)Npad * Kpad)) + (size_t)ks0 * (kConvBK * 2);
     }
+    const float h3_inv = H3 ? P.w[(size_t)Npad * Kpad] : 1.f;
+    float m1 = -1.f;
+    if constexpr (H3) asm volatile("s_mov_b32 %0, 0xbf800000" : "=s"(m1));      // -1.0f, opaque: x - h1 as one v_fma_mix_f32
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm"
 #define FPC_CONV_DMA_B(BUF)                                                                                   \
@@ -400,7 +417,7 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128) ? 1 : 2) void k_conv_ig
             const int q_ = swave + 4 * i, pl_ = q_ / kRG, rg_ = q_ - pl_ * kRG;                               \
             asm volatile("s_mov_b32 m0, %0\n s_nop 0\n global_load_lds_dwordx4 %1, %2\n"                      \
                          :: "s"((unsigned)(size_t)(__attribute__((address_space(3))) void*)(reinterpret_cast<char*>(lds) + \
-                                 (BUF) * (BM + BN) * 192 + pl_ * (BM + BN) * 64 + (BM + rg_ * 16) * 64)),       \
+                                 (BUF) * (BM + BN) * kPlB + pl_ * (BM + BN) * 64 + (BM + rg_ * 16) * 64)),      \
                             "v"(bvo[i]), "s"(w3b) : "memory", "m0");                                          \
         }                                                                                                     \
         w3b += kConvBK * 2;                                                                                   \
@@ -556,8 +573,99 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128) ? 1 : 2) void k_conv_ig
         }                                                                                                     \
         __builtin_amdgcn_s_setprio(0);                                                                        \
     } while (0)
-#define FPC_STORE_ANY(BUF, ra, rb) do { if (BF3) FPC_CONV_STORE_BF3(BUF, ra, rb); else FPC_CONV_STORE(BUF, ra, rb); } while (0)
-#define FPC_COMPUTE_ANY(BUF) do { if (BF3) FPC_CONV_COMPUTE_BF3(BUF); else FPC_CONV_COMPUTE(BUF); } while (0)
+    // Three-product form (H3): per 16-deep k group two fp16 planes per operand, acc += A2 B1 + A1 B2 + A1 B1 — three MFMAs per
+    // 32x32 tile instead of six.  The activation rows are split on the way into LDS (split_h2), the weight planes come by LDS-DMA.
+#define FPC_H3_FRAG(KK, FA, FB)                                                                               \
+    do {                                                                                                      \
+        _Pragma("unroll") for (int p_ = 0; p_ < 2; ++p_) {                                                    \
+            _Pragma("unroll") for (int i = 0; i < TM; ++i) FA[p_][i] = __builtin_bit_cast(f16x8,              \
+                *reinterpret_cast<const u32x4*>(Ab + p_ * (BM + BN) * 64 + i * 32 * 64 + bf3_r[KK]));         \
+            _Pragma("unroll") for (int j = 0; j < TN; ++j) FB[p_][j] = __builtin_bit_cast(f16x8,              \
+                *reinterpret_cast<const u32x4*>(Bb + p_ * (BM + BN) * 64 + j * 32 * 64 + bf3_r[KK]));         \
+        }                                                                                                     \
+    } while (0)
+#define FPC_H3_MFMA(FA, FB)                                                                                   \
+    do {                                                                                                      \
+        _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                        \
+            _Pragma("unroll") for (int j = 0; j < TN; ++j) {                                                  \
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(FA[1][i], FB[0][j], acc[i][j], 0, 0, 0);   \
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(FA[0][i], FB[1][j], acc[i][j], 0, 0, 0);   \
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(FA[0][i], FB[0][j], acc[i][j], 0, 0, 0);   \
+            }                                                                                                 \
+    } while (0)
+#define FPC_CONV_COMPUTE_H3(BUF)                                                                              \
+    do {                                                                                                      \
+        const char* Ab = reinterpret_cast<const char*>(lds) + (BUF) * (BM + BN) * kPlB + (wm * (BM / 2) + li) * 64;        \
+        const char* Bb = reinterpret_cast<const char*>(lds) + (BUF) * (BM + BN) * kPlB + (BM + wn * (BN / 2) + li) * 64;   \
+        f16x8 ha0[2][TM], hb0[2][TN], ha1[2][TM], hb1[2][TN];                                                 \
+        FPC_H3_FRAG(0, ha0, hb0);                                                                             \
+        FPC_H3_FRAG(1, ha1, hb1);                                                                             \
+        __builtin_amdgcn_sched_barrier(0);                                                                    \
+        __builtin_amdgcn_s_setprio(FPC_IGEMM_PRIO);                                                           \
+        FPC_H3_MFMA(ha0, hb0);                                                                                \
+        FPC_H3_MFMA(ha1, hb1);                                                                                \
+        __builtin_amdgcn_s_setprio(0);                                                                        \
+    } while (0)
+    // ... with the split of the NEXT step's activation registers (ra -> the two planes of buffer BUF ^ 1) cut into 4 micro-steps
+    // per row (two truncating conversions, four v_fma_mix residuals, two conversions, two 8-byte LDS stores) issued one after each
+    // MFMA, as FPC_CONV_COMPUTE_STORE_BF3.  Not for the 128 x 128 tile.
+#define FPC_CONV_COMPUTE_STORE_H3(BUF, ra)                                                                    \
+    do {                                                                                                      \
+        const char* Ab = reinterpret_cast<const char*>(lds) + (BUF) * (BM + BN) * kPlB + (wm * (BM / 2) + li) * 64;        \
+        const char* Bb = reinterpret_cast<const char*>(lds) + (BUF) * (BM + BN) * kPlB + (BM + wn * (BN / 2) + li) * 64;   \
+        char* st_ = reinterpret_cast<char*>(lds) + ((BUF) ^ 1) * (BM + BN) * kPlB;                            \
+        f16x8 ha[2][2][TM], hb[2][2][TN];                                                                     \
+        FPC_H3_FRAG(0, ha[0], hb[0]);                                                                         \
+        FPC_H3_FRAG(1, ha[1], hb[1]);                                                                         \
+        __builtin_amdgcn_sched_barrier(0);                                                                    \
+        __builtin_amdgcn_s_setprio(FPC_IGEMM_PRIO);                                                           \
+        constexpr int kNM = 6 * TM * TN, kNS = 4 * AR;      /* MFMAs, split micro-steps */                     \
+        constexpr int kPa[3] = {1, 0, 0}, kPb[3] = {0, 1, 0};                                                 \
+        fp16x2 sh1_[AR][2];                                                                                   \
+        float sr_[AR][4];                                                                                     \
+        u32x2 sp1_[AR], sp2_[AR];                                                                             \
+        _Pragma("unroll") for (int m_ = 0; m_ < kNM; ++m_) {                                                  \
+            const int kk_ = m_ / (3 * TM * TN), t_ = (m_ / 3) % (TM * TN), c_ = m_ % 3;                       \
+            const int i_ = t_ / TN, j_ = t_ % TN;                                                             \
+            acc[i_][j_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ha[kk_][kPa[c_]][i_], hb[kk_][kPb[c_]][j_], acc[i_][j_], 0, 0, 0); \
+            _Pragma("unroll") for (int ns_ = m_ * kNS / kNM; ns_ < (m_ + 1) * kNS / kNM; ++ns_) {             \
+                const int r_ = ns_ / 4, ph_ = ns_ % 4;                                                        \
+                if (ph_ == 0) {                                                                               \
+                    const float x0_ = ra[r_][0], x1_ = ra[r_][1], x2_ = ra[r_][2], x3_ = ra[r_][3];           \
+                    sh1_[r_][0] = __builtin_amdgcn_cvt_pkrtz(x0_, x1_);                                       \
+                    sh1_[r_][1] = __builtin_amdgcn_cvt_pkrtz(x2_, x3_);                                       \
+                }                                                                                             \
+                if (ph_ == 1) { _Pragma("unroll") for (int e = 0; e < 4; ++e) { const float x_ = ra[r_][e]; sr_[r_][e] = __builtin_fmaf((float)sh1_[r_][e >> 1][e & 1], m1, x_); } } \
+                if (ph_ == 2) {                                                                               \
+                    sp1_[r_] = u32x2{__builtin_bit_cast(unsigned, sh1_[r_][0]), __builtin_bit_cast(unsigned, sh1_[r_][1])};           \
+                    sp2_[r_] = u32x2{__builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(sr_[r_][0], sr_[r_][1])),                 \
+                                     __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(sr_[r_][2], sr_[r_][3]))};                \
+                }                                                                                             \
+                if (ph_ == 3) {                                                                               \
+                    char* d_ = st_ + (sr + 32 * r_) * 64 + bf3_w;                                             \
+                    *reinterpret_cast<u32x2*>(d_) = sp1_[r_];                                                 \
+                    *reinterpret_cast<u32x2*>(d_ + (BM + BN) * 64) = sp2_[r_];                                \
+                }                                                                                             \
+            }                                                                                                 \
+            __builtin_amdgcn_sched_barrier(0);                                                                \
+        }                                                                                                     \
+        __builtin_amdgcn_s_setprio(0);                                                                        \
+    } while (0)
+#define FPC_CONV_STORE_H3(BUF, ra)                                                                            \
+    do {                                                                                                      \
+        char* st_ = reinterpret_cast<char*>(lds) + (BUF) * (BM + BN) * kPlB;                                  \
+        _Pragma("unroll") for (int i = 0; i < AR; ++i) {                                                      \
+            u32x2 p1_, p2_;                                                                                   \
+            split_h2(ra[i], m1, p1_, p2_);                                                                    \
+            char* d_ = st_ + (sr + 32 * i) * 64 + bf3_w;                                                      \
+            *reinterpret_cast<u32x2*>(d_) = p1_;                                                              \
+            *reinterpret_cast<u32x2*>(d_ + (BM + BN) * 64) = p2_;                                             \
+        }                                                                                                     \
+    } while (0)
+#define FPC_STORE_ANY(BUF, ra, rb) do { if (H3) FPC_CONV_STORE_H3(BUF, ra); else if (BF3) FPC_CONV_STORE_BF3(BUF, ra, rb); else FPC_CONV_STORE(BUF, ra, rb); } while (0)
+#define FPC_COMPUTE_ANY(BUF) do { if (H3) FPC_CONV_COMPUTE_H3(BUF); else if (BF3) FPC_CONV_COMPUTE_BF3(BUF); else FPC_CONV_COMPUTE(BUF); } while (0)
+    // the interleaved split-and-compute block of the split forms (the 128 x 128 tile computes, then stores)
+#define FPC_COMPUTE_STORE_SPLIT(BUF, ra) do { if constexpr (H3) FPC_CONV_COMPUTE_STORE_H3(BUF, ra); else FPC_CONV_COMPUTE_STORE_BF3(BUF, ra); } while (0)
 
     // Split precision: the weight planes of step k + 1 are DMA'd into the other LDS buffer at the start of step k (that buffer
     // was last read in step k - 1) and must have landed at the barrier that ends step k; the activation loads issued after
@@ -577,7 +685,7 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128) ? 1 : 2) void k_conv_ig
         // even phase: LDS buffer 0 holds step ks, set 0 holds ks+1
         if constexpr (DMAB) { if (ks + 1 < ks1) FPC_CONV_DMA_B(1); }
         if (ks + 2 < ks1) FPC_CONV_LOAD(ks + 2, ra1, rb1);
-        if constexpr (DMAB && FPC_IGEMM_INTERLEAVE && BM * BN < 128 * 128) FPC_CONV_COMPUTE_STORE_BF3(0, ra0);
+        if constexpr (DMAB && FPC_IGEMM_INTERLEAVE && BM * BN < 128 * 128) FPC_COMPUTE_STORE_SPLIT(0, ra0);
         else {
             FPC_COMPUTE_ANY(0);
             if (ks + 1 < ks1) FPC_STORE_ANY(1, ra0, rb0);
@@ -588,7 +696,7 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128) ? 1 : 2) void k_conv_ig
         // odd phase: LDS buffer 1 holds step ks+1, set 1 holds ks+2
         if constexpr (DMAB) { if (ks + 2 < ks1) FPC_CONV_DMA_B(0); }
         if (ks + 3 < ks1) FPC_CONV_LOAD(ks + 3, ra0, rb0);
-        if constexpr (DMAB && FPC_IGEMM_INTERLEAVE && BM * BN < 128 * 128) FPC_CONV_COMPUTE_STORE_BF3(1, ra1);
+        if constexpr (DMAB && FPC_IGEMM_INTERLEAVE && BM * BN < 128 * 128) FPC_COMPUTE_STORE_SPLIT(1, ra1);
         else {
             FPC_COMPUTE_ANY(1);
             if (ks + 2 < ks1) FPC_STORE_ANY(0, ra1, rb1);
@@ -597,6 +705,14 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128) ? 1 : 2) void k_conv_ig
         __syncthreads();
     }
 #pragma clang diagnostic pop
+    // H3: the sums are of weights scaled by s = 2^k; 1 / s is a power of two, so this is exact — the epilogue and the split-K
+    // partials (k_conv_splitk_epilogue, the fused last-arriver sum) see unscaled sums
+    if constexpr (H3) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j) acc[i][j] *= h3_inv;
+    }
 
 #ifdef FPC_STAMP_IGEMM
     const long long st2 = clock64();
@@ -1317,6 +1433,35 @@ __global__ __launch_bounds__(256) void k_pack_weight_bf3(const float* __restrict
     }
 }
 
+// The same [Npad][Kpad] image as TWO fp16 planes for k_conv_igemm's three-product form: scaled by s = 2^k, the largest power of
+// two with max |w| s < 2^13 (k_wino_pack_h2's rule without the transform's 2.25; max |w| from k_absmax_bits in tail[1]), and split
+// by truncation, w s = g1 + g2 + rest with |rest| <= 2^-22 |w s|: out[(plane * Npad + n) * Kpad + k], tail[0] = 1 / s.
+__global__ __launch_bounds__(256) void k_pack_weight_h3(const float* __restrict__ w, unsigned short* __restrict__ out, float* __restrict__ tail,
+                                                        int Cout, int Cin, int Cinp, int Kh, int Kw, int Kwp, int Npad, int Kpad) {
+    const float wmax = __builtin_bit_cast(float, reinterpret_cast<const unsigned*>(tail)[1]);
+    int ex = 0;
+    if (wmax > 0.f && wmax < 3.0e38f) { (void)frexpf(wmax, &ex); ex = 13 - ex; }      // wmax = m 2^e, m in [0.5, 1): wmax 2^(13 - e) < 2^13
+    ex = max(-100, min(100, ex));
+    const float sc = ldexpf(1.0f, ex);
+    if (blockIdx.x == 0 && threadIdx.x == 0) tail[0] = ldexpf(1.0f, -ex);
+    const int K = Cinp * Kh * Kwp;
+    const long long total = (long long)Npad * Kpad;
+    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (long long)gridDim.x * blockDim.x) {
+        int n = (int)(g / Kpad), k = (int)(g - (long long)n * Kpad);
+        float v = 0.f;
+        if (n < Cout && k < K) {
+            int tap = k / Cinp, ci = k - tap * Cinp;
+            int kh = tap / Kwp, kw = tap - kh * Kwp;
+            if (ci < Cin && kw < Kw) v = w[(((size_t)n * Cin + ci) * Kh + kh) * Kw + kw] * sc;      // (a power of two: exact)
+        }
+        const fp16x2 h = __builtin_amdgcn_cvt_pkrtz(v, 0.f);
+        const float r = v - (float)h[0];
+        const fp16x2 h2 = __builtin_amdgcn_cvt_pkrtz(r, 0.f);
+        out[g] = (unsigned short)(__builtin_bit_cast(unsigned, h) & 0xFFFFu);
+        out[total + g] = (unsigned short)(__builtin_bit_cast(unsigned, h2) & 0xFFFFu);
+    }
+}
+
 // image NCHW [B,3,H,W] -> NHWC4 [B,H,W,4] (4th channel 0): 16-byte pixels for the stem's loader
 __global__ __launch_bounds__(256) void k_nchw3_to_nhwc4(const float* __restrict__ x, float* __restrict__ out, int B,
                                                         int HW) {
@@ -1346,7 +1491,9 @@ __global__ void k_fold_bn(const float* __restrict__ gamma, const float* __restri
 template <int BM, int BN>
 static void launch_conv_t(const ConvArgs& a, int groups, hipStream_t s) {
     dim3 grid(a.mtiles * a.B * a.ntiles * a.nsplit * groups);
-    if (a.generic == 0 && a.bf3)
+    if (a.generic == 0 && a.h3)
+        hipLaunchKernelGGL((k_conv_igemm<BM, BN, 0, false, true>), grid, dim3(256), 0, s, a);
+    else if (a.generic == 0 && a.bf3)
         hipLaunchKernelGGL((k_conv_igemm<BM, BN, 0, true>), grid, dim3(256), 0, s, a);
     else if (a.generic == 0)
         hipLaunchKernelGGL((k_conv_igemm<BM, BN, 0>), grid, dim3(256), 0, s, a);
@@ -1364,6 +1511,7 @@ int launch_conv(const ConvArgs& a, int groups, hipStream_t s) {
                            ((long long)a.Hi + 2 * a.pad) * a.in_sh * 4 >= (1LL << 31)))
         return FPC_EINVAL;      // tap mask is 32 bits, lane offsets are 31 bits
     if ((long long)a.Npad * a.Kpad * 4 >= (1LL << 31)) return FPC_EINVAL;
+    if (a.h3 && (a.generic != 0 || a.bf3 || a.lanepx)) return FPC_EINVAL;      // the three-product form rides on the fast loader alone
     if (a.nsplit > 1 && a.fused && (!a.tickets || (long long)groups * a.B * a.mtiles * a.ntiles > kConvTickets || a.Cout % 4 != 0))
         return FPC_EINVAL;
     if (a.generic == 2 && (a.Cin % 4 != 0 || a.in_sc != 1 || a.in_sw % 4 != 0 || a.in_sh % 4 != 0 || a.in_sb % 4 != 0))
@@ -2310,6 +2458,18 @@ int launch_pack_weight_bf3(const float* w, float* packed, int Cout, int Cin, int
     if (Kwp < Kw || Cinp < Cin) return FPC_EINVAL;
     hipLaunchKernelGGL(k_pack_weight_bf3, dim3(stream_grid((long long)Npad * Kpad)), dim3(256), 0, s, w,
                        reinterpret_cast<unsigned short*>(packed + (size_t)Npad * Kpad), Cout, Cin, Cinp, Kh, Kw, Kwp, Npad, Kpad);
+    return check_launch();
+}
+
+int launch_pack_weight_h3(const float* w, float* packed, int Cout, int Cin, int Cinp, int Kh, int Kw, int Kwp, int Npad,
+                          int Kpad, hipStream_t s) {
+    if (Kwp < Kw || Cinp < Cin || ((uintptr_t)w & 15)) return FPC_EINVAL;
+    float* tail = packed + (size_t)Npad * Kpad;
+    if (hipMemsetAsync(tail, 0, 2 * sizeof(float), s) != hipSuccess) return FPC_ELAUNCH;
+    const int rc = launch_absmax_bits(w, (long long)Cout * Cin * Kh * Kw, reinterpret_cast<unsigned*>(tail) + 1, s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_pack_weight_h3, dim3(stream_grid((long long)Npad * Kpad)), dim3(256), 0, s, w,
+                       reinterpret_cast<unsigned short*>(packed), tail, Cout, Cin, Cinp, Kh, Kw, Kwp, Npad, Kpad);
     return check_launch();
 }
 

@@ -35,9 +35,12 @@ struct ConvArgs {
     long long in_sb, in_sh, in_sw, in_sc;   // element strides of the input
     int relu, nsplit, mtiles, ntiles, ksteps, bm, bn, generic, groups;
     int bf3;              // MODE 0 only: split-precision matrix products (three bf16 planes per operand, six MFMAs per tile)
-    int lanepx;           // MODE 0 only: 1 = a K-step is 8 consecutive pixels of `Cin / 8` channels (one kernel ROW of the
+    int h3;               // MODE 0 only: two fp16 pieces per operand, three piece products per tile; .p[g].w = the
+                          // k_pack_weight_h3 image (two planes + the 1 / scale tail), not the f32 image
+    int lanepx;          // MODE 0 only: 1 = a K-step is 8 consecutive pixels of `Cin / 8` channels (one kernel ROW of the
                           // stem: Kw = 1, Cin = 32 virtual channels); horizontal padding is then per lane
     const float* wino_w[kMaxGroup];   // host side only: Winograd-packed weights per group (or null)
+    const float* h3_w[kMaxGroup];     // host side only: k_pack_weight_h3 images per group (or null: the site has none)
     const float* zeros;               // host side only: 64 zero floats for the all-DMA Winograd form (or null)
     // host side only, the FPN p2 fold of s2.0 (ConvPlan::fold; null where the site cannot fold): c2, the h3 images of Wc and W, p3,
     // bias table
@@ -61,6 +64,8 @@ struct LatArgs {
     int B, Ho, Wo, Cout, Npad, Kpad, groups, relu;
     unsigned bias_mask;                     // set by launch_lateral1x1: 0 = no bias (shift then points at readable memory)
     int parts;                              // workgroups per 128-pixel tile: each walks (groups * Cout / 32) / parts weight tiles
+    int h3;                                 // 1: wpl = k_pack_weight_h3's images ([2][Npad][Kpad] fp16 + 1 / scale), three fp16
+                                            // piece products per 16-deep k group
 };
 int launch_lateral1x1(const LatArgs& a, hipStream_t s);
 
@@ -234,6 +239,12 @@ int launch_pack_weight(const float* w_oihw, float* packed, int Cout, int Cin, in
 int launch_pack_weight_bf3(const float* w_oihw, float* packed, int Cout, int Cin, int Cinp, int Kh, int Kw, int Kwp, int Npad,
                            int Kpad, hipStream_t s);
 inline size_t conv_packed_floats(int Npad, int Kpad) { return ((size_t)Npad * Kpad * 5 / 2 + 63) / 64 * 64; }
+// The same image as two fp16 planes [2][Npad][Kpad] (Npad * Kpad floats) scaled by ONE power of two s per convolution (max |w| s
+// < 2^13, set on the device from max |w|), then a tail of 2 floats: 1 / s and max |w|'s bits — the weight operand of
+// k_conv_igemm's three-product form (ConvArgs::h3).  h3_packed_floats() = its room.
+int launch_pack_weight_h3(const float* w_oihw, float* packed, int Cout, int Cin, int Cinp, int Kh, int Kw, int Kwp, int Npad,
+                          int Kpad, hipStream_t s);
+inline size_t h3_packed_floats(int Npad, int Kpad) { return ((size_t)Npad * Kpad + 2 + 63) / 64 * 64; }
 int launch_nchw3_to_nhwc4(const float* x, float* out, int B, int HW, hipStream_t s);
 int launch_fold_bn(const float* gamma, const float* beta, const float* mean, const float* var, float eps, int C,
                    float* scale, float* shift, hipStream_t s);

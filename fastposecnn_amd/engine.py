@@ -113,6 +113,14 @@ class NetEngine:
             nat.check(rc, "fpc_net_force_fold")
         return rc
 
+    def force_direct_h3(self, on):
+        """Every site with the three-product direct form's image on that form (on = 1) or back on the f32 tiling (on = 0);
+        returns the number of sites changed."""
+        rc = self._lib.fpc_net_force_direct_h3(self._h, int(on))
+        if rc < 0:
+            nat.check(rc, "fpc_net_force_direct_h3")
+        return rc
+
     def force_pointwise(self, on):
         """Every eligible 1x1 site on k_conv1x1 (on = 1) or back on k_conv_igemm (on = 0); returns the number of sites changed."""
         rc = self._lib.fpc_net_force_pointwise(self._h, int(on))

@@ -43,8 +43,9 @@
 extern "C" {
 #endif
 
-/* 11 also covers the Bottleneck encoders (fpc_net_create_encoder, fpc_net_force_pointwise, fpc_conv2d's 4000 + variant) and
- * the FPN p2 fold (fpc_net_force_fold): additions only, every earlier entry point keeps its behaviour. */
+/* 11 also covers the Bottleneck encoders (fpc_net_create_encoder, fpc_net_force_pointwise, fpc_conv2d's 4000 + variant),
+ * the FPN p2 fold (fpc_net_force_fold) and the three-product direct form (fpc_net_force_direct_h3, fpc_conv2d's 6000 + split and 7000 + parts, fpc_net_graph_recorded):
+ * additions only, every earlier entry point keeps its behaviour. */
 #define FPC_ABI_VERSION 11
 
 #define FPC_OK 0
@@ -396,13 +397,22 @@ int fpc_net_autotune_next(fpc_net_t* net, int mode /* 0: minimise each conv's la
  * two terms every two-piece form drops — and the same tests hold it to the same bars.  At this level the autotuner also times
  * s2.0 with the FPN p2 level folded in (ResNet-18/34 encoders): conv3x3(W, L c2 + b + up2(p3)) as conv3x3(W L, c2) + conv3x3(W,
  * up2(p3)) + a bias table by border class, in one launch that never writes p2; it is kept only when it beats the p2 lateral and
- * s2.0 together.  s2.0 then reports -9 and the p2 lateral site nsplit = 5000 (no launch).
+ * s2.0 together.  s2.0 then reports -9 and the p2 lateral site nsplit = 5000 (no launch).  Level 3 also offers, beside the bf16 x 3
+ * tilings, the same k_conv_igemm tilings on two fp16 pieces per operand with three piece products (reported as 6000 + split-K
+ * factor) at the direct sites of ResNet-18/34 plans that do not run on Winograd: the stride-2 3x3 and 1x1 convolutions and the
+ * p5 / p4 / p3 laterals; and the pixel-resident lateral product on the same two pieces (reported as 7000 + parts).  The images
+ * of this form are packed only at level 3 (by fpc_net_load_params, or when the level is raised on a loaded plan, on the stream of the
+ * last load); their room is always reserved.  Weights: one power of two per convolution from max |w|, undone exactly before the epilogue; activations
+ * as they come, with the range of the -8 / -9 forms (2^-22 relative while |x| >= 2^-3, 2^-25 absolute below, saturation beyond
+ * 1.3e5 — finite).
  * The Python front end uses 3 unless HPARAM.ENGINE_SPLIT_F16_3P (then 2) or HPARAM.ENGINE_SPLIT_F16 (then 1) is False. */
 int fpc_net_set_split_precision(fpc_net_t* net, int on);
 /* HIP graph replay (default 0).  1: after autotuning, the frame-invariant launches of fpc_net_forward (everything
  * between the image conversion and the final upsample / class compression, ~57 kernels on the plan's workspace) are
  * captured once on the caller's stream and replayed with one hipGraphLaunch per frame. */
 int fpc_net_set_graph(fpc_net_t* net, int on);
+/* 1 while a recorded graph replays the frame (set_graph on and the frame was capturable), else 0. */
+int fpc_net_graph_recorded(const fpc_net_t* net);
 int fpc_net_conv_count(const fpc_net_t* net);
 int fpc_net_conv_plan(const fpc_net_t* net, int i, int* out5);
 /* Copies the convolution plans (tilings, split-K factors, kernel forms) of `src` into `dst`: same encoder, classes and frame
@@ -420,6 +430,11 @@ int fpc_net_force_pointwise(fpc_net_t* net, int on);
 /* s2.0 with the FPN p2 level folded in (on = 1, ResNet-18/34 plans; see fpc_net_set_split_precision) or on plain form -9 (on = 0).
  * Returns 1 when the plan changed, 0 when it already was so, or a negative code.  Drops the recorded graph. */
 int fpc_net_force_fold(fpc_net_t* net, int on);
+/* on = 1 (split level 3 only): every site that has the three-product direct form's image on that form — a pixel-resident lateral
+ * site on k_lateral1x1's two-piece build (7000 + parts), any other on its own implicit-GEMM tiling or the heuristic one (6000 +
+ * split); on = 0: those sites back on the heuristic f32 tiling.  Returns the number of sites changed or a negative code.  Drops the
+ * recorded graph. */
+int fpc_net_force_direct_h3(fpc_net_t* net, int on);
 /* FLOP of one forward over the batch under the current plans: out3 = {2 x MACs of the direct convolutions (what the
  * reference's cuDNN path executes), multiply-add FLOP the plans execute (Winograd sites: / 2.25), Winograd share}. */
 int fpc_net_flops(const fpc_net_t* net, double* out3);
@@ -436,7 +451,9 @@ int fpc_net_tensor(const fpc_net_t* net, const char* name, const float** ptr, in
  * summed by a second launch, 1000 + k split-precision (bf16 x 3) products, 2000 + parts the pixel-resident FPN lateral
  * product (1x1, Cin 64 / 128, bias + `up` epilogue), 3000 the weight-resident 7x7 / s2 stem (Cin = 4: NHWC4 image),
  * 4000 + variant the 1x1 GEMM (pad 0, stride 1 / 2, Cin and Cout multiples of 64, channel stride 1, no GroupNorm partials;
- * variant 0: 64-pixel tiles on 4 waves, 1: 128-pixel tiles on 8 waves; bf16 x 3 products). */
+ * variant 0: 64-pixel tiles on 4 waves, 1: 128-pixel tiles on 8 waves; bf16 x 3 products), 6000 + k (1 <= k < 100) the
+ * implicit GEMM with split-K factor k on two fp16 pieces per operand and three piece products (channel stride 1, Cin a multiple
+ * of 32; 6100 + k: split-K summed by a second launch), 7000 + parts the pixel-resident FPN lateral product on the same two pieces.  5000 is never a request: fpc_net_conv_plan's "folded away". */
 size_t fpc_conv2d_workspace_bytes(int B, int Ho, int Wo, int Cin, int Cout, int Kh, int Kw);
 /* the exact need of one request (same bm / bn / nsplit as the fpc_conv2d call): <= the bound above, which reserves 32
  * split-K slices of the whole output; fpc_conv2d accepts either size */
