@@ -50,6 +50,7 @@ struct ConvPlan {
     int pw = 0;              // > 0: k_conv1x1 (pointwise.hip), variant pw - 1 (net_kernels.hpp: PwArgs::variant)
     int fold = 0;            // s2.0 with wino 9 only: the FPN p2 level folded into the launch (wino_h3.hip, FOLD); no p2 lateral runs
     int h3 = 0;              // k_conv_igemm on two fp16 pieces, three piece products (ConvArgs::h3; PackedConv::h3_ok sites)
+    int pool = 0;            // the stem site only (with stem > 0): k_stem_pool_h3 writes the pooled tensor, no stem output, no max-pool launch
 };
 
 // the 7x7 / stride-2 / pad-3 stem in its row-per-K-step layout (NHWC4 image, 8 taps x 4 channels per kernel row, K = 224) with a
@@ -198,6 +199,7 @@ struct fpc_net {
     // one scale (wino_h3.hip: launch_wino_pack_h3_pair) and the border-class bias table
     bool h3_packed = false;               // the PackedConv::h3_ok images hold the current weights (split level 3, pack_h3_images)
     hipStream_t load_stream = nullptr;    // stream of the last fpc_net_load_params
+    size_t stem_h3_off = 0;               // the stem's k_pack_weight_h3 image (k_stem_pool_h3; packed with the h3_ok images)
     bool fold_ok = false;
     size_t fold_wc_off[4] = {}, fold_img1_off[4] = {}, fold_img2_off[4] = {}, fold_tab_off[4] = {};
 
@@ -358,6 +360,7 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
             c.h3_off = n->alloc(h3_packed_floats(c.Npad, c.Kpad));
         }
     }
+    n->stem_h3_off = n->alloc(h3_packed_floats(n->convs[n->c_stem].Npad, n->convs[n->c_stem].Kpad));      // every encoder shares the stem
     n->zeros_off = n->alloc(64);
     n->tickets_off = n->alloc(kConvTickets);
     n->packed_floats = n->bump;
@@ -484,6 +487,9 @@ static int pack_h3_images(fpc_net* n, hipStream_t s) {
             int rc = launch_pack_weight_h3(n->pptr[c.p_w], n->ws + c.h3_off, c.Cout, c.Cin, c.Cinp, c.Kh, c.Kw, c.Kwp, c.Npad, c.Kpad, s);
             if (rc) return rc;
         }
+    const PackedConv& st = n->convs[n->c_stem];
+    int rc = launch_pack_weight_h3(n->pptr[st.p_w], n->ws + n->stem_h3_off, st.Cout, st.Cin, st.Cinp, st.Kh, st.Kw, st.Kwp, st.Npad, st.Kpad, s);
+    if (rc) return rc;
     n->h3_packed = true;
     return FPC_OK;
 }
@@ -806,6 +812,19 @@ int run_conv(fpc_net* n, ConvArgs& a, int groups, int ci, hipStream_t s) {
 
 #define FPC_TRY(x) do { int rc__ = (x); if (rc__) return rc__; } while (0)
 
+// the stem site's fused launch: image -> pooled tensor (k_stem_pool_h3).  `a` as the stem site fills it; FPC_EINVAL where the shape
+// is not eligible (launch_stem_pool_h3) or the h3 image is not there
+static int launch_stem_pool(const ConvArgs& a, const float* h3_image, float* pool, int Hp, int Wp, hipStream_t s) {
+    if (!h3_image || !stem_ok(a)) return FPC_EINVAL;
+    StemPoolArgs t;
+    memset(&t, 0, sizeof(t));
+    t.in = a.p[0].in; t.wpl = reinterpret_cast<const unsigned short*>(h3_image); t.out = pool;
+    t.scale = a.p[0].scale; t.shift = a.p[0].shift;
+    t.B = a.B; t.Hi = a.Hi; t.Wi = a.Wi; t.Ho = a.Ho; t.Wo = a.Wo; t.Hp = Hp; t.Wp = Wp; t.Npad = a.Npad; t.Kpad = a.Kpad; t.relu = a.relu;
+    t.band = kStemPoolBand; t.grid = 256;
+    return launch_stem_pool_h3(t, s);
+}
+
 // Everything between the NCHW -> NHWC4 conversion of the caller's image and the final upsample / class
 // compression into the caller's tensors: ~57 launches that touch only the plan's workspace and parameters, i.e.
 // identical every frame — the part that can be replayed as a HIP graph.
@@ -826,10 +845,40 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
                        1, true, 0);
         a.Cin = 8 * c.Cinp; a.Kw = 1; a.K = c.K; a.lanepx = 1;
         a.p[0] = ConvPtrs{ws + n->a_img4.off, ws + c.w_off, ws + n->a_stem.off, ws + c.scale_off, ws + c.shift_off, nullptr, nullptr, nullptr};
-        FPC_TRY(run_conv(n, a, 1, n->c_stem, s));
+        const float* h3img = n->h3_packed ? ws + n->stem_h3_off : nullptr;
+        auto pool_launch = [&]() {
+            return launch_maxpool3x3s2(ws + n->a_stem.off, ws + n->a_pool.off, B, n->a_stem.H, n->a_stem.W, 64, n->a_pool.H, n->a_pool.W, s);
+        };
+        if (n->cplan[n->c_stem].pool && !n->tuning) {      // one launch to the pooled tensor: a_stem is not written
+            FPC_TRY(launch_stem_pool(a, h3img, ws + n->a_pool.off, n->a_pool.H, n->a_pool.W, s));
+        } else {
+            n->cplan[n->c_stem].pool = 0;
+            FPC_TRY(run_conv(n, a, 1, n->c_stem, s));
+            FPC_TRY(pool_launch());
+            // level 3: the fused launch against the site's best plan AND the max-pool together (it replaces both), timed as the p2
+            // fold is; the whole chip: score = ms.  Kept only when it beats them
+            if (n->tuning && n->split_precision >= 3 && launch_stem_pool(a, h3img, ws + n->a_pool.off, n->a_pool.H, n->a_pool.W, s) == FPC_OK) {
+                hipEvent_t e0, e1;
+                if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return FPC_ELAUNCH;
+                const ConvPlan cur = n->cplan[n->c_stem];
+                float ms_pair = 1e30f, ms_fused = 1e30f;
+                for (int rep = 0; rep < 6; ++rep) {
+                    const bool fused = rep & 1;
+                    float t = 0.f;
+                    bool timed = hipEventRecord(e0, s) == hipSuccess &&
+                                 (fused ? launch_stem_pool(a, h3img, ws + n->a_pool.off, n->a_pool.H, n->a_pool.W, s) == FPC_OK
+                                        : (launch_conv_plan(a, cur, 1, s) == FPC_OK && pool_launch() == FPC_OK)) &&
+                                 hipEventRecord(e1, s) == hipSuccess && hipEventSynchronize(e1) == hipSuccess &&
+                                 hipEventElapsedTime(&t, e0, e1) == hipSuccess;
+                    if (timed && fused && t < ms_fused) ms_fused = t;
+                    if (timed && !fused && t < ms_pair) ms_pair = t;
+                }
+                (void)hipEventDestroy(e0);
+                (void)hipEventDestroy(e1);
+                if (ms_fused < ms_pair) { ConvPlan q; q.stem = 256; q.pool = 1; n->cplan[n->c_stem] = q; }
+            }
+        }
     }
-    FPC_TRY(launch_maxpool3x3s2(ws + n->a_stem.off, ws + n->a_pool.off, B, n->a_stem.H, n->a_stem.W, 64, n->a_pool.H,
-                                n->a_pool.W, s));
     // encoder stages
     Act cur = n->a_pool;
     Act feat[4];
@@ -1122,7 +1171,7 @@ extern "C" int fpc_net_conv_plan(const fpc_net_t* n, int i, int* out5) {
     if (!n || !out5 || i < 0 || i >= (int)n->convs.size()) return FPC_EINVAL;
     out5[0] = n->cplan[i].bm; out5[1] = n->cplan[i].bn; out5[2] = n->cplan[i].wino ? -n->cplan[i].wino : n->cplan[i].nsplit;
     if (n->cplan[i].lat) { out5[0] = 128; out5[1] = 32; out5[2] = 2000 + n->cplan[i].lat; }      // k_lateral1x1 (fpc_conv2d's hook value)
-    if (n->cplan[i].stem) { out5[0] = 64; out5[1] = 64; out5[2] = 3000; }                        // k_stem7x7
+    if (n->cplan[i].stem) { out5[0] = 64; out5[1] = 64; out5[2] = n->cplan[i].pool ? 3100 : 3000; }      // k_stem7x7 / k_stem_pool_h3 (with the max-pool)
     if (n->cplan[i].pw) { out5[0] = pw_tile_pixels(n->cplan[i].pw - 1); out5[1] = 64; out5[2] = 4000 + n->cplan[i].pw - 1; }      // k_conv1x1
     // the three-product form: k_conv_igemm 6000 + split (fused or not, as the plain tilings), k_lateral1x1 7000 + parts
     if (n->cplan[i].h3) out5[2] = n->cplan[i].lat ? 7000 + n->cplan[i].lat : 6000 + n->cplan[i].nsplit;
@@ -1208,6 +1257,21 @@ extern "C" int fpc_net_force_direct_h3(fpc_net_t* n, int on) {
     return changed;
 }
 
+// The stem and its max-pool as one launch (on = 1: k_stem_pool_h3, split level 3 only — its weight image is packed there — and a
+// shape the launcher takes: conv output rows even, columns a multiple of 64) or back on k_stem7x7 + k_maxpool3x3s2 (on = 0).  Returns 1
+// when the plan changed, 0 when it was already so, or a negative code.  Drops the recorded graph.
+extern "C" int fpc_net_force_stem_pool(fpc_net_t* n, int on) {
+    if (!n || on < 0 || on > 1 || (on && !n->h3_packed)) return FPC_EINVAL;
+    if (on && ((n->a_stem.H & 1) || (n->a_stem.W & 63) || (long long)n->H * n->W * 16 >= (1LL << 31))) return FPC_EINVAL;
+    ConvPlan& p = n->cplan[n->c_stem];
+    if (p.pool == on) return 0;
+    ConvPlan q;
+    q.stem = 256; q.pool = on;
+    p = q;
+    if (n->graph_exec) { (void)hipGraphExecDestroy(n->graph_exec); n->graph_exec = nullptr; }
+    return 1;
+}
+
 // Plans of `src` -> `dst` (same encoder, classes, H, W; batch sizes may differ): runs a small batch on the tilings, split-K
 // factors and kernel forms a larger one was autotuned to (tests: the headline configuration's kernels against float64 on two
 // frames).  A plan whose split-K partials do not fit dst's workspace keeps dst's own.  Drops dst's recorded graph.
@@ -1223,7 +1287,7 @@ extern "C" int fpc_net_copy_plans(fpc_net_t* dst, const fpc_net_t* src) {
         const ConvPlan& q = src->cplan[i];
         if (splitk_floats_for(q, dst->c_groups[i] ? dst->c_groups[i] : 1, dst->B, dst->convs[i].Npad) > dst->splitk_floats) continue;
         if (q.nsplit > 1 && q.fused && !can_fuse(q, dst->c_groups[i] ? dst->c_groups[i] : 1, dst->B)) continue;
-        if (q.h3 && !dst->h3_packed) continue;      // dst is not at split level 3: no three-product images
+        if ((q.h3 || q.pool) && !dst->h3_packed) continue;      // dst is not at split level 3: no three-product images
         dst->cplan[i] = q;
     }
     dst->tuned = true;
@@ -1257,7 +1321,10 @@ extern "C" int fpc_net_tensor(const fpc_net_t* n, const char* name, const float*
     if (!n || !n->ws || !name || !ptr || !H || !W || !C) return FPC_EINVAL;
     Act t;
     bool ok = false;
-    if (!strcmp(name, "stem")) { t = n->a_stem; ok = true; }
+    if (!strcmp(name, "stem")) {
+        if (n->cplan[n->c_stem].pool) return FPC_EINVAL;      // fused with the max-pool: never written
+        t = n->a_stem; ok = true;
+    }
     else if (!strcmp(name, "pool")) { t = n->a_pool; ok = true; }
     else if (name[0] == 'c' && name[1] >= '2' && name[1] <= '5' && !name[2]) { t = n->a_blk_y[name[1] - '2'].back(); ok = true; }
     else if (name[0] == 'd' && name[1] >= '0' && name[1] <= '3' && name[2] == '.') {
@@ -1272,6 +1339,16 @@ extern "C" int fpc_net_tensor(const fpc_net_t* n, const char* name, const float*
     }
     if (!ok) return FPC_EINVAL;
     *ptr = n->ws + t.off; *H = t.H; *W = t.W; *C = t.C;
+    return FPC_OK;
+}
+
+// k_stem_pool_h3's wave tasks for a conv output of Ho x Wo (host arithmetic, no device): out4 = bands, strips per frame, conv outputs
+// computed per frame (band overlap rows and halo tiles included), conv outputs that exist.  FPC_EINVAL for a shape the launcher refuses.
+extern "C" int fpc_stem_pool_tasks(int Ho, int Wo, int64_t* out4) {
+    if (!out4 || Ho < 2 || (Ho & 1) || Wo < 64 || (Wo & 63)) return FPC_EINVAL;
+    long long o[4];
+    stem_pool_tasks(Ho, Wo, kStemPoolBand, o);
+    for (int i = 0; i < 4; ++i) out4[i] = o[i];
     return FPC_OK;
 }
 
@@ -1300,9 +1377,9 @@ extern "C" int fpc_conv2d_plan(int B, int Ho, int Wo, int Cin, int Cout, int Kh,
 
 namespace {
 // the hooks folded into fpc_conv2d's `nsplit` argument
-struct Conv2dRequest { int nsplit; bool bf3, two_launch, wino; int lat; bool stem; int pw; bool h3; };
+struct Conv2dRequest { int nsplit; bool bf3, two_launch, wino; int lat; bool stem; int pw; bool h3; bool pool; };
 Conv2dRequest conv2d_request(int nsplit) {
-    Conv2dRequest r{nsplit, false, false, false, 0, false, 0, false};
+    Conv2dRequest r{nsplit, false, false, false, 0, false, 0, false, false};
     if (r.nsplit >= 7000 && r.nsplit < 8000) { r.lat = r.nsplit - 7000; r.h3 = true; r.nsplit = 1; return r; }      // 7000 + parts = k_lateral1x1 on two fp16 pieces
     if (r.nsplit >= 6000 && r.nsplit < 6200) {      // 6000 + split = k_conv_igemm's three-product form (fused split-K), 6100 + split: two launches
         r.h3 = true; r.nsplit -= 6000;
@@ -1310,6 +1387,7 @@ Conv2dRequest conv2d_request(int nsplit) {
         return r;
     }
     if (r.nsplit >= 4000) { r.pw = r.nsplit - 4000 + 1; r.bf3 = true; r.nsplit = 1; return r; }   // 4000 + variant = k_conv1x1 (pointwise.hip)
+    if (r.nsplit == 3100) { r.stem = true; r.pool = true; r.h3 = true; r.nsplit = 1; return r; }     // 3100 = k_stem_pool_h3: NHWC4 input, `out` = the POOLED tensor
     if (r.nsplit == 3000) { r.stem = true; r.bf3 = true; r.nsplit = 1; return r; }                   // 3000 = k_stem7x7 (stem.hip): NHWC4 input
     if (r.nsplit >= 2000) { r.lat = r.nsplit - 2000; r.bf3 = true; r.nsplit = 1; return r; }      // 2000 + parts = k_lateral1x1 (lateral.hip)
     if (r.nsplit >= 1000) { r.bf3 = true; r.nsplit -= 1000; }          // 1000 + split = split-precision matrix products
@@ -1342,6 +1420,7 @@ ConvPlan conv2d_plan_for(int B, int Ho, int Wo, int Cin, int Cout, int Kh, int K
     if (r.two_launch) p.fused = 0;
     p.lat = r.lat;
     p.stem = r.stem ? 256 : 0;
+    p.pool = r.pool ? 1 : 0;
     p.pw = r.pw;
     return p;
 }
@@ -1380,6 +1459,16 @@ extern "C" int fpc_conv2d(const float* in, int64_t sb, int64_t sh, int64_t sw, i
             sb != (int64_t)4 * Hi * Wi || res || up || gn_part)
             return FPC_EINVAL;
         c.Kwp = 8; c.K = 4 * 7 * 8; c.Kpad = 224;
+        if (rq.pool) {      // conv + BN + ReLU + max-pool 3x3 / 2 / 1 in one launch: out is [B][Ho / 2][Wo / 2][64]
+            FPC_TRY(launch_pack_weight_h3(w_oihw, packed, Cout, Cin, Cin, Kh, Kw, c.Kwp, c.Npad, c.Kpad, s));
+            fpc_net tmp1;
+            tmp1.B = B; tmp1.ws = packed; tmp1.splitk_off = lay.packed;
+            ConvArgs a1;
+            fill_conv_args(&tmp1, a1, c, p, Hi, Wi, Ho, Wo, sb, sh, sw, sc, relu != 0, 0);
+            a1.Cin = 8 * c.Cinp; a1.Kw = 1; a1.K = c.K; a1.lanepx = 1;
+            a1.p[0] = ConvPtrs{in, packed, out, scale, shift, nullptr, nullptr, nullptr};
+            return launch_stem_pool(a1, packed, out, Ho / 2, Wo / 2, s);
+        }
         FPC_TRY(launch_pack_weight_bf3(w_oihw, packed, Cout, Cin, Cin, Kh, Kw, c.Kwp, c.Npad, c.Kpad, s));
         fpc_net tmp0;
         tmp0.B = B; tmp0.ws = packed; tmp0.splitk_off = lay.packed;

@@ -99,6 +99,23 @@ struct StemArgs {
 };
 int launch_stem7x7(const StemArgs& a, hipStream_t s);
 
+// the stem and its 3x3 / stride-2 / pad-1 max-pool as one launch on three fp16 piece products (stem.hip, k_stem_pool_h3): the
+// stem's own output is never written.  Eligible: launch_stem7x7's shapes with even Ho / Wo and ReLU on (the pool's zero padding)
+struct StemPoolArgs {
+    const float* in;             // [B][Hi][Wi][4] f32 (4th channel 0), contiguous
+    const unsigned short* wpl;   // k_pack_weight_h3's image: [2][Npad][Kpad = 224] fp16, k = (kh * 8 + tap) * 4 + channel, then 1 / scale
+    float* out;                  // the POOLED tensor [B][Hp = Ho / 2][Wp = Wo / 2][64]; every element written exactly once
+    const float* scale;          // folded BatchNorm, or null
+    const float* shift;
+    int B, Hi, Wi, Ho, Wo, Hp, Wp, Npad, Kpad, relu;
+    int band;                    // pool rows per wave task (kStemPoolBand); a shorter last band is fine
+    int grid;                    // persistent workgroups (0: one per CU of an MI355X)
+};
+constexpr int kStemPoolBand = 10;
+int launch_stem_pool_h3(const StemPoolArgs& a, hipStream_t s);
+// out4 = bands, strips per frame, conv outputs the launch computes per frame, conv outputs that exist (Ho x Wo)
+void stem_pool_tasks(int Ho, int Wo, int band, long long out4[4]);
+
 constexpr int kMaxGnSites = 4;    // segmentation sites finalized by one launch (x kMaxGroup decoders each)
 struct GnFinArgs {
     const float* gn_part[kMaxGnSites * kMaxGroup];   // [site * kMaxGroup + decoder]: [B][P][C][2]

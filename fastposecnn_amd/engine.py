@@ -121,6 +121,14 @@ class NetEngine:
             nat.check(rc, "fpc_net_force_direct_h3")
         return rc
 
+    def force_stem_pool(self, on):
+        """The stem and its max-pool as one launch (on = 1, split level 3) or back on stem kernel + max-pool (on = 0); returns 1
+        when the plan changed."""
+        rc = self._lib.fpc_net_force_stem_pool(self._h, int(on))
+        if rc < 0:
+            nat.check(rc, "fpc_net_force_stem_pool")
+        return rc
+
     def force_pointwise(self, on):
         """Every eligible 1x1 site on k_conv1x1 (on = 1) or back on k_conv_igemm (on = 0); returns the number of sites changed."""
         rc = self._lib.fpc_net_force_pointwise(self._h, int(on))

@@ -45,6 +45,7 @@ extern "C" {
 
 /* 11 also covers the Bottleneck encoders (fpc_net_create_encoder, fpc_net_force_pointwise, fpc_conv2d's 4000 + variant),
  * the FPN p2 fold (fpc_net_force_fold) and the three-product direct form (fpc_net_force_direct_h3, fpc_conv2d's 6000 + split and 7000 + parts, fpc_net_graph_recorded):
+ * and the stem fused with its max-pool (fpc_net_force_stem_pool, fpc_stem_pool_tasks, fpc_conv2d's 3100):
  * additions only, every earlier entry point keeps its behaviour. */
 #define FPC_ABI_VERSION 11
 
@@ -435,6 +436,17 @@ int fpc_net_force_fold(fpc_net_t* net, int on);
  * split); on = 0: those sites back on the heuristic f32 tiling.  Returns the number of sites changed or a negative code.  Drops the
  * recorded graph. */
 int fpc_net_force_direct_h3(fpc_net_t* net, int on);
+/* on = 1 (split level 3 only; conv output rows even, columns a multiple of 64): the 7x7 stem and its 3x3 / 2 max-pool as ONE launch
+ * on three fp16 piece products (csrc/stem.hip, k_stem_pool_h3; fpc_net_conv_plan reports 3100 at the stem site): the stem's own
+ * output is never written, so fpc_net_tensor("stem") returns FPC_EINVAL while it is chosen ("pool" stays valid).  on = 0: back on
+ * the weight-resident stem kernel (3000) followed by the max-pool launch.  At split level 3 the autotuner offers the fused launch
+ * itself and keeps it where it beats stem + max-pool together.  Returns 1 when the plan changed, 0 when it was already so, or a
+ * negative code.  Drops the recorded graph. */
+int fpc_net_force_stem_pool(fpc_net_t* net, int on);
+/* k_stem_pool_h3's task arithmetic for a stem output of Ho x Wo (host only, no device): out4 = bands of 10 pool rows, strips of 64
+ * conv columns, conv outputs one frame's launch computes (the band overlap rows and the halo tiles included), conv outputs that
+ * exist (Ho * Wo).  FPC_EINVAL for a shape the fused launch does not take. */
+int fpc_stem_pool_tasks(int Ho, int Wo, int64_t* out4);
 /* FLOP of one forward over the batch under the current plans: out3 = {2 x MACs of the direct convolutions (what the
  * reference's cuDNN path executes), multiply-add FLOP the plans execute (Winograd sites: / 2.25), Winograd share}. */
 int fpc_net_flops(const fpc_net_t* net, double* out3);
@@ -450,6 +462,8 @@ int fpc_net_tensor(const fpc_net_t* net, const char* name, const float** ptr, in
  * `nsplit` also selects the engine's other kernels for tests: -1..-5 Winograd forms (-5 split precision), 100 + k split-K
  * summed by a second launch, 1000 + k split-precision (bf16 x 3) products, 2000 + parts the pixel-resident FPN lateral
  * product (1x1, Cin 64 / 128, bias + `up` epilogue), 3000 the weight-resident 7x7 / s2 stem (Cin = 4: NHWC4 image),
+ * 3100 the same stem fused with its 3x3 / 2 / pad-1 max-pool on three fp16 piece products (`out` is then the POOLED tensor
+ * [B][Ho / 2][Wo / 2][64]; relu must be on, Ho even, Wo a multiple of 64),
  * 4000 + variant the 1x1 GEMM (pad 0, stride 1 / 2, Cin and Cout multiples of 64, channel stride 1, no GroupNorm partials;
  * variant 0: 64-pixel tiles on 4 waves, 1: 128-pixel tiles on 8 waves; bf16 x 3 products), 6000 + k (1 <= k < 100) the
  * implicit GEMM with split-K factor k on two fp16 pieces per operand and three piece products (channel stride 1, Cin a multiple
