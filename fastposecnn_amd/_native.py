@@ -86,6 +86,9 @@ _SIGNATURES = {
     "fpc_net_force_direct_h3": (_i, [_vp, _i]),
     "fpc_net_force_stem_pool": (_i, [_vp, _i]),
     "fpc_stem_pool_tasks": (_i, [_i, _i, ctypes.POINTER(_i64)]),
+    "fpc_wino_pack_geometry": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(_i64)]),
+    "fpc_net_set_wino_pack": (_i, [_vp, _i]),
+    "fpc_net_wino_blocks": (_i64, [_vp]),
     "fpc_net_graph_recorded": (_i, [_vp]),
     "fpc_net_flops": (_i, [_vp, ctypes.POINTER(ctypes.c_double)]),
     "fpc_net_tensor": (_i, [_vp, ctypes.c_char_p, ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i),

@@ -190,6 +190,8 @@ struct fpc_net {
     int merge_split = -1;         // -1: two passes unless FPC_MERGE_SPLIT=0, 0: k_merge_head (one pass), 1: two passes
     size_t splitk_off = 0, splitk_floats = 0;
     int use_graph = 0;            // replay the frame-invariant launches as a HIP graph (fpc_net_set_graph)
+    long long wino_blocks = 0;    // workgroups of the form-9 launches of the last forward that launched its kernels (fpc_net_wino_blocks)
+    int wino_pack = 1;            // form-9 launches cut their patches out of canvas rows of several frames where that saves patches (fpc_net_set_wino_pack)
     int split_precision = 0;      // autotuning may pick the bf16 x 3 form of a direct convolution (fpc_net_set_split_precision)
     hipGraphExec_t graph_exec = nullptr;
     size_t zeros_off = 0;         // 64 zero floats (DMA source for out-of-image positions)
@@ -454,6 +456,8 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
         int HoWo = fh[seg_level[i]] * fw[seg_level[i]];
         plan(n->dec[0].seg[i], HoWo, 4);
         n->gn_P[i] = cdiv(HoWo, 128) * 4;      // upper bound of mtiles*bm/32 over the tilings
+        // ... and of the packed form-9 launch's records per frame (a seam patch writes one per frame it touches)
+        n->gn_P[i] = std::max(n->gn_P[i], wino_pack_geometry(fh[seg_level[i]], fw[seg_level[i]], B, n->convs[n->dec[0].seg[i]].Cin, true).gn_rows);
         for (int d = 0; d < 4; ++d) {
             n->gn_part_off[d][i] = n->alloc((size_t)B * n->gn_P[i] * 128 * 2);
             n->gn_aff_off[d][i] = n->alloc((size_t)B * 128 * 2);
@@ -503,6 +507,19 @@ extern "C" int fpc_net_set_split_precision(fpc_net_t* n, int on) {
 
 // 1 while a recorded graph replays the frame (fpc_net_set_graph, after the first frame that could be captured), else 0
 extern "C" int fpc_net_graph_recorded(const fpc_net_t* n) { return n && n->use_graph && n->graph_exec ? 1 : 0; }
+
+// on = 1 (the default): a form-9 (k_conv_wino_h3) launch lays the frames of a small map side by side and cuts its 8 x 8 tile patches
+// out of that canvas wherever this needs fewer patches (wino_pack_geometry); on = 0: one frame per patch row, as before.  The plans
+// do not change (a site on form 9 reports -9 either way); the recorded graph is dropped.
+extern "C" int fpc_net_set_wino_pack(fpc_net_t* n, int on) {
+    if (!n || on < 0 || on > 1) return FPC_EINVAL;
+    if (n->wino_pack != on && n->graph_exec) { (void)hipGraphExecDestroy(n->graph_exec); n->graph_exec = nullptr; }
+    n->wino_pack = on;
+    return FPC_OK;
+}
+
+// workgroups of all form-9 launches of the last forward that launched (or captured) its kernels; -1 without a plan
+extern "C" int64_t fpc_net_wino_blocks(const fpc_net_t* n) { return n ? (int64_t)n->wino_blocks : -1; }
 
 extern "C" int fpc_net_set_graph(fpc_net_t* n, int on) {
     if (!n) return FPC_EINVAL;
@@ -595,6 +612,7 @@ void fill_conv_args(const fpc_net* n, ConvArgs& a, const PackedConv& c, const Co
     a.zeros = n->ws + n->zeros_off;
     a.tickets = (int*)(n->ws + n->tickets_off);
     a.fused = p.fused;
+    a.wino_pack = n->wino_pack;
 }
 
 int launch_conv_plan(ConvArgs& a, const ConvPlan& p, int groups, hipStream_t s) {
@@ -661,6 +679,11 @@ int launch_conv_plan(ConvArgs& a, const ConvPlan& p, int groups, hipStream_t s) 
         w.B = a.B; w.H = a.Ho; w.W = a.Wo; w.Cin = a.Cin; w.Cout = a.Cout; w.relu = a.relu;
         w.waves = (p.wino == 2 || p.wino == 4 || p.wino == 5 || p.wino == 7 || p.wino == 8 || p.wino == 9) ? 8 : 4;
         w.tbx = cdiv(cdiv(a.Wo, 2), 8); w.tby = cdiv(cdiv(a.Ho, 2), w.waves);
+        if (p.wino == 9) {      // packing: the same workgroups, fewer of them — a property of the launch, not of the plan
+            const WinoPackGeom q = wino_pack_geometry(a.Ho, a.Wo, a.B, a.Cin, a.wino_pack && !p.fold);
+            if (q.G > 1) { w.pack = q.G; w.tbx = q.tbx; w.pack_rx = q.rx; }
+            a.wino_blocks = q.patches * (a.Cout / 64) * groups;
+        }
         if (p.fold) {      // c2 on Wc's image + up2(p3) on W's (the p2 input of .p[g] is not read)
             if (p.wino != 9 || !a.fold_in) return FPC_EINVAL;
             for (int g = 0; g < groups; ++g) {
@@ -699,7 +722,8 @@ int launch_conv_plan(ConvArgs& a, const ConvPlan& p, int groups, hipStream_t s) 
 }
 
 // number of GroupNorm partial rows per image a plan writes
-int plan_gn_rows(const ConvPlan& p, int Ho, int Wo) {
+int plan_gn_rows(const ConvPlan& p, int Ho, int Wo, int B, int Cin, int pack) {
+    if (p.wino == 9) return wino_pack_geometry(Ho, Wo, B, Cin, pack && !p.fold).gn_rows;
     return p.wino ? cdiv(cdiv(Wo, 2), 8) * cdiv(cdiv(Ho, 2), (p.wino == 2 || p.wino == 4 || p.wino == 5 || p.wino == 7 || p.wino == 8 || p.wino == 9) ? 8 : 4) : p.mtiles * p.bm / 32;
 }
 
@@ -772,6 +796,7 @@ int run_conv(fpc_net* n, ConvArgs& a, int groups, int ci, hipStream_t s) {
                 double nblk = q.stem ? 512.0      // (a persistent 512-thread, 86 KB workgroup per CU: the whole chip, whatever its grid)
                               : q.lat ? (double)cdiv(a.Ho * a.Wo, 128) * a.B * q.lat
                               : q.pw ? (double)cdiv(a.B * a.Ho * a.Wo, pw_tile_pixels(q.pw - 1)) * (a.Cout / 64) * groups * q.pw      // (8-wave workgroups count twice)
+                              : q.wino == 9 ? (double)wino_pack_geometry(a.Ho, a.Wo, a.B, a.Cin, a.wino_pack && !q.fold).patches * (a.Cout / 64) * groups
                               : q.wino ? (double)cdiv(cdiv(a.Wo, 2), 8) * cdiv(cdiv(a.Ho, 2), (q.wino == 2 || q.wino == 4 || q.wino == 5 || q.wino == 7 || q.wino == 8 || q.wino == 9) ? 8 : 4) * a.B * (a.Cout / (q.wino == 6 ? 128 : 64)) * groups
                                      : (double)q.mtiles * q.ntiles * q.nsplit * a.B * groups;
                 double slots = 256.0 * ((q.wino == 2 || q.wino == 4 || q.wino == 5 || q.wino == 6 || q.wino == 7 || q.wino == 8 || q.wino == 9) ? 1.0 : 2.0);
@@ -805,7 +830,9 @@ int run_conv(fpc_net* n, ConvArgs& a, int groups, int ci, hipStream_t s) {
         n->cplan[ci] = best;
     }
     ConvPlan p = n ? n->cplan[ci] : ConvPlan{a.bm, a.bn, a.nsplit, a.mtiles, a.ntiles, 0, a.bf3, a.fused};
-    return launch_conv_plan(a, p, groups, s);
+    const int rc = launch_conv_plan(a, p, groups, s);
+    if (n && !rc && p.wino == 9) n->wino_blocks += a.wino_blocks;
+    return rc;
 }
 
 }  // namespace
@@ -830,6 +857,7 @@ static int launch_stem_pool(const ConvArgs& a, const float* h3_image, float* poo
 // identical every frame — the part that can be replayed as a HIP graph.
 static int forward_middle(fpc_net* n, hipStream_t s) {
     float* ws = n->ws;
+    n->wino_blocks = 0;
     const int B = n->B, H = n->H, W = n->W;
     ConvArgs a;
     auto nhwc = [&](const Act& t, long long& sb, long long& sh, long long& sw, long long& sc) {
@@ -1009,7 +1037,7 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
                 g.beta[k * kMaxGroup + d] = n->pptr[n->dec[d].p_gn[si] + 1];
                 g.affine[k * kMaxGroup + d] = ws + n->gn_aff_off[d][si];
             }
-            g.P[k] = plan_gn_rows(n->cplan[n->dec[0].seg[si]], o0.H, o0.W);
+            g.P[k] = plan_gn_rows(n->cplan[n->dec[0].seg[si]], o0.H, o0.W, B, n->convs[n->dec[0].seg[si]].Cin, n->wino_pack);
             g.count[k] = (long long)o0.H * o0.W * 4;
             ++k;
         }
@@ -1352,6 +1380,18 @@ extern "C" int fpc_stem_pool_tasks(int Ho, int Wo, int64_t* out4) {
     return FPC_OK;
 }
 
+// k_conv_wino_h3's launch geometry for a 3x3 / stride-1 site with output H x W, batch B and Cin input channels (host arithmetic, no
+// device; fold = 1: the folded s2.0, which never packs): out8 = frames per canvas row G (1: plain), patches per full canvas row,
+// patch rows, launched patches per (64-channel block, decoder), their tile slots, tiles that exist, GroupNorm records per frame,
+// GroupNorm records per frame and patch row.
+extern "C" int fpc_wino_pack_geometry(int H, int W, int B, int Cin, int fold, int64_t* out8) {
+    if (!out8 || H < 1 || W < 1 || B < 1 || Cin < 1) return FPC_EINVAL;
+    const WinoPackGeom q = wino_pack_geometry(H, W, B, Cin, !fold);
+    out8[0] = q.G; out8[1] = q.tbx; out8[2] = q.tby; out8[3] = q.patches; out8[4] = q.slots; out8[5] = q.tiles; out8[6] = q.gn_rows;
+    out8[7] = q.rx;
+    return FPC_OK;
+}
+
 // ---- stand-alone convolution (unit tests / micro-benchmarks of k_conv_igemm) -----------------
 extern "C" size_t fpc_conv2d_workspace_bytes(int B, int Ho, int Wo, int Cin, int Cout, int Kh, int Kw) {
     int K = Cin * Kh * Kw, Kpad = cdiv(K, kConvBK) * kConvBK, Npad = cdiv(Cout, kConvNAlign) * kConvNAlign;
@@ -1369,17 +1409,20 @@ extern "C" int fpc_conv2d_plan(int B, int Ho, int Wo, int Cin, int Cout, int Kh,
     if (nsplit >= 2000) nsplit = 1;          // k_lateral1x1 / k_stem7x7 / k_conv1x1: no split-K, no GroupNorm rows
     if (nsplit >= 1000) nsplit -= 1000;      // fpc_conv2d's split-precision / two-launch hooks do not change the tiling
     if (nsplit >= 100) nsplit -= 100;
+    const int pack = nsplit == -10;      // form 9 on the packed geometry
+    if (pack) nsplit = -9;
     ConvPlan p = plan_conv(Ho * Wo, B, Cout, Kpad / kConvBK, 1, bm, bn, nsplit);
-    if (nsplit <= -1 && nsplit >= -9) { p.wino = -nsplit; p.nsplit = nsplit; }
-    out4[0] = p.bm; out4[1] = p.bn; out4[2] = p.nsplit; out4[3] = plan_gn_rows(p, Ho, Wo);
+    if (nsplit <= -1 && nsplit >= -9) { p.wino = -nsplit; p.nsplit = pack ? -10 : nsplit; }
+    out4[0] = p.bm; out4[1] = p.bn; out4[2] = p.nsplit; out4[3] = plan_gn_rows(p, Ho, Wo, B, Cin, pack);
     return FPC_OK;
 }
 
 namespace {
 // the hooks folded into fpc_conv2d's `nsplit` argument
-struct Conv2dRequest { int nsplit; bool bf3, two_launch, wino; int lat; bool stem; int pw; bool h3; bool pool; };
+struct Conv2dRequest { int nsplit; bool bf3, two_launch, wino; int lat; bool stem; int pw; bool h3; bool pool; bool pack; };
 Conv2dRequest conv2d_request(int nsplit) {
-    Conv2dRequest r{nsplit, false, false, false, 0, false, 0, false, false};
+    Conv2dRequest r{nsplit, false, false, false, 0, false, 0, false, false, false};
+    if (r.nsplit == -10) { r.pack = true; r.nsplit = -9; }      // -10: form -9 with its patches cut out of canvas rows of several frames (wino_pack_geometry)
     if (r.nsplit >= 7000 && r.nsplit < 8000) { r.lat = r.nsplit - 7000; r.h3 = true; r.nsplit = 1; return r; }      // 7000 + parts = k_lateral1x1 on two fp16 pieces
     if (r.nsplit >= 6000 && r.nsplit < 6200) {      // 6000 + split = k_conv_igemm's three-product form (fused split-K), 6100 + split: two launches
         r.h3 = true; r.nsplit -= 6000;
@@ -1489,6 +1532,7 @@ extern "C" int fpc_conv2d(const float* in, int64_t sb, int64_t sh, int64_t sw, i
                : (sc == 1 && Cin % 4 == 0 && sw % 4 == 0 && sh % 4 == 0 && sb % 4 == 0 && ((uintptr_t)in & 15) == 0) ? 2 : 1;
     fpc_net tmp;
     tmp.B = B;
+    tmp.wino_pack = rq.pack ? 1 : 0;      // (-9 itself stays on the plain geometry)
     tmp.ws = packed;
     tmp.splitk_off = lay.packed;
     ConvArgs a;

@@ -52,6 +52,8 @@ struct ConvArgs {
     int fold_cin;
     float fold_lat_ms;                // tuning: the p2 lateral's best score, the fold's time must beat lateral + s2.0
     void* dbg;                        // host side only: diagnostic stamp buffer for k_conv_wino (or null)
+    long long wino_blocks;            // host side only, written by a form-9 launch: its workgroups
+    int wino_pack;                    // host side only: a form-9 launch may use the packed patch geometry (wino_pack_geometry)
 };
 
 // FPN lateral 1x1 convolutions of all decoders as one pixel-resident product (lateral.hip): K = Cin in {64, 128}
@@ -189,6 +191,9 @@ struct WinoArgs {
     const float* w2[kMaxGroup];      // W's h3 image (Cin2 channels) with .p[g].w's scale (launch_wino_pack_h3_pair)
     const float* btab[kMaxGroup];    // [4 row classes][4 column classes][Cout]: class bit 0 = first row / column, bit 1 = last
     int fold, Cin2;
+    // k_conv_wino_h3 only: > 1 = the patches are cut out of canvas rows of `pack` frames side by side (wino_pack_geometry's G; tbx =
+    // its patches per full row), pack_rx = GroupNorm records per frame and patch row.  0 / 1: one frame per patch row, as ever
+    int pack, pack_rx;
 };
 int launch_conv_wino(const WinoArgs& a, int groups, hipStream_t s);
 const float* zero_page();      // 64 zero floats in the code object (per device context), or null
@@ -209,6 +214,10 @@ int launch_absmax_bits(const float* w, long long n, unsigned* out_bits, hipStrea
 // wino_h3.hip: k_conv_wino_h2 with three of the four piece products, over pairs of K-steps (Cin a multiple of 16); its own image:
 // 16 * Cout * Cin + 2 floats
 int launch_conv_wino_h3(const WinoArgs& a, int groups, hipStream_t s);
+// its launch geometry: G frames per canvas row (1: plain), patches per full row and patch rows, GroupNorm records per frame and
+// patch row, launched patches per (64-channel block, group), their tile slots, tiles that exist, GroupNorm records per frame
+struct WinoPackGeom { int G, tbx, tby, rx; long long patches, slots, tiles; int gn_rows; };
+WinoPackGeom wino_pack_geometry(int H, int W, int B, int Cin, bool allow);
 int launch_wino_pack_h3(const float* w_oihw, float* packed, int Cout, int Cin, hipStream_t s);
 // the fold's weights: wc = W . L (OIHW [Cout][Cmid -> Cin][3][3], f64 sums) and the bias table conv3x3(W, bias . 1_inside) per border
 // class (WinoArgs::btab); W [Cout][Cmid][3][3], L the 1x1 lateral [Cmid][Cin], bias [Cmid]

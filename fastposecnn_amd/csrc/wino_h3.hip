@@ -83,7 +83,13 @@ __device__ __forceinline__ f32x4 add_s4(f32x4 a, f32x4 b) { return f32x4{a[0] + 
 // and column 2 are zero: every wave skips its xi column 2 in phase 2 (operands, weight loads, matrix instructions), 36 of 48 matrix
 // instructions per pair.  Wave 2's row is zero too, but it still runs the loop (its products add exact zeros): a branch that gave it
 // only the staging made the compiler spill ~1 KB per wave at the phase boundary.
-template <int VAR, bool FOLD>
+//
+// PACK: the patches are cut out of a canvas of a.pack frames side by side (wino_pack_geometry; a.tbx = patches per canvas row of a
+// full group).  A patch that starts at tile column tx0 of frame f and meets the frame's end after ks < 8 columns carries a SEAM: its
+// tile columns k >= ks are columns k - ks of frame f + 1.  The staged region then holds ONE gap column, tile column k reads region
+// columns k + (k >= ks) + ch: region column ks holds frame f's last pixel (and the zero of x = W), column ks + 1 the zero of
+// x = -1 and frame f + 1's first pixel.  Only the set-up and the epilogue know about it; the K loop is the plain one.
+template <int VAR, bool FOLD, bool PACK>
 __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[kLdsFloats];
     const long long t_entry = a.dbg ? clock64() : 0;
@@ -96,14 +102,33 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
     const int nnb = Cout / kBN;
     const int nb = bid % nnb; bid /= nnb;
     const int grp = bid % a.groups; bid /= a.groups;
-    const int bx = bid % a.tbx; bid /= a.tbx;
-    const int by = bid % a.tby;
-    const int b = bid / a.tby;
+    int bx, by, b, tx0;
+    int pk_ks = 99, pk_raw = 99, pk_slot = 0;      // PACK: seam after pk_ks tile columns (99: none), tcw - tx0, this patch's GroupNorm record of frame b
+    bool pk_two = false;                           // PACK: the frame behind the seam exists
+    if constexpr (!PACK) {
+        bx = bid % a.tbx; bid /= a.tbx;
+        by = bid % a.tby;
+        b = bid / a.tby;
+        tx0 = bx * kTX;
+    } else {
+        const int G = a.pack, tcw = (a.W + 1) >> 1, per = a.tbx * a.tby;
+        const int g = bid / per, rem = bid - g * per;
+        const int nf = min(G, a.B - g * G);                        // frames of this canvas row (a ragged last group has fewer,
+        const int tbxg = min(a.tbx, (nf * tcw + kTX - 1) / kTX);   // and only the patches that reach them)
+        bx = rem % tbxg; by = rem / tbxg;
+        const int f = (kTX * bx) / tcw;
+        tx0 = kTX * bx - f * tcw;
+        b = g * G + f;
+        pk_raw = tcw - tx0;
+        pk_ks = pk_raw < kTX ? pk_raw : 99;
+        pk_two = pk_ks < kTX && f + 1 < nf;
+        pk_slot = bx - (f * tcw) / kTX;
+    }
     ConvPtrs P = a.p[0];
     if (grp == 1) P = a.p[1];
     if (grp == 2) P = a.p[2];
     if (grp == 3) P = a.p[3];
-    const int ty0 = by * kTY, tx0 = bx * kTX;
+    const int ty0 = by * kTY;
     const int y_in0 = 2 * ty0 - 1, x_in0 = 2 * tx0 - 1;
 
     f32x16 acc[4][2][2];      // [xi column j][tile half mt][32-channel tile nt]; zeroed while the first operands are on their way
@@ -152,9 +177,13 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
         const int ah = (cell / 3) * 4 + (res & 3), qh = (cell % 3) * 4 + (res >> 2);
         const int hf = blk & 1;
         const int ry = 2 * ah + ((blk >> 2) & 1), rx = 2 * qh + ((blk >> 1) & 1);
-        const int y = y_in0 + ry, x = x_in0 + rx;
-        iok[i] = wi + 4 * i < kInPieces && ah <= kTY && qh <= kTX && y >= 0 && y < H && x >= 0 && x < W;
-        ivo[i] = iok[i] ? (unsigned)((((size_t)(y >> up) * Ws + (x >> up)) * Cs + 4 * hf) * sizeof(float)) : 0u;
+        const bool far = PACK && qh > pk_ks;      // behind the seam: frame b + 1, one gap column in between
+        const int y = y_in0 + ry, x = far ? rx - 2 * pk_ks - 3 : x_in0 + rx;
+        const int qmax = (PACK && pk_ks < kTX) ? kTX + 1 : kTX;
+        iok[i] = wi + 4 * i < kInPieces && ah <= kTY && qh <= qmax && y >= 0 && y < H && x >= 0 && x < W && (!far || pk_two);
+        ivo[i] = iok[i] ? (unsigned)((((size_t)(y >> up) * Ws + (x >> up)) * Cs + 4 * hf) * sizeof(float)) +
+                              (far ? (unsigned)((size_t)Hs * Ws * Cs * sizeof(float)) : 0u)
+                        : 0u;
     }
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm"
@@ -186,7 +215,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
 
     // ---- fragment addressing: this lane's tile of half 0 (half 1 = four tile rows further down = + 3 cells), the two region rows of
     // transform row wi, columns 2 txl + c
-    const int tyl = li >> 3, txl = li & 7;
+    const int tyl = li >> 3, txl = (li & 7) + ((PACK && (li & 7) >= pk_ks) ? 1 : 0);
     // row pair (ra, rb) and sign of B^T row wi:  0: d0-d2   1: d1+d2   2: d2-d1   3: d1-d3
     const int ra = (wi == 0) ? 0 : (wi == 2 ? 2 : 1);
     const int rb = (wi == 0) ? 2 : (wi == 1 ? 2 : (wi == 2 ? 1 : 3));
@@ -201,7 +230,8 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
 
     // a patch that reaches over the image border zeroes the input ring once (inactive DMA lanes leave it alone); an
     // interior patch rewrites every unit the fragment reads touch with every step's DMA
-    if (y_in0 < 0 || x_in0 < 0 || y_in0 + kRH > H || x_in0 + kRW > W) {
+    // (a seam patch too: the units of x = W and x = -1 at the seam are never staged and must read zero)
+    if (y_in0 < 0 || x_in0 < 0 || y_in0 + kRH > H || x_in0 + kRW > W || (PACK && pk_ks < kTX)) {
         for (int i = t; i < kRing * kInFloats / 4; i += 256) reinterpret_cast<f32x4*>(lds)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __syncthreads();
@@ -414,7 +444,15 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
     // transform-row waves through LDS: y0 = z[0] + z[1] + z[2], y1 = z[1] - z[2] - z[3].  Z[row][cc][tile 64][co 64], one pass.
     // Output stage: thread = (tile of a 16-tile pass, 16-byte channel quad): within a ds_read_b128 lane group the 16 quads are 16
     // different bank slots; a wave stores 4 tiles x 256 contiguous bytes.
-    const int oq = t & 15, otl = t >> 4;                      // quad 0..15, tile 0..15 (+ 16 per tile pass)
+    // (PACK: the thread's indices are rebuilt from the lane counter here instead of being carried over the K loop: the packed
+    // set-up needs a few registers more, and the allocator otherwise parks these in scratch from the set-up to the epilogue)
+    const int lane_e = PACK ? (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) : lane;
+    const int t_e = PACK ? wi * 64 + lane_e : t;
+    const int oq = t_e & 15, otl = t_e >> 4;                  // quad 0..15, tile 0..15 (+ 16 per tile pass)
+    // (ot & 7 is the same in all four tile passes of a thread: it lies wholly on one side of a seam)
+    const bool o_far = PACK && (otl & 7) >= pk_ks;
+    const int ob = o_far ? b + 1 : b, otx = o_far ? (otl & 7) - pk_ks : tx0 + (otl & 7);
+    const bool o_ok = !o_far || pk_two;
     const int n = nb * kBN + oq * 4;
     const f32x4 e_sc = P.scale ? *reinterpret_cast<const f32x4*>(P.scale + n) : f32x4{1.f, 1.f, 1.f, 1.f};
     const f32x4 e_sh = P.shift ? *reinterpret_cast<const f32x4*>(P.shift + n) : f32x4{0.f, 0.f, 0.f, 0.f};
@@ -430,12 +468,12 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int ot = otl + 16 * tp;
-            const int y = 2 * (ty0 + (ot >> 3)) + (q >> 1), x = 2 * (tx0 + (ot & 7)) + (q & 1);
-            e_res[tp][q] = (P.res && y < H && x < W) ? *reinterpret_cast<const f32x4*>(P.res + ((size_t)b * HW + (size_t)y * W + x) * Cout + n)
+            const int y = 2 * (ty0 + (ot >> 3)) + (q >> 1), x = 2 * otx + (q & 1);
+            e_res[tp][q] = (P.res && o_ok && y < H && x < W) ? *reinterpret_cast<const f32x4*>(P.res + ((size_t)ob * HW + (size_t)y * W + x) * Cout + n)
                                                      : f32x4{0.f, 0.f, 0.f, 0.f};
         }
     __syncthreads();
-    float* const zb = lds + ((wi * 2) * kNT + 4 * lh) * kBN + li;
+    float* const zb = lds + ((wi * 2) * kNT + 4 * (PACK ? lane_e >> 5 : lh)) * kBN + (PACK ? lane_e & 31 : li);
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -453,7 +491,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
 #pragma unroll
     for (int tp = 0; tp < 4; ++tp) {
         const int ot = otl + 16 * tp;
-        const int oty = ty0 + (ot >> 3), otx = tx0 + (ot & 7);
+        const int oty = ty0 + (ot >> 3);
         f32x4 z[4][2];
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -464,7 +502,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
 #pragma unroll
             for (int cc = 0; cc < 2; ++cc) {
                 const int y = 2 * oty + rr, x = 2 * otx + cc;
-                if (y >= H || x >= W) continue;
+                if (y >= H || x >= W || !o_ok) continue;
                 f32x4 val = (rr == 0 ? z[0][cc] + z[1][cc] + z[2][cc] : z[1][cc] - z[2][cc] - z[3][cc]) * inv_s;      // (a power of two: exact)
                 if (FOLD) {      // conv3x3(W, b 1_inside): by the output pixel's border class
                     const int cls = (((y == 0) | ((y == H - 1) << 1)) << 2) | (x == 0) | ((x == W - 1) << 1);
@@ -472,7 +510,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
                 }
                 if (P.scale) val = val * e_sc;
                 val = val + e_sh;
-                const size_t o = ((size_t)b * HW + (size_t)y * W + x) * Cout + n;
+                const size_t o = ((size_t)ob * HW + (size_t)y * W + x) * Cout + n;
                 if (P.res) val += e_res[tp][2 * rr + cc];
                 if (a.relu) { val[0] = fmaxf(val[0], 0.f); val[1] = fmaxf(val[1], 0.f); val[2] = fmaxf(val[2], 0.f); val[3] = fmaxf(val[3], 0.f); }
                 *reinterpret_cast<f32x4*>(P.out + o) = val;
@@ -480,7 +518,43 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
                 s2 += val * val;
             }
     }
-    if (P.gn_part) {
+    if (PACK && P.gn_part) {
+        // one record per frame this workgroup touches: two sets of sums, a thread's go to its side of the seam; the reduction is the
+        // plain one on both.  Record of frame b: slot pk_slot of row by (a.pack_rx slots per row: the most patches a frame meets),
+        // of frame b + 1: slot 0.  The patch that holds a frame's last tile column zeroes the slots the frame does not use, so every
+        // record k_gn_finalize reads is written by this launch.
+        f32x4 q1[2] = {o_far ? f32x4{0.f, 0.f, 0.f, 0.f} : s1, o_far ? s1 : f32x4{0.f, 0.f, 0.f, 0.f}};
+        f32x4 q2[2] = {o_far ? f32x4{0.f, 0.f, 0.f, 0.f} : s2, o_far ? s2 : f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+        for (int sd = 0; sd < 2; ++sd)
+#pragma unroll
+            for (int o = 16; o < 64; o <<= 1)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { q1[sd][k] += __shfl_xor(q1[sd][k], o, 64); q2[sd][k] += __shfl_xor(q2[sd][k], o, 64); }
+        __syncthreads();
+        float* red = lds;                                     // [2 sides][4 waves][64 ch][2]
+        if (lane_e < 16) {
+#pragma unroll
+            for (int sd = 0; sd < 2; ++sd)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    red[((sd * 4 + wi) * kBN + oq * 4 + k) * 2] = q1[sd][k];
+                    red[((sd * 4 + wi) * kBN + oq * 4 + k) * 2 + 1] = q2[sd][k];
+                }
+        }
+        __syncthreads();
+        if (t_e < 2 * kBN && (t_e < kBN || pk_two)) {
+            const int sd = t_e >> 6, ch = t_e & (kBN - 1);
+            float u1 = 0.f, u2 = 0.f;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) { u1 += red[((sd * 4 + w) * kBN + ch) * 2]; u2 += red[((sd * 4 + w) * kBN + ch) * 2 + 1]; }
+            const int rx = a.pack_rx, Pn = a.tby * rx, slot = sd ? 0 : pk_slot;
+            float* g = P.gn_part + (((size_t)(b + sd) * Pn + by * rx + slot) * Cout + nb * kBN + ch) * 2;
+            g[0] = u1; g[1] = u2;
+            if (sd == 0 && pk_raw <= kTX)
+                for (int z = slot + 1; z < rx; ++z) { g += (size_t)Cout * 2; g[0] = 0.f; g[1] = 0.f; }
+        }
+    } else if (P.gn_part) {
         // per-channel sums of this workgroup's outputs: a wave holds 4 tiles (lane bits 4-5) x 16 quads (lane bits 0-3) per pass:
         // butterfly over the tile bits, then the four waves' sums through LDS in wave order
 #pragma unroll
@@ -554,11 +628,44 @@ __global__ __launch_bounds__(256) void k_wino_pack_h3(const float* __restrict__ 
     }
 }
 
+// The patch geometry of one k_conv_wino_h3 launch (host arithmetic).  tcw = ceil(W / 2) tile columns per frame; G = the smallest frame
+// count in 1 .. min(B, 8) that minimises ceil(G tcw / 8) / G.  Packing is eligible when `allow` (not the fold), tcw >= 8 (a patch
+// then straddles at most two frames) and two consecutive frames of the input fit 32-bit lane offsets; otherwise, and where it saves
+// nothing, G = 1: today's grid.  Frames g G .. g G + G - 1 form canvas row g; a ragged last row launches only the patches that
+// reach its frames.
+WinoPackGeom wino_pack_geometry(int H, int W, int B, int Cin, bool allow) {
+    WinoPackGeom q;
+    const int tcw = cdiv(W, 2), tch = cdiv(H, 2);
+    q.G = 1;
+    q.tby = cdiv(tch, kTY);
+    if (allow && tcw >= kTX && 2LL * H * W * Cin * (long long)sizeof(float) < (1LL << 32)) {
+        int best = cdiv(tcw, kTX);      // patches per G frames, compared as fractions
+        for (int g = 2; g <= std::min(B, 8); ++g)
+            if ((long long)cdiv(g * tcw, kTX) * q.G < (long long)best * g) { best = cdiv(g * tcw, kTX); q.G = g; }
+    }
+    q.tbx = cdiv(q.G * tcw, kTX);
+    q.rx = 1;
+    for (int f = 0; f < q.G; ++f) q.rx = std::max(q.rx, (f * tcw + tcw - 1) / kTX - (f * tcw) / kTX + 1);
+    q.patches = (long long)q.tby * ((long long)(B / q.G) * q.tbx + cdiv((B % q.G) * tcw, kTX));
+    q.slots = q.patches * kNT;
+    q.tiles = (long long)B * tch * tcw;
+    q.gn_rows = q.tby * q.rx;
+    return q;
+}
+
 // .w = the k_wino_pack_h3 image (+ its tail), tby = ceil(ceil(H / 2) / 8): 8 x 8 tile patches
 int launch_conv_wino_h3(const WinoArgs& a, int groups, hipStream_t s) {
     if (groups < 1 || groups > kMaxGroup || a.Cin % 16 != 0 || a.Cout % kBN != 0) return FPC_EINVAL;      // pairs of 8-channel K-steps
     if ((long long)a.H * a.W * a.Cin * (long long)sizeof(float) >= (1LL << 32)) return FPC_EINVAL;      // 32-bit lane offsets inside one image
     if ((long long)(a.Cin >> 4) * kPairBytes >= (1LL << 31)) return FPC_EINVAL;                          // 31-bit buffer offsets inside one block's images
+    if (a.pack > 1) {      // patches cut out of canvas rows of a.pack frames: the geometry must be wino_pack_geometry's own
+        const WinoPackGeom q = wino_pack_geometry(a.H, a.W, a.B, a.Cin, !a.fold);
+        if (q.G != a.pack || q.tbx != a.tbx || q.tby != a.tby || q.rx != a.pack_rx) return FPC_EINVAL;
+        const long long nblk = q.patches * (a.Cout / kBN) * groups;
+        if (nblk < 1 || nblk >= (1LL << 31)) return FPC_EINVAL;
+        hipLaunchKernelGGL((k_conv_wino_h3<0, false, true>), dim3((unsigned)nblk), dim3(256), 0, s, a);
+        return check_launch();
+    }
     if (a.tbx != cdiv(cdiv(a.W, 2), kTX) || a.tby != cdiv(cdiv(a.H, 2), kTY)) return FPC_EINVAL;
     const long long nblk = (long long)a.tbx * a.tby * a.B * (a.Cout / kBN) * groups;
     if (nblk < 1 || nblk >= (1LL << 31)) return FPC_EINVAL;
@@ -568,12 +675,12 @@ int launch_conv_wino_h3(const WinoArgs& a, int groups, hipStream_t s) {
             return FPC_EINVAL;
         for (int g = 0; g < groups; ++g)
             if (!a.in2[g] || !a.w2[g] || !a.btab[g] || a.p[g].scale || a.p[g].shift || a.p[g].res || a.p[g].up) return FPC_EINVAL;
-        hipLaunchKernelGGL((k_conv_wino_h3<0, true>), dim3((unsigned)nblk), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((k_conv_wino_h3<0, true, false>), dim3((unsigned)nblk), dim3(256), 0, s, a);
         return check_launch();
     }
     static const int var = getenv("FPC_H3_VAR") ? atoi(getenv("FPC_H3_VAR")) : 0;      // diagnostic
-    if (var == 1) hipLaunchKernelGGL((k_conv_wino_h3<1, false>), dim3((unsigned)nblk), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_conv_wino_h3<0, false>), dim3((unsigned)nblk), dim3(256), 0, s, a);
+    if (var == 1) hipLaunchKernelGGL((k_conv_wino_h3<1, false, false>), dim3((unsigned)nblk), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_conv_wino_h3<0, false, false>), dim3((unsigned)nblk), dim3(256), 0, s, a);
     return check_launch();
 }
 

@@ -129,6 +129,15 @@ class NetEngine:
             nat.check(rc, "fpc_net_force_stem_pool")
         return rc
 
+    def set_wino_pack(self, on):
+        """Form-9 Winograd launches cut their tile patches out of canvas rows of several frames where that needs fewer patches
+        (on = 1, the library's default) or keep one frame per patch row (on = 0).  The plans do not change."""
+        nat.check(self._lib.fpc_net_set_wino_pack(self._h, int(on)), "fpc_net_set_wino_pack")
+
+    def wino_blocks(self):
+        """Workgroups of all form-9 launches of the last forward that launched its kernels."""
+        return int(self._lib.fpc_net_wino_blocks(self._h))
+
     def force_pointwise(self, on):
         """Every eligible 1x1 site on k_conv1x1 (on = 1) or back on k_conv_igemm (on = 0); returns the number of sites changed."""
         rc = self._lib.fpc_net_force_pointwise(self._h, int(on))

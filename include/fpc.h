@@ -46,6 +46,7 @@ extern "C" {
 /* 11 also covers the Bottleneck encoders (fpc_net_create_encoder, fpc_net_force_pointwise, fpc_conv2d's 4000 + variant),
  * the FPN p2 fold (fpc_net_force_fold) and the three-product direct form (fpc_net_force_direct_h3, fpc_conv2d's 6000 + split and 7000 + parts, fpc_net_graph_recorded):
  * and the stem fused with its max-pool (fpc_net_force_stem_pool, fpc_stem_pool_tasks, fpc_conv2d's 3100):
+ * and form -9's packed patch geometry (fpc_wino_pack_geometry, fpc_net_set_wino_pack, fpc_net_wino_blocks, fpc_conv2d's -10):
  * additions only, every earlier entry point keeps its behaviour. */
 #define FPC_ABI_VERSION 11
 
@@ -447,6 +448,18 @@ int fpc_net_force_stem_pool(fpc_net_t* net, int on);
  * conv columns, conv outputs one frame's launch computes (the band overlap rows and the halo tiles included), conv outputs that
  * exist (Ho * Wo).  FPC_EINVAL for a shape the fused launch does not take. */
 int fpc_stem_pool_tasks(int Ho, int Wo, int64_t* out4);
+/* Form -9's launch geometry (host arithmetic, no device) for a 3x3 / stride-1 site with output H x W, batch B, Cin input channels.
+ * Where the tile columns of a frame do not fill whole 8-column patches, G frames are laid side by side on a canvas row and the
+ * patches are cut out of the canvas (G = the smallest count in 1 .. min(B, 8) that minimises ceil(G tcw / 8) / G, tcw = ceil(W / 2);
+ * eligible: tcw >= 8, not the folded s2.0, two frames of the input within 32-bit byte offsets).  out8 = G (1: one frame per patch
+ * row), patches per full canvas row, patch rows, launched patches per (64-channel block, decoder), their tile slots (x 64), tiles
+ * that exist, GroupNorm records per frame, GroupNorm records per frame and patch row. */
+int fpc_wino_pack_geometry(int H, int W, int B, int Cin, int fold, int64_t* out8);
+/* on = 1 (default): form-9 launches of the plan use that geometry where it needs fewer patches; on = 0: one frame per patch row.
+ * The plans and fpc_net_conv_plan's reports do not change.  Drops the recorded graph. */
+int fpc_net_set_wino_pack(fpc_net_t* net, int on);
+/* Workgroups of all form-9 launches of the last forward that launched (or captured) its kernels: what the switch above changes. */
+int64_t fpc_net_wino_blocks(const fpc_net_t* net);
 /* FLOP of one forward over the batch under the current plans: out3 = {2 x MACs of the direct convolutions (what the
  * reference's cuDNN path executes), multiply-add FLOP the plans execute (Winograd sites: / 2.25), Winograd share}. */
 int fpc_net_flops(const fpc_net_t* net, double* out3);
@@ -459,7 +472,8 @@ int fpc_net_tensor(const fpc_net_t* net, const char* name, const float** ptr, in
  * in: any element strides (sb, sh, sw, sc); w_oihw torch layout; out NHWC [B,Ho,Wo,Cout];
  * optional per-channel scale / shift, residual (as out), nearest-x2 `up` [B,Ho/2,Wo/2,Cout], ReLU,
  * GroupNorm partials gn_part [B][P32][Cout][2]; bm/bn/nsplit = 0 -> chosen by the planner.
- * `nsplit` also selects the engine's other kernels for tests: -1..-5 Winograd forms (-5 split precision), 100 + k split-K
+ * `nsplit` also selects the engine's other kernels for tests: -1..-9 Winograd forms (-5 split precision; -10: form -9 with its
+ * patches cut out of canvas rows of several frames, fpc_wino_pack_geometry, P32 = its records per frame), 100 + k split-K
  * summed by a second launch, 1000 + k split-precision (bf16 x 3) products, 2000 + parts the pixel-resident FPN lateral
  * product (1x1, Cin 64 / 128, bias + `up` epilogue), 3000 the weight-resident 7x7 / s2 stem (Cin = 4: NHWC4 image),
  * 3100 the same stem fused with its 3x3 / 2 / pad-1 max-pool on three fp16 piece products (`out` is then the POOLED tensor
