@@ -144,6 +144,98 @@ static size_t splitk_floats_for(const ConvPlan& p, int groups, int B, int Npad) 
     return p.nsplit > 1 ? (size_t)groups * p.nsplit * B * p.mtiles * p.bm * Npad : 0;
 }
 
+// ---- the Winograd forms (ConvPlan::wino = 1..9, reported and requested as -form) and the weight images they read.
+// A new form adds: one row of kWinoForms, one entry of kWinoImages if it reads an image of its own, and its launcher.
+// A site's image region holds the images in the order of kWinoImages, each `units` x Cout x Cin floats followed by `tail` floats; the
+// 128-channel form's image is there only where Cout % 128 == 0.  Behind the last image the region keeps kWinoSlack floats.
+enum WinoImage { kImgF32, kImgBf3, kImgC128, kImgH2, kImgH3, kWinoImageCount };
+struct WinoImageDesc { int units, tail; int (*pack)(const float* w_oihw, float* packed, int Cout, int Cin, hipStream_t s); };
+constexpr WinoImageDesc kWinoImages[kWinoImageCount] = {
+    {16, 0, launch_wino_pack},            // f32
+    {24, 0, launch_wino_pack_bf3},        // split precision: three bf16 planes
+    {24, 0, launch_wino_pack_c128},       // ... in the 128-channel form's fragment order (wino128.hip)
+    {16, 8, launch_wino_pack_h2},         // two fp16 pieces in fragment order (wino_h2.hip); the tail: its two scale floats, kept 32-byte aligned
+    {16, 8, launch_wino_pack_h3},         // ... in pair order (wino_h3.hip), with the same tail
+};
+constexpr size_t kWinoSlack = 128;      // a 64-float line for the tails + 64 zero floats (fpc_conv2d's zero page where the code object has none)
+
+constexpr int kWinoFormCount = 10;      // forms 1..9; row 0 is "not Winograd"
+constexpr int kWinoH2 = 8, kWinoH3 = 9;      // the fp16 x 2 form and its three-product form: the one launch that may pack frames or fold p2 in
+struct WinoForm {
+    int waves;               // 4: 8 x 4 tile patch per workgroup, 8: 8 x 8
+    int bn, ck;              // output channels per workgroup; input channels per K-loop step: Cout and Cin are multiples of these
+    int variant;             // WinoArgs::variant
+    WinoImage image;
+    int wg_per_cu;           // workgroups of the form that share a CU (the tuner's occupancy share)
+    int min_split;           // lowest fpc_net_set_split_precision level at which the tuner offers the form
+    bool zeros;              // reads the zero page (WinoArgs::zeros)
+    int (*launch)(const WinoArgs& a, int groups, hipStream_t s);
+};
+constexpr WinoForm kWinoForms[kWinoFormCount] = {
+    {},
+    {4, 64, 8, 0, kImgF32, 2, 0, false, launch_conv_wino},             // -1: 4 waves
+    {8, 64, 8, 0, kImgF32, 1, 0, false, launch_conv_wino},             // -2: 8 waves
+    {4, 64, 8, 1, kImgF32, 2, 0, false, launch_conv_wino},             // -3: wave-private K loop
+    {8, 64, 8, 2, kImgF32, 1, 0, true, launch_conv_wino},              // -4: all-DMA 3-stage
+    {8, 64, 8, 3, kImgBf3, 1, 1, true, launch_conv_wino},              // -5: split-precision products, 8 waves
+    {4, 128, 8, 0, kImgC128, 1, 1, false, launch_conv_wino_c128},      // -6: ... 8 x 4 tiles x 128 channels per workgroup, 4 waves (wino128.hip)
+    {8, 64, 8, 0, kImgBf3, 1, 1, false, launch_conv_wino_w4},          // -7: ... 64 channels, four waves of 512 registers, weights direct (wino_w4.hip)
+    {8, 64, 8, 0, kImgH2, 1, 2, false, launch_conv_wino_h2},           // -8: the -7 form on two fp16 pieces per operand (range-limited: fpc.h; wino_h2.hip)
+    {8, 64, 16, 0, kImgH3, 1, 3, false, launch_conv_wino_h3},          // -9: three of the four piece products of -8, over pairs of K-steps (wino_h3.hip)
+};
+// the shape rules of a form, on top of PackedConv::wino_ok
+static bool wino_form_ok(int form, int Cin, int Cout) {
+    return form >= 1 && form < kWinoFormCount && Cout % kWinoForms[form].bn == 0 && Cin % kWinoForms[form].ck == 0;
+}
+// units and tail floats of the images in front of image `end`; c128: the region has the 128-channel form's image
+struct WinoSpan { size_t units, tails; };
+static WinoSpan wino_span(int end, bool c128) {
+    WinoSpan sp{0, 0};
+    for (int i = 0; i < end; ++i)
+        if (i != kImgC128 || c128) { sp.units += kWinoImages[i].units; sp.tails += kWinoImages[i].tail; }
+    return sp;
+}
+static_assert(kWinoImages[kImgH2].tail + kWinoImages[kImgH3].tail <= 64, "kWinoSlack keeps one 64-float line for all tails");
+// float offset of image `img` in a site's region
+static size_t wino_image_offset(WinoImage img, int Cout, int Cin) {
+    const WinoSpan sp = wino_span(img, Cout % 128 == 0);
+    return sp.units * Cout * Cin + sp.tails;
+}
+// floats of a region that ends with image `last`: what one form needs (fpc_conv2d's exact workspace), and with the last image of
+// all what a site needs (fpc_net::add_conv); c128 = true bounds both (fpc_conv2d_workspace_bytes)
+static size_t wino_region_floats(WinoImage last, int Cout, int Cin, bool c128) { return (wino_span(last, c128).units + kWinoImages[last].units) * Cout * Cin + kWinoSlack; }
+// tile patches of one frame: tbx x tby workgroups per (frame, channel block, group)
+struct WinoGrid { int tbx, tby; int patches() const { return tbx * tby; } };
+static WinoGrid wino_grid(int form, int H, int W) { return {cdiv(cdiv(W, 2), 8), cdiv(cdiv(H, 2), kWinoForms[form].waves)}; }
+
+// ---- the integer a plan is reported by (fpc_net_conv_plan's out5[2]) and requested by (fpc_conv2d's `nsplit`): fpc.h, FPC_PLAN_*.
+// What a request asks for (nsplit: the split-K factor, 0 = the planner's, or -form; wino: the form or 0):
+struct Conv2dRequest { int nsplit; bool bf3, two_launch; int wino, lat; bool stem; int pw; bool h3, pool, pack; };
+static Conv2dRequest decode_plan(int code) {
+    Conv2dRequest r{code, false, false, 0, 0, false, 0, false, false, false};
+    if (code == FPC_PLAN_WINO_PACKED) { r.pack = true; r.nsplit = -kWinoH3; }      // form -9 with its patches cut out of canvas rows of several frames (wino_pack_geometry)
+    if (r.nsplit >= FPC_PLAN_LATERAL_H3 && r.nsplit < FPC_PLAN_LATERAL_H3 + 1000) { r.lat = r.nsplit - FPC_PLAN_LATERAL_H3; r.h3 = true; r.nsplit = 1; return r; }      // + parts = k_lateral1x1 on two fp16 pieces
+    if (r.nsplit >= FPC_PLAN_H3 && r.nsplit < FPC_PLAN_H3 + 200) { r.h3 = true; r.nsplit -= FPC_PLAN_H3; }      // + split = k_conv_igemm's three-product form; what is left (< 200) reaches the two-launch line only
+    if (r.nsplit >= FPC_PLAN_POINTWISE) { r.pw = r.nsplit - FPC_PLAN_POINTWISE + 1; r.bf3 = true; r.nsplit = 1; return r; }   // + variant = k_conv1x1 (pointwise.hip)
+    if (r.nsplit == FPC_PLAN_STEM_POOL) { r.stem = true; r.pool = true; r.h3 = true; r.nsplit = 1; return r; }     // k_stem_pool_h3: NHWC4 input, `out` = the POOLED tensor
+    if (r.nsplit == FPC_PLAN_STEM) { r.stem = true; r.bf3 = true; r.nsplit = 1; return r; }                   // k_stem7x7 (stem.hip): NHWC4 input
+    if (r.nsplit >= FPC_PLAN_LATERAL) { r.lat = r.nsplit - FPC_PLAN_LATERAL; r.bf3 = true; r.nsplit = 1; return r; }      // + parts = k_lateral1x1 (lateral.hip)
+    if (r.nsplit >= FPC_PLAN_BF3) { r.bf3 = true; r.nsplit -= FPC_PLAN_BF3; }          // + split = split-precision matrix products
+    if (r.nsplit >= FPC_PLAN_TWO_LAUNCH) { r.two_launch = true; r.nsplit -= FPC_PLAN_TWO_LAUNCH; }      // + split = split-K summed by k_conv_splitk_epilogue
+    if (r.nsplit <= -1 && r.nsplit > -kWinoFormCount) r.wino = -r.nsplit;      // -form: kWinoForms
+    return r;
+}
+// What a plan reports; folded_away: the p2 lateral site while s2.0 runs with that level folded in (never a request)
+static int encode_plan(const ConvPlan& p, bool folded_away) {
+    if (folded_away) return FPC_PLAN_FOLDED;
+    // the three-product form: k_conv_igemm + split (fused or not, as the plain tilings), k_lateral1x1 + parts
+    if (p.h3) return p.lat ? FPC_PLAN_LATERAL_H3 + p.lat : FPC_PLAN_H3 + p.nsplit;
+    if (p.pw) return FPC_PLAN_POINTWISE + p.pw - 1;
+    if (p.stem) return p.pool ? FPC_PLAN_STEM_POOL : FPC_PLAN_STEM;
+    if (p.lat) return FPC_PLAN_LATERAL + p.lat;
+    return p.wino ? -p.wino : p.nsplit;
+}
+
 }  // namespace fpc
 
 using namespace fpc;
@@ -233,13 +325,16 @@ struct fpc_net {
         c.w_off = alloc(conv_packed_floats(c.Npad, c.Kpad));      // f32 image + its three bf16 planes
         if (bn_prefix) { c.scale_off = alloc(Cout); c.shift_off = alloc(Cout); }
         c.wino_ok = (k == 3 && stride == 1 && pad == 1 && c.Cinp == Cin && Cin % 8 == 0 && Cout % 64 == 0);
-        // f32 image (16 x) + split-precision image (24 x) + the 128-channel form's fragment-order image (24 x, wino128.hip)
-        // ... + the fp16 x 2 form's fragment-order image (16 x + its two-float tail, wino_h2.hip)
-        if (c.wino_ok) c.wino_off = alloc((size_t)(Cout % 128 == 0 ? 96 : 72) * Cout * Cin + 80);
+        if (c.wino_ok) c.wino_off = alloc(wino_region_floats(kImgH3, Cout, Cin, Cout % 128 == 0));      // every image (kWinoImages)
         convs.push_back(c);
         return (int)convs.size() - 1;
     }
 };
+
+// the recorded graph no longer matches the plans, the parameters or the launch geometry
+static void drop_graph(fpc_net* n) {
+    if (n->graph_exec) { (void)hipGraphExecDestroy(n->graph_exec); n->graph_exec = nullptr; }
+}
 
 static const char* kDecNames[4] = {"mask_decoder", "rotation_decoder", "translation_decoder", "scales_decoder"};
 static const char* kHeadNames[4] = {"segmentation_head", "rotation_head", "translation_head", "scales_head"};
@@ -250,12 +345,9 @@ static int conv_out(int x, int k, int s, int p) { return (x + 2 * p - k) / s + 1
 static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** out);
 
 extern "C" int fpc_net_create(const char* encoder, int classes, int B, int H, int W, fpc_net_t** out) {
-    if (!encoder || !out || classes < 2 || classes > 8 || B < 1 || H < 32 || W < 32 || H % 32 || W % 32) return FPC_EINVAL;
-    fpc_net* n = new fpc_net();
-    if (!strcmp(encoder, "resnet18")) { int l[4] = {2, 2, 2, 2}; memcpy(n->layers, l, sizeof(l)); }
-    else if (!strcmp(encoder, "resnet34")) { int l[4] = {3, 4, 6, 3}; memcpy(n->layers, l, sizeof(l)); }
-    else { delete n; return FPC_EINVAL; }
-    return net_build(n, classes, B, H, W, out);
+    const int r18[4] = {2, 2, 2, 2}, r34[4] = {3, 4, 6, 3};
+    if (!encoder || (strcmp(encoder, "resnet18") && strcmp(encoder, "resnet34"))) return FPC_EINVAL;
+    return fpc_net_create_encoder(1, strcmp(encoder, "resnet18") ? r34 : r18, classes, B, H, W, out);
 }
 
 // An encoder by its descriptor: block 1 = BasicBlock, 4 = Bottleneck (torchvision's: the stride on the 3x3), layers4 = blocks per
@@ -440,15 +532,9 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
     for (int L = 0; L < 4; ++L)
         for (size_t bi = 0; bi < n->blocks[L].size(); ++bi) {
             const fpc_net::Block& blk = n->blocks[L][bi];
-            if (e == 4) {
-                plan(blk.conv1, n->a_blk_t[L][bi].H * n->a_blk_t[L][bi].W, 1);
-                plan(blk.conv2, fh[L] * fw[L], 1);
-                plan(blk.conv3, fh[L] * fw[L], 1);
-                if (blk.ds >= 0) plan(blk.ds, fh[L] * fw[L], 1);
-                continue;
-            }
-            plan(blk.conv1, fh[L] * fw[L], 1);
+            plan(blk.conv1, n->a_blk_t[L][bi].H * n->a_blk_t[L][bi].W, 1);      // (a Bottleneck's first conv1 of a stage: the stage's input resolution)
             plan(blk.conv2, fh[L] * fw[L], 1);
+            if (blk.conv3 >= 0) plan(blk.conv3, fh[L] * fw[L], 1);
             if (blk.ds >= 0) plan(blk.ds, fh[L] * fw[L], 1);
         }
     for (int i = 0; i < 4; ++i) plan(n->dec[0].lat[i], fh[3 - i] * fw[3 - i], 4);
@@ -513,7 +599,7 @@ extern "C" int fpc_net_graph_recorded(const fpc_net_t* n) { return n && n->use_g
 // do not change (a site on form 9 reports -9 either way); the recorded graph is dropped.
 extern "C" int fpc_net_set_wino_pack(fpc_net_t* n, int on) {
     if (!n || on < 0 || on > 1) return FPC_EINVAL;
-    if (n->wino_pack != on && n->graph_exec) { (void)hipGraphExecDestroy(n->graph_exec); n->graph_exec = nullptr; }
+    if (n->wino_pack != on) drop_graph(n);
     n->wino_pack = on;
     return FPC_OK;
 }
@@ -524,7 +610,7 @@ extern "C" int64_t fpc_net_wino_blocks(const fpc_net_t* n) { return n ? (int64_t
 extern "C" int fpc_net_set_graph(fpc_net_t* n, int on) {
     if (!n) return FPC_EINVAL;
     n->use_graph = on ? 1 : 0;
-    if (!on && n->graph_exec) { (void)hipGraphExecDestroy(n->graph_exec); n->graph_exec = nullptr; }
+    if (!on) drop_graph(n);
     return FPC_OK;
 }
 extern "C" int fpc_net_param_count(const fpc_net_t* n) { return n ? (int)n->pnames.size() : 0; }
@@ -540,7 +626,7 @@ extern "C" int fpc_net_load_params(fpc_net_t* n, const float* const* params, int
                                    fpc_stream_t stream) {
     if (!n || !params || count != (int)n->pnames.size() || !ws) return FPC_EINVAL;
     if (((uintptr_t)ws & 255) != 0 || ws_bytes < n->total_floats * sizeof(float)) return FPC_EWORKSPACE;
-    if (n->graph_exec) { (void)hipGraphExecDestroy(n->graph_exec); n->graph_exec = nullptr; }       // pointers may change
+    drop_graph(n);       // pointers may change
     for (int i = 0; i < count; ++i)
         if (!params[i] || ((uintptr_t)params[i] & 15)) return FPC_EINVAL;
     hipStream_t s = (hipStream_t)stream;
@@ -557,18 +643,11 @@ extern "C" int fpc_net_load_params(fpc_net_t* n, const float* const* params, int
         rc = launch_pack_weight_bf3(n->pptr[c.p_w], n->ws + c.w_off, c.Cout, c.Cin, c.Cinp, c.Kh, c.Kw, c.Kwp, c.Npad, c.Kpad, s);
         if (rc) return rc;
         if (c.wino_ok) {
-            rc = launch_wino_pack(n->pptr[c.p_w], n->ws + c.wino_off, c.Cout, c.Cin, s);
-            if (rc) return rc;
-            rc = launch_wino_pack_bf3(n->pptr[c.p_w], n->ws + c.wino_off + (size_t)16 * c.Cout * c.Cin, c.Cout, c.Cin, s);
-            if (rc) return rc;
-            if (c.Cout % 128 == 0) {
-                rc = launch_wino_pack_c128(n->pptr[c.p_w], n->ws + c.wino_off + (size_t)40 * c.Cout * c.Cin, c.Cout, c.Cin, s);
-                if (rc) return rc;
-            }
-            rc = launch_wino_pack_h2(n->pptr[c.p_w], n->ws + c.wino_off + (size_t)(c.Cout % 128 == 0 ? 64 : 40) * c.Cout * c.Cin, c.Cout, c.Cin, s);
-            if (rc) return rc;
-            if (c.Cin % 16 == 0) {      // the pair-order image of the three-product fp16 form, behind the fp16 x 2 image and its tail
-                rc = launch_wino_pack_h3(n->pptr[c.p_w], n->ws + c.wino_off + (size_t)(c.Cout % 128 == 0 ? 80 : 56) * c.Cout * c.Cin + 8, c.Cout, c.Cin, s);
+            for (int f = 1, done = 0; f < kWinoFormCount; ++f) {      // every image a form this site may run on reads, once
+                const WinoImage img = kWinoForms[f].image;
+                if (!wino_form_ok(f, c.Cin, c.Cout) || (done >> img & 1)) continue;
+                done |= 1 << img;
+                rc = kWinoImages[img].pack(n->pptr[c.p_w], n->ws + c.wino_off + wino_image_offset(img, c.Cout, c.Cin), c.Cout, c.Cin, s);
                 if (rc) return rc;
             }
         }
@@ -662,30 +741,30 @@ int launch_conv_plan(ConvArgs& a, const ConvPlan& p, int groups, hipStream_t s) 
         return launch_lateral1x1(l, s);
     }
     if (p.wino) {
+        if (!wino_form_ok(p.wino, a.Cin, a.Cout)) return FPC_EINVAL;
+        const WinoForm& f = kWinoForms[p.wino];
         WinoArgs w;
         memset(&w, 0, sizeof(w));
         for (int g = 0; g < groups; ++g) {
             if (!a.wino_w[g] || a.p[g].up) return FPC_EINVAL;
             w.p[g] = a.p[g];
-            // the split-precision image follows the f32 one, the 128-channel form's fragment-order image follows that
-            w.p[g].w = a.wino_w[g] + ((p.wino == 5 || p.wino == 7) ? (size_t)16 * a.Cout * a.Cin : p.wino == 6 ? (size_t)40 * a.Cout * a.Cin
-                                      : p.wino == 8 ? (size_t)(a.Cout % 128 == 0 ? 64 : 40) * a.Cout * a.Cin      // ... the fp16 x 2 image
-                                      : p.wino == 9 ? (size_t)(a.Cout % 128 == 0 ? 80 : 56) * a.Cout * a.Cin + 8 : 0);      // ... its pair-order form last
+            w.p[g].w = a.wino_w[g] + wino_image_offset(f.image, a.Cout, a.Cin);
         }
-        w.variant = p.wino == 3 ? 1 : (p.wino == 4 ? 2 : (p.wino == 5 ? 3 : 0));
+        w.variant = f.variant;
         w.zeros = a.zeros;
         w.dbg = (long long*)a.dbg;
         w.groups = groups;
         w.B = a.B; w.H = a.Ho; w.W = a.Wo; w.Cin = a.Cin; w.Cout = a.Cout; w.relu = a.relu;
-        w.waves = (p.wino == 2 || p.wino == 4 || p.wino == 5 || p.wino == 7 || p.wino == 8 || p.wino == 9) ? 8 : 4;
-        w.tbx = cdiv(cdiv(a.Wo, 2), 8); w.tby = cdiv(cdiv(a.Ho, 2), w.waves);
-        if (p.wino == 9) {      // packing: the same workgroups, fewer of them — a property of the launch, not of the plan
+        w.waves = f.waves;
+        const WinoGrid wg = wino_grid(p.wino, a.Ho, a.Wo);
+        w.tbx = wg.tbx; w.tby = wg.tby;
+        if (p.wino == kWinoH3) {      // packing: the same workgroups, fewer of them — a property of the launch, not of the plan
             const WinoPackGeom q = wino_pack_geometry(a.Ho, a.Wo, a.B, a.Cin, a.wino_pack && !p.fold);
             if (q.G > 1) { w.pack = q.G; w.tbx = q.tbx; w.pack_rx = q.rx; }
             a.wino_blocks = q.patches * (a.Cout / 64) * groups;
         }
         if (p.fold) {      // c2 on Wc's image + up2(p3) on W's (the p2 input of .p[g] is not read)
-            if (p.wino != 9 || !a.fold_in) return FPC_EINVAL;
+            if (p.wino != kWinoH3 || !a.fold_in) return FPC_EINVAL;
             for (int g = 0; g < groups; ++g) {
                 w.in2[g] = a.fold_up[g]; w.w2[g] = a.fold_w2[g];
                 w.btab[g] = a.fold_tab[g];
@@ -693,116 +772,124 @@ int launch_conv_plan(ConvArgs& a, const ConvPlan& p, int groups, hipStream_t s) 
             }
             w.fold = 1; w.Cin2 = a.Cin; w.Cin = a.fold_cin;
         }
-        if (p.wino == 6) return a.Cout % 128 == 0 ? launch_conv_wino_c128(w, groups, s) : FPC_EINVAL;      // 8 x 4 tiles x 128 channels (wino128.hip)
-        if (p.wino == 7) return launch_conv_wino_w4(w, groups, s);
-        if (p.wino == 9) return launch_conv_wino_h3(w, groups, s);      // three fp16 piece products over pairs of K-steps (wino_h3.hip)
-        if (p.wino == 8) return launch_conv_wino_h2(w, groups, s);      // the same on two fp16 pieces per operand (wino_h2.hip)      // 8 x 8 tiles x 64 channels as four waves of 512 registers (wino_w4.hip)
-        return launch_conv_wino(w, groups, s);
+        return f.launch(w, groups, s);
     }
     a.bm = p.bm; a.bn = p.bn; a.nsplit = p.nsplit; a.mtiles = p.mtiles; a.ntiles = p.ntiles; a.groups = groups;
     a.bf3 = (p.bf3 && a.generic == 0) ? 1 : 0;
     a.fused = (p.fused && p.nsplit > 1) ? 1 : 0;
     a.h3 = 0;
+    ConvArgs h;
     if (p.h3) {      // the same launch on the site's k_pack_weight_h3 images (a is left as it was: the tuner reuses it)
         if (a.generic != 0) return FPC_EINVAL;
-        ConvArgs h = a;
+        h = a;
         h.bf3 = 0; h.h3 = 1;
         for (int g = 0; g < groups; ++g) {
             if (!a.h3_w[g]) return FPC_EINVAL;
             h.p[g].w = a.h3_w[g];
         }
-        int rc = launch_conv(h, groups, s);
-        if (!rc && h.nsplit > 1 && !h.fused) rc = launch_conv_splitk_epilogue(h, groups, s);
-        return rc;
     }
-    int rc = launch_conv(a, groups, s);
-    if (rc) return rc;
-    if (a.nsplit > 1 && !a.fused) rc = launch_conv_splitk_epilogue(a, groups, s);
+    const ConvArgs& l = p.h3 ? h : a;
+    int rc = launch_conv(l, groups, s);
+    if (!rc && l.nsplit > 1 && !l.fused) rc = launch_conv_splitk_epilogue(l, groups, s);
     return rc;
 }
 
 // number of GroupNorm partial rows per image a plan writes
 int plan_gn_rows(const ConvPlan& p, int Ho, int Wo, int B, int Cin, int pack) {
-    if (p.wino == 9) return wino_pack_geometry(Ho, Wo, B, Cin, pack && !p.fold).gn_rows;
-    return p.wino ? cdiv(cdiv(Wo, 2), 8) * cdiv(cdiv(Ho, 2), (p.wino == 2 || p.wino == 4 || p.wino == 5 || p.wino == 7 || p.wino == 8 || p.wino == 9) ? 8 : 4) : p.mtiles * p.bm / 32;
+    if (p.wino == kWinoH3) return wino_pack_geometry(Ho, Wo, B, Cin, pack && !p.fold).gn_rows;
+    return p.wino ? wino_grid(p.wino, Ho, Wo).patches() : p.mtiles * p.bm / 32;
 }
 
-// Runs conv site `ci` with its current plan; in tuning mode first times every candidate tiling
-// (HIP events on the stream, synchronising — only ever inside fpc_net_autotune) and keeps the fastest.
-int run_conv(fpc_net* n, ConvArgs& a, int groups, int ci, hipStream_t s) {
-    if (n && n->tuning) {
-        hipEvent_t e0, e1;
-        if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return FPC_ELAUNCH;
-        float best_ms = 1e30f;
-        ConvPlan best = n->cplan[ci];
-        size_t cap = n->splitk_floats;
-        std::vector<ConvPlan> cands = conv_candidates(a.Ho * a.Wo, a.B, a.Cout, a.ksteps, groups);
-        const size_t nf = cands.size();
-        if (n->split_precision && a.generic == 0) {          // the same tilings with split-precision matrix products
-            for (size_t i = 0; i < nf; ++i) { ConvPlan q = cands[i]; q.bf3 = 1; cands.push_back(q); }
+// Minimum elapsed time (ms) of `reps` runs of `run` (-> FPC_OK) on stream `s`, synchronising after each; 1e30 if it could not be
+// timed: such a candidate is never chosen.  The autotuner's clock; its events are gone on return.
+template <class F> float min_ms(hipStream_t s, int reps, F run) {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    float ms = 1e30f;
+    if (hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess)
+        for (int rep = 0; rep < reps; ++rep) {
+            float t = 0.f;
+            bool timed = hipEventRecord(e0, s) == hipSuccess && run() == FPC_OK && hipEventRecord(e1, s) == hipSuccess &&
+                         hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&t, e0, e1) == hipSuccess;
+            if (timed && t < ms) ms = t;
         }
-        if (n->split_precision >= 3 && a.generic == 0 && a.h3_w[0]) {      // ... and with the three fp16 piece products (level 3)
-            for (size_t i = 0; i < nf; ++i) { ConvPlan q = cands[i]; q.h3 = 1; cands.push_back(q); }
-        }
-        if (n->split_precision && groups == 1 && stem_ok(a)) {   // weight-resident stem (bf16 x 3 planes), one workgroup per CU
-            ConvPlan sq; sq.stem = 256; cands.push_back(sq);
-        }
-        if (n->split_precision && lateral_ok(a, groups)) {   // pixel-resident lateral product (bf16 x 3 planes)
-            const int tiles = groups * (a.Cout / 32);
-            for (int parts = 1; parts <= tiles; parts *= 2)
-                if (tiles % parts == 0) {
-                    ConvPlan lq; lq.lat = parts; cands.push_back(lq);
-                    if (n->split_precision >= 3 && a.h3_w[0]) { lq.h3 = 1; cands.push_back(lq); }      // ... on two fp16 pieces
-                }
-        }
-        if (n->split_precision && n->expansion == 4 && pw_ok(a, groups)) {      // the 1x1 GEMM (bf16 x 3 planes), Bottleneck plans only
-            ConvPlan pq;
-            pq.pw = 1; cands.push_back(pq);
-            pq.pw = 2; cands.push_back(pq);
-        }
-        if (a.wino_w[0] && !a.p[0].up) {
-            ConvPlan wq;
-            wq.wino = 1; cands.push_back(wq);
-            wq.wino = 2; cands.push_back(wq);
-            wq.wino = 3; cands.push_back(wq);
-            if (a.zeros) { wq.wino = 4; cands.push_back(wq); }
-            if (n->split_precision && a.zeros) { wq.wino = 5; cands.push_back(wq); }      // split-precision products, 8 waves
-            if (n->split_precision && a.Cout % 128 == 0) { wq.wino = 6; cands.push_back(wq); }      // ... 128 channels per workgroup, 4 waves
-            if (n->split_precision) { wq.wino = 7; cands.push_back(wq); }      // ... 64 channels, four waves of 512 registers, weights direct
-            // ... on two fp16 pieces (range-limited: fpc.h): all four piece products, or (level 3, Cin a multiple of 16) three of them over
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    return ms;
+}
+
+// The plans the autotuner times for the site `a` describes, in the order it times them (the first of equal scores is kept):
+// `split` = the plan's split-precision level, `expansion` = its encoder's block kind.
+std::vector<ConvPlan> tune_candidates(const ConvArgs& a, int groups, int split, int expansion) {
+    std::vector<ConvPlan> cands = conv_candidates(a.Ho * a.Wo, a.B, a.Cout, a.ksteps, groups);
+    const size_t nf = cands.size();
+    if (split && a.generic == 0) {          // the same tilings with split-precision matrix products
+        for (size_t i = 0; i < nf; ++i) { ConvPlan q = cands[i]; q.bf3 = 1; cands.push_back(q); }
+    }
+    if (split >= 3 && a.generic == 0 && a.h3_w[0]) {      // ... and with the three fp16 piece products (level 3)
+        for (size_t i = 0; i < nf; ++i) { ConvPlan q = cands[i]; q.h3 = 1; cands.push_back(q); }
+    }
+    if (split && groups == 1 && stem_ok(a)) {   // weight-resident stem (bf16 x 3 planes), one workgroup per CU
+        ConvPlan sq; sq.stem = 256; cands.push_back(sq);
+    }
+    if (split && lateral_ok(a, groups)) {   // pixel-resident lateral product (bf16 x 3 planes)
+        const int tiles = groups * (a.Cout / 32);
+        for (int parts = 1; parts <= tiles; parts *= 2)
+            if (tiles % parts == 0) {
+                ConvPlan lq; lq.lat = parts; cands.push_back(lq);
+                if (split >= 3 && a.h3_w[0]) { lq.h3 = 1; cands.push_back(lq); }      // ... on two fp16 pieces
+            }
+    }
+    if (split && expansion == 4 && pw_ok(a, groups)) {      // the 1x1 GEMM (bf16 x 3 planes), Bottleneck plans only
+        ConvPlan pq;
+        pq.pw = 1; cands.push_back(pq);
+        pq.pw = 2; cands.push_back(pq);
+    }
+    if (a.wino_w[0] && !a.p[0].up) {
+        auto offered = [&](int f) { return split >= kWinoForms[f].min_split && wino_form_ok(f, a.Cin, a.Cout) && (a.zeros || !kWinoForms[f].zeros); };
+        for (int f = 1; f < kWinoFormCount; ++f) {
+            // the fp16 x 2 forms (range-limited: fpc.h): all four piece products, or (level 3, Cin a multiple of 16) three of them over
             // pairs of K-steps.  Where the second form is allowed it REPLACES the first as a candidate: one launch timed from a cold
             // clock ranks them by their entry costs, the forward in steady state by their power (all sites on form 9 against all on
             // form 8: 14.05 / 14.58 and 14.21 / 15.04 ms on two boxes, while per-site timing picked form 9 for 2 of 33 sites)
-            if (n->split_precision >= 3 && a.Cin % 16 == 0) { wq.wino = 9; cands.push_back(wq); }
-            else if (n->split_precision >= 2) { wq.wino = 8; cands.push_back(wq); }
+            if (!offered(f) || (f == kWinoH2 && offered(kWinoH3))) continue;
+            ConvPlan wq; wq.wino = f; cands.push_back(wq);
         }
-        for (const ConvPlan& q : cands) {
-            if (splitk_floats_for(q, groups, a.B, a.Npad) > cap) continue;
+    }
+    return cands;
+}
+
+// Workgroups plan `q` launches on site `a` and the share of the chip's workgroup slots they take, held to [1/8, 1].
+struct PlanFootprint { double nblk, share; };
+PlanFootprint plan_footprint(const ConvPlan& q, const ConvArgs& a, int groups) {
+    double nblk = q.stem ? 512.0      // (a persistent 512-thread, 86 KB workgroup per CU: the whole chip, whatever its grid)
+                  : q.lat ? (double)cdiv(a.Ho * a.Wo, 128) * a.B * q.lat
+                  : q.pw ? (double)cdiv(a.B * a.Ho * a.Wo, pw_tile_pixels(q.pw - 1)) * (a.Cout / 64) * groups * q.pw      // (8-wave workgroups count twice)
+                  : q.wino == kWinoH3 ? (double)wino_pack_geometry(a.Ho, a.Wo, a.B, a.Cin, a.wino_pack && !q.fold).patches * (a.Cout / 64) * groups
+                  : q.wino ? (double)wino_grid(q.wino, a.Ho, a.Wo).patches() * a.B * (a.Cout / kWinoForms[q.wino].bn) * groups
+                         : (double)q.mtiles * q.ntiles * q.nsplit * a.B * groups;
+    double share = nblk / (256.0 * (q.wino ? kWinoForms[q.wino].wg_per_cu : 2));
+    if (share > 1.0) share = 1.0;
+    if (share < 0.125) share = 0.125;
+    return {nblk, share};
+}
+
+// Runs conv site `ci` with its current plan; in tuning mode first times every candidate (HIP events on the stream,
+// synchronising — only ever inside fpc_net_autotune): candidates, time each, keep the best, the fold challenger, launch.
+int run_conv(fpc_net* n, ConvArgs& a, int groups, int ci, hipStream_t s) {
+    if (n && n->tuning) {
+        float best_ms = 1e30f;
+        ConvPlan best = n->cplan[ci];
+        for (const ConvPlan& q : tune_candidates(a, groups, n->split_precision, n->expansion)) {
+            if (splitk_floats_for(q, groups, a.B, a.Npad) > n->splitk_floats) continue;
             int rc = launch_conv_plan(a, q, groups, s);     // warm-up (also validates the launch)
             if (rc == FPC_EINVAL) continue;                 // a candidate whose launcher refuses this site (its own preconditions) is skipped
-            if (rc) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return rc; }
-            float ms = 1e30f;
-            for (int rep = 0; rep < 3; ++rep) {
-                float t = 0.f;
-                bool timed = hipEventRecord(e0, s) == hipSuccess && launch_conv_plan(a, q, groups, s) == FPC_OK &&
-                             hipEventRecord(e1, s) == hipSuccess && hipEventSynchronize(e1) == hipSuccess &&
-                             hipEventElapsedTime(&t, e0, e1) == hipSuccess;
-                if (timed && t < ms) ms = t;             // a candidate that cannot be timed keeps ms = 1e30: never chosen
-            }
+            if (rc) return rc;
+            const float ms = min_ms(s, 3, [&] { return launch_conv_plan(a, q, groups, s); });
             // objective: latency, or (throughput mode) latency x the share of the chip the launch occupies —
             // with several frames in flight a launch that leaves CUs free lets another stream's kernels run
             float score = ms;
             if (n->tune_mode >= 1) {
-                double nblk = q.stem ? 512.0      // (a persistent 512-thread, 86 KB workgroup per CU: the whole chip, whatever its grid)
-                              : q.lat ? (double)cdiv(a.Ho * a.Wo, 128) * a.B * q.lat
-                              : q.pw ? (double)cdiv(a.B * a.Ho * a.Wo, pw_tile_pixels(q.pw - 1)) * (a.Cout / 64) * groups * q.pw      // (8-wave workgroups count twice)
-                              : q.wino == 9 ? (double)wino_pack_geometry(a.Ho, a.Wo, a.B, a.Cin, a.wino_pack && !q.fold).patches * (a.Cout / 64) * groups
-                              : q.wino ? (double)cdiv(cdiv(a.Wo, 2), 8) * cdiv(cdiv(a.Ho, 2), (q.wino == 2 || q.wino == 4 || q.wino == 5 || q.wino == 7 || q.wino == 8 || q.wino == 9) ? 8 : 4) * a.B * (a.Cout / (q.wino == 6 ? 128 : 64)) * groups
-                                     : (double)q.mtiles * q.ntiles * q.nsplit * a.B * groups;
-                double slots = 256.0 * ((q.wino == 2 || q.wino == 4 || q.wino == 5 || q.wino == 6 || q.wino == 7 || q.wino == 8 || q.wino == 9) ? 1.0 : 2.0);
-                double share = nblk / slots;
-                if (share > 1.0) share = 1.0;
-                if (share < 0.125) share = 0.125;
+                const double share = plan_footprint(q, a, groups).share;
                 score = ms * (float)(n->tune_mode == 2 ? share : sqrt(share));      // 2: latency x share = the launch's CU-time
             }
             if (score < best_ms) { best_ms = score; best = q; }
@@ -812,26 +899,17 @@ int run_conv(fpc_net* n, ConvArgs& a, int groups, int ci, hipStream_t s) {
         // of both best scores (the lateral's was taken earlier in this pass).  Same timing rule as above; the whole chip: score = ms.
         if (n->split_precision >= 3 && a.fold_in && a.fold_lat_ms > 0.f) {
             ConvPlan fq;
-            fq.wino = 9; fq.fold = 1;
+            fq.wino = kWinoH3; fq.fold = 1;
             int rc = launch_conv_plan(a, fq, groups, s);
-            if (rc && rc != FPC_EINVAL) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return rc; }
-            float ms = 1e30f;
-            for (int rep = 0; rep < 3 && !rc; ++rep) {
-                float t = 0.f;
-                bool timed = hipEventRecord(e0, s) == hipSuccess && launch_conv_plan(a, fq, groups, s) == FPC_OK &&
-                             hipEventRecord(e1, s) == hipSuccess && hipEventSynchronize(e1) == hipSuccess &&
-                             hipEventElapsedTime(&t, e0, e1) == hipSuccess;
-                if (timed && t < ms) ms = t;
-            }
+            if (rc && rc != FPC_EINVAL) return rc;
+            const float ms = rc ? 1e30f : min_ms(s, 3, [&] { return launch_conv_plan(a, fq, groups, s); });
             if (ms < best_ms + a.fold_lat_ms) best = fq;
         }
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
         n->cplan[ci] = best;
     }
     ConvPlan p = n ? n->cplan[ci] : ConvPlan{a.bm, a.bn, a.nsplit, a.mtiles, a.ntiles, 0, a.bf3, a.fused};
     const int rc = launch_conv_plan(a, p, groups, s);
-    if (n && !rc && p.wino == 9) n->wino_blocks += a.wino_blocks;
+    if (n && !rc && p.wino == kWinoH3) n->wino_blocks += a.wino_blocks;
     return rc;
 }
 
@@ -886,28 +964,28 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
             // level 3: the fused launch against the site's best plan AND the max-pool together (it replaces both), timed as the p2
             // fold is; the whole chip: score = ms.  Kept only when it beats them
             if (n->tuning && n->split_precision >= 3 && launch_stem_pool(a, h3img, ws + n->a_pool.off, n->a_pool.H, n->a_pool.W, s) == FPC_OK) {
-                hipEvent_t e0, e1;
-                if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return FPC_ELAUNCH;
                 const ConvPlan cur = n->cplan[n->c_stem];
                 float ms_pair = 1e30f, ms_fused = 1e30f;
-                for (int rep = 0; rep < 6; ++rep) {
-                    const bool fused = rep & 1;
-                    float t = 0.f;
-                    bool timed = hipEventRecord(e0, s) == hipSuccess &&
-                                 (fused ? launch_stem_pool(a, h3img, ws + n->a_pool.off, n->a_pool.H, n->a_pool.W, s) == FPC_OK
-                                        : (launch_conv_plan(a, cur, 1, s) == FPC_OK && pool_launch() == FPC_OK)) &&
-                                 hipEventRecord(e1, s) == hipSuccess && hipEventSynchronize(e1) == hipSuccess &&
-                                 hipEventElapsedTime(&t, e0, e1) == hipSuccess;
-                    if (timed && fused && t < ms_fused) ms_fused = t;
-                    if (timed && !fused && t < ms_pair) ms_pair = t;
+                for (int rep = 0; rep < 3; ++rep) {      // six runs, the two sides in turn
+                    ms_pair = std::min(ms_pair, min_ms(s, 1, [&] { int rc = launch_conv_plan(a, cur, 1, s); return rc ? rc : pool_launch(); }));
+                    ms_fused = std::min(ms_fused, min_ms(s, 1, [&] { return launch_stem_pool(a, h3img, ws + n->a_pool.off, n->a_pool.H, n->a_pool.W, s); }));
                 }
-                (void)hipEventDestroy(e0);
-                (void)hipEventDestroy(e1);
                 if (ms_fused < ms_pair) { ConvPlan q; q.stem = 256; q.pool = 1; n->cplan[n->c_stem] = q; }
             }
         }
     }
-    // encoder stages
+    // encoder stages.  One site: conv `ci` from `in` to `out` with BatchNorm, the residual and ReLU in its epilogue, on whichever
+    // images the site has
+    auto enc_conv = [&](int ci, const Act& in, const Act& out, bool relu, const float* res) -> int {
+        long long sb, sh, sw, sc;
+        nhwc(in, sb, sh, sw, sc);
+        const PackedConv& c = n->convs[ci];
+        fill_conv_args(n, a, c, n->cplan[ci], in.H, in.W, out.H, out.W, sb, sh, sw, sc, relu, 0);
+        a.p[0] = ConvPtrs{ws + in.off, ws + c.w_off, ws + out.off, ws + c.scale_off, ws + c.shift_off, res, nullptr, nullptr};
+        if (c.wino_ok) a.wino_w[0] = ws + c.wino_off;
+        if (c.h3_ok && n->h3_packed) a.h3_w[0] = ws + c.h3_off;
+        return run_conv(n, a, 1, ci, s);
+    };
     Act cur = n->a_pool;
     Act feat[4];
     for (int L = 0; L < 4; ++L) {
@@ -915,63 +993,27 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
             const fpc_net::Block& blk = n->blocks[L][bi];
             const Act& T = n->a_blk_t[L][bi];
             const Act& Y = n->a_blk_y[L][bi];
-            long long sb, sh, sw, sc;
+            const float* res = ws + cur.off;
             if (n->expansion == 4) {
                 // Bottleneck: conv1 (1x1, BN + ReLU) -> conv2 (3x3 with the stride, BN + ReLU), the downsample (1x1, stride, BN),
                 // conv3 (1x1, BN + residual + ReLU)
                 const Act& T2 = n->a_blk_t2[L][bi];
-                nhwc(cur, sb, sh, sw, sc);
-                const PackedConv& c1 = n->convs[blk.conv1];
-                fill_conv_args(n, a, c1, n->cplan[blk.conv1], cur.H, cur.W, T.H, T.W, sb, sh, sw, sc, true, 0);
-                a.p[0] = ConvPtrs{ws + cur.off, ws + c1.w_off, ws + T.off, ws + c1.scale_off, ws + c1.shift_off, nullptr, nullptr, nullptr};
-                FPC_TRY(run_conv(n, a, 1, blk.conv1, s));
-                long long tb, th, tw, tc;
-                nhwc(T, tb, th, tw, tc);
-                const PackedConv& c2 = n->convs[blk.conv2];
-                fill_conv_args(n, a, c2, n->cplan[blk.conv2], T.H, T.W, T2.H, T2.W, tb, th, tw, tc, true, 0);
-                a.p[0] = ConvPtrs{ws + T.off, ws + c2.w_off, ws + T2.off, ws + c2.scale_off, ws + c2.shift_off, nullptr, nullptr, nullptr};
-                if (c2.wino_ok) a.wino_w[0] = ws + c2.wino_off;
-                FPC_TRY(run_conv(n, a, 1, blk.conv2, s));
-                const float* res = ws + cur.off;
+                FPC_TRY(enc_conv(blk.conv1, cur, T, true, nullptr));
+                FPC_TRY(enc_conv(blk.conv2, T, T2, true, nullptr));
                 if (blk.ds >= 0) {
-                    const PackedConv& cd = n->convs[blk.ds];
-                    const Act& D = n->a_blk_d[L][bi];
-                    fill_conv_args(n, a, cd, n->cplan[blk.ds], cur.H, cur.W, D.H, D.W, sb, sh, sw, sc, false, 0);
-                    a.p[0] = ConvPtrs{ws + cur.off, ws + cd.w_off, ws + D.off, ws + cd.scale_off, ws + cd.shift_off, nullptr, nullptr, nullptr};
-                    FPC_TRY(run_conv(n, a, 1, blk.ds, s));
-                    res = ws + D.off;
+                    FPC_TRY(enc_conv(blk.ds, cur, n->a_blk_d[L][bi], false, nullptr));
+                    res = ws + n->a_blk_d[L][bi].off;
                 }
-                nhwc(T2, tb, th, tw, tc);
-                const PackedConv& c3 = n->convs[blk.conv3];
-                fill_conv_args(n, a, c3, n->cplan[blk.conv3], T2.H, T2.W, Y.H, Y.W, tb, th, tw, tc, true, 0);
-                a.p[0] = ConvPtrs{ws + T2.off, ws + c3.w_off, ws + Y.off, ws + c3.scale_off, ws + c3.shift_off, res, nullptr, nullptr};
-                FPC_TRY(run_conv(n, a, 1, blk.conv3, s));
+                FPC_TRY(enc_conv(blk.conv3, T2, Y, true, res));
                 cur = Y;
                 continue;
             }
-            nhwc(cur, sb, sh, sw, sc);
-            const PackedConv& c1 = n->convs[blk.conv1];
-            fill_conv_args(n, a, c1, n->cplan[blk.conv1], cur.H, cur.W, T.H, T.W, sb, sh, sw, sc, true, 0);
-            a.p[0] = ConvPtrs{ws + cur.off, ws + c1.w_off, ws + T.off, ws + c1.scale_off, ws + c1.shift_off, nullptr, nullptr, nullptr};
-            if (c1.wino_ok) a.wino_w[0] = ws + c1.wino_off;
-            if (c1.h3_ok && n->h3_packed) a.h3_w[0] = ws + c1.h3_off;
-            FPC_TRY(run_conv(n, a, 1, blk.conv1, s));
-            const float* res = ws + cur.off;
+            FPC_TRY(enc_conv(blk.conv1, cur, T, true, nullptr));
             if (blk.ds >= 0) {
-                const PackedConv& cd = n->convs[blk.ds];
-                const Act& D = n->a_blk_d[L][bi];
-                fill_conv_args(n, a, cd, n->cplan[blk.ds], cur.H, cur.W, D.H, D.W, sb, sh, sw, sc, false, 0);
-                a.p[0] = ConvPtrs{ws + cur.off, ws + cd.w_off, ws + D.off, ws + cd.scale_off, ws + cd.shift_off, nullptr, nullptr, nullptr};
-                if (cd.h3_ok && n->h3_packed) a.h3_w[0] = ws + cd.h3_off;
-                FPC_TRY(run_conv(n, a, 1, blk.ds, s));
-                res = ws + D.off;
+                FPC_TRY(enc_conv(blk.ds, cur, n->a_blk_d[L][bi], false, nullptr));
+                res = ws + n->a_blk_d[L][bi].off;
             }
-            nhwc(T, sb, sh, sw, sc);
-            const PackedConv& c2 = n->convs[blk.conv2];
-            fill_conv_args(n, a, c2, n->cplan[blk.conv2], T.H, T.W, Y.H, Y.W, sb, sh, sw, sc, true, 0);
-            a.p[0] = ConvPtrs{ws + T.off, ws + c2.w_off, ws + Y.off, ws + c2.scale_off, ws + c2.shift_off, res, nullptr, nullptr};
-            if (c2.wino_ok) a.wino_w[0] = ws + c2.wino_off;
-            FPC_TRY(run_conv(n, a, 1, blk.conv2, s));
+            FPC_TRY(enc_conv(blk.conv2, T, Y, true, res));
             cur = Y;
         }
         feat[L] = cur;
@@ -1188,7 +1230,7 @@ extern "C" int fpc_net_autotune_next(fpc_net_t* n, int mode) {
     if (!n || !n->loaded || mode < 0 || mode > 2) return FPC_EINVAL;
     n->tuning = true;
     n->tune_mode = mode;
-    if (n->graph_exec) { (void)hipGraphExecDestroy(n->graph_exec); n->graph_exec = nullptr; }      // tilings may change
+    drop_graph(n);      // tilings may change
     return FPC_OK;
 }
 
@@ -1197,33 +1239,32 @@ extern "C" int fpc_net_autotune_next(fpc_net_t* n, int mode) {
 extern "C" int fpc_net_conv_count(const fpc_net_t* n) { return n ? (int)n->convs.size() : 0; }
 extern "C" int fpc_net_conv_plan(const fpc_net_t* n, int i, int* out5) {
     if (!n || !out5 || i < 0 || i >= (int)n->convs.size()) return FPC_EINVAL;
-    out5[0] = n->cplan[i].bm; out5[1] = n->cplan[i].bn; out5[2] = n->cplan[i].wino ? -n->cplan[i].wino : n->cplan[i].nsplit;
-    if (n->cplan[i].lat) { out5[0] = 128; out5[1] = 32; out5[2] = 2000 + n->cplan[i].lat; }      // k_lateral1x1 (fpc_conv2d's hook value)
-    if (n->cplan[i].stem) { out5[0] = 64; out5[1] = 64; out5[2] = n->cplan[i].pool ? 3100 : 3000; }      // k_stem7x7 / k_stem_pool_h3 (with the max-pool)
-    if (n->cplan[i].pw) { out5[0] = pw_tile_pixels(n->cplan[i].pw - 1); out5[1] = 64; out5[2] = 4000 + n->cplan[i].pw - 1; }      // k_conv1x1
-    // the three-product form: k_conv_igemm 6000 + split (fused or not, as the plain tilings), k_lateral1x1 7000 + parts
-    if (n->cplan[i].h3) out5[2] = n->cplan[i].lat ? 7000 + n->cplan[i].lat : 6000 + n->cplan[i].nsplit;
-    if (n->fold_ok && i == n->dec[0].lat[3] && n->cplan[n->dec[0].seg[6]].fold) out5[2] = 5000;      // the p2 lateral, folded into s2.0
+    const ConvPlan& p = n->cplan[i];
+    out5[0] = p.bm; out5[1] = p.bn;
+    if (p.lat) { out5[0] = 128; out5[1] = 32; }      // k_lateral1x1
+    if (p.stem) { out5[0] = 64; out5[1] = 64; }      // k_stem7x7 / k_stem_pool_h3 (with the max-pool)
+    if (p.pw) { out5[0] = pw_tile_pixels(p.pw - 1); out5[1] = 64; }      // k_conv1x1
+    out5[2] = encode_plan(p, n->fold_ok && i == n->dec[0].lat[3] && n->cplan[n->dec[0].seg[6]].fold);
     out5[3] = n->convs[i].Cout; out5[4] = n->convs[i].K;
     return FPC_OK;
 }
 
-// Every 3x3 / stride-1 site that has Winograd images -> Winograd form `form` (1..8, fpc_conv2d's -form; 6 only where Cout % 128 == 0,
-// other sites keep their plan): tests run the whole network on ONE form (e.g. 8: every eligible product on fp16 x 2 pieces) and
+// Every 3x3 / stride-1 site that has Winograd images -> Winograd form `form` (1..9, fpc_conv2d's -form; wino_form_ok: 6 only where
+// Cout % 128 == 0, 9 only where Cin % 16 == 0; other sites keep their plan): tests run the whole network on ONE form (e.g. 8: every eligible product on fp16 x 2 pieces) and
 // hold it to the float64 bars.  Returns the number of sites changed, or a negative code.  Drops the recorded graph.
 extern "C" int fpc_net_force_winograd(fpc_net_t* n, int form) {
-    if (!n || form < 1 || form > 9) return FPC_EINVAL;
+    if (!n || form < 1 || form >= kWinoFormCount) return FPC_EINVAL;
     int changed = 0;
     for (size_t i = 0; i < n->convs.size(); ++i) {
         const PackedConv& c = n->convs[i];
-        if (!c.wino_ok || !n->c_groups[i] || (form == 6 && c.Cout % 128 != 0) || (form == 9 && c.Cin % 16 != 0)) continue;
+        if (!c.wino_ok || !n->c_groups[i] || !wino_form_ok(form, c.Cin, c.Cout)) continue;
         ConvPlan q = n->cplan[i];
         q.wino = form; q.lat = 0; q.stem = 0;
-        if (form != 9) q.fold = 0;      // (form 9 keeps s2.0's fold: it runs on that form)
+        if (form != kWinoH3) q.fold = 0;      // (form 9 keeps s2.0's fold: it runs on that form)
         n->cplan[i] = q;
         ++changed;
     }
-    if (n->graph_exec) { (void)hipGraphExecDestroy(n->graph_exec); n->graph_exec = nullptr; }
+    drop_graph(n);
     return changed;
 }
 
@@ -1234,9 +1275,9 @@ extern "C" int fpc_net_force_fold(fpc_net_t* n, int on) {
     ConvPlan& p = n->cplan[n->dec[0].seg[6]];
     if (p.fold == on) return 0;
     ConvPlan q;
-    q.wino = 9; q.fold = on;
+    q.wino = kWinoH3; q.fold = on;
     p = q;
-    if (n->graph_exec) { (void)hipGraphExecDestroy(n->graph_exec); n->graph_exec = nullptr; }
+    drop_graph(n);
     return 1;
 }
 
@@ -1260,7 +1301,7 @@ extern "C" int fpc_net_force_pointwise(fpc_net_t* n, int on) {
         }
         ++changed;
     }
-    if (n->graph_exec) { (void)hipGraphExecDestroy(n->graph_exec); n->graph_exec = nullptr; }
+    drop_graph(n);
     return changed;
 }
 
@@ -1281,7 +1322,7 @@ extern "C" int fpc_net_force_direct_h3(fpc_net_t* n, int on) {
         n->cplan[i] = q;
         ++changed;
     }
-    if (n->graph_exec) { (void)hipGraphExecDestroy(n->graph_exec); n->graph_exec = nullptr; }
+    drop_graph(n);
     return changed;
 }
 
@@ -1296,7 +1337,7 @@ extern "C" int fpc_net_force_stem_pool(fpc_net_t* n, int on) {
     ConvPlan q;
     q.stem = 256; q.pool = on;
     p = q;
-    if (n->graph_exec) { (void)hipGraphExecDestroy(n->graph_exec); n->graph_exec = nullptr; }
+    drop_graph(n);
     return 1;
 }
 
@@ -1319,7 +1360,7 @@ extern "C" int fpc_net_copy_plans(fpc_net_t* dst, const fpc_net_t* src) {
         dst->cplan[i] = q;
     }
     dst->tuned = true;
-    if (dst->graph_exec) { (void)hipGraphExecDestroy(dst->graph_exec); dst->graph_exec = nullptr; }
+    drop_graph(dst);
     return FPC_OK;
 }
 
@@ -1397,51 +1438,11 @@ extern "C" size_t fpc_conv2d_workspace_bytes(int B, int Ho, int Wo, int Cin, int
     int K = Cin * Kh * Kw, Kpad = cdiv(K, kConvBK) * kConvBK, Npad = cdiv(Cout, kConvNAlign) * kConvNAlign;
     size_t packed = conv_packed_floats(Npad, Kpad);
     size_t splitk = (size_t)32 * B * (cdiv(Ho * Wo, 128) * 128) * Npad;
-    size_t wino = (size_t)96 * Cout * Cin + 128;      // f32 + split-precision (two layouts) Winograd images + a zero page for the all-DMA form
+    size_t wino = wino_region_floats(kImgH3, Cout, Cin, true);      // every Winograd image + a zero page for the all-DMA form
     return (packed + splitk + wino + kConvTickets) * sizeof(float);
 }
 
-extern "C" int fpc_conv2d_plan(int B, int Ho, int Wo, int Cin, int Cout, int Kh, int Kw, int bm, int bn, int nsplit,
-                               int* out4) {
-    if (!out4) return FPC_EINVAL;
-    int Kpad = cdiv(Cin * Kh * Kw, kConvBK) * kConvBK;
-    if (nsplit >= 6000 && nsplit < 6200) nsplit -= 6000;      // the three-product form keeps the tiling (100 + split: two launches)
-    if (nsplit >= 2000) nsplit = 1;          // k_lateral1x1 / k_stem7x7 / k_conv1x1: no split-K, no GroupNorm rows
-    if (nsplit >= 1000) nsplit -= 1000;      // fpc_conv2d's split-precision / two-launch hooks do not change the tiling
-    if (nsplit >= 100) nsplit -= 100;
-    const int pack = nsplit == -10;      // form 9 on the packed geometry
-    if (pack) nsplit = -9;
-    ConvPlan p = plan_conv(Ho * Wo, B, Cout, Kpad / kConvBK, 1, bm, bn, nsplit);
-    if (nsplit <= -1 && nsplit >= -9) { p.wino = -nsplit; p.nsplit = pack ? -10 : nsplit; }
-    out4[0] = p.bm; out4[1] = p.bn; out4[2] = p.nsplit; out4[3] = plan_gn_rows(p, Ho, Wo, B, Cin, pack);
-    return FPC_OK;
-}
-
 namespace {
-// the hooks folded into fpc_conv2d's `nsplit` argument
-struct Conv2dRequest { int nsplit; bool bf3, two_launch, wino; int lat; bool stem; int pw; bool h3; bool pool; bool pack; };
-Conv2dRequest conv2d_request(int nsplit) {
-    Conv2dRequest r{nsplit, false, false, false, 0, false, 0, false, false, false};
-    if (r.nsplit == -10) { r.pack = true; r.nsplit = -9; }      // -10: form -9 with its patches cut out of canvas rows of several frames (wino_pack_geometry)
-    if (r.nsplit >= 7000 && r.nsplit < 8000) { r.lat = r.nsplit - 7000; r.h3 = true; r.nsplit = 1; return r; }      // 7000 + parts = k_lateral1x1 on two fp16 pieces
-    if (r.nsplit >= 6000 && r.nsplit < 6200) {      // 6000 + split = k_conv_igemm's three-product form (fused split-K), 6100 + split: two launches
-        r.h3 = true; r.nsplit -= 6000;
-        if (r.nsplit >= 100) { r.two_launch = true; r.nsplit -= 100; }
-        return r;
-    }
-    if (r.nsplit >= 4000) { r.pw = r.nsplit - 4000 + 1; r.bf3 = true; r.nsplit = 1; return r; }   // 4000 + variant = k_conv1x1 (pointwise.hip)
-    if (r.nsplit == 3100) { r.stem = true; r.pool = true; r.h3 = true; r.nsplit = 1; return r; }     // 3100 = k_stem_pool_h3: NHWC4 input, `out` = the POOLED tensor
-    if (r.nsplit == 3000) { r.stem = true; r.bf3 = true; r.nsplit = 1; return r; }                   // 3000 = k_stem7x7 (stem.hip): NHWC4 input
-    if (r.nsplit >= 2000) { r.lat = r.nsplit - 2000; r.bf3 = true; r.nsplit = 1; return r; }      // 2000 + parts = k_lateral1x1 (lateral.hip)
-    if (r.nsplit >= 1000) { r.bf3 = true; r.nsplit -= 1000; }          // 1000 + split = split-precision matrix products
-    if (r.nsplit >= 100) { r.two_launch = true; r.nsplit -= 100; }      // 100 + split = split-K summed by k_conv_splitk_epilogue
-    // -1: 4 waves, -2: 8 waves, -3: wave-private, -4: all-DMA 3-stage, -5: 8 waves split precision, -6: split precision, 128 channels per workgroup
-    // -7: split precision, 64 channels, four waves of 512 registers (the -5 image)
-    // -8: the -7 form on two fp16 pieces per operand (its own image)
-    // -9: three of the four products of -8, over pairs of K-steps (its own image; Cin a multiple of 16)
-    r.wino = r.nsplit <= -1 && r.nsplit >= -9;
-    return r;
-}
 // workspace of ONE fpc_conv2d call (floats): [packed weights | split-K partials of this plan | Winograd images + zero page |
 // arrival counters]; regions a plan does not use are empty
 struct Conv2dLayout { size_t packed, splitk, wino, tickets, total; };
@@ -1450,7 +1451,7 @@ Conv2dLayout conv2d_layout(int B, int Cin, int Cout, int Kh, int Kw, const ConvP
     Conv2dLayout L;
     L.packed = r.wino ? 0 : conv_packed_floats(Npad, Kpad);
     L.splitk = r.wino ? 0 : (splitk_floats_for(p, 1, B, Npad) + 63) / 64 * 64;
-    L.wino = r.wino ? (size_t)(r.nsplit == -9 ? (Cout % 128 == 0 ? 96 : 72) : r.nsplit == -8 ? (Cout % 128 == 0 ? 80 : 56) : r.nsplit == -6 ? 64 : (r.nsplit == -5 || r.nsplit == -7) ? 40 : 16) * Cout * Cin + 128 : 0;
+    L.wino = r.wino ? wino_region_floats(kWinoForms[r.wino].image, Cout, Cin, Cout % 128 == 0) : 0;      // up to the image the form reads
     L.tickets = (!r.wino && p.fused && p.nsplit > 1) ? kConvTickets : 0;
     L.total = L.packed + L.splitk + L.wino + L.tickets;
     return L;
@@ -1465,16 +1466,30 @@ ConvPlan conv2d_plan_for(int B, int Ho, int Wo, int Cin, int Cout, int Kh, int K
     p.stem = r.stem ? 256 : 0;
     p.pool = r.pool ? 1 : 0;
     p.pw = r.pw;
+    p.wino = r.wino;
     return p;
 }
 }  // namespace
+
+extern "C" int fpc_conv2d_plan(int B, int Ho, int Wo, int Cin, int Cout, int Kh, int Kw, int bm, int bn, int nsplit,
+                               int* out4) {
+    if (!out4) return FPC_EINVAL;
+    const int Kpad = cdiv(Cin * Kh * Kw, kConvBK) * kConvBK;
+    // whatever kernel or product the request selects, the tiling reported is k_conv_igemm's with the request's split-K factor (no
+    // GroupNorm rows of its own for k_lateral1x1 / k_stem7x7 / k_conv1x1); a Winograd request: 64 x 64, the request, the form's rows
+    const Conv2dRequest r = decode_plan(nsplit);
+    ConvPlan p = plan_conv(Ho * Wo, B, Cout, Kpad / kConvBK, 1, bm, bn, r.nsplit);
+    p.wino = r.wino;
+    out4[0] = p.bm; out4[1] = p.bn; out4[2] = r.wino ? nsplit : p.nsplit; out4[3] = plan_gn_rows(p, Ho, Wo, B, Cin, r.pack);
+    return FPC_OK;
+}
 
 // Exact workspace of fpc_conv2d for ONE request (same bm / bn / nsplit): at most fpc_conv2d_workspace_bytes, usually far
 // less (that bound reserves 32 split-K slices of the whole output).  fpc_conv2d accepts either.
 extern "C" size_t fpc_conv2d_workspace_bytes_for(int B, int Ho, int Wo, int Cin, int Cout, int Kh, int Kw, int bm, int bn,
                                                  int nsplit) {
     if (B < 1 || Ho < 1 || Wo < 1 || Cin < 1 || Cout < 1 || Kh < 1 || Kw < 1) return 0;
-    const Conv2dRequest r = conv2d_request(nsplit);
+    const Conv2dRequest r = decode_plan(nsplit);
     const ConvPlan p = conv2d_plan_for(B, Ho, Wo, Cin, Cout, Kh, Kw, bm, bn, r);
     return std::max<size_t>(conv2d_layout(B, Cin, Cout, Kh, Kw, p, r).total * sizeof(float), 256);
 }
@@ -1486,9 +1501,8 @@ extern "C" int fpc_conv2d(const float* in, int64_t sb, int64_t sh, int64_t sw, i
     if (!in || !w_oihw || !out || !ws || B < 1 || Kh != Kw) return FPC_EINVAL;
     int Ho = conv_out(Hi, Kh, stride, pad), Wo = conv_out(Wi, Kw, stride, pad);
     if (Ho < 1 || Wo < 1) return FPC_EINVAL;
-    const Conv2dRequest rq = conv2d_request(nsplit);
-    nsplit = rq.nsplit;
-    const bool wino = rq.wino;
+    const Conv2dRequest rq = decode_plan(nsplit);
+    const int wino = rq.wino;
     ConvPlan p = conv2d_plan_for(B, Ho, Wo, Cin, Cout, Kh, Kw, bm, bn, rq);
     const Conv2dLayout lay = conv2d_layout(B, Cin, Cout, Kh, Kw, p, rq);
     if (ws_bytes < lay.total * sizeof(float) || ((uintptr_t)ws & 255)) return FPC_EWORKSPACE;
@@ -1502,32 +1516,21 @@ extern "C" int fpc_conv2d(const float* in, int64_t sb, int64_t sh, int64_t sw, i
             sb != (int64_t)4 * Hi * Wi || res || up || gn_part)
             return FPC_EINVAL;
         c.Kwp = 8; c.K = 4 * 7 * 8; c.Kpad = 224;
-        if (rq.pool) {      // conv + BN + ReLU + max-pool 3x3 / 2 / 1 in one launch: out is [B][Ho / 2][Wo / 2][64]
-            FPC_TRY(launch_pack_weight_h3(w_oihw, packed, Cout, Cin, Cin, Kh, Kw, c.Kwp, c.Npad, c.Kpad, s));
-            fpc_net tmp1;
-            tmp1.B = B; tmp1.ws = packed; tmp1.splitk_off = lay.packed;
-            ConvArgs a1;
-            fill_conv_args(&tmp1, a1, c, p, Hi, Wi, Ho, Wo, sb, sh, sw, sc, relu != 0, 0);
-            a1.Cin = 8 * c.Cinp; a1.Kw = 1; a1.K = c.K; a1.lanepx = 1;
-            a1.p[0] = ConvPtrs{in, packed, out, scale, shift, nullptr, nullptr, nullptr};
-            return launch_stem_pool(a1, packed, out, Ho / 2, Wo / 2, s);
-        }
-        FPC_TRY(launch_pack_weight_bf3(w_oihw, packed, Cout, Cin, Cin, Kh, Kw, c.Kwp, c.Npad, c.Kpad, s));
+        // pool: conv + BN + ReLU + max-pool 3x3 / 2 / 1 in one launch on the h3 image: out is [B][Ho / 2][Wo / 2][64]
+        FPC_TRY((rq.pool ? launch_pack_weight_h3 : launch_pack_weight_bf3)(w_oihw, packed, Cout, Cin, Cin, Kh, Kw, c.Kwp, c.Npad, c.Kpad, s));
         fpc_net tmp0;
         tmp0.B = B; tmp0.ws = packed; tmp0.splitk_off = lay.packed;
         ConvArgs a0;
         fill_conv_args(&tmp0, a0, c, p, Hi, Wi, Ho, Wo, sb, sh, sw, sc, relu != 0, 0);
         a0.Cin = 8 * c.Cinp; a0.Kw = 1; a0.K = c.K; a0.lanepx = 1;
         a0.p[0] = ConvPtrs{in, packed, out, scale, shift, nullptr, nullptr, nullptr};
-        return launch_conv_plan(a0, p, 1, s);
+        return rq.pool ? launch_stem_pool(a0, packed, out, Ho / 2, Wo / 2, s) : launch_conv_plan(a0, p, 1, s);
     }
     // (the split-precision forms — bf16 x 3 tiles, k_lateral1x1 — read only the planes behind the f32 image: it is not packed for them)
     static_assert(FPC_IGEMM_DMA_B, "the split-precision direct form stages its B rows from the bf16 planes by LDS-DMA; a build that loads "
                                    "them from the f32 image must pack that image here as well");
     // (the three-product form reads its own image at the start of the packed region: conv_packed_floats() > h3_packed_floats())
-    if (!wino && !p.bf3 && !p.h3) FPC_TRY(launch_pack_weight(w_oihw, packed, Cout, Cin, Cin, Kh, Kw, Kw, c.Npad, c.Kpad, s));
-    if (!wino && p.bf3) FPC_TRY(launch_pack_weight_bf3(w_oihw, packed, Cout, Cin, Cin, Kh, Kw, Kw, c.Npad, c.Kpad, s));
-    if (!wino && p.h3) FPC_TRY(launch_pack_weight_h3(w_oihw, packed, Cout, Cin, Cin, Kh, Kw, Kw, c.Npad, c.Kpad, s));
+    if (!wino) FPC_TRY((p.h3 ? launch_pack_weight_h3 : p.bf3 ? launch_pack_weight_bf3 : launch_pack_weight)(w_oihw, packed, Cout, Cin, Cin, Kh, Kw, Kw, c.Npad, c.Kpad, s));
     int mode = (sc == 1 && Cin % kConvBK == 0 && Kh * Kw <= 32 && ((int64_t)Hi + 2 * pad) * sh * 4 < ((int64_t)1 << 31)) ? 0
                : (sc == 1 && Cin % 4 == 0 && sw % 4 == 0 && sh % 4 == 0 && sb % 4 == 0 && ((uintptr_t)in & 15) == 0) ? 2 : 1;
     fpc_net tmp;
@@ -1554,13 +1557,10 @@ extern "C" int fpc_conv2d(const float* in, int64_t sb, int64_t sh, int64_t sw, i
             sh != (int64_t)Wi * Cin || sb != (int64_t)Hi * Wi * Cin)
             return FPC_EINVAL;
         float* wp = packed + lay.packed + lay.splitk;
-        // (the split-precision form reads only its own image: the f32 image is not packed for it — 78 launches of a training step)
-        if (nsplit == -6 && Cout % 128) return FPC_EINVAL;
-        if (nsplit > -5) FPC_TRY(launch_wino_pack(w_oihw, wp, Cout, Cin, s));
-        if (nsplit == -5 || nsplit == -7) FPC_TRY(launch_wino_pack_bf3(w_oihw, wp + (size_t)16 * Cout * Cin, Cout, Cin, s));
-        if (nsplit == -6) FPC_TRY(launch_wino_pack_c128(w_oihw, wp + (size_t)40 * Cout * Cin, Cout, Cin, s));
-        if (nsplit == -9) FPC_TRY(launch_wino_pack_h3(w_oihw, wp + (size_t)(Cout % 128 == 0 ? 80 : 56) * Cout * Cin + 8, Cout, Cin, s));
-        if (nsplit == -8) FPC_TRY(launch_wino_pack_h2(w_oihw, wp + (size_t)(Cout % 128 == 0 ? 64 : 40) * Cout * Cin, Cout, Cin, s));
+        // (a form reads only its own image: the f32 image is not packed for a split-precision form — 78 launches of a training step)
+        if (!wino_form_ok(wino, Cin, Cout)) return FPC_EINVAL;
+        const WinoImage img = kWinoForms[wino].image;
+        FPC_TRY(kWinoImages[img].pack(w_oihw, wp + wino_image_offset(img, Cout, Cin), Cout, Cin, s));
         a.wino_w[0] = wp;
         a.zeros = zero_page();       // (the workspace's last 64 floats stay reserved for it: fpc_conv2d_workspace_bytes is unchanged)
         if (!a.zeros) {
@@ -1568,7 +1568,6 @@ extern "C" int fpc_conv2d(const float* in, int64_t sb, int64_t sh, int64_t sw, i
             if (hipMemsetAsync(zp, 0, 64 * sizeof(float), s) != hipSuccess) return FPC_ELAUNCH;
             a.zeros = zp;
         }
-        p.wino = -nsplit;
         return launch_conv_plan(a, p, 1, s);
     }
     if (p.h3) {

@@ -421,7 +421,7 @@ int fpc_net_conv_plan(const fpc_net_t* net, int i, int* out5);
  * size, any batch sizes — a small batch then runs on the kernels a larger one was autotuned to (tests/test_gpu_net.py: the
  * headline configuration's plan set against float64 on two frames).  Plans whose split-K partials do not fit dst keep dst's own. */
 int fpc_net_copy_plans(fpc_net_t* dst, const fpc_net_t* src);
-/* Puts every 3x3 / stride-1 site on Winograd form `form` (1..8: fpc_conv2d's -form; 6 only where Cout % 128 == 0; other sites keep
+/* Puts every 3x3 / stride-1 site on Winograd form `form` (1..9: fpc_conv2d's -form; 6 only where Cout % 128 == 0, 9 only where Cin % 16 == 0; other sites keep
  * their plan) — tests hold the whole network on ONE form (8: every eligible product on fp16 x 2 pieces) to the float64 bars.
  * Returns the number of sites changed or a negative code. */
 int fpc_net_force_winograd(fpc_net_t* net, int form);
@@ -482,6 +482,10 @@ int fpc_net_tensor(const fpc_net_t* net, const char* name, const float** ptr, in
  * variant 0: 64-pixel tiles on 4 waves, 1: 128-pixel tiles on 8 waves; bf16 x 3 products), 6000 + k (1 <= k < 100) the
  * implicit GEMM with split-K factor k on two fp16 pieces per operand and three piece products (channel stride 1, Cin a multiple
  * of 32; 6100 + k: split-K summed by a second launch), 7000 + parts the pixel-resident FPN lateral product on the same two pieces.  5000 is never a request: fpc_net_conv_plan's "folded away". */
+enum {      /* the bases of those codes, as fpc_net_conv_plan reports them and fpc_conv2d takes them (a Winograd form: -form) */
+    FPC_PLAN_WINO_PACKED = -10, FPC_PLAN_TWO_LAUNCH = 100, FPC_PLAN_BF3 = 1000, FPC_PLAN_LATERAL = 2000, FPC_PLAN_STEM = 3000,
+    FPC_PLAN_STEM_POOL = 3100, FPC_PLAN_POINTWISE = 4000, FPC_PLAN_FOLDED = 5000, FPC_PLAN_H3 = 6000, FPC_PLAN_LATERAL_H3 = 7000
+};
 size_t fpc_conv2d_workspace_bytes(int B, int Ho, int Wo, int Cin, int Cout, int Kh, int Kw);
 /* the exact need of one request (same bm / bn / nsplit as the fpc_conv2d call): <= the bound above, which reserves 32
  * split-K slices of the whole output; fpc_conv2d accepts either size */
