@@ -35,6 +35,13 @@ class DEFAULT_POSE_HPARAM(argparse.Namespace):
 
     HV_NUM_OF_HYPOTHESES = 128
 
+    # Not in the reference: which matrix products the native backbone engine's plans may use.
+    # The fp16-piece forms take activations as they come: full accuracy while the values a 3x3 site reads lie in about
+    # 2^-2 .. 2^14 (3 * 2^-23 relative; 2^-24 ABSOLUTE below, saturation from 1.3e5); the bf16 x 3 and f32 forms have no such range.
+    ENGINE_SPLIT_PRECISION = True     # False: f32 matrix products only
+    ENGINE_SPLIT_F16 = True           # False: split-precision sites on three bf16 pieces only (no operand range)
+    ENGINE_SPLIT_F16_3P = True        # False: the fp16-piece forms keep all four piece products
+
 
 class MASK_TRAINING(DEFAULT_POSE_HPARAM):
     FREEZE_ROTATION_TRAINING = True

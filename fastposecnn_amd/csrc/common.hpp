@@ -123,9 +123,10 @@ __device__ __forceinline__ void split_bf3(f32x4 v, u32x2& p1, u32x2& p2, u32x2& 
 typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
 
 // Two fp16 pieces of four activations (k_conv_igemm's three-product form, H3): h1 = fp16(x) by truncation, h2 = fp16(x - h1) with
-// the residual in ONE v_fma_mix_f32 (m1 = -1 in a scalar register, as wino_h3.hip).  x = h1 + h2 + r with |r| <= 2^-22 |x| while
-// h2 is normal (|x| >= 2^-3); below that the second piece is subnormal and x is kept to 2^-25 absolute; |x| > 131 008 saturates
-// (round-toward-zero conversions never give infinity).  p1 / p2 = {h1 x 4} / {h2 x 4} in K order.
+// the residual in ONE v_fma_mix_f32 (m1 = -1 in a scalar register, as wino_h3.hip).  x = h1 + h2 + r with |r| <= 3 * 2^-23 |x|
+// (truncation twice: the last two of 24 bits, attained by a mantissa of all ones) while 2^-2 <= |x| < 2^16; below 2^-2 |r| < 2^-24
+// absolute (fp16's subnormal spacing); from 2^16 on h1 is pinned at 65 504 and |r| < 2^-10 (|x| - 65 504); |x| > 131 008 saturates
+// (round-toward-zero conversions never give infinity).  |h2| < 2^-10 |x|.  Emulated in tests/test_piece_arithmetic.py.  p1 / p2 = {h1 x 4} / {h2 x 4} in K order.
 __device__ __forceinline__ void split_h2(f32x4 v, float m1, u32x2& p1, u32x2& p2) {
     const float x0 = v[0], x1 = v[1], x2 = v[2], x3 = v[3];
     const fp16x2 a = __builtin_amdgcn_cvt_pkrtz(x0, x1), b = __builtin_amdgcn_cvt_pkrtz(x2, x3);

@@ -17,7 +17,8 @@
 //                       Split forms (MODE 0): BF3, three bf16 planes per operand and six products per 16-deep k group
 //                       (fpc_conv2d's 1000 + split); H3, two fp16 planes and three products (6000 + split, 6100 + split with
 //                       the second-launch split-K sum) on k_pack_weight_h3's power-of-two-scaled weights — activations keep
-//                       2^-22 relative for |x| >= 2^-3, 2^-25 absolute below, and saturate (finite) beyond 1.3e5.
+//                       3 * 2^-23 relative for 2^-2 <= |x| < 2^16, 2^-24 absolute below, lose precision above (2^-12 of the
+//                       value at 131 008) and saturate (finite) beyond 131 008 (common.hpp: split_h2).
 //   k_conv_splitk_epilogue  fixed-order sum of the split-K partials + the same epilogue.
 //   k_maxpool3x3s2, k_gn_finalize, k_gn_relu_up2, k_merge_head, k_up4_compress: HBM-bound
 //                       streaming kernels, lanes along the contiguous (channel or x) axis.
@@ -1435,7 +1436,7 @@ __global__ __launch_bounds__(256) void k_pack_weight_bf3(const float* __restrict
 
 // The same [Npad][Kpad] image as TWO fp16 planes for k_conv_igemm's three-product form: scaled by s = 2^k, the largest power of
 // two with max |w| s < 2^13 (k_wino_pack_h2's rule without the transform's 2.25; max |w| from k_absmax_bits in tail[1]), and split
-// by truncation, w s = g1 + g2 + rest with |rest| <= 2^-22 |w s|: out[(plane * Npad + n) * Kpad + k], tail[0] = 1 / s.
+// by truncation, w s = g1 + g2 + rest with |rest| <= 3 * 2^-23 |w s| (< 2^-24 where |w s| < 2^-2): out[(plane * Npad + n) * Kpad + k], tail[0] = 1 / s.
 __global__ __launch_bounds__(256) void k_pack_weight_h3(const float* __restrict__ w, unsigned short* __restrict__ out, float* __restrict__ tail,
                                                         int Cout, int Cin, int Cinp, int Kh, int Kw, int Kwp, int Npad, int Kpad) {
     const float wmax = __builtin_bit_cast(float, reinterpret_cast<const unsigned*>(tail)[1]);

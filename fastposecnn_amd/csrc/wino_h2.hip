@@ -4,7 +4,8 @@
 // Why.  The split-precision forms are bound by instruction issue and by chip power: per K-step of 8 channels and
 // 64 x 64 (tiles x channels) the bf16 x 3 form issues 48 matrix instructions, ~330 vector instructions (176 of them the three-way
 // split, 96 operand moves) and streams 48 KB of weights.  With fp16 pieces an f32 operand needs TWO: x = h1 + h2 + rest with
-// |rest| <= 2^-22 |x| (11 + 11 significant bits; truncating conversions, residuals exact in f32).  All four piece products are
+// |rest| <= 3 * 2^-23 |x| (11 + 11 significant bits by TRUNCATION: the last two of x's 24 bits can be left over, 1.5 * 2^-22, and a
+// mantissa of all ones attains it; residuals exact in f32; tests/test_piece_arithmetic.py).  All four piece products are
 // kept: A = {h1, h1} x B = {g1, g2} and A = {h2, h2} x B = {g1, g2} — (h1 + h2)(g1 + g2) exactly, f32 accumulation; the SAME
 // 16-byte weight fragment serves both, so a K-step is 32 matrix instructions, ~200 vector instructions (a pair of values
 // splits in 8: v_cvt_pkrtz_f16_f32, two conversions back, two subtractions, v_cvt_pkrtz again, two copies) and 32 KB of
@@ -13,10 +14,13 @@
 // Range (what fp16 pieces cost).  fp16 spans 2^-24 .. 65504.  WEIGHTS: k_wino_pack_h2 scales the transformed weights of a
 // convolution by a power of two s (from max |w| of the convolution, found on the device) so that max |U s| < 2^13, and the kernel
 // multiplies its sums by 1 / s — exact.  ACTIVATIONS are not scaled: a transformed input value v (a signed sum of four activations)
-// is represented to 2^-22 |v| while |v| >= 2^-3 and to 2^-25 ABSOLUTE below (the second piece turns subnormal), and SATURATES at
-// |v| > 131 008 (round-toward-zero conversions never produce infinity).  Against a tensor of scale ~1 that is f32-level accuracy
+// is represented to 3 * 2^-23 |v| (below 2^-21) while 2^-2 <= |v| < 2^16 and to 2^-24 ABSOLUTE below 2^-2 (fp16's subnormal spacing:
+// the second piece, then the first, turn subnormal).  From |v| = 2^16 on the first piece is pinned at 65 504 and the second carries
+// the excess on 11 bits: the error grows to 2^-10 (|v| - 65 504), 2^-12 of the value at 131 008 = 2 x 65 504, and beyond that the
+// pair SATURATES (round-toward-zero conversions never produce infinity).  Against a tensor of scale ~1 that is f32-level accuracy
 // (tests/test_gpu_net.py holds this form to the 2e-5 bar of every other form and the network to the 1e-4 float64 bars); a tensor
-// whose values are all tiny (scale 1e-2) keeps ~3e-6 of ITS scale, one with values beyond 1.3e5 is wrong.  The bf16 x 3 forms have
+// whose values are all tiny (scale 1e-2) keeps ~3e-6 of ITS scale, one with transformed values beyond 6.5e4 loses precision and
+// beyond 1.3e5 is wrong (tests/test_gpu_conv_operands.py; DESIGN.md 4.2, "Operand envelope").  The bf16 x 3 forms have
 // neither limit and stay selectable: fpc_net_set_split_precision(net, 1) never picks this form, 2 allows it.
 //
 // Everything else — one wave per SIMD with 512 registers, a matrix instruction followed by its own item of the step's other work,
@@ -427,7 +431,8 @@ int launch_absmax_bits(const float* w, long long n, unsigned* out, hipStream_t s
 }
 
 // OIHW 3x3 weights -> U = G g G^T, scaled by s = 2^k (the largest power of two with 2.25 max |w| s < 2^13: |U| <= 2.25 max |w|) and
-// split into two fp16 pieces by truncation (U s = g1 + g2 + rest, |rest| <= 2^-22 |U s|), in the fragment order the lanes load:
+// split into two fp16 pieces by truncation (U s = g1 + g2 + rest, |rest| <= 3 * 2^-23 |U s| while |U s| >= 2^-2, < 2^-24 below), in
+// the fragment order the lanes load.  (s = 2^(13 - e), 2.25 max |w| = m 2^e, m in [0.5, 1); 13 - e is clamped to +-100.)
 // [Cout/64][Cin/8][xi 16][tile 2][lane 64] x {g1 x 4 ch, g2 x 4 ch}, lane = (channel half) * 32 + (co & 31), tile = (co & 63) >> 5;
 // tail[0] = 1 / s (f32).  tail[1] holds max |w|'s bits (k_absmax_bits).
 __global__ __launch_bounds__(256) void k_wino_pack_h2(const float* __restrict__ w, unsigned short* __restrict__ out, float* __restrict__ tail,

@@ -4,8 +4,8 @@
 // Why.  k_conv_wino_h2 runs at the chip's power limit: taking its barrier out saves 10 % of its cycles and none of its time (the clock
 // drops from 1.93 to 1.77 GHz), taking a quarter of its matrix instructions out saves no cycles and 11 % of its time (the clock rises to
 // 2.15 GHz) — profiles/r06_wino_forms.md.  What shortens it is less work per product, not fewer stalls.
-//   x w = (h1 + h2 + rx)(g1 + g2 + rw),  |h2| <= 2^-11 |x|, |g2| <= 2^-11 |w|, |rx| <= 2^-22 |x|, |rw| <= 2^-22 |w|
-// The form keeps h1 g1 + h2 g1 + h1 g2 and drops h2 g2 (<= 2^-22 |x w|: the size of the two terms every two-piece form already
+//   x w = (h1 + h2 + rx)(g1 + g2 + rw),  |h2| < 2^-10 |x|, |g2| < 2^-10 |w|, |rx| <= 3 * 2^-23 |x|, |rw| <= 3 * 2^-23 |w|   (truncation)
+// The form keeps h1 g1 + h2 g1 + h1 g2 and drops h2 g2 (< 2^-20 |x w| at worst, 2^-22 |x w| for mantissas of all ones, ~2^-23 on average: the size of the two terms every two-piece form already
 // drops, x rw and rx w).  Three products do not fit two matrix instructions per 8 channels, but they fit THREE per 16: the K dimension
 // of v_mfma_f32_32x32x16_f16 carries 4 channels of the even K-step and 4 of the odd one,
 //   A1 = {h1 even, h1 odd}   A2 = {h2 even, h2 odd}      B1 = {g1 even, g1 odd}   B2 = {g2 even, g2 odd}

@@ -392,10 +392,10 @@ int fpc_net_autotune_next(fpc_net_t* net, int mode /* 0: minimise each conv's la
  * workgroup / four waves of 512 registers).
  * 2 (round 6): additionally the fp16 x 2 Winograd form (csrc/wino_h2.hip, reported as -8): two fp16 pieces per operand, all four
  * piece products in two matrix instructions per 8 channels.  Weights are scaled by a power of two on the device; a transformed ACTIVATION v is
- * represented to 2^-22 |v| while |v| >= 2^-3, to 2^-25 absolute below, and saturates beyond 1.3e5 — f32-level accuracy for
+ * represented to 3 * 2^-23 |v| while 2^-2 <= |v| < 2^16, to 2^-24 absolute below, loses precision above 2^16 and saturates beyond 1.3e5 — f32-level accuracy for
  * activations of ordinary scale (the tests hold it to the bars of every other form), NOT for tensors of tiny or huge values.  The
  * 3: additionally (and, where Cin is a multiple of 16, INSTEAD of -8) its three-product form (csrc/wino_h3.hip, reported as -9):
- * h1 g1 + h2 g1 + h1 g2 in three matrix instructions per 16 channels; the dropped h2 g2 is <= 2^-22 of the term — the size of the
+ * h1 g1 + h2 g1 + h1 g2 in three matrix instructions per 16 channels; the dropped h2 g2 is < 2^-20 of the term (2^-23 on average) — the size of the
  * two terms every two-piece form drops — and the same tests hold it to the same bars.  At this level the autotuner also times
  * s2.0 with the FPN p2 level folded in (ResNet-18/34 encoders): conv3x3(W, L c2 + b + up2(p3)) as conv3x3(W L, c2) + conv3x3(W,
  * up2(p3)) + a bias table by border class, in one launch that never writes p2; it is kept only when it beats the p2 lateral and
@@ -405,7 +405,7 @@ int fpc_net_autotune_next(fpc_net_t* net, int mode /* 0: minimise each conv's la
  * p5 / p4 / p3 laterals; and the pixel-resident lateral product on the same two pieces (reported as 7000 + parts).  The images
  * of this form are packed only at level 3 (by fpc_net_load_params, or when the level is raised on a loaded plan, on the stream of the
  * last load); their room is always reserved.  Weights: one power of two per convolution from max |w|, undone exactly before the epilogue; activations
- * as they come, with the range of the -8 / -9 forms (2^-22 relative while |x| >= 2^-3, 2^-25 absolute below, saturation beyond
+ * as they come, with the range of the -8 / -9 forms (3 * 2^-23 relative while 2^-2 <= |x| < 2^16, 2^-24 absolute below, saturation beyond
  * 1.3e5 — finite).
  * The Python front end uses 3 unless HPARAM.ENGINE_SPLIT_F16_3P (then 2) or HPARAM.ENGINE_SPLIT_F16 (then 1) is False. */
 int fpc_net_set_split_precision(fpc_net_t* net, int on);
