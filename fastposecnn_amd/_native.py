@@ -85,6 +85,10 @@ _SIGNATURES = {
     "fpc_net_force_fold": (_i, [_vp, _i]),
     "fpc_net_force_direct_h3": (_i, [_vp, _i]),
     "fpc_net_force_stem_pool": (_i, [_vp, _i]),
+    "fpc_act_range": (_i, [_vp, ctypes.c_longlong, _vp, _vp]),
+    "fpc_net_survey_next": (_i, [_vp, _vp, _i]),
+    "fpc_net_guard_ranges": (_i, [_vp, ctypes.POINTER(ctypes.c_uint32), _i, _f, _f]),
+    "fpc_net_guarded": (_i, [_vp, _i]),
     "fpc_stem_pool_tasks": (_i, [_i, _i, ctypes.POINTER(_i64)]),
     "fpc_wino_pack_geometry": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(_i64)]),
     "fpc_net_set_wino_pack": (_i, [_vp, _i]),

@@ -41,6 +41,13 @@ class DEFAULT_POSE_HPARAM(argparse.Namespace):
     ENGINE_SPLIT_PRECISION = True     # False: f32 matrix products only
     ENGINE_SPLIT_F16 = True           # False: split-precision sites on three bf16 pieces only (no operand range)
     ENGINE_SPLIT_F16_3P = True        # False: the fp16-piece forms keep all four piece products
+    # The guard of that range ("The activation-range guard"): off by default.  On: the first real forward of a plan
+    # surveys what every convolution site reads and moves the fp16-piece sites whose input lies outside LO .. HI (on max |x|; or is
+    # not finite) to their range-free plans, for good, with one warning; the frame is then run again on the guarded plans.
+    ENGINE_RANGE_GUARD = False
+    ENGINE_RANGE_GUARD_EVERY = 0      # N > 0: every N-th forward of a plan surveys again (demotions are never undone)
+    ENGINE_RANGE_LO = 2.0 ** -2       # a site whose input has 0 < max |x| < LO is demoted (conservative: the bound is on the maximum)
+    ENGINE_RANGE_HI = 2.0 ** 14       # ... or max |x| >= HI (x 4 by the Winograd input transform stays below 2^16)
 
 
 class MASK_TRAINING(DEFAULT_POSE_HPARAM):

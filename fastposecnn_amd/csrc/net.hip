@@ -160,6 +160,7 @@ constexpr WinoImageDesc kWinoImages[kWinoImageCount] = {
 constexpr size_t kWinoSlack = 128;      // a 64-float line for the tails + 64 zero floats (fpc_conv2d's zero page where the code object has none)
 
 constexpr int kWinoFormCount = 10;      // forms 1..9; row 0 is "not Winograd"
+constexpr int kWinoBf3 = 5, kWinoW4 = 7;     // the range-free split-precision forms a guarded site falls back to (-7 where offered, else -5)
 constexpr int kWinoH2 = 8, kWinoH3 = 9;      // the fp16 x 2 form and its three-product form: the one launch that may pack frames or fold p2 in
 struct WinoForm {
     int waves;               // 4: 8 x 4 tile patch per workgroup, 8: 8 x 8
@@ -169,19 +170,20 @@ struct WinoForm {
     int wg_per_cu;           // workgroups of the form that share a CU (the tuner's occupancy share)
     int min_split;           // lowest fpc_net_set_split_precision level at which the tuner offers the form
     bool zeros;              // reads the zero page (WinoArgs::zeros)
+    bool range_limited;      // two fp16 pieces per operand: the activation envelope of fpc.h (fpc_net_guard_ranges demotes such a site)
     int (*launch)(const WinoArgs& a, int groups, hipStream_t s);
 };
 constexpr WinoForm kWinoForms[kWinoFormCount] = {
     {},
-    {4, 64, 8, 0, kImgF32, 2, 0, false, launch_conv_wino},             // -1: 4 waves
-    {8, 64, 8, 0, kImgF32, 1, 0, false, launch_conv_wino},             // -2: 8 waves
-    {4, 64, 8, 1, kImgF32, 2, 0, false, launch_conv_wino},             // -3: wave-private K loop
-    {8, 64, 8, 2, kImgF32, 1, 0, true, launch_conv_wino},              // -4: all-DMA 3-stage
-    {8, 64, 8, 3, kImgBf3, 1, 1, true, launch_conv_wino},              // -5: split-precision products, 8 waves
-    {4, 128, 8, 0, kImgC128, 1, 1, false, launch_conv_wino_c128},      // -6: ... 8 x 4 tiles x 128 channels per workgroup, 4 waves (wino128.hip)
-    {8, 64, 8, 0, kImgBf3, 1, 1, false, launch_conv_wino_w4},          // -7: ... 64 channels, four waves of 512 registers, weights direct (wino_w4.hip)
-    {8, 64, 8, 0, kImgH2, 1, 2, false, launch_conv_wino_h2},           // -8: the -7 form on two fp16 pieces per operand (range-limited: fpc.h; wino_h2.hip)
-    {8, 64, 16, 0, kImgH3, 1, 3, false, launch_conv_wino_h3},          // -9: three of the four piece products of -8, over pairs of K-steps (wino_h3.hip)
+    {4, 64, 8, 0, kImgF32, 2, 0, false, false, launch_conv_wino},      // -1: 4 waves
+    {8, 64, 8, 0, kImgF32, 1, 0, false, false, launch_conv_wino},      // -2: 8 waves
+    {4, 64, 8, 1, kImgF32, 2, 0, false, false, launch_conv_wino},      // -3: wave-private K loop
+    {8, 64, 8, 2, kImgF32, 1, 0, true, false, launch_conv_wino},       // -4: all-DMA 3-stage
+    {8, 64, 8, 3, kImgBf3, 1, 1, true, false, launch_conv_wino},       // -5: split-precision products, 8 waves
+    {4, 128, 8, 0, kImgC128, 1, 1, false, false, launch_conv_wino_c128},      // -6: ... 8 x 4 tiles x 128 channels per workgroup, 4 waves (wino128.hip)
+    {8, 64, 8, 0, kImgBf3, 1, 1, false, false, launch_conv_wino_w4},   // -7: ... 64 channels, four waves of 512 registers, weights direct (wino_w4.hip)
+    {8, 64, 8, 0, kImgH2, 1, 2, false, true, launch_conv_wino_h2},     // -8: the -7 form on two fp16 pieces per operand (range-limited: fpc.h; wino_h2.hip)
+    {8, 64, 16, 0, kImgH3, 1, 3, false, true, launch_conv_wino_h3},    // -9: three of the four piece products of -8, over pairs of K-steps (wino_h3.hip)
 };
 // the shape rules of a form, on top of PackedConv::wino_ok
 static bool wino_form_ok(int form, int Cin, int Cout) {
@@ -204,6 +206,11 @@ static size_t wino_image_offset(WinoImage img, int Cout, int Cin) {
 // floats of a region that ends with image `last`: what one form needs (fpc_conv2d's exact workspace), and with the last image of
 // all what a site needs (fpc_net::add_conv); c128 = true bounds both (fpc_conv2d_workspace_bytes)
 static size_t wino_region_floats(WinoImage last, int Cout, int Cin, bool c128) { return (wino_span(last, c128).units + kWinoImages[last].units) * Cout * Cin + kWinoSlack; }
+// a plan whose matrix products run on two fp16 pieces per operand, i.e. under the activation envelope: the range-limited Winograd
+// forms (packed or not, with or without the p2 fold), the three-product direct and lateral forms, the stem fused with its max-pool
+static bool plan_range_limited(const ConvPlan& p) {
+    return p.h3 || p.fold || p.pool || (p.wino && kWinoForms[p.wino].range_limited);
+}
 // tile patches of one frame: tbx x tby workgroups per (frame, channel block, group)
 struct WinoGrid { int tbx, tby; int patches() const { return tbx * tby; } };
 static WinoGrid wino_grid(int form, int H, int W) { return {cdiv(cdiv(W, 2), 8), cdiv(cdiv(H, 2), kWinoForms[form].waves)}; }
@@ -300,6 +307,11 @@ struct fpc_net {
     // per-conv launch plans (index = conv id of decoder 0 for grouped ones)
     std::vector<ConvPlan> cplan;
     std::vector<float> tune_score;       // the autotuner's best score per site (ms, or its throughput objective)
+    // the activation-range guard (fpc_net_survey_next / fpc_net_guard_ranges)
+    unsigned* survey = nullptr;          // device records [convs][4] the NEXT forward fills (k_act_range in front of every site's launch)
+    std::vector<ConvPlan> free_plan;     // the autotuner's best-scoring candidate that is not range-limited, kept beside the best ...
+    std::vector<char> has_free;          // ... 1 where the site was autotuned and had one
+    std::vector<char> guarded;           // 1: the site stands demoted to a range-free plan (sticky: the tuner offers it no fp16-piece form)
     std::vector<int> c_howo, c_groups;   // output pixels per image and launch multiplicity of every planned conv site (0: not a site)
 
     size_t bump = 0;
@@ -515,6 +527,9 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
     // ---- conv plans (+ split-K scratch for the worst candidate, GroupNorm partials for the largest P32)
     n->cplan.resize(n->convs.size());
     n->tune_score.assign(n->convs.size(), 0.f);
+    n->free_plan.assign(n->convs.size(), ConvPlan());
+    n->has_free.assign(n->convs.size(), 0);
+    n->guarded.assign(n->convs.size(), 0);
     n->c_howo.assign(n->convs.size(), 0);
     n->c_groups.assign(n->convs.size(), 0);
     auto plan = [&](int ci, int HoWo, int groups) {
@@ -873,14 +888,39 @@ PlanFootprint plan_footprint(const ConvPlan& q, const ConvArgs& a, int groups) {
     return {nblk, share};
 }
 
+// The survey pass of site `ci` (fpc_net_survey_next): k_act_range over every activation tensor plan `p` reads as its matrix operand,
+// accumulated into the site's record.  Every engine input is a contiguous NHWC tensor of B frames (in_sb elements each; the stem's:
+// the NHWC4 image, whose fourth channel is zero).  Groups that share one input (the laterals) survey it once.  The folded s2.0 reads
+// two operands of their own scales, not p2: c2 into its own record, p3 at ITS resolution (nearest x2 inside the kernel: the same
+// values) into the record of the p2 lateral site, which does not run while it is folded away.
+int survey_site(const fpc_net* n, const ConvArgs& a, const ConvPlan& p, int groups, int ci, hipStream_t s) {
+    unsigned* rec = n->survey + 4 * (size_t)ci;
+    if (p.fold) {
+        unsigned* rec_up = n->survey + 4 * (size_t)n->dec[0].lat[3];
+        int rc = launch_act_range(a.fold_in, (long long)a.B * a.Ho * a.Wo * a.fold_cin, rec, s);
+        for (int g = 0; g < groups && !rc; ++g) rc = launch_act_range(a.fold_up[g], (long long)a.B * (a.Ho / 2) * (a.Wo / 2) * a.Cin, rec_up, s);
+        return rc;
+    }
+    for (int g = 0; g < groups; ++g) {
+        bool seen = false;
+        for (int h = 0; h < g; ++h) seen = seen || a.p[h].in == a.p[g].in;
+        if (seen) continue;
+        const int rc = launch_act_range(a.p[g].in, (long long)a.B * a.in_sb, rec, s);
+        if (rc) return rc;
+    }
+    return FPC_OK;
+}
+
 // Runs conv site `ci` with its current plan; in tuning mode first times every candidate (HIP events on the stream,
 // synchronising — only ever inside fpc_net_autotune): candidates, time each, keep the best, the fold challenger, launch.
 int run_conv(fpc_net* n, ConvArgs& a, int groups, int ci, hipStream_t s) {
     if (n && n->tuning) {
-        float best_ms = 1e30f;
+        float best_ms = 1e30f, free_ms = 1e30f;
         ConvPlan best = n->cplan[ci];
+        n->has_free[ci] = 0;
         for (const ConvPlan& q : tune_candidates(a, groups, n->split_precision, n->expansion)) {
             if (splitk_floats_for(q, groups, a.B, a.Npad) > n->splitk_floats) continue;
+            if (n->guarded[ci] && plan_range_limited(q)) continue;      // a demoted site stays range-free
             int rc = launch_conv_plan(a, q, groups, s);     // warm-up (also validates the launch)
             if (rc == FPC_EINVAL) continue;                 // a candidate whose launcher refuses this site (its own preconditions) is skipped
             if (rc) return rc;
@@ -893,11 +933,12 @@ int run_conv(fpc_net* n, ConvArgs& a, int groups, int ci, hipStream_t s) {
                 score = ms * (float)(n->tune_mode == 2 ? share : sqrt(share));      // 2: latency x share = the launch's CU-time
             }
             if (score < best_ms) { best_ms = score; best = q; }
+            if (score < free_ms && !plan_range_limited(q)) { free_ms = score; n->free_plan[ci] = q; n->has_free[ci] = 1; }      // the guard's fallback
         }
         n->tune_score[ci] = best_ms;
         // s2.0 with the FPN p2 level folded in (level 3, wino_h3.hip): it replaces the p2 lateral AND this site, so it must beat the sum
         // of both best scores (the lateral's was taken earlier in this pass).  Same timing rule as above; the whole chip: score = ms.
-        if (n->split_precision >= 3 && a.fold_in && a.fold_lat_ms > 0.f) {
+        if (n->split_precision >= 3 && a.fold_in && a.fold_lat_ms > 0.f && !n->guarded[ci]) {
             ConvPlan fq;
             fq.wino = kWinoH3; fq.fold = 1;
             int rc = launch_conv_plan(a, fq, groups, s);
@@ -908,6 +949,7 @@ int run_conv(fpc_net* n, ConvArgs& a, int groups, int ci, hipStream_t s) {
         n->cplan[ci] = best;
     }
     ConvPlan p = n ? n->cplan[ci] : ConvPlan{a.bm, a.bn, a.nsplit, a.mtiles, a.ntiles, 0, a.bf3, a.fused};
+    if (n && n->survey) { const int rs = survey_site(n, a, p, groups, ci, s); if (rs) return rs; }
     const int rc = launch_conv_plan(a, p, groups, s);
     if (n && !rc && p.wino == kWinoH3) n->wino_blocks += a.wino_blocks;
     return rc;
@@ -956,6 +998,7 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
             return launch_maxpool3x3s2(ws + n->a_stem.off, ws + n->a_pool.off, B, n->a_stem.H, n->a_stem.W, 64, n->a_pool.H, n->a_pool.W, s);
         };
         if (n->cplan[n->c_stem].pool && !n->tuning) {      // one launch to the pooled tensor: a_stem is not written
+            if (n->survey) FPC_TRY(survey_site(n, a, n->cplan[n->c_stem], 1, n->c_stem, s));      // (not through run_conv: the image)
             FPC_TRY(launch_stem_pool(a, h3img, ws + n->a_pool.off, n->a_pool.H, n->a_pool.W, s));
         } else {
             n->cplan[n->c_stem].pool = 0;
@@ -963,7 +1006,7 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
             FPC_TRY(pool_launch());
             // level 3: the fused launch against the site's best plan AND the max-pool together (it replaces both), timed as the p2
             // fold is; the whole chip: score = ms.  Kept only when it beats them
-            if (n->tuning && n->split_precision >= 3 && launch_stem_pool(a, h3img, ws + n->a_pool.off, n->a_pool.H, n->a_pool.W, s) == FPC_OK) {
+            if (n->tuning && n->split_precision >= 3 && !n->guarded[n->c_stem] && launch_stem_pool(a, h3img, ws + n->a_pool.off, n->a_pool.H, n->a_pool.W, s) == FPC_OK) {
                 const ConvPlan cur = n->cplan[n->c_stem];
                 float ms_pair = 1e30f, ms_fused = 1e30f;
                 for (int rep = 0; rep < 3; ++rep) {      // six runs, the two sides in turn
@@ -1175,9 +1218,21 @@ extern "C" int fpc_net_forward(fpc_net_t* n, const float* x, float* logits_mask,
     return fpc_net_forward_bits(n, x, logits_mask, logits_quat, logits_scales, logits_xy, logits_z, cat_mask, cq, cs, cxy, cz, nullptr, stream);
 }
 
+static int forward_bits(fpc_net_t* n, const float* x, float* logits_mask, float* logits_quat, float* logits_scales,
+                        float* logits_xy, float* logits_z, int64_t* cat_mask, float* cq, float* cs, float* cxy, float* cz,
+                        uint64_t* fg_bits, fpc_stream_t stream);
+
 extern "C" int fpc_net_forward_bits(fpc_net_t* n, const float* x, float* logits_mask, float* logits_quat,
                                     float* logits_scales, float* logits_xy, float* logits_z, int64_t* cat_mask, float* cq,
                                     float* cs, float* cxy, float* cz, uint64_t* fg_bits, fpc_stream_t stream) {
+    const int rc = forward_bits(n, x, logits_mask, logits_quat, logits_scales, logits_xy, logits_z, cat_mask, cq, cs, cxy, cz, fg_bits, stream);
+    if (n) n->survey = nullptr;      // a survey is armed for ONE call, whatever became of it (a refused call included): never a stale pointer
+    return rc;
+}
+
+static int forward_bits(fpc_net_t* n, const float* x, float* logits_mask, float* logits_quat, float* logits_scales,
+                        float* logits_xy, float* logits_z, int64_t* cat_mask, float* cq, float* cs, float* cxy, float* cz,
+                        uint64_t* fg_bits, fpc_stream_t stream) {
     if (!n || !n->loaded || !x || !cat_mask || !cq || !cs || !cxy || !cz) return FPC_EINVAL;
     if (fg_bits && (n->W % 64 != 0 || ((uintptr_t)fg_bits & 7))) return FPC_EINVAL;
     bool any = logits_mask || logits_quat || logits_scales || logits_xy || logits_z;
@@ -1190,7 +1245,8 @@ extern "C" int fpc_net_forward_bits(fpc_net_t* n, const float* x, float* logits_
     // stem: image -> NHWC4 (16-byte pixels), 7x7/2 with BN + ReLU in the epilogue
     FPC_TRY(launch_nchw3_to_nhwc4(x, ws + n->a_img4.off, B, H * W, s));
     // graph replay needs a capturable stream: not the null (legacy default) stream
-    if (n->use_graph && !n->tuning && s != nullptr && !n->graph_exec) {
+    const bool plain = n->tuning || n->survey;      // a tuning or a survey forward launches its kernels: no capture, no replay
+    if (n->use_graph && !plain && s != nullptr && !n->graph_exec) {
         // first such frame after tuning: record the launches instead of running them
         hipGraph_t g = nullptr;
         if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
@@ -1203,7 +1259,7 @@ extern "C" int fpc_net_forward_bits(fpc_net_t* n, const float* x, float* logits_
         }
         if (!n->graph_exec) { (void)hipGetLastError(); n->use_graph = 0; }      // not capturable here: plain launches from now on
     }
-    if (n->use_graph && !n->tuning && s != nullptr && n->graph_exec) {
+    if (n->use_graph && !plain && s != nullptr && n->graph_exec) {
         if (hipGraphLaunch(n->graph_exec, s) != hipSuccess) return FPC_ELAUNCH;
     } else {
         FPC_TRY(forward_middle(n, s));
@@ -1234,6 +1290,70 @@ extern "C" int fpc_net_autotune_next(fpc_net_t* n, int mode) {
     return FPC_OK;
 }
 
+// The NEXT fpc_net_forward, and only that one, also surveys the activations: in front of every convolution site's launch k_act_range
+// (act_range.hip) accumulates max |x| over the finite elements, the non-finite count and the visit count of every tensor the site's
+// CURRENT plan reads as its matrix operand into records_dev[4 * site] (device memory the caller owns and zeroed; grouped sites: the
+// four decoders into the index of decoder 0).  That forward launches its kernels (no graph capture or replay, as a tuning pass),
+// changes no plan and writes what an ordinary forward writes.  sites = fpc_net_conv_count.  The survey is disarmed when that call
+// returns, whatever it returns, and by records_dev = NULL.
+extern "C" int fpc_net_survey_next(fpc_net_t* n, unsigned* records_dev, int sites) {
+    if (n && !records_dev) { n->survey = nullptr; return FPC_OK; }      // NULL disarms (the caller's buffer is going away)
+    if (!n || !n->loaded || ((uintptr_t)records_dev & 3) || sites != (int)n->convs.size()) return FPC_EINVAL;
+    n->survey = records_dev;
+    return FPC_OK;
+}
+
+// The plan a range-limited site falls back to: the autotuner's best range-free candidate where the site was tuned, else what the
+// planner gives at split level 1 — a Winograd site (the folded s2.0 too: its p2 lateral keeps its own, never range-limited, plan and
+// runs again) form -7 where offered, else -5; a three-product direct or lateral plan the same tiling or parts on bf16 x 3; the fused
+// stem + max-pool what fpc_net_force_stem_pool(net, 0) restores.
+static ConvPlan range_free_plan(const fpc_net* n, int i) {
+    if (n->has_free[i]) return n->free_plan[i];
+    const PackedConv& c = n->convs[i];
+    ConvPlan q = n->cplan[i];
+    if (q.pool) { ConvPlan st; st.stem = 256; return st; }
+    if (q.wino) {
+        q.wino = wino_form_ok(kWinoW4, c.Cin, c.Cout) ? kWinoW4 : kWinoBf3;
+        q.fold = 0;
+        return q;
+    }
+    q.h3 = 0; q.bf3 = 1;
+    return q;
+}
+
+// Host arithmetic only.  records_host: the records of a survey forward, copied to the host.  Every site whose current plan is
+// range-limited (plan_range_limited) and whose record shows a non-finite element, max |x| >= hi or 0 < max |x| < lo is demoted to
+// its range-free plan (range_free_plan) and stays so: fpc_net_guarded reports it, fpc_net_load_params keeps it, fpc_net_copy_plans
+// carries it, a later autotuning pass offers the site no fp16-piece form; only an explicit fpc_net_force_* puts it back.  A record
+// of all zeros (every form is exact on zeros) or with no visit (not surveyed) demotes nothing.  The folded s2.0 has two operands of
+// two scales and two records: c2 in its own, p3 in the p2 lateral site's; either one outside demotes it.  Returns the number of sites demoted by
+// THIS call (a second call with the same records: 0) and drops the recorded graph when that is not zero.
+extern "C" int fpc_net_guard_ranges(fpc_net_t* n, const unsigned* records_host, int sites, float lo, float hi) {
+    if (!n || !records_host || sites != (int)n->convs.size() || !(lo >= 0.f) || !(hi > lo)) return FPC_EINVAL;
+    auto outside = [&](int site) {
+        const unsigned* rec = records_host + 4 * (size_t)site;
+        float mx;
+        memcpy(&mx, &rec[0], sizeof(mx));
+        return rec[2] != 0 && (rec[1] > 0 || mx >= hi || (mx > 0.f && mx < lo));
+    };
+    int demoted = 0;
+    for (int i = 0; i < sites; ++i) {
+        if (!n->c_groups[i] || !plan_range_limited(n->cplan[i]) || records_host[4 * (size_t)i + 2] == 0) continue;
+        // (the folded s2.0: its second operand, p3, was surveyed into the p2 lateral's record)
+        if (!(outside(i) || (n->cplan[i].fold && outside(n->dec[0].lat[3])))) continue;
+        n->cplan[i] = range_free_plan(n, i);
+        n->guarded[i] = 1;
+        ++demoted;
+    }
+    if (demoted) drop_graph(n);
+    return demoted;
+}
+
+// 1: site `i` stands demoted by fpc_net_guard_ranges, 0: not (or no such site)
+extern "C" int fpc_net_guarded(const fpc_net_t* n, int i) {
+    return n && i >= 0 && i < (int)n->guarded.size() && n->guarded[i] ? 1 : 0;
+}
+
 // Chosen tiling of convolution site `i` (0 <= i < fpc_net_conv_count): out5 = bm, bn, nsplit, Cout, K.  nsplit 5000: the p2 lateral
 // site, folded into s2.0's launch (which reports -9).
 extern "C" int fpc_net_conv_count(const fpc_net_t* n) { return n ? (int)n->convs.size() : 0; }
@@ -1262,6 +1382,7 @@ extern "C" int fpc_net_force_winograd(fpc_net_t* n, int form) {
         q.wino = form; q.lat = 0; q.stem = 0;
         if (form != kWinoH3) q.fold = 0;      // (form 9 keeps s2.0's fold: it runs on that form)
         n->cplan[i] = q;
+        n->guarded[i] = 0;      // an explicit request wins over the range guard
         ++changed;
     }
     drop_graph(n);
@@ -1277,6 +1398,7 @@ extern "C" int fpc_net_force_fold(fpc_net_t* n, int on) {
     ConvPlan q;
     q.wino = kWinoH3; q.fold = on;
     p = q;
+    n->guarded[n->dec[0].seg[6]] = 0;
     drop_graph(n);
     return 1;
 }
@@ -1320,6 +1442,7 @@ extern "C" int fpc_net_force_direct_h3(fpc_net_t* n, int on) {
         q.bf3 = 0;
         q.h3 = on;
         n->cplan[i] = q;
+        n->guarded[i] = 0;
         ++changed;
     }
     drop_graph(n);
@@ -1337,6 +1460,7 @@ extern "C" int fpc_net_force_stem_pool(fpc_net_t* n, int on) {
     ConvPlan q;
     q.stem = 256; q.pool = on;
     p = q;
+    n->guarded[n->c_stem] = 0;
     drop_graph(n);
     return 1;
 }
@@ -1358,6 +1482,17 @@ extern "C" int fpc_net_copy_plans(fpc_net_t* dst, const fpc_net_t* src) {
         if (q.nsplit > 1 && q.fused && !can_fuse(q, dst->c_groups[i] ? dst->c_groups[i] : 1, dst->B)) continue;
         if ((q.h3 || q.pool) && !dst->h3_packed) continue;      // dst is not at split level 3: no three-product images
         dst->cplan[i] = q;
+    }
+    // the range guard's state: the fallback plans (where they fit dst as above) and the demotions — a site that stands demoted in src
+    // or in dst is demoted in dst afterwards, also where dst kept a plan of its own or src's plan for it is an fp16-piece form
+    for (size_t i = 0; i < dst->convs.size(); ++i) {
+        const ConvPlan& q = src->free_plan[i];
+        const int groups = dst->c_groups[i] ? dst->c_groups[i] : 1;
+        dst->has_free[i] = src->has_free[i] && splitk_floats_for(q, groups, dst->B, dst->convs[i].Npad) <= dst->splitk_floats &&
+                           !(q.nsplit > 1 && q.fused && !can_fuse(q, groups, dst->B));
+        if (dst->has_free[i]) dst->free_plan[i] = q;
+        dst->guarded[i] = dst->guarded[i] || src->guarded[i];      // (a demotion of dst's own is never undone by a copy)
+        if (dst->guarded[i] && plan_range_limited(dst->cplan[i])) dst->cplan[i] = range_free_plan(dst, (int)i);
     }
     dst->tuned = true;
     drop_graph(dst);

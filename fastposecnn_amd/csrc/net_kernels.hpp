@@ -211,6 +211,10 @@ int launch_conv_wino_w4(const WinoArgs& a, int groups, hipStream_t s);
 int launch_conv_wino_h2(const WinoArgs& a, int groups, hipStream_t s);
 int launch_wino_pack_h2(const float* w_oihw, float* packed, int Cout, int Cin, hipStream_t s);
 int launch_absmax_bits(const float* w, long long n, unsigned* out_bits, hipStream_t s);      // max |w| as the bits of a non-negative float (atomicMax into *out_bits)
+// act_range.hip: one pass over n contiguous floats into a 4-word record — rec[0] max |x| over the finite elements (bits, atomicMax),
+// rec[1] += non-finite elements, rec[2] += n (saturating); accumulates over launches.  x 4-byte aligned; n = 0 launches nothing.
+// fpc_act_range (fpc.h) is this call.
+int launch_act_range(const float* x, long long n, unsigned* rec4, hipStream_t s);
 // wino_h3.hip: k_conv_wino_h2 with three of the four piece products, over pairs of K-steps (Cin a multiple of 16); its own image:
 // 16 * Cout * Cin + 2 floats
 int launch_conv_wino_h3(const WinoArgs& a, int groups, hipStream_t s);

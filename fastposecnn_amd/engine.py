@@ -39,6 +39,7 @@ class NetEngine:
             assert self._ws.data_ptr() % 256 == 0
         self.reloads = 0
         self.generation = 0          # the owner's count of unversioned writes when this plan was last bound (pose_regressor.py)
+        self.guard_forwards = 0      # forwards this plan ran under HPARAM.ENGINE_RANGE_GUARD (pose_regressor.py: which of them survey)
         self.bind(model)
         if split_precision:
             nat.check(L.fpc_net_set_split_precision(h, int(split_precision)), "fpc_net_set_split_precision")
@@ -96,7 +97,8 @@ class NetEngine:
         return out
 
     def copy_plans_from(self, other):
-        """Run this engine on the plans `other` (same network and frame size, another batch) was autotuned to."""
+        """Run this engine on the plans `other` (same network and frame size, another batch) was autotuned to; the range guard's
+        demotions and fallback plans come along."""
         nat.check(self._lib.fpc_net_copy_plans(self._h, other._h), "fpc_net_copy_plans")
 
     def force_winograd(self, form):
@@ -128,6 +130,51 @@ class NetEngine:
         if rc < 0:
             nat.check(rc, "fpc_net_force_stem_pool")
         return rc
+
+    def survey(self, x, want_logits=True):
+        """One forward that also surveys the activations (fpc_net_survey_next): in front of every convolution site's launch one pass
+        over what the site's current plan reads.  Returns (logits, cat, records): the outputs of an ordinary forward, bit for bit, and
+        an int64 CPU tensor [sites, 4] — per site the bits of max |x| over the finite elements, the number of non-finite elements,
+        the number of elements visited (saturating at 2^32 - 1; 0: the site did not run), and a reserved word.  It changes no plan;
+        it reads the records back, so it synchronises the stream."""
+        if tuple(x.shape) != (self.B, 3, self.H, self.W) or x.device != self.device:      # before arming: forward() would refuse it
+            raise RuntimeError("NetEngine.survey: input shape / device does not match the plan")
+        sites = self._lib.fpc_net_conv_count(self._h)
+        with torch.cuda.device(self.device):
+            rec = torch.zeros((sites, 4), dtype=torch.int32, device=self.device)
+            nat.check(self._lib.fpc_net_survey_next(self._h, rec.data_ptr(), sites), "fpc_net_survey_next")
+        try:
+            logits, cat = self.forward(x, want_logits=want_logits)
+        finally:      # the library disarms when its forward returns; this covers a forward that never reached it
+            self._lib.fpc_net_survey_next(self._h, None, sites)
+        return logits, cat, rec.cpu().to(torch.int64) & 0xFFFFFFFF
+
+    @staticmethod
+    def record_max(records):
+        """max |x| of every record of `survey` as float32 values [sites]."""
+        return (records[:, 0] & 0xFFFFFFFF).to(torch.int32).view(torch.float32) if records.dtype == torch.int64 \
+            else records[:, 0].contiguous().view(torch.float32)
+
+    def guard_ranges(self, records, lo=2.0 ** -2, hi=2.0 ** 14):
+        """Demote every site on an fp16-piece form whose record (of `survey`) shows a non-finite element, max |x| >= hi or
+        0 < max |x| < lo to its best range-free plan (fpc_net_guard_ranges; host arithmetic).  Returns the indices of the sites
+        demoted by this call; they stay demoted (`guarded`)."""
+        sites = self._lib.fpc_net_conv_count(self._h)
+        flat = [int(v) & 0xFFFFFFFF for v in records.reshape(-1).tolist()]
+        if len(flat) != 4 * sites:
+            raise RuntimeError("NetEngine.guard_ranges: records must be [sites, 4]")
+        before = set(self.guarded())
+        rc = self._lib.fpc_net_guard_ranges(self._h, (ctypes.c_uint32 * len(flat))(*flat), sites, float(lo), float(hi))
+        if rc < 0:
+            nat.check(rc, "fpc_net_guard_ranges")
+        return [i for i in self.guarded() if i not in before]
+
+    def guarded(self):
+        """The sites that stand demoted by `guard_ranges`."""
+        return [i for i in range(self._lib.fpc_net_conv_count(self._h)) if self._lib.fpc_net_guarded(self._h, i)]
+
+    def graph_recorded(self):
+        return bool(self._lib.fpc_net_graph_recorded(self._h))
 
     def set_wino_pack(self, on):
         """Form-9 Winograd launches cut their tile patches out of canvas rows of several frames where that needs fewer patches

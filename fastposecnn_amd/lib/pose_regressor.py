@@ -8,6 +8,7 @@ constructor signature, `forward` output schema and state-dict names are the same
 forward(x[B,3,H,W]) -> {'logits': {...}, 'categorical': {...}, 'aggregated': AggData | None}
 """
 import logging
+import warnings
 from typing import Optional, OrderedDict, Union
 
 import numpy as np
@@ -282,11 +283,52 @@ class PoseRegressor(Model, torch.nn.Module):
         self._drop_engines()
         return super()._apply(fn, *args, **kwargs)
 
+    def _guarded_forward(self, eng, x):
+        """HPARAM.ENGINE_RANGE_GUARD: the first real forward of a plan (the autotuning pass on zeros is none), and every
+        ENGINE_RANGE_GUARD_EVERY-th after it, surveys the activations every convolution site reads; a site on an fp16-piece form
+        whose input lies outside ENGINE_RANGE_LO .. ENGINE_RANGE_HI is demoted to its range-free plan, for good, and the frame runs
+        again so that what is returned already comes from the guarded plans.  One warning per surveyed frame that demoted names
+        the sites."""
+        k = eng.guard_forwards
+        eng.guard_forwards += 1
+        every = int(getattr(self.HPARAM, 'ENGINE_RANGE_GUARD_EVERY', 0))
+        if k != 0 and not (every > 0 and k % every == 0):
+            return eng.forward(x)
+        lo = float(getattr(self.HPARAM, 'ENGINE_RANGE_LO', 2.0 ** -2))
+        hi = float(getattr(self.HPARAM, 'ENGINE_RANGE_HI', 2.0 ** 14))
+        before, moved = eng.conv_plans(), []
+        while True:
+            # a site behind a saturating one was surveyed on ITS wrong output: after a demotion the frame is run again as a survey,
+            # until a pass demotes nothing (every pass but the last demotes a site for good, so there are at most sites + 1)
+            logits, cat, records = eng.survey(x)
+            demoted = eng.guard_ranges(records, lo, hi)
+            if not demoted:
+                break
+            mx = eng.record_max(records)
+            for i in demoted:
+                j = i
+                # the folded s2.0 has a second operand, p3, surveyed into the record of the p2 lateral (reported 5000 while folded
+                # away): name the record that is outside the bounds
+                own_ok = not records[i, 1].item() and (mx[i].item() == 0 or lo <= mx[i].item() < hi)
+                if own_ok and before[i][2] == -9:
+                    j = next((k for k, p in enumerate(before) if p[2] == 5000), i)
+                moved.append((i, mx[j].item(), int(records[j, 1].item()), " (its p3 operand)" if j != i else ""))
+        if moved:
+            after = eng.conv_plans()
+            warnings.warn("fastposecnn_amd: activation-range guard (%g <= max|x| < %g) moved %d convolution site(s) of the %dx%dx%d "
+                          "plan off the fp16-piece forms: %s" % (lo, hi, len(moved), eng.B, eng.H, eng.W, ", ".join(
+                              "site %d max|x| %.4g%s%s plan %d -> %d" % (i, m, what, " (%d non-finite)" % bad if bad else "", before[i][2], after[i][2])
+                              for i, m, bad, what in moved)), RuntimeWarning, stacklevel=3)
+        return logits, cat
+
     @MODEL_TIMER
     def pure_model_forward(self, x: torch.Tensor):
         eng = self._engine_for(x)
         if eng is not None:
-            logits, cat = eng.forward(x)
+            if getattr(self.HPARAM, 'ENGINE_RANGE_GUARD', False):
+                logits, cat = self._guarded_forward(eng, x)
+            else:
+                logits, cat = eng.forward(x)
             self._fused = (logits, cat)
             return logits
         if self.training:

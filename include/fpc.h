@@ -47,6 +47,7 @@ extern "C" {
  * the FPN p2 fold (fpc_net_force_fold) and the three-product direct form (fpc_net_force_direct_h3, fpc_conv2d's 6000 + split and 7000 + parts, fpc_net_graph_recorded):
  * and the stem fused with its max-pool (fpc_net_force_stem_pool, fpc_stem_pool_tasks, fpc_conv2d's 3100):
  * and form -9's packed patch geometry (fpc_wino_pack_geometry, fpc_net_set_wino_pack, fpc_net_wino_blocks, fpc_conv2d's -10):
+ * and the activation-range guard of the fp16-piece forms (fpc_act_range, fpc_net_survey_next, fpc_net_guard_ranges, fpc_net_guarded):
  * additions only, every earlier entry point keeps its behaviour. */
 #define FPC_ABI_VERSION 11
 
@@ -444,6 +445,51 @@ int fpc_net_force_direct_h3(fpc_net_t* net, int on);
  * itself and keeps it where it beats stem + max-pool together.  Returns 1 when the plan changed, 0 when it was already so, or a
  * negative code.  Drops the recorded graph. */
 int fpc_net_force_stem_pool(fpc_net_t* net, int on);
+/* ---- The activation-range guard of the fp16-piece forms (opt-in; nothing here runs unless it is called).
+ * The forms on two fp16 pieces per operand — Winograd -8 / -9 / -10, s2.0 with the p2 level folded in, the 6000 + split and 7000 +
+ * parts plans, the fused stem 3100 — hold an activation to 3 * 2^-23 relative only while it lies in 2^-2 .. 2^16 (see
+ * fpc_net_set_split_precision), and nothing in a forward looks at the activations.  The guard surveys them and moves the sites whose
+ * input lies outside onto their range-free plans.
+ *
+ * fpc_act_range: one pass over n contiguous floats (x 4-byte aligned; any n >= 0), accumulated into the 4-word device record rec4:
+ *   rec4[0]  the bits of max |x| over the FINITE elements, a non-negative float (atomicMax on the unsigned word; -0.0 counts as 0)
+ *   rec4[1]  += the number of non-finite elements (inf, NaN)
+ *   rec4[2]  += n, saturating at 2^32 - 1 (non-zero: the record was written at all)
+ *   rec4[3]  reserved, not touched
+ * The caller zeroes the record; several calls into one record give the maximum and the sums over all their tensors. */
+int fpc_act_range(const float* x, long long n, unsigned* rec4, fpc_stream_t stream);
+/* The NEXT fpc_net_forward, and only that one, runs fpc_act_range in front of every convolution site's launch, over every tensor the
+ * site's CURRENT plan reads as its matrix operand, into records_dev + 4 * site (device memory, 4 * sites words, owned and zeroed by
+ * the caller; sites must equal fpc_net_conv_count).  The four decoders of a grouped site accumulate into the index of decoder 0 (the
+ * other decoders' indices stay zero); the folded s2.0 surveys what it reads, two operands of two scales: c2 into its own record and p3, at
+ * p3's resolution (its nearest x2 upsample holds the same values), into the record of the p2 lateral site, which does not run while
+ * it is folded away (either record outside the bounds demotes the fold); the fused stem surveys the image.  That forward
+ * launches its kernels (no graph capture or replay, like a tuning pass; a recorded graph is kept), changes no plan, and its outputs
+ * are those of an ordinary forward bit for bit.  The workspace does not grow.  The survey is disarmed when that forward call returns,
+ * whatever it returns (a refused call included), and by records_dev = NULL (returns FPC_OK): the engine never keeps the pointer.
+ * FPC_EINVAL: a plan without loaded parameters, records_dev not 4-byte aligned, sites != fpc_net_conv_count. */
+int fpc_net_survey_next(fpc_net_t* net, unsigned* records_dev, int sites);
+/* Host arithmetic only (no device call).  records_host: a survey's records copied to the host.  A site whose current plan is an
+ * fp16-piece form is DEMOTED when its record shows a non-finite element (rec[1] > 0), max |x| >= hi, or 0 < max |x| < lo; not when
+ * the record is all zeros (every form is exact on zeros) or was never written (rec[2] == 0).  It goes to its best range-free plan:
+ * the best-scoring candidate of the autotuner that is not an fp16-piece form where the site was autotuned, else the plan of split
+ * level 1 — a Winograd site -7 (else -5), a 6000 + split / 7000 + parts plan the same tiling / parts on three bf16 pieces, the
+ * folded s2.0 the unfolded pair (the p2 lateral runs again on its own plan, s2.0 by the rule above), 3100 the stem kernel 3000 and
+ * the max-pool launch.  Returns the number of sites demoted by this call (idempotent: the same records again give 0) or a negative
+ * code (sites != fpc_net_conv_count, lo < 0, hi <= lo), and drops the recorded graph when it demoted any.  Demotions are sticky:
+ * they outlast fpc_net_load_params, travel with fpc_net_copy_plans (with the fallback plans; dst keeps its own demotions too), and a later autotuning pass offers a
+ * demoted site no fp16-piece form; an explicit fpc_net_force_* of the site wins and clears it.
+ * The bounds the Python front end passes are lo = 2^-2 and hi = 2^14, the envelope above with the headroom of the Winograd forms:
+ * the F(2x2, 3x3) input transform adds up to four values, so max |x| < 2^14 keeps every TRANSFORMED value below 2^16.  The direct and
+ * lateral forms (6000 +, 7000 +, 3100) have no transform and could take 4 x more; they are held to the same two numbers so that
+ * there is ONE rule.  The lower bound is on max |x|, not on the values that carry the sum: a tensor is demoted only when ALL of
+ * it lies below 2^-2, where the pair's error is 2^-24 absolute instead of relative.  That is conservative by about the ratio of a
+ * tensor's maximum to its RMS (a tensor with max 2^-3 and RMS 2^-6 is demoted although 2^-24 absolute is 2^-18 of its scale, and one
+ * with max 1 and RMS 2^-8 is not): the record carries no second moment on purpose — one word, one atomic, exact to test — and the
+ * guard sees only the frames that were surveyed. */
+int fpc_net_guard_ranges(fpc_net_t* net, const unsigned* records_host, int sites, float lo, float hi);
+/* 1 while site i stands demoted by fpc_net_guard_ranges, else 0. */
+int fpc_net_guarded(const fpc_net_t* net, int i);
 /* k_stem_pool_h3's task arithmetic for a stem output of Ho x Wo (host only, no device): out4 = bands of 10 pool rows, strips of 64
  * conv columns, conv outputs one frame's launch computes (the band overlap rows and the halo tiles included), conv outputs that
  * exist (Ho * Wo).  FPC_EINVAL for a shape the fused launch does not take. */
