@@ -1435,7 +1435,7 @@ __global__ __launch_bounds__(256) void k_pack_weight_bf3(const float* __restrict
 }
 
 // The same [Npad][Kpad] image as TWO fp16 planes for k_conv_igemm's three-product form: scaled by s = 2^k, the largest power of
-// two with max |w| s < 2^13 (k_wino_pack_h2's rule without the transform's 2.25; max |w| from k_absmax_bits in tail[1]), and split
+// two with max |w| s < 2^13 (k_wino_pack_fp16's rule without the transform's 2.25; max |w| from k_absmax_bits in tail[1]), and split
 // by truncation, w s = g1 + g2 + rest with |rest| <= 3 * 2^-23 |w s| (< 2^-24 where |w s| < 2^-2): out[(plane * Npad + n) * Kpad + k], tail[0] = 1 / s.
 __global__ __launch_bounds__(256) void k_pack_weight_h3(const float* __restrict__ w, unsigned short* __restrict__ out, float* __restrict__ tail,
                                                         int Cout, int Cin, int Cinp, int Kh, int Kw, int Kwp, int Npad, int Kpad) {

@@ -1,0 +1,354 @@
+// wino_tile.hpp — what the four-wave Winograd F(2x2, 3x3) kernels share (wino_w4.hip, wino_h2.hip, wino_h3.hip): one workgroup =
+// an 8 x 8 tile patch (16 x 16 output pixels) x 64 output channels, 256 threads = one wave per SIMD with up to 512 registers, wave
+// w owning transform row w; the K loop's input buffers and, after it, the 128 KB output transform image in LDS.  The files keep
+// their K loops (the operands' number format, the slot schedule, the weight image); the set-up around the loop and everything
+// behind it is here, once:
+//   patch decode (wino_patch) — staging plan and LDS-DMA issue (wino_stage_plan, wino_issue_in) — fragment addressing (wino_frag)
+//   and border zeroing (wino_zero_ring) — output transform and epilogue (wino_output) — the launchers' shape check
+//   (wino_tile_check) — the fp16 weight packers' host entry (launch_wino_pack_fp16, defined in wino_h2.hip)
+// Everything a kernel calls is __forceinline__ and takes VALUES (a reference to the kernel argument that survives inlining puts the
+// argument in scratch): the kernels sit at 512 registers, and their listings are the test of a change here (tools_dev/isa_stats.py).
+#pragma once
+#include <algorithm>
+#include "net_kernels.hpp"
+
+namespace fpc {
+namespace wino_tile {      // the three files say `using namespace wino_tile;`: nothing else sees these names
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
+
+constexpr int kTX = 8, kTY = 8;                  // tile patch 8 x 8 (16 x 16 output pixels)
+constexpr int kRW = 2 * kTX + 2, kRH = 2 * kTY + 2;      // staged input region 18 x 18
+constexpr int kBN = 64;                          // output channels per workgroup
+constexpr int kNT = kTX * kTY;                   // 64 tiles = two M halves
+constexpr int kInPieces = 18;                    // 1 KB LDS-DMA pieces of one K-step's input image (k_conv_wino's permuted image)
+constexpr int kInFloats = kInPieces * 256;       // 4608 floats per input buffer
+constexpr int kPairBytes = 16 * 2 * 2 * 64 * 16; // k_wino_pack_fp16<true>'s image of one pair of K-steps (wino_h3.hip): [xi 16][tile 2][piece 2][lane 64] x 16 bytes {4 ch of the even step, 4 ch of the odd step}
+constexpr int kLdsFloats = 4 * 2 * kNT * kBN;    // output transform image = 128 KB; the K loop's input buffers live in its space
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0x7FFFFFFF, 0x00020000);
+}
+// one scalar instruction per element (the files are built with -fno-slp-vectorize: beside matrix instructions a packed f32 instruction
+// costs more than the two scalar ones it replaces).  Plain C++, not inline asm: the compiler brackets an asm statement it cannot see
+// into with hazard s_nops (4 issue cycles each).  sgn = +-1: the fused form is exact either way.
+__device__ __forceinline__ f32x4 fma_s4(float s, f32x4 b, f32x4 a) {
+    return f32x4{__builtin_fmaf(s, b[0], a[0]), __builtin_fmaf(s, b[1], a[1]), __builtin_fmaf(s, b[2], a[2]), __builtin_fmaf(s, b[3], a[3])};
+}
+__device__ __forceinline__ f32x4 sub_s4(f32x4 a, f32x4 b) { return f32x4{a[0] - b[0], a[1] - b[1], a[2] - b[2], a[3] - b[3]}; }
+__device__ __forceinline__ f32x4 add_s4(f32x4 a, f32x4 b) { return f32x4{a[0] + b[0], a[1] + b[1], a[2] + b[2], a[3] + b[3]}; }
+
+__device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p; }
+
+// ---- patch decode.  Weight slice (64-channel block, group) fastest in the workgroup id: fixed per XCD under round-robin dispatch
+// (k_conv_wino).  The patch covers tiles (ty0 .., tx0 ..) of frame b.
+// PACK (wino_h3.hip): the patches are cut out of a canvas of `pack` frames side by side (wino_pack_geometry; tbx = patches per canvas
+// row of a full group).  A patch that starts at tile column tx0 of frame f and meets the frame's end after ks < 8 columns carries a
+// SEAM: its tile columns k >= ks are columns k - ks of frame f + 1.
+struct WinoPatch {
+    int nb, grp, bx, by, b, tx0, ty0;
+    int pk_ks, pk_raw, pk_slot;      // PACK: seam after pk_ks tile columns (99: none), tcw - tx0, this patch's GroupNorm record of frame b
+    bool pk_two;                     // PACK: the frame behind the seam exists
+};
+template <bool PACK>
+__device__ __forceinline__ WinoPatch wino_patch(int bid, int nnb, int groups, int tbx, int tby, int pack, int W, int B) {
+    WinoPatch q;
+    q.pk_ks = 99; q.pk_raw = 99; q.pk_slot = 0; q.pk_two = false;
+    q.nb = bid % nnb; bid /= nnb;
+    q.grp = bid % groups; bid /= groups;
+    if constexpr (!PACK) {
+        q.bx = bid % tbx; bid /= tbx;
+        q.by = bid % tby;
+        q.b = bid / tby;
+        q.tx0 = q.bx * kTX;
+    } else {
+        const int G = pack, tcw = (W + 1) >> 1, per = tbx * tby;
+        const int g = bid / per, rem = bid - g * per;
+        const int nf = min(G, B - g * G);                      // frames of this canvas row (a ragged last group has fewer,
+        const int tbxg = min(tbx, (nf * tcw + kTX - 1) / kTX); // and only the patches that reach them)
+        q.bx = rem % tbxg; q.by = rem / tbxg;
+        const int f = (kTX * q.bx) / tcw;
+        q.tx0 = kTX * q.bx - f * tcw;
+        q.b = g * G + f;
+        q.pk_raw = tcw - q.tx0;
+        q.pk_ks = q.pk_raw < kTX ? q.pk_raw : 99;
+        q.pk_two = q.pk_ks < kTX && f + 1 < nf;
+        q.pk_slot = q.bx - (f * tcw) / kTX;
+    }
+    q.ty0 = q.by * kTY;
+    return q;
+}
+// one decoder's entry of a per-group table (ConvPtrs, a pointer), the four entries passed as VALUES: selects, no indexed read of the
+// kernel argument (and no reference to it)
+template <class T>
+__device__ __forceinline__ T wino_group(const T v0, const T v1, const T v2, const T v3, int grp) {
+    T r = v0;
+    if (grp == 1) r = v1;
+    if (grp == 2) r = v2;
+    if (grp == 3) r = v3;
+    return r;
+}
+
+// ---- input staging: per K-step the 18 x 18 region x 8 channels as LDS-DMA pieces (wave + 4 i), i < 5 (18 pieces of 1 KB).  The image
+// is PERMUTED so that the fragment reads are conflict-free, and the 16-byte unit a lane's data lands in decides the global address
+// it fetches (k_conv_wino, PERM): unit = (cell * 8 + block) * 16 + 4 * (qh & 3) + (ah & 3), cell = (ah >> 2) * 3 + (qh >> 2),
+// block = (ry & 1) * 4 + (rx & 1) * 2 + channel half, ah = ry >> 1, qh = rx >> 1 (0..8).  The plan is fixed for the whole K loop: a
+// byte offset inside the image per lane and piece (ivo; the base moves 8 floats per step) and the piece's lane mask (imask).
+// up = 1: the source is read as its nearest-x2 upsample (wino_h3.hip's fold, phase 2: a lane's address is its low-resolution pixel).
+// PACK: the staged region of a seam patch holds ONE gap column, tile column k reads region columns k + (k >= ks) + ch: region column
+// ks holds frame f's last pixel (and the zero of x = W), column ks + 1 the zero of x = -1 and frame f + 1's first pixel.
+template <bool PACK>
+__device__ __forceinline__ void wino_stage_plan(unsigned (&ivo)[5], unsigned long long (&imask)[5], int wi, int lane, int y_in0, int x_in0, int H,
+                                                int W, int Cs, int up, int pk_ks, bool pk_two) {
+    const int Hs = H >> up, Ws = W >> up;                      // the source image's own size
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        const int slot = (wi + 4 * i) * 64 + lane;
+        const int blk = slot >> 4, res = slot & 15, cell = blk >> 3;
+        const int ah = (cell / 3) * 4 + (res & 3), qh = (cell % 3) * 4 + (res >> 2);
+        const int hf = blk & 1;
+        const int ry = 2 * ah + ((blk >> 2) & 1), rx = 2 * qh + ((blk >> 1) & 1);
+        const bool far = PACK && qh > pk_ks;      // behind the seam: frame b + 1, one gap column in between
+        const int y = y_in0 + ry, x = far ? rx - 2 * pk_ks - 3 : x_in0 + rx;
+        const int qmax = (PACK && pk_ks < kTX) ? kTX + 1 : kTX;
+        const bool iok = wi + 4 * i < kInPieces && ah <= kTY && qh <= qmax && y >= 0 && y < H && x >= 0 && x < W && (!far || pk_two);
+        ivo[i] = iok ? (unsigned)((((size_t)(y >> up) * Ws + (x >> up)) * Cs + 4 * hf) * sizeof(float)) +
+                              (far ? (unsigned)((size_t)Hs * Ws * Cs * sizeof(float)) : 0u)
+                        : 0u;
+        imask[i] = __ballot(iok);
+    }
+}
+// One K-step's pieces -> the input buffer at `buf` from the image at `src` (wave-uniform).  One asm block, no branch: EXEC is set to
+// each piece's lane mask (a wave-uniform 64-bit value; 0 for a piece this wave does not have or whose positions all lie outside the
+// image: the instruction then moves nothing but still counts in vmcnt, so every wave issues exactly five VMEM instructions per step
+// whatever the patch).  The compiler's own if (mask) form cost ~10 scalar / branch instructions per piece, in a loop that is bound
+// by instruction issue.  Nothing waits here: the caller counts the five in its s_waitcnt vmcnt.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+__device__ __forceinline__ void wino_issue_in(const float* buf, int wi, const unsigned (&ivo)[5], const unsigned long long (&imask)[5], const float* src) {
+    unsigned long long sv_;
+    const unsigned l0_ = lds_addr(buf + wi * 256);
+    asm volatile("s_mov_b64 %0, exec\n"
+                 "s_mov_b64 exec, %1\n s_mov_b32 m0, %6\n s_nop 0\n global_load_lds_dwordx4 %11, %16\n"
+                 "s_mov_b64 exec, %2\n s_mov_b32 m0, %7\n s_nop 0\n global_load_lds_dwordx4 %12, %16\n"
+                 "s_mov_b64 exec, %3\n s_mov_b32 m0, %8\n s_nop 0\n global_load_lds_dwordx4 %13, %16\n"
+                 "s_mov_b64 exec, %4\n s_mov_b32 m0, %9\n s_nop 0\n global_load_lds_dwordx4 %14, %16\n"
+                 "s_mov_b64 exec, %5\n s_mov_b32 m0, %10\n s_nop 0\n global_load_lds_dwordx4 %15, %16\n"
+                 "s_mov_b64 exec, %0\n"
+                 : "=&s"(sv_)
+                 : "s"(imask[0]), "s"(imask[1]), "s"(imask[2]), "s"(imask[3]), "s"(imask[4]),
+                   "s"(l0_), "s"(l0_ + 4096), "s"(l0_ + 8192), "s"(l0_ + 12288), "s"(l0_ + 16384),
+                   "v"(ivo[0]), "v"(ivo[1]), "v"(ivo[2]), "v"(ivo[3]), "v"(ivo[4]), "s"(src)
+                 : "memory", "m0");
+}
+#pragma clang diagnostic pop
+
+// ---- fragment addressing: this lane's tile of half 0 (half 1 = four tile rows further down = + 3 cells), the two region rows of
+// transform row wi, columns 2 txl + c.  in_a[ch] / in_b[ch]: float offsets of rows ra / rb at column 2 (txl + ch) in an input buffer;
+// returns the sign.  Row pair (ra, rb) and sign of B^T row wi:  0: d0-d2   1: d1+d2   2: d2-d1   3: d1-d3.  PACK: columns behind the seam lie one further.
+constexpr int in_cs = 2 * 16 * 4;          // + 1 column: the (rx & 1) block bit
+constexpr int in_ms = 3 * 8 * 16 * 4;      // + 4 tile rows (tile half 1): the next row of cells
+template <bool PACK>
+__device__ __forceinline__ float wino_frag(int (&in_a)[2], int (&in_b)[2], int wi, int li, int lh, int pk_ks) {
+    const int tyl = li >> 3, txl = (li & 7) + ((PACK && (li & 7) >= pk_ks) ? 1 : 0);
+    const int ra = (wi == 0) ? 0 : (wi == 2 ? 2 : 1);
+    const int rb = (wi == 0) ? 2 : (wi == 1 ? 2 : (wi == 2 ? 1 : 3));
+    auto unit = [&](int r, int ch) {      // float offset of row 2 tyl + r, column 2 (txl + ch), this lane's channel half
+        const int ah = tyl + (r >> 1), qh = txl + ch;
+        return ((((ah >> 2) * 3 + (qh >> 2)) * 8 + (r & 1) * 4 + lh) * 16 + 4 * (qh & 3) + (ah & 3)) * 4;
+    };
+    in_a[0] = unit(ra, 0); in_a[1] = unit(ra, 1);
+    in_b[0] = unit(rb, 0); in_b[1] = unit(rb, 1);
+    return (wi == 1) ? 1.f : -1.f;
+}
+// a patch that reaches over the image border zeroes its nbuf input buffers once (inactive DMA lanes leave them alone); an interior
+// patch rewrites every unit the fragment reads touch with every step's DMA.  (A seam patch zeroes too: the units of x = W and
+// x = -1 at the seam are never staged and must read zero.)
+__device__ __forceinline__ void wino_zero_ring(float* lds, int t, int nbuf, int y_in0, int x_in0, int H, int W, bool seam) {
+    if (y_in0 < 0 || x_in0 < 0 || y_in0 + kRH > H || x_in0 + kRW > W || seam) {
+        for (int i = t; i < nbuf * kInFloats / 4; i += 256) reinterpret_cast<f32x4*>(lds)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+}
+
+// ---- output transform and epilogue of the accumulators acc[xi column j][tile half mt][32-channel tile nt].  Column part inside the
+// wave: z0 = m0 + m1 + m2, z1 = m1 - m2 - m3; row part across the four transform-row waves through LDS: y0 = z[0] + z[1] + z[2],
+// y1 = z[1] - z[2] - z[3].  Z[row][cc][tile 64][co 64], one pass.  Output stage: thread = (tile of a 16-tile pass, 16-byte channel
+// quad): within a ds_read_b128 lane group the 16 quads are 16 different bank slots; a wave stores 4 tiles x 256 contiguous bytes.
+// out = relu(inv_s * y [+ btab by border class] [* scale] + shift [+ res]); GroupNorm records of the stored values.  No staging may
+// be in flight.  Ends with the stamp record's last word (tools_dev/wino_stamps.py).
+// FOLD: the bias table and nothing else (launch_conv_wino_h3 refuses scale, shift, residual and ReLU with a fold): the 64 registers of
+// residual prefetch and the tests fall away at compile time.
+// inv_s = 1 / (the power of two the weights were scaled by): exact; 1.0f for an unscaled image.  btab (FOLD): conv3x3(W, b 1_inside)
+// by the output pixel's border class, [16][Cout].  (The pointers and the float are arguments of their own: in a struct beside the
+// ints, the fold kernel kept the struct in memory.)
+struct WinoEpi { int H, W, Cout, relu, tbx, tby, pack_rx; };
+template <bool PACK, bool FOLD>
+__device__ __forceinline__ void wino_output(float* lds, const f32x16 (&acc)[4][2][2], const ConvPtrs P, const WinoPatch pt, const WinoEpi e,
+                                            const float inv_s, const float* btab, long long* dbg, const long long t_kend, const int t,
+                                            const int wi) {
+    const int H = e.H, W = e.W, Cout = e.Cout, HW = H * W;
+    // (PACK: the thread's indices are rebuilt from the lane counter here instead of being carried over the K loop: the packed
+    // set-up needs a few registers more, and the allocator otherwise parks these in scratch from the set-up to the epilogue)
+    const int lane = PACK ? (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) : t & 63;
+    const int t_e = PACK ? wi * 64 + lane : t;
+    const int oq = t_e & 15, otl = t_e >> 4;                  // quad 0..15, tile 0..15 (+ 16 per tile pass)
+    // (ot & 7 is the same in all four tile passes of a thread: it lies wholly on one side of a seam)
+    const bool o_far = PACK && (otl & 7) >= pt.pk_ks;
+    const int ob = o_far ? pt.b + 1 : pt.b, otx = o_far ? (otl & 7) - pt.pk_ks : pt.tx0 + (otl & 7);
+    const bool o_ok = !o_far || pt.pk_two;
+    const int n = pt.nb * kBN + oq * 4;
+    const f32x4 e_sc = (!FOLD && P.scale) ? *reinterpret_cast<const f32x4*>(P.scale + n) : f32x4{1.f, 1.f, 1.f, 1.f};
+    const f32x4 e_sh = (!FOLD && P.shift) ? *reinterpret_cast<const f32x4*>(P.shift + n) : f32x4{0.f, 0.f, 0.f, 0.f};
+    // the residual of this thread's 4 x 4 outputs is requested BEFORE the output transform's barriers (one workgroup per CU: nothing
+    // else hides that latency; k_conv_wino does the same)
+    f32x4 e_res[4][4];
+#pragma unroll
+    for (int tp = 0; tp < 4; ++tp)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int ot = otl + 16 * tp;
+            const int y = 2 * (pt.ty0 + (ot >> 3)) + (q >> 1), x = 2 * otx + (q & 1);
+            e_res[tp][q] = (!FOLD && P.res && o_ok && y < H && x < W) ? *reinterpret_cast<const f32x4*>(P.res + ((size_t)ob * HW + (size_t)y * W + x) * Cout + n)
+                                                             : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    __syncthreads();
+    float* const zb = lds + ((wi * 2) * kNT + 4 * (lane >> 5)) * kBN + (lane & 31);
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                // one base register per lane + a compile-time offset (< 64 KB: the instruction's immediate) per store
+                const int mc = mt * 32 + (r & 3) + 8 * (r >> 2);
+                const float m0 = acc[0][mt][nt][r], m1 = acc[1][mt][nt][r], m2 = acc[2][mt][nt][r], m3 = acc[3][mt][nt][r];
+                zb[(0 * kNT + mc) * kBN + nt * 32] = m0 + m1 + m2;
+                zb[(1 * kNT + mc) * kBN + nt * 32] = m1 - m2 - m3;
+            }
+    __syncthreads();
+    f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int tp = 0; tp < 4; ++tp) {
+        const int ot = otl + 16 * tp;
+        const int oty = pt.ty0 + (ot >> 3);
+        f32x4 z[4][2];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int cc = 0; cc < 2; ++cc) z[i][cc] = *reinterpret_cast<const f32x4*>(lds + ((i * 2 + cc) * kNT + ot) * kBN + oq * 4);
+#pragma unroll
+        for (int rr = 0; rr < 2; ++rr)
+#pragma unroll
+            for (int cc = 0; cc < 2; ++cc) {
+                const int y = 2 * oty + rr, x = 2 * otx + cc;
+                if (y >= H || x >= W || !o_ok) continue;
+                f32x4 val = (rr == 0 ? z[0][cc] + z[1][cc] + z[2][cc] : z[1][cc] - z[2][cc] - z[3][cc]) * inv_s;      // (a power of two: exact)
+                if (FOLD) {
+                    const int cls = (((y == 0) | ((y == H - 1) << 1)) << 2) | (x == 0) | ((x == W - 1) << 1);
+                    val += *reinterpret_cast<const f32x4*>(btab + (size_t)cls * Cout + n);
+                }
+                if (!FOLD && P.scale) val = val * e_sc;
+                val = val + e_sh;
+                const size_t o = ((size_t)ob * HW + (size_t)y * W + x) * Cout + n;
+                if (!FOLD && P.res) val += e_res[tp][2 * rr + cc];
+                if (!FOLD && e.relu) { val[0] = fmaxf(val[0], 0.f); val[1] = fmaxf(val[1], 0.f); val[2] = fmaxf(val[2], 0.f); val[3] = fmaxf(val[3], 0.f); }
+                *reinterpret_cast<f32x4*>(P.out + o) = val;
+                s1 += val;
+                s2 += val * val;
+            }
+    }
+    if (PACK && P.gn_part) {
+        // one record per frame this workgroup touches: two sets of sums, a thread's go to its side of the seam; the reduction is the
+        // plain one on both.  Record of frame b: slot pk_slot of row by (pack_rx slots per row: the most patches a frame meets),
+        // of frame b + 1: slot 0.  The patch that holds a frame's last tile column zeroes the slots the frame does not use, so every
+        // record k_gn_finalize reads is written by this launch.
+        f32x4 q1[2] = {o_far ? f32x4{0.f, 0.f, 0.f, 0.f} : s1, o_far ? s1 : f32x4{0.f, 0.f, 0.f, 0.f}};
+        f32x4 q2[2] = {o_far ? f32x4{0.f, 0.f, 0.f, 0.f} : s2, o_far ? s2 : f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+        for (int sd = 0; sd < 2; ++sd)
+#pragma unroll
+            for (int o = 16; o < 64; o <<= 1)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { q1[sd][k] += __shfl_xor(q1[sd][k], o, 64); q2[sd][k] += __shfl_xor(q2[sd][k], o, 64); }
+        __syncthreads();
+        float* red = lds;                                     // [2 sides][4 waves][64 ch][2]
+        if (lane < 16) {
+#pragma unroll
+            for (int sd = 0; sd < 2; ++sd)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    red[((sd * 4 + wi) * kBN + oq * 4 + k) * 2] = q1[sd][k];
+                    red[((sd * 4 + wi) * kBN + oq * 4 + k) * 2 + 1] = q2[sd][k];
+                }
+        }
+        __syncthreads();
+        if (t_e < 2 * kBN && (t_e < kBN || pt.pk_two)) {
+            const int sd = t_e >> 6, ch = t_e & (kBN - 1);
+            float u1 = 0.f, u2 = 0.f;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) { u1 += red[((sd * 4 + w) * kBN + ch) * 2]; u2 += red[((sd * 4 + w) * kBN + ch) * 2 + 1]; }
+            const int rx = e.pack_rx, Pn = e.tby * rx, slot = sd ? 0 : pt.pk_slot;
+            float* g = P.gn_part + (((size_t)(pt.b + sd) * Pn + pt.by * rx + slot) * Cout + pt.nb * kBN + ch) * 2;
+            g[0] = u1; g[1] = u2;
+            if (sd == 0 && pt.pk_raw <= kTX)
+                for (int z = slot + 1; z < rx; ++z) { g += (size_t)Cout * 2; g[0] = 0.f; g[1] = 0.f; }
+        }
+    } else if (P.gn_part) {
+        // per-channel sums of this workgroup's outputs: a wave holds 4 tiles (lane bits 4-5) x 16 quads (lane bits 0-3) per pass:
+        // butterfly over the tile bits, then the four waves' sums through LDS in wave order
+#pragma unroll
+        for (int o = 16; o < 64; o <<= 1)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { s1[k] += __shfl_xor(s1[k], o, 64); s2[k] += __shfl_xor(s2[k], o, 64); }
+        __syncthreads();
+        float* red = lds;                                     // [4 waves][64 ch][2]
+        if (lane < 16) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { red[(wi * kBN + oq * 4 + k) * 2] = s1[k]; red[(wi * kBN + oq * 4 + k) * 2 + 1] = s2[k]; }
+        }
+        __syncthreads();
+        if (t_e < kBN) {
+            float u1 = 0.f, u2 = 0.f;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) { u1 += red[(w * kBN + t_e) * 2]; u2 += red[(w * kBN + t_e) * 2 + 1]; }
+            const int Pn = e.tbx * e.tby;
+            float* g = P.gn_part + (((size_t)pt.b * Pn + pt.by * e.tbx + pt.bx) * Cout + pt.nb * kBN + t_e) * 2;
+            g[0] = u1; g[1] = u2;
+        }
+    }
+    if (dbg && lane == 0) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        dbg[((size_t)blockIdx.x * 4 + wi) * 8 + 7] = clock64() - t_kend;      // K loop end -> last store acknowledged
+    }
+}
+
+// ---- host side.  What every launcher of the family checks: groups, Cin a multiple of kch (the form's channels per K-step or pair),
+// Cout of 64, 32-bit lane offsets inside one image, 31-bit buffer offsets inside one block's weight images (step_bytes per kch
+// channels), the patch grid (packed: wino_pack_geometry's own; otherwise one frame per patch row) and the workgroup
+// count, returned in *nblk.
+inline int wino_tile_check(const WinoArgs& a, int groups, int kch, int step_bytes, bool packed, long long* nblk) {
+    if (groups < 1 || groups > kMaxGroup || a.Cin % kch != 0 || a.Cout % kBN != 0) return FPC_EINVAL;
+    if ((long long)a.H * a.W * a.Cin * (long long)sizeof(float) >= (1LL << 32)) return FPC_EINVAL;
+    if ((long long)(a.Cin / kch) * step_bytes >= (1LL << 31)) return FPC_EINVAL;
+    if (packed) {
+        const WinoPackGeom q = wino_pack_geometry(a.H, a.W, a.B, a.Cin, !a.fold);
+        if (q.G != a.pack || q.tbx != a.tbx || q.tby != a.tby || q.rx != a.pack_rx) return FPC_EINVAL;
+        *nblk = q.patches * (a.Cout / kBN) * groups;
+    } else {
+        if (a.tbx != cdiv(cdiv(a.W, 2), kTX) || a.tby != cdiv(cdiv(a.H, 2), kTY)) return FPC_EINVAL;
+        *nblk = (long long)a.tbx * a.tby * a.B * (a.Cout / kBN) * groups;
+    }
+    return (*nblk < 1 || *nblk >= (1LL << 31)) ? FPC_EINVAL : 0;
+}
+}  // namespace wino_tile
+
+// wino_h2.hip: clears the image's two-float tail, finds max |w| (of w and, if given, of w_also too: images that share one scale),
+// packs.  pair = wino_h3.hip's fragment order.
+int launch_wino_pack_fp16(const float* w_oihw, float* packed, int Cout, int Cin, bool pair, const float* w_also, int Cin_also, hipStream_t s);
+
+}  // namespace fpc

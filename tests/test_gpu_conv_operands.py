@@ -159,7 +159,7 @@ def test_numpy_winograd_is_the_convolution():
 # ---- the packers' power-of-two weight scale and the propagated bound
 
 def _weight_scale(w, wino):
-    """k_wino_pack_h2 / k_pack_weight_h3: the largest power of two s with 2.25 max |w| s < 2^13 (Winograd) or max |w| s < 2^13."""
+    """k_wino_pack_fp16 / k_pack_weight_h3: the largest power of two s with 2.25 max |w| s < 2^13 (Winograd) or max |w| s < 2^13."""
     wmax = np.float32(w.abs().max().item())
     _, e = np.frexp(np.float32(2.25) * wmax if wino else wmax)
     return 2.0 ** (13 - int(e))

@@ -4,7 +4,7 @@ with the p3 term's Winograd F(2x2, 3x3) input transform zero in row 2 and column
 import numpy as np
 import pytest
 
-# the kernel's B^T rows (wino_h3.hip: 0: d0-d2  1: d1+d2  2: d2-d1  3: d1-d3), G and A^T of F(2x2, 3x3) (k_wino_pack_h3, the epilogue)
+# the kernel's B^T rows (wino_tile.hpp, wino_frag: 0: d0-d2  1: d1+d2  2: d2-d1  3: d1-d3), G and A^T of F(2x2, 3x3) (k_wino_pack_fp16, the epilogue)
 BT = np.array([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], dtype=np.float64)
 G = np.array([[1, 0, 0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0, 0, 1]], dtype=np.float64)
 AT = np.array([[1, 1, 1, 0], [0, 1, -1, -1]], dtype=np.float64)

@@ -1,6 +1,6 @@
 """The piece arithmetic of the split-precision convolution forms, emulated in numpy and held to the bound the kernels' headers print.
 
-split_h2 (csrc/common.hpp, and the same two conversions in k_wino_pack_h2 / k_pack_weight_h3): x = h1 + h2 + rest, h1 = fp16(x) and
+split_h2 (csrc/common.hpp, and the same two conversions in k_wino_pack_fp16 / k_pack_weight_h3): x = h1 + h2 + rest, h1 = fp16(x) and
 h2 = fp16(x - h1), both by v_cvt_pkrtz_f16_f32 — round toward zero, subnormals kept, no infinity (the largest finite value instead).
 split_bf3: x = p1 + p2 + p3, each the high 16 bits of what is left.
 

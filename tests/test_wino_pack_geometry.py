@@ -2,7 +2,7 @@
 
 G frames of a small map lie side by side on a canvas row and the 8 x 8 tile patches are cut out of the canvas; a patch that meets a
 frame's end after ks < 8 tile columns carries a seam, and its staged region one gap column.  The model below repeats the kernel's
-slot decode, its seam arithmetic and its fragment addressing (csrc/wino_h3.hip) on the geometry the library reports and checks
+slot decode, its seam arithmetic and its fragment addressing (csrc/wino_tile.hpp: wino_patch, wino_stage_plan, wino_frag) on the geometry the library reports and checks
 that every fragment read sees the pixel it should (or an unstaged unit, which reads zero), that every tile of every frame is owned
 by exactly one (patch, slot), and that every GroupNorm record k_gn_finalize reads is written exactly once."""
 import ctypes
