@@ -150,12 +150,13 @@ static size_t splitk_floats_for(const ConvPlan& p, int groups, int B, int Npad) 
 // 128-channel form's image is there only where Cout % 128 == 0.  Behind the last image the region keeps kWinoSlack floats.
 enum WinoImage { kImgF32, kImgBf3, kImgC128, kImgH2, kImgH3, kWinoImageCount };
 struct WinoImageDesc { int units, tail; int (*pack)(const float* w_oihw, float* packed, int Cout, int Cin, hipStream_t s); };
+static int pack_h3_plain(const float* w_oihw, float* packed, int Cout, int Cin, hipStream_t s) { return launch_wino_pack_h3(w_oihw, packed, Cout, Cin, false, s); }
 constexpr WinoImageDesc kWinoImages[kWinoImageCount] = {
     {16, 0, launch_wino_pack},            // f32
     {24, 0, launch_wino_pack_bf3},        // split precision: three bf16 planes
     {24, 0, launch_wino_pack_c128},       // ... in the 128-channel form's fragment order (wino128.hip)
     {16, 8, launch_wino_pack_h2},         // two fp16 pieces in fragment order (wino_h2.hip); the tail: its two scale floats, kept 32-byte aligned
-    {16, 8, launch_wino_pack_h3},         // ... in pair order (wino_h3.hip), with the same tail
+    {16, 8, pack_h3_plain},               // ... in pair order (wino_h3.hip), with the same tail; a transposed site's: pack_wino_h3_image
 };
 constexpr size_t kWinoSlack = 128;      // a 64-float line for the tails + 64 zero floats (fpc_conv2d's zero page where the code object has none)
 
@@ -217,9 +218,10 @@ static WinoGrid wino_grid(int form, int H, int W) { return {cdiv(cdiv(W, 2), 8),
 
 // ---- the integer a plan is reported by (fpc_net_conv_plan's out5[2]) and requested by (fpc_conv2d's `nsplit`): fpc.h, FPC_PLAN_*.
 // What a request asks for (nsplit: the split-K factor, 0 = the planner's, or -form; wino: the form or 0):
-struct Conv2dRequest { int nsplit; bool bf3, two_launch; int wino, lat; bool stem; int pw; bool h3, pool, pack; };
+struct Conv2dRequest { int nsplit; bool bf3, two_launch; int wino, lat; bool stem; int pw; bool h3, pool, pack, orient; };
 static Conv2dRequest decode_plan(int code) {
-    Conv2dRequest r{code, false, false, 0, 0, false, 0, false, false, false};
+    Conv2dRequest r{code, false, false, 0, 0, false, 0, false, false, false, false};
+    if (code == FPC_PLAN_WINO_ORIENT) { r.orient = true; r.nsplit = -kWinoH3; }      // form -9 in the orientation its shape asks for (wino_orient_rule), transposed sites packed along y
     if (code == FPC_PLAN_WINO_PACKED) { r.pack = true; r.nsplit = -kWinoH3; }      // form -9 with its patches cut out of canvas rows of several frames (wino_pack_geometry)
     if (r.nsplit >= FPC_PLAN_LATERAL_H3 && r.nsplit < FPC_PLAN_LATERAL_H3 + 1000) { r.lat = r.nsplit - FPC_PLAN_LATERAL_H3; r.h3 = true; r.nsplit = 1; return r; }      // + parts = k_lateral1x1 on two fp16 pieces
     if (r.nsplit >= FPC_PLAN_H3 && r.nsplit < FPC_PLAN_H3 + 200) { r.h3 = true; r.nsplit -= FPC_PLAN_H3; }      // + split = k_conv_igemm's three-product form; what is left (< 200) reaches the two-launch line only
@@ -291,6 +293,8 @@ struct fpc_net {
     int use_graph = 0;            // replay the frame-invariant launches as a HIP graph (fpc_net_set_graph)
     long long wino_blocks = 0;    // workgroups of the form-9 launches of the last forward that launched its kernels (fpc_net_wino_blocks)
     int wino_pack = 1;            // form-9 launches cut their patches out of canvas rows of several frames where that saves patches (fpc_net_set_wino_pack)
+    int wino_orient = 1;          // form-9 launches run transposed at the sites wino_orient_rule names (fpc_net_set_wino_orient)
+    std::vector<char> c_tr;       // 1: the conv is a form-9 candidate at a shape the rule transposes (every decoder's; its h3 image follows wino_orient)
     int split_precision = 0;      // autotuning may pick the bf16 x 3 form of a direct convolution (fpc_net_set_split_precision)
     hipGraphExec_t graph_exec = nullptr;
     size_t zeros_off = 0;         // 64 zero floats (DMA source for out-of-image positions)
@@ -532,6 +536,10 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
     n->guarded.assign(n->convs.size(), 0);
     n->c_howo.assign(n->convs.size(), 0);
     n->c_groups.assign(n->convs.size(), 0);
+    n->c_tr.assign(n->convs.size(), 0);
+    auto oriented = [&](int ci, int h, int w) { if (ci >= 0 && n->convs[ci].wino_ok) n->c_tr[ci] = wino_orient_rule(h, w) ? 1 : 0; };
+    for (int L = 0; L < 4; ++L)
+        for (const fpc_net::Block& blk : n->blocks[L]) { oriented(blk.conv1, fh[L], fw[L]); oriented(blk.conv2, fh[L], fw[L]); }
     auto plan = [&](int ci, int HoWo, int groups) {
         const PackedConv& c = n->convs[ci];
         n->c_howo[ci] = HoWo; n->c_groups[ci] = groups;
@@ -559,6 +567,10 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
         n->gn_P[i] = cdiv(HoWo, 128) * 4;      // upper bound of mtiles*bm/32 over the tilings
         // ... and of the packed form-9 launch's records per frame (a seam patch writes one per frame it touches)
         n->gn_P[i] = std::max(n->gn_P[i], wino_pack_geometry(fh[seg_level[i]], fw[seg_level[i]], B, n->convs[n->dec[0].seg[i]].Cin, true).gn_rows);
+        // a transposed launch's records lie inside that reservation (the rule asks for 8 tile rows: wino_orient_rule); it does not grow
+        bool tr;
+        if (wino_launch_geometry(fh[seg_level[i]], fw[seg_level[i]], B, n->convs[n->dec[0].seg[i]].Cin, true, true, &tr).gn_rows > n->gn_P[i]) { delete n; return FPC_EINVAL; }
+        for (int d = 0; d < 4; ++d) oriented(n->dec[d].seg[i], fh[seg_level[i]], fw[seg_level[i]]);
         for (int d = 0; d < 4; ++d) {
             n->gn_part_off[d][i] = n->alloc((size_t)B * n->gn_P[i] * 128 * 2);
             n->gn_aff_off[d][i] = n->alloc((size_t)B * 128 * 2);
@@ -619,6 +631,40 @@ extern "C" int fpc_net_set_wino_pack(fpc_net_t* n, int on) {
     return FPC_OK;
 }
 
+// The h3 image of conv `ci` in the orientation the site runs in, and decoder d's fold images and bias table in s2.0's.
+static int pack_wino_h3_image(const fpc_net* n, int ci, hipStream_t s) {
+    const PackedConv& c = n->convs[ci];
+    return launch_wino_pack_h3(n->pptr[c.p_w], n->ws + c.wino_off + wino_image_offset(kImgH3, c.Cout, c.Cin), c.Cout, c.Cin,
+                               n->wino_orient && n->c_tr[ci], s);
+}
+static int pack_fold_images(const fpc_net* n, int d, hipStream_t s) {
+    const PackedConv &sc = n->convs[n->dec[d].seg[6]], &lc = n->convs[n->dec[d].lat[3]];
+    const bool tr = n->wino_orient && n->c_tr[n->dec[d].seg[6]];
+    int rc = launch_fold_compose(n->pptr[sc.p_w], n->pptr[lc.p_w], n->pptr[lc.p_bias], n->ws + n->fold_wc_off[d],
+                                 n->ws + n->fold_tab_off[d], sc.Cout, sc.Cin, lc.Cin, tr, s);
+    if (!rc) rc = launch_wino_pack_h3_pair(n->ws + n->fold_wc_off[d], n->ws + n->fold_img1_off[d], lc.Cin, n->pptr[sc.p_w],
+                                           n->ws + n->fold_img2_off[d], sc.Cin, sc.Cout, tr, s);
+    return rc;
+}
+
+// on = 1 (the default): a form-9 launch runs TRANSPOSED at the sites wino_orient_rule names (wide maps whose tile columns fill whole
+// patches and whose tile rows do not: frames then pack along the image's y); on = 0: every site in the stored orientation.  A site
+// keeps ONE h3 image, in the orientation it runs in: the switch repacks the affected sites' images (and the fold's) in place from the
+// parameters, on the stream of the last load, and waits for it.  The plans and the workspace do not change; the recorded graph is dropped.
+extern "C" int fpc_net_set_wino_orient(fpc_net_t* n, int on) {
+    if (!n || on < 0 || on > 1) return FPC_EINVAL;
+    if (n->wino_orient == on) return FPC_OK;
+    drop_graph(n);
+    n->wino_orient = on;
+    if (!n->loaded) return FPC_OK;
+    if (hipDeviceSynchronize() != hipSuccess) return FPC_ELAUNCH;      // no launch may be reading an image that is repacked
+    for (size_t ci = 0; ci < n->convs.size(); ++ci)
+        if (n->c_tr[ci] && wino_form_ok(kWinoH3, n->convs[ci].Cin, n->convs[ci].Cout)) { const int rc = pack_wino_h3_image(n, (int)ci, n->load_stream); if (rc) return rc; }
+    if (n->fold_ok && n->c_tr[n->dec[0].seg[6]])
+        for (int d = 0; d < 4; ++d) { const int rc = pack_fold_images(n, d, n->load_stream); if (rc) return rc; }
+    return hipStreamSynchronize(n->load_stream) == hipSuccess ? FPC_OK : FPC_ELAUNCH;
+}
+
 // workgroups of all form-9 launches of the last forward that launched (or captured) its kernels; -1 without a plan
 extern "C" int64_t fpc_net_wino_blocks(const fpc_net_t* n) { return n ? (int64_t)n->wino_blocks : -1; }
 
@@ -652,7 +698,8 @@ extern "C" int fpc_net_load_params(fpc_net_t* n, const float* const* params, int
     if (n->split_precision >= 3) { int rc = pack_h3_images(n, s); if (rc) return rc; }
     if (hipMemsetAsync(n->ws + n->zeros_off, 0, 64 * sizeof(float), s) != hipSuccess) return FPC_ELAUNCH;
     if (hipMemsetAsync(n->ws + n->tickets_off, 0, kConvTickets * sizeof(int), s) != hipSuccess) return FPC_ELAUNCH;
-    for (const PackedConv& c : n->convs) {
+    for (size_t ci = 0; ci < n->convs.size(); ++ci) {
+        const PackedConv& c = n->convs[ci];
         int rc = launch_pack_weight(n->pptr[c.p_w], n->ws + c.w_off, c.Cout, c.Cin, c.Cinp, c.Kh, c.Kw, c.Kwp, c.Npad, c.Kpad, s);
         if (rc) return rc;
         rc = launch_pack_weight_bf3(n->pptr[c.p_w], n->ws + c.w_off, c.Cout, c.Cin, c.Cinp, c.Kh, c.Kw, c.Kwp, c.Npad, c.Kpad, s);
@@ -662,7 +709,8 @@ extern "C" int fpc_net_load_params(fpc_net_t* n, const float* const* params, int
                 const WinoImage img = kWinoForms[f].image;
                 if (!wino_form_ok(f, c.Cin, c.Cout) || (done >> img & 1)) continue;
                 done |= 1 << img;
-                rc = kWinoImages[img].pack(n->pptr[c.p_w], n->ws + c.wino_off + wino_image_offset(img, c.Cout, c.Cin), c.Cout, c.Cin, s);
+                rc = img == kImgH3 ? pack_wino_h3_image(n, (int)ci, s)      // (in the site's orientation)
+                                   : kWinoImages[img].pack(n->pptr[c.p_w], n->ws + c.wino_off + wino_image_offset(img, c.Cout, c.Cin), c.Cout, c.Cin, s);
                 if (rc) return rc;
             }
         }
@@ -674,11 +722,7 @@ extern "C" int fpc_net_load_params(fpc_net_t* n, const float* const* params, int
     }
     if (n->fold_ok)
         for (int d = 0; d < 4; ++d) {
-            const PackedConv &sc = n->convs[n->dec[d].seg[6]], &lc = n->convs[n->dec[d].lat[3]];
-            int rc = launch_fold_compose(n->pptr[sc.p_w], n->pptr[lc.p_w], n->pptr[lc.p_bias], n->ws + n->fold_wc_off[d],
-                                         n->ws + n->fold_tab_off[d], sc.Cout, sc.Cin, lc.Cin, s);
-            if (!rc) rc = launch_wino_pack_h3_pair(n->ws + n->fold_wc_off[d], n->ws + n->fold_img1_off[d], lc.Cin, n->pptr[sc.p_w],
-                                                   n->ws + n->fold_img2_off[d], sc.Cin, sc.Cout, s);
+            const int rc = pack_fold_images(n, d, s);
             if (rc) return rc;
         }
     n->loaded = true;
@@ -707,6 +751,7 @@ void fill_conv_args(const fpc_net* n, ConvArgs& a, const PackedConv& c, const Co
     a.tickets = (int*)(n->ws + n->tickets_off);
     a.fused = p.fused;
     a.wino_pack = n->wino_pack;
+    a.wino_orient = n->wino_orient;
 }
 
 int launch_conv_plan(ConvArgs& a, const ConvPlan& p, int groups, hipStream_t s) {
@@ -773,9 +818,11 @@ int launch_conv_plan(ConvArgs& a, const ConvPlan& p, int groups, hipStream_t s) 
         w.waves = f.waves;
         const WinoGrid wg = wino_grid(p.wino, a.Ho, a.Wo);
         w.tbx = wg.tbx; w.tby = wg.tby;
-        if (p.wino == kWinoH3) {      // packing: the same workgroups, fewer of them — a property of the launch, not of the plan
-            const WinoPackGeom q = wino_pack_geometry(a.Ho, a.Wo, a.B, a.Cin, a.wino_pack && !p.fold);
-            if (q.G > 1) { w.pack = q.G; w.tbx = q.tbx; w.pack_rx = q.rx; }
+        if (p.wino == kWinoH3) {      // packing and orientation: the same workgroups, fewer of them — properties of the launch, not of the plan
+            bool tr;
+            const WinoPackGeom q = wino_launch_geometry(a.Ho, a.Wo, a.B, a.Cin, a.wino_orient, a.wino_pack && !p.fold, &tr);
+            if (q.G > 1 || tr) { w.pack = q.G; w.tbx = q.tbx; w.tby = q.tby; w.pack_rx = q.rx; }
+            w.orient = tr ? 1 : 0;
             a.wino_blocks = q.patches * (a.Cout / 64) * groups;
         }
         if (p.fold) {      // c2 on Wc's image + up2(p3) on W's (the p2 input of .p[g] is not read)
@@ -810,8 +857,9 @@ int launch_conv_plan(ConvArgs& a, const ConvPlan& p, int groups, hipStream_t s) 
 }
 
 // number of GroupNorm partial rows per image a plan writes
-int plan_gn_rows(const ConvPlan& p, int Ho, int Wo, int B, int Cin, int pack) {
-    if (p.wino == kWinoH3) return wino_pack_geometry(Ho, Wo, B, Cin, pack && !p.fold).gn_rows;
+int plan_gn_rows(const ConvPlan& p, int Ho, int Wo, int B, int Cin, int pack, int orient) {
+    bool tr;
+    if (p.wino == kWinoH3) return wino_launch_geometry(Ho, Wo, B, Cin, orient, pack && !p.fold, &tr).gn_rows;
     return p.wino ? wino_grid(p.wino, Ho, Wo).patches() : p.mtiles * p.bm / 32;
 }
 
@@ -876,10 +924,11 @@ std::vector<ConvPlan> tune_candidates(const ConvArgs& a, int groups, int split, 
 // Workgroups plan `q` launches on site `a` and the share of the chip's workgroup slots they take, held to [1/8, 1].
 struct PlanFootprint { double nblk, share; };
 PlanFootprint plan_footprint(const ConvPlan& q, const ConvArgs& a, int groups) {
+    bool tr;
     double nblk = q.stem ? 512.0      // (a persistent 512-thread, 86 KB workgroup per CU: the whole chip, whatever its grid)
                   : q.lat ? (double)cdiv(a.Ho * a.Wo, 128) * a.B * q.lat
                   : q.pw ? (double)cdiv(a.B * a.Ho * a.Wo, pw_tile_pixels(q.pw - 1)) * (a.Cout / 64) * groups * q.pw      // (8-wave workgroups count twice)
-                  : q.wino == kWinoH3 ? (double)wino_pack_geometry(a.Ho, a.Wo, a.B, a.Cin, a.wino_pack && !q.fold).patches * (a.Cout / 64) * groups
+                  : q.wino == kWinoH3 ? (double)wino_launch_geometry(a.Ho, a.Wo, a.B, a.Cin, a.wino_orient, a.wino_pack && !q.fold, &tr).patches * (a.Cout / 64) * groups
                   : q.wino ? (double)wino_grid(q.wino, a.Ho, a.Wo).patches() * a.B * (a.Cout / kWinoForms[q.wino].bn) * groups
                          : (double)q.mtiles * q.ntiles * q.nsplit * a.B * groups;
     double share = nblk / (256.0 * (q.wino ? kWinoForms[q.wino].wg_per_cu : 2));
@@ -1122,7 +1171,7 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
                 g.beta[k * kMaxGroup + d] = n->pptr[n->dec[d].p_gn[si] + 1];
                 g.affine[k * kMaxGroup + d] = ws + n->gn_aff_off[d][si];
             }
-            g.P[k] = plan_gn_rows(n->cplan[n->dec[0].seg[si]], o0.H, o0.W, B, n->convs[n->dec[0].seg[si]].Cin, n->wino_pack);
+            g.P[k] = plan_gn_rows(n->cplan[n->dec[0].seg[si]], o0.H, o0.W, B, n->convs[n->dec[0].seg[si]].Cin, n->wino_pack, n->wino_orient);
             g.count[k] = (long long)o0.H * o0.W * 4;
             ++k;
         }
@@ -1568,6 +1617,19 @@ extern "C" int fpc_wino_pack_geometry(int H, int W, int B, int Cin, int fold, in
     return FPC_OK;
 }
 
+// The same for a site under the orientation rule (wino_orient_rule / wino_launch_geometry; host arithmetic): out9[0] = 1 where the
+// launch runs transposed — then out9[1..8] is fpc_wino_pack_geometry's out8 of the virtual image W x H, packed whatever `pack` says
+// and with or without the fold — else 0 and out9[1..8] = the plain site's geometry with packing as `pack` (0 / 1) allows.
+extern "C" int fpc_wino_orient_geometry(int H, int W, int B, int Cin, int fold, int pack, int64_t* out9) {
+    if (!out9 || H < 1 || W < 1 || B < 1 || Cin < 1) return FPC_EINVAL;
+    bool tr;
+    const WinoPackGeom q = wino_launch_geometry(H, W, B, Cin, true, pack && !fold, &tr);
+    out9[0] = tr ? 1 : 0;
+    out9[1] = q.G; out9[2] = q.tbx; out9[3] = q.tby; out9[4] = q.patches; out9[5] = q.slots; out9[6] = q.tiles; out9[7] = q.gn_rows;
+    out9[8] = q.rx;
+    return FPC_OK;
+}
+
 // ---- stand-alone convolution (unit tests / micro-benchmarks of k_conv_igemm) -----------------
 extern "C" size_t fpc_conv2d_workspace_bytes(int B, int Ho, int Wo, int Cin, int Cout, int Kh, int Kw) {
     int K = Cin * Kh * Kw, Kpad = cdiv(K, kConvBK) * kConvBK, Npad = cdiv(Cout, kConvNAlign) * kConvNAlign;
@@ -1615,7 +1677,7 @@ extern "C" int fpc_conv2d_plan(int B, int Ho, int Wo, int Cin, int Cout, int Kh,
     const Conv2dRequest r = decode_plan(nsplit);
     ConvPlan p = plan_conv(Ho * Wo, B, Cout, Kpad / kConvBK, 1, bm, bn, r.nsplit);
     p.wino = r.wino;
-    out4[0] = p.bm; out4[1] = p.bn; out4[2] = r.wino ? nsplit : p.nsplit; out4[3] = plan_gn_rows(p, Ho, Wo, B, Cin, r.pack);
+    out4[0] = p.bm; out4[1] = p.bn; out4[2] = r.wino ? nsplit : p.nsplit; out4[3] = plan_gn_rows(p, Ho, Wo, B, Cin, r.pack, r.orient);
     return FPC_OK;
 }
 
@@ -1670,7 +1732,8 @@ extern "C" int fpc_conv2d(const float* in, int64_t sb, int64_t sh, int64_t sw, i
                : (sc == 1 && Cin % 4 == 0 && sw % 4 == 0 && sh % 4 == 0 && sb % 4 == 0 && ((uintptr_t)in & 15) == 0) ? 2 : 1;
     fpc_net tmp;
     tmp.B = B;
-    tmp.wino_pack = rq.pack ? 1 : 0;      // (-9 itself stays on the plain geometry)
+    tmp.wino_pack = rq.pack ? 1 : 0;      // (-9 itself stays on the plain geometry
+    tmp.wino_orient = rq.orient ? 1 : 0;  // and in the stored orientation)
     tmp.ws = packed;
     tmp.splitk_off = lay.packed;
     ConvArgs a;
@@ -1695,7 +1758,8 @@ extern "C" int fpc_conv2d(const float* in, int64_t sb, int64_t sh, int64_t sw, i
         // (a form reads only its own image: the f32 image is not packed for a split-precision form — 78 launches of a training step)
         if (!wino_form_ok(wino, Cin, Cout)) return FPC_EINVAL;
         const WinoImage img = kWinoForms[wino].image;
-        FPC_TRY(kWinoImages[img].pack(w_oihw, wp + wino_image_offset(img, Cout, Cin), Cout, Cin, s));
+        if (rq.orient && wino_orient_rule(Ho, Wo)) FPC_TRY(launch_wino_pack_h3(w_oihw, wp + wino_image_offset(img, Cout, Cin), Cout, Cin, true, s));
+        else FPC_TRY(kWinoImages[img].pack(w_oihw, wp + wino_image_offset(img, Cout, Cin), Cout, Cin, s));
         a.wino_w[0] = wp;
         a.zeros = zero_page();       // (the workspace's last 64 floats stay reserved for it: fpc_conv2d_workspace_bytes is unchanged)
         if (!a.zeros) {

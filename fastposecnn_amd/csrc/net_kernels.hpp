@@ -54,6 +54,7 @@ struct ConvArgs {
     void* dbg;                        // host side only: diagnostic stamp buffer for k_conv_wino (or null)
     long long wino_blocks;            // host side only, written by a form-9 launch: its workgroups
     int wino_pack;                    // host side only: a form-9 launch may use the packed patch geometry (wino_pack_geometry)
+    int wino_orient;                  // host side only: a form-9 launch runs transposed where wino_orient_rule says so (wino_launch_geometry)
 };
 
 // FPN lateral 1x1 convolutions of all decoders as one pixel-resident product (lateral.hip): K = Cin in {64, 128}
@@ -194,6 +195,10 @@ struct WinoArgs {
     // k_conv_wino_h3 only: > 1 = the patches are cut out of canvas rows of `pack` frames side by side (wino_pack_geometry's G; tbx =
     // its patches per full row), pack_rx = GroupNorm records per frame and patch row.  0 / 1: one frame per patch row, as ever
     int pack, pack_rx;
+    // k_conv_wino_h3 only: 1 = the launch runs transposed (wino_orient_rule): H x W stay the stored image's, the launcher swaps them
+    // for the kernel; tbx / tby / pack / pack_rx are wino_pack_geometry's on the swapped sizes (pack >= 1), the images were packed
+    // from the transposed taps
+    int orient;
 };
 int launch_conv_wino(const WinoArgs& a, int groups, hipStream_t s);
 const float* zero_page();      // 64 zero floats in the code object (per device context), or null
@@ -223,12 +228,17 @@ int launch_conv_wino_h3(const WinoArgs& a, int groups, hipStream_t s);
 // patch row, launched patches per (64-channel block, group), their tile slots, tiles that exist, GroupNorm records per frame
 struct WinoPackGeom { int G, tbx, tby, rx; long long patches, slots, tiles; int gn_rows; };
 WinoPackGeom wino_pack_geometry(int H, int W, int B, int Cin, bool allow);
-int launch_wino_pack_h3(const float* w_oihw, float* packed, int Cout, int Cin, hipStream_t s);
+// the orientation rule (a property of the site's shape alone) and the geometry the launch uses under it: *transposed = the launch
+// runs on the virtual image W x H (the returned geometry is that image's), pack_allow governs the plain sites only
+bool wino_orient_rule(int H, int W);
+WinoPackGeom wino_launch_geometry(int H, int W, int B, int Cin, bool orient, bool pack_allow, bool* transposed);
+int launch_wino_pack_h3(const float* w_oihw, float* packed, int Cout, int Cin, bool transpose, hipStream_t s);
 // the fold's weights: wc = W . L (OIHW [Cout][Cmid -> Cin][3][3], f64 sums) and the bias table conv3x3(W, bias . 1_inside) per border
 // class (WinoArgs::btab); W [Cout][Cmid][3][3], L the 1x1 lateral [Cmid][Cin], bias [Cmid]
-int launch_wino_pack_h3_pair(const float* w1, float* packed1, int Cin1, const float* w2, float* packed2, int Cin2, int Cout, hipStream_t s);
+int launch_wino_pack_h3_pair(const float* w1, float* packed1, int Cin1, const float* w2, float* packed2, int Cin2, int Cout, bool transpose,
+                             hipStream_t s);
 int launch_fold_compose(const float* W, const float* L, const float* bias, float* wc, float* btab, int Cout, int Cmid, int Cin,
-                        hipStream_t s);
+                        bool transpose, hipStream_t s);
 int launch_conv(const ConvArgs& a, int groups, hipStream_t s);
 int launch_conv_splitk_epilogue(const ConvArgs& a, int groups, hipStream_t s);
 int launch_maxpool3x3s2(const float* in, float* out, int B, int Hi, int Wi, int C, int Ho, int Wo, hipStream_t s);

@@ -253,10 +253,11 @@ int launch_absmax_bits(const float* w, long long n, unsigned* out, hipStream_t s
 // lane = (channel half) * 32 + (co & 31), tile = (co & 63) >> 5; the two forms differ only in where a fragment lands:
 //   k_conv_wino_h2  [Cout/64][Cin/8][xi 16][tile 2][lane 64] x {g1 x 4 ch, g2 x 4 ch}
 //   PAIR (k_conv_wino_h3)  [Cout/64][Cin/16][xi 16][tile 2][piece 2][lane 64] x {4 ch of the even K-step, 4 ch of the odd one}
-// tail[0] = 1 / s (f32).  tail[1] holds max |w|'s bits (k_absmax_bits).
+// tail[0] = 1 / s (f32).  tail[1] holds max |w|'s bits (k_absmax_bits).  tr = 1: the taps are read transposed, tap (r, c) from
+// (c, r): the image of a site that runs transposed (wino_h3.hip: wino_orient_rule).
 template <bool PAIR>
 __global__ __launch_bounds__(256) void k_wino_pack_fp16(const float* __restrict__ w, unsigned short* __restrict__ out, float* __restrict__ tail,
-                                                        int Cout, int Cin) {
+                                                        int Cout, int Cin, int tr) {
     const float wmax = __builtin_bit_cast(float, reinterpret_cast<const unsigned*>(tail)[1]);
     int ex = 0;
     if (wmax > 0.f && wmax < 3.0e38f) { (void)frexpf(2.25f * wmax, &ex); ex = 13 - ex; }      // 2.25 wmax = m 2^e, m in [0.5, 1): (2.25 wmax) 2^(13 - e) < 2^13
@@ -268,9 +269,10 @@ __global__ __launch_bounds__(256) void k_wino_pack_fp16(const float* __restrict_
         const int ci = (int)(g % Cin), co = (int)(g / Cin);
         const float* k = w + ((size_t)co * Cin + ci) * 9;
         float gg[4][3];
+        const int sr = tr ? 1 : 3, scol = tr ? 3 : 1;      // strides of a tap row / column in the 3 x 3 block
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const float g0 = k[c] * sc, g1 = k[3 + c] * sc, g2 = k[6 + c] * sc;      // (a power of two: commutes with the transform's roundings)
+            const float g0 = k[c * scol] * sc, g1 = k[sr + c * scol] * sc, g2 = k[2 * sr + c * scol] * sc;      // (a power of two: commutes with the transform's roundings)
             gg[0][c] = g0;
             gg[1][c] = 0.5f * (g0 + g1 + g2);
             gg[2][c] = 0.5f * (g0 - g1 + g2);
@@ -301,7 +303,8 @@ __global__ __launch_bounds__(256) void k_wino_pack_fp16(const float* __restrict_
 }
 
 // fragment-order fp16 x 2 image: 16 * Cout * Cin floats + a tail of 2 (1 / scale, max |w| bits); every byte is written
-int launch_wino_pack_fp16(const float* w_oihw, float* packed, int Cout, int Cin, bool pair, const float* w_also, int Cin_also, hipStream_t s) {
+int launch_wino_pack_fp16(const float* w_oihw, float* packed, int Cout, int Cin, bool pair, const float* w_also, int Cin_also, bool transpose,
+                          hipStream_t s) {
     if (Cin % (pair ? 16 : 8) != 0 || Cout % kBN != 0 || ((uintptr_t)w_oihw & 15) || ((uintptr_t)w_also & 15)) return FPC_EINVAL;
     float* tail = packed + (size_t)16 * Cout * Cin;
     if (hipMemsetAsync(tail, 0, 2 * sizeof(float), s) != hipSuccess) return FPC_ELAUNCH;
@@ -309,13 +312,13 @@ int launch_wino_pack_fp16(const float* w_oihw, float* packed, int Cout, int Cin,
     if (!rc && w_also) rc = launch_absmax_bits(w_also, (long long)Cout * Cin_also * 9, reinterpret_cast<unsigned*>(tail) + 1, s);
     if (rc) return rc;
     const dim3 grid((unsigned)std::min<long long>(((long long)Cout * Cin + 255) / 256, 4096));
-    if (pair) hipLaunchKernelGGL(k_wino_pack_fp16<true>, grid, dim3(256), 0, s, w_oihw, reinterpret_cast<unsigned short*>(packed), tail, Cout, Cin);
-    else hipLaunchKernelGGL(k_wino_pack_fp16<false>, grid, dim3(256), 0, s, w_oihw, reinterpret_cast<unsigned short*>(packed), tail, Cout, Cin);
+    if (pair) hipLaunchKernelGGL(k_wino_pack_fp16<true>, grid, dim3(256), 0, s, w_oihw, reinterpret_cast<unsigned short*>(packed), tail, Cout, Cin, transpose ? 1 : 0);
+    else hipLaunchKernelGGL(k_wino_pack_fp16<false>, grid, dim3(256), 0, s, w_oihw, reinterpret_cast<unsigned short*>(packed), tail, Cout, Cin, transpose ? 1 : 0);
     return check_launch();
 }
 
 int launch_wino_pack_h2(const float* w_oihw, float* packed, int Cout, int Cin, hipStream_t s) {
-    return launch_wino_pack_fp16(w_oihw, packed, Cout, Cin, false, nullptr, 0, s);
+    return launch_wino_pack_fp16(w_oihw, packed, Cout, Cin, false, nullptr, 0, false, s);
 }
 
 // .w = the k_wino_pack_fp16<false> image (+ its tail), .waves = 8 (tby = ceil(ceil(H / 2) / 8): 8 x 8 tile patches)

@@ -64,7 +64,11 @@ __device__ __forceinline__ const float* sgpr_ptr(const float* p) {
 //
 // PACK: the patches are cut out of a canvas of a.pack frames side by side and a patch may carry a SEAM (wino_tile.hpp: wino_patch,
 // wino_stage_plan).  Only the set-up and the epilogue know about it; the K loop is the plain one.
-template <int VAR, bool FOLD, bool PACK>
+//
+// TR: the launch runs TRANSPOSED (wino_orient_rule): a.H x a.W is the virtual image H' = W, W' = H whose pixel (y, x) is the stored
+// pixel (x, y), the weight image was packed from the transposed taps.  The staging plan's byte offsets and the epilogue's output and
+// residual offsets know; nothing else does.  Always with PACK (a single frame per canvas row is pack = 1).
+template <int VAR, bool FOLD, bool PACK, bool TR = false>
 __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[kLdsFloats];
     const long long t_entry = a.dbg ? clock64() : 0;
@@ -114,7 +118,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
     const float* isb = sgpr_ptr(src + (size_t)pt.b * (H >> up) * (W >> up) * Cs);      // image base, + 8 floats per step
     unsigned ivo[5];
     unsigned long long imask[5];
-    wino_stage_plan<PACK>(ivo, imask, wi, lane, y_in0, x_in0, H, W, Cs, up, pk_ks, pt.pk_two);
+    wino_stage_plan<PACK, TR>(ivo, imask, wi, lane, y_in0, x_in0, H, W, Cs, up, pk_ks, pt.pk_two);
 #define FPC_H3_ISSUE_IN(BUF, PTR) wino_issue_in(lds + (BUF) * kInFloats, wi, ivo, imask, PTR)
     int in_a[2], in_b[2];
     const float sgn = wino_frag<PACK>(in_a, in_b, wi, li, lh, pk_ks);
@@ -310,12 +314,13 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
     // (no staging is in flight here: a step past the last is never issued, every real step was waited for at the end of its pair; the
     // last pair's redundant weight reloads target registers, whose reuse the compiler guards itself)
     const long long t_kend = a.dbg ? clock64() : 0;
-    if (a.dbg && lane == 0) {      // tools_dev/wino_stamps.py: shader-clock ticks and 100 MHz reference ticks of the K loop, entry -> loop
+    // (the packed fold never stamps — its launcher refuses a.dbg — and would carry `lane` across both loops in scratch for this test)
+    if (!(FOLD && PACK) && a.dbg && lane == 0) {      // tools_dev/wino_stamps.py: shader-clock ticks and 100 MHz reference ticks of the K loop, entry -> loop
         long long* o = a.dbg + ((size_t)blockIdx.x * 4 + wi) * 8;
         o[0] = t_issued - t_entry; o[1] = t_landed - t_issued; o[2] = t_synced - t_landed;      // entry: set-up + issue | first operands land | barrier
         o[3] = t_kend - c_begin; o[4] = wall_clock64() - r_begin; o[5] = a.Cin >> 3; o[6] = c_begin - t_entry;
     }
-    wino_output<PACK, FOLD>(lds, acc, P, pt, WinoEpi{H, W, Cout, a.relu, a.tbx, a.tby, a.pack_rx}, inv_s,
+    wino_output<PACK, FOLD, TR>(lds, acc, P, pt, WinoEpi{H, W, Cout, a.relu, a.tbx, a.tby, a.pack_rx}, inv_s,
                             wino_group(a.btab[0], a.btab[1], a.btab[2], a.btab[3], grp), a.dbg, t_kend, t, wi);
 }
 
@@ -344,10 +349,53 @@ WinoPackGeom wino_pack_geometry(int H, int W, int B, int Cin, bool allow) {
     return q;
 }
 
+// what the fold's launch needs on top of wino_tile_check (wino_output<PACK, true> RELIES on these refusals)
+static int wino_fold_check(const WinoArgs& a, int groups) {
+    if (a.Cin2 % 16 != 0 || (a.H | a.W) & 1 || (long long)(a.H / 2) * (a.W / 2) * a.Cin2 * (long long)sizeof(float) >= (1LL << 32) ||
+        (long long)(a.Cin2 >> 4) * kPairBytes >= (1LL << 31) || a.relu || a.dbg)
+        return FPC_EINVAL;
+    for (int g = 0; g < groups; ++g)
+        if (!a.in2[g] || !a.w2[g] || !a.btab[g] || a.p[g].scale || a.p[g].shift || a.p[g].res || a.p[g].up) return FPC_EINVAL;
+    return 0;
+}
+
+// The ORIENTATION RULE of a form-9 site, a property of its output shape alone (so a site keeps one weight image): run TRANSPOSED —
+// the patch's x axis walks the image's y — iff the tile columns fill whole patches and the tile rows do not, and there are at least
+// 8 tile rows (below that nothing can pack along them, and the GroupNorm records of a transposed launch would no longer fit the
+// reservation of cdiv(H W, 128) * 4 per frame).  Frames then pack along the image's y (wino_pack_geometry on the swapped sizes).
+bool wino_orient_rule(int H, int W) {
+    const int tcw = cdiv(W, 2), tch = cdiv(H, 2);
+    return tcw % kTX == 0 && tch % kTY != 0 && tch >= kTY;
+}
+
+// The geometry a form-9 launch of an H x W site uses: transposed where `orient` and the rule say so (then on the virtual image
+// W x H, packing whatever `pack_allow` says: fpc_net_set_wino_pack governs the plain sites only), else wino_pack_geometry's.
+// FPC_H3_ORIENT_G1 (diagnostic): a transposed launch keeps one frame per canvas row — the plain launch's patch count.
+WinoPackGeom wino_launch_geometry(int H, int W, int B, int Cin, bool orient, bool pack_allow, bool* transposed) {
+    static const bool g1 = getenv("FPC_H3_ORIENT_G1") && atoi(getenv("FPC_H3_ORIENT_G1")) != 0;
+    *transposed = orient && wino_orient_rule(H, W);
+    return *transposed ? wino_pack_geometry(W, H, B, Cin, !g1) : wino_pack_geometry(H, W, B, Cin, pack_allow);
+}
+
 // .w = the k_wino_pack_fp16<true> image (+ its tail; wino_h2.hip), tby = ceil(ceil(H / 2) / 8): 8 x 8 tile patches
 int launch_conv_wino_h3(const WinoArgs& a, int groups, hipStream_t s) {
     // pairs of 8-channel K-steps; a.pack > 1: patches cut out of canvas rows of a.pack frames, the geometry must be wino_pack_geometry's own
     long long nblk;
+    if (a.orient) {
+        // a.H x a.W is the stored image; the kernel gets the virtual one.  Always the packed decode (a.pack >= 1), images packed from
+        // the transposed taps (launch_wino_pack_h3 / _pair, launch_fold_compose with transpose = true)
+        WinoArgs t = a;
+        std::swap(t.H, t.W);
+        if (a.pack < 1 || a.dbg) return FPC_EINVAL;
+        if (const int rc = wino_tile_check(t, groups, 16, kPairBytes, true, &nblk)) return rc;
+        if (a.fold) {
+            if (const int rc = wino_fold_check(a, groups)) return rc;
+            hipLaunchKernelGGL((k_conv_wino_h3<0, true, true, true>), dim3((unsigned)nblk), dim3(256), 0, s, t);
+        } else {
+            hipLaunchKernelGGL((k_conv_wino_h3<0, false, true, true>), dim3((unsigned)nblk), dim3(256), 0, s, t);
+        }
+        return check_launch();
+    }
     if (const int rc = wino_tile_check(a, groups, 16, kPairBytes, a.pack > 1, &nblk)) return rc;
     if (a.pack > 1) {
         hipLaunchKernelGGL((k_conv_wino_h3<0, false, true>), dim3((unsigned)nblk), dim3(256), 0, s, a);
@@ -356,11 +404,7 @@ int launch_conv_wino_h3(const WinoArgs& a, int groups, hipStream_t s) {
     // c2 + up2(p3): both phases pairs of K-steps, p2 exactly 2 x p3, the bias table and nothing else in the epilogue.  wino_output<PACK, true>
     // (wino_tile.hpp) RELIES on the refusals below: it compiles scale, shift, residual and ReLU out
     if (a.fold) {
-        if (a.Cin2 % 16 != 0 || (a.H | a.W) & 1 || (long long)(a.H / 2) * (a.W / 2) * a.Cin2 * (long long)sizeof(float) >= (1LL << 32) ||
-            (long long)(a.Cin2 >> 4) * kPairBytes >= (1LL << 31) || a.relu || a.dbg)
-            return FPC_EINVAL;
-        for (int g = 0; g < groups; ++g)
-            if (!a.in2[g] || !a.w2[g] || !a.btab[g] || a.p[g].scale || a.p[g].shift || a.p[g].res || a.p[g].up) return FPC_EINVAL;
+        if (const int rc = wino_fold_check(a, groups)) return rc;
         hipLaunchKernelGGL((k_conv_wino_h3<0, true, false>), dim3((unsigned)nblk), dim3(256), 0, s, a);
         return check_launch();
     }
@@ -372,9 +416,10 @@ int launch_conv_wino_h3(const WinoArgs& a, int groups, hipStream_t s) {
 
 // wc[o][k][tap] = sum_c W[o][c][tap] L[c][k]; btab[(rc * 4 + cc) * Cout + o] = sum over the taps a pixel of row class rc / column class
 // cc sees inside the image (bit 0: first row / column: no tap above / left; bit 1: last: none below / right) of sum_c W[o][c][tap] b[c].
-// f64 sums, rounded once.
+// f64 sums, rounded once.  tr = 1: the table of the TRANSPOSED taps (a transposed launch's classes are the virtual image's: its row
+// class is the stored image's column class); wc stays in W's own tap order (the packer transposes).
 __global__ __launch_bounds__(256) void k_fold_compose(const float* __restrict__ w, const float* __restrict__ l, const float* __restrict__ bias,
-                                                      float* __restrict__ wc, float* __restrict__ btab, int Cout, int Cmid, int Cin) {
+                                                      float* __restrict__ wc, float* __restrict__ btab, int Cout, int Cmid, int Cin, int tr) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     const int nw = Cout * Cin * 9;
     if (g < nw) {
@@ -387,30 +432,32 @@ __global__ __launch_bounds__(256) void k_fold_compose(const float* __restrict__ 
         double acc = 0.0;
         for (int ky = (rc & 1); ky < 3 - ((rc >> 1) & 1); ++ky)
             for (int kx = (cc & 1); kx < 3 - ((cc >> 1) & 1); ++kx)
-                for (int c = 0; c < Cmid; ++c) acc += (double)w[((size_t)o * Cmid + c) * 9 + ky * 3 + kx] * (double)bias[c];
+                for (int c = 0; c < Cmid; ++c) acc += (double)w[((size_t)o * Cmid + c) * 9 + (tr ? kx * 3 + ky : ky * 3 + kx)] * (double)bias[c];
         btab[(size_t)cls * Cout + o] = (float)acc;
     }
 }
 
 int launch_fold_compose(const float* W, const float* L, const float* bias, float* wc, float* btab, int Cout, int Cmid, int Cin,
-                        hipStream_t s) {
+                        bool transpose, hipStream_t s) {
     if (!W || !L || !bias || !wc || !btab || Cout < 1 || Cmid < 1 || Cin < 1) return FPC_EINVAL;
     const long long work = (long long)Cout * Cin * 9 + 16LL * Cout;
-    hipLaunchKernelGGL(k_fold_compose, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, s, W, L, bias, wc, btab, Cout, Cmid, Cin);
+    hipLaunchKernelGGL(k_fold_compose, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, s, W, L, bias, wc, btab, Cout, Cmid, Cin, transpose ? 1 : 0);
     return check_launch();
 }
 
 // the fold's two images (Wc: Cin1 channels, W: Cin2) scaled by ONE power of two, from the larger max |w| of the two.  (The packer
 // kernel and launch_wino_pack_fp16 live in wino_h2.hip and are built with that file's flags.)
-int launch_wino_pack_h3_pair(const float* w1, float* packed1, int Cin1, const float* w2, float* packed2, int Cin2, int Cout, hipStream_t s) {
+int launch_wino_pack_h3_pair(const float* w1, float* packed1, int Cin1, const float* w2, float* packed2, int Cin2, int Cout, bool transpose,
+                             hipStream_t s) {
     if (Cin2 % 16 != 0 || ((uintptr_t)w2 & 15)) return FPC_EINVAL;      // (before the first image is touched)
-    const int rc = launch_wino_pack_fp16(w1, packed1, Cout, Cin1, true, w2, Cin2, s);
-    return rc ? rc : launch_wino_pack_fp16(w2, packed2, Cout, Cin2, true, w1, Cin1, s);
+    const int rc = launch_wino_pack_fp16(w1, packed1, Cout, Cin1, true, w2, Cin2, transpose, s);
+    return rc ? rc : launch_wino_pack_fp16(w2, packed2, Cout, Cin2, true, w1, Cin1, transpose, s);
 }
 
-// pair-order fp16 x 2 image: 16 * Cout * Cin floats + a tail of 2 (1 / scale, max |w| bits); every byte is written
-int launch_wino_pack_h3(const float* w_oihw, float* packed, int Cout, int Cin, hipStream_t s) {
-    return launch_wino_pack_fp16(w_oihw, packed, Cout, Cin, true, nullptr, 0, s);
+// pair-order fp16 x 2 image: 16 * Cout * Cin floats + a tail of 2 (1 / scale, max |w| bits); every byte is written.  transpose: of
+// the transposed taps, for a site that runs transposed (wino_orient_rule)
+int launch_wino_pack_h3(const float* w_oihw, float* packed, int Cout, int Cin, bool transpose, hipStream_t s) {
+    return launch_wino_pack_fp16(w_oihw, packed, Cout, Cin, true, nullptr, 0, transpose, s);
 }
 
 }  // namespace fpc

@@ -100,7 +100,9 @@ __device__ __forceinline__ T wino_group(const T v0, const T v1, const T v2, cons
 // up = 1: the source is read as its nearest-x2 upsample (wino_h3.hip's fold, phase 2: a lane's address is its low-resolution pixel).
 // PACK: the staged region of a seam patch holds ONE gap column, tile column k reads region columns k + (k >= ks) + ch: region column
 // ks holds frame f's last pixel (and the zero of x = W), column ks + 1 the zero of x = -1 and frame f + 1's first pixel.
-template <bool PACK>
+// TR: H x W is the VIRTUAL image of a transposed launch (wino_orient_rule): its pixel (y, x) is the stored image's pixel (x, y), whose
+// rows are H pixels long.  Only the lane's byte offset knows; a frame is as large either way.
+template <bool PACK, bool TR = false>
 __device__ __forceinline__ void wino_stage_plan(unsigned (&ivo)[5], unsigned long long (&imask)[5], int wi, int lane, int y_in0, int x_in0, int H,
                                                 int W, int Cs, int up, int pk_ks, bool pk_two) {
     const int Hs = H >> up, Ws = W >> up;                      // the source image's own size
@@ -115,7 +117,8 @@ __device__ __forceinline__ void wino_stage_plan(unsigned (&ivo)[5], unsigned lon
         const int y = y_in0 + ry, x = far ? rx - 2 * pk_ks - 3 : x_in0 + rx;
         const int qmax = (PACK && pk_ks < kTX) ? kTX + 1 : kTX;
         const bool iok = wi + 4 * i < kInPieces && ah <= kTY && qh <= qmax && y >= 0 && y < H && x >= 0 && x < W && (!far || pk_two);
-        ivo[i] = iok ? (unsigned)((((size_t)(y >> up) * Ws + (x >> up)) * Cs + 4 * hf) * sizeof(float)) +
+        const size_t px = TR ? (size_t)(x >> up) * Hs + (y >> up) : (size_t)(y >> up) * Ws + (x >> up);
+        ivo[i] = iok ? (unsigned)((px * Cs + 4 * hf) * sizeof(float)) +
                               (far ? (unsigned)((size_t)Hs * Ws * Cs * sizeof(float)) : 0u)
                         : 0u;
         imask[i] = __ballot(iok);
@@ -186,8 +189,10 @@ __device__ __forceinline__ void wino_zero_ring(float* lds, int t, int nbuf, int 
 // inv_s = 1 / (the power of two the weights were scaled by): exact; 1.0f for an unscaled image.  btab (FOLD): conv3x3(W, b 1_inside)
 // by the output pixel's border class, [16][Cout].  (The pointers and the float are arguments of their own: in a struct beside the
 // ints, the fold kernel kept the struct in memory.)
+// TR: y, x, H, W below are the virtual image's (wino_stage_plan); the output and the residual are stored images: pixel (x, y), rows
+// of H pixels.  (The fold's border classes are the virtual image's too: k_fold_compose wrote the table for the transposed taps.)
 struct WinoEpi { int H, W, Cout, relu, tbx, tby, pack_rx; };
-template <bool PACK, bool FOLD>
+template <bool PACK, bool FOLD, bool TR = false>
 __device__ __forceinline__ void wino_output(float* lds, const f32x16 (&acc)[4][2][2], const ConvPtrs P, const WinoPatch pt, const WinoEpi e,
                                             const float inv_s, const float* btab, long long* dbg, const long long t_kend, const int t,
                                             const int wi) {
@@ -213,7 +218,7 @@ __device__ __forceinline__ void wino_output(float* lds, const f32x16 (&acc)[4][2
         for (int q = 0; q < 4; ++q) {
             const int ot = otl + 16 * tp;
             const int y = 2 * (pt.ty0 + (ot >> 3)) + (q >> 1), x = 2 * otx + (q & 1);
-            e_res[tp][q] = (!FOLD && P.res && o_ok && y < H && x < W) ? *reinterpret_cast<const f32x4*>(P.res + ((size_t)ob * HW + (size_t)y * W + x) * Cout + n)
+            e_res[tp][q] = (!FOLD && P.res && o_ok && y < H && x < W) ? *reinterpret_cast<const f32x4*>(P.res + ((size_t)ob * HW + (TR ? (size_t)x * H + y : (size_t)y * W + x)) * Cout + n)
                                                              : f32x4{0.f, 0.f, 0.f, 0.f};
         }
     __syncthreads();
@@ -254,7 +259,7 @@ __device__ __forceinline__ void wino_output(float* lds, const f32x16 (&acc)[4][2
                 }
                 if (!FOLD && P.scale) val = val * e_sc;
                 val = val + e_sh;
-                const size_t o = ((size_t)ob * HW + (size_t)y * W + x) * Cout + n;
+                const size_t o = ((size_t)ob * HW + (TR ? (size_t)x * H + y : (size_t)y * W + x)) * Cout + n;
                 if (!FOLD && P.res) val += e_res[tp][2 * rr + cc];
                 if (!FOLD && e.relu) { val[0] = fmaxf(val[0], 0.f); val[1] = fmaxf(val[1], 0.f); val[2] = fmaxf(val[2], 0.f); val[3] = fmaxf(val[3], 0.f); }
                 *reinterpret_cast<f32x4*>(P.out + o) = val;
@@ -330,13 +335,14 @@ __device__ __forceinline__ void wino_output(float* lds, const f32x16 (&acc)[4][2
 // ---- host side.  What every launcher of the family checks: groups, Cin a multiple of kch (the form's channels per K-step or pair),
 // Cout of 64, 32-bit lane offsets inside one image, 31-bit buffer offsets inside one block's weight images (step_bytes per kch
 // channels), the patch grid (packed: wino_pack_geometry's own; otherwise one frame per patch row) and the workgroup
-// count, returned in *nblk.
+// count, returned in *nblk.  (A transposed launch, a.orient: a.H x a.W is the virtual image; it packs
+// with or without the fold, and a.pack = 1 is one frame per canvas row.)
 inline int wino_tile_check(const WinoArgs& a, int groups, int kch, int step_bytes, bool packed, long long* nblk) {
     if (groups < 1 || groups > kMaxGroup || a.Cin % kch != 0 || a.Cout % kBN != 0) return FPC_EINVAL;
     if ((long long)a.H * a.W * a.Cin * (long long)sizeof(float) >= (1LL << 32)) return FPC_EINVAL;
     if ((long long)(a.Cin / kch) * step_bytes >= (1LL << 31)) return FPC_EINVAL;
     if (packed) {
-        const WinoPackGeom q = wino_pack_geometry(a.H, a.W, a.B, a.Cin, !a.fold);
+        const WinoPackGeom q = wino_pack_geometry(a.H, a.W, a.B, a.Cin, a.orient ? a.pack > 1 : !a.fold);
         if (q.G != a.pack || q.tbx != a.tbx || q.tby != a.tby || q.rx != a.pack_rx) return FPC_EINVAL;
         *nblk = q.patches * (a.Cout / kBN) * groups;
     } else {
@@ -348,7 +354,8 @@ inline int wino_tile_check(const WinoArgs& a, int groups, int kch, int step_byte
 }  // namespace wino_tile
 
 // wino_h2.hip: clears the image's two-float tail, finds max |w| (of w and, if given, of w_also too: images that share one scale),
-// packs.  pair = wino_h3.hip's fragment order.
-int launch_wino_pack_fp16(const float* w_oihw, float* packed, int Cout, int Cin, bool pair, const float* w_also, int Cin_also, hipStream_t s);
+// packs.  pair = wino_h3.hip's fragment order; transpose = the image of the transposed taps (tap (r, c) read as (c, r)).
+int launch_wino_pack_fp16(const float* w_oihw, float* packed, int Cout, int Cin, bool pair, const float* w_also, int Cin_also, bool transpose,
+                          hipStream_t s);
 
 }  // namespace fpc

@@ -181,6 +181,12 @@ class NetEngine:
         (on = 1, the library's default) or keep one frame per patch row (on = 0).  The plans do not change."""
         nat.check(self._lib.fpc_net_set_wino_pack(self._h, int(on)), "fpc_net_set_wino_pack")
 
+    def set_wino_orient(self, on):
+        """Form-9 Winograd launches run transposed at the sites whose shape asks for it (on = 1, the library's default: tile columns a
+        multiple of 8, tile rows not) or all in the stored orientation (on = 0).  Repacks those sites' weight images; the plans and
+        the workspace do not change."""
+        nat.check(self._lib.fpc_net_set_wino_orient(self._h, int(on)), "fpc_net_set_wino_orient")
+
     def wino_blocks(self):
         """Workgroups of all form-9 launches of the last forward that launched its kernels."""
         return int(self._lib.fpc_net_wino_blocks(self._h))

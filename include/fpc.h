@@ -504,6 +504,15 @@ int fpc_wino_pack_geometry(int H, int W, int B, int Cin, int fold, int64_t* out8
 /* on = 1 (default): form-9 launches of the plan use that geometry where it needs fewer patches; on = 0: one frame per patch row.
  * The plans and fpc_net_conv_plan's reports do not change.  Drops the recorded graph. */
 int fpc_net_set_wino_pack(fpc_net_t* net, int on);
+/* The ORIENTATION of a form-9 site: a site whose output has ceil(W / 2) a multiple of 8 and ceil(H / 2) not (and >= 8) runs
+ * TRANSPOSED: the patch's x axis walks the image's y, the frames pack along y, the weight image is packed from the transposed taps.
+ * The rule depends on the shape alone.  on = 1 (default) / 0: every site in the stored orientation.  The switch repacks the affected
+ * sites' images in place from the parameters and drops the recorded graph; plans, reports and the workspace do not change, and
+ * fpc_net_set_wino_pack keeps governing the other sites only.  Results of a transposed site differ from the plain one's by rounding. */
+int fpc_net_set_wino_orient(fpc_net_t* net, int on);
+/* fpc_wino_pack_geometry under that rule (host only): out9[0] = 1 where the site runs transposed, then out9[1..8] = the out8 above of
+ * the virtual image W x H (packed with or without the fold, whatever `pack`); else 0 and the plain site's out8 with packing as `pack`. */
+int fpc_wino_orient_geometry(int H, int W, int B, int Cin, int fold, int pack, int64_t* out9);
 /* Workgroups of all form-9 launches of the last forward that launched (or captured) its kernels: what the switch above changes. */
 int64_t fpc_net_wino_blocks(const fpc_net_t* net);
 /* FLOP of one forward over the batch under the current plans: out3 = {2 x MACs of the direct convolutions (what the
@@ -519,7 +528,8 @@ int fpc_net_tensor(const fpc_net_t* net, const char* name, const float** ptr, in
  * optional per-channel scale / shift, residual (as out), nearest-x2 `up` [B,Ho/2,Wo/2,Cout], ReLU,
  * GroupNorm partials gn_part [B][P32][Cout][2]; bm/bn/nsplit = 0 -> chosen by the planner.
  * `nsplit` also selects the engine's other kernels for tests: -1..-9 Winograd forms (-5 split precision; -10: form -9 with its
- * patches cut out of canvas rows of several frames, fpc_wino_pack_geometry, P32 = its records per frame), 100 + k split-K
+ * patches cut out of canvas rows of several frames, fpc_wino_pack_geometry, P32 = its records per frame; -11: form -9 in the
+ * orientation fpc_wino_orient_geometry gives the shape, P32 = that geometry's records; a shape the rule leaves alone: -9), 100 + k split-K
  * summed by a second launch, 1000 + k split-precision (bf16 x 3) products, 2000 + parts the pixel-resident FPN lateral
  * product (1x1, Cin 64 / 128, bias + `up` epilogue), 3000 the weight-resident 7x7 / s2 stem (Cin = 4: NHWC4 image),
  * 3100 the same stem fused with its 3x3 / 2 / pad-1 max-pool on three fp16 piece products (`out` is then the POOLED tensor
@@ -529,7 +539,7 @@ int fpc_net_tensor(const fpc_net_t* net, const char* name, const float** ptr, in
  * implicit GEMM with split-K factor k on two fp16 pieces per operand and three piece products (channel stride 1, Cin a multiple
  * of 32; 6100 + k: split-K summed by a second launch), 7000 + parts the pixel-resident FPN lateral product on the same two pieces.  5000 is never a request: fpc_net_conv_plan's "folded away". */
 enum {      /* the bases of those codes, as fpc_net_conv_plan reports them and fpc_conv2d takes them (a Winograd form: -form) */
-    FPC_PLAN_WINO_PACKED = -10, FPC_PLAN_TWO_LAUNCH = 100, FPC_PLAN_BF3 = 1000, FPC_PLAN_LATERAL = 2000, FPC_PLAN_STEM = 3000,
+    FPC_PLAN_WINO_ORIENT = -11, FPC_PLAN_WINO_PACKED = -10, FPC_PLAN_TWO_LAUNCH = 100, FPC_PLAN_BF3 = 1000, FPC_PLAN_LATERAL = 2000, FPC_PLAN_STEM = 3000,
     FPC_PLAN_STEM_POOL = 3100, FPC_PLAN_POINTWISE = 4000, FPC_PLAN_FOLDED = 5000, FPC_PLAN_H3 = 6000, FPC_PLAN_LATERAL_H3 = 7000
 };
 size_t fpc_conv2d_workspace_bytes(int B, int Ho, int Wo, int Cin, int Cout, int Kh, int Kw);
