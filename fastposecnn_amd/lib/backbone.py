@@ -56,26 +56,54 @@ class UpsamplingBilinear2d(nn.UpsamplingBilinear2d):
         return super().forward(x)
 
 
+class BatchNorm2d(nn.BatchNorm2d):
+    """nn.BatchNorm2d whose TRAINING-mode forward on a channel-last GPU tensor under autograd runs on the native kernels, forward
+    and backward (csrc/batchnorm.hip, lib/train_conv.batchnorm_act); everything else — evaluation mode, CPU tensors, a no_grad
+    forward, whatever the front end refuses — is nn.BatchNorm2d's own forward.  Same parameters, buffers and state_dict names;
+    the engine folds it at plan build like any nn.BatchNorm2d."""
+
+    def forward(self, x):
+        if x.is_cuda and torch.is_grad_enabled():
+            from fastposecnn_amd.lib import train_conv
+            y = train_conv.batchnorm_act(x, self, relu=False)
+            if y is not None:
+                return y
+        return super().forward(x)
+
+
+def _bn_act(x, bn, act, res=None):
+    """act(bn(x) + res) at a block's BatchNorm.  In the training step BatchNorm, the add and the ReLU are one native op; the
+    ReLU (and with it the add) is fused only while `act` is an nn.ReLU — a test may have swapped it for a smooth activation,
+    and then the BatchNorm runs native and plain (its own forward), the add and the activation stay torch."""
+    if isinstance(act, nn.ReLU) and isinstance(bn, BatchNorm2d) and bn.training and x.is_cuda and torch.is_grad_enabled():
+        from fastposecnn_amd.lib import train_conv
+        y = train_conv.batchnorm_act(x, bn, res, relu=True, count_refusal=False)      # (refused: bn(x) below asks again, plain)
+        if y is not None:
+            return y
+    y = bn(x)
+    if res is not None:
+        y = y + res
+    return act(y)
+
+
 class BasicBlock(nn.Module):
     expansion = 1
 
     def __init__(self, inplanes, planes, stride=1, downsample=None):
         super().__init__()
         self.conv1 = Conv2d(inplanes, planes, 3, stride, 1, bias=False)
-        self.bn1 = nn.BatchNorm2d(planes)
+        self.bn1 = BatchNorm2d(planes)
         self.relu = nn.ReLU(inplace=True)
         self.conv2 = Conv2d(planes, planes, 3, 1, 1, bias=False)
-        self.bn2 = nn.BatchNorm2d(planes)
+        self.bn2 = BatchNorm2d(planes)
         self.downsample = downsample
         self.stride = stride
 
     def forward(self, x):
-        identity = x
-        out = self.relu(self.bn1(self.conv1(x)))
-        out = self.bn2(self.conv2(out))
-        if self.downsample is not None:
-            identity = self.downsample(x)
-        return self.relu(out + identity)
+        out = _bn_act(self.conv1(x), self.bn1, self.relu)
+        out = self.conv2(out)
+        identity = x if self.downsample is None else self.downsample(x)
+        return _bn_act(out, self.bn2, self.relu, identity)
 
 
 class Bottleneck(nn.Module):
@@ -85,23 +113,21 @@ class Bottleneck(nn.Module):
     def __init__(self, inplanes, planes, stride=1, downsample=None):
         super().__init__()
         self.conv1 = Conv2d(inplanes, planes, 1, bias=False)
-        self.bn1 = nn.BatchNorm2d(planes)
+        self.bn1 = BatchNorm2d(planes)
         self.conv2 = Conv2d(planes, planes, 3, stride, 1, bias=False)
-        self.bn2 = nn.BatchNorm2d(planes)
+        self.bn2 = BatchNorm2d(planes)
         self.conv3 = Conv2d(planes, planes * self.expansion, 1, bias=False)
-        self.bn3 = nn.BatchNorm2d(planes * self.expansion)
+        self.bn3 = BatchNorm2d(planes * self.expansion)
         self.relu = nn.ReLU(inplace=True)
         self.downsample = downsample
         self.stride = stride
 
     def forward(self, x):
-        identity = x
-        out = self.relu(self.bn1(self.conv1(x)))
-        out = self.relu(self.bn2(self.conv2(out)))
-        out = self.bn3(self.conv3(out))
-        if self.downsample is not None:
-            identity = self.downsample(x)
-        return self.relu(out + identity)
+        out = _bn_act(self.conv1(x), self.bn1, self.relu)
+        out = _bn_act(self.conv2(out), self.bn2, self.relu)
+        out = self.conv3(out)
+        identity = x if self.downsample is None else self.downsample(x)
+        return _bn_act(out, self.bn3, self.relu, identity)
 
 
 # name -> (block, blocks per stage), as torchvision / smp
@@ -131,7 +157,7 @@ class ResNetEncoder(nn.Module):
         self.out_channels = (in_channels, 64, 64 * e, 128 * e, 256 * e, 512 * e)
         self.inplanes = 64
         self.conv1 = Conv2d(in_channels, 64, 7, 2, 3, bias=False)
-        self.bn1 = nn.BatchNorm2d(64)
+        self.bn1 = BatchNorm2d(64)
         self.relu = nn.ReLU(inplace=True)
         self.maxpool = nn.MaxPool2d(3, 2, 1)
         self.layer1 = self._make_layer(64, layers[0])
@@ -150,7 +176,7 @@ class ResNetEncoder(nn.Module):
         downsample = None
         if stride != 1 or self.inplanes != planes * block.expansion:
             downsample = nn.Sequential(Conv2d(self.inplanes, planes * block.expansion, 1, stride, bias=False),
-                                       nn.BatchNorm2d(planes * block.expansion))
+                                       BatchNorm2d(planes * block.expansion))
         layers = [block(self.inplanes, planes, stride, downsample)]
         self.inplanes = planes * block.expansion
         for _ in range(1, blocks):
@@ -159,7 +185,7 @@ class ResNetEncoder(nn.Module):
 
     def forward(self, x):
         feats = [x]
-        x = self.relu(self.bn1(self.conv1(x)))
+        x = _bn_act(self.conv1(x), self.bn1, self.relu)
         feats.append(x)
         x = self.layer1(self.maxpool(x))
         feats.append(x)

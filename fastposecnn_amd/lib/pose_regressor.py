@@ -275,7 +275,9 @@ class PoseRegressor(Model, torch.nn.Module):
         """Something rewrote parameters or buffers without PyTorch's version counters seeing it (BatchNorm's running
         statistics in a training-mode forward, a kernel writing through raw pointers): every native plan bound to these
         tensors - this module's and its FrameStreamer copies', which share the counter - repacks at its next forward
-        (bind() keeps the tuned tilings and the workspace: no re-tune)."""
+        (bind() keeps the tuned tilings and the workspace: no re-tune).  The encoder's native BatchNorm (csrc/batchnorm.hip) is
+        such a kernel: it writes running_mean / running_var through their data pointers, inside the training-mode forward that
+        calls this first."""
         self._weights_gen[0] += 1
 
     def _apply(self, fn, *args, **kwargs):

@@ -351,3 +351,78 @@ def groupnorm_relu(x, gn):
             and x.shape[0] <= 65535 and x.stride(1) == 1 and x.is_contiguous(memory_format=torch.channels_last)):
         return _GroupNormReLUFn.apply(x, gn.weight, gn.bias, G, gn.eps)
     return torch.relu(gn(x))
+
+
+# ---- training-mode BatchNorm2d (+ residual add) (+ ReLU) on channel-last activations (the encoder's blocks) -----------------
+
+# Off by default: on the batch-8 step the native path has fewer launches and less kernel time, but the step time did not move by
+# more than the spread between repeated runs (profiles/train_bn_step_kernels.txt).
+NATIVE_BN = bool(int(os.environ.get("FPC_TRAIN_NATIVE_BN", "0")))
+counters.update(bn_native=0, bn_torch=0)
+
+
+def _dense_nhwc(t):
+    return t.stride(1) == 1 and t.is_contiguous(memory_format=torch.channels_last) and t.data_ptr() % 16 == 0
+
+
+class _BatchNormActFn(torch.autograd.Function):
+    """y = bn(x) over the batch statistics, + res, relu (csrc/batchnorm.hip).  running_mean / running_var are rewritten through
+    their raw pointers: their version counters do not move (PoseRegressor.note_unversioned_write)."""
+
+    @staticmethod
+    def forward(ctx, x, res, gamma, beta, running_mean, running_var, eps, momentum, relu):
+        B, C, H, W = x.shape
+        P = B * H * W
+        L = nat.lib()
+        y = torch.empty_like(x, memory_format=torch.channels_last)
+        stats = torch.empty((C, 2), dtype=torch.float32, device=x.device)
+        part = nat.workspace("train_bn", x.device, 4 * L.fpc_batchnorm_scratch_floats(P, C))
+        nat.check(L.fpc_batchnorm_fwd(x.data_ptr(), nat.ptr(res), gamma.data_ptr(), beta.data_ptr(), running_mean.data_ptr(),
+                                      running_var.data_ptr(), y.data_ptr(), stats.data_ptr(), part.data_ptr(), P, C, float(eps),
+                                      float(momentum), int(relu), nat.stream()), "fpc_batchnorm_fwd")
+        ctx.save_for_backward(x, gamma, stats, *((y,) if relu else ()))
+        ctx.relu = relu
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, gamma, stats = ctx.saved_tensors[:3]
+        y = ctx.saved_tensors[3] if ctx.relu else None
+        B, C, H, W = x.shape
+        P = B * H * W
+        L = nat.lib()
+        gy = _channels_last(gy)
+        if gy.data_ptr() % 16:
+            gy = gy.clone(memory_format=torch.channels_last)
+        dx = torch.empty_like(x, memory_format=torch.channels_last) if ctx.needs_input_grad[0] else None
+        dres = torch.empty_like(x, memory_format=torch.channels_last) if ctx.needs_input_grad[1] else None
+        dgb = torch.empty((2, C), dtype=torch.float32, device=x.device)
+        part = nat.workspace("train_bn", x.device, 4 * L.fpc_batchnorm_scratch_floats(P, C))
+        nat.check(L.fpc_batchnorm_bwd(x.data_ptr(), nat.ptr(y), gy.data_ptr(), gamma.data_ptr(), stats.data_ptr(), nat.ptr(dx),
+                                      nat.ptr(dres), dgb.data_ptr(), dgb.data_ptr() + 4 * C, part.data_ptr(), P, C, int(ctx.relu),
+                                      nat.stream()), "fpc_batchnorm_bwd")
+        return (dx, dres, dgb[0] if ctx.needs_input_grad[2] else None, dgb[1] if ctx.needs_input_grad[3] else None,
+                None, None, None, None, None)
+
+
+def batchnorm_act(x, bn, res=None, relu=True, count_refusal=True):
+    """relu(bn(x) + res) (res and relu optional; a residual needs relu) for a torch.nn.BatchNorm2d `bn` in TRAINING mode, as one
+    native op each way on dense channel-last f32 GPU tensors: batch statistics, the module's running statistics and
+    num_batches_tracked updated as torch does.  None when the native path does not apply — evaluation mode, no affine parameters,
+    no running statistics, momentum=None (torch's cumulative average), another layout (never a layout copy to get here) or
+    dtype, a tensor that is not on the current device, fewer than two values per channel, the switch FPC_TRAIN_NATIVE_BN off (its
+    default) — and the caller runs the torch modules (counted as
+    bn_torch unless the caller says it will ask again)."""
+    ok = (ENABLED and NATIVE_BN and bn.training and bn.affine and bn.track_running_stats and bn.momentum is not None
+          and bn.running_mean is not None and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+          and x.shape[1] % 4 == 0 and x.shape[1] == bn.num_features and 2 <= x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31 - 256
+          and _dense_nhwc(x) and x.device.index == torch.cuda.current_device()      # (the launches go to the current device's stream)
+          and (res is None or (relu and res.shape == x.shape and res.dtype == x.dtype and res.device == x.device and _dense_nhwc(res)))
+          and all(t.dtype == torch.float32 and t.device == x.device and t.is_contiguous() and t.data_ptr() % 16 == 0
+                  for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)))
+    if not ok:
+        counters["bn_torch"] += int(count_refusal)
+        return None
+    bn.num_batches_tracked.add_(1)
+    counters["bn_native"] += 1
+    return _BatchNormActFn.apply(x, res, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum, bool(relu))

@@ -5,7 +5,8 @@ What runs where (stated in the JSON line as well):
   * encoder / decoder / head convolutions: lib/train_conv.py — forward on the engine's implicit-GEMM / Winograd kernels,
     data gradient on the same kernels (stride 1: flipped weights; stride 2: four parity convolutions of dy; heads of odd
     width: zero-padded to 32 channels), weight gradient on csrc/conv_wgrad.hip; torch keeps the 7x7 stem (Cin = 3);
-    bilinear upsampling forward / backward on csrc/upsample.hip; BatchNorm / GroupNorm / ReLU / adds: torch
+    bilinear upsampling forward / backward on csrc/upsample.hip; the decoder's GroupNorm + ReLU on csrc/groupnorm.hip; the
+    encoder's BatchNorm + residual add + ReLU: torch's modules, or csrc/batchnorm.hip with FPC_TRAIN_NATIVE_BN=1
     (FPC_TRAIN_NATIVE_CONV=0 returns every convolution and upsampling to torch: the A/B this file's numbers come with);
   * everything after the logits, forward: the inference kernels (class compression, connected components, aggregation,
     RANSAC vote, RT); backward: csrc/train.hip through lib/train_functions.py;
@@ -62,7 +63,9 @@ def _conv_note():
     c = train_conv.counters
     return ("native: forward fpc_conv2d (implicit GEMM / Winograd), data gradient on the same kernels (stride 2: four parity "
             "convolutions of dy; odd-width heads zero-padded), weight gradient fpc_conv2d_wgrad, bilinear upsampling "
-            "fpc_upsample_bilinear_fwd/bwd; torch for the 7x7 stem alone (Cin = 3: outside these counters) "
+            "fpc_upsample_bilinear_fwd/bwd; torch for the 7x7 stem alone (Cin = 3: outside these counters); the encoder's "
+            "BatchNorm + add + ReLU " + ("fpc_batchnorm_fwd/bwd (bn_native; bn_torch: left to torch) "
+                                         if train_conv.NATIVE_BN else "torch (FPC_TRAIN_NATIVE_BN=1: native) ") +
             f"(calls so far: {dict(c)})")
 
 

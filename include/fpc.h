@@ -594,6 +594,28 @@ int fpc_groupnorm4_relu_fwd(const float* x, const float* gamma, const float* bet
 int fpc_groupnorm4_relu_bwd(const float* x, const float* dy, const float* gamma, const float* beta, const float* stats, float* dx,
                             float* part, int B, int HW, int C, int groups, fpc_stream_t stream);
 
+/* Training-mode BatchNorm2d on channel-last activations, fused with the residual add and the ReLU behind it, forward and
+ * backward, for the training step.  Replaces torch.nn.BatchNorm2d (and the add / ReLU after it) inside the smp / torchvision
+ * ResNet encoder the reference builds at F/lib/pose_regressor.py:608, under Lightning's training step.  x, res, y, dy, dx,
+ * dres are [P, C] f32 (P = B H W pixels, channel stride 1), gamma / beta / dgamma / dbeta [C], stats [C][2] = mean, rstd
+ * (forward -> backward); all of them and `part` 16-byte aligned.  FPC_EINVAL for C % 4 != 0, P < 2, a null or misaligned
+ * pointer, or a residual without relu (no block has it).  No allocation inside; three launches each way; per-chunk partial
+ * sums (centred per chunk) are combined in double in a fixed order: bit-identical from run to run.
+ *
+ * fpc_batchnorm_scratch_floats: floats of `part`, for the forward and for the backward alike.
+ * fpc_batchnorm_fwd: y = (x - mean) rstd gamma + beta over the batch statistics (biased variance, rstd = 1/sqrt(var + eps)),
+ *   then y = relu(y) when relu, y = relu(y + res) when res is given too.  running_mean / running_var (both or neither) move
+ *   by `momentum` towards the batch mean and the UNBIASED batch variance, as torch's module buffers do.
+ * fpc_batchnorm_bwd: with g = dy [y > 0] (relu: the mask of the forward's saved output y; y may be null otherwise) or dy:
+ *   dbeta = sum g, dgamma = sum g xhat, dx = gamma rstd (g - dbeta / P - xhat dgamma / P), dres = g.  dx and dres are each
+ *   written only when not null (dres needs relu); neither: the elementwise pass is skipped. */
+size_t fpc_batchnorm_scratch_floats(int P, int C);
+int fpc_batchnorm_fwd(const float* x, const float* res, const float* gamma, const float* beta, float* running_mean,
+                      float* running_var, float* y, float* stats, float* part, int P, int C, float eps, float momentum, int relu,
+                      fpc_stream_t stream);
+int fpc_batchnorm_bwd(const float* x, const float* y, const float* dy, const float* gamma, const float* stats, float* dx,
+                      float* dres, float* dgamma, float* dbeta, float* part, int P, int C, int relu, fpc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
