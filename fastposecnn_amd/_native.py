@@ -19,6 +19,7 @@ _i = ctypes.c_int
 _i64 = ctypes.c_int64
 _u64 = ctypes.c_uint64
 _f = ctypes.c_float
+_d = ctypes.c_double
 _sz = ctypes.c_size_t
 
 _SIGNATURES = {
@@ -52,6 +53,9 @@ _SIGNATURES = {
     "fpc_vote_refine_backward": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _vp, _f, _i, _u64, _vp, _vp, _vp]),
     "fpc_class_compress_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "fpc_mask_losses": (_i, [_vp, _vp, _i, _i, _i, _i64, _i64, _f, _f, _vp, _vp, _vp, _vp]),
+    "fpc_match_assign": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "fpc_matched_losses": (_i, [_vp, _vp, _vp, _i, _i] + [_vp] * 10 + [_i, _d, _i, _i, _i, ctypes.POINTER(_d)] + [_vp] * 5),
+    "fpc_matched_losses_backward": (_i, [_vp, _vp, _vp, _i, _i] + [_vp] * 10 + [_i, _d, _i, _i, _i, ctypes.POINTER(_d)] + [_vp] * 8),
     "fpc_grad_sumsq": (_i, [_vp, _sz, _vp, _vp]),
     "fpc_lookahead_radam_step": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _i64, _i, _f, _vp, _vp]),
     "fpc_pose_rt": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),

@@ -7,6 +7,7 @@ quaternion loss over 360 rotations about the object's axis in float64, XY / scal
 Z on log-depth.  `FocalLoss` restates pytorch_toolbelt.losses.FocalLoss (upstream, not in the reference tree; parity
 unpinned) as the reference uses it: applied per class to LOG-SOFTMAX outputs as if they were logits.
 """
+import ctypes
 import functools
 
 import torch
@@ -351,3 +352,137 @@ def total_loss(criterion, outputs, batch, gt_pred_matches, perform_matching=True
         if not bool(torch.isnan(task_total)):
             total = total + task_total
     return total, report
+
+
+# ---- the matched half on the device (csrc/match_loss.hip) --------------------------------------------------------
+counters = {'device': 0, 'fallback': 0}         # total_loss_device calls with matches: native launches / materialize() + total_loss
+
+_MATCHED = ((QLoss, 'quaternion'), (XYLoss, 'xy'), (ZLoss, 'z'), (ScalesLoss, 'scales'))      # fpc_matched_losses' order
+_LOSS_CODES = {nn.MSELoss: 0, nn.L1Loss: 1, nn.SmoothL1Loss: 2}                                 # FPC_LOSS_*
+_dev_weights = {}
+
+
+def _weights_on(weights, dev):
+    """The four weights as a device tensor, filled without a host-to-device copy (which would synchronise)."""
+    key = (weights, str(dev))
+    if key not in _dev_weights:
+        _dev_weights[key] = torch.stack([torch.full((), v, dtype=torch.float64, device=dev) for v in weights])
+    return _dev_weights[key]
+
+
+class _MatchedLossesFn(torch.autograd.Function):
+    """(losses f64 [4], task totals f64 [4], their NaN-skipping sum f64 [1]) of the four matched losses over a DeviceMatches:
+    one launch forward, one backward."""
+
+    @staticmethod
+    def forward(ctx, q, xy, z, s, dm, gt, cfg):
+        from fastposecnn_amd import _native as nat
+        eps, types, weights = cfg
+        dev = q.device
+        n1, n2 = gt[0].shape[0], q.shape[0]
+        rot = gtf._rotation_table(dev)
+        losses, tasks, total = (torch.empty(n, dtype=torch.float64, device=dev) for n in (4, 4, 1))
+        best_rot = torch.empty(n1, dtype=torch.int32, device=dev)
+        pred = tuple(t.detach().contiguous() for t in (q, xy, z, s))
+        head = [nat.ptr(dm.order), nat.ptr(dm.match_pred), nat.ptr(dm.count), n1, n2, *[nat.ptr(t) for t in gt], *[nat.ptr(t) for t in pred],
+                nat.ptr(rot), rot.shape[0], eps, *types, (ctypes.c_double * 4)(*weights)]
+        with torch.cuda.device(dev):
+            nat.check(nat.lib().fpc_matched_losses(*head, nat.ptr(losses), nat.ptr(tasks), nat.ptr(total), nat.ptr(best_rot),
+                                                   nat.stream()), "fpc_matched_losses")
+        ctx.keep = (head, dm, gt, pred, rot)                        # the tensors `head` points into
+        ctx.save_for_backward(losses, best_rot, _weights_on(weights, dev))
+        return losses, tasks, total
+
+    @staticmethod
+    def backward(ctx, g_losses, g_tasks, g_total):
+        from fastposecnn_amd import _native as nat
+        head, pred = ctx.keep[0], ctx.keep[3]
+        losses, best_rot, w = ctx.saved_tensors
+        g = (g_losses + w * (g_tasks + g_total)).contiguous()         # task_total[k] = w[k] * losses[k]; the total sums them
+        grads = tuple(torch.empty_like(t) for t in pred)
+        with torch.cuda.device(g.device):
+            nat.check(nat.lib().fpc_matched_losses_backward(*head, nat.ptr(losses), nat.ptr(best_rot), nat.ptr(g), *[nat.ptr(t) for t in grads],
+                                                            nat.stream()), "fpc_matched_losses_backward")
+        return (*grads, None, None, None)
+
+
+def _matched_plan(criterion, dm):
+    """What fpc_matched_losses needs from the criterion and the two dicts, or None where total_loss must run: the matched
+    entries are one QLoss, XYLoss, ZLoss and ScalesLoss on their own keys, each alone in its task; the eight value tensors
+    are f32 on the current GPU; no ground truth requires grad; the sizes are within the device matching's limit."""
+    if dm.order is None:
+        return None
+    found = {}
+    for task, entries in criterion.items():
+        for name, attrs in entries.items():
+            if attrs['D'] != 'matched':
+                continue
+            fn = attrs['F']
+            slot = [k for k, (cls, key) in enumerate(_MATCHED) if type(fn) is cls and fn.key == key]
+            if not slot or slot[0] in found or len(entries) != 1:
+                return None
+            found[slot[0]] = (task, name, fn, float(attrs['weight']))
+    if len(found) != 4:
+        return None
+    types = []
+    for k in (1, 2, 3):
+        lf = found[k][2].loss_func
+        if type(lf) not in _LOSS_CODES or lf.reduction != 'mean' or getattr(lf, 'beta', 1.0) != 1.0:
+            return None
+        types.append(_LOSS_CODES[type(lf)])
+    gts, preds = dm.gts, dm.preds
+    dev = dm.order.device
+    n1, n2 = dm.order.shape[0], preds['class_ids'].shape[0]
+    tensors = []
+    for d, n in ((gts, n1), (preds, n2)):
+        for (_, key), width in zip(_MATCHED, (4, 2, 1, 3)):
+            t = d.get(key)
+            if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.device == dev and tuple(t.shape) == (n, width)):
+                return None
+            tensors.append(t)
+    sym = gts.get('symmetric_ids')
+    if not (torch.is_tensor(sym) and sym.device == dev and tuple(sym.shape) == (n1,) and not sym.is_floating_point()):
+        return None
+    if dev.index != torch.cuda.current_device() or any(t.requires_grad for t in tensors[:4]):
+        return None
+    gt = tuple(t.detach().contiguous() for t in tensors[:4]) + (sym.to(torch.int64).contiguous(),)
+    cfg = (float(found[0][2].eps), tuple(types), tuple(found[k][3] for k in range(4)))
+    return found, gt, tensors[4:], cfg
+
+
+def total_loss_device(criterion, outputs, batch, device_matches):
+    """`total_loss` on a `matching.DeviceMatches` without a host synchronisation: the pixel-wise entries as they are, the
+    four matched losses through fpc_matched_losses, the NaN rules of `total_loss` as tensor ops.  Same (total, report);
+    every value is a 0-dim device tensor.  A criterion or tensors the native entry does not cover (see _matched_plan) go
+    through materialize() and `total_loss`; `counters` says which of the two ran.  None: `total_loss(..., None)`."""
+    if device_matches is None:
+        return total_loss(criterion, outputs, batch, None)
+    plan = _matched_plan(criterion, device_matches)
+    if plan is None:
+        counters['fallback'] += 1
+        return total_loss(criterion, outputs, batch, device_matches.materialize())
+    counters['device'] += 1
+    found, gt, pred, cfg = plan
+    losses, tasks, matched_total = _MatchedLossesFn.apply(*pred, device_matches, gt, cfg)
+    losses32, tasks32 = losses.float(), tasks.float()                    # the dtypes of the classes: QLoss f64, the others f32
+    by_task = {found[k][0]: {found[k][1]: (losses if k == 0 else losses32)[k], 'task_total_loss': (tasks if k == 0 else tasks32)[k]}
+               for k in range(4)}
+    dev = outputs['logits']['mask'].device
+    total = torch.zeros((), device=dev)
+    report = {}
+    for task_name, entries in criterion.items():
+        if task_name in by_task:
+            report[task_name] = by_task[task_name]
+            continue
+        losses_t = {k: a['F'](outputs, batch) for k, a in entries.items() if a['D'] == 'pixel-wise'}
+        if losses_t:
+            weighted = torch.stack([v * entries[k]['weight'] for k, v in losses_t.items()])
+            is_nan = torch.isnan(weighted)
+            task_total = torch.where(is_nan.all(), torch.full_like(weighted[0], float('nan')),
+                                     torch.where(is_nan, torch.zeros_like(weighted), weighted).sum())
+        else:
+            task_total = torch.full((), float('nan'), device=dev)
+        losses_t['task_total_loss'] = task_total
+        report[task_name] = losses_t
+        total = total + torch.where(torch.isnan(task_total), torch.zeros_like(task_total), task_total)
+    return total + matched_total[0], report

@@ -10,7 +10,9 @@ What runs where (stated in the JSON line as well):
     (FPC_TRAIN_NATIVE_CONV=0 returns every convolution and upsampling to torch: the A/B this file's numbers come with);
   * everything after the logits, forward: the inference kernels (class compression, connected components, aggregation,
     RANSAC vote, RT); backward: csrc/train.hip through lib/train_functions.py;
-  * matching (fpc_mask_iou) and the loss arithmetic of F/lib/pose_regressor.py:188-307 with lib/loss.py;
+  * matching (fpc_mask_iou) and the loss arithmetic of F/lib/pose_regressor.py:188-307 with lib/loss.py: the arg-max on
+    the host and the matched losses as torch ops, or with FPC_TRAIN_DEVICE_LOSS=1 both on the device without a host
+    synchronisation (csrc/match_loss.hip; the line's config.losses says which ran);
   * gradients: bucketed RCCL reduce-scatter overlapped with backward, sharded native Lookahead(RAdam) step with clipping
     and the inf/NaN guard on device scalars, all-gather of the parameters (fastposecnn_amd/train_parallel.py).
 
@@ -122,6 +124,9 @@ def run(args, quiet=False):
     opt = ShardedLookaheadRAdam(model, lr=1e-5, weight_decay=3e-4, clip_norm=0.15, bucket_mb=args.bucket_mb)
     n_param = sum(p.numel() for p in model.parameters() if p.requires_grad)
 
+    # FPC_TRAIN_DEVICE_LOSS=1: matching and matched losses stay on the device (csrc/match_loss.hip); 0: the host forms
+    device_loss = bool(int(os.environ.get("FPC_TRAIN_DEVICE_LOSS", "0")))
+
     ev = {k: [torch.cuda.Event(enable_timing=True) for _ in range(2)] for k in ("fwd", "loss", "bwd", "opt")}
     last = {}
 
@@ -130,8 +135,12 @@ def run(args, quiet=False):
         if timed: ev["fwd"][0].record()
         out = model(batch["image"])
         if timed: ev["fwd"][1].record(); ev["loss"][0].record()
-        matches = mg.batchwise_find_matches(out["aggregated"], batch["agg_data"])
-        total, report = loss_lib.total_loss(criterion, out, batch, matches)
+        if device_loss:
+            matches = mg.batchwise_find_matches_device(out["aggregated"], batch["agg_data"])
+            total, report = loss_lib.total_loss_device(criterion, out, batch, matches)
+        else:
+            matches = mg.batchwise_find_matches(out["aggregated"], batch["agg_data"])
+            total, report = loss_lib.total_loss(criterion, out, batch, matches)
         if timed: ev["loss"][1].record(); ev["bwd"][0].record()
         total.backward()
         if timed: ev["bwd"][1].record(); ev["opt"][0].record()
@@ -167,7 +176,8 @@ def run(args, quiet=False):
     step(timed=True)
     torch.cuda.synchronize()
     stages = {k: round(a.elapsed_time(b), 3) for k, (a, b) in ev.items()}
-    matched = 0 if last["matches"] is None else int(last["matches"]["class_ids"].shape[0])
+    matches = last["matches"].materialize() if isinstance(last["matches"], mg.DeviceMatches) else last["matches"]
+    matched = 0 if matches is None else int(matches["class_ids"].shape[0])
     in_sync = True
     if world > 1:       # every rank must hold the same parameters after the all-gathers
         cs = opt.flat_p.double().sum().reshape(1)
@@ -193,6 +203,11 @@ def run(args, quiet=False):
                        "optimizer": "Lookahead(RAdam) k=5 alpha=0.5, lr 1e-5, weight decay 3e-4, clip 0.15; native shard kernel",
                        "optimizer_state_bytes_per_rank": opt.state_bytes(),
                        "convolutions": _conv_note(),
+                       "losses": (f"mask losses fpc_mask_losses; matching and matched losses on the device: fpc_mask_iou + "
+                                  f"fpc_match_assign + fpc_matched_losses / _backward, no host synchronisation "
+                                  f"(FPC_TRAIN_DEVICE_LOSS=1; total_loss_device calls: {dict(loss_lib.counters)})") if device_loss else
+                                 "mask losses fpc_mask_losses; matching on the host from fpc_mask_iou's matrix, matched losses torch "
+                                 "ops (FPC_TRAIN_DEVICE_LOSS=1: both on the device)",
                        "post_network": "HIP kernels forward (inference path) and backward (csrc/train.hip)"},
             "stages_ms": stages,
             "step_check": {"total_loss": round(float(last["total"]), 6), "losses": losses, "predicted_instances": last["n_pred"],

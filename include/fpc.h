@@ -29,6 +29,9 @@
  *   fpc_vote_refine_backward     torch autograd over RV/ransac_voting_gpu.py:583-599
  *   fpc_class_compress_backward  torch autograd over lib/gpu_tensor_funcs.py:37-99
  *   fpc_mask_losses              lib/loss.py:26-98 (CE, CCE, Focal: forward sums and the combined logit gradient)
+ *   fpc_match_assign             lib/matching.py:252-299 (the per-class arg-max and validity of batchwise_find_matches)
+ *   fpc_matched_losses           lib/loss.py:272-541 (QLoss, XYLoss, ZLoss, ScalesLoss) + lib/pose_regressor.py:265-307 (task sums)
+ *   fpc_matched_losses_backward  torch autograd over the same
  *   fpc_lookahead_radam_step     lib/pose_regressor.py:417-423 (catalyst Lookahead(RAdam)), F/train.py gradient_clip_val,
  *                                lib/pose_regressor.py:341-415 (inf / NaN guard)
  * The Python-side bindings a maintainer would add are shown in INTEGRATION.md.
@@ -320,6 +323,53 @@ int fpc_class_compress_backward(const int64_t* cat_mask, const float* quat, cons
 int fpc_mask_losses(const float* logits, const int64_t* target, int B, int C, int HW, int64_t ignore_ce,
                     int64_t ignore_cce, float alpha, float gamma, double* sums6, const float* w3, float* grad,
                     fpc_stream_t stream);
+/* ---- training: instance matching and the matched losses, results left on the device (csrc/match_loss.hip) ----------
+ * fpc_match_assign: the assignment half of matching.batchwise_find_matches.  iou f32 [n1,n2] row-major (fpc_mask_iou),
+ * gt_cls i64 [n1], pred_cls i64 [n2].  For ground truth i the candidates are the predictions j with pred_cls[j] ==
+ * gt_cls[i] in ascending j; the winner is torch.max's (the first index of the maximum; a NaN among the candidates makes
+ * the maximum NaN) and i is matched iff the maximum is > 0.  match_pred i32 [n1]: the winner or -1.  order i32 [n1]:
+ * order[0..count) = the matched ground-truth indices in the reference's output order (ascending class id, then ascending
+ * i), the rest -1.  count i32 [1].  One launch of one workgroup.
+ * n1 and n2 are limited to FPC_MATCH_MAX_INSTANCES each (FPC_EINVAL beyond it, before any launch; this holds for the two
+ * entries below as well).  n1 == 0 is a no-op. */
+#define FPC_MATCH_MAX_INSTANCES 1024
+int fpc_match_assign(const float* iou, const int64_t* gt_cls, const int64_t* pred_cls, int n1, int n2, int32_t* match_pred,
+                     int32_t* order, int32_t* count, fpc_stream_t stream);
+/* The four matched losses of the criterion table over the pairs (i, match_pred[i]), i in order[0..count): ground truth
+ * gt_quaternion [n1,4], gt_xy [n1,2], gt_z [n1,1], gt_scales [n1,3] and symmetric_ids i64 [n1]; predictions quaternion
+ * [n2,4], xy [n2,2], z [n2,1], scales [n2,3]; all f32.  rot f32 [nrot,4]: quat_symmetric_tf's table, as fpc_pose_errors
+ * takes it.  *_type: FPC_LOSS_* of XYLoss / ZLoss / ScalesLoss.  weights: HOST f64 [4], read during the call.
+ * losses f64 [4] = QLoss, XYLoss, ZLoss, ScalesLoss:
+ *   QLoss   per pair log(1 - dot^2 + eps) - log(eps): the f32 dot where symmetric_ids == 0, else the minimum over the nrot
+ *           rotations of the ground truth (rotated and normalised in f64; the first minimum wins, a NaN among them makes
+ *           the pair NaN); NaN pairs are dropped before the mean, no pair left gives NaN.
+ *   XY / Scales   sum over the components of the mean over the pairs of L2 / L1 / SmoothL1(beta = 1); Z the same on
+ *           log(gt), log(pred).  No NaN filter.
+ *   count == 0: all four are NaN.
+ * task_total f64 [4] = weights[k] * losses[k] (NaN where the loss is NaN); matched_total f64 [1] = the sum of the non-NaN
+ * task totals (0 without any).  best_rot i32 [n1]: per ground truth the winning rotation of a symmetric pair, 0 for a
+ * plain pair, -1 where the pair was dropped as NaN or the ground truth is unmatched (kept for the backward). */
+#define FPC_LOSS_L2 0
+#define FPC_LOSS_L1 1
+#define FPC_LOSS_SMOOTH_L1 2
+int fpc_matched_losses(const int32_t* order, const int32_t* match_pred, const int32_t* count, int n1, int n2,
+                       const float* gt_quaternion, const float* gt_xy, const float* gt_z, const float* gt_scales,
+                       const int64_t* symmetric_ids, const float* quaternion, const float* xy, const float* z,
+                       const float* scales, const float* rot, int nrot, double eps, int xy_type, int z_type, int scales_type,
+                       const double* weights, double* losses, double* task_total, double* matched_total, int32_t* best_rot,
+                       fpc_stream_t stream);
+/* d(sum_k g_losses[k] * losses[k]) / d(predictions): the forward's inputs, its outputs losses and best_rot, and g_losses
+ * f64 [4] on the device.  Every element of g_quaternion [n2,4], g_xy [n2,2], g_z [n2,1], g_scales [n2,3] (f32) is written;
+ * an unmatched prediction gets 0, a prediction matched by several ground truths the sum of their terms in `order` order
+ * (no atomics: two runs are bit-identical).  A loss that was NaN in the forward and a QLoss pair that was dropped
+ * contribute exactly 0 (their terms are skipped, not multiplied by 0).  Symmetric pairs: through best_rot only. */
+int fpc_matched_losses_backward(const int32_t* order, const int32_t* match_pred, const int32_t* count, int n1, int n2,
+                                const float* gt_quaternion, const float* gt_xy, const float* gt_z, const float* gt_scales,
+                                const int64_t* symmetric_ids, const float* quaternion, const float* xy, const float* z,
+                                const float* scales, const float* rot, int nrot, double eps, int xy_type, int z_type,
+                                int scales_type, const double* weights, const double* losses, const int32_t* best_rot,
+                                const double* g_losses, float* g_quaternion, float* g_xy, float* g_z, float* g_scales,
+                                fpc_stream_t stream);
 /* out2 f64 [2] (caller zeroes): [0] += sum g^2, [1] += 1 when a non-finite element was seen.  g 16-byte aligned. */
 int fpc_grad_sumsq(const float* g, size_t n, double* out2, fpc_stream_t stream);
 /* One Lookahead(RAdam) step on a flat f32 shard (p, g, m, v, slow: n elements each; step counts from 1).
