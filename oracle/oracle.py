@@ -166,9 +166,18 @@ def cc_label(fg):
 
 def aggregate(cat):
     """cat: categorical dict (see class_compress) -> AggData dict of numpy arrays."""
+    labels, N = cc_label(np.asarray(cat["mask"]) != 0)
+    return aggregate_labels(labels, cat, N)
+
+
+def aggregate_labels(labels, cat, N):
+    """The same on a label plane given by the caller (i32 [B,H,W], 0 = background, labels 1..N; any partition, connected or
+    not) -> AggData dict of numpy arrays.  A label above N is refused."""
     cm = np.ascontiguousarray(cat["mask"], dtype=np.int64)
     B, H, W = cm.shape
-    labels, N = cc_label(cm != 0)
+    labels = np.ascontiguousarray(labels, dtype=np.int32)
+    assert labels.shape == cm.shape
+    N = int(N)
     q = _f32(cat["quaternion"]); s = _f32(cat["scales"]); xy = _f32(cat["xy"]); z = _f32(cat["z"])
     cls = np.zeros(N, np.int64); sid = np.zeros(N, np.int64)
     im = np.zeros((N, H, W), np.float32)
