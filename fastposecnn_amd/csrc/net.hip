@@ -1746,7 +1746,9 @@ extern "C" int fpc_conv2d(const float* in, int64_t sb, int64_t sh, int64_t sw, i
         a.tickets = (int*)tk;
         if (hipMemsetAsync(tk, 0, kConvTickets * sizeof(int), s) != hipSuccess) return FPC_ELAUNCH;
     }
+#ifdef FPC_STAMP_WINO      // diagnostic builds only: relu = 77 turns ReLU off and hands gn_part to the kernel as its stamp buffer
     if (wino && relu == 77) { a.dbg = gn_part; a.p[0].gn_part = nullptr; a.relu = 0; }
+#endif
 #ifdef FPC_STAMP_IGEMM
     if (!wino && relu == 77) { a.dbg = gn_part; a.p[0].gn_part = nullptr; a.relu = 0; }
 #endif

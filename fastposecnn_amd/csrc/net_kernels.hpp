@@ -1,5 +1,5 @@
-// net_kernels.hpp — argument structs and launch wrappers of the backbone kernels
-// (net_kernels.hip), used by the engine (net.hip).  gfx950 only.
+// net_kernels.hpp — argument structs and launch wrappers of the backbone kernels (conv_igemm.hip, wino_f32.hip and the other
+// wino_*.hip, net_kernels.hip, lateral.hip, pointwise.hip, stem.hip, ...), used by the engine (net.hip).  gfx950 only.
 #pragma once
 #include "common.hpp"
 
@@ -51,7 +51,7 @@ struct ConvArgs {
     const float* fold_tab[kMaxGroup];
     int fold_cin;
     float fold_lat_ms;                // tuning: the p2 lateral's best score, the fold's time must beat lateral + s2.0
-    void* dbg;                        // host side only: diagnostic stamp buffer for k_conv_wino (or null)
+    void* dbg;                        // host side only: stamp buffer of a diagnostic build (-DFPC_STAMP_IGEMM / -DFPC_STAMP_WINO), else null
     long long wino_blocks;            // host side only, written by a form-9 launch: its workgroups
     int wino_pack;                    // host side only: a form-9 launch may use the packed patch geometry (wino_pack_geometry)
     int wino_orient;                  // host side only: a form-9 launch runs transposed where wino_orient_rule says so (wino_launch_geometry)
@@ -176,10 +176,20 @@ struct Up4Args {
     unsigned long long* fg_bits; size_t fg_stride;                        // nullable: foreground bit words [B][fg_stride] (W % 64 == 0)
 };
 
+// The Winograd kernels' diagnostics (phase stamps into WinoArgs::dbg; instantiations that skip the weight reload, the staging or the
+// barrier, picked by FPC_W4_MODE / FPC_H2_MODE / FPC_W2_MODE / FPC_H3_VAR / FPC_H3_ORIENT_G1) exist in a diagnostic build only
+// (-DFPC_STAMP_WINO, tools_dev/wino_stamps.py).  Elsewhere the kernels see a constant null stamp pointer, so every stamp test and
+// clock read folds away, the launchers read no environment and refuse a stamp buffer.  The structs are the same in both builds.
+#ifdef FPC_STAMP_WINO
+constexpr bool kWinoStamp = true;
+#else
+constexpr bool kWinoStamp = false;
+#endif
+
 // Winograd F(2x2,3x3) convolution (3x3, stride 1, pad 1, NHWC, Cin % 8 == 0, Cout % 64 == 0)
 struct WinoArgs {
     ConvPtrs p[kMaxGroup];   // .w = Winograd-packed weights [Cout/64][Cin/8][16][64][8]; .up unused
-    long long* dbg;          // diagnostic builds: per (workgroup, wave) cycle sums of the K-loop phases, or null
+    long long* dbg;          // -DFPC_STAMP_WINO builds: per (workgroup, wave) cycle sums of the K-loop phases, or null; otherwise null
     const float* zeros;      // >= 16 bytes of zeros, 16-byte aligned (source of out-of-image DMA pieces; variant 2)
     int variant;             // 0: barrier form, 1: wave-private barrier-free K loop (4 waves), 2: all-DMA 3-stage (8 waves),
                              // 3: split-precision barrier form (8 waves; .w = the k_wino_pack_bf3 image)

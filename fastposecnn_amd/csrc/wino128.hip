@@ -40,14 +40,12 @@
 //   residual, ReLU, GroupNorm partial sums per patch.
 // Reference: the 3x3 / stride-1 convolutions of F/lib/pose_regressor.py:709-743 (smp encoder + FPN decoder, not vendored).
 #include <algorithm>
+#ifdef FPC_STAMP_WINO
 #include <cstdlib>
-#include "net_kernels.hpp"
+#endif
+#include "conv_device.hpp"      // make_rsrc, the per-element fma_s4 / sub_s4 / add_s4
 
 namespace fpc {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
@@ -63,36 +61,16 @@ constexpr int kXiBytes = 6 * 1024;               // ... of which one xi's: 2 KB 
 constexpr int kLdsFloats = 4 * 2 * kNT * kBN;    // output transform image Z[row 4][cc 2][tile 32][co 128] = 128 KB
 static_assert(kLdsFloats >= 2 * kInFloats, "the K loop's two input buffers live in the output image's space");
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0x7FFFFFFF, 0x00020000);
-}
-__device__ __forceinline__ f32x4 fma_s4(float s, f32x4 b, f32x4 a) {      // s * b + a, one v_fma_f32 per element (net_kernels.hip)
-    f32x4 r;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { float x = b[k], y = a[k], z; asm("v_fma_f32 %0, %1, %2, %3" : "=v"(z) : "v"(s), "v"(x), "v"(y)); r[k] = z; }
-    return r;
-}
-__device__ __forceinline__ f32x4 sub_s4(f32x4 a, f32x4 b) {
-    f32x4 r;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { float x = a[k], y = b[k], z; asm("v_sub_f32 %0, %1, %2" : "=v"(z) : "v"(x), "v"(y)); r[k] = z; }
-    return r;
-}
-__device__ __forceinline__ f32x4 add_s4(f32x4 a, f32x4 b) {
-    f32x4 r;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { float x = a[k], y = b[k], z; asm("v_add_f32 %0, %1, %2" : "=v"(z) : "v"(x), "v"(y)); r[k] = z; }
-    return r;
-}
-
 }  // namespace
 
-// MODE (diagnostic instantiations, FPC_W2_MODE at launch): bit 0 = the K loop reloads no weights, bit 1 = it stages no input and has
+// MODE (diagnostic instantiations of a -DFPC_STAMP_WINO build, FPC_W2_MODE at launch; the product is MODE 0): bit 0 = the K loop
+// reloads no weights, bit 1 = it stages no input and has
 // no barrier — wrong results, the same instruction stream otherwise: what the loop costs without either memory path
 template <int MODE>
 __global__ __launch_bounds__(256, 1) void k_conv_wino_c128(const WinoArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[kLdsFloats];
-    const long long t_entry = a.dbg ? clock64() : 0;
+    long long* const dbg = kWinoStamp ? a.dbg : nullptr;      // a constant in the product build: the stamp code below folds away
+    const long long t_entry = dbg ? clock64() : 0;
     const int t = threadIdx.x, lane = t & 63;
     const int wi = __builtin_amdgcn_readfirstlane(t >> 6);      // transform row of this wave (wave-uniform)
     const int li = lane & 31, lh = lane >> 5;
@@ -205,7 +183,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_c128(const WinoArgs a) {
 
 #define FPC_W2_MFMA(J, NT, A, B) acc[J][NT] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, A), __builtin_bit_cast(bf16x8, B), acc[J][NT], 0, 0, 0)
     int cur = 0;
-    const long long c_begin = a.dbg ? clock64() : 0, r_begin = a.dbg ? wall_clock64() : 0;
+    const long long c_begin = dbg ? clock64() : 0, r_begin = dbg ? wall_clock64() : 0;
 #pragma unroll 1
     for (int kb = 0; kb < nkb; ++kb) {
         // input of step kb + 2 -> the buffer step kb's fragments were read from during step kb - 1 (oldest in the queue: see the wait below)
@@ -293,9 +271,9 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_c128(const WinoArgs a) {
 #undef FPC_LDS_ADDR
 #pragma clang diagnostic pop
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the last steps' redundant staging has landed before LDS is reused
-    const long long t_kend = a.dbg ? clock64() : 0;
-    if (a.dbg && lane == 0) {      // tools_dev/wino_stamps.py: shader-clock ticks and 100 MHz reference ticks of the K loop, entry -> loop
-        long long* o = a.dbg + ((size_t)blockIdx.x * 4 + wi) * 8;
+    const long long t_kend = dbg ? clock64() : 0;
+    if (dbg && lane == 0) {      // tools_dev/wino_stamps.py: shader-clock ticks and 100 MHz reference ticks of the K loop, entry -> loop
+        long long* o = dbg + ((size_t)blockIdx.x * 4 + wi) * 8;
         o[0] = 0; o[1] = 0; o[2] = 0;
         o[3] = t_kend - c_begin; o[4] = wall_clock64() - r_begin; o[5] = nkb; o[6] = c_begin - t_entry;
     }
@@ -386,9 +364,9 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_c128(const WinoArgs a) {
             g[0] = u1; g[1] = u2;
         }
     }
-    if (a.dbg && lane == 0) {
+    if (dbg && lane == 0) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        a.dbg[((size_t)blockIdx.x * 4 + wi) * 8 + 7] = clock64() - t_kend;      // K loop end -> last store acknowledged
+        dbg[((size_t)blockIdx.x * 4 + wi) * 8 + 7] = clock64() - t_kend;      // K loop end -> last store acknowledged
     }
 }
 
@@ -434,17 +412,20 @@ __global__ __launch_bounds__(256) void k_wino_pack_c128(const float* __restrict_
 }
 
 int launch_conv_wino_c128(const WinoArgs& a, int groups, hipStream_t s) {
-    if (groups < 1 || groups > kMaxGroup || a.Cin % 8 != 0 || a.Cout % kBN != 0 || a.waves != 4) return FPC_EINVAL;
+    if (groups < 1 || groups > kMaxGroup || a.Cin % 8 != 0 || a.Cout % kBN != 0 || a.waves != 4 || (!kWinoStamp && a.dbg)) return FPC_EINVAL;
     if ((long long)a.H * a.W * a.Cin * (long long)sizeof(float) >= (1LL << 32)) return FPC_EINVAL;      // 32-bit lane offsets inside one image
     if ((long long)(a.Cin >> 3) * kStepBytes >= (1LL << 31)) return FPC_EINVAL;                          // 31-bit buffer offsets inside one block's images
     if (a.tbx != cdiv(cdiv(a.W, 2), kTX) || a.tby != cdiv(cdiv(a.H, 2), kTY)) return FPC_EINVAL;
     const long long nblk = (long long)a.tbx * a.tby * a.B * (a.Cout / kBN) * groups;
     if (nblk < 1 || nblk >= (1LL << 31)) return FPC_EINVAL;
+#ifdef FPC_STAMP_WINO
     static const int mode = getenv("FPC_W2_MODE") ? atoi(getenv("FPC_W2_MODE")) : 0;      // diagnostic
     if (mode == 1) hipLaunchKernelGGL(k_conv_wino_c128<1>, dim3((unsigned)nblk), dim3(256), 0, s, a);
     else if (mode == 2) hipLaunchKernelGGL(k_conv_wino_c128<2>, dim3((unsigned)nblk), dim3(256), 0, s, a);
     else if (mode == 3) hipLaunchKernelGGL(k_conv_wino_c128<3>, dim3((unsigned)nblk), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k_conv_wino_c128<0>, dim3((unsigned)nblk), dim3(256), 0, s, a);
+    else
+#endif
+    hipLaunchKernelGGL(k_conv_wino_c128<0>, dim3((unsigned)nblk), dim3(256), 0, s, a);
     return check_launch();
 }
 

@@ -29,7 +29,9 @@
 // the output transform are wino_tile.hpp's; see there.
 // Reference: the 3x3 / stride-1 convolutions of F/lib/pose_regressor.py:709-743 (smp encoder + FPN decoder, not vendored).
 #include <algorithm>
+#ifdef FPC_STAMP_WINO
 #include <cstdlib>
+#endif
 #include "wino_tile.hpp"
 
 namespace fpc {
@@ -40,12 +42,14 @@ constexpr int kStepBytes = 16 * 64 * 32;         // k_wino_pack_fp16<false>'s im
 static_assert(kLdsFloats >= 2 * kInFloats, "the K loop's two input buffers live in the output image's space");
 }  // namespace
 
-// MODE (diagnostic instantiations, FPC_H2_MODE at launch): bit 0 = the K loop reloads no weights, bit 1 = it stages no input and has
+// MODE (diagnostic instantiations of a -DFPC_STAMP_WINO build, FPC_H2_MODE at launch; the product is MODE 0): bit 0 = the K loop
+// reloads no weights, bit 1 = it stages no input and has
 // no barrier — wrong results, the same instruction stream otherwise
 template <int MODE>
 __global__ __launch_bounds__(256, 1) void k_conv_wino_h2(const WinoArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[kLdsFloats];
-    const long long t_entry = a.dbg ? clock64() : 0;
+    long long* const dbg = kWinoStamp ? a.dbg : nullptr;      // a constant in the product build: the stamp code below folds away
+    const long long t_entry = dbg ? clock64() : 0;
     const int t = threadIdx.x, lane = t & 63;
     const int wi = __builtin_amdgcn_readfirstlane(t >> 6);      // transform row of this wave (wave-uniform)
     const int li = lane & 31, lh = lane >> 5;
@@ -92,11 +96,11 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h2(const WinoArgs a) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[j][mt][nt][r] = 0.f;
 
-    const long long t_issued = a.dbg ? clock64() : 0;
+    const long long t_issued = dbg ? clock64() : 0;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const long long t_landed = a.dbg ? clock64() : 0;
+    const long long t_landed = dbg ? clock64() : 0;
     __syncthreads();
-    const long long t_synced = a.dbg ? clock64() : 0;
+    const long long t_synced = dbg ? clock64() : 0;
 
     // operands of the current step's transformed fragments, as the matrix instructions take them: TA1[j][mt] = {h1, h1},
     // TA2[j][mt] = {h2, h2} (four channels per piece); transformed values vn[mt][j] of the step
@@ -136,7 +140,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h2(const WinoArgs a) {
 #define FPC_H2_MFMA(J, MT, NT, A, B) acc[J][MT][NT] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, A), __builtin_bit_cast(f16x8, B), acc[J][MT][NT], 0, 0, 0)
 #define FPC_H2_PIN4(V) asm volatile("" :: "v"(V))
     int cur = 0;
-    const long long c_begin = a.dbg ? clock64() : 0, r_begin = a.dbg ? wall_clock64() : 0;
+    const long long c_begin = dbg ? clock64() : 0, r_begin = dbg ? wall_clock64() : 0;
 #pragma unroll 1
     for (int kb = 0; kb < nkb; ++kb) {
         // input of step kb + 2 -> the buffer step kb's fragments were read from during step kb - 1 (oldest in the queue: see the wait below)
@@ -210,13 +214,13 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h2(const WinoArgs a) {
 #undef FPC_H2_ISSUE_IN
 #undef FPC_H2_LOAD_U
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the last steps' redundant staging has landed before LDS is reused
-    const long long t_kend = a.dbg ? clock64() : 0;
-    if (a.dbg && lane == 0) {      // tools_dev/wino_stamps.py: shader-clock ticks and 100 MHz reference ticks of the K loop, entry -> loop
-        long long* o = a.dbg + ((size_t)blockIdx.x * 4 + wi) * 8;
+    const long long t_kend = dbg ? clock64() : 0;
+    if (dbg && lane == 0) {      // tools_dev/wino_stamps.py: shader-clock ticks and 100 MHz reference ticks of the K loop, entry -> loop
+        long long* o = dbg + ((size_t)blockIdx.x * 4 + wi) * 8;
         o[0] = t_issued - t_entry; o[1] = t_landed - t_issued; o[2] = t_synced - t_landed;      // entry: set-up + issue | first operands land | barrier
         o[3] = t_kend - c_begin; o[4] = wall_clock64() - r_begin; o[5] = nkb; o[6] = c_begin - t_entry;
     }
-    wino_output<false, false>(lds, acc, P, pt, WinoEpi{H, W, Cout, a.relu, a.tbx, a.tby, 0}, inv_s, nullptr, a.dbg, t_kend, t, wi);
+    wino_output<false, false>(lds, acc, P, pt, WinoEpi{H, W, Cout, a.relu, a.tbx, a.tby, 0}, inv_s, nullptr, dbg, t_kend, t, wi);
 }
 
 // max |w| of a convolution's weights as the bit pattern of a non-negative float (atomicMax on unsigned keeps the order): one atomic
@@ -325,6 +329,7 @@ int launch_wino_pack_h2(const float* w_oihw, float* packed, int Cout, int Cin, h
 int launch_conv_wino_h2(const WinoArgs& a, int groups, hipStream_t s) {
     long long nblk;
     if (const int rc = wino_tile_check(a, groups, 8, kStepBytes, false, &nblk)) return rc;
+#ifdef FPC_STAMP_WINO
     static const int mode = getenv("FPC_H2_MODE") ? atoi(getenv("FPC_H2_MODE")) : 0;      // diagnostic
     if (mode == 1) hipLaunchKernelGGL(k_conv_wino_h2<1>, dim3((unsigned)nblk), dim3(256), 0, s, a);
     else if (mode == 2) hipLaunchKernelGGL(k_conv_wino_h2<2>, dim3((unsigned)nblk), dim3(256), 0, s, a);
@@ -332,7 +337,9 @@ int launch_conv_wino_h2(const WinoArgs& a, int groups, hipStream_t s) {
     else if (mode == 5) hipLaunchKernelGGL(k_conv_wino_h2<5>, dim3((unsigned)nblk), dim3(256), 0, s, a);      // no weights, DMA, no barrier
     else if (mode == 9) hipLaunchKernelGGL(k_conv_wino_h2<9>, dim3((unsigned)nblk), dim3(256), 0, s, a);      // no weights, barrier, no DMA
     else if (mode == 4) hipLaunchKernelGGL(k_conv_wino_h2<4>, dim3((unsigned)nblk), dim3(256), 0, s, a);      // everything but the barrier
-    else hipLaunchKernelGGL(k_conv_wino_h2<0>, dim3((unsigned)nblk), dim3(256), 0, s, a);
+    else
+#endif
+    hipLaunchKernelGGL(k_conv_wino_h2<0>, dim3((unsigned)nblk), dim3(256), 0, s, a);
     return check_launch();
 }
 

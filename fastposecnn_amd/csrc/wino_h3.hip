@@ -29,7 +29,9 @@
 // wino_tile.hpp's; Cin must be a multiple of 16.
 // Reference: the 3x3 / stride-1 convolutions of F/lib/pose_regressor.py:709-743 (smp encoder + FPN decoder, not vendored).
 #include <algorithm>
+#ifdef FPC_STAMP_WINO
 #include <cstdlib>
+#endif
 #include <type_traits>
 #include "wino_tile.hpp"
 
@@ -50,7 +52,7 @@ __device__ __forceinline__ const float* sgpr_ptr(const float* p) {
 
 }  // namespace
 
-// VAR (diagnostic, FPC_H3_VAR at launch): 1 = a piece's residual by conversion + subtraction instead of v_fma_mix_f32 (the same bits)
+// VAR (diagnostic, a -DFPC_STAMP_WINO build's FPC_H3_VAR at launch; the product is VAR 0): 1 = a piece's residual by conversion + subtraction instead of v_fma_mix_f32 (the same bits)
 //
 // FOLD: the FPN p2 level folded into s2.0 (a.fold; p2 = L c2 + b + up2_nearest(p3) is never written).  By linearity
 //   conv3x3(W, p2) = conv3x3(W L, c2) + conv3x3(W, up2(p3)) + conv3x3(W, b 1_inside)
@@ -71,7 +73,8 @@ __device__ __forceinline__ const float* sgpr_ptr(const float* p) {
 template <int VAR, bool FOLD, bool PACK, bool TR = false>
 __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[kLdsFloats];
-    const long long t_entry = a.dbg ? clock64() : 0;
+    long long* const dbg = kWinoStamp ? a.dbg : nullptr;      // a constant in the product build: the stamp code below folds away
+    const long long t_entry = dbg ? clock64() : 0;
     const int t = threadIdx.x, lane = t & 63;
     const int wi = __builtin_amdgcn_readfirstlane(t >> 6);      // transform row of this wave (wave-uniform)
     const int li = lane & 31, lh = lane >> 5;
@@ -85,7 +88,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
     f32x16 acc[4][2][2];      // [xi column j][tile half mt][32-channel tile nt]; zeroed while the first operands are on their way
     float inv_s = 1.f;        // 1 / (the power of two the weights of the LAST phase were scaled by)
     long long t_issued = 0, t_landed = 0, t_synced = 0, c_begin = 0, r_begin = 0;
-    const bool stamp = a.dbg != nullptr;      // (the loop below never names `a`: a reference to the kernel argument puts it in scratch)
+    const bool stamp = dbg != nullptr;      // (the loop below never names `a`: a reference to the kernel argument puts it in scratch)
 
     // The K loop over one input image `src` (Cs channels; up = 1: read as its nearest-x2 upsample) on the weight image `wimg`.
     // PH 0: the whole loop (acc zeroed first); 1: fold phase 2 (xi column 2 skipped).  Every phase ends after a barrier with no
@@ -313,15 +316,15 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
     }
     // (no staging is in flight here: a step past the last is never issued, every real step was waited for at the end of its pair; the
     // last pair's redundant weight reloads target registers, whose reuse the compiler guards itself)
-    const long long t_kend = a.dbg ? clock64() : 0;
-    // (the packed fold never stamps — its launcher refuses a.dbg — and would carry `lane` across both loops in scratch for this test)
-    if (!(FOLD && PACK) && a.dbg && lane == 0) {      // tools_dev/wino_stamps.py: shader-clock ticks and 100 MHz reference ticks of the K loop, entry -> loop
-        long long* o = a.dbg + ((size_t)blockIdx.x * 4 + wi) * 8;
+    const long long t_kend = dbg ? clock64() : 0;
+    // (the packed fold never stamps — its launcher refuses dbg — and would carry `lane` across both loops in scratch for this test)
+    if (!(FOLD && PACK) && dbg && lane == 0) {      // tools_dev/wino_stamps.py: shader-clock ticks and 100 MHz reference ticks of the K loop, entry -> loop
+        long long* o = dbg + ((size_t)blockIdx.x * 4 + wi) * 8;
         o[0] = t_issued - t_entry; o[1] = t_landed - t_issued; o[2] = t_synced - t_landed;      // entry: set-up + issue | first operands land | barrier
         o[3] = t_kend - c_begin; o[4] = wall_clock64() - r_begin; o[5] = a.Cin >> 3; o[6] = c_begin - t_entry;
     }
     wino_output<PACK, FOLD, TR>(lds, acc, P, pt, WinoEpi{H, W, Cout, a.relu, a.tbx, a.tby, a.pack_rx}, inv_s,
-                            wino_group(a.btab[0], a.btab[1], a.btab[2], a.btab[3], grp), a.dbg, t_kend, t, wi);
+                            wino_group(a.btab[0], a.btab[1], a.btab[2], a.btab[3], grp), dbg, t_kend, t, wi);
 }
 
 // The patch geometry of one k_conv_wino_h3 launch (host arithmetic).  tcw = ceil(W / 2) tile columns per frame; G = the smallest frame
@@ -370,9 +373,13 @@ bool wino_orient_rule(int H, int W) {
 
 // The geometry a form-9 launch of an H x W site uses: transposed where `orient` and the rule say so (then on the virtual image
 // W x H, packing whatever `pack_allow` says: fpc_net_set_wino_pack governs the plain sites only), else wino_pack_geometry's.
-// FPC_H3_ORIENT_G1 (diagnostic): a transposed launch keeps one frame per canvas row — the plain launch's patch count.
+// FPC_H3_ORIENT_G1 (a -DFPC_STAMP_WINO build only): a transposed launch keeps one frame per canvas row — the plain launch's patch count.
 WinoPackGeom wino_launch_geometry(int H, int W, int B, int Cin, bool orient, bool pack_allow, bool* transposed) {
+#ifdef FPC_STAMP_WINO
     static const bool g1 = getenv("FPC_H3_ORIENT_G1") && atoi(getenv("FPC_H3_ORIENT_G1")) != 0;
+#else
+    constexpr bool g1 = false;
+#endif
     *transposed = orient && wino_orient_rule(H, W);
     return *transposed ? wino_pack_geometry(W, H, B, Cin, !g1) : wino_pack_geometry(H, W, B, Cin, pack_allow);
 }
@@ -408,9 +415,12 @@ int launch_conv_wino_h3(const WinoArgs& a, int groups, hipStream_t s) {
         hipLaunchKernelGGL((k_conv_wino_h3<0, true, false>), dim3((unsigned)nblk), dim3(256), 0, s, a);
         return check_launch();
     }
+#ifdef FPC_STAMP_WINO
     static const int var = getenv("FPC_H3_VAR") ? atoi(getenv("FPC_H3_VAR")) : 0;      // diagnostic
     if (var == 1) hipLaunchKernelGGL((k_conv_wino_h3<1, false, false>), dim3((unsigned)nblk), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_conv_wino_h3<0, false, false>), dim3((unsigned)nblk), dim3(256), 0, s, a);
+    else
+#endif
+    hipLaunchKernelGGL((k_conv_wino_h3<0, false, false>), dim3((unsigned)nblk), dim3(256), 0, s, a);
     return check_launch();
 }
 

@@ -326,19 +326,19 @@ __device__ __forceinline__ void wino_output(float* lds, const f32x16 (&acc)[4][2
             g[0] = u1; g[1] = u2;
         }
     }
-    if (dbg && lane == 0) {
+    if (kWinoStamp && dbg && lane == 0) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         dbg[((size_t)blockIdx.x * 4 + wi) * 8 + 7] = clock64() - t_kend;      // K loop end -> last store acknowledged
     }
 }
 
-// ---- host side.  What every launcher of the family checks: groups, Cin a multiple of kch (the form's channels per K-step or pair),
+// ---- host side.  What every launcher of the family checks: no stamp buffer outside a diagnostic build, groups, Cin a multiple of kch (the form's channels per K-step or pair),
 // Cout of 64, 32-bit lane offsets inside one image, 31-bit buffer offsets inside one block's weight images (step_bytes per kch
 // channels), the patch grid (packed: wino_pack_geometry's own; otherwise one frame per patch row) and the workgroup
 // count, returned in *nblk.  (A transposed launch, a.orient: a.H x a.W is the virtual image; it packs
 // with or without the fold, and a.pack = 1 is one frame per canvas row.)
 inline int wino_tile_check(const WinoArgs& a, int groups, int kch, int step_bytes, bool packed, long long* nblk) {
-    if (groups < 1 || groups > kMaxGroup || a.Cin % kch != 0 || a.Cout % kBN != 0) return FPC_EINVAL;
+    if (groups < 1 || groups > kMaxGroup || a.Cin % kch != 0 || a.Cout % kBN != 0 || (!kWinoStamp && a.dbg)) return FPC_EINVAL;
     if ((long long)a.H * a.W * a.Cin * (long long)sizeof(float) >= (1LL << 32)) return FPC_EINVAL;
     if ((long long)(a.Cin / kch) * step_bytes >= (1LL << 31)) return FPC_EINVAL;
     if (packed) {

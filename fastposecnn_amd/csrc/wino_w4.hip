@@ -28,7 +28,9 @@
 // forms: wino_tile.hpp.
 // Reference: the 3x3 / stride-1 convolutions of F/lib/pose_regressor.py:709-743 (smp encoder + FPN decoder, not vendored).
 #include <algorithm>
+#ifdef FPC_STAMP_WINO
 #include <cstdlib>
+#endif
 #include "wino_tile.hpp"
 
 namespace fpc {
@@ -41,12 +43,14 @@ constexpr int kStepBytes = 12288 * 4;            // k_wino_pack_bf3's image of o
 static_assert(kLdsFloats >= 2 * kInFloats, "the K loop's two input buffers live in the output image's space");
 }  // namespace
 
-// MODE (diagnostic instantiations, FPC_W4_MODE at launch): bit 0 = the K loop reloads no weights, bit 1 = it stages no input and has
+// MODE (diagnostic instantiations of a -DFPC_STAMP_WINO build, FPC_W4_MODE at launch; the product is MODE 0): bit 0 = the K loop
+// reloads no weights, bit 1 = it stages no input and has
 // no barrier — wrong results, the same instruction stream otherwise
 template <int MODE>
 __global__ __launch_bounds__(256, 1) void k_conv_wino_w4(const WinoArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[kLdsFloats];
-    const long long t_entry = a.dbg ? clock64() : 0;
+    long long* const dbg = kWinoStamp ? a.dbg : nullptr;      // a constant in the product build: the stamp code below folds away
+    const long long t_entry = dbg ? clock64() : 0;
     const int t = threadIdx.x, lane = t & 63;
     const int wi = __builtin_amdgcn_readfirstlane(t >> 6);      // transform row of this wave (wave-uniform)
     const int li = lane & 31, lh = lane >> 5;
@@ -142,7 +146,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_w4(const WinoArgs a) {
 #define FPC_W4_PIN4(V) asm volatile("" :: "v"(V))
     u32x4 Atup = {pa[0][0][0][0], pa[0][0][0][1], pa[0][0][0][0], pa[0][0][0][1]};      // operand of the first pair of slots (xi 0, a1 b1 + a1 b2, half 0)
     int cur = 0;
-    const long long c_begin = a.dbg ? clock64() : 0, r_begin = a.dbg ? wall_clock64() : 0;
+    const long long c_begin = dbg ? clock64() : 0, r_begin = dbg ? wall_clock64() : 0;
 #pragma unroll 1
     for (int kb = 0; kb < nkb; ++kb) {
         // input of step kb + 2 -> the buffer step kb's fragments were read from during step kb - 1 (oldest in the queue: see the wait below)
@@ -235,19 +239,20 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_w4(const WinoArgs a) {
 #undef FPC_W4_LOAD_U
 #undef FPC_W4_LOAD_T
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the last steps' redundant staging has landed before LDS is reused
-    const long long t_kend = a.dbg ? clock64() : 0;
-    if (a.dbg && lane == 0) {      // tools_dev/wino_stamps.py: shader-clock ticks and 100 MHz reference ticks of the K loop, entry -> loop
-        long long* o = a.dbg + ((size_t)blockIdx.x * 4 + wi) * 8;
+    const long long t_kend = dbg ? clock64() : 0;
+    if (dbg && lane == 0) {      // tools_dev/wino_stamps.py: shader-clock ticks and 100 MHz reference ticks of the K loop, entry -> loop
+        long long* o = dbg + ((size_t)blockIdx.x * 4 + wi) * 8;
         o[0] = 0; o[1] = 0; o[2] = 0;
         o[3] = t_kend - c_begin; o[4] = wall_clock64() - r_begin; o[5] = nkb; o[6] = c_begin - t_entry;
     }
-    wino_output<false, false>(lds, acc, P, pt, WinoEpi{H, W, Cout, a.relu, a.tbx, a.tby, 0}, 1.0f, nullptr, a.dbg, t_kend, t, wi);
+    wino_output<false, false>(lds, acc, P, pt, WinoEpi{H, W, Cout, a.relu, a.tbx, a.tby, 0}, 1.0f, nullptr, dbg, t_kend, t, wi);
 }
 
 // .w = the k_wino_pack_bf3 image (as variant 3 of launch_conv_wino), .waves = 8 (tby = ceil(ceil(H / 2) / 8): 8 x 8 tile patches)
 int launch_conv_wino_w4(const WinoArgs& a, int groups, hipStream_t s) {
     long long nblk;
     if (const int rc = wino_tile_check(a, groups, 8, kStepBytes, false, &nblk)) return rc;
+#ifdef FPC_STAMP_WINO
     static const int mode = getenv("FPC_W4_MODE") ? atoi(getenv("FPC_W4_MODE")) : 0;      // diagnostic
     if (mode == 1) hipLaunchKernelGGL(k_conv_wino_w4<1>, dim3((unsigned)nblk), dim3(256), 0, s, a);
     else if (mode == 2) hipLaunchKernelGGL(k_conv_wino_w4<2>, dim3((unsigned)nblk), dim3(256), 0, s, a);
@@ -255,7 +260,9 @@ int launch_conv_wino_w4(const WinoArgs& a, int groups, hipStream_t s) {
     else if (mode == 5) hipLaunchKernelGGL(k_conv_wino_w4<5>, dim3((unsigned)nblk), dim3(256), 0, s, a);      // no weights, DMA, no barrier
     else if (mode == 9) hipLaunchKernelGGL(k_conv_wino_w4<9>, dim3((unsigned)nblk), dim3(256), 0, s, a);      // no weights, barrier, no DMA
     else if (mode == 4) hipLaunchKernelGGL(k_conv_wino_w4<4>, dim3((unsigned)nblk), dim3(256), 0, s, a);      // everything but the barrier
-    else hipLaunchKernelGGL(k_conv_wino_w4<0>, dim3((unsigned)nblk), dim3(256), 0, s, a);
+    else
+#endif
+    hipLaunchKernelGGL(k_conv_wino_w4<0>, dim3((unsigned)nblk), dim3(256), 0, s, a);
     return check_launch();
 }
 

@@ -160,7 +160,7 @@ def test_the_printed_constants_are_the_emulated_ones():
     """Every place that states the fp16 pair's bound names the emulated constants."""
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     assert H2_REL == 3 * 2.0 ** -23 and H2_ABS == 2.0 ** -24
-    for rel in ("fastposecnn_amd/csrc/wino_h2.hip", "fastposecnn_amd/csrc/common.hpp", "fastposecnn_amd/csrc/net_kernels.hip",
+    for rel in ("fastposecnn_amd/csrc/wino_h2.hip", "fastposecnn_amd/csrc/common.hpp", "fastposecnn_amd/csrc/conv_igemm.hip",
                 "include/fpc.h"):
         text = open(os.path.join(repo, rel)).read()
         assert "3 * 2^-23" in text and "2^-24" in text, rel

@@ -1,9 +1,14 @@
-"""Cycle stamps of the Winograd K loop (diagnostic hook of fpc_conv2d: relu == 77 routes gn_part to the stamp buffer)."""
+"""Cycle stamps of the Winograd K loop from a -DFPC_STAMP_WINO build (its hook in fpc_conv2d: relu == 77 routes gn_part to the stamp buffer).
+    python -c "from fastposecnn_amd import build; build.build(extra=['-DFPC_STAMP_WINO'])"; python tools_dev/wino_stamps.py [form]
+then rebuild without the flag.  The same build reads FPC_W4_MODE / FPC_H2_MODE / FPC_W2_MODE / FPC_H3_VAR / FPC_H3_ORIENT_G1."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from fastposecnn_amd import _native as nat
 dev = torch.device("cuda:0"); L = nat.lib()
+if not hasattr(L, "fpc_dbg_wino_diag"):      # a product library: relu = 77 is plain ReLU there and gn_part would come back holding GroupNorm sums
+    sys.exit("wino_stamps.py needs a diagnostic build of the library:\n"
+             "    python -c \"from fastposecnn_amd import build; build.build(extra=['-DFPC_STAMP_WINO'])\"")
 VAR = int(sys.argv[1]) if len(sys.argv) > 1 else -1      # -1: 4-wave barrier form, -4: 8-wave all-DMA form
 NWAVE = 8 if VAR in (-4, -2, -5) else 4      # (-6, -7: four waves)
 B, Cin, Hi, Wi, Cout, k = 4, 256, 120, 160, 128, 3
