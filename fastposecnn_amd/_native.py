@@ -49,6 +49,9 @@ _SIGNATURES = {
     "fpc_aggregate_bits": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "fpc_mask_bits_words": (_sz, [_i, _i]),
     "fpc_pose_errors": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "fpc_pose_metrics_state_words": (_sz, [_i, _i, _i, _i, _i]),
+    "fpc_pose_metrics_update": (_i, [_vp, _vp, _vp, _i, _i] + [_vp] * 11 + [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i] + [_vp] * 5 + [_i, _vp]),
+    "fpc_confusion_update": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
     "fpc_post_network_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _i, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fpc_vote_refine_backward": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _vp, _f, _i, _u64, _vp, _vp, _vp]),
     "fpc_class_compress_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),

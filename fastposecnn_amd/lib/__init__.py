@@ -5,7 +5,7 @@ under their bare names (`gpu_tensor_funcs`, `aggregation_layer`, `hough_voting`,
 `pose_regressor`, `ransac_voting_gpu_layer.*`), so `train.py` / `evaluate.py` /
 `inference.py` keep working with `import lib` pointed at this directory.
 `matching.batchwise_find_matches`, `loss` and `metrics` (ranks 2 and 4: the classes
-train.py selects) are shipped; the rest of matching.py is outside the hot path and is not.
+train.py selects) are shipped, and `metrics_device` (the same metrics and the mask's accumulated on the device); the rest of matching.py is outside the hot path and is not.
 """
 import os
 import sys
@@ -25,3 +25,4 @@ import pose_regressor  # noqa: E402
 import matching  # noqa: E402
 import loss  # noqa: E402
 import metrics  # noqa: E402
+import metrics_device  # noqa: E402

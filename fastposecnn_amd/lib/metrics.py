@@ -133,7 +133,8 @@ class OffsetError(_RunningMean):
 
 def head_training_metrics():
     """The 'pose' block of train.py's metrics table (:208-215); the mask block uses pl.metrics.functional (dice / iou / f1
-    of the arg-max mask), which stays with Lightning."""
+    of the arg-max mask), which stays with Lightning (metrics_device.MaskMetricsDevice: textbook IoU / dice / F1 from a
+    confusion matrix accumulated on the device, not claimed equal to Lightning's)."""
     return {'pose': {
         'degree_error': {'D': 'matched', 'F': DegreeError()},
         'degree_error_AP_5': {'D': 'matched', 'F': DegreeErrorMeanAP(5)},

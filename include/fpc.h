@@ -25,6 +25,8 @@
  *   fpc_preprocess_u8            tools/dataset.py:249-262 (preprocessing_fn, transpose, / max|.|, img_as_float32)
  *   fpc_png_info / _decode / _decode_batch   tools/dataset.py:158-176 (skimage.io.imread / cv2.imread of *_color / *_mask / *_depth.png)
  *   fpc_pose_errors              lib/gpu_tensor_funcs.py:411-476, 486-547, 563-565 (degree error, 3-D IoU, offset error)
+ *   fpc_pose_metrics_update      lib/metrics.py:11-260, lib/gpu_tensor_funcs.py:611-713, evaluate.py:238-292 (metric accumulators, APs)
+ *   fpc_confusion_update         (none: the confusion matrix of the arg-max mask; the reference's mask metrics are Lightning's)
  *   fpc_post_network_backward    torch autograd over lib/aggregation_layer.py:119-156 + RV/ransac_voting_gpu.py:583-599
  *   fpc_vote_refine_backward     torch autograd over RV/ransac_voting_gpu.py:583-599
  *   fpc_class_compress_backward  torch autograd over lib/gpu_tensor_funcs.py:37-99
@@ -293,6 +295,48 @@ int fpc_pose_errors(const float* q0, const float* q1, const int64_t* symmetric_i
                     const float* RT1, const float* RT2, const float* scales1, const float* scales2,
                     const float* T1, const float* T2, int n, double* out_degree, float* out_iou3d, float* out_offset,
                     fpc_stream_t stream);
+
+/* ---- evaluation metrics accumulated on the device (lib/metrics.py:11-260, lib/gpu_tensor_funcs.py:611-713,
+ * evaluate.py:238-292) ----------------------------------------------------------------------------------------------
+ * fpc_pose_metrics_update folds the matched pairs (g, match_pred[g]), g = order[0..count), of ONE fpc_match_assign into a
+ * persistent device state: one launch of one workgroup, nothing read back.  Per pair it takes fpc_pose_errors' three
+ * errors (same device functions, csrc/pose_errors.hpp) from the ground truth's quaternion f32 [n1,4], RT f32 [n1,4,4],
+ * scales f32 [n1,3], T f32 [n1,3], symmetric_ids i64 [n1], class_ids i64 [n1] and the predictions' f32 [n2,..] arrays.
+ *
+ * state i64 [fpc_pose_metrics_state_words(C, n_deg, n_iou, n_off, K)], zero-initialised by the caller; M = metric 0 degree,
+ * 1 IoU, 2 offset; words marked f64 hold a double's bits:
+ *   [0] updates with count > 0   [1] pairs left out of the per-class words (class id outside 1..C-1)
+ *   [2] raw-log cursor (pairs offered so far)   [3] raw-log overflow (pairs offered beyond raw_capacity)
+ *   [4],[5] DegreeErrorMeanAP correct, total (NaN pairs leave total)   [6],[7] Iou3dAP   [8],[9] OffsetAP (NaN pairs stay in total)
+ *   [10] f64 DegreeError   [11] f64 Iou3dAccuracy   [12] f64 OffsetError: state = (state + this update's value) / 2
+ *   [13..15] reserved (0)
+ *   [16 + 6 c + 2 M], [.. + 1]          class c: non-NaN samples, NaN samples of metric M
+ *   [16 + 6 C + c (n_deg + n_iou + n_off) + j]   class c: hits of threshold j (degree's, then IoU's, then offset's)
+ *   [16 + 6 C + C (n_deg + n_iou + n_off) + c K + k]   class c: pairs with degree < thr_complex[k] and offset < thr_complex[K + k]
+ * A hit is error < threshold (degree, offset) or error > threshold (IoU), strict, the error widened to f64; a NaN never hits.
+ * thr_degree / thr_iou / thr_offset f64 [n_*], thr_complex f64 [2,K], thr_table f64 [3] (the thresholds of words 4-9), on
+ * the device.  This update's values for words 10-12: the mean of the non-NaN degree errors, the mean of IoU * 100 (f32
+ * product, NaN propagates), and from_RTs_get_T_offset_errors: ONE distance over all pairs between the camera origins
+ * under inverse(RT), times 10.  Their sums run over the pairs in `order` order in f64, so two runs give the same bits.
+ * count == 0 writes nothing at all (words 10-12 are not halved).  A class id outside 1..C-1 is never an index: the pair
+ * still enters words 2-12 and the raw log, and is counted in word 1.
+ * Raw log (raw_capacity > 0): raw_degree f64, raw_iou f32, raw_offset f32, raw_class i32, each [raw_capacity]; the pairs go
+ * to cursor, cursor + 1, .. in `order` order while they fit.
+ * Limits as fpc_match_assign: n1, n2 <= FPC_MATCH_MAX_INSTANCES; also 2 <= C <= 4096 and n_deg + n_iou + n_off + K <= 4096
+ * (FPC_EINVAL before any launch). */
+size_t fpc_pose_metrics_state_words(int num_classes, int n_deg, int n_iou, int n_off, int n_complex);
+int fpc_pose_metrics_update(const int32_t* order, const int32_t* match_pred, const int32_t* count, int n1, int n2,
+                            const float* gt_quaternion, const float* gt_RT, const float* gt_scales, const float* gt_T,
+                            const int64_t* symmetric_ids, const int64_t* class_ids, const float* quaternion, const float* RT,
+                            const float* scales, const float* T, const float* rot, int nrot, const double* thr_degree, int n_deg,
+                            const double* thr_iou, int n_iou, const double* thr_offset, int n_off, const double* thr_complex,
+                            int n_complex, const double* thr_table, int num_classes, int64_t* state, double* raw_degree,
+                            float* raw_iou, float* raw_offset, int32_t* raw_class, int raw_capacity, fpc_stream_t stream);
+
+/* Confusion matrix of two label planes: pred, gt i64 [n] (n = B * H * W), state i64 [C * C + 1], C <= 32.
+ * state[gt * C + pred] += 1 for every pixel with both labels in [0, C); state[C * C] += the pixels left out (ignore
+ * labels, negative values).  Integer atomics only; any n >= 0. */
+int fpc_confusion_update(const int64_t* pred, const int64_t* gt, int64_t n, int num_classes, int64_t* state, fpc_stream_t stream);
 
 /* ---- training: backward of the post-network path, optimiser step ----------------
  * fpc_post_network_backward: labels i32 [B,H,W] (fpc_cc_label), cat_xy f32 [B,2,H,W] (the categorical vote planes the
