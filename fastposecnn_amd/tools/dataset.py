@@ -22,6 +22,11 @@ per-instance ground truth of `generate_agg_data` :373-434, z <= 0 rejection, cla
 reference's sample dict key for key (pinned by tests/golden/nocs_sample.npz, which the reference's own class wrote:
 oracle/gen_golden.py).  `evaluate.py:148` and the training step feed `batchwise_find_matches` from exactly this dict.
 Augmentation is not mirrored (the reference has it commented out, :239-242).
+
+The same ground truth built on the device: `NOCSDataset.gt_item` is the half of `__getitem__` that the side file alone
+decides, `GroundTruthUploader` uploads the instance-id masks beside it and has fpc_gt_build (csrc/gt_build.hip) write the
+class mask and the per-instance planes where `my_collate_fn` would copy them to; `build_gt_host` states in numpy what that
+kernel computes.  `__getitem__` and `my_collate_fn` are unchanged.
 """
 import ctypes
 import os
@@ -350,20 +355,12 @@ class NOCSDataset(torch.utils.data.Dataset):
         # Which pixels survive: instances the side file lists (distractor objects are not listed) whose class is one of
         # the wanted ones (F/tools/dataset.py:183-228).  Two 256-entry tables indexed by the mask's instance id — id -> id
         # and id -> class index — replace the reference's per-instance sweeps over the image.
-        listed = [(int(k), c) for k, c in json_data['instance_dict'].items()]
-        rows = [r for r, (_, c) in enumerate(listed) if c in self.class_values_map]
+        good_json_data = self.wanted_instances(json_data)
         id_of = np.zeros(256, dtype=mask.dtype)
         class_of = np.zeros(256, dtype=mask.dtype)
-        good_json_data = {'instance_dict': {}}
-        for r in rows:
-            inst_id, c = listed[r]
+        for inst_id, c in good_json_data['instance_dict'].items():
             id_of[inst_id] = inst_id
-            class_of[inst_id] = self.class_values_map[c]
-            good_json_data['instance_dict'][inst_id] = self.class_values_map[c]
-        if rows:
-            for key, per_instance in json_data.items():
-                if key != 'instance_dict':
-                    good_json_data[key] = np.stack([per_instance[r] for r in rows])
+            class_of[inst_id] = c
         pixel_ids = mask.astype(np.intp)
         good_instances_mask = id_of[pixel_ids]
 
@@ -387,6 +384,44 @@ class NOCSDataset(torch.utils.data.Dataset):
         })
         return sample
 
+    def wanted_instances(self, json_data):
+        """The side file restricted to the instances of a wanted class, in file order: {'instance_dict': {instance id:
+        class index in self.classes}, and every per-instance key stacked over the rows kept}."""
+        listed = [(int(k), c) for k, c in json_data['instance_dict'].items()]
+        rows = [r for r, (_, c) in enumerate(listed) if c in self.class_values_map]
+        good_json_data = {'instance_dict': {}}
+        for r in rows:
+            inst_id, c = listed[r]
+            good_json_data['instance_dict'][inst_id] = self.class_values_map[c]
+        if rows:
+            for key, per_instance in json_data.items():
+                if key != 'instance_dict':
+                    good_json_data[key] = np.stack([per_instance[r] for r in rows])
+        return good_json_data
+
+    def gt_item(self, i):
+        """The half of `__getitem__` that the side file alone decides — no pixel is touched, no mask file is read:
+        {'path', 'mask_path', 'ids' (instance id per row of agg_data: side-file order after the class filter),
+        'class_values' (class index per row), 'valid' (False where `__getitem__` returns None: an instance with z <= 0),
+        'table' (the float64 per-instance blocks of `generate_agg_data` but instance_masks)}.  GroundTruthUploader builds
+        the pixel half on the device from these and the mask's instance ids.  Instance ids are the mask's byte values
+        1 .. 254 (0 and 255 are background): a side file that lists another one raises ValueError (the host path lets
+        id 0 through and then miscounts its instances)."""
+        color_fp = str(self.images_fps[i])
+        return self.gt_from_side_file(jt.load_from_json(color_fp.replace('_color.png', '_meta+.json')), self.images_fps[i],
+                                      color_fp.replace('_color.png', '_mask.png'))
+
+    def gt_from_side_file(self, json_data, path=None, mask_path=None):
+        """`gt_item` for a side file that is already loaded."""
+        for key in json_data['instance_dict']:
+            if not 1 <= int(key) <= 254:
+                raise ValueError("%s lists instance id %s: ids are the mask's byte values 1 .. 254" % (path, key))
+        good_json_data = self.wanted_instances(json_data)
+        ids = list(good_json_data['instance_dict'])
+        table = self.instance_table(good_json_data, len(ids))
+        return {'path': path, 'mask_path': mask_path, 'ids': ids, 'class_values': list(good_json_data['instance_dict'].values()),
+                'valid': not (table['z'] <= 0).any(), 'table': table}
+
     def get_random_batched_sample(self, batch_size=1, device=None):
         ids = np.random.choice(np.arange(len(self)), size=batch_size, replace=False)
         return my_collate_fn([self[int(k)] for k in ids], device)
@@ -397,9 +432,16 @@ class NOCSDataset(torch.utils.data.Dataset):
         instance's binary mask, quaternion, scales / norm factor, and from the RT matrices the projected origin (flipped to
         the other coordinate style), z, T and R (tools/data_manipulation.py).  Filled one fancy-indexed block per key."""
         n = np.unique(instances_mask).size - 1
+        inst = np.array(list(json_data['instance_dict'])).reshape(len(json_data['instance_dict']))
+        return self.instance_table(json_data, n, lambda block: block(instances_mask[None] == inst[:, None, None],
+                                                                     *instances_mask.shape))
+
+    def instance_table(self, json_data, n, instance_masks=None):
+        """The per-instance blocks of `generate_agg_data` for n rows, one fancy-indexed block per key.  `instance_masks`
+        (a callable on the block builder) adds that key in its place; without it the table is the part of agg_data that
+        the side file alone decides (`gt_item`)."""
         listed = list(json_data['instance_dict'].items())             # (instance id, class id)
         k = len(listed)
-        inst = np.array([i for i, _ in listed]).reshape(k)
         cls = np.array([c for _, c in listed], dtype=np.float64).reshape(k)
         per_instance = dict(dm.extract_xyz_R_T_from_RTs(json_data['RTs'], self.INTRINSICS),      # xy, z, T, R
                             quaternion=json_data['quaternions'], scales=json_data['scales'], RT=json_data['RTs'])
@@ -411,7 +453,7 @@ class NOCSDataset(torch.utils.data.Dataset):
 
         agg_data = {
             'class_ids': block(cls), 'symmetric_ids': block(np.isin(cls, self.symmetric_classes)),
-            'instance_masks': block(instances_mask[None] == inst[:, None, None], *instances_mask.shape),
+            **({'instance_masks': instance_masks(block)} if instance_masks else {}),
             'quaternion': block(per_instance['quaternion'], 4),
             'scales': block(per_instance['scales'], 3) / np.expand_dims(json_data['norm_factors'], axis=1),
             'xy': block(per_instance['xy'], 2)[:, ::-1],              # (row, col) -> the other style
@@ -454,3 +496,259 @@ def my_collate_fn(batch, device=None):
     out = {key: (put(np.stack(vals)) if isinstance(vals[0], np.ndarray) else vals) for key, vals in columns.items()}
     out["agg_data"] = {subkey: put(np.concatenate(vals, axis=0)) for subkey, vals in agg.items()}
     return out
+
+
+# ------------------------------------------------------------------------------------- ground-truth batches on the device
+
+# the float64 per-instance keys of agg_data in generate_agg_data's order, with their row shapes
+GT_TABLE_KEYS = (('class_ids', ()), ('symmetric_ids', ()), ('quaternion', (4,)), ('scales', (3,)), ('xy', (2,)), ('z', (1,)),
+                 ('T', (3,)), ('R', (3, 3)), ('RT', (4, 4)))
+_MASK_ELEM = {torch.float64: 8, torch.float32: 4, torch.uint8: 1}
+
+
+def gt_tables(items):
+    """`gt_item` dicts of B frames -> (row_of int16 [B,256], class_of uint8 [B,256], first_row int32 [B+1], n): the rows of
+    agg_data are the frames' instances in order, so frame b owns rows first_row[b] .. first_row[b+1] - 1.  Ids that no
+    item lists (distractors, unwanted classes, the background 0 and 255) map to row -1 and class 0."""
+    B = len(items)
+    row_of = np.full((B, 256), -1, np.int16)
+    class_of = np.zeros((B, 256), np.uint8)
+    first_row = np.zeros(B + 1, np.int32)
+    n = 0
+    for b, item in enumerate(items):
+        for inst_id, c in zip(item['ids'], item['class_values']):
+            row_of[b, inst_id] = n
+            class_of[b, inst_id] = c
+            n += 1
+        first_row[b + 1] = n
+    return row_of, class_of, first_row, n
+
+
+def build_gt_host(ids_u8, pix_stride, row_of, class_of, first_row, n, mask_dtype=np.float64):
+    """What fpc_gt_build computes, in numpy.  ids_u8: uint8 [B,H,W] (pix_stride 1) or [B,H,W,pix_stride] (the id is channel
+    0) -> (class_mask int64 [B,H,W], instance_masks mask_dtype [n,H,W], pix_count int32 [n])."""
+    ids_u8 = np.asarray(ids_u8)
+    B, H, W = ids_u8.shape[:3]
+    ids = ids_u8.reshape(B, -1)[:, ::pix_stride]
+    frames = np.arange(B)[:, None]
+    class_mask = np.asarray(class_of)[frames, ids].astype(np.int64).reshape(B, H, W)
+    rows = np.asarray(row_of)[frames, ids]
+    inst = np.zeros((n, H, W), mask_dtype)
+    for b in range(B):
+        for r in range(max(int(first_row[b]), 0), min(int(first_row[b + 1]), n)):
+            inst[r] = (rows[b] == r).reshape(H, W)
+    return class_mask, inst, np.count_nonzero(inst.reshape(n, -1), axis=1).astype(np.int32)
+
+
+class GroundTruthUploader:
+    """Instance-id masks + `NOCSDataset.gt_item` dicts -> the ground-truth half of a batch on the device, the twin of
+    FrameUploader: pinned staging, asynchronous H2D copies and one fpc_gt_build launch on its own stream, `slots` deep.
+    `upload(...)` / `upload_png(...)` return (batch_dict, event); wait on the event before the first consumer kernel.
+
+    batch_dict['mask'] (int64 [B',H,W]) and batch_dict['agg_data'] carry the keys, dtypes, shapes and values of
+    `my_collate_fn([ds[i] for i in ...], device)`, 'sample_ids' included; only 'instance_masks' takes `mask_dtype`
+    (float64 as the reference; float32 or uint8 on request — uint8 is what batchwise_get_2d_iou reads without a
+    conversion pass).  On top come agg_data['pixel_counts'] (int32 [n]) and, `with_depth`, batch_dict['depth'] (float32).
+    Every value is a contiguous view `[:n]` / `[:B']` of a slot buffer: nothing is allocated per upload.
+
+    What the host bytes cost: the id planes (H W channels bytes a frame) and two small tables cross the bus; the float64
+    planes (8 H W bytes an instance) are written by the device at its own rate.
+
+    Slot ownership is FrameUploader's: the dict returned by an upload is overwritten `slots` uploads later; pass
+    `consumed` (an event recorded after its last reader) to have the uploader wait for it on the device.
+
+    An instance the side file lists but the mask does not contain: the host path raises for it (n < k in
+    generate_agg_data); this path cannot know without a synchronisation, so it emits the row with an all-zero plane and
+    pixel_counts == 0.  `GroundTruthUploader.check(batch_dict)` synchronises and raises ValueError for such a batch."""
+
+    def __init__(self, batch, height, width, channels, device="cuda:0", slots=2, max_instances=256,
+                 mask_dtype=torch.float64, with_depth=False):
+        if mask_dtype not in _MASK_ELEM:
+            raise ValueError("mask_dtype must be torch.float64, torch.float32 or torch.uint8")
+        if not 1 <= channels <= 4:
+            raise ValueError("channels must be 1 .. 4")
+        self.device = torch.device(device)
+        self.shape = (batch, height, width, channels)
+        self.max_instances, self.mask_dtype, self.with_depth = int(max_instances), mask_dtype, bool(with_depth)
+        self.stream = torch.cuda.Stream(device=self.device)
+        B, H, W, M = batch, height, width, self.max_instances
+        # one buffer for the integer tables: sample_ids i64 [M] | first_row i32 [B+1] | row_of i16 [B,256] | class_of u8 [B,256]
+        o_first = 8 * M
+        o_row = o_first + -(-4 * (B + 1) // 16) * 16
+        o_cls = o_row + 512 * B
+        self._cuts = (o_first, o_row, o_cls, o_cls + 256 * B)
+        widths = [int(np.prod(s, dtype=np.int64)) for _, s in GT_TABLE_KEYS]
+        self._offs = np.concatenate([[0], np.cumsum(widths)]) * M          # the float64 table, key by key
+        self._slots = []
+        for _ in range(slots):
+            s = {'ids_host': torch.empty(self.shape, dtype=torch.uint8).pin_memory(),
+                 'ids_dev': torch.empty(self.shape, dtype=torch.uint8, device=self.device),
+                 'int_host': torch.zeros(self._cuts[3], dtype=torch.uint8).pin_memory(),
+                 'int_dev': torch.empty(self._cuts[3], dtype=torch.uint8, device=self.device),
+                 'f64_host': torch.zeros(int(self._offs[-1]), dtype=torch.float64).pin_memory(),
+                 'f64_dev': torch.empty(int(self._offs[-1]), dtype=torch.float64, device=self.device),
+                 'class_mask': torch.empty((B, H, W), dtype=torch.int64, device=self.device),
+                 'inst': torch.empty((M, H, W), dtype=mask_dtype, device=self.device),
+                 'count': torch.empty(M, dtype=torch.int32, device=self.device)}
+            if self.with_depth:        # a depth file is 16-bit grey or R,G,B(,A) bytes: at most four bytes a pixel
+                s['depth_host'] = torch.empty(B * H * W * 4, dtype=torch.uint8).pin_memory()      # frames packed at their own size
+                s['depth_dev'] = torch.empty(B * H * W * 4, dtype=torch.uint8, device=self.device)
+                s['depth'] = torch.empty((B, H, W), dtype=torch.float32, device=self.device)
+            s['ids_np'], s['int_np'], s['f64_np'] = s['ids_host'].numpy(), s['int_host'].numpy(), s['f64_host'].numpy()
+            s['tables'] = self._carve(s['int_np'], lambda a, dt: a.view(dt))
+            s['tables_dev'] = self._carve(s['int_dev'], lambda a, dt: a.view(getattr(torch, np.dtype(dt).name)))
+            self._slots.append(s)
+        self._free = [None] * slots          # event: the slot's previous batch has been consumed
+        self._busy = [None] * slots          # event: the slot's H2D copies have left the pinned buffers
+        self._i = 0
+        self._pool = None
+
+    def _carve(self, raw, view):
+        """(sample_ids, first_row, row_of, class_of) views of the integer buffer."""
+        a, b, c, d = self._cuts
+        return view(raw[:a], np.int64), view(raw[a:a + 4 * (self.shape[0] + 1)], np.int32), view(raw[b:c], np.int16), raw[c:d]
+
+    def _next_slot(self, items):
+        B = len(items)
+        if not 1 <= B <= self.shape[0]:
+            raise ValueError(f"expected 1 .. {self.shape[0]} items, got {B}")
+        for item in items:
+            if not item['valid']:
+                raise ValueError(f"{item['path']}: an invalid item (z <= 0); drop the frame before uploading it")
+        n = sum(len(item['ids']) for item in items)
+        if n > self.max_instances:
+            raise ValueError(f"{n} instances in the batch, the uploader holds {self.max_instances}")
+        k = self._i % len(self._slots)
+        self._i += 1
+        if self._busy[k] is not None:
+            self._busy[k].synchronize()      # the pinned buffers are about to be rewritten by the CPU
+        return k, self._slots[k]
+
+    def upload(self, id_planes, items, consumed=None, depth=None):
+        """id_planes: uint8 array / CPU tensor [B',H,W,channels] ([B',H,W] when channels == 1), the mask files as decoded;
+        items: the B' `gt_item` dicts.  depth (with_depth): uint16 [B',H,W] or uint8 [B',H,W,3|4] as decoded."""
+        k, s = self._next_slot(items)
+        B = len(items)
+        src = id_planes if isinstance(id_planes, np.ndarray) else id_planes.numpy()
+        np.copyto(s['ids_np'][:B], src.reshape((B,) + self.shape[1:]))
+        kind = None
+        if self.with_depth:
+            if depth is None:
+                raise ValueError("this uploader was built with_depth: pass the decoded depth planes")
+            d = depth if isinstance(depth, np.ndarray) else depth.numpy()
+            kind = self._depth_kind(16 if d.dtype == np.uint16 else 8, d.shape[3] if d.ndim == 4 else 1)
+            flat = np.ascontiguousarray(d).reshape(-1).view(np.uint8)
+            np.copyto(s['depth_host'].numpy()[:flat.size], flat)
+        return self._enqueue(k, items, consumed, kind)
+
+    def upload_png(self, mask_files, items, consumed=None, threads=4, depth_files=None):
+        """mask_files: the B' `*_mask.png` files as bytes, decoded as stored (fpc_png_decode mode 0) by `threads` host
+        threads straight into the pinned slot; their size and channel count must be the uploader's (ValueError).
+        depth_files (with_depth): the `*_depth.png` files, all 16-bit grey or all colour-coded."""
+        k, s = self._next_slot(items)
+        B = len(items)
+        if len(mask_files) != B:
+            raise ValueError(f"{B} items, {len(mask_files)} mask files")
+        _, H, W, C = self.shape
+        jobs = [(f, s['ids_np'][j]) for j, f in enumerate(mask_files)]
+        for f, _ in jobs:
+            if self._png_info(f) != (W, H, 8, C):
+                raise ValueError("a mask file is not %d x %d with %d 8-bit channels" % (W, H, C))
+        kind = None
+        if self.with_depth:
+            if depth_files is None or len(depth_files) != B:
+                raise ValueError("this uploader was built with_depth: pass one depth file per item")
+            infos = {self._png_info(f) for f in depth_files}
+            if len(infos) != 1 or next(iter(infos))[:2] != (W, H):
+                raise ValueError("the depth files are not all %d x %d of one format" % (W, H))
+            _, _, bits, ch = next(iter(infos))
+            kind = self._depth_kind(bits, ch)
+            nbytes = H * W * ch * bits // 8
+            jobs += [(f, s['depth_host'].numpy()[j * nbytes:(j + 1) * nbytes]) for j, f in enumerate(depth_files)]
+        if threads > 1 and len(jobs) > 1:
+            if self._pool is None or self._pool[0] != int(threads):      # kept between uploads: starting threads costs a decode
+                from concurrent.futures import ThreadPoolExecutor
+                self._pool = (int(threads), ThreadPoolExecutor(max_workers=int(threads)))
+            list(self._pool[1].map(lambda job: self._png_decode(*job), jobs))
+        else:
+            for job in jobs:
+                self._png_decode(*job)
+        return self._enqueue(k, items, consumed, kind)
+
+    @staticmethod
+    def _png_info(data):
+        buf = np.frombuffer(data, dtype=np.uint8)
+        info = (ctypes.c_int32 * 5)()
+        nat.check(nat.lib().fpc_png_info(buf.ctypes.data, buf.size, info), "fpc_png_info")
+        return int(info[0]), int(info[1]), int(info[2]), int(info[4])          # width, height, bit depth, channels
+
+    @staticmethod
+    def _png_decode(data, out):
+        buf = np.frombuffer(data, dtype=np.uint8)
+        nat.check(nat.lib().fpc_png_decode(buf.ctypes.data, buf.size, out.ctypes.data, out.nbytes, 0), "fpc_png_decode")
+
+    @staticmethod
+    def _depth_kind(bits, channels):
+        """(src_kind, channels) of fpc_depth_decode for what standardize_depth takes."""
+        if bits == 16 and channels == 1:
+            return 1, 1
+        if bits == 8 and channels in (3, 4):
+            return 0, channels
+        raise ValueError("unsupported depth image")
+
+    def _enqueue(self, k, items, consumed, depth_kind):
+        s = self._slots[k]
+        B, (_, H, W, C) = len(items), self.shape
+        row_of, class_of, first_row, n = gt_tables(items)
+        sample_ids, t_first, t_row, t_cls = s['tables']
+        sample_ids[:n] = np.repeat(np.arange(B), np.diff(first_row))
+        t_first[:B + 1], t_row[:256 * B], t_cls[:256 * B] = first_row, row_of.reshape(-1), class_of.reshape(-1)
+        M = self.max_instances
+        for (key, shape), off in zip(GT_TABLE_KEYS, self._offs):
+            w = int(np.prod(shape, dtype=np.int64))
+            dst = s['f64_np'][off:off + n * w].reshape((n,) + shape)
+            r = 0
+            for item in items:
+                m = len(item['ids'])
+                dst[r:r + m] = item['table'][key]
+                r += m
+        L = nat.lib()
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            if self._free[k] is not None:
+                self.stream.wait_event(self._free[k])
+            s['ids_dev'][:B].copy_(s['ids_host'][:B], non_blocking=True)
+            s['int_dev'].copy_(s['int_host'], non_blocking=True)
+            s['f64_dev'].copy_(s['f64_host'], non_blocking=True)
+            if depth_kind is not None:
+                used = B * H * W * (2 if depth_kind[0] == 1 else depth_kind[1])
+                s['depth_dev'][:used].copy_(s['depth_host'][:used], non_blocking=True)
+            self._busy[k] = torch.cuda.Event()
+            self._busy[k].record()
+            d_sample, d_first, d_row, d_cls = s['tables_dev']
+            nat.check(L.fpc_gt_build(nat.ptr(s['ids_dev']), C, H * W * C, B, H, W, nat.ptr(d_row), nat.ptr(d_cls), nat.ptr(d_first), n,
+                                     nat.ptr(s['class_mask']), nat.ptr(s['inst']), _MASK_ELEM[self.mask_dtype], nat.ptr(s['count']),
+                                     nat.stream()), "fpc_gt_build")
+            if depth_kind is not None:
+                nat.check(L.fpc_depth_decode(nat.ptr(s['depth_dev']), depth_kind[0], depth_kind[1], B, H, W, nat.ptr(s['depth']),
+                                             nat.stream()), "fpc_depth_decode")
+            done = torch.cuda.Event()
+            done.record()
+        self._free[k] = consumed
+        agg = {'sample_ids': d_sample[:n]}
+        for (key, shape), off in zip(GT_TABLE_KEYS, self._offs):
+            w = int(np.prod(shape, dtype=np.int64))
+            agg[key] = s['f64_dev'][off:off + M * w].view((M,) + shape)[:n]
+            if key == 'symmetric_ids':
+                agg['instance_masks'] = s['inst'][:n]
+        agg['pixel_counts'] = s['count'][:n]
+        out = {'mask': s['class_mask'][:B], 'agg_data': agg}
+        if depth_kind is not None:
+            out['depth'] = s['depth'][:B]
+        return out, done
+
+    @staticmethod
+    def check(batch_dict):
+        """Synchronises.  ValueError when an instance of the batch has no pixel in its mask (the host path's n < k)."""
+        empty = torch.nonzero(batch_dict['agg_data']['pixel_counts'] == 0).flatten().tolist()
+        if empty:
+            raise ValueError("instances without a pixel in their mask: rows %s" % empty)

@@ -24,6 +24,7 @@
  *   fpc_net_*                    lib/pose_regressor.py:709-743 (+ segmentation_models_pytorch encoder/decoder/head)
  *   fpc_preprocess_u8            tools/dataset.py:249-262 (preprocessing_fn, transpose, / max|.|, img_as_float32)
  *   fpc_png_info / _decode / _decode_batch   tools/dataset.py:158-176 (skimage.io.imread / cv2.imread of *_color / *_mask / *_depth.png)
+ *   fpc_gt_build / fpc_depth_decode   tools/dataset.py:183-228, 373-434 (class filter and instance_masks of a sample), data_manipulation.py:153-163
  *   fpc_pose_errors              lib/gpu_tensor_funcs.py:411-476, 486-547, 563-565 (degree error, 3-D IoU, offset error)
  *   fpc_pose_metrics_update      lib/metrics.py:11-260, lib/gpu_tensor_funcs.py:611-713, evaluate.py:238-292 (metric accumulators, APs)
  *   fpc_confusion_update         (none: the confusion matrix of the arg-max mask; the reference's mask metrics are Lightning's)
@@ -53,6 +54,7 @@ extern "C" {
  * and the stem fused with its max-pool (fpc_net_force_stem_pool, fpc_stem_pool_tasks, fpc_conv2d's 3100):
  * and form -9's packed patch geometry (fpc_wino_pack_geometry, fpc_net_set_wino_pack, fpc_net_wino_blocks, fpc_conv2d's -10):
  * and the activation-range guard of the fp16-piece forms (fpc_act_range, fpc_net_survey_next, fpc_net_guard_ranges, fpc_net_guarded):
+ * and the ground-truth batch builder (fpc_gt_build, fpc_depth_decode):
  * additions only, every earlier entry point keeps its behaviour. */
 #define FPC_ABI_VERSION 11
 
@@ -283,6 +285,27 @@ int fpc_preprocess_u8(const uint8_t* img_hwc, int B, int H, int W, const double*
 int fpc_png_info(const uint8_t* data, size_t nbytes, int32_t* out5);
 int fpc_png_decode(const uint8_t* data, size_t nbytes, void* out, size_t out_bytes, int mode);
 int fpc_png_decode_batch(const uint8_t* const* datas, const size_t* sizes, int n, uint8_t* out, int H, int W, int threads);
+
+/* ---- ground-truth side: instance-id masks -> the batch's class mask and per-instance planes (ABI 11 addition) -------
+ * tools/dataset.py: __getitem__'s class filter and generate_agg_data's instance_masks for B frames in one launch
+ * (csrc/gt_build.hip).  ids: DEVICE bytes, the id of pixel p of frame b is ids[b * frame_stride + p * pix_stride]
+ * (pix_stride 1: a grey mask; 4: the CAMERA set's RGBA mask files as decoded, the other channels are ignored).
+ * row_of i16 [B][256]: the row of agg_data (0 .. n-1) of this id in this frame, or -1; class_of u8 [B][256]: its class
+ * index, 0 = background / not wanted; first_row i32 [B+1]: the rows of frame b are first_row[b] .. first_row[b+1] - 1
+ * (contiguous, ascending).  All three DEVICE.  The kernel applies the tables and nothing else (id 255 is background by
+ * the caller's tables).
+ * -> class_mask i64 [B,H,W] = class_of[b][id]; inst_masks [n,H,W] of f64 / f32 / u8 (mask_elem 8 / 4 / 1; 16-byte
+ *    aligned): 1 where row_of[b][id] == r, else 0, every plane of a frame's rows written in full; pix_count i32 [n]: set
+ *    pixels per row (zeroed on the stream by the entry).  Each output is optional (NULL).  Rows >= n are never touched;
+ *    n == 0 still writes the class mask.  Bytes written: n H W mask_elem + 8 B H W.
+ * FPC_EINVAL before any launch: NULL ids / tables, B < 1, H < 1, W < 1, n < 0, n > 32767, pix_stride outside 1 .. 4,
+ * inst_masks given with another mask_elem or not 16-byte aligned, H W or the grid beyond 2^31. */
+int fpc_gt_build(const uint8_t* ids, int64_t pix_stride, int64_t frame_stride, int B, int H, int W,
+                 const int16_t* row_of, const uint8_t* class_of, const int32_t* first_row, int n,
+                 int64_t* class_mask, void* inst_masks, int mask_elem, int32_t* pix_count, fpc_stream_t stream);
+/* The batch's `depth` key: standardize_depth(...).astype('float32') of tools/dataset.py.  src_kind 0: u8 [B,H,W,channels]
+ * (channels 3 or 4, R,G,B(,A)): G * 256 + R; src_kind 1: u16 [B,H,W].  -> depth_f32 [B,H,W].  All DEVICE. */
+int fpc_depth_decode(const void* src, int src_kind, int channels, int B, int H, int W, float* depth_f32, fpc_stream_t stream);
 
 /* ---- evaluation maths on matched pairs (lib/gpu_tensor_funcs.py:411-476, 486-547, 563-565) ----------------------
  * One launch for n (ground truth, prediction) pairs; every output is optional (NULL skips it and its inputs).
