@@ -103,6 +103,8 @@ _SIGNATURES = {
     "fpc_net_set_wino_pack": (_i, [_vp, _i]),
     "fpc_net_set_wino_orient": (_i, [_vp, _i]),
     "fpc_wino_orient_geometry": (_i, [_i, _i, _i, _i, _i, _i, ctypes.POINTER(_i64)]),
+    "fpc_wino_recip": (_i, [ctypes.c_uint32, ctypes.POINTER(_i64)]),
+    "fpc_wino_decode": (_i, [_i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(_i64)]),
     "fpc_net_wino_blocks": (_i64, [_vp]),
     "fpc_net_graph_recorded": (_i, [_vp]),
     "fpc_net_flops": (_i, [_vp, ctypes.POINTER(ctypes.c_double)]),

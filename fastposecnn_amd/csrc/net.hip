@@ -1630,6 +1630,22 @@ extern "C" int fpc_wino_orient_geometry(int H, int W, int B, int Cin, int fold, 
     return FPC_OK;
 }
 
+// The reciprocals of the four-wave Winograd kernels' workgroup-id decode (wino_recip, wino_decode: host arithmetic), as the
+// launchers compute them.
+extern "C" int fpc_wino_recip(uint32_t d, int64_t* out2) {
+    if (!out2 || d < 1 || d > (1u << 31)) return FPC_EINVAL;
+    const WinoRecip r = wino_recip(d);
+    out2[0] = r.m; out2[1] = r.sh;
+    return FPC_OK;
+}
+extern "C" int fpc_wino_decode(int Cout, int groups, int tbx, int tby, int W, int B, int pack, int64_t* out14) {
+    if (!out14 || Cout < 64 || groups < 1 || tbx < 1 || tby < 1 || W < 1 || B < 1 || pack < 0) return FPC_EINVAL;
+    const WinoDecode d = wino_decode(Cout, groups, tbx, tby, W, B, pack);
+    const WinoRecip r[7] = {d.nnb, d.groups, d.tbx, d.tby, d.per, d.tbxl, d.tcw};
+    for (int i = 0; i < 7; ++i) { out14[2 * i] = r[i].m; out14[2 * i + 1] = r[i].sh; }
+    return FPC_OK;
+}
+
 // ---- stand-alone convolution (unit tests / micro-benchmarks of k_conv_igemm) -----------------
 extern "C" size_t fpc_conv2d_workspace_bytes(int B, int Ho, int Wo, int Cin, int Cout, int Kh, int Kw) {
     int K = Cin * Kh * Kw, Kpad = cdiv(K, kConvBK) * kConvBK, Npad = cdiv(Cout, kConvNAlign) * kConvNAlign;

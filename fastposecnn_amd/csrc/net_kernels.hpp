@@ -177,7 +177,7 @@ struct Up4Args {
 };
 
 // The Winograd kernels' diagnostics (phase stamps into WinoArgs::dbg; instantiations that skip the weight reload, the staging or the
-// barrier, picked by FPC_W4_MODE / FPC_H2_MODE / FPC_W2_MODE / FPC_H3_VAR / FPC_H3_ORIENT_G1) exist in a diagnostic build only
+// barrier, picked by FPC_W4_MODE / FPC_H2_MODE / FPC_W2_MODE / FPC_H3_VAR / FPC_H3_ORIENT_G1; FPC_WINO_SERIAL: the serial path's phase stamps) exist in a diagnostic build only
 // (-DFPC_STAMP_WINO, tools_dev/wino_stamps.py).  Elsewhere the kernels see a constant null stamp pointer, so every stamp test and
 // clock read folds away, the launchers read no environment and refuse a stamp buffer.  The structs are the same in both builds.
 #ifdef FPC_STAMP_WINO
@@ -185,6 +185,29 @@ constexpr bool kWinoStamp = true;
 #else
 constexpr bool kWinoStamp = false;
 #endif
+constexpr int kWinoSerialStamps = 16;      // WinoArgs::variant of a k_conv_wino_h3 launch whose stamp buffer also holds 16-word serial-path records (set by the diagnostic launcher only)
+
+// n / d for 0 <= n < 2^31 as (n * m) >> sh in 64 bits: two scalar multiplies and a shift where a runtime division is a software
+// sequence of some tens of instructions.  sh = 31 + ceil(log2 d), m = ceil(2^sh / d) < 2^32; then 2^sh <= m d <= 2^sh + 2^(sh - 31), so
+// n m / 2^sh lies in [n / d, n / d + n / (2^31 d)], and n < 2^31 keeps that below the next multiple of 1 / d: the floor is n / d's
+// (Granlund & Montgomery, "Division by invariant integers using multiplication", 1994, theorem 4.2 with N = 31).  1 <= d <= 2^31.
+struct WinoRecip { unsigned m; int sh; };
+inline WinoRecip wino_recip(unsigned d) {
+    int l = 0;
+    while ((1ull << l) < d) ++l;
+    const int sh = 31 + l;
+    return WinoRecip{(unsigned)(((1ull << sh) + d - 1) / d), sh};
+}
+// The divisors of the four-wave Winograd kernels' workgroup-id decode (wino_tile.hpp: wino_patch), all launch constants; filled by
+// the launchers (wino_decode).  Plain: nnb, groups, tbx, tby.  Packed: nnb, groups, per = tbx * tby, tbx, tbxl = the patches per row
+// of a ragged last canvas row (tbx where there is none), tcw = tile columns per frame.
+struct WinoDecode { WinoRecip nnb, groups, tbx, tby, per, tbxl, tcw; };
+// of a launch on a (virtual) image W pixels wide with B frames, `pack` frames per canvas row (0: a plain launch)
+inline WinoDecode wino_decode(int Cout, int groups, int tbx, int tby, int W, int B, int pack) {
+    const int tcw = (W + 1) / 2, last = pack > 0 ? ((B % pack) * tcw + 7) / 8 : 0;
+    return WinoDecode{wino_recip(Cout / 64), wino_recip(groups), wino_recip(tbx), wino_recip(tby), wino_recip(tbx * tby),
+                      wino_recip(last ? last : tbx), wino_recip(tcw)};
+}
 
 // Winograd F(2x2,3x3) convolution (3x3, stride 1, pad 1, NHWC, Cin % 8 == 0, Cout % 64 == 0)
 struct WinoArgs {
@@ -209,6 +232,8 @@ struct WinoArgs {
     // for the kernel; tbx / tby / pack / pack_rx are wino_pack_geometry's on the swapped sizes (pack >= 1), the images were packed
     // from the transposed taps
     int orient;
+    // wino_w4.hip, wino_h2.hip, wino_h3.hip: the reciprocals of the workgroup-id decode; the launchers fill them (callers leave them zero)
+    WinoDecode dec;
 };
 int launch_conv_wino(const WinoArgs& a, int groups, hipStream_t s);
 const float* zero_page();      // 64 zero floats in the code object (per device context), or null

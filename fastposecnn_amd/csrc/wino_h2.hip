@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h2(const WinoArgs a) {
     const int H = a.H, W = a.W, Cin = a.Cin, Cout = a.Cout, HW = H * W;
     const int nkb = Cin >> 3;
     // weight slice (group, 64-channel block) fastest: fixed per XCD under round-robin dispatch (k_conv_wino)
-    const WinoPatch pt = wino_patch<false>(blockIdx.x, Cout / kBN, a.groups, a.tbx, a.tby, 0, W, a.B);
+    const WinoPatch pt = wino_patch<false>(blockIdx.x, Cout / kBN, a.groups, a.tbx, a.tby, 0, W, a.B, a.dec);
     const int nb = pt.nb, nnb = Cout / kBN;
     const ConvPtrs P = wino_group(a.p[0], a.p[1], a.p[2], a.p[3], pt.grp);
     const int y_in0 = 2 * pt.ty0 - 1, x_in0 = 2 * pt.tx0 - 1;
@@ -326,9 +326,11 @@ int launch_wino_pack_h2(const float* w_oihw, float* packed, int Cout, int Cin, h
 }
 
 // .w = the k_wino_pack_fp16<false> image (+ its tail), .waves = 8 (tby = ceil(ceil(H / 2) / 8): 8 x 8 tile patches)
-int launch_conv_wino_h2(const WinoArgs& a, int groups, hipStream_t s) {
+int launch_conv_wino_h2(const WinoArgs& a_in, int groups, hipStream_t s) {
     long long nblk;
-    if (const int rc = wino_tile_check(a, groups, 8, kStepBytes, false, &nblk)) return rc;
+    if (const int rc = wino_tile_check(a_in, groups, 8, kStepBytes, false, &nblk)) return rc;
+    WinoArgs a = a_in;      // + the reciprocals of the workgroup-id decode (wino_patch)
+    a.dec = wino_decode(a.Cout, groups, a.tbx, a.tby, a.W, a.B, 0);
 #ifdef FPC_STAMP_WINO
     static const int mode = getenv("FPC_H2_MODE") ? atoi(getenv("FPC_H2_MODE")) : 0;      // diagnostic
     if (mode == 1) hipLaunchKernelGGL(k_conv_wino_h2<1>, dim3((unsigned)nblk), dim3(256), 0, s, a);

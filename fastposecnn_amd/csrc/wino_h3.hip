@@ -80,10 +80,13 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
     const int li = lane & 31, lh = lane >> 5;
     const int H = a.H, W = a.W, Cout = a.Cout;
     const int nnb = Cout / kBN;
-    const WinoPatch pt = wino_patch<PACK>(blockIdx.x, nnb, a.groups, a.tbx, a.tby, a.pack, W, a.B);
+    const WinoPatch pt = wino_patch<PACK>(blockIdx.x, nnb, a.groups, a.tbx, a.tby, a.pack, W, a.B, a.dec);
     const int nb = pt.nb, grp = pt.grp, pk_ks = pt.pk_ks;
     const ConvPtrs P = wino_group(a.p[0], a.p[1], a.p[2], a.p[3], grp);
     const int y_in0 = 2 * pt.ty0 - 1, x_in0 = 2 * pt.tx0 - 1;
+    // (diagnostic build, FPC_WINO_SERIAL=1: a second, 16-word record per wave behind the first ones splits entry and exit, tools_dev/wino_serial_stamps.py)
+    const bool fine = kWinoStamp && dbg && a.variant == kWinoSerialStamps;
+    long long t_dec = fine ? clock64() : 0, t_wld = 0, t_plan = 0, t_zero = 0;
 
     f32x16 acc[4][2][2];      // [xi column j][tile half mt][32-channel tile nt]; zeroed while the first operands are on their way
     float inv_s = 1.f;        // 1 / (the power of two the weights of the LAST phase were scaled by)
@@ -116,6 +119,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) { FPC_H3_LOAD_U1(j, nt); FPC_H3_LOAD_U2(j, nt); }
     if (npair > 1) so_u += kPairBytes;
+    if (PH == 0) t_wld = fine ? clock64() : 0;
 
     // ---- input staging and fragment addressing (wino_tile.hpp)
     const float* isb = sgpr_ptr(src + (size_t)pt.b * (H >> up) * (W >> up) * Cs);      // image base, + 8 floats per step
@@ -125,7 +129,9 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
 #define FPC_H3_ISSUE_IN(BUF, PTR) wino_issue_in(lds + (BUF) * kInFloats, wi, ivo, imask, PTR)
     int in_a[2], in_b[2];
     const float sgn = wino_frag<PACK>(in_a, in_b, wi, li, lh, pk_ks);
+    if (PH == 0) t_plan = fine ? clock64() : 0;
     wino_zero_ring(lds, t, kRing, y_in0, x_in0, H, W, PACK && pk_ks < kTX);
+    if (PH == 0) t_zero = fine ? clock64() : 0;
     // steps 0, 1, 2 -> buffers 0, 1, 2
     FPC_H3_ISSUE_IN(0, isb);
     isb += 8;                      // (nkb >= 2)
@@ -323,8 +329,10 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
         o[0] = t_issued - t_entry; o[1] = t_landed - t_issued; o[2] = t_synced - t_landed;      // entry: set-up + issue | first operands land | barrier
         o[3] = t_kend - c_begin; o[4] = wall_clock64() - r_begin; o[5] = a.Cin >> 3; o[6] = c_begin - t_entry;
     }
+    long long* const fdbg = (!(FOLD && PACK) && fine) ? dbg + (size_t)gridDim.x * 32 + ((size_t)blockIdx.x * 4 + wi) * 16 : nullptr;
+    if (fdbg && lane == 0) { fdbg[0] = t_dec - t_entry; fdbg[1] = t_wld - t_entry; fdbg[2] = t_plan - t_entry; fdbg[3] = t_zero - t_entry; fdbg[4] = t_issued - t_entry; }
     wino_output<PACK, FOLD, TR>(lds, acc, P, pt, WinoEpi{H, W, Cout, a.relu, a.tbx, a.tby, a.pack_rx}, inv_s,
-                            wino_group(a.btab[0], a.btab[1], a.btab[2], a.btab[3], grp), dbg, t_kend, t, wi);
+                            wino_group(a.btab[0], a.btab[1], a.btab[2], a.btab[3], grp), dbg, t_kend, t, wi, fdbg);
 }
 
 // The patch geometry of one k_conv_wino_h3 launch (host arithmetic).  tcw = ceil(W / 2) tile columns per frame; G = the smallest frame
@@ -385,16 +393,18 @@ WinoPackGeom wino_launch_geometry(int H, int W, int B, int Cin, bool orient, boo
 }
 
 // .w = the k_wino_pack_fp16<true> image (+ its tail; wino_h2.hip), tby = ceil(ceil(H / 2) / 8): 8 x 8 tile patches
-int launch_conv_wino_h3(const WinoArgs& a, int groups, hipStream_t s) {
+int launch_conv_wino_h3(const WinoArgs& a_in, int groups, hipStream_t s) {
     // pairs of 8-channel K-steps; a.pack > 1: patches cut out of canvas rows of a.pack frames, the geometry must be wino_pack_geometry's own
     long long nblk;
-    if (a.orient) {
+    if (a_in.orient) {
+        const WinoArgs& a = a_in;
         // a.H x a.W is the stored image; the kernel gets the virtual one.  Always the packed decode (a.pack >= 1), images packed from
         // the transposed taps (launch_wino_pack_h3 / _pair, launch_fold_compose with transpose = true)
         WinoArgs t = a;
         std::swap(t.H, t.W);
         if (a.pack < 1 || a.dbg) return FPC_EINVAL;
         if (const int rc = wino_tile_check(t, groups, 16, kPairBytes, true, &nblk)) return rc;
+        t.dec = wino_decode(t.Cout, groups, t.tbx, t.tby, t.W, t.B, t.pack);
         if (a.fold) {
             if (const int rc = wino_fold_check(a, groups)) return rc;
             hipLaunchKernelGGL((k_conv_wino_h3<0, true, true, true>), dim3((unsigned)nblk), dim3(256), 0, s, t);
@@ -403,7 +413,9 @@ int launch_conv_wino_h3(const WinoArgs& a, int groups, hipStream_t s) {
         }
         return check_launch();
     }
-    if (const int rc = wino_tile_check(a, groups, 16, kPairBytes, a.pack > 1, &nblk)) return rc;
+    if (const int rc = wino_tile_check(a_in, groups, 16, kPairBytes, a_in.pack > 1, &nblk)) return rc;
+    WinoArgs a = a_in;      // + the reciprocals of the workgroup-id decode (wino_patch)
+    a.dec = wino_decode(a.Cout, groups, a.tbx, a.tby, a.W, a.B, a.pack > 1 ? a.pack : 0);
     if (a.pack > 1) {
         hipLaunchKernelGGL((k_conv_wino_h3<0, false, true>), dim3((unsigned)nblk), dim3(256), 0, s, a);
         return check_launch();
@@ -417,6 +429,8 @@ int launch_conv_wino_h3(const WinoArgs& a, int groups, hipStream_t s) {
     }
 #ifdef FPC_STAMP_WINO
     static const int var = getenv("FPC_H3_VAR") ? atoi(getenv("FPC_H3_VAR")) : 0;      // diagnostic
+    static const bool serial = getenv("FPC_WINO_SERIAL") && atoi(getenv("FPC_WINO_SERIAL")) != 0;      // the stamp buffer holds the 16-word records too
+    if (serial && a.dbg) a.variant = kWinoSerialStamps;
     if (var == 1) hipLaunchKernelGGL((k_conv_wino_h3<1, false, false>), dim3((unsigned)nblk), dim3(256), 0, s, a);
     else
 #endif

@@ -27,7 +27,21 @@ constexpr int kNT = kTX * kTY;                   // 64 tiles = two M halves
 constexpr int kInPieces = 18;                    // 1 KB LDS-DMA pieces of one K-step's input image (k_conv_wino's permuted image)
 constexpr int kInFloats = kInPieces * 256;       // 4608 floats per input buffer
 constexpr int kPairBytes = 16 * 2 * 2 * 64 * 16; // k_wino_pack_fp16<true>'s image of one pair of K-steps (wino_h3.hip): [xi 16][tile 2][piece 2][lane 64] x 16 bytes {4 ch of the even step, 4 ch of the odd step}
-constexpr int kLdsFloats = 4 * 2 * kNT * kBN;    // output transform image = 128 KB; the K loop's input buffers live in its space
+// The output transform image Z: per transform row i, column cc (z0 / z1), 64 tiles x 64 channels, as RUNS of 64 floats = the 64 lanes
+// of one accumulator register: run (cc, mt, r, nt) holds channels nt * 32 .. + 31 of tile mt * 32 + (r & 3) + 8 (r >> 2) and then of the
+// tile four further (wino_output).  Row i's copy of a run lies 256 bytes behind row i - 1's.  The runs of odd r live in a second
+// 64 KB region that starts HALF a 256-byte bank row late: a ds_read_b128 lane group of the output stage holds eight quads of an even
+// tile and eight of the odd tile beside it, all from the same half of their runs (lane bit 5 of the writer = tile bit 2, the same for
+// a whole reading wave) — the shift puts the odd tile's on the other 128 bytes of the bank row, 16 different 16-byte slots per group.
+constexpr int kZOdd = 64 * 1024 + 128;           // byte offset of the odd runs' region
+constexpr int z_run(int cc, int mt, int r, int nt) { return ((((cc * 2 + mt) * 8 + (r >> 1)) * 2 + nt) * 4) * 256 + (r & 1) * kZOdd; }
+// ds_write_addtid_b32 adds M0's low 16 bits and a 16-bit immediate: the even runs from M0 = image + 256 wi (immediates up to 63 KB),
+// the odd ones from that + kZOddM0 (immediates 960 .. 65 472); both fit while the image starts in the first kZM0Slack bytes of LDS
+constexpr int kZOddM0 = 64704;
+constexpr int kZM0Slack = 65535 - 3 * 256 - kZOddM0;
+static_assert(z_run(1, 1, 15, 1) - kZOddM0 < 65536 && z_run(0, 0, 1, 0) >= kZOddM0 && kZM0Slack >= 0, "ds_write_addtid_b32's reach");
+constexpr int kLdsFloats = 4 * 2 * kNT * kBN + 32;      // the Z image = 128 KB + the odd region's shift; the K loop's input buffers live in its space
+static_assert(z_run(1, 1, 15, 1) + 3 * 256 + 256 == kLdsFloats * 4, "the last run ends the image");
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0x7FFFFFFF, 0x00020000);
@@ -53,24 +67,30 @@ struct WinoPatch {
     int pk_ks, pk_raw, pk_slot;      // PACK: seam after pk_ks tile columns (99: none), tcw - tx0, this patch's GroupNorm record of frame b
     bool pk_two;                     // PACK: the frame behind the seam exists
 };
+// Every divisor is a launch constant and every quotient is taken by the launch's reciprocals (dc, WinoRecip: n / d = (n * m) >> sh,
+// exact for 0 <= n < 2^31): the decode stands in front of the first load of the kernel, where nothing hides it.
+__device__ __forceinline__ int wino_div(int n, const WinoRecip r) { return (int)(((unsigned long long)(unsigned)n * r.m) >> r.sh); }
 template <bool PACK>
-__device__ __forceinline__ WinoPatch wino_patch(int bid, int nnb, int groups, int tbx, int tby, int pack, int W, int B) {
+__device__ __forceinline__ WinoPatch wino_patch(int bid, int nnb, int groups, int tbx, int tby, int pack, int W, int B, const WinoDecode dc) {
     WinoPatch q;
     q.pk_ks = 99; q.pk_raw = 99; q.pk_slot = 0; q.pk_two = false;
-    q.nb = bid % nnb; bid /= nnb;
-    q.grp = bid % groups; bid /= groups;
+    int up = wino_div(bid, dc.nnb);
+    q.nb = bid - up * nnb; bid = up;
+    up = wino_div(bid, dc.groups);
+    q.grp = bid - up * groups; bid = up;
     if constexpr (!PACK) {
-        q.bx = bid % tbx; bid /= tbx;
-        q.by = bid % tby;
-        q.b = bid / tby;
+        up = wino_div(bid, dc.tbx);
+        q.bx = bid - up * tbx; bid = up;
+        q.b = wino_div(bid, dc.tby);
+        q.by = bid - q.b * tby;
         q.tx0 = q.bx * kTX;
     } else {
         const int G = pack, tcw = (W + 1) >> 1, per = tbx * tby;
-        const int g = bid / per, rem = bid - g * per;
+        const int g = wino_div(bid, dc.per), rem = bid - g * per;
         const int nf = min(G, B - g * G);                      // frames of this canvas row (a ragged last group has fewer,
-        const int tbxg = min(tbx, (nf * tcw + kTX - 1) / kTX); // and only the patches that reach them)
-        q.bx = rem % tbxg; q.by = rem / tbxg;
-        const int f = (kTX * q.bx) / tcw;
+        const int tbxg = min(tbx, (nf * tcw + kTX - 1) / kTX); // and only the patches that reach them: dc.tbxl's divisor)
+        q.by = wino_div(rem, tbxg == tbx ? dc.tbx : dc.tbxl); q.bx = rem - q.by * tbxg;
+        const int f = wino_div(kTX * q.bx, dc.tcw);
         q.tx0 = kTX * q.bx - f * tcw;
         q.b = g * G + f;
         q.pk_raw = tcw - q.tx0;
@@ -180,8 +200,8 @@ __device__ __forceinline__ void wino_zero_ring(float* lds, int t, int nbuf, int 
 
 // ---- output transform and epilogue of the accumulators acc[xi column j][tile half mt][32-channel tile nt].  Column part inside the
 // wave: z0 = m0 + m1 + m2, z1 = m1 - m2 - m3; row part across the four transform-row waves through LDS: y0 = z[0] + z[1] + z[2],
-// y1 = z[1] - z[2] - z[3].  Z[row][cc][tile 64][co 64], one pass.  Output stage: thread = (tile of a 16-tile pass, 16-byte channel
-// quad): within a ds_read_b128 lane group the 16 quads are 16 different bank slots; a wave stores 4 tiles x 256 contiguous bytes.
+// y1 = z[1] - z[2] - z[3].  The Z image in runs of 64 floats (z_run, above), one pass.  Output stage: thread = (tile of a 16-tile pass,
+// 16-byte channel quad): within a ds_read_b128 lane group the 16 quads are 16 different bank slots; a wave stores 4 tiles x 256 contiguous bytes.
 // out = relu(inv_s * y [+ btab by border class] [* scale] + shift [+ res]); GroupNorm records of the stored values.  No staging may
 // be in flight.  Ends with the stamp record's last word (tools_dev/wino_stamps.py).
 // FOLD: the bias table and nothing else (launch_conv_wino_h3 refuses scale, shift, residual and ReLU with a fold): the 64 registers of
@@ -192,10 +212,12 @@ __device__ __forceinline__ void wino_zero_ring(float* lds, int t, int nbuf, int 
 // TR: y, x, H, W below are the virtual image's (wino_stage_plan); the output and the residual are stored images: pixel (x, y), rows
 // of H pixels.  (The fold's border classes are the virtual image's too: k_fold_compose wrote the table for the transposed taps.)
 struct WinoEpi { int H, W, Cout, relu, tbx, tby, pack_rx; };
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"      // (the Z stores name m0 as clobbered)
 template <bool PACK, bool FOLD, bool TR = false>
 __device__ __forceinline__ void wino_output(float* lds, const f32x16 (&acc)[4][2][2], const ConvPtrs P, const WinoPatch pt, const WinoEpi e,
                                             const float inv_s, const float* btab, long long* dbg, const long long t_kend, const int t,
-                                            const int wi) {
+                                            const int wi, long long* fdbg = nullptr) {
     const int H = e.H, W = e.W, Cout = e.Cout, HW = H * W;
     // (PACK: the thread's indices are rebuilt from the lane counter here instead of being carried over the K loop: the packed
     // set-up needs a few registers more, and the allocator otherwise parks these in scratch from the set-up to the epilogue)
@@ -222,30 +244,61 @@ __device__ __forceinline__ void wino_output(float* lds, const f32x16 (&acc)[4][2
                                                              : f32x4{0.f, 0.f, 0.f, 0.f};
         }
     __syncthreads();
-    float* const zb = lds + ((wi * 2) * kNT + 4 * (lane >> 5)) * kBN + (lane & 31);
+    // (fdbg: the exit's phases in a diagnostic build, ticks since the K loop's end: words 8 .. 12 of the wave's 16-word record)
+    if (kWinoStamp && fdbg && (t & 63) == 0) fdbg[8] = clock64() - t_kend;      // first barrier passed
+    // Z stores: accumulator register r of (mt, nt) holds, over the wave's 64 lanes, channels nt * 32 + (lane & 31) of tile rows
+    // (r & 3) + 8 (r >> 2) + 4 (lane >> 5) — one RUN of 64 floats per (row wi, cc, mt, r, nt) in lane order, which is what
+    // ds_write_addtid_b32 stores (address = M0 + immediate + 4 lane, no address or base register, twice ds_write_b32's rate).  Run at
+    // byte z_run(cc, mt, r, nt) + 256 wi; M0 = the wave's base (16 bits) + an immediate below 64 KB reach every run from two bases.
+    // (The image is the kernels' only LDS object: it starts at LDS address 0.)
+    {
+        const unsigned zm0 = lds_addr(lds) + wi * 256;
 #pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
+        for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
+            for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                // one base register per lane + a compile-time offset (< 64 KB: the instruction's immediate) per store
-                const int mc = mt * 32 + (r & 3) + 8 * (r >> 2);
-                const float m0 = acc[0][mt][nt][r], m1 = acc[1][mt][nt][r], m2 = acc[2][mt][nt][r], m3 = acc[3][mt][nt][r];
-                zb[(0 * kNT + mc) * kBN + nt * 32] = m0 + m1 + m2;
-                zb[(1 * kNT + mc) * kBN + nt * 32] = m1 - m2 - m3;
-            }
+                for (int cc = 0; cc < 2; ++cc)
+#pragma unroll
+                    for (int odd = 0; odd < 2; ++odd) {
+                        float z[8];
+#pragma unroll
+                        for (int h = 0; h < 8; ++h) {
+                            const int r = 2 * h + odd;
+                            const float m0 = acc[0][mt][nt][r], m1 = acc[1][mt][nt][r], m2 = acc[2][mt][nt][r], m3 = acc[3][mt][nt][r];
+                            z[h] = cc == 0 ? m0 + m1 + m2 : m1 - m2 - m3;
+                        }
+#define FPC_Z_IMM(H) "i"(z_run(cc, mt, 2 * (H) + odd, nt) - odd * kZOddM0)
+                        asm volatile("s_mov_b32 m0, %8\n s_nop 0\n"
+                                     "ds_write_addtid_b32 %0 offset:%9\n ds_write_addtid_b32 %1 offset:%10\n"
+                                     "ds_write_addtid_b32 %2 offset:%11\n ds_write_addtid_b32 %3 offset:%12\n"
+                                     "ds_write_addtid_b32 %4 offset:%13\n ds_write_addtid_b32 %5 offset:%14\n"
+                                     "ds_write_addtid_b32 %6 offset:%15\n ds_write_addtid_b32 %7 offset:%16\n"
+                                     :: "v"(z[0]), "v"(z[1]), "v"(z[2]), "v"(z[3]), "v"(z[4]), "v"(z[5]), "v"(z[6]), "v"(z[7]),
+                                        "s"(zm0 + odd * kZOddM0), FPC_Z_IMM(0), FPC_Z_IMM(1), FPC_Z_IMM(2), FPC_Z_IMM(3), FPC_Z_IMM(4),
+                                        FPC_Z_IMM(5), FPC_Z_IMM(6), FPC_Z_IMM(7)
+                                     : "memory", "m0");
+#undef FPC_Z_IMM
+                    }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (the compiler does not count an asm statement's stores)
+    }
+    if (kWinoStamp && fdbg && (t & 63) == 0) fdbg[9] = clock64() - t_kend;       // Z stores done
     __syncthreads();
+    if (kWinoStamp && fdbg && (t & 63) == 0) fdbg[10] = clock64() - t_kend;      // barrier
     f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
+    // this thread's quad of its tile of pass 0, row 0, cc 0
+    const float* const zr = lds + z_run(0, 0, (otl & 3) + 4 * (otl >> 3), oq >> 3) / 4 +
+                            ((otl >> 2) & 1) * 32 + (oq & 7) * 4;
 #pragma unroll
     for (int tp = 0; tp < 4; ++tp) {
         const int ot = otl + 16 * tp;
         const int oty = pt.ty0 + (ot >> 3);
         f32x4 z[4][2];
+        // tile ot = otl + 16 tp of the Z image: mt = tp >> 1, r = (otl & 3) + 4 ((otl >> 3) + 2 (tp & 1)), writer half (otl >> 2) & 1
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int cc = 0; cc < 2; ++cc) z[i][cc] = *reinterpret_cast<const f32x4*>(lds + ((i * 2 + cc) * kNT + ot) * kBN + oq * 4);
+            for (int cc = 0; cc < 2; ++cc) z[i][cc] = *reinterpret_cast<const f32x4*>(zr + (z_run(cc, tp >> 1, 8 * (tp & 1), 0) + 256 * i) / 4);
 #pragma unroll
         for (int rr = 0; rr < 2; ++rr)
 #pragma unroll
@@ -267,6 +320,7 @@ __device__ __forceinline__ void wino_output(float* lds, const f32x16 (&acc)[4][2
                 s2 += val * val;
             }
     }
+    if (kWinoStamp && fdbg && (t & 63) == 0) fdbg[11] = clock64() - t_kend;      // reads, epilogue, last store issued
     if (PACK && P.gn_part) {
         // one record per frame this workgroup touches: two sets of sums, a thread's go to its side of the seam; the reduction is the
         // plain one on both.  Record of frame b: slot pk_slot of row by (pack_rx slots per row: the most patches a frame meets),
@@ -326,11 +380,13 @@ __device__ __forceinline__ void wino_output(float* lds, const f32x16 (&acc)[4][2
             g[0] = u1; g[1] = u2;
         }
     }
+    if (kWinoStamp && fdbg && lane == 0) fdbg[12] = clock64() - t_kend;          // record reduction
     if (kWinoStamp && dbg && lane == 0) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         dbg[((size_t)blockIdx.x * 4 + wi) * 8 + 7] = clock64() - t_kend;      // K loop end -> last store acknowledged
     }
 }
+#pragma clang diagnostic pop
 
 // ---- host side.  What every launcher of the family checks: no stamp buffer outside a diagnostic build, groups, Cin a multiple of kch (the form's channels per K-step or pair),
 // Cout of 64, 32-bit lane offsets inside one image, 31-bit buffer offsets inside one block's weight images (step_bytes per kch

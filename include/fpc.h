@@ -630,6 +630,13 @@ int fpc_net_set_wino_orient(fpc_net_t* net, int on);
 /* fpc_wino_pack_geometry under that rule (host only): out9[0] = 1 where the site runs transposed, then out9[1..8] = the out8 above of
  * the virtual image W x H (packed with or without the fold, whatever `pack`); else 0 and the plain site's out8 with packing as `pack`. */
 int fpc_wino_orient_geometry(int H, int W, int B, int Cin, int fold, int pack, int64_t* out9);
+/* The four-wave Winograd kernels decode their workgroup id by multiply-shift reciprocals of the launch's divisors, n / d =
+ * (n * m) >> sh in 64 bits for 0 <= n < 2^31 (host only).  fpc_wino_recip: out2 = {m, sh} of the divisor d, 1 <= d <= 2^31.
+ * fpc_wino_decode: what a launcher passes for a launch of `groups` groups and Cout output channels with tbx x tby patches per canvas
+ * row on a (virtual) image W pixels wide, B frames, `pack` frames per canvas row (0: a plain launch): out14 = {m, sh} of Cout / 64,
+ * groups, tbx, tby, tbx * tby, the patches per row of a ragged last canvas row (tbx where there is none), ceil(W / 2). */
+int fpc_wino_recip(uint32_t d, int64_t* out2);
+int fpc_wino_decode(int Cout, int groups, int tbx, int tby, int W, int B, int pack, int64_t* out14);
 /* Workgroups of all form-9 launches of the last forward that launched (or captured) its kernels: what the switch above changes. */
 int64_t fpc_net_wino_blocks(const fpc_net_t* net);
 /* FLOP of one forward over the batch under the current plans: out3 = {2 x MACs of the direct convolutions (what the
