@@ -221,7 +221,9 @@ __global__ __launch_bounds__(256) void k_mask_losses(const float* __restrict__ l
 #pragma unroll
         for (int c = 0; c < MAXC; ++c)
             if (c < C) se += expf(v[c] - mx);
-        const float lse = mx + logf(se);
+        // y = (x - mx) - log sum exp(x - mx), the max taken off first: x - (mx + log ..) rounds y to an ulp of the LOGIT, which
+        // at logits of some tens costs the focal term's gradient a decade of its precision (tests/test_gpu_train_kernels.py)
+        const float lg = logf(se);
         const bool ce_on = t != ignore_ce && t >= 0 && t < C, cce_on = t != ignore_cce && t >= 0 && t < C;
         const bool foc_on = t != ignore_cce;
         float gy[MAXC];
@@ -229,7 +231,7 @@ __global__ __launch_bounds__(256) void k_mask_losses(const float* __restrict__ l
 #pragma unroll
         for (int c = 0; c < MAXC; ++c)
             if (c < C) {
-                const float y = v[c] - lse;
+                const float y = (v[c] - mx) - lg;
                 const bool pos = t == c;
                 float g = 0.0f;
                 if (pos && ce_on) { acc[0] -= (double)y; g -= w0; }
@@ -249,7 +251,7 @@ __global__ __launch_bounds__(256) void k_mask_losses(const float* __restrict__ l
             float* go = grad + (size_t)b * C * HW + p;
 #pragma unroll
             for (int c = 0; c < MAXC; ++c)
-                if (c < C) go[(size_t)c * HW] = gy[c] - expf(v[c] - lse) * gsum;
+                if (c < C) go[(size_t)c * HW] = gy[c] - expf((v[c] - mx) - lg) * gsum;
         }
     }
     if (!BWD) {

@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from _train_refs import radam_lookahead_reference as _radam_lookahead_reference
+
 pytestmark = pytest.mark.gpu
 
 
@@ -158,34 +160,6 @@ def test_vote_refine_fn_matches_autograd(oracle):
     want = vr.grad
     scale = want.abs().max().item()
     assert scale > 0 and (got - want).abs().max().item() <= 2e-4 * scale
-
-
-def _radam_lookahead_reference(p, grads, lr, betas, eps, wd, k, alpha):
-    """catalyst.contrib.nn.RAdam + Lookahead (published algorithms; Liu et al. 2020, Zhang et al. 2019) in float64."""
-    p = p.clone().double()
-    m, v = torch.zeros_like(p), torch.zeros_like(p)
-    slow = None
-    b1, b2 = betas
-    for step, g in enumerate(grads, start=1):
-        g = g.double()
-        v = v * b2 + (1 - b2) * g * g
-        m = m * b1 + (1 - b1) * g
-        b2t = b2 ** step
-        sma_max = 2 / (1 - b2) - 1
-        sma = sma_max - 2 * step * b2t / (1 - b2t)
-        if wd:
-            p = p + (-wd * lr) * p
-        if sma >= 5:
-            ss = lr * math.sqrt((1 - b2t) * (sma - 4) / (sma_max - 4) * (sma - 2) / sma * sma_max / (sma_max - 2)) / (1 - b1 ** step)
-            p = p - ss * m / (v.sqrt() + eps)
-        else:
-            p = p - lr / (1 - b1 ** step) * m
-        if (step - 1) % k == 0:
-            if slow is None:
-                slow = p.clone()
-            slow = slow + (p - slow) * alpha
-            p = slow.clone()
-    return p
 
 
 def test_lookahead_radam_kernel():
