@@ -75,6 +75,7 @@ _SIGNATURES = {
     "fpc_depth_decode": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "fpc_net_create": (_i, [ctypes.c_char_p, _i, _i, _i, _i, ctypes.POINTER(_vp)]),
     "fpc_net_create_encoder": (_i, [_i, ctypes.POINTER(_i), _i, _i, _i, _i, ctypes.POINTER(_vp)]),
+    "fpc_net_create_encoder_ex": (_i, [_i, ctypes.POINTER(_i), _i, _i, _i, _i, _i, _i, ctypes.POINTER(_vp)]),
     "fpc_net_destroy": (None, [_vp]),
     "fpc_net_set_graph": (_i, [_vp, _i]),
     "fpc_net_set_split_precision": (_i, [_vp, _i]),
@@ -115,6 +116,8 @@ _SIGNATURES = {
     "fpc_conv2d_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(_i)]),
     "fpc_conv2d": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i,
                         _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "fpc_conv2d_grouped_workspace_bytes": (_sz, [_i, _i]),
+    "fpc_conv2d_grouped": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "fpc_conv2d_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "fpc_upsample_bilinear_fwd": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "fpc_upsample_bilinear_bwd_scratch_floats": (_sz, [_i, _i, _i, _i, _i]),

@@ -4,7 +4,8 @@
 //
 // The graph is the one segmentation_models_pytorch builds for FastPoseCNN
 // (encoder = ResNet BasicBlock x {2,2,2,2} or {3,4,6,3}, or Bottleneck x {3,4,6,3} / {3,4,23,3} / {3,8,36,3} whose 1x1 sites
-// may run on k_conv1x1 (pointwise.hip); four FPN decoders, merge "add";
+// may run on k_conv1x1 (pointwise.hip) and whose conv2, in the ResNeXt encoders, is a grouped 3x3 on k_conv3x3_grouped
+// (conv_grouped.hip); four FPN decoders, merge "add";
 // four 1x1 heads + x4 bilinear), see fastposecnn_amd/lib/backbone.py.  The plan owns no device
 // memory: packed weights, activations and split-K scratch live in one caller-provided workspace.
 // Launch order per frame (R18): stem conv, max-pool, 16 encoder convs (+3 downsample 1x1) with
@@ -39,6 +40,8 @@ struct PackedConv {
     size_t h3_off = 0;       // k_pack_weight_h3's image (h3_ok sites only)
     bool h3_ok = false;      // a candidate of k_conv_igemm's three-product form: the direct sites of ResNet-18/34 plans that do not
                              // run on Winograd — the stride-2 3x3 and 1x1 convolutions and the p5 / p4 / p3 laterals
+    int cg = 0;              // > 0: a grouped 3x3 site (conv_grouped.hip) of Cin = Cout channels in groups of cg; K = 9 cg.  It has
+    size_t grp_off = 0;      // k_pack_grouped's image only (no implicit-GEMM, Winograd or h3 image)
 };
 
 struct Act { size_t off = 0; int H = 0, W = 0, C = 0; };
@@ -51,6 +54,7 @@ struct ConvPlan {
     int fold = 0;            // s2.0 with wino 9 only: the FPN p2 level folded into the launch (wino_h3.hip, FOLD); no p2 lateral runs
     int h3 = 0;              // k_conv_igemm on two fp16 pieces, three piece products (ConvArgs::h3; PackedConv::h3_ok sites)
     int pool = 0;            // the stem site only (with stem > 0): k_stem_pool_h3 writes the pooled tensor, no stem output, no max-pool launch
+    int grp = 0;             // > 0: k_conv3x3_grouped (conv_grouped.hip), form grp - 1; the only plans of a PackedConv::cg site
 };
 
 // the 7x7 / stride-2 / pad-3 stem in its row-per-K-step layout (NHWC4 image, 8 taps x 4 channels per kernel row, K = 224) with a
@@ -218,9 +222,10 @@ static WinoGrid wino_grid(int form, int H, int W) { return {cdiv(cdiv(W, 2), 8),
 
 // ---- the integer a plan is reported by (fpc_net_conv_plan's out5[2]) and requested by (fpc_conv2d's `nsplit`): fpc.h, FPC_PLAN_*.
 // What a request asks for (nsplit: the split-K factor, 0 = the planner's, or -form; wino: the form or 0):
-struct Conv2dRequest { int nsplit; bool bf3, two_launch; int wino, lat; bool stem; int pw; bool h3, pool, pack, orient; };
+struct Conv2dRequest { int nsplit; bool bf3, two_launch; int wino, lat; bool stem; int pw; bool h3, pool, pack, orient; int grp; };
 static Conv2dRequest decode_plan(int code) {
-    Conv2dRequest r{code, false, false, 0, 0, false, 0, false, false, false, false};
+    Conv2dRequest r{code, false, false, 0, 0, false, 0, false, false, false, false, 0};
+    if (code >= FPC_PLAN_GROUPED && code < FPC_PLAN_GROUPED + 1000) { r.grp = code - FPC_PLAN_GROUPED + 1; r.nsplit = 1; return r; }      // + form = k_conv3x3_grouped (fpc_conv2d_grouped's request; fpc_conv2d has no groups and refuses it)
     if (code == FPC_PLAN_WINO_ORIENT) { r.orient = true; r.nsplit = -kWinoH3; }      // form -9 in the orientation its shape asks for (wino_orient_rule), transposed sites packed along y
     if (code == FPC_PLAN_WINO_PACKED) { r.pack = true; r.nsplit = -kWinoH3; }      // form -9 with its patches cut out of canvas rows of several frames (wino_pack_geometry)
     if (r.nsplit >= FPC_PLAN_LATERAL_H3 && r.nsplit < FPC_PLAN_LATERAL_H3 + 1000) { r.lat = r.nsplit - FPC_PLAN_LATERAL_H3; r.h3 = true; r.nsplit = 1; return r; }      // + parts = k_lateral1x1 on two fp16 pieces
@@ -237,6 +242,7 @@ static Conv2dRequest decode_plan(int code) {
 // What a plan reports; folded_away: the p2 lateral site while s2.0 runs with that level folded in (never a request)
 static int encode_plan(const ConvPlan& p, bool folded_away) {
     if (folded_away) return FPC_PLAN_FOLDED;
+    if (p.grp) return FPC_PLAN_GROUPED + p.grp - 1;
     // the three-product form: k_conv_igemm + split (fused or not, as the plain tilings), k_lateral1x1 + parts
     if (p.h3) return p.lat ? FPC_PLAN_LATERAL_H3 + p.lat : FPC_PLAN_H3 + p.nsplit;
     if (p.pw) return FPC_PLAN_POINTWISE + p.pw - 1;
@@ -253,6 +259,7 @@ struct fpc_net {
     int layers[4];
     int classes, B, H, W;
     int expansion = 1;            // 1: BasicBlock encoder, 4: Bottleneck (1x1, 3x3 with the stride, 1x1 x 4)
+    int groups = 1, width = 64;   // Bottleneck: conv2's groups and torchvision's width_per_group (ResNeXt: 32 and 4 / 8); (1, 64) = ResNet
     std::vector<std::string> pnames;
     std::vector<int64_t> pnumel;
     std::vector<const float*> pptr;
@@ -345,6 +352,22 @@ struct fpc_net {
         convs.push_back(c);
         return (int)convs.size() - 1;
     }
+    // a grouped 3x3 / pad-1 site of C channels in groups of cg, with BatchNorm: its packed image is k_pack_grouped's alone
+    int add_grouped_conv(const std::string& wname, int C, int cg, int stride, const char* bn_prefix) {
+        PackedConv c;
+        c.Cin = c.Cinp = c.Cout = C; c.Kh = c.Kw = c.Kwp = 3; c.stride = stride; c.pad = 1; c.cg = cg;
+        c.K = cg * 9; c.Kpad = cdiv(c.K, kConvBK) * kConvBK; c.Npad = cdiv(C, kConvNAlign) * kConvNAlign;
+        c.p_w = add_param(wname, (int64_t)C * cg * 9);
+        std::string p(bn_prefix);
+        c.p_bn = add_param(p + ".weight", C);
+        add_param(p + ".bias", C);
+        add_param(p + ".running_mean", C);
+        add_param(p + ".running_var", C);
+        c.grp_off = alloc((size_t)C * cg * 9);
+        c.scale_off = alloc(C); c.shift_off = alloc(C);
+        convs.push_back(c);
+        return (int)convs.size() - 1;
+    }
 };
 
 // the recorded graph no longer matches the plans, the parameters or the launch geometry
@@ -361,22 +384,42 @@ static int conv_out(int x, int k, int s, int p) { return (x + 2 * p - k) / s + 1
 static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** out);
 
 extern "C" int fpc_net_create(const char* encoder, int classes, int B, int H, int W, fpc_net_t** out) {
-    const int r18[4] = {2, 2, 2, 2}, r34[4] = {3, 4, 6, 3};
-    if (!encoder || (strcmp(encoder, "resnet18") && strcmp(encoder, "resnet34"))) return FPC_EINVAL;
+    const int r18[4] = {2, 2, 2, 2}, r34[4] = {3, 4, 6, 3}, r101[4] = {3, 4, 23, 3};
+    if (!encoder) return FPC_EINVAL;
+    // the ResNeXt encoders: Bottleneck x {3,4,6,3} / {3,4,23,3} with 32 groups of width 4 (8) on conv2
+    if (!strcmp(encoder, "resnext50_32x4d")) return fpc_net_create_encoder_ex(4, r34, 32, 4, classes, B, H, W, out);
+    if (!strcmp(encoder, "resnext101_32x4d")) return fpc_net_create_encoder_ex(4, r101, 32, 4, classes, B, H, W, out);
+    if (!strcmp(encoder, "resnext101_32x8d")) return fpc_net_create_encoder_ex(4, r101, 32, 8, classes, B, H, W, out);
+    if (strcmp(encoder, "resnet18") && strcmp(encoder, "resnet34")) return FPC_EINVAL;
     return fpc_net_create_encoder(1, strcmp(encoder, "resnet18") ? r34 : r18, classes, B, H, W, out);
 }
 
 // An encoder by its descriptor: block 1 = BasicBlock, 4 = Bottleneck (torchvision's: the stride on the 3x3), layers4 = blocks per
 // stage.  (1, {2,2,2,2}) and (1, {3,4,6,3}) are the plans fpc_net_create builds for "resnet18" / "resnet34".
 extern "C" int fpc_net_create_encoder(int block, const int* layers4, int classes, int B, int H, int W, fpc_net_t** out) {
+    return fpc_net_create_encoder_ex(block, layers4, 1, 64, classes, B, H, W, out);
+}
+
+// ... with torchvision's `groups` and `width_per_group`: a Bottleneck's conv2 is then a grouped 3x3 of planes * width / 64 * groups
+// channels (k_conv3x3_grouped) between 1x1 sites of that width; (groups, width) = (1, 64) is fpc_net_create_encoder.  Refused:
+// groups > 1 on BasicBlock, a width other than 64 without groups, channels per group outside k_conv3x3_grouped's set at any stage.
+extern "C" int fpc_net_create_encoder_ex(int block, const int* layers4, int groups, int width_per_group, int classes, int B, int H,
+                                         int W, fpc_net_t** out) {
     if (!layers4 || !out || (block != 1 && block != 4) || classes < 2 || classes > 8 || B < 1 || H < 32 || W < 32 || H % 32 ||
         W % 32)
         return FPC_EINVAL;
     for (int L = 0; L < 4; ++L)
         if (layers4[L] < 1 || layers4[L] > 64) return FPC_EINVAL;
+    if (groups < 1 || width_per_group < 1 || (groups == 1 && width_per_group != 64) || (groups > 1 && block != 4)) return FPC_EINVAL;
+    if (groups > 1)
+        for (int planes = 64; planes <= 512; planes *= 2) {
+            const int cg = planes * width_per_group / 64;      // torchvision: width = int(planes * base_width / 64) * groups
+            if (!grouped_cg_ok(cg) || (long long)cg * groups > 8192 || (cg * groups) % 64) return FPC_EINVAL;
+        }
     fpc_net* n = new fpc_net();
     memcpy(n->layers, layers4, sizeof(n->layers));
     n->expansion = block;
+    n->groups = groups; n->width = width_per_group;
     return net_build(n, classes, B, H, W, out);
 }
 
@@ -401,9 +444,11 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
             std::string p(buf);
             if (e == 4) {      // Bottleneck: 1x1 -> 3x3 (stride) -> 1x1 x 4, torchvision's parameter order
                 const int C = 4 * planes[L];
-                blk.conv1 = n->add_conv(p + ".conv1.weight", inpl, planes[L], 1, 1, 0, (p + ".bn1").c_str(), nullptr);
-                blk.conv2 = n->add_conv(p + ".conv2.weight", planes[L], planes[L], 3, stride, 1, (p + ".bn2").c_str(), nullptr);
-                blk.conv3 = n->add_conv(p + ".conv3.weight", planes[L], C, 1, 1, 0, (p + ".bn3").c_str(), nullptr);
+                const int mid = planes[L] * n->width / 64 * n->groups;      // ResNet: planes[L]
+                blk.conv1 = n->add_conv(p + ".conv1.weight", inpl, mid, 1, 1, 0, (p + ".bn1").c_str(), nullptr);
+                blk.conv2 = n->groups > 1 ? n->add_grouped_conv(p + ".conv2.weight", mid, mid / n->groups, stride, (p + ".bn2").c_str())
+                                          : n->add_conv(p + ".conv2.weight", mid, mid, 3, stride, 1, (p + ".bn2").c_str(), nullptr);
+                blk.conv3 = n->add_conv(p + ".conv3.weight", mid, C, 1, 1, 0, (p + ".bn3").c_str(), nullptr);
                 blk.ds = -1;
                 if (stride != 1 || inpl != C)
                     blk.ds = n->add_conv(p + ".downsample.0.weight", inpl, C, 1, stride, 0, (p + ".downsample.1").c_str(), nullptr);
@@ -493,7 +538,8 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
                 // input resolution, is the largest), conv2's, the downsample's and two outputs in turn (a block reads its
                 // predecessor's as input and residual); the last block's is the stage's feature map
                 const int C = 4 * planes[L];
-                const Act t1 = n->alloc_act(hin, win, planes[L]), t2 = n->alloc_act(h, w, planes[L]);
+                const int mid = planes[L] * n->width / 64 * n->groups;
+                const Act t1 = n->alloc_act(hin, win, mid), t2 = n->alloc_act(h, w, mid);
                 const Act y[2] = {n->alloc_act(h, w, C), n->alloc_act(h, w, C)};
                 const Act dd = n->alloc_act(h, w, C);
                 for (int bi = 0; bi < n->layers[L]; ++bi) {
@@ -543,6 +589,7 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
     auto plan = [&](int ci, int HoWo, int groups) {
         const PackedConv& c = n->convs[ci];
         n->c_howo[ci] = HoWo; n->c_groups[ci] = groups;
+        if (c.cg) { ConvPlan q; q.grp = 1; n->cplan[ci] = q; return; }      // a grouped site: k_conv3x3_grouped's form 0, no split-K scratch
         n->cplan[ci] = plan_conv(HoWo, B, c.Cout, c.Kpad / kConvBK, groups);
         size_t need = splitk_floats_for(n->cplan[ci], groups, B, c.Npad);
         for (const ConvPlan& q : conv_candidates(HoWo, B, c.Cout, c.Kpad / kConvBK, groups)) {
@@ -700,6 +747,13 @@ extern "C" int fpc_net_load_params(fpc_net_t* n, const float* const* params, int
     if (hipMemsetAsync(n->ws + n->tickets_off, 0, kConvTickets * sizeof(int), s) != hipSuccess) return FPC_ELAUNCH;
     for (size_t ci = 0; ci < n->convs.size(); ++ci) {
         const PackedConv& c = n->convs[ci];
+        if (c.cg) {      // a grouped site: its own image and the folded BatchNorm
+            int rg = launch_pack_grouped(n->pptr[c.p_w], n->ws + c.grp_off, c.Cout, c.cg, s);
+            if (!rg) rg = launch_fold_bn(n->pptr[c.p_bn], n->pptr[c.p_bn + 1], n->pptr[c.p_bn + 2], n->pptr[c.p_bn + 3], 1e-5f, c.Cout,
+                                         n->ws + c.scale_off, n->ws + c.shift_off, s);
+            if (rg) return rg;
+            continue;
+        }
         int rc = launch_pack_weight(n->pptr[c.p_w], n->ws + c.w_off, c.Cout, c.Cin, c.Cinp, c.Kh, c.Kw, c.Kwp, c.Npad, c.Kpad, s);
         if (rc) return rc;
         rc = launch_pack_weight_bf3(n->pptr[c.p_w], n->ws + c.w_off, c.Cout, c.Cin, c.Cinp, c.Kh, c.Kw, c.Kwp, c.Npad, c.Kpad, s);
@@ -755,6 +809,18 @@ void fill_conv_args(const fpc_net* n, ConvArgs& a, const PackedConv& c, const Co
 }
 
 int launch_conv_plan(ConvArgs& a, const ConvPlan& p, int groups, hipStream_t s) {
+    if (p.grp || a.cg) {      // a grouped site runs on k_conv3x3_grouped and on nothing else
+        if (!p.grp || p.grp > kGroupedForms || !a.cg || !a.grp_w || groups != 1 || a.in_sc != 1 || a.Kh != 3 || a.pad != 1 ||
+            a.Cin != a.Cout || a.p[0].res || a.p[0].up || a.p[0].gn_part)
+            return FPC_EINVAL;
+        GroupedArgs g;
+        memset(&g, 0, sizeof(g));
+        g.in = a.p[0].in; g.w = a.grp_w; g.out = a.p[0].out; g.scale = a.p[0].scale; g.shift = a.p[0].shift;
+        g.in_sb = a.in_sb; g.in_sh = a.in_sh; g.in_sw = a.in_sw;
+        g.B = a.B; g.Hi = a.Hi; g.Wi = a.Wi; g.Ho = a.Ho; g.Wo = a.Wo; g.C = a.Cout; g.CG = a.cg; g.stride = a.stride; g.relu = a.relu;
+        g.form = p.grp - 1;
+        return launch_conv3x3_grouped(g, s);
+    }
     if (p.stem) {
         if (groups != 1 || !stem_ok(a)) return FPC_EINVAL;
         StemArgs t;
@@ -883,6 +949,11 @@ template <class F> float min_ms(hipStream_t s, int reps, F run) {
 // The plans the autotuner times for the site `a` describes, in the order it times them (the first of equal scores is kept):
 // `split` = the plan's split-precision level, `expansion` = its encoder's block kind.
 std::vector<ConvPlan> tune_candidates(const ConvArgs& a, int groups, int split, int expansion) {
+    if (a.cg) {      // a grouped site: the forms of k_conv3x3_grouped that are built
+        std::vector<ConvPlan> gc;
+        for (int f = 0; f < kGroupedForms; ++f) { ConvPlan q; q.grp = f + 1; gc.push_back(q); }
+        return gc;
+    }
     std::vector<ConvPlan> cands = conv_candidates(a.Ho * a.Wo, a.B, a.Cout, a.ksteps, groups);
     const size_t nf = cands.size();
     if (split && a.generic == 0) {          // the same tilings with split-precision matrix products
@@ -925,7 +996,8 @@ std::vector<ConvPlan> tune_candidates(const ConvArgs& a, int groups, int split, 
 struct PlanFootprint { double nblk, share; };
 PlanFootprint plan_footprint(const ConvPlan& q, const ConvArgs& a, int groups) {
     bool tr;
-    double nblk = q.stem ? 512.0      // (a persistent 512-thread, 86 KB workgroup per CU: the whole chip, whatever its grid)
+    double nblk = q.grp ? (double)cdiv(a.Ho, 8) * cdiv(a.Wo, grouped_tile_cols(a.stride)) * (a.Cout / 32) * a.B
+                  : q.stem ? 512.0      // (a persistent 512-thread, 86 KB workgroup per CU: the whole chip, whatever its grid)
                   : q.lat ? (double)cdiv(a.Ho * a.Wo, 128) * a.B * q.lat
                   : q.pw ? (double)cdiv(a.B * a.Ho * a.Wo, pw_tile_pixels(q.pw - 1)) * (a.Cout / 64) * groups * q.pw      // (8-wave workgroups count twice)
                   : q.wino == kWinoH3 ? (double)wino_launch_geometry(a.Ho, a.Wo, a.B, a.Cin, a.wino_orient, a.wino_pack && !q.fold, &tr).patches * (a.Cout / 64) * groups
@@ -1076,6 +1148,7 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
         a.p[0] = ConvPtrs{ws + in.off, ws + c.w_off, ws + out.off, ws + c.scale_off, ws + c.shift_off, res, nullptr, nullptr};
         if (c.wino_ok) a.wino_w[0] = ws + c.wino_off;
         if (c.h3_ok && n->h3_packed) a.h3_w[0] = ws + c.h3_off;
+        if (c.cg) { a.cg = c.cg; a.grp_w = ws + c.grp_off; }
         return run_conv(n, a, 1, ci, s);
     };
     Act cur = n->a_pool;
@@ -1413,6 +1486,7 @@ extern "C" int fpc_net_conv_plan(const fpc_net_t* n, int i, int* out5) {
     if (p.lat) { out5[0] = 128; out5[1] = 32; }      // k_lateral1x1
     if (p.stem) { out5[0] = 64; out5[1] = 64; }      // k_stem7x7 / k_stem_pool_h3 (with the max-pool)
     if (p.pw) { out5[0] = pw_tile_pixels(p.pw - 1); out5[1] = 64; }      // k_conv1x1
+    if (p.grp) { out5[0] = 8 * grouped_tile_cols(n->convs[i].stride); out5[1] = 32; }      // k_conv3x3_grouped
     out5[2] = encode_plan(p, n->fold_ok && i == n->dec[0].lat[3] && n->cplan[n->dec[0].seg[6]].fold);
     out5[3] = n->convs[i].Cout; out5[4] = n->convs[i].K;
     return FPC_OK;
@@ -1522,7 +1596,7 @@ extern "C" int fpc_net_copy_plans(fpc_net_t* dst, const fpc_net_t* src) {
     for (size_t i = 0; i < dst->convs.size(); ++i) {
         const PackedConv &a = dst->convs[i], &b = src->convs[i];
         if (a.Cin != b.Cin || a.Cout != b.Cout || a.Kh != b.Kh || a.Kw != b.Kw || a.stride != b.stride || a.Npad != b.Npad ||
-            a.Kpad != b.Kpad || dst->c_groups[i] != src->c_groups[i])
+            a.Kpad != b.Kpad || a.cg != b.cg || dst->c_groups[i] != src->c_groups[i])
             return FPC_EINVAL;
     }
     for (size_t i = 0; i < dst->convs.size(); ++i) {
@@ -1557,7 +1631,7 @@ extern "C" int fpc_net_flops(const fpc_net_t* n, double* out3) {
     for (size_t i = 0; i < n->convs.size(); ++i) {
         if (!n->c_groups[i]) continue;
         const PackedConv& c = n->convs[i];
-        const double f = 2.0 * n->B * (double)n->c_howo[i] * c.Cout * c.Cin * c.Kh * c.Kw * n->c_groups[i];
+        const double f = 2.0 * n->B * (double)n->c_howo[i] * c.Cout * (c.cg ? c.cg : c.Cin) * c.Kh * c.Kw * n->c_groups[i];
         direct += f;
         if (n->cplan[i].wino) { executed += f / 2.25; wino += f; } else executed += f;
     }
@@ -1715,6 +1789,7 @@ extern "C" int fpc_conv2d(const float* in, int64_t sb, int64_t sh, int64_t sw, i
     int Ho = conv_out(Hi, Kh, stride, pad), Wo = conv_out(Wi, Kw, stride, pad);
     if (Ho < 1 || Wo < 1) return FPC_EINVAL;
     const Conv2dRequest rq = decode_plan(nsplit);
+    if (rq.grp) return FPC_EINVAL;      // this entry has no groups: fpc_conv2d_grouped
     const int wino = rq.wino;
     ConvPlan p = conv2d_plan_for(B, Ho, Wo, Cin, Cout, Kh, Kw, bm, bn, rq);
     const Conv2dLayout lay = conv2d_layout(B, Cin, Cout, Kh, Kw, p, rq);
@@ -1796,4 +1871,34 @@ extern "C" int fpc_conv2d(const float* in, int64_t sb, int64_t sh, int64_t sw, i
     if (p.bf3 && mode != 0) return FPC_EINVAL;
     if (p.lat || p.pw) return launch_conv_plan(a, p, 1, s);
     return run_conv(nullptr, a, 1, 0, s);
+}
+
+// ---- stand-alone grouped 3x3 convolution (unit tests / micro-benchmarks of k_conv3x3_grouped) -----------------
+// workspace: k_pack_grouped's image, C * (C / groups) * 9 floats (0: a shape fpc_conv2d_grouped refuses)
+extern "C" size_t fpc_conv2d_grouped_workspace_bytes(int C, int groups) {
+    if (C < 32 || C % 32 || groups < 1 || C % groups || !grouped_cg_ok(C / groups)) return 0;
+    return std::max<size_t>(align_up((size_t)C * (C / groups) * 9 * sizeof(float), 256), 256);
+}
+
+extern "C" int fpc_conv2d_grouped(const float* in, int64_t sb, int64_t sh, int64_t sw, int64_t sc, const float* w_oihw,
+                                  const float* scale, const float* shift, float* out, int B, int Hi, int Wi, int C, int groups,
+                                  int stride, int relu, int form, void* ws, size_t ws_bytes, fpc_stream_t stream) {
+    if (!in || !w_oihw || !out || !ws || B < 1 || Hi < 1 || Wi < 1 || C < 32 || C % 32 || groups < 1 || C % groups ||
+        !grouped_cg_ok(C / groups) || (stride != 1 && stride != 2) || sc != 1 || form < 0 || form >= 1000)
+        return FPC_EINVAL;
+    const Conv2dRequest rq = decode_plan(FPC_PLAN_GROUPED + form);
+    if (!rq.grp || rq.grp > kGroupedForms) return FPC_EINVAL;
+    if (ws_bytes < fpc_conv2d_grouped_workspace_bytes(C, groups) || ((uintptr_t)ws & 255)) return FPC_EWORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    GroupedArgs g;
+    memset(&g, 0, sizeof(g));
+    g.in = in; g.w = (const float*)ws; g.out = out; g.scale = scale; g.shift = shift;
+    g.in_sb = sb; g.in_sh = sh; g.in_sw = sw;
+    g.B = B; g.Hi = Hi; g.Wi = Wi; g.Ho = conv_out(Hi, 3, stride, 1); g.Wo = conv_out(Wi, 3, stride, 1);
+    g.C = C; g.CG = C / groups; g.stride = stride; g.relu = relu ? 1 : 0; g.form = rq.grp - 1;
+    // (every refusal of the launcher is tested here first, on a null stream-free path: nothing is packed for a refused request)
+    if (((uintptr_t)in | (uintptr_t)out | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)w_oihw) & 15) return FPC_EINVAL;
+    if ((sb | sh | sw) % 4 || sw < C) return FPC_EINVAL;
+    FPC_TRY(launch_pack_grouped(w_oihw, (float*)ws, C, g.CG, s));
+    return launch_conv3x3_grouped(g, s);
 }

@@ -55,6 +55,8 @@ struct ConvArgs {
     long long wino_blocks;            // host side only, written by a form-9 launch: its workgroups
     int wino_pack;                    // host side only: a form-9 launch may use the packed patch geometry (wino_pack_geometry)
     int wino_orient;                  // host side only: a form-9 launch runs transposed where wino_orient_rule says so (wino_launch_geometry)
+    int cg;                           // host side only: > 0 = a grouped 3x3 site of Cin = Cout channels in groups of cg (conv_grouped.hip) ...
+    const float* grp_w;               // ... and its k_pack_grouped image
 };
 
 // FPN lateral 1x1 convolutions of all decoders as one pixel-resident product (lateral.hip): K = Cin in {64, 128}
@@ -89,6 +91,25 @@ struct PwArgs {
 };
 int launch_conv1x1(const PwArgs& a, hipStream_t s);
 inline int pw_tile_pixels(int variant) { return variant == 0 ? 64 : 128; }
+
+// grouped 3x3 / pad-1 convolution of the ResNeXt encoders (conv_grouped.hip, k_conv3x3_grouped): C channels in and out,
+// C / CG groups of CG channels, CG in {4, 8, 16, 32, 64}, C a multiple of 32, stride 1 or 2, plain f32 products (form 0)
+struct GroupedArgs {
+    const float* in;             // pixel (b, y, x): in + b in_sb + y in_sh + x in_sw, its C channels contiguous
+    const float* w;              // k_pack_grouped's image (C * CG * 9 floats)
+    float* out;                  // [B][Ho][Wo][C]
+    const float* scale;          // folded BatchNorm multiplier or null
+    const float* shift;          // folded BatchNorm addend or null
+    long long in_sb, in_sh, in_sw;
+    int B, Hi, Wi, Ho, Wo, C, CG, stride, relu;
+    int form;                    // 0: the only form built
+    int tx, ty;                  // tile columns / rows per frame: the launcher fills them
+};
+constexpr int kGroupedForms = 1;
+bool grouped_cg_ok(int cg);
+int launch_pack_grouped(const float* w_oihw, float* packed, int C, int CG, hipStream_t s);
+int launch_conv3x3_grouped(const GroupedArgs& a, hipStream_t s);
+inline int grouped_tile_cols(int stride) { return stride == 1 ? 16 : 8; }      // x 8 rows x 32 channels per workgroup
 
 // the 7x7 / stride-2 / pad-3 stem on the NHWC4 image as a weight-resident product (stem.hip)
 struct StemArgs {

@@ -26,7 +26,11 @@ class NetEngine:
         h = ctypes.c_void_p()
         from fastposecnn_amd.lib import backbone
         block, layers = backbone.encoder_layout(model.encoder.name)
-        if block == 1:      # the named nets, as always
+        groups, width = backbone.encoder_groups(model.encoder.name)
+        if groups > 1:      # ResNeXt: Bottleneck with a grouped conv2
+            nat.check(L.fpc_net_create_encoder_ex(block, (ctypes.c_int * 4)(*layers), groups, width, self.classes, B, H, W,
+                                                  ctypes.byref(h)), "fpc_net_create_encoder_ex")
+        elif block == 1:    # the named nets, as always
             nat.check(L.fpc_net_create(model.encoder.name.encode(), self.classes, B, H, W, ctypes.byref(h)), "fpc_net_create")
         else:               # Bottleneck encoders by their descriptor
             nat.check(L.fpc_net_create_encoder(block, (ctypes.c_int * 4)(*layers), self.classes, B, H, W, ctypes.byref(h)),

@@ -30,11 +30,11 @@ class Conv2d(nn.Conv2d):
     state_dict names as nn.Conv2d."""
 
     def forward(self, x):
-        if self.training and x.is_cuda and self.groups == 1 and self.dilation == (1, 1) and self.padding_mode == "zeros" \
+        if self.training and x.is_cuda and self.dilation == (1, 1) and self.padding_mode == "zeros" \
                 and self.stride[0] == self.stride[1] and self.padding[0] == self.padding[1] and not isinstance(self.padding, str):
             from fastposecnn_amd.lib import train_conv
-            if train_conv.ENABLED:
-                return train_conv.conv2d(x, self.weight, self.bias, self.stride[0], self.padding[0])
+            if train_conv.ENABLED:      # (groups > 1: torch's grouped convolution on the channel-last tensor)
+                return train_conv.conv2d(x, self.weight, self.bias, self.stride[0], self.padding[0], self.groups)
         return super().forward(x)
 
 
@@ -107,16 +107,18 @@ class BasicBlock(nn.Module):
 
 
 class Bottleneck(nn.Module):
-    """torchvision's Bottleneck (ResNet V1.5, which smp's ResNetEncoder subclasses): 1x1 -> 3x3 (the stride) -> 1x1 x 4."""
+    """torchvision's Bottleneck (ResNet V1.5, which smp's ResNetEncoder subclasses): 1x1 -> 3x3 (the stride) -> 1x1 x 4.
+    ResNeXt: the 3x3 in `groups` groups over a middle of int(planes * base_width / 64) * groups channels."""
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, base_width=64):
         super().__init__()
-        self.conv1 = Conv2d(inplanes, planes, 1, bias=False)
-        self.bn1 = BatchNorm2d(planes)
-        self.conv2 = Conv2d(planes, planes, 3, stride, 1, bias=False)
-        self.bn2 = BatchNorm2d(planes)
-        self.conv3 = Conv2d(planes, planes * self.expansion, 1, bias=False)
+        width = int(planes * base_width / 64) * groups
+        self.conv1 = Conv2d(inplanes, width, 1, bias=False)
+        self.bn1 = BatchNorm2d(width)
+        self.conv2 = Conv2d(width, width, 3, stride, 1, groups=groups, bias=False)
+        self.bn2 = BatchNorm2d(width)
+        self.conv3 = Conv2d(width, planes * self.expansion, 1, bias=False)
         self.bn3 = BatchNorm2d(planes * self.expansion)
         self.relu = nn.ReLU(inplace=True)
         self.downsample = downsample
@@ -133,13 +135,24 @@ class Bottleneck(nn.Module):
 # name -> (block, blocks per stage), as torchvision / smp
 _RESNET_LAYERS = {"resnet18": (BasicBlock, [2, 2, 2, 2]), "resnet34": (BasicBlock, [3, 4, 6, 3]),
                   "resnet50": (Bottleneck, [3, 4, 6, 3]), "resnet101": (Bottleneck, [3, 4, 23, 3]),
-                  "resnet152": (Bottleneck, [3, 8, 36, 3])}
+                  "resnet152": (Bottleneck, [3, 8, 36, 3]),
+                  "resnext50_32x4d": (Bottleneck, [3, 4, 6, 3]), "resnext101_32x4d": (Bottleneck, [3, 4, 23, 3]),
+                  "resnext101_32x8d": (Bottleneck, [3, 4, 23, 3])}
+# name -> (groups, width per group) of the ResNeXt encoders; every other encoder is (1, 64)
+_RESNEXT_WIDTHS = {"resnext50_32x4d": (32, 4), "resnext101_32x4d": (32, 4), "resnext101_32x8d": (32, 8)}
 
 
 def encoder_layout(name):
     """(block expansion, blocks per stage) of encoder `name`: the descriptor fpc_net_create_encoder takes."""
     block, layers = _RESNET_LAYERS[name]
     return block.expansion, list(layers)
+
+
+def encoder_groups(name):
+    """(groups, width per group) of encoder `name`: what fpc_net_create_encoder_ex takes beside encoder_layout's pair."""
+    if name not in _RESNET_LAYERS:
+        raise KeyError(name)
+    return _RESNEXT_WIDTHS.get(name, (1, 64))
 
 
 class ResNetEncoder(nn.Module):
@@ -153,6 +166,7 @@ class ResNetEncoder(nn.Module):
         self.name = name
         self._depth = depth
         self._block = block
+        self._groups, self._base_width = encoder_groups(name)
         e = block.expansion
         self.out_channels = (in_channels, 64, 64 * e, 128 * e, 256 * e, 512 * e)
         self.inplanes = 64
@@ -177,10 +191,11 @@ class ResNetEncoder(nn.Module):
         if stride != 1 or self.inplanes != planes * block.expansion:
             downsample = nn.Sequential(Conv2d(self.inplanes, planes * block.expansion, 1, stride, bias=False),
                                        BatchNorm2d(planes * block.expansion))
-        layers = [block(self.inplanes, planes, stride, downsample)]
+        kw = dict(groups=self._groups, base_width=self._base_width) if self._groups > 1 else {}
+        layers = [block(self.inplanes, planes, stride, downsample, **kw)]
         self.inplanes = planes * block.expansion
         for _ in range(1, blocks):
-            layers.append(block(self.inplanes, planes))
+            layers.append(block(self.inplanes, planes, **kw))
         return nn.Sequential(*layers)
 
     def forward(self, x):

@@ -261,8 +261,14 @@ def conv2d_up_add(x, w, bias, top, pad):
     return _ConvUpAddFn.apply(x, w, bias, top, int(pad))
 
 
-def conv2d(x, w, bias, stride, pad):
-    """Training-mode convolution: native when the shapes allow it, torch otherwise (same signature either way)."""
+def conv2d(x, w, bias, stride, pad, groups=1):
+    """Training-mode convolution: native when the shapes allow it, torch otherwise (same signature either way).  A grouped
+    convolution (conv2 of the ResNeXt blocks) is torch's own on the channel-last tensor, forward and backward: like the stem it
+    is counted neither as native nor as aten in `counters`."""
+    if groups != 1:
+        if ENABLED and x.is_cuda and x.dim() == 4:
+            x = _channels_last(x)
+        return torch.nn.functional.conv2d(x, w, bias, stride, pad, 1, groups)
     if ENABLED and x.is_cuda and x.dtype == torch.float32 and _native_forward_ok(x, w):
         return _Conv2dFn.apply(x, w, bias, int(stride), int(pad))
     if ENABLED and x.is_cuda and x.dim() == 4:

@@ -476,6 +476,15 @@ int fpc_net_create(const char* encoder, int classes, int B, int H, int W, fpc_ne
  * (1, {2,2,2,2}) and (1, {3,4,6,3}) give the parameter tables and workspaces of "resnet18" / "resnet34".  Same H / W / classes
  * rules as fpc_net_create. */
 int fpc_net_create_encoder(int block, const int* layers4, int classes, int B, int H, int W, fpc_net_t** out);
+/* ... with torchvision's `groups` and `width_per_group` (the ResNeXt encoders: Bottleneck, groups = 32, width 4 or 8): conv2 of
+ * every block is then a GROUPED 3x3 of planes * width_per_group / 64 * groups channels (csrc/conv_grouped.hip; fpc_net_conv_plan
+ * reports FPC_PLAN_GROUPED + form there), conv1 / conv3 are 1x1 sites of that width, the stage outputs stay 256 .. 2048.
+ * (block, layers4, 1, 64) is fpc_net_create_encoder(block, layers4): the same parameter table, workspace and plans.
+ * fpc_net_create answers "resnext50_32x4d", "resnext101_32x4d" and "resnext101_32x8d" with (4, {3,4,6,3} / {3,4,23,3}, 32, 4 / 8).
+ * FPC_EINVAL: groups > 1 with block != 4, groups == 1 with another width than 64, channels per group (planes * width_per_group
+ * / 64 at planes = 64 .. 512) outside {4, 8, 16, 32, 64}. */
+int fpc_net_create_encoder_ex(int block, const int* layers4, int groups, int width_per_group, int classes, int B, int H, int W,
+                              fpc_net_t** out);
 void fpc_net_destroy(fpc_net_t* net);
 int fpc_net_param_count(const fpc_net_t* net);
 const char* fpc_net_param_name(const fpc_net_t* net, int i);
@@ -664,7 +673,8 @@ int fpc_net_tensor(const fpc_net_t* net, const char* name, const float** ptr, in
  * of 32; 6100 + k: split-K summed by a second launch), 7000 + parts the pixel-resident FPN lateral product on the same two pieces.  5000 is never a request: fpc_net_conv_plan's "folded away". */
 enum {      /* the bases of those codes, as fpc_net_conv_plan reports them and fpc_conv2d takes them (a Winograd form: -form) */
     FPC_PLAN_WINO_ORIENT = -11, FPC_PLAN_WINO_PACKED = -10, FPC_PLAN_TWO_LAUNCH = 100, FPC_PLAN_BF3 = 1000, FPC_PLAN_LATERAL = 2000, FPC_PLAN_STEM = 3000,
-    FPC_PLAN_STEM_POOL = 3100, FPC_PLAN_POINTWISE = 4000, FPC_PLAN_FOLDED = 5000, FPC_PLAN_H3 = 6000, FPC_PLAN_LATERAL_H3 = 7000
+    FPC_PLAN_STEM_POOL = 3100, FPC_PLAN_POINTWISE = 4000, FPC_PLAN_FOLDED = 5000, FPC_PLAN_H3 = 6000, FPC_PLAN_LATERAL_H3 = 7000,
+    FPC_PLAN_GROUPED = 8000      /* + form: the grouped 3x3 kernel (fpc_conv2d_grouped; fpc_conv2d itself refuses the code) */
 };
 size_t fpc_conv2d_workspace_bytes(int B, int Ho, int Wo, int Cin, int Cout, int Kh, int Kw);
 /* the exact need of one request (same bm / bn / nsplit as the fpc_conv2d call): <= the bound above, which reserves 32
@@ -676,6 +686,20 @@ int fpc_conv2d(const float* in, int64_t sb, int64_t sh, int64_t sw, int64_t sc, 
                const float* scale, const float* shift, const float* res, const float* up, float* out,
                float* gn_part, int B, int Hi, int Wi, int Cin, int Cout, int Kh, int Kw, int stride, int pad,
                int relu, int bm, int bn, int nsplit, void* ws, size_t ws_bytes, fpc_stream_t stream);
+
+/* Stand-alone GROUPED 3x3 convolution, pad 1, stride 1 or 2 (csrc/conv_grouped.hip, k_conv3x3_grouped: conv2 of the ResNeXt
+ * blocks): C channels in and out in `groups` groups of C / groups channels each.  in: element strides (sb, sh, sw, sc) with sc = 1
+ * (channels contiguous), sb / sh / sw multiples of 4, sw >= C; w_oihw torch's [C][C / groups][3][3]; out NHWC [B][Ho][Wo][C], Ho =
+ * (Hi - 1) / stride + 1; optional per-channel scale / shift (folded BatchNorm) and ReLU.  form: 0 = plain f32 products (v_fma_f32,
+ * fixed summation order: results are bit-identical run to run) — the only form built; fpc_net_conv_plan reports a site on it as
+ * FPC_PLAN_GROUPED + form.  ws: fpc_conv2d_grouped_workspace_bytes(C, groups) bytes, 256-byte aligned (the weights are repacked
+ * into it on every call).  FPC_EINVAL before any launch: groups not dividing C, C / groups outside {4, 8, 16, 32, 64}, C not a
+ * multiple of 32, another stride or form, sc != 1, a pointer that is null or not 16-byte aligned.  The workspace size of a shape
+ * the call refuses is 0. */
+size_t fpc_conv2d_grouped_workspace_bytes(int C, int groups);
+int fpc_conv2d_grouped(const float* in, int64_t sb, int64_t sh, int64_t sw, int64_t sc, const float* w_oihw, const float* scale,
+                       const float* shift, float* out, int B, int Hi, int Wi, int C, int groups, int stride, int relu, int form,
+                       void* ws, size_t ws_bytes, fpc_stream_t stream);
 
 /* Weight gradient of a convolution for the training step (BASELINE.json configs[4]; the reference leaves the
  * convolutions' backward to cuDNN through autograd, F/lib/pose_regressor.py:709-743 under Lightning's backward).
