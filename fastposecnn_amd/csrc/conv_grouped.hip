@@ -42,8 +42,11 @@ struct GrpGeom {
     static_assert((IN_FLOATS + W_FLOATS) * 4 <= 65536, "static LDS");
 };
 
-// torch's [C][CG][3][3] -> [C / 32][pass][tap][ci in pass][32]
-__global__ __launch_bounds__(256) void k_pack_grouped(const float* __restrict__ w, float* __restrict__ packed, int C, int CG) {
+// torch's [C][CG][3][3] -> [C / 32][pass][tap][ci in pass][32].  mode 0: the forward's image.  mode 1: the image of the stride-1
+// data gradient, W'[g CG + ci][co][ky][kx] = W[g CG + co][ci][2 - ky][2 - kx] (transposed inside each group and flipped), read
+// straight from the OIHW source.  mode 2: transposed inside each group, taps as they are (k_conv3x3_grouped_dgrad_s2 names the
+// forward's tap itself).
+__global__ __launch_bounds__(256) void k_pack_grouped(const float* __restrict__ w, float* __restrict__ packed, int C, int CG, int mode) {
     const int KB = CG < 16 ? CG : 16, NPASS = CG / KB;
     const long long total = (long long)C * CG * 9;
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -55,7 +58,12 @@ __global__ __launch_bounds__(256) void k_pack_grouped(const float* __restrict__ 
     const int pass = (int)(r % NPASS);
     const int chunk = (int)(r / NPASS);
     const int c = chunk * kGrpCC + co, ci = pass * KB + k;
-    packed[i] = w[((size_t)c * CG + ci) * 9 + t];
+    if (mode == 0) {
+        packed[i] = w[((size_t)c * CG + ci) * 9 + t];
+    } else {
+        const int g = c / CG, cl = c - g * CG;
+        packed[i] = w[((size_t)(g * CG + ci) * CG + cl) * 9 + (mode == 1 ? 8 - t : t)];
+    }
 }
 
 template <int CG, int STRIDE>
@@ -167,10 +175,10 @@ inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 bool grouped_cg_ok(int cg) { return cg == 4 || cg == 8 || cg == 16 || cg == 32 || cg == 64; }
 
-int launch_pack_grouped(const float* w, float* packed, int C, int CG, hipStream_t s) {
-    if (!w || !packed || C < 32 || C % 32 || !grouped_cg_ok(CG) || C % CG) return FPC_EINVAL;
+int launch_pack_grouped(const float* w, float* packed, int C, int CG, hipStream_t s, int mode) {
+    if (!w || !packed || C < 32 || C % 32 || !grouped_cg_ok(CG) || C % CG || mode < 0 || mode > 2) return FPC_EINVAL;
     const long long total = (long long)C * CG * 9;
-    hipLaunchKernelGGL(k_pack_grouped, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, packed, C, CG);
+    hipLaunchKernelGGL(k_pack_grouped, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, packed, C, CG, mode);
     return check_launch();
 }
 

@@ -107,9 +107,11 @@ struct GroupedArgs {
 };
 constexpr int kGroupedForms = 1;
 bool grouped_cg_ok(int cg);
-int launch_pack_grouped(const float* w_oihw, float* packed, int C, int CG, hipStream_t s);
+int launch_pack_grouped(const float* w_oihw, float* packed, int C, int CG, hipStream_t s, int mode = 0);      // mode: k_pack_grouped
 int launch_conv3x3_grouped(const GroupedArgs& a, hipStream_t s);
 inline int grouped_tile_cols(int stride) { return stride == 1 ? 16 : 8; }      // x 8 rows x 32 channels per workgroup
+// (the training step's data and weight gradients of this convolution have no launcher here: conv_grouped_train.hip holds their
+// kernels and the C entries fpc_conv2d_grouped_dgrad / _wgrad)
 
 // the 7x7 / stride-2 / pad-3 stem on the NHWC4 image as a weight-resident product (stem.hip)
 struct StemArgs {

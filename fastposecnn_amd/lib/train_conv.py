@@ -12,7 +12,11 @@ autograd.Function over three native pieces, all on channel-last (NHWC) activatio
                  minimal multiply-adds);  heads whose width is not a multiple of 32: dy and W zero-padded to 32 channels
   weight gradient  fpc_conv2d_wgrad (csrc/conv_wgrad.hip): pixels-as-K GEMM on the f32 matrix cores, fixed-order
                  split over the pixels; a width that is not a multiple of 4 (mask / scales / xyz heads) is padded likewise
-The 7x7 stem (Cin = 3) is the one convolution left to torch, forward and backward: its input needs no gradient and its
+A GROUPED 3x3 convolution (conv2 of the ResNeXt blocks) is torch's own by default; with FPC_TRAIN_NATIVE_GROUPED=1 it is
+_GroupedConv2dFn: k_conv3x3_grouped forward, the same kernel on the in-group transposed, flipped weights (stride 1) or
+k_conv3x3_grouped_dgrad_s2 (stride 2) for the data gradient, k_conv3x3_grouped_wgrad for the weight gradient
+(csrc/conv_grouped_train.hip) — plain f32 products, one form, nothing tuned.
+The 7x7 stem (Cin = 3) is the one dense convolution left to torch, forward and backward: its input needs no gradient and its
 weight gradient is a K = 147 GEMM no tile of these kernels fits (counted neither as native nor as aten below: it never
 enters this module's autograd functions).
 
@@ -261,11 +265,119 @@ def conv2d_up_add(x, w, bias, top, pad):
     return _ConvUpAddFn.apply(x, w, bias, top, int(pad))
 
 
+# ---- the grouped 3x3 convolution (conv2 of the ResNeXt blocks) ---------------------------------------------------------------
+
+# Off by default: with it off a grouped convolution is torch's own, forward and backward, as before (DESIGN.md 4.2a'').
+NATIVE_GROUPED = bool(int(os.environ.get("FPC_TRAIN_NATIVE_GROUPED", "0")))
+counters.update(grouped_fwd_native=0, grouped_dgrad_native=0, grouped_wgrad_native=0)
+GROUPED_CG = (4, 8, 16, 32, 64)      # channels per group csrc/conv_grouped.hip is built for
+
+
+def _grouped_native_op(op, cg, stride):
+    """Whether `op` ("dgrad" / "wgrad") of the (channels per group, stride) combination runs native.  A combination whose native
+    kernel measured slower than torch's on the training shapes is listed here and keeps torch's kernel (DESIGN.md 4.2a'', the
+    per-site table); the forward always runs native."""
+    return (op, cg, stride) not in _GROUPED_KEEP_TORCH
+
+
+_GROUPED_KEEP_TORCH = frozenset()
+
+
+def _grouped_ok(x, w, bias, stride, pad, groups):
+    if not (ENABLED and NATIVE_GROUPED and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+            and w.dtype == torch.float32 and w.device == x.device and x.device.index == torch.cuda.current_device()):
+        return False
+    C = x.shape[1]
+    # the bias is the kernel's `shift`: f32 on the same device, one value per channel, contiguous and 16-byte aligned as it stands
+    if bias is not None and not (bias.dtype == torch.float32 and bias.device == x.device and tuple(bias.shape) == (C,)
+                                 and bias.is_contiguous() and bias.data_ptr() % 16 == 0):
+        return False
+    return (groups >= 1 and C % 32 == 0 and C % groups == 0 and C // groups in GROUPED_CG and tuple(w.shape) == (C, C // groups, 3, 3)
+            and pad == 1 and stride in (1, 2) and x.numel() > 0)
+
+
+class _GroupedConv2dFn(torch.autograd.Function):
+    """The grouped 3x3 / pad-1 convolution on the native kernels, forward (k_conv3x3_grouped through fpc_conv2d_grouped, the bias as
+    its shift) and backward (fpc_conv2d_grouped_dgrad / _wgrad, csrc/conv_grouped_train.hip).  One form: nothing is tuned."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, stride, groups):
+        x = _channels_last(x)
+        if x.data_ptr() % 16:
+            x = x.clone(memory_format=torch.channels_last)
+        w = w.contiguous()
+        B, C, H, W = x.shape
+        Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+        out = torch.empty((B, C, Ho, Wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        L = nat.lib()
+        shift = None if bias is None else bias.detach()
+        sb, sc, sh, sw = x.stride()
+        ws = nat.workspace("train_grouped", x.device, L.fpc_conv2d_grouped_workspace_bytes(C, groups))
+        nat.check(L.fpc_conv2d_grouped(x.data_ptr(), sb, sh, sw, sc, w.data_ptr(), None, nat.ptr(shift), out.data_ptr(), B, H, W, C,
+                                       groups, stride, 0, 0, ws.data_ptr(), ws.numel(), nat.stream()), "fpc_conv2d_grouped (training)")
+        ctx.stride, ctx.groups, ctx.has_bias = stride, groups, bias is not None
+        ctx.save_for_backward(x, w)
+        counters["grouped_fwd_native"] += 1
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        stride, groups = ctx.stride, ctx.groups
+        B, C, H, W = x.shape
+        cg = C // groups
+        gy = _channels_last(gy)
+        if gy.data_ptr() % 16:
+            gy = gy.clone(memory_format=torch.channels_last)
+        Ho, Wo = gy.shape[2], gy.shape[3]
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gx = gw = gb = None
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            gb = gy.sum((0, 2, 3))
+        L = nat.lib()
+        aten_x = need_x and not _grouped_native_op("dgrad", cg, stride)
+        aten_w = need_w and not _grouped_native_op("wgrad", cg, stride)
+        if need_x and not aten_x:
+            gx = torch.empty((B, C, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+            ws = nat.workspace("train_grouped", x.device, L.fpc_conv2d_grouped_dgrad_workspace_bytes(C, groups))
+            nat.check(L.fpc_conv2d_grouped_dgrad(gy.data_ptr(), w.data_ptr(), gx.data_ptr(), B, H, W, C, groups, stride, ws.data_ptr(),
+                                                 ws.numel(), nat.stream()), "fpc_conv2d_grouped_dgrad")
+            counters["grouped_dgrad_native"] += 1
+        if need_w and not aten_w:
+            sink = grad_sinks.get(w.data_ptr())
+            if sink is not None and sink.owner() is None:        # its optimiser is gone: the address may belong to another tensor now
+                del grad_sinks[w.data_ptr()]
+                sink = None
+            if sink is not None and (sink.written or sink.view.shape != w.shape or not sink.view.is_contiguous()
+                                     or sink.view.data_ptr() % 16):
+                sink = None
+            gw = sink.view if sink is not None else torch.empty_like(w)
+            sb, sc, sh, sw = x.stride()
+            ws = nat.workspace("train_grouped_wgrad", x.device, L.fpc_conv2d_grouped_wgrad_workspace_bytes(B, Ho, Wo, C, groups))
+            nat.check(L.fpc_conv2d_grouped_wgrad(x.data_ptr(), sb, sh, sw, gy.data_ptr(), gw.data_ptr(), B, H, W, C, groups, stride,
+                                                 ws.data_ptr(), ws.numel(), nat.stream()), "fpc_conv2d_grouped_wgrad")
+            counters["grouped_wgrad_native"] += 1
+            if sink is not None:                # written in place: nothing for autograd to accumulate
+                sink.written = True
+                sink.callback()
+                gw = None
+        if aten_x or aten_w:
+            ax, aw, _ = torch.ops.aten.convolution_backward(gy, x, w, None, [stride, stride], [1, 1], [1, 1], False, [0, 0], groups,
+                                                            [aten_x, aten_w, False])
+            gx = ax if aten_x else gx
+            gw = aw if aten_w else gw
+        return gx, gw, gb, None, None
+
+
 def conv2d(x, w, bias, stride, pad, groups=1):
     """Training-mode convolution: native when the shapes allow it, torch otherwise (same signature either way).  A grouped
-    convolution (conv2 of the ResNeXt blocks) is torch's own on the channel-last tensor, forward and backward: like the stem it
-    is counted neither as native nor as aten in `counters`."""
+    convolution (conv2 of the ResNeXt blocks) is torch's own on the channel-last tensor, forward and backward, and like the stem
+    counted neither as native nor as aten in `counters` — unless NATIVE_GROUPED (FPC_TRAIN_NATIVE_GROUPED=1) is set and it is
+    a 3x3 / pad-1 / stride-1 or -2 convolution of the class csrc/conv_grouped.hip takes: then _GroupedConv2dFn, counted in
+    grouped_fwd_native / grouped_dgrad_native / grouped_wgrad_native."""
     if groups != 1:
+        if _grouped_ok(x, w, bias, stride, pad, groups):
+            return _GroupedConv2dFn.apply(x, w, bias, int(stride), int(groups))
         if ENABLED and x.is_cuda and x.dim() == 4:
             x = _channels_last(x)
         return torch.nn.functional.conv2d(x, w, bias, stride, pad, 1, groups)

@@ -701,6 +701,31 @@ int fpc_conv2d_grouped(const float* in, int64_t sb, int64_t sh, int64_t sw, int6
                        const float* shift, float* out, int B, int Hi, int Wi, int C, int groups, int stride, int relu, int form,
                        void* ws, size_t ws_bytes, fpc_stream_t stream);
 
+/* Data gradient of that GROUPED 3x3 convolution for the training step (csrc/conv_grouped_train.hip), pad 1, stride 1 or 2.
+ * dy NHWC [B][Ho][Wo][C] contiguous, Ho = (Hi - 1) / stride + 1 (odd Hi / Wi included); w_oihw torch's [C][C / groups][3][3], the
+ * FORWARD's weights; dx NHWC [B][Hi][Wi][C] contiguous, every element written.  Stride 1: k_conv3x3_grouped over dy on the weights
+ * transposed inside each group and flipped; stride 2: k_conv3x3_grouped_dgrad_s2, each 2 x 2 block of dx from the 2 x 2 window of
+ * dy it sees (9 tap products per channel pair).  Plain f32 products, fixed summation order: bit-identical run to run.  ws:
+ * fpc_conv2d_grouped_dgrad_workspace_bytes(C, groups) bytes, 256-byte aligned: k_pack_grouped's image of the transposed weights,
+ * rewritten on every call.  FPC_EINVAL before any launch: everything fpc_conv2d_grouped refuses (groups not dividing C, C / groups
+ * outside {4, 8, 16, 32, 64}, C not a multiple of 32, another stride), a pointer that is null or not 16-byte aligned (ws: 256), a
+ * workspace that is too small.  The workspace size of a shape the call refuses is 0. */
+size_t fpc_conv2d_grouped_dgrad_workspace_bytes(int C, int groups);
+int fpc_conv2d_grouped_dgrad(const float* dy, const float* w_oihw, float* dx, int B, int Hi, int Wi, int C, int groups, int stride,
+                             void* ws, size_t ws_bytes, fpc_stream_t stream);
+/* Weight gradient of that convolution (k_conv3x3_grouped_wgrad + k_wgrad_grouped_reduce): dw OIHW [C][C / groups][3][3], every
+ * element written (not accumulated), dw[c][ci][ky][kx] = sum over b, oy, ox of dy[b][oy][ox][c] x[b][s oy + ky - 1][s ox + kx - 1]
+ * [g (C / groups) + ci].  x: pixel (b, y, x) at x + b sb + y sh + x sw with its C channels contiguous (a channel slice of a wider
+ * tensor is fine), sb / sh / sw multiples of 4, sw >= C; dy NHWC [B][Ho][Wo][C] contiguous.  The (frame, tile) list is cut into
+ * slices, one partial per slice, summed in slice order: plain f32, no atomics, bit-identical run to run.  ws:
+ * fpc_conv2d_grouped_wgrad_workspace_bytes(B, Ho, Wo, C, groups) bytes, 256-byte aligned: the partials [slice][C][C / groups][9]
+ * (the call's slice count is that size over C * (C / groups) * 36, or its tile count — 8 x 16 output pixels at stride 1, 8 x 8 at
+ * stride 2 — where that is less; with one slice the workspace is not touched).  FPC_EINVAL before any launch: as
+ * fpc_conv2d_grouped_dgrad, and strides that are not multiples of 4 or sw < C.  The workspace size of a refused shape is 0. */
+size_t fpc_conv2d_grouped_wgrad_workspace_bytes(int B, int Ho, int Wo, int C, int groups);
+int fpc_conv2d_grouped_wgrad(const float* x, int64_t sb, int64_t sh, int64_t sw, const float* dy, float* dw, int B, int Hi, int Wi,
+                             int C, int groups, int stride, void* ws, size_t ws_bytes, fpc_stream_t stream);
+
 /* Weight gradient of a convolution for the training step (BASELINE.json configs[4]; the reference leaves the
  * convolutions' backward to cuDNN through autograd, F/lib/pose_regressor.py:709-743 under Lightning's backward).
  * x: input [B,Hi,Wi,Cin] channel-last (channel stride 1; element strides sb, sh, sw multiples of 4; 16-byte aligned),
