@@ -122,6 +122,12 @@ _SIGNATURES = {
     "fpc_conv2d_grouped_dgrad": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "fpc_conv2d_grouped_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "fpc_conv2d_grouped_wgrad": (_i, [_vp, _i64, _i64, _i64, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "fpc_image_nhwc4": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "fpc_stem_wgrad_workspace_bytes": (_sz, [_i, _i, _i]),
+    "fpc_stem_wgrad_slices": (_i, [_i, _i, _i]),
+    "fpc_stem_wgrad": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    "fpc_maxpool3x3s2_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "fpc_maxpool3x3s2_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "fpc_conv2d_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "fpc_upsample_bilinear_fwd": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "fpc_upsample_bilinear_bwd_scratch_floats": (_sz, [_i, _i, _i, _i, _i]),

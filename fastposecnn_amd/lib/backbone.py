@@ -71,6 +71,23 @@ class BatchNorm2d(nn.BatchNorm2d):
         return super().forward(x)
 
 
+class MaxPool2d(nn.MaxPool2d):
+    """nn.MaxPool2d whose 3x3 / stride-2 / pad-1 forward on a dense channel-last f32 GPU tensor that requires grad runs on the
+    native kernels, forward and backward, when FPC_TRAIN_NATIVE_STEM=1 (lib/train_conv.maxpool3x3s2, csrc/stem_train.hip);
+    everything else — another geometry, return_indices, ceil_mode, CPU tensors, a no_grad forward, the switch off (its default) —
+    is nn.MaxPool2d's own forward.  No parameters: state_dicts are untouched."""
+
+    def forward(self, x):
+        if x.is_cuda and torch.is_grad_enabled() and x.requires_grad and not self.return_indices and not self.ceil_mode \
+                and self.kernel_size in (3, (3, 3)) and self.stride in (2, (2, 2)) and self.padding in (1, (1, 1)) \
+                and self.dilation in (1, (1, 1)):
+            from fastposecnn_amd.lib import train_conv
+            y = train_conv.maxpool3x3s2(x)
+            if y is not None:
+                return y
+        return super().forward(x)
+
+
 def _bn_act(x, bn, act, res=None):
     """act(bn(x) + res) at a block's BatchNorm.  In the training step BatchNorm, the add and the ReLU are one native op; the
     ReLU (and with it the add) is fused only while `act` is an nn.ReLU — a test may have swapped it for a smooth activation,
@@ -173,7 +190,7 @@ class ResNetEncoder(nn.Module):
         self.conv1 = Conv2d(in_channels, 64, 7, 2, 3, bias=False)
         self.bn1 = BatchNorm2d(64)
         self.relu = nn.ReLU(inplace=True)
-        self.maxpool = nn.MaxPool2d(3, 2, 1)
+        self.maxpool = MaxPool2d(3, 2, 1)
         self.layer1 = self._make_layer(64, layers[0])
         self.layer2 = self._make_layer(128, layers[1], stride=2)
         self.layer3 = self._make_layer(256, layers[2], stride=2)

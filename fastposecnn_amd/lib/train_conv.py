@@ -16,9 +16,12 @@ A GROUPED 3x3 convolution (conv2 of the ResNeXt blocks) is torch's own by defaul
 _GroupedConv2dFn: k_conv3x3_grouped forward, the same kernel on the in-group transposed, flipped weights (stride 1) or
 k_conv3x3_grouped_dgrad_s2 (stride 2) for the data gradient, k_conv3x3_grouped_wgrad for the weight gradient
 (csrc/conv_grouped_train.hip) — plain f32 products, one form, nothing tuned.
-The 7x7 stem (Cin = 3) is the one dense convolution left to torch, forward and backward: its input needs no gradient and its
-weight gradient is a K = 147 GEMM no tile of these kernels fits (counted neither as native nor as aten below: it never
-enters this module's autograd functions).
+The 7x7 stem (Cin = 3) is torch's own by default, forward and backward: its input needs no gradient and its weight gradient is a
+K = 147 GEMM no tile of the kernels above fits (counted neither as native nor as aten below).  With FPC_TRAIN_NATIVE_STEM=1 it
+is _StemConvFn — the image repacked to NHWC4 (fpc_image_nhwc4), the forward on k_stem7x7 (fpc_conv2d code 3000; a row that does
+not divide into 64-pixel segments: the implicit-GEMM kernel's generic loader), the weight gradient on k_stem_wgrad
+(csrc/stem_train.hip) — and the 3x3 / stride-2 max-pool behind it is _MaxPoolFn (k_maxpool3x3s2 / k_maxpool3x3s2_bwd), counted
+in stem_fwd_native / stem_wgrad_native / pool_fwd_native / pool_bwd_native: no convolution of the step is MIOpen's then.
 
 The tiling / Winograd form of a shape is chosen once, by timing the candidates on the first call with that shape (this
 synchronises: it happens in the warm-up steps).  f32 operands, accumulation and results, products in plain f32 or as the
@@ -369,12 +372,129 @@ class _GroupedConv2dFn(torch.autograd.Function):
         return gx, gw, gb, None, None
 
 
+# ---- the 7x7 / stride-2 stem (Cin = 3) and the 3x3 / stride-2 max-pool behind it -------------------------------------------
+
+# Off by default: with it off the stem and the max-pool are torch's own, forward and backward, as before (DESIGN.md 4.2a''').
+NATIVE_STEM = bool(int(os.environ.get("FPC_TRAIN_NATIVE_STEM", "0")))
+counters.update(stem_fwd_native=0, stem_wgrad_native=0, pool_fwd_native=0, pool_bwd_native=0)
+
+
+def _stem_ok(x, w, bias, stride, pad):
+    return (NATIVE_STEM and ENABLED and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+            and w.dtype == torch.float32 and w.device == x.device and x.device.index == torch.cuda.current_device()
+            and tuple(w.shape) == (64, 3, 7, 7) and stride == 2 and pad == 3 and bias is None and x.shape[1] == 3
+            and x.shape[0] >= 1 and x.shape[2] >= 8 and x.shape[3] >= 8 and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0
+            and x.numel() < 2 ** 31
+            and not x.requires_grad             # there is no data gradient here: an input that needs one stays on torch
+            and torch.is_grad_enabled() and w.requires_grad)
+
+
+class _StemConvFn(torch.autograd.Function):
+    """The encoder's conv1 on the native kernels: y = conv(x, w) raw (training-mode BatchNorm follows), channel-last.  The NHWC4
+    image is saved for the backward, which is the weight gradient alone (fpc_stem_wgrad): x gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, w):
+        x = x.contiguous()
+        if x.data_ptr() % 16:
+            x = x.clone()
+        w = w.contiguous()
+        B, _, H, W = x.shape
+        Ho, Wo = H // 2, W // 2
+        L = nat.lib()
+        img4 = torch.empty((B, H, W, 4), dtype=torch.float32, device=x.device)
+        nat.check(L.fpc_image_nhwc4(x.data_ptr(), img4.data_ptr(), B, H, W, nat.stream()), "fpc_image_nhwc4")
+        out = torch.empty((B, 64, Ho, Wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        if Wo % 64 == 0:        # k_stem7x7: weights [64][4][7][7] (the image's fourth channel: zero weights), no scale / shift / ReLU
+            w4 = torch.zeros((64, 4, 7, 7), dtype=torch.float32, device=x.device)
+            w4[:, :3] = w.detach()
+            ws = nat.workspace("train_conv", x.device, L.fpc_conv2d_workspace_bytes_for(B, Ho, Wo, 4, 64, 7, 7, 0, 0, 3000))
+            nat.check(L.fpc_conv2d(img4.data_ptr(), 4 * H * W, 4 * W, 4, 1, w4.data_ptr(), None, None, None, None, out.data_ptr(), None,
+                                   B, H, W, 4, 64, 7, 7, 2, 3, 0, 0, 0, 3000, ws.data_ptr(), ws.numel(), nat.stream()),
+                      "fpc_conv2d (training, stem)")
+        else:                   # a row k_stem7x7's 64-pixel segments do not divide: k_conv_igemm's generic loader on the NCHW image
+            _run(x, w.detach(), None, 2, 3, 0, out)
+        ctx.save_for_backward(img4, w)
+        counters["stem_fwd_native"] += 1
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        img4, w = ctx.saved_tensors
+        if not ctx.needs_input_grad[1]:
+            return None, None
+        B, H, W, _ = img4.shape
+        gy = _channels_last(gy)
+        if gy.data_ptr() % 16:
+            gy = gy.clone(memory_format=torch.channels_last)
+        L = nat.lib()
+        sink = grad_sinks.get(w.data_ptr())
+        if sink is not None and sink.owner() is None:        # its optimiser is gone: the address may belong to another tensor now
+            del grad_sinks[w.data_ptr()]
+            sink = None
+        if sink is not None and (sink.written or sink.view.shape != w.shape or not sink.view.is_contiguous()
+                                 or sink.view.data_ptr() % 16):
+            sink = None
+        gw = sink.view if sink is not None else torch.empty((64, 3, 7, 7), dtype=torch.float32, device=gy.device)
+        ws = nat.workspace("train_stem_wgrad", gy.device, L.fpc_stem_wgrad_workspace_bytes(B, H, W))
+        nat.check(L.fpc_stem_wgrad(img4.data_ptr(), gy.data_ptr(), gw.data_ptr(), B, H, W, ws.data_ptr(), ws.numel(), nat.stream()),
+                  "fpc_stem_wgrad")
+        counters["stem_wgrad_native"] += 1
+        if sink is not None:                # written in place: nothing for autograd to accumulate
+            sink.written = True
+            sink.callback()
+            gw = None
+        return None, gw
+
+
+class _MaxPoolFn(torch.autograd.Function):
+    """max_pool2d(x, 3, 2, 1) on a dense channel-last tensor.  Only x is saved: the backward finds each window's arg-max again,
+    by torch's rule (the first maximum in row-major order), and gathers dy (csrc/stem_train.hip: k_maxpool3x3s2_bwd)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        B, C, H, W = x.shape
+        y = torch.empty((B, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        nat.check(nat.lib().fpc_maxpool3x3s2_fwd(x.data_ptr(), y.data_ptr(), B, H, W, C, nat.stream()), "fpc_maxpool3x3s2_fwd")
+        ctx.save_for_backward(x)
+        counters["pool_fwd_native"] += 1
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, = ctx.saved_tensors
+        B, C, H, W = x.shape
+        gy = _channels_last(gy)
+        if gy.data_ptr() % 16:
+            gy = gy.clone(memory_format=torch.channels_last)
+        dx = torch.empty_like(x, memory_format=torch.channels_last)
+        nat.check(nat.lib().fpc_maxpool3x3s2_bwd(x.data_ptr(), gy.data_ptr(), dx.data_ptr(), B, H, W, C, nat.stream()),
+                  "fpc_maxpool3x3s2_bwd")
+        counters["pool_bwd_native"] += 1
+        return dx
+
+
+def maxpool3x3s2(x):
+    """max_pool2d(x, 3, 2, 1) on the native kernels, forward and backward, for a dense channel-last f32 GPU tensor that requires
+    grad under autograd, with NATIVE_STEM set; None otherwise (the caller keeps torch's module)."""
+    if not (NATIVE_STEM and ENABLED and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+            and torch.is_grad_enabled() and x.requires_grad and x.device.index == torch.cuda.current_device()
+            and x.shape[1] % 4 == 0 and 0 < x.numel() < 2 ** 32 and x.stride(1) == 1
+            and x.is_contiguous(memory_format=torch.channels_last) and x.data_ptr() % 16 == 0):
+        return None
+    return _MaxPoolFn.apply(x)
+
+
 def conv2d(x, w, bias, stride, pad, groups=1):
     """Training-mode convolution: native when the shapes allow it, torch otherwise (same signature either way).  A grouped
     convolution (conv2 of the ResNeXt blocks) is torch's own on the channel-last tensor, forward and backward, and like the stem
     counted neither as native nor as aten in `counters` — unless NATIVE_GROUPED (FPC_TRAIN_NATIVE_GROUPED=1) is set and it is
     a 3x3 / pad-1 / stride-1 or -2 convolution of the class csrc/conv_grouped.hip takes: then _GroupedConv2dFn, counted in
-    grouped_fwd_native / grouped_dgrad_native / grouped_wgrad_native."""
+    grouped_fwd_native / grouped_dgrad_native / grouped_wgrad_native.  The 7x7 stem likewise: torch's own unless NATIVE_STEM
+    (FPC_TRAIN_NATIVE_STEM=1) is set and it is the 3 -> 64 / stride-2 / pad-3 convolution without bias of an even-sized image
+    that needs no gradient: then _StemConvFn, counted in stem_fwd_native / stem_wgrad_native."""
+    if groups == 1 and _stem_ok(x, w, bias, stride, pad):
+        return _StemConvFn.apply(x, w)
     if groups != 1:
         if _grouped_ok(x, w, bias, stride, pad, groups):
             return _GroupedConv2dFn.apply(x, w, bias, int(stride), int(groups))

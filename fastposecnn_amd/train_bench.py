@@ -4,7 +4,8 @@ batch 8 per GPU (64 on 8 GPUs), forward + HEAD_TRAINING losses + backward + grad
 What runs where (stated in the JSON line as well):
   * encoder / decoder / head convolutions: lib/train_conv.py — forward on the engine's implicit-GEMM / Winograd kernels,
     data gradient on the same kernels (stride 1: flipped weights; stride 2: four parity convolutions of dy; heads of odd
-    width: zero-padded to 32 channels), weight gradient on csrc/conv_wgrad.hip; torch keeps the 7x7 stem (Cin = 3);
+    width: zero-padded to 32 channels), weight gradient on csrc/conv_wgrad.hip; torch keeps the 7x7 stem (Cin = 3) and its max-pool unless
+    FPC_TRAIN_NATIVE_STEM=1 (csrc/stem_train.hip);
     bilinear upsampling forward / backward on csrc/upsample.hip; the decoder's GroupNorm + ReLU on csrc/groupnorm.hip; the
     encoder's BatchNorm + residual add + ReLU: torch's modules, or csrc/batchnorm.hip with FPC_TRAIN_NATIVE_BN=1
     (FPC_TRAIN_NATIVE_CONV=0 returns every convolution and upsampling to torch: the A/B this file's numbers come with);
@@ -65,7 +66,11 @@ def _conv_note():
     c = train_conv.counters
     return ("native: forward fpc_conv2d (implicit GEMM / Winograd), data gradient on the same kernels (stride 2: four parity "
             "convolutions of dy; odd-width heads zero-padded), weight gradient fpc_conv2d_wgrad, bilinear upsampling "
-            "fpc_upsample_bilinear_fwd/bwd; torch for the 7x7 stem alone (Cin = 3: outside these counters); the encoder's "
+            "fpc_upsample_bilinear_fwd/bwd; " +
+            ("the 7x7 stem native as well: fpc_image_nhwc4 + fpc_conv2d code 3000 forward, fpc_stem_wgrad backward, the max-pool "
+             "behind it fpc_maxpool3x3s2_fwd/bwd (stem_fwd_native / stem_wgrad_native / pool_fwd_native / pool_bwd_native); "
+             if train_conv.NATIVE_STEM else
+             "torch for the 7x7 stem alone (Cin = 3: outside these counters; FPC_TRAIN_NATIVE_STEM=1: native); ") + "the encoder's "
             "BatchNorm + add + ReLU " + ("fpc_batchnorm_fwd/bwd (bn_native; bn_torch: left to torch) "
                                          if train_conv.NATIVE_BN else "torch (FPC_TRAIN_NATIVE_BN=1: native) ") +
             f"(calls so far: {dict(c)})")

@@ -726,6 +726,36 @@ size_t fpc_conv2d_grouped_wgrad_workspace_bytes(int B, int Ho, int Wo, int C, in
 int fpc_conv2d_grouped_wgrad(const float* x, int64_t sb, int64_t sh, int64_t sw, const float* dy, float* dw, int B, int Hi, int Wi,
                              int C, int groups, int stride, void* ws, size_t ws_bytes, fpc_stream_t stream);
 
+/* The training step's 7x7 / stride-2 / pad-3 stem (3 -> 64 channels) and the 3x3 / stride-2 / pad-1 max-pool behind it
+ * (csrc/stem_train.hip, lib/train_conv.py: _StemConvFn, _MaxPoolFn).  Each entry replaces its part of conv1 / maxpool of the smp
+ * ResNet encoder the reference builds at F/lib/pose_regressor.py:608, forward and backward under Lightning's training step
+ * (cuDNN / aten there).  f32 throughout; no atomics and a fixed summation order: bit-identical run to run.  Every entry returns
+ * FPC_EINVAL BEFORE any launch for a shape outside its class and for a pointer that is null or not 16-byte aligned.
+ *
+ * fpc_image_nhwc4 (k_nchw3_to_nhwc4): x NCHW contiguous [B][3][H][W] -> out [B][H][W][4], the fourth channel 0: the image the stem
+ *   kernels read (fpc_conv2d's code 3000, fpc_stem_wgrad).  B, H, W >= 1, B H W < 2^31, H W < 2^30.  Replaces the layout
+ *   change cuDNN makes inside conv1 (F/lib/pose_regressor.py:608).
+ * fpc_stem_wgrad (k_stem_wgrad + k_stem_wgrad_reduce): dw OIHW [64][3][7][7], every element overwritten,
+ *   dw[co][c][kh][kw] = sum over b, oy, ox of dy[b][oy][ox][co] img4[b][2 oy + kh - 3][2 ox + kw - 3][c], zero outside the image.
+ *   img4 [B][Hi][Wi][4] (the fourth channel is ignored), dy NHWC [B][Hi / 2][Wi / 2][64] contiguous.  Shape class: Hi, Wi even and
+ *   >= 8, B >= 1, B Hi Wi < 2^31.  Exact f32 products on the matrix cores.  The list of (frame, output row, 64-pixel segment)
+ *   units is cut into fpc_stem_wgrad_slices(B, Hi, Wi) contiguous slices — a function of the shape alone —, one partial
+ *   [64][224] per slice, added in slice order in double.  ws: fpc_stem_wgrad_workspace_bytes(B, Hi, Wi) = slices * 64 * 224 * 4
+ *   bytes, 256-byte aligned (misaligned: FPC_EINVAL; too small: FPC_EWORKSPACE).  Slices and bytes of a refused shape are 0.
+ *   Replaces the weight gradient of conv1 (cuDNN under autograd, F/lib/pose_regressor.py:608).
+ * fpc_maxpool3x3s2_fwd (k_maxpool3x3s2): x NHWC [B][Hi][Wi][C] -> y [B][(Hi - 1) / 2 + 1][(Wi - 1) / 2 + 1][C].
+ * fpc_maxpool3x3s2_bwd (k_maxpool3x3s2_bwd): dx [B][Hi][Wi][C] from x and dy (y's shape), every element written once: dy of each
+ *   window goes to the window's FIRST maximum in row-major order over its in-bounds elements (torch's rule), contributions added
+ *   in (window row, window column) order.  Shape class of both: Hi, Wi >= 1, C >= 4 and C % 4 == 0, B Hi Wi C < 2^32.  Inputs
+ *   are finite: NaN is outside the contract.  Replace encoder.maxpool (F/lib/pose_regressor.py:608), aten forward / backward. */
+int fpc_image_nhwc4(const float* x, float* out, int B, int H, int W, fpc_stream_t stream);
+size_t fpc_stem_wgrad_workspace_bytes(int B, int Hi, int Wi);
+int fpc_stem_wgrad_slices(int B, int Hi, int Wi);
+int fpc_stem_wgrad(const float* img4, const float* dy, float* dw, int B, int Hi, int Wi, void* ws, size_t ws_bytes,
+                   fpc_stream_t stream);
+int fpc_maxpool3x3s2_fwd(const float* x, float* y, int B, int Hi, int Wi, int C, fpc_stream_t stream);
+int fpc_maxpool3x3s2_bwd(const float* x, const float* dy, float* dx, int B, int Hi, int Wi, int C, fpc_stream_t stream);
+
 /* Weight gradient of a convolution for the training step (BASELINE.json configs[4]; the reference leaves the
  * convolutions' backward to cuDNN through autograd, F/lib/pose_regressor.py:709-743 under Lightning's backward).
  * x: input [B,Hi,Wi,Cin] channel-last (channel stride 1; element strides sb, sh, sw multiples of 4; 16-byte aligned),
