@@ -71,6 +71,11 @@ _SIGNATURES = {
     "fpc_png_info": (_i, [_vp, _sz, ctypes.POINTER(ctypes.c_int32)]),
     "fpc_png_decode": (_i, [_vp, _sz, _vp, _sz, _i]),
     "fpc_png_decode_batch": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_sz), _i, _vp, _i, _i, _i]),
+    "fpc_inflate_host": (_i, [_vp, _sz, _vp, _sz, ctypes.POINTER(_sz)]),
+    "fpc_png_pack_bytes": (_sz, [_i, _i, _i]),
+    "fpc_png_pack_batch": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_sz), _i, _i, _i, _i, _vp, _sz, _vp, ctypes.POINTER(_sz)]),
+    "fpc_png_decode_device_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "fpc_png_decode_device": (_i, [_vp, _sz, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _sz, _vp]),
     "fpc_gt_build": (_i, [_vp, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     "fpc_depth_decode": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "fpc_net_create": (_i, [ctypes.c_char_p, _i, _i, _i, _i, ctypes.POINTER(_vp)]),

@@ -13,7 +13,8 @@ File decoding (:158-176: skimage.io.imread of `*_color.png` / `*_mask.png`, cv2.
 (csrc/png_decode.hip over zlib; libpng's headers are not in the image): `imread_png` returns what imread returns,
 `read_frame_files` mirrors the first lines of `__getitem__` (image, mask with background 255 -> 0, standardised depth),
 and `FrameUploader.upload_png` decodes a batch of colour files straight into its pinned staging slot on a few host
-threads.
+threads.  Opt-in, `upload_png(..., decode="device")` of both uploaders leaves the host the container walk and one copy of
+the compressed bytes: csrc/png_device.hip inflates and un-filters on the uploader's stream.
 
 The ground-truth half of a dataset item (round 4, SURVEY.md 8f rank 3 remainder): `NOCSDataset` / `CAMERADataset` /
 `REALDataset` mirror F/tools/dataset.py:99-434 — the directory walk for `*_color.png` frames with wanted instances
@@ -134,6 +135,65 @@ def read_frame_files(color_path, camera=True):
     return out
 
 
+class _DevicePngDecoder:
+    """One slot of the device decode path (csrc/png_device.hip): a pinned staging buffer for the COMPRESSED bytes of up to `n`
+    files, their descriptors and statuses.  `pack` is the host's whole share (container walk, CRCs, one copy of the IDAT
+    payloads); `enqueue` puts the copy, the two kernels and the status read-back on the current stream."""
+
+    def __init__(self, n, height, width, device):
+        L = nat.lib()
+        self.n, self.H, self.W, self.device = int(n), int(height), int(width), device
+        nbytes = int(L.fpc_png_pack_bytes(self.n, self.H, self.W))
+        if nbytes < 1:
+            raise ValueError("no device PNG decode for %d files of %d x %d" % (n, height, width))
+        self.z_host = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+        self.z_dev = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        self.desc_host = torch.zeros((self.n, 8), dtype=torch.int64).pin_memory()
+        self.desc_dev = torch.empty((self.n, 8), dtype=torch.int64, device=device)
+        self.status_host = torch.zeros(self.n, dtype=torch.int32).pin_memory()
+        self.status_dev = torch.empty(self.n, dtype=torch.int32, device=device)
+        self._desc_np, self._status_np = self.desc_host.numpy(), self.status_host.numpy()
+        self.done = None                     # event: the statuses of the last enqueue are in status_host
+        self.count = 0
+
+    def wait(self):
+        """The pinned buffers are free to be rewritten; RuntimeError for a file of the last enqueue that did not decode."""
+        if self.done is None:
+            return
+        self.done.synchronize()
+        self.done = None
+        bad = np.nonzero(self._status_np[:self.count])[0]
+        if bad.size:
+            raise RuntimeError("device PNG decode failed for file %d of the batch (status %d, include/fpc.h FPC_INF_* / FPC_PNG_*)"
+                               % (int(bad[0]), int(self._status_np[bad[0]])))
+
+    def pack(self, files, mode):
+        """-> (bytes to copy, largest bytes-per-pixel); the caller has called wait()."""
+        B = len(files)
+        bufs = [np.frombuffer(f, dtype=np.uint8) for f in files]
+        ptrs = (ctypes.c_void_p * B)(*[b.ctypes.data for b in bufs])
+        sizes = (ctypes.c_size_t * B)(*[b.size for b in bufs])
+        used = ctypes.c_size_t(0)
+        nat.check(nat.lib().fpc_png_pack_batch(ptrs, sizes, B, self.H, self.W, int(mode), self.z_host.data_ptr(), self.z_host.numel(),
+                                               self.desc_host.data_ptr(), ctypes.byref(used)), "fpc_png_pack_batch")
+        d = self._desc_np[:B]
+        self.count = B
+        return int(used.value), int((d[:, 4] * d[:, 6] // 8).max())
+
+    def enqueue(self, used, max_bpp, mode, out, frame_bytes):
+        """On the current stream: compressed bytes to the device, decode into `out` (file i at i * frame_bytes), statuses back."""
+        B, L = self.count, nat.lib()
+        self.z_dev[:used].copy_(self.z_host[:used], non_blocking=True)
+        self.desc_dev[:B].copy_(self.desc_host[:B], non_blocking=True)
+        ws = nat.workspace("pngdev", self.device, L.fpc_png_decode_device_workspace_bytes(B, self.H, self.W, max_bpp))
+        nat.check(L.fpc_png_decode_device(nat.ptr(self.z_dev), used, nat.ptr(self.desc_dev), B, self.H, self.W, int(mode), max_bpp,
+                                          nat.ptr(out), int(frame_bytes), nat.ptr(self.status_dev), nat.ptr(ws), ws.numel(),
+                                          nat.stream()), "fpc_png_decode_device")
+        self.status_host[:B].copy_(self.status_dev[:B], non_blocking=True)
+        self.done = torch.cuda.Event()
+        self.done.record()
+
+
 class FrameUploader:
     """Host frames -> network tensors: pinned staging + asynchronous H2D copy + preprocess_frames, buffered `slots` deep
     on its own HIP stream so the copy of batch i+1 overlaps the network of batch i.  `upload(frames)` returns
@@ -159,6 +219,7 @@ class FrameUploader:
         self._out = [torch.empty((batch, 3, height, width), dtype=torch.float32, device=self.device) for _ in range(slots)]
         self._free = [None] * slots          # event: the slot's previous output has been consumed
         self._busy = [None] * slots          # event: the slot's H2D copy has left the pinned buffer
+        self._png = [None] * slots           # decode="device": the slot's _DevicePngDecoder, built at first use
         self._i = 0
 
     def upload(self, frames, consumed=None):
@@ -172,14 +233,27 @@ class FrameUploader:
         np.copyto(self._host_np[k], src)
         return self._enqueue(k, consumed)
 
-    def upload_png(self, files, consumed=None, threads=4):
+    def upload_png(self, files, consumed=None, threads=4, decode="host"):
         """files: B PNG files as bytes (`*_color.png`, all of the uploader's H x W): decoded by `threads` host threads
-        straight into the pinned staging slot (fpc_png_decode_batch: RGB8, alpha dropped), then the same copy and kernels."""
+        straight into the pinned staging slot (fpc_png_decode_batch: RGB8, alpha dropped), then the same copy and kernels.
+        decode="device": the host only walks the containers and copies the compressed bytes; inflate and un-filter run on
+        the uploader's stream (fpc_png_decode_device, mode 3), then the same preprocessing.  A file that does not decode
+        raises RuntimeError at the next upload_png on its slot or at check_decoded(), whichever comes first."""
+        if decode not in ("host", "device"):
+            raise ValueError("decode must be 'host' or 'device'")
         k = self._i % len(self._host)
         self._i += 1
         B, H, W, _ = self._host_np[k].shape
         if len(files) != B:
             raise ValueError(f"expected {B} files, got {len(files)}")
+        if self._png[k] is not None:
+            self._png[k].wait()
+        if decode == "device":
+            if self._png[k] is None:
+                self._png[k] = _DevicePngDecoder(B, H, W, self.device)
+            dec = self._png[k]
+            used, max_bpp = dec.pack(files, 3)
+            return self._enqueue(k, consumed, lambda: dec.enqueue(used, max_bpp, 3, self._dev[k], H * W * 3))
         if self._busy[k] is not None:
             self._busy[k].synchronize()
         bufs = [np.frombuffer(f, dtype=np.uint8) for f in files]
@@ -189,11 +263,20 @@ class FrameUploader:
                   "fpc_png_decode_batch")
         return self._enqueue(k, consumed)
 
-    def _enqueue(self, k, consumed):
-        with torch.cuda.stream(self.stream):
+    def check_decoded(self):
+        """Synchronises with every device decode enqueued so far; RuntimeError for a file that did not decode."""
+        for dec in self._png:
+            if dec is not None:
+                dec.wait()
+
+    def _enqueue(self, k, consumed, device_png=None):
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
             if self._free[k] is not None:
                 self.stream.wait_event(self._free[k])
-            self._dev[k].copy_(self._host[k], non_blocking=True)
+            if device_png is not None:
+                device_png()                 # compressed bytes up, frames decoded into _dev[k]
+            else:
+                self._dev[k].copy_(self._host[k], non_blocking=True)
             self._busy[k] = torch.cuda.Event()
             self._busy[k].record()
             preprocess_frames(self._dev[k], self.params, out=self._out[k])
@@ -602,6 +685,7 @@ class GroundTruthUploader:
         self._busy = [None] * slots          # event: the slot's H2D copies have left the pinned buffers
         self._i = 0
         self._pool = None
+        self._png = [[None, None] for _ in range(slots)]      # decode="device": the slot's mask and depth _DevicePngDecoder
 
     def _carve(self, raw, view):
         """(sample_ids, first_row, row_of, class_of) views of the integer buffer."""
@@ -641,11 +725,19 @@ class GroundTruthUploader:
             np.copyto(s['depth_host'].numpy()[:flat.size], flat)
         return self._enqueue(k, items, consumed, kind)
 
-    def upload_png(self, mask_files, items, consumed=None, threads=4, depth_files=None):
+    def upload_png(self, mask_files, items, consumed=None, threads=4, depth_files=None, decode="host"):
         """mask_files: the B' `*_mask.png` files as bytes, decoded as stored (fpc_png_decode mode 0) by `threads` host
         threads straight into the pinned slot; their size and channel count must be the uploader's (ValueError).
-        depth_files (with_depth): the `*_depth.png` files, all 16-bit grey or all colour-coded."""
+        depth_files (with_depth): the `*_depth.png` files, all 16-bit grey or all colour-coded.
+        decode="device": the compressed bytes are uploaded and fpc_png_decode_device (mode 0) writes the planes the host
+        path would have copied; a file that does not decode raises RuntimeError at the next upload_png on its slot or
+        at check_decoded()."""
+        if decode not in ("host", "device"):
+            raise ValueError("decode must be 'host' or 'device'")
         k, s = self._next_slot(items)
+        for dec in self._png[k]:
+            if dec is not None:
+                dec.wait()
         B = len(items)
         if len(mask_files) != B:
             raise ValueError(f"{B} items, {len(mask_files)} mask files")
@@ -665,6 +757,18 @@ class GroundTruthUploader:
             kind = self._depth_kind(bits, ch)
             nbytes = H * W * ch * bits // 8
             jobs += [(f, s['depth_host'].numpy()[j * nbytes:(j + 1) * nbytes]) for j, f in enumerate(depth_files)]
+        if decode == "device":
+            decs = self._png[k]
+            for j in range(2 if kind is not None else 1):
+                if decs[j] is None:
+                    decs[j] = _DevicePngDecoder(self.shape[0], H, W, self.device)
+            packed = [decs[0].pack(mask_files, 0)] + ([decs[1].pack(depth_files, 0)] if kind is not None else [])
+
+            def device_png():
+                decs[0].enqueue(*packed[0], 0, s['ids_dev'], H * W * C)
+                if kind is not None:
+                    decs[1].enqueue(*packed[1], 0, s['depth_dev'], nbytes)
+            return self._enqueue(k, items, consumed, kind, device_png)
         if threads > 1 and len(jobs) > 1:
             if self._pool is None or self._pool[0] != int(threads):      # kept between uploads: starting threads costs a decode
                 from concurrent.futures import ThreadPoolExecutor
@@ -696,7 +800,14 @@ class GroundTruthUploader:
             return 0, channels
         raise ValueError("unsupported depth image")
 
-    def _enqueue(self, k, items, consumed, depth_kind):
+    def check_decoded(self):
+        """Synchronises with every device decode enqueued so far; RuntimeError for a file that did not decode."""
+        for decs in self._png:
+            for dec in decs:
+                if dec is not None:
+                    dec.wait()
+
+    def _enqueue(self, k, items, consumed, depth_kind, device_png=None):
         s = self._slots[k]
         B, (_, H, W, C) = len(items), self.shape
         row_of, class_of, first_row, n = gt_tables(items)
@@ -716,10 +827,13 @@ class GroundTruthUploader:
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
             if self._free[k] is not None:
                 self.stream.wait_event(self._free[k])
-            s['ids_dev'][:B].copy_(s['ids_host'][:B], non_blocking=True)
+            if device_png is not None:
+                device_png()                 # compressed bytes up, id (and depth) planes decoded into ids_dev / depth_dev
+            else:
+                s['ids_dev'][:B].copy_(s['ids_host'][:B], non_blocking=True)
             s['int_dev'].copy_(s['int_host'], non_blocking=True)
             s['f64_dev'].copy_(s['f64_host'], non_blocking=True)
-            if depth_kind is not None:
+            if depth_kind is not None and device_png is None:
                 used = B * H * W * (2 if depth_kind[0] == 1 else depth_kind[1])
                 s['depth_dev'][:used].copy_(s['depth_host'][:used], non_blocking=True)
             self._busy[k] = torch.cuda.Event()

@@ -24,6 +24,7 @@
  *   fpc_net_*                    lib/pose_regressor.py:709-743 (+ segmentation_models_pytorch encoder/decoder/head)
  *   fpc_preprocess_u8            tools/dataset.py:249-262 (preprocessing_fn, transpose, / max|.|, img_as_float32)
  *   fpc_png_info / _decode / _decode_batch   tools/dataset.py:158-176 (skimage.io.imread / cv2.imread of *_color / *_mask / *_depth.png)
+ *   fpc_png_pack_batch / _decode_device      the same files, inflated and un-filtered on the device (opt-in)
  *   fpc_gt_build / fpc_depth_decode   tools/dataset.py:183-228, 373-434 (class filter and instance_masks of a sample), data_manipulation.py:153-163
  *   fpc_pose_errors              lib/gpu_tensor_funcs.py:411-476, 486-547, 563-565 (degree error, 3-D IoU, offset error)
  *   fpc_pose_metrics_update      lib/metrics.py:11-260, lib/gpu_tensor_funcs.py:611-713, evaluate.py:238-292 (metric accumulators, APs)
@@ -55,6 +56,7 @@ extern "C" {
  * and form -9's packed patch geometry (fpc_wino_pack_geometry, fpc_net_set_wino_pack, fpc_net_wino_blocks, fpc_conv2d's -10):
  * and the activation-range guard of the fp16-piece forms (fpc_act_range, fpc_net_survey_next, fpc_net_guard_ranges, fpc_net_guarded):
  * and the ground-truth batch builder (fpc_gt_build, fpc_depth_decode):
+ * and the device PNG decode (fpc_inflate_host, fpc_png_pack_bytes, fpc_png_pack_batch, fpc_png_decode_device and its _workspace_bytes):
  * additions only, every earlier entry point keeps its behaviour. */
 #define FPC_ABI_VERSION 11
 
@@ -285,6 +287,65 @@ int fpc_preprocess_u8(const uint8_t* img_hwc, int B, int H, int W, const double*
 int fpc_png_info(const uint8_t* data, size_t nbytes, int32_t* out5);
 int fpc_png_decode(const uint8_t* data, size_t nbytes, void* out, size_t out_bytes, int mode);
 int fpc_png_decode_batch(const uint8_t* const* datas, const size_t* sizes, int n, uint8_t* out, int H, int W, int threads);
+
+/* ---- frame decoding, DEVICE side (ABI 11 addition; opt-in, the host decoder above is untouched) --------------------
+ * The host walks the container and copies the COMPRESSED bytes; the device inflates (csrc/inflate.hpp, RFC 1950/1951,
+ * no zlib) and un-filters (csrc/png_device.hip: k_png_inflate, one wave per file; k_png_unfilter).
+ *
+ * fpc_inflate_host: the same inflate.hpp on the host.  `in` [zbytes]: a zlib stream; `out` [cap]: cap is the EXPECTED
+ * size (a PNG's H (1 + W bpp)); *out_len (may be NULL) = bytes produced, also on failure.  Returns 0, FPC_EINVAL, or a
+ * positive FPC_INF_* status, one per failure class.  Reads only [in, in + zbytes), writes only [out, out + cap); total
+ * work is bounded by a constant times 8 zbytes + cap for any bytes.
+ *
+ * fpc_png_pack_batch: HOST.  n files of ONE size H x W (mode 0: also one bit depth and one mode-0 channel count), else
+ * FPC_EINVAL with nothing written.  Signature, IHDR and every chunk CRC are checked as fpc_png_decode does (FPC_EFORMAT);
+ * the IDAT payloads of file i are copied back to back to staging + desc[i][0] (a multiple of 16; the slice is zero-
+ * padded to 16 bytes and, for a palette file, followed by 768 palette bytes).  staging: 16-byte aligned (pinned, for
+ * an asynchronous copy), *used = bytes to copy to the device.  FPC_EWORKSPACE when staging_bytes does not hold the
+ * payloads.  desc: int64 [n][FPC_PNG_DESC_WORDS] = {staging offset, compressed bytes, width, height, bit depth,
+ * colour type, channels per pixel in the file, palette entries}.
+ * fpc_png_pack_bytes(n, H, W): a staging size for n files, per file the raw scanlines at 8 bytes a pixel + 1/8 + 1024 +
+ * the palette: no deflate stream that carries data can exceed it (stored blocks cost 5 bytes per 65535); a file padded
+ * with empty blocks beyond it is refused by fpc_png_pack_batch with FPC_EWORKSPACE.
+ *
+ * fpc_png_decode_device: staging [staging_bytes] and desc as packed, DEVICE copies.  out: DEVICE, file i at
+ * out + i * frame_bytes: mode 3 RGB8 [H][W][3] as fpc_png_decode mode 3; mode 0 the samples as stored (u16 LITTLE-
+ * endian for 16-bit files, a palette expanded to RGB8).  status i32 [n] DEVICE: 0, an FPC_INF_* status, FPC_PNG_EDESC
+ * (a descriptor that does not fit the call: size, max_bpp, staging_bytes, frame_bytes) or FPC_PNG_EFILTER (a filter
+ * byte > 4); a file with a non-zero status leaves its frame of `out` unwritten (FPC_PNG_EFILTER: written, the row read
+ * as filter 0) and never touches another file's bytes.  max_bpp: the largest bytes-per-pixel among the files (1 .. 8);
+ * workspace >= fpc_png_decode_device_workspace_bytes(n, H, W, max_bpp), 16-byte aligned.  W * max_bpp <= 32768.
+ * FPC_EINVAL before any launch: NULL or misaligned pointers (staging, out, workspace 16; desc 8; status 4), n < 1,
+ * any total size from 2^31 bytes on.  Results are bit-identical run to run.  No synchronisation. */
+#define FPC_PNG_DESC_WORDS 8
+#define FPC_INF_ETRUNCATED 1
+#define FPC_INF_EBLOCK_TYPE 2
+#define FPC_INF_ESTORED_LEN 3
+#define FPC_INF_EOVERSUBSCRIBED 4
+#define FPC_INF_EINCOMPLETE 5
+#define FPC_INF_EREPEAT_FIRST 6
+#define FPC_INF_ELITLEN_SYMBOL 7
+#define FPC_INF_EDIST_SYMBOL 8
+#define FPC_INF_EDIST_TOO_FAR 9
+#define FPC_INF_EOUT_OVERFLOW 10
+#define FPC_INF_EOUT_SHORT 11
+#define FPC_INF_EADLER 12
+#define FPC_INF_EFDICT 13
+#define FPC_INF_EMETHOD 14
+#define FPC_INF_EFCHECK 15
+#define FPC_INF_ELENGTHS_OVERRUN 16
+#define FPC_INF_ENO_END_CODE 17
+#define FPC_INF_EBAD_CODE 18
+#define FPC_PNG_EDESC 20
+#define FPC_PNG_EFILTER 21
+int fpc_inflate_host(const uint8_t* in, size_t zbytes, uint8_t* out, size_t cap, size_t* out_len);
+size_t fpc_png_pack_bytes(int n, int H, int W);
+int fpc_png_pack_batch(const uint8_t* const* datas, const size_t* sizes, int n, int H, int W, int mode, uint8_t* staging,
+                       size_t staging_bytes, int64_t* desc, size_t* used);
+size_t fpc_png_decode_device_workspace_bytes(int n, int H, int W, int max_bpp);
+int fpc_png_decode_device(const uint8_t* staging, size_t staging_bytes, const int64_t* desc, int n, int H, int W, int mode,
+                          int max_bpp, void* out, size_t frame_bytes, int32_t* status, void* workspace, size_t workspace_bytes,
+                          fpc_stream_t stream);
 
 /* ---- ground-truth side: instance-id masks -> the batch's class mask and per-instance planes (ABI 11 addition) -------
  * tools/dataset.py: __getitem__'s class filter and generate_agg_data's instance_masks for B frames in one launch
