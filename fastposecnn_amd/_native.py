@@ -81,6 +81,7 @@ _SIGNATURES = {
     "fpc_net_create": (_i, [ctypes.c_char_p, _i, _i, _i, _i, ctypes.POINTER(_vp)]),
     "fpc_net_create_encoder": (_i, [_i, ctypes.POINTER(_i), _i, _i, _i, _i, ctypes.POINTER(_vp)]),
     "fpc_net_create_encoder_ex": (_i, [_i, ctypes.POINTER(_i), _i, _i, _i, _i, _i, _i, ctypes.POINTER(_vp)]),
+    "fpc_net_create_encoder_se": (_i, [ctypes.POINTER(_i), _i, _i, _i, _i, _i, ctypes.POINTER(_vp)]),
     "fpc_net_destroy": (None, [_vp]),
     "fpc_net_set_graph": (_i, [_vp, _i]),
     "fpc_net_set_split_precision": (_i, [_vp, _i]),
@@ -133,6 +134,11 @@ _SIGNATURES = {
     "fpc_stem_wgrad": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
     "fpc_maxpool3x3s2_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "fpc_maxpool3x3s2_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "fpc_se_pool_slabs": (_i, [_i, _i, _i]),
+    "fpc_se_scratch_floats": (_sz, [_i, _i, _i, _i]),
+    "fpc_se_gate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "fpc_se_scale_add_relu": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "fpc_maxpool3x3s2_ceil_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "fpc_conv2d_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "fpc_upsample_bilinear_fwd": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "fpc_upsample_bilinear_bwd_scratch_floats": (_sz, [_i, _i, _i, _i, _i]),

@@ -5,7 +5,8 @@
 // The graph is the one segmentation_models_pytorch builds for FastPoseCNN
 // (encoder = ResNet BasicBlock x {2,2,2,2} or {3,4,6,3}, or Bottleneck x {3,4,6,3} / {3,4,23,3} / {3,8,36,3} whose 1x1 sites
 // may run on k_conv1x1 (pointwise.hip) and whose conv2, in the ResNeXt encoders, is a grouped 3x3 on k_conv3x3_grouped
-// (conv_grouped.hip); four FPN decoders, merge "add";
+// (conv_grouped.hip), or the SE-ResNet Bottleneck x {3,4,6,3} / {3,4,23,3} / {3,8,36,3}: the stride on conv1, a dense 3x3 conv2 and the
+// squeeze-and-excitation gate of se.hip between bn3 and the residual add; four FPN decoders, merge "add";
 // four 1x1 heads + x4 bilinear), see fastposecnn_amd/lib/backbone.py.  The plan owns no device
 // memory: packed weights, activations and split-K scratch live in one caller-provided workspace.
 // Launch order per frame (R18): stem conv, max-pool, 16 encoder convs (+3 downsample 1x1) with
@@ -260,6 +261,7 @@ struct fpc_net {
     int classes, B, H, W;
     int expansion = 1;            // 1: BasicBlock encoder, 4: Bottleneck (1x1, 3x3 with the stride, 1x1 x 4)
     int groups = 1, width = 64;   // Bottleneck: conv2's groups and torchvision's width_per_group (ResNeXt: 32 and 4 / 8); (1, 64) = ResNet
+    int se = 0;                   // > 0: the SE-ResNet Bottleneck (pretrainedmodels.senet) with this reduction; expansion is 4 then
     std::vector<std::string> pnames;
     std::vector<int64_t> pnumel;
     std::vector<const float*> pptr;
@@ -274,7 +276,7 @@ struct fpc_net {
 
     // conv indices
     int c_stem = -1;
-    struct Block { int conv1, conv2, ds, conv3 = -1; };      // conv3: Bottleneck only
+    struct Block { int conv1, conv2, ds, conv3 = -1; int p_se = -1; };      // conv3: Bottleneck only; p_se: first of se_module's (fc1.weight, fc1.bias, fc2.weight, fc2.bias)
     std::vector<Block> blocks[4];
     struct Dec {
         int lat[4];               // p5, p4, p3, p2 (1x1, bias)
@@ -297,6 +299,7 @@ struct fpc_net {
     Act a_lsum[4];                // two-pass merge + head: the head of the three upsampled branches' sum at their own resolution
     int merge_split = -1;         // -1: two passes unless FPC_MERGE_SPLIT=0, 0: k_merge_head (one pass), 1: two passes
     size_t splitk_off = 0, splitk_floats = 0;
+    size_t se_gate_off = 0, se_part_off = 0;      // SE plans: gate [B][2048] and the slab partials of the stage that needs most (k_se_pool / k_se_excite)
     int use_graph = 0;            // replay the frame-invariant launches as a HIP graph (fpc_net_set_graph)
     long long wino_blocks = 0;    // workgroups of the form-9 launches of the last forward that launched its kernels (fpc_net_wino_blocks)
     int wino_pack = 1;            // form-9 launches cut their patches out of canvas rows of several frames where that saves patches (fpc_net_set_wino_pack)
@@ -390,6 +393,11 @@ extern "C" int fpc_net_create(const char* encoder, int classes, int B, int H, in
     if (!strcmp(encoder, "resnext50_32x4d")) return fpc_net_create_encoder_ex(4, r34, 32, 4, classes, B, H, W, out);
     if (!strcmp(encoder, "resnext101_32x4d")) return fpc_net_create_encoder_ex(4, r101, 32, 4, classes, B, H, W, out);
     if (!strcmp(encoder, "resnext101_32x8d")) return fpc_net_create_encoder_ex(4, r101, 32, 8, classes, B, H, W, out);
+    // the SE-ResNets: pretrainedmodels' SEResNetBottleneck x {3,4,6,3} / {3,4,23,3} / {3,8,36,3}, reduction 16
+    const int r152[4] = {3, 8, 36, 3};
+    if (!strcmp(encoder, "se_resnet50")) return fpc_net_create_encoder_se(r34, 16, classes, B, H, W, out);
+    if (!strcmp(encoder, "se_resnet101")) return fpc_net_create_encoder_se(r101, 16, classes, B, H, W, out);
+    if (!strcmp(encoder, "se_resnet152")) return fpc_net_create_encoder_se(r152, 16, classes, B, H, W, out);
     if (strcmp(encoder, "resnet18") && strcmp(encoder, "resnet34")) return FPC_EINVAL;
     return fpc_net_create_encoder(1, strcmp(encoder, "resnet18") ? r34 : r18, classes, B, H, W, out);
 }
@@ -423,6 +431,22 @@ extern "C" int fpc_net_create_encoder_ex(int block, const int* layers4, int grou
     return net_build(n, classes, B, H, W, out);
 }
 
+// The SE-ResNet encoders: SEResNetBottleneck x layers4 — conv1 1x1 WITH the stride, conv2 a dense 3x3 / stride 1 (a Winograd site at
+// every stage), conv3 1x1 x 4 with BatchNorm only, then the gate of se.hip (fc1 C -> C / reduction, fc2 back, both with bias) and the
+// scale + residual + ReLU pass; parameters named as pretrainedmodels' (encoder.layer0.conv1.weight, encoder.layerN.i.se_module.fc1.bias).
+// Refused: a reduction that does not divide 256 (the narrowest stage output).
+extern "C" int fpc_net_create_encoder_se(const int* layers4, int reduction, int classes, int B, int H, int W, fpc_net_t** out) {
+    if (!layers4 || !out || classes < 2 || classes > 8 || B < 1 || H < 32 || W < 32 || H % 32 || W % 32) return FPC_EINVAL;
+    for (int L = 0; L < 4; ++L)
+        if (layers4[L] < 1 || layers4[L] > 64) return FPC_EINVAL;
+    if (reduction < 1 || 256 % reduction) return FPC_EINVAL;
+    fpc_net* n = new fpc_net();
+    memcpy(n->layers, layers4, sizeof(n->layers));
+    n->expansion = 4;
+    n->se = reduction;
+    return net_build(n, classes, B, H, W, out);
+}
+
 static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** out) {
     n->classes = classes; n->B = B; n->H = H; n->W = W;
     {   // merge + head in two passes (merge_split.hip) unless FPC_MERGE_SPLIT=0; read once, here
@@ -432,7 +456,8 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
     char buf[256];
 
     // ---- parameters + packed storage (persistent region first)
-    n->c_stem = n->add_conv("encoder.conv1.weight", 3, 64, 7, 2, 3, "encoder.bn1", nullptr, 4, 8);     // NHWC4 pixels, 8 taps per row
+    n->c_stem = n->se ? n->add_conv("encoder.layer0.conv1.weight", 3, 64, 7, 2, 3, "encoder.layer0.bn1", nullptr, 4, 8)
+                      : n->add_conv("encoder.conv1.weight", 3, 64, 7, 2, 3, "encoder.bn1", nullptr, 4, 8);     // NHWC4 pixels, 8 taps per row
     const int planes[4] = {64, 128, 256, 512};
     const int e = n->expansion;
     int inpl = 64;
@@ -442,6 +467,22 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
             fpc_net::Block blk;
             snprintf(buf, sizeof(buf), "encoder.layer%d.%d", L + 1, bi);
             std::string p(buf);
+            if (n->se) {      // SE Bottleneck: 1x1 (stride) -> 3x3 -> 1x1 x 4 -> gate, pretrainedmodels' parameter order
+                const int C = 4 * planes[L], Cr = C / n->se;
+                blk.conv1 = n->add_conv(p + ".conv1.weight", inpl, planes[L], 1, stride, 0, (p + ".bn1").c_str(), nullptr);
+                blk.conv2 = n->add_conv(p + ".conv2.weight", planes[L], planes[L], 3, 1, 1, (p + ".bn2").c_str(), nullptr);
+                blk.conv3 = n->add_conv(p + ".conv3.weight", planes[L], C, 1, 1, 0, (p + ".bn3").c_str(), nullptr);
+                blk.p_se = n->add_param(p + ".se_module.fc1.weight", (int64_t)Cr * C);      // plain parameters, read in place
+                n->add_param(p + ".se_module.fc1.bias", Cr);
+                n->add_param(p + ".se_module.fc2.weight", (int64_t)C * Cr);
+                n->add_param(p + ".se_module.fc2.bias", C);
+                blk.ds = -1;
+                if (stride != 1 || inpl != C)
+                    blk.ds = n->add_conv(p + ".downsample.0.weight", inpl, C, 1, stride, 0, (p + ".downsample.1").c_str(), nullptr);
+                inpl = C;
+                n->blocks[L].push_back(blk);
+                continue;
+            }
             if (e == 4) {      // Bottleneck: 1x1 -> 3x3 (stride) -> 1x1 x 4, torchvision's parameter order
                 const int C = 4 * planes[L];
                 const int mid = planes[L] * n->width / 64 * n->groups;      // ResNet: planes[L]
@@ -524,7 +565,8 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
     int h1 = conv_out(H, 7, 2, 3), w1 = conv_out(W, 7, 2, 3);
     n->a_img4 = n->alloc_act(H, W, 4);
     n->a_stem = n->alloc_act(h1, w1, 64);
-    int hp = conv_out(h1, 3, 2, 1), wp = conv_out(w1, 3, 2, 1);
+    // (the SE-ResNet stem pool has no padding and ceil_mode: h1 / 2 — the same size for the even h1 every plan has, other windows)
+    int hp = n->se ? h1 / 2 : conv_out(h1, 3, 2, 1), wp = n->se ? w1 / 2 : conv_out(w1, 3, 2, 1);
     n->a_pool = n->alloc_act(hp, wp, 64);
     int fh[4], fw[4];
     {
@@ -539,7 +581,9 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
                 // predecessor's as input and residual); the last block's is the stage's feature map
                 const int C = 4 * planes[L];
                 const int mid = planes[L] * n->width / 64 * n->groups;
-                const Act t1 = n->alloc_act(hin, win, mid), t2 = n->alloc_act(h, w, mid);
+                // (SE: conv1 carries the stride, so its output is at the stage's OUTPUT resolution in every block; conv3 writes the
+                // pre-gate tensor into the block's own output, which the scale pass then rewrites in place)
+                const Act t1 = n->se ? n->alloc_act(h, w, mid) : n->alloc_act(hin, win, mid), t2 = n->alloc_act(h, w, mid);
                 const Act y[2] = {n->alloc_act(h, w, C), n->alloc_act(h, w, C)};
                 const Act dd = n->alloc_act(h, w, C);
                 for (int bi = 0; bi < n->layers[L]; ++bi) {
@@ -558,6 +602,12 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
                 n->a_blk_d[L].push_back(n->blocks[L][bi].ds >= 0 ? n->alloc_act(h, w, planes[L]) : Act());
             }
         }
+    }
+    if (n->se) {      // the gate of one block at a time: [B][C] and the slab partials of the stage with the most
+        size_t part = 0;
+        for (int L = 0; L < 4; ++L) part = std::max(part, (size_t)se_pool_slabs(fh[L], fw[L], 4 * planes[L]) * 4 * planes[L]);
+        n->se_gate_off = n->alloc((size_t)B * 4 * planes[3]);
+        n->se_part_off = n->alloc((size_t)B * part);
     }
     // FPN needs exact x2 relations between levels
     for (int L = 1; L < 4; ++L)
@@ -1118,7 +1168,11 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
         auto pool_launch = [&]() {
             return launch_maxpool3x3s2(ws + n->a_stem.off, ws + n->a_pool.off, B, n->a_stem.H, n->a_stem.W, 64, n->a_pool.H, n->a_pool.W, s);
         };
-        if (n->cplan[n->c_stem].pool && !n->tuning) {      // one launch to the pooled tensor: a_stem is not written
+        if (n->se) {      // the SE-ResNet stem: its pool has no padding (k_stem_pool_h3 is a pad-1 kernel: neither tuned nor forced here)
+            n->cplan[n->c_stem].pool = 0;
+            FPC_TRY(run_conv(n, a, 1, n->c_stem, s));
+            FPC_TRY(launch_maxpool3x3s2_ceil(ws + n->a_stem.off, ws + n->a_pool.off, B, n->a_stem.H, n->a_stem.W, 64, s));
+        } else if (n->cplan[n->c_stem].pool && !n->tuning) {      // one launch to the pooled tensor: a_stem is not written
             if (n->survey) FPC_TRY(survey_site(n, a, n->cplan[n->c_stem], 1, n->c_stem, s));      // (not through run_conv: the image)
             FPC_TRY(launch_stem_pool(a, h3img, ws + n->a_pool.off, n->a_pool.H, n->a_pool.W, s));
         } else {
@@ -1159,6 +1213,24 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
             const Act& T = n->a_blk_t[L][bi];
             const Act& Y = n->a_blk_y[L][bi];
             const float* res = ws + cur.off;
+            if (n->se) {
+                // SE Bottleneck: conv1 (1x1 with the stride, BN + ReLU) -> conv2 (3x3, BN + ReLU), the downsample (1x1, stride, BN),
+                // conv3 (1x1, BN only) into Y, the gate from Y's channel means, then Y = relu(Y * gate + residual) in place
+                const Act& T2 = n->a_blk_t2[L][bi];
+                FPC_TRY(enc_conv(blk.conv1, cur, T, true, nullptr));
+                FPC_TRY(enc_conv(blk.conv2, T, T2, true, nullptr));
+                if (blk.ds >= 0) {
+                    FPC_TRY(enc_conv(blk.ds, cur, n->a_blk_d[L][bi], false, nullptr));
+                    res = ws + n->a_blk_d[L][bi].off;
+                }
+                FPC_TRY(enc_conv(blk.conv3, T2, Y, false, nullptr));
+                FPC_TRY(launch_se_pool(ws + Y.off, ws + n->se_part_off, B, Y.H, Y.W, Y.C, s));
+                FPC_TRY(launch_se_excite(ws + n->se_part_off, n->pptr[blk.p_se], n->pptr[blk.p_se + 1], n->pptr[blk.p_se + 2],
+                                         n->pptr[blk.p_se + 3], ws + n->se_gate_off, B, Y.H, Y.W, Y.C, n->se, s));
+                FPC_TRY(launch_se_scale_add_relu(ws + Y.off, ws + n->se_gate_off, res, ws + Y.off, B, Y.H, Y.W, Y.C, s));
+                cur = Y;
+                continue;
+            }
             if (n->expansion == 4) {
                 // Bottleneck: conv1 (1x1, BN + ReLU) -> conv2 (3x3 with the stride, BN + ReLU), the downsample (1x1, stride, BN),
                 // conv3 (1x1, BN + residual + ReLU)
@@ -1577,6 +1649,7 @@ extern "C" int fpc_net_force_direct_h3(fpc_net_t* n, int on) {
 // when the plan changed, 0 when it was already so, or a negative code.  Drops the recorded graph.
 extern "C" int fpc_net_force_stem_pool(fpc_net_t* n, int on) {
     if (!n || on < 0 || on > 1 || (on && !n->h3_packed)) return FPC_EINVAL;
+    if (on && n->se) return FPC_EINVAL;      // the SE-ResNet stem pool has no padding: the fused launch computes another pool
     if (on && ((n->a_stem.H & 1) || (n->a_stem.W & 63) || (long long)n->H * n->W * 16 >= (1LL << 31))) return FPC_EINVAL;
     ConvPlan& p = n->cplan[n->c_stem];
     if (p.pool == on) return 0;

@@ -11,8 +11,10 @@
 namespace fpc {
 
 // ------------------------------------------------------------------------------------------
-// max pooling 3x3 stride 2 pad 1, NHWC, one float4 of channels per thread
+// max pooling 3x3 stride 2, NHWC, one float4 of channels per thread.  PAD = 1: torchvision's stem pool (windows start at -1);
+// PAD = 0: the SE-ResNet stem's MaxPool2d(3, 2, ceil_mode=True) — windows start at 2 i, Ho = Hi / 2, the last one clipped
 
+template <int PAD>
 __global__ __launch_bounds__(256) void k_maxpool3x3s2(const float* __restrict__ in, float* __restrict__ out, int B,
                                                       int Hi, int Wi, int C, int Ho, int Wo) {
     const unsigned C4 = C >> 2;
@@ -26,11 +28,11 @@ __global__ __launch_bounds__(256) void k_maxpool3x3s2(const float* __restrict__ 
         float4 m = make_float4(-__builtin_huge_valf(), -__builtin_huge_valf(), -__builtin_huge_valf(), -__builtin_huge_valf());
 #pragma unroll
         for (int dy = 0; dy < 3; ++dy) {
-            int hi = ho * 2 - 1 + dy;
+            int hi = ho * 2 - PAD + dy;
             if (hi < 0 || hi >= Hi) continue;
 #pragma unroll
             for (int dx = 0; dx < 3; ++dx) {
-                int wi = wo * 2 - 1 + dx;
+                int wi = wo * 2 - PAD + dx;
                 if (wi < 0 || wi >= Wi) continue;
                 float4 v = *reinterpret_cast<const float4*>(in + (((size_t)b * Hi + hi) * Wi + wi) * C + 4 * c4);
                 m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
@@ -538,7 +540,16 @@ __global__ void k_fold_bn(const float* __restrict__ gamma, const float* __restri
 int launch_maxpool3x3s2(const float* in, float* out, int B, int Hi, int Wi, int C, int Ho, int Wo, hipStream_t s) {
     // (xcd_walk's 32-bit `first + k * step` must not wrap: one grid stride — at most 4096 x 256 items — of headroom below 2^32)
     if (C % 4 != 0 || (long long)B * Ho * Wo * (C / 4) >= (1LL << 32) - 4096LL * 256 - 8) return FPC_EINVAL;
-    hipLaunchKernelGGL(k_maxpool3x3s2, dim3(stream_grid((long long)B * Ho * Wo * (C / 4))), dim3(256), 0, s, in, out, B,
+    hipLaunchKernelGGL(k_maxpool3x3s2<1>, dim3(stream_grid((long long)B * Ho * Wo * (C / 4))), dim3(256), 0, s, in, out, B,
+                       Hi, Wi, C, Ho, Wo);
+    return check_launch();
+}
+
+// the pad-0 ceil-mode form: out [B][Hi / 2][Wi / 2][C] (torch's output size for every Hi, Wi >= 2: no window starts outside)
+int launch_maxpool3x3s2_ceil(const float* in, float* out, int B, int Hi, int Wi, int C, hipStream_t s) {
+    const int Ho = Hi / 2, Wo = Wi / 2;
+    if (C % 4 != 0 || Hi < 2 || Wi < 2 || (long long)B * Ho * Wo * (C / 4) >= (1LL << 32) - 4096LL * 256 - 8) return FPC_EINVAL;
+    hipLaunchKernelGGL(k_maxpool3x3s2<0>, dim3(stream_grid((long long)B * Ho * Wo * (C / 4))), dim3(256), 0, s, in, out, B,
                        Hi, Wi, C, Ho, Wo);
     return check_launch();
 }

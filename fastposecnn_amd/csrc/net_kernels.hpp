@@ -300,6 +300,15 @@ int launch_fold_compose(const float* W, const float* L, const float* bias, float
 int launch_conv(const ConvArgs& a, int groups, hipStream_t s);
 int launch_conv_splitk_epilogue(const ConvArgs& a, int groups, hipStream_t s);
 int launch_maxpool3x3s2(const float* in, float* out, int B, int Hi, int Wi, int C, int Ho, int Wo, hipStream_t s);
+int launch_maxpool3x3s2_ceil(const float* in, float* out, int B, int Hi, int Wi, int C, hipStream_t s);      // pad 0, ceil_mode: out [B][Hi / 2][Wi / 2][C]
+// se.hip: the squeeze-and-excitation gate of the SE-ResNet encoders.  NHWC f32, C % 64 == 0 (<= 8192), fixed summation orders.
+// partial [B][se_pool_slabs(H, W, C)][C] per-slab channel sums; gate [B][C] = sigmoid(w2 relu(w1 mean + b1) + b2) with w1 [C / R][C],
+// w2 [C][C / R]; y = max(x gate + res, 0), y == x allowed
+int se_pool_slabs(int H, int W, int C);      // a function of the shape only; 0 for a refused one
+int launch_se_pool(const float* x, float* partial, int B, int H, int W, int C, hipStream_t s);
+int launch_se_excite(const float* partial, const float* w1, const float* b1, const float* w2, const float* b2, float* gate, int B, int H,
+                     int W, int C, int R, hipStream_t s);
+int launch_se_scale_add_relu(const float* x, const float* gate, const float* res, float* y, int B, int H, int W, int C, hipStream_t s);
 int launch_gn_finalize(const GnFinArgs& a, int groups, hipStream_t s);
 int launch_gn_relu_up2(const GnUpArgs& a, int groups, hipStream_t s);
 int launch_merge_head(const MergeHeadArgs& a, int groups, hipStream_t s);

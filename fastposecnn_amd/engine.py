@@ -27,7 +27,11 @@ class NetEngine:
         from fastposecnn_amd.lib import backbone
         block, layers = backbone.encoder_layout(model.encoder.name)
         groups, width = backbone.encoder_groups(model.encoder.name)
-        if groups > 1:      # ResNeXt: Bottleneck with a grouped conv2
+        reduction = backbone.encoder_reduction(model.encoder.name)
+        if reduction:       # SE-ResNet: the Bottleneck with the stride on conv1 and the squeeze-and-excitation gate
+            nat.check(L.fpc_net_create_encoder_se((ctypes.c_int * 4)(*layers), reduction, self.classes, B, H, W, ctypes.byref(h)),
+                      "fpc_net_create_encoder_se")
+        elif groups > 1:    # ResNeXt: Bottleneck with a grouped conv2
             nat.check(L.fpc_net_create_encoder_ex(block, (ctypes.c_int * 4)(*layers), groups, width, self.classes, B, H, W,
                                                   ctypes.byref(h)), "fpc_net_create_encoder_ex")
         elif block == 1:    # the named nets, as always

@@ -15,6 +15,9 @@ Structure (encoder_depth = 5, FPN, merge "add"):
               align_corners=True)] with n = 3,2,1,0 upsamples (at least one conv);
               sum of the four 1/4-scale maps; Dropout2d(0.2)
   SegmentationHead: conv 1x1 -> UpsamplingBilinear2d(x4) (align_corners=True) -> Identity
+The SE-ResNet encoders (se_resnet50 / 101 / 152) are smp's SENetEncoder over pretrainedmodels.senet, restated the same way
+(neither package is here: parity unpinned): encoder.layer0.{conv1,bn1,relu1,pool}, SEResNetBottleneck blocks with
+se_module.fc1 / fc2, the same six feature levels.
 state_dict names follow smp: encoder.conv1.weight, encoder.layer1.0.conv1.weight, ...,
 <dec>.p5.weight, <dec>.p4.skip_conv.weight, <dec>.seg_blocks.0.block.0.block.0.weight (conv),
 ...block.1.weight (GroupNorm), <head>.0.weight.
@@ -149,6 +152,50 @@ class Bottleneck(nn.Module):
         return _bn_act(out, self.bn3, self.relu, identity)
 
 
+class SEModule(nn.Module):
+    """pretrainedmodels.senet.SEModule: x * sigmoid(fc2(relu(fc1(avgpool(x))))), fc1 / fc2 1x1 convolutions WITH bias.  Plain
+    torch modules in every mode: the engine's plan runs the gate on k_se_pool / k_se_excite (csrc/se.hip) at inference."""
+
+    def __init__(self, channels, reduction):
+        super().__init__()
+        self.avg_pool = nn.AdaptiveAvgPool2d(1)
+        self.fc1 = nn.Conv2d(channels, channels // reduction, kernel_size=1, padding=0)
+        self.relu = nn.ReLU(inplace=True)
+        self.fc2 = nn.Conv2d(channels // reduction, channels, kernel_size=1, padding=0)
+        self.sigmoid = nn.Sigmoid()
+
+    def forward(self, x):
+        g = self.sigmoid(self.fc2(self.relu(self.fc1(self.avg_pool(x)))))
+        return x * g
+
+
+class SEResNetBottleneck(nn.Module):
+    """pretrainedmodels.senet.SEResNetBottleneck (the Caffe-style ResNet: the stride on conv1, a 1x1) with the squeeze-and-
+    excitation gate between bn3 and the residual add: relu(se_module(bn3(conv3(.))) + residual).  bn3 therefore never fuses the
+    add or the ReLU."""
+    expansion = 4
+
+    def __init__(self, inplanes, planes, reduction, stride=1, downsample=None):
+        super().__init__()
+        self.conv1 = Conv2d(inplanes, planes, 1, stride, bias=False)
+        self.bn1 = BatchNorm2d(planes)
+        self.conv2 = Conv2d(planes, planes, 3, 1, 1, bias=False)
+        self.bn2 = BatchNorm2d(planes)
+        self.conv3 = Conv2d(planes, planes * 4, 1, bias=False)
+        self.bn3 = BatchNorm2d(planes * 4)
+        self.relu = nn.ReLU(inplace=True)
+        self.se_module = SEModule(planes * 4, reduction)
+        self.downsample = downsample
+        self.stride = stride
+
+    def forward(self, x):
+        out = _bn_act(self.conv1(x), self.bn1, self.relu)
+        out = _bn_act(self.conv2(out), self.bn2, self.relu)
+        out = self.bn3(self.conv3(out))
+        residual = x if self.downsample is None else self.downsample(x)
+        return self.relu(self.se_module(out) + residual)
+
+
 # name -> (block, blocks per stage), as torchvision / smp
 _RESNET_LAYERS = {"resnet18": (BasicBlock, [2, 2, 2, 2]), "resnet34": (BasicBlock, [3, 4, 6, 3]),
                   "resnet50": (Bottleneck, [3, 4, 6, 3]), "resnet101": (Bottleneck, [3, 4, 23, 3]),
@@ -157,19 +204,30 @@ _RESNET_LAYERS = {"resnet18": (BasicBlock, [2, 2, 2, 2]), "resnet34": (BasicBloc
                   "resnext101_32x8d": (Bottleneck, [3, 4, 23, 3])}
 # name -> (groups, width per group) of the ResNeXt encoders; every other encoder is (1, 64)
 _RESNEXT_WIDTHS = {"resnext50_32x4d": (32, 4), "resnext101_32x4d": (32, 4), "resnext101_32x8d": (32, 8)}
+# the squeeze-and-excitation ResNets (smp's SENetEncoder over pretrainedmodels.senet): name -> (block, blocks per stage, reduction)
+_SENET_LAYERS = {"se_resnet50": (SEResNetBottleneck, [3, 4, 6, 3], 16), "se_resnet101": (SEResNetBottleneck, [3, 4, 23, 3], 16),
+                 "se_resnet152": (SEResNetBottleneck, [3, 8, 36, 3], 16)}
 
 
 def encoder_layout(name):
     """(block expansion, blocks per stage) of encoder `name`: the descriptor fpc_net_create_encoder takes."""
-    block, layers = _RESNET_LAYERS[name]
+    block, layers = _SENET_LAYERS[name][:2] if name in _SENET_LAYERS else _RESNET_LAYERS[name]
     return block.expansion, list(layers)
 
 
 def encoder_groups(name):
     """(groups, width per group) of encoder `name`: what fpc_net_create_encoder_ex takes beside encoder_layout's pair."""
-    if name not in _RESNET_LAYERS:
+    if name not in _RESNET_LAYERS and name not in _SENET_LAYERS:
         raise KeyError(name)
     return _RESNEXT_WIDTHS.get(name, (1, 64))
+
+
+def encoder_reduction(name):
+    """The squeeze-and-excitation reduction of encoder `name` (16 for the SE-ResNets: what fpc_net_create_encoder_se takes), 0 for
+    every encoder without the gate."""
+    if name not in _RESNET_LAYERS and name not in _SENET_LAYERS:
+        raise KeyError(name)
+    return _SENET_LAYERS[name][2] if name in _SENET_LAYERS else 0
 
 
 class ResNetEncoder(nn.Module):
@@ -178,7 +236,7 @@ class ResNetEncoder(nn.Module):
     def __init__(self, name="resnet18", in_channels=3, depth=5):
         super().__init__()
         if name not in _RESNET_LAYERS:
-            raise KeyError(f"encoder {name!r} not available (have {sorted(_RESNET_LAYERS)})")
+            raise KeyError(f"encoder {name!r} not available (have {sorted(_RESNET_LAYERS) + sorted(_SENET_LAYERS)})")
         block, layers = _RESNET_LAYERS[name]
         self.name = name
         self._depth = depth
@@ -230,6 +288,65 @@ class ResNetEncoder(nn.Module):
         return feats
 
 
+class SENetEncoder(nn.Module):
+    """smp's SENetEncoder for the SE-ResNets (pretrainedmodels.senet.SENet with groups = 1, inplanes = 64, a 7x7 stem and 1x1
+    downsamples, without avg_pool / last_linear), returning 6 feature levels.  layer0 is the stem as a Sequential of named
+    children; its pool is MaxPool2d(3, stride=2, ceil_mode=True) WITHOUT padding (windows start at 0, the last one is clipped),
+    a plain nn.MaxPool2d in every mode: the native training pool kernels are pad-1 kernels."""
+
+    def __init__(self, name="se_resnet50", in_channels=3, depth=5):
+        super().__init__()
+        if name not in _SENET_LAYERS:
+            raise KeyError(f"encoder {name!r} not available (have {sorted(_RESNET_LAYERS) + sorted(_SENET_LAYERS)})")
+        from collections import OrderedDict
+        block, layers, reduction = _SENET_LAYERS[name]
+        self.name = name
+        self._depth = depth
+        self._reduction = reduction
+        self.out_channels = (in_channels, 64, 256, 512, 1024, 2048)
+        self.inplanes = 64
+        self.layer0 = nn.Sequential(OrderedDict([
+            ("conv1", Conv2d(in_channels, 64, 7, 2, 3, bias=False)), ("bn1", BatchNorm2d(64)), ("relu1", nn.ReLU(inplace=True)),
+            ("pool", nn.MaxPool2d(3, stride=2, ceil_mode=True))]))
+        self.layer1 = self._make_layer(block, 64, layers[0])
+        self.layer2 = self._make_layer(block, 128, layers[1], stride=2)
+        self.layer3 = self._make_layer(block, 256, layers[2], stride=2)
+        self.layer4 = self._make_layer(block, 512, layers[3], stride=2)
+        # (pretrainedmodels leaves torch's default initialisation; the bias-free convolutions and the BatchNorms start as the
+        # ResNet encoders' here, fc1 / fc2 keep nn.Conv2d's default.  A checkpoint or a weights file overwrites all of it.)
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d) and m.bias is None:
+                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+            elif isinstance(m, nn.BatchNorm2d):
+                nn.init.constant_(m.weight, 1)
+                nn.init.constant_(m.bias, 0)
+
+    def _make_layer(self, block, planes, blocks, stride=1):
+        downsample = None
+        if stride != 1 or self.inplanes != planes * block.expansion:
+            downsample = nn.Sequential(Conv2d(self.inplanes, planes * block.expansion, 1, stride, bias=False),
+                                       BatchNorm2d(planes * block.expansion))
+        layers = [block(self.inplanes, planes, self._reduction, stride, downsample)]
+        self.inplanes = planes * block.expansion
+        for _ in range(1, blocks):
+            layers.append(block(self.inplanes, planes, self._reduction))
+        return nn.Sequential(*layers)
+
+    def forward(self, x):
+        feats = [x]
+        x = _bn_act(self.layer0.conv1(x), self.layer0.bn1, self.layer0.relu1)
+        feats.append(x)
+        x = self.layer1(self.layer0.pool(x))
+        feats.append(x)
+        x = self.layer2(x)
+        feats.append(x)
+        x = self.layer3(x)
+        feats.append(x)
+        x = self.layer4(x)
+        feats.append(x)
+        return feats
+
+
 _WARNED_WEIGHTS = set()
 
 
@@ -239,12 +356,13 @@ def get_encoder(name, in_channels=3, depth=5, weights=None):
     smp downloads the torchvision ImageNet checkpoint for weights='imagenet' (every HPARAM preset asks for it,
     F/config.py).  There is no network here, so pretrained weights come from a local file:
     `FPC_ENCODER_WEIGHTS_DIR/<name>.pth` (or `FPC_ENCODER_WEIGHTS=<file>`) holding the torchvision ResNet state
-    dict (keys conv1.weight, bn1.*, layer1.0.conv1.weight, ...; fc.* is dropped, as smp does).  When `weights` is
+    dict (keys conv1.weight, bn1.*, layer1.0.conv1.weight, ...; fc.* is dropped, as smp does) or, for an SE-ResNet, the
+    pretrainedmodels one (layer0.conv1.weight, ..., layerN.i.se_module.fc1.bias; last_linear.* is dropped).  When `weights` is
     requested and no file is configured the encoder stays randomly initialised and a warning says so once per
     encoder — a checkpoint loaded afterwards (load_from_ckpt) overwrites the encoder anyway."""
     import logging
     import os
-    enc = ResNetEncoder(name, in_channels=in_channels, depth=depth)
+    enc = (SENetEncoder if name in _SENET_LAYERS else ResNetEncoder)(name, in_channels=in_channels, depth=depth)
     enc.requested_weights = weights
     enc.loaded_weights = None
     if weights is not None:
@@ -254,7 +372,7 @@ def get_encoder(name, in_channels=3, depth=5, weights=None):
         if path:
             import torch
             sd = torch.load(path, map_location="cpu")
-            sd = {k: v for k, v in sd.items() if not k.startswith("fc.")}
+            sd = {k: v for k, v in sd.items() if not k.startswith(("fc.", "last_linear."))}
             enc.load_state_dict(sd)                  # strict: a wrong file fails loudly
             enc.loaded_weights = path
         elif (name, weights) not in _WARNED_WEIGHTS:

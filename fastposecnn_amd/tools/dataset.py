@@ -48,7 +48,7 @@ IMAGENET_PARAMS = {"input_space": "RGB", "input_range": [0, 1], "mean": [0.485, 
 
 def get_preprocessing_params(encoder_name="resnet18", pretrained="imagenet"):
     """smp.encoders.get_preprocessing_params for the encoders this package builds (lib/backbone.py)."""
-    if pretrained != "imagenet" or not str(encoder_name).startswith(("resnet", "resnext")):
+    if pretrained != "imagenet" or not str(encoder_name).startswith(("resnet", "resnext", "se_resnet")):
         raise ValueError("no preprocessing parameters for encoder %r / weights %r" % (encoder_name, pretrained))
     return {k: (list(v) if isinstance(v, list) else v) for k, v in IMAGENET_PARAMS.items()}
 

@@ -57,6 +57,7 @@ extern "C" {
  * and the activation-range guard of the fp16-piece forms (fpc_act_range, fpc_net_survey_next, fpc_net_guard_ranges, fpc_net_guarded):
  * and the ground-truth batch builder (fpc_gt_build, fpc_depth_decode):
  * and the device PNG decode (fpc_inflate_host, fpc_png_pack_bytes, fpc_png_pack_batch, fpc_png_decode_device and its _workspace_bytes):
+ * and the SE-ResNet encoders (fpc_net_create_encoder_se, fpc_se_pool_slabs, fpc_se_scratch_floats, fpc_se_gate, fpc_se_scale_add_relu, fpc_maxpool3x3s2_ceil_fwd):
  * additions only, every earlier entry point keeps its behaviour. */
 #define FPC_ABI_VERSION 11
 
@@ -546,6 +547,16 @@ int fpc_net_create_encoder(int block, const int* layers4, int classes, int B, in
  * / 64 at planes = 64 .. 512) outside {4, 8, 16, 32, 64}. */
 int fpc_net_create_encoder_ex(int block, const int* layers4, int groups, int width_per_group, int classes, int B, int H, int W,
                               fpc_net_t** out);
+/* The SE-ResNet encoders (smp's SENetEncoder over pretrainedmodels.senet, reached through smp.encoders.get_encoder at
+ * F/lib/pose_regressor.py:608-613 with HPARAM.ENCODER = "se_resnet50" / "se_resnet101" / "se_resnet152"): SEResNetBottleneck x
+ * layers4 — conv1 a 1x1 WITH the stride, conv2 a dense 3x3 / stride 1, conv3 a 1x1 x 4 with BatchNorm only, then the squeeze-and-
+ * excitation gate sigmoid(fc2(relu(fc1(mean)))) (fc1: C -> C / reduction, fc2 back, both with bias; csrc/se.hip) and
+ * relu(x * gate + residual).  The stem is layer0 (conv1, bn1, relu1, pool) and its pool MaxPool2d(3, 2, ceil_mode=True) without
+ * padding.  Parameters by pretrainedmodels' names under "encoder." ("encoder.layer0.conv1.weight",
+ * "encoder.layer2.0.se_module.fc1.bias"); fc1 / fc2 weights and biases are read in place.  fpc_net_create answers the three names
+ * with {3,4,6,3} / {3,4,23,3} / {3,8,36,3} and reduction 16.  On such a plan fpc_net_force_stem_pool(net, 1) is refused (the fused
+ * stem launch is a pad-1 pool) and the autotuner does not offer it.  FPC_EINVAL: a reduction < 1 or one that does not divide 256. */
+int fpc_net_create_encoder_se(const int* layers4, int reduction, int classes, int B, int H, int W, fpc_net_t** out);
 void fpc_net_destroy(fpc_net_t* net);
 int fpc_net_param_count(const fpc_net_t* net);
 const char* fpc_net_param_name(const fpc_net_t* net, int i);
@@ -816,6 +827,29 @@ int fpc_stem_wgrad(const float* img4, const float* dy, float* dw, int B, int Hi,
                    fpc_stream_t stream);
 int fpc_maxpool3x3s2_fwd(const float* x, float* y, int B, int Hi, int Wi, int C, fpc_stream_t stream);
 int fpc_maxpool3x3s2_bwd(const float* x, const float* dy, float* dx, int B, int Hi, int Wi, int C, fpc_stream_t stream);
+
+/* ---- The squeeze-and-excitation gate of the SE-ResNet encoders, stand-alone (unit tests; the engine runs the same launches).
+ * They replace pretrainedmodels.senet.SEModule.forward and the `se_module(out) + residual` / ReLU lines of
+ * SEResNetBottleneck.forward (aten kernels in the reference, reached through smp.encoders.get_encoder, F/lib/pose_regressor.py:
+ * 608-613), and layer0.pool = nn.MaxPool2d(3, stride=2, ceil_mode=True) of the same encoder.  NHWC f32, C a multiple of 64 (at
+ * most 8192), every pointer 16-byte aligned; no float atomics and summation orders that depend on the shape alone: two calls agree
+ * bit for bit.  FPC_EINVAL: C % 64 != 0, R < 1 or R not dividing C, a NULL or misaligned pointer, B < 1.
+ *
+ * fpc_se_pool_slabs: the slabs k_se_pool cuts one frame's H W pixels into — a function of (H, W, C) only; 0 for a refused shape.
+ * fpc_se_scratch_floats: floats of `scratch` = B * slabs * C (the per-slab channel sums).
+ * fpc_se_gate (k_se_pool + k_se_excite): gate[b][c] = 1 / (1 + exp(-(w2 relu(w1 m_b + b1) + b2)[c])) with m_b the mean of x[b] over
+ *   its H W pixels (slab sums added in slab order, times 1 / (H W)), w1 [C / R][C], b1 [C / R], w2 [C][C / R], b2 [C]: the weights
+ *   and biases of fc1 / fc2 in torch's layout.  A pre-activation of +-100 gives exactly 1 / 0.
+ * fpc_se_scale_add_relu (k_se_scale_add_relu): y = max(x * gate[b][c] + res, 0) over [B][H][W][C]; y may be x.
+ * fpc_maxpool3x3s2_ceil_fwd (k_maxpool3x3s2<0>): x [B][Hi][Wi][C] -> y [B][Hi / 2][Wi / 2][C], window (i, j) = rows 2 i .. 2 i + 2 and
+ *   columns 2 j .. 2 j + 2 clipped to the map: F.max_pool2d(x, 3, 2, 0, ceil_mode=True) for every Hi, Wi >= 2 (odd ones included). */
+int fpc_se_pool_slabs(int H, int W, int C);
+size_t fpc_se_scratch_floats(int B, int H, int W, int C);
+int fpc_se_gate(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, float* gate, float* scratch, int B,
+                int H, int W, int C, int R, fpc_stream_t stream);
+int fpc_se_scale_add_relu(const float* x, const float* gate, const float* res, float* y, int B, int H, int W, int C,
+                          fpc_stream_t stream);
+int fpc_maxpool3x3s2_ceil_fwd(const float* x, float* y, int B, int Hi, int Wi, int C, fpc_stream_t stream);
 
 /* Weight gradient of a convolution for the training step (BASELINE.json configs[4]; the reference leaves the
  * convolutions' backward to cuDNN through autograd, F/lib/pose_regressor.py:709-743 under Lightning's backward).
