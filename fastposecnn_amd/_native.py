@@ -139,6 +139,9 @@ _SIGNATURES = {
     "fpc_se_gate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "fpc_se_scale_add_relu": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "fpc_maxpool3x3s2_ceil_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "fpc_se_gate_train": (_i, [_vp] * 9 + [_i, _i, _i, _i, _i, _vp]),
+    "fpc_se_bwd_scratch_floats": (_sz, [_i, _i, _i, _i, _i]),
+    "fpc_se_bwd": (_i, [_vp] * 15 + [_i, _i, _i, _i, _i, _vp]),
     "fpc_conv2d_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "fpc_upsample_bilinear_fwd": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "fpc_upsample_bilinear_bwd_scratch_floats": (_sz, [_i, _i, _i, _i, _i]),

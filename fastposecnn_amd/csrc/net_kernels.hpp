@@ -309,6 +309,21 @@ int launch_se_pool(const float* x, float* partial, int B, int H, int W, int C, h
 int launch_se_excite(const float* partial, const float* w1, const float* b1, const float* w2, const float* b2, float* gate, int B, int H,
                      int W, int C, int R, hipStream_t s);
 int launch_se_scale_add_relu(const float* x, const float* gate, const float* res, float* y, int B, int H, int W, int C, hipStream_t s);
+// launch_se_excite that also writes mean [B][C] and hidden [B][C / R] = relu(w1 mean + b1), what the backward of se_train.hip reads:
+// the SAVE instantiation of the same kernel, the same operations in the same order, so the gate's bits are launch_se_excite's
+int launch_se_excite_train(const float* partial, const float* w1, const float* b1, const float* w2, const float* b2, float* gate,
+                           float* mean, float* hidden, int B, int H, int W, int C, int R, hipStream_t s);
+// the slab geometry of k_se_pool, shared with k_se_bwd_reduce (se_train.hip): the channel quads of a pixel take min(C / 4, 256)
+// lanes, the rest of the workgroup takes further pixels as thread rows; a slab is se_rows(C) * kSeRowPixels pixels
+constexpr int kSeThreads = 256;
+constexpr int kSeRowPixels = 64;      // pixels one thread row of k_se_pool adds per slab
+constexpr int kSeMaxC = 8192;         // k_se_excite keeps the means of one frame in LDS
+inline int se_lanes(int C) { return C / 4 < kSeThreads ? C / 4 : kSeThreads; }
+inline int se_rows(int C) { return kSeThreads / se_lanes(C); }
+inline bool se_shape_ok(int B, int H, int W, int C) {
+    return B >= 1 && B <= 65535 && H >= 1 && W >= 1 && C >= 64 && C % 64 == 0 && C <= kSeMaxC && (long long)H * W < (1LL << 31) &&
+           (long long)B * H * W * (C / 4) < (1LL << 32) - 4096LL * 256 - 8;      // (xcd_walk's 32-bit walk: launch_maxpool3x3s2's bound)
+}
 int launch_gn_finalize(const GnFinArgs& a, int groups, hipStream_t s);
 int launch_gn_relu_up2(const GnUpArgs& a, int groups, hipStream_t s);
 int launch_merge_head(const MergeHeadArgs& a, int groups, hipStream_t s);

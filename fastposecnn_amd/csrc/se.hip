@@ -9,7 +9,8 @@
 //                        the rows; writes partial[b][slab][C].  se_pool_slabs(H, W, C) is a function of the shape only.
 //   k_se_excite          one workgroup per frame: the slabs added in slab order and multiplied by 1 / (H W); fc1 with one wave per
 //                        output row, four rows at once (lanes stride over C, xor butterfly), bias, ReLU; fc2 with 16 lanes per
-//                        output row, bias, 1 / (1 + exp(-v)) through div_ieee; writes gate[b][C].
+//                        output row, bias, 1 / (1 + exp(-v)) through div_ieee; writes gate[b][C].  k_se_excite<true> (the training
+//                        step: launch_se_excite_train, se_train.hip) also writes the means and the hidden activations.
 //   k_se_scale_add_relu  y = max(x * gate[b][c] + res, 0), one float4 per thread and step on the XCD-banded walk of the other
 //                        streaming kernels; may run in place (y == x).
 // The SE-ResNet stem's max-pool (3x3 / stride 2 / no padding / ceil_mode) is k_maxpool3x3s2<0> in net_kernels.hip; its stand-alone
@@ -20,17 +21,7 @@
 
 namespace fpc {
 
-namespace {
-
-constexpr int kSeThreads = 256;
-constexpr int kSeRowPixels = 64;      // pixels one thread row of k_se_pool adds per slab
-constexpr int kSeMaxC = 8192;         // k_se_excite keeps the means of one frame in LDS
-
-// thread rows of k_se_pool: the channel quads of a pixel take min(C / 4, 256) lanes, the rest of the workgroup takes further pixels
-inline int se_lanes(int C) { return C / 4 < kSeThreads ? C / 4 : kSeThreads; }
-inline int se_rows(int C) { return kSeThreads / se_lanes(C); }
-
-}  // namespace
+// (kSeThreads, kSeRowPixels, kSeMaxC, se_lanes, se_rows, se_shape_ok: net_kernels.hpp, shared with se_train.hip)
 
 int se_pool_slabs(int H, int W, int C) {
     if (H < 1 || W < 1 || C < 64 || C % 64) return 0;
@@ -76,10 +67,13 @@ __global__ __launch_bounds__(256) void k_se_pool(const float* __restrict__ x, fl
 // grid (B).  Dynamic LDS: C + Cr floats.  w1 [Cr][C], b1 [Cr], w2 [C][Cr], b2 [C] (torch's layouts of the two 1x1 convolutions).
 // One workgroup streams both weight matrices (2 C Cr floats: 2 MB at C = 2048), so what bounds it is the loads in flight: a wave
 // (fc1) or a 16-lane group (fc2) works on four output rows at once, with 16-byte loads where Cr allows them.
+// SAVE (the training step, launch_se_excite_train): the means and the hidden activations also go to mean_out [B][C] / hid_out [B][Cr],
+// the values the gate is computed from; SAVE = false is the inference kernel, which never reads the two pointers.
+template <bool SAVE>
 __global__ __launch_bounds__(256) void k_se_excite(const float* __restrict__ partial, const float* __restrict__ w1,
                                                    const float* __restrict__ b1, const float* __restrict__ w2,
                                                    const float* __restrict__ b2, float* __restrict__ gate, int slabs, int C, int Cr,
-                                                   float inv_hw) {
+                                                   float inv_hw, float* __restrict__ mean_out, float* __restrict__ hid_out) {
     extern __shared__ float4 s_se4[];      // (float4: the 16-byte alignment of both halves, C % 4 == 0)
     float* s_mean = reinterpret_cast<float*>(s_se4);
     float* s_hid = s_mean + C;
@@ -89,6 +83,7 @@ __global__ __launch_bounds__(256) void k_se_excite(const float* __restrict__ par
         float s = 0.f;
         for (int k = 0; k < slabs; ++k) s += part[(size_t)k * C + c];      // slab order
         s_mean[c] = s * inv_hw;
+        if (SAVE) mean_out[(size_t)b * C + c] = s_mean[c];
     }
     __syncthreads();
     // fc1: rows j0 .. j0 + 3 per wave and step; a lane adds its quads of C in ascending order, then the xor butterfly
@@ -108,7 +103,10 @@ __global__ __launch_bounds__(256) void k_se_excite(const float* __restrict__ par
         for (int r = 0; r < 4; ++r) {
 #pragma unroll
             for (int off = 32; off >= 1; off >>= 1) acc[r] += __shfl_xor(acc[r], off);
-            if (lane == 0 && j0 + r < Cr) s_hid[j0 + r] = fmaxf(acc[r] + b1[j0 + r], 0.f);
+            if (lane == 0 && j0 + r < Cr) {
+                s_hid[j0 + r] = fmaxf(acc[r] + b1[j0 + r], 0.f);
+                if (SAVE) hid_out[(size_t)b * Cr + j0 + r] = s_hid[j0 + r];
+            }
         }
     }
     __syncthreads();
@@ -165,11 +163,6 @@ __global__ __launch_bounds__(256) void k_se_scale_add_relu(const float* x, const
     }
 }
 
-static bool se_shape_ok(int B, int H, int W, int C) {
-    return B >= 1 && B <= 65535 && H >= 1 && W >= 1 && C >= 64 && C % 64 == 0 && C <= kSeMaxC && (long long)H * W < (1LL << 31) &&
-           (long long)B * H * W * (C / 4) < (1LL << 32) - 4096LL * 256 - 8;      // (xcd_walk's 32-bit walk: launch_maxpool3x3s2's bound)
-}
-
 int launch_se_pool(const float* x, float* partial, int B, int H, int W, int C, hipStream_t s) {
     if (!se_shape_ok(B, H, W, C)) return FPC_EINVAL;
     const int rows = se_rows(C);
@@ -182,8 +175,17 @@ int launch_se_excite(const float* partial, const float* w1, const float* b1, con
                      int W, int C, int R, hipStream_t s) {
     if (!se_shape_ok(B, H, W, C) || R < 1 || C % R) return FPC_EINVAL;
     const int Cr = C / R;
-    hipLaunchKernelGGL(k_se_excite, dim3(B), dim3(kSeThreads), (size_t)(C + Cr) * sizeof(float), s, partial, w1, b1, w2, b2, gate,
-                       se_pool_slabs(H, W, C), C, Cr, 1.0f / (float)((long long)H * W));
+    hipLaunchKernelGGL(k_se_excite<false>, dim3(B), dim3(kSeThreads), (size_t)(C + Cr) * sizeof(float), s, partial, w1, b1, w2, b2, gate,
+                       se_pool_slabs(H, W, C), C, Cr, 1.0f / (float)((long long)H * W), (float*)nullptr, (float*)nullptr);
+    return check_launch();
+}
+
+int launch_se_excite_train(const float* partial, const float* w1, const float* b1, const float* w2, const float* b2, float* gate,
+                           float* mean, float* hidden, int B, int H, int W, int C, int R, hipStream_t s) {
+    if (!se_shape_ok(B, H, W, C) || R < 1 || C % R || !mean || !hidden) return FPC_EINVAL;
+    const int Cr = C / R;
+    hipLaunchKernelGGL(k_se_excite<true>, dim3(B), dim3(kSeThreads), (size_t)(C + Cr) * sizeof(float), s, partial, w1, b1, w2, b2, gate,
+                       se_pool_slabs(H, W, C), C, Cr, 1.0f / (float)((long long)H * W), mean, hidden);
     return check_launch();
 }
 

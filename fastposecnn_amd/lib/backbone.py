@@ -153,8 +153,10 @@ class Bottleneck(nn.Module):
 
 
 class SEModule(nn.Module):
-    """pretrainedmodels.senet.SEModule: x * sigmoid(fc2(relu(fc1(avgpool(x))))), fc1 / fc2 1x1 convolutions WITH bias.  Plain
-    torch modules in every mode: the engine's plan runs the gate on k_se_pool / k_se_excite (csrc/se.hip) at inference."""
+    """pretrainedmodels.senet.SEModule: x * sigmoid(fc2(relu(fc1(avgpool(x))))), fc1 / fc2 1x1 convolutions WITH bias.  Its own
+    forward is plain torch modules; the engine's plan runs the gate on k_se_pool / k_se_excite (csrc/se.hip) at inference, and in the
+    training step with FPC_TRAIN_NATIVE_SE=1 SEResNetBottleneck runs it, fused with its add and ReLU, on the same kernels and on
+    csrc/se_train.hip (lib/train_conv.se_gate_add_relu) — from these parameters, whose names and shapes stay as they are."""
 
     def __init__(self, channels, reduction):
         super().__init__()
@@ -172,7 +174,9 @@ class SEModule(nn.Module):
 class SEResNetBottleneck(nn.Module):
     """pretrainedmodels.senet.SEResNetBottleneck (the Caffe-style ResNet: the stride on conv1, a 1x1) with the squeeze-and-
     excitation gate between bn3 and the residual add: relu(se_module(bn3(conv3(.))) + residual).  bn3 therefore never fuses the
-    add or the ReLU."""
+    add or the ReLU.  Gate, add and ReLU are torch ops by default; under autograd on a GPU with FPC_TRAIN_NATIVE_SE=1 they are one
+    native op each way (lib/train_conv.se_gate_add_relu), which whatever it refuses — another layout or dtype, a swapped
+    activation, the switch off — hands back to the torch lines."""
     expansion = 4
 
     def __init__(self, inplanes, planes, reduction, stride=1, downsample=None):
@@ -193,6 +197,11 @@ class SEResNetBottleneck(nn.Module):
         out = _bn_act(self.conv2(out), self.bn2, self.relu)
         out = self.bn3(self.conv3(out))
         residual = x if self.downsample is None else self.downsample(x)
+        if out.is_cuda and torch.is_grad_enabled():
+            from fastposecnn_amd.lib import train_conv
+            y = train_conv.se_gate_add_relu(out, self.se_module, residual, self.relu)
+            if y is not None:
+                return y
         return self.relu(self.se_module(out) + residual)
 
 

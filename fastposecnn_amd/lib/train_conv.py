@@ -22,6 +22,10 @@ is _StemConvFn — the image repacked to NHWC4 (fpc_image_nhwc4), the forward on
 not divide into 64-pixel segments: the implicit-GEMM kernel's generic loader), the weight gradient on k_stem_wgrad
 (csrc/stem_train.hip) — and the 3x3 / stride-2 max-pool behind it is _MaxPoolFn (k_maxpool3x3s2 / k_maxpool3x3s2_bwd), counted
 in stem_fwd_native / stem_wgrad_native / pool_fwd_native / pool_bwd_native: no convolution of the step is MIOpen's then.
+The squeeze-and-excitation gate of the SE-ResNet blocks, the residual add and the ReLU behind it are torch's own by default (SEModule's
+pool, two 1x1 convolutions, sigmoid and multiply, then an add and a ReLU); with FPC_TRAIN_NATIVE_SE=1 they are _SEGateAddReLUFn: the
+forward on k_se_pool / k_se_excite / k_se_scale_add_relu (csrc/se.hip), the whole backward on csrc/se_train.hip, counted in
+se_fwd_native / se_bwd_native (a refused block in se_torch).
 
 The tiling / Winograd form of a shape is chosen once, by timing the candidates on the first call with that shape (this
 synchronises: it happens in the warm-up steps).  f32 operands, accumulation and results, products in plain f32 or as the
@@ -664,3 +668,92 @@ def batchnorm_act(x, bn, res=None, relu=True, count_refusal=True):
     bn.num_batches_tracked.add_(1)
     counters["bn_native"] += 1
     return _BatchNormActFn.apply(x, res, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum, bool(relu))
+
+
+# ---- the squeeze-and-excitation gate + residual add + ReLU of the SE-ResNet blocks (behind bn3) ------------------------------
+
+# Off by default: with it off the gate is SEModule's chain of torch ops, the add and the ReLU two more, forward and backward, as
+# before (DESIGN.md 4.2a''''').
+NATIVE_SE = bool(int(os.environ.get("FPC_TRAIN_NATIVE_SE", "0")))
+counters.update(se_fwd_native=0, se_bwd_native=0, se_torch=0)
+
+
+class _SEGateAddReLUFn(torch.autograd.Function):
+    """y = relu(x * sigmoid(fc2(relu(fc1(mean_hw(x))))) + res) on dense channel-last tensors: the forward on the inference kernels
+    (csrc/se.hip; k_se_excite also writes the means and the hidden activations), the whole backward on csrc/se_train.hip.
+    w1 [Cr, C, 1, 1] / w2 [C, Cr, 1, 1] are fc1's / fc2's weights as they stand; their gradients come back as views of those shapes."""
+
+    @staticmethod
+    def forward(ctx, x, res, w1, b1, w2, b2):
+        B, C, H, W = x.shape
+        Cr = w1.shape[0]
+        L = nat.lib()
+        dev = x.device
+        gate = torch.empty((B, C), dtype=torch.float32, device=dev)
+        mean = torch.empty((B, C), dtype=torch.float32, device=dev)
+        hidden = torch.empty((B, Cr), dtype=torch.float32, device=dev)
+        y = torch.empty_like(x, memory_format=torch.channels_last)
+        ws = nat.workspace("train_se", dev, 4 * L.fpc_se_scratch_floats(B, H, W, C))
+        nat.check(L.fpc_se_gate_train(x.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), gate.data_ptr(),
+                                      mean.data_ptr(), hidden.data_ptr(), ws.data_ptr(), B, H, W, C, C // Cr, nat.stream()),
+                  "fpc_se_gate_train")
+        nat.check(L.fpc_se_scale_add_relu(x.data_ptr(), gate.data_ptr(), res.data_ptr(), y.data_ptr(), B, H, W, C, nat.stream()),
+                  "fpc_se_scale_add_relu (training)")
+        ctx.save_for_backward(x, y, gate, mean, hidden, w1, w2)
+        counters["se_fwd_native"] += 1
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, y, gate, mean, hidden, w1, w2 = ctx.saved_tensors
+        B, C, H, W = x.shape
+        Cr = w1.shape[0]
+        L = nat.lib()
+        gy = _channels_last(gy)
+        if gy.data_ptr() % 16:
+            gy = gy.clone(memory_format=torch.channels_last)
+        need = ctx.needs_input_grad
+        dx = torch.empty_like(x, memory_format=torch.channels_last)
+        dres = torch.empty_like(x, memory_format=torch.channels_last) if need[1] else None
+        # one buffer for the four parameter gradients: dw2 [C][Cr], dw1 [Cr][C], db2 [C], db1 [Cr] (every offset a multiple of 64 floats)
+        flat = torch.empty(2 * C * Cr + C + Cr, dtype=torch.float32, device=x.device)
+        dw2, dw1, db2, db1 = flat.split((C * Cr, C * Cr, C, Cr))
+        ws = nat.workspace("train_se_bwd", x.device, 4 * L.fpc_se_bwd_scratch_floats(B, H, W, C, C // Cr))
+        nat.check(L.fpc_se_bwd(x.data_ptr(), y.data_ptr(), gy.data_ptr(), gate.data_ptr(), mean.data_ptr(), hidden.data_ptr(),
+                               w1.data_ptr(), w2.data_ptr(), dx.data_ptr(), nat.ptr(dres), dw1.data_ptr(), db1.data_ptr(), dw2.data_ptr(),
+                               db2.data_ptr(), ws.data_ptr(), B, H, W, C, C // Cr, nat.stream()), "fpc_se_bwd")
+        counters["se_bwd_native"] += 1
+        return (dx if need[0] else None, dres, dw1.view(w1.shape) if need[2] else None, db1 if need[3] else None,
+                dw2.view(w2.shape) if need[4] else None, db2 if need[5] else None)
+
+
+def _se_fc_ok(fc, cin, cout, dev):
+    return (isinstance(fc, torch.nn.Conv2d) and fc.kernel_size == (1, 1) and fc.stride == (1, 1) and fc.padding == (0, 0)
+            and fc.dilation == (1, 1) and fc.groups == 1 and fc.bias is not None and fc.in_channels == cin and fc.out_channels == cout
+            and all(t.dtype == torch.float32 and t.device == dev and t.is_contiguous() and t.data_ptr() % 16 == 0
+                    for t in (fc.weight, fc.bias)))
+
+
+def se_gate_add_relu(x, se_module, res, act=None):
+    """act(se_module(x) + res) of an SEResNetBottleneck — x is bn3's output, `act` the block's activation — as one native op each
+    way (_SEGateAddReLUFn), with NATIVE_SE (FPC_TRAIN_NATIVE_SE=1) set, under autograd, for dense channel-last 16-byte-aligned f32
+    tensors of one shape on the current device with C % 64 == 0 and C <= 8192, an se_module whose fc1 / fc2 are biased 1x1
+    convolutions with contiguous aligned f32 parameters, and nn.ReLU as BOTH the block's activation (act=None: the caller's is a
+    plain ReLU) and the gate's (a test may have swapped either for a smooth activation).  None otherwise — never a layout copy to get here — and the caller runs the
+    torch modules (counted in se_torch)."""
+    ok = (ENABLED and NATIVE_SE and torch.is_grad_enabled() and torch.is_tensor(x) and torch.is_tensor(res) and x.is_cuda
+          and x.dtype == torch.float32 and x.dim() == 4 and res.dtype == torch.float32 and res.device == x.device
+          and res.shape == x.shape and x.device.index == torch.cuda.current_device()
+          and x.shape[1] % 64 == 0 and 64 <= x.shape[1] <= 8192 and 1 <= x.shape[0] <= 65535 and x.shape[2] >= 1 and x.shape[3] >= 1
+          and x.numel() // 4 < 2 ** 32 - 4096 * 256 - 8 and _dense_nhwc(x) and _dense_nhwc(res)
+          and (act is None or isinstance(act, torch.nn.ReLU)) and isinstance(getattr(se_module, "relu", None), torch.nn.ReLU)
+          and isinstance(getattr(se_module, "sigmoid", None), torch.nn.Sigmoid)
+          and isinstance(getattr(se_module, "fc1", None), torch.nn.Conv2d) and se_module.fc1.out_channels >= 1
+          and x.shape[1] % se_module.fc1.out_channels == 0
+          and _se_fc_ok(se_module.fc1, x.shape[1], se_module.fc1.out_channels, x.device)
+          and _se_fc_ok(getattr(se_module, "fc2", None), se_module.fc1.out_channels, x.shape[1], x.device))
+    if not ok:
+        counters["se_torch"] += 1
+        return None
+    fc1, fc2 = se_module.fc1, se_module.fc2
+    return _SEGateAddReLUFn.apply(x, res, fc1.weight, fc1.bias, fc2.weight, fc2.bias)

@@ -8,6 +8,7 @@ What runs where (stated in the JSON line as well):
     FPC_TRAIN_NATIVE_STEM=1 (csrc/stem_train.hip);
     bilinear upsampling forward / backward on csrc/upsample.hip; the decoder's GroupNorm + ReLU on csrc/groupnorm.hip; the
     encoder's BatchNorm + residual add + ReLU: torch's modules, or csrc/batchnorm.hip with FPC_TRAIN_NATIVE_BN=1
+    the SE-ResNet blocks' gate + add + ReLU: torch's modules, or csrc/se.hip + csrc/se_train.hip with FPC_TRAIN_NATIVE_SE=1
     (FPC_TRAIN_NATIVE_CONV=0 returns every convolution and upsampling to torch: the A/B this file's numbers come with);
   * everything after the logits, forward: the inference kernels (class compression, connected components, aggregation,
     RANSAC vote, RT); backward: csrc/train.hip through lib/train_functions.py;
@@ -73,6 +74,9 @@ def _conv_note():
              "torch for the 7x7 stem alone (Cin = 3: outside these counters; FPC_TRAIN_NATIVE_STEM=1: native); ") + "the encoder's "
             "BatchNorm + add + ReLU " + ("fpc_batchnorm_fwd/bwd (bn_native; bn_torch: left to torch) "
                                          if train_conv.NATIVE_BN else "torch (FPC_TRAIN_NATIVE_BN=1: native) ") +
+            ("; the SE-ResNet blocks' gate + add + ReLU fpc_se_gate_train / fpc_se_scale_add_relu forward, fpc_se_bwd backward "
+             "(se_fwd_native / se_bwd_native; se_torch: left to torch) "
+             if train_conv.NATIVE_SE else "; the SE-ResNet blocks' gate + add + ReLU torch (FPC_TRAIN_NATIVE_SE=1: native) ") +
             f"(calls so far: {dict(c)})")
 
 

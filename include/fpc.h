@@ -58,6 +58,7 @@ extern "C" {
  * and the ground-truth batch builder (fpc_gt_build, fpc_depth_decode):
  * and the device PNG decode (fpc_inflate_host, fpc_png_pack_bytes, fpc_png_pack_batch, fpc_png_decode_device and its _workspace_bytes):
  * and the SE-ResNet encoders (fpc_net_create_encoder_se, fpc_se_pool_slabs, fpc_se_scratch_floats, fpc_se_gate, fpc_se_scale_add_relu, fpc_maxpool3x3s2_ceil_fwd):
+ * and their gate in the training step (fpc_se_gate_train, fpc_se_bwd_scratch_floats, fpc_se_bwd):
  * additions only, every earlier entry point keeps its behaviour. */
 #define FPC_ABI_VERSION 11
 
@@ -850,6 +851,35 @@ int fpc_se_gate(const float* x, const float* w1, const float* b1, const float* w
 int fpc_se_scale_add_relu(const float* x, const float* gate, const float* res, float* y, int B, int H, int W, int C,
                           fpc_stream_t stream);
 int fpc_maxpool3x3s2_ceil_fwd(const float* x, float* y, int B, int Hi, int Wi, int C, fpc_stream_t stream);
+
+/* ---- The same gate in the training step (csrc/se_train.hip; lib/train_conv.se_gate_add_relu behind FPC_TRAIN_NATIVE_SE=1).  They
+ * replace autograd through pretrainedmodels.senet.SEModule and through the add / ReLU of SEResNetBottleneck.forward (aten forward
+ * and backward kernels in the reference, reached from F/lib/pose_regressor.py:608-613).  Conventions, shape class and refusals of
+ * the entries above: FPC_EINVAL, before any launch, for a NULL pointer (dres alone may be NULL), a pointer that is not 16-byte
+ * aligned, C < 64 or C % 64 != 0 or C > 8192, R < 1 or R not dividing C, B < 1 or any other shape the entries above refuse.
+ *
+ * fpc_se_gate_train (k_se_pool + k_se_excite<SAVE>): fpc_se_gate, the same operations in the same order (the gate's bits are
+ *   fpc_se_gate's), that also writes what the backward reads: mean [B][C] (the slab sums in slab order, times 1 / (H W)) and
+ *   hidden [B][C / R] = relu(w1 mean + b1).  scratch: fpc_se_scratch_floats(B, H, W, C) floats.
+ * fpc_se_bwd_scratch_floats: floats of fpc_se_bwd's scratch = B * (slabs * C + 2 C + C / R) with slabs = fpc_se_pool_slabs(H, W, C):
+ *   the per-slab sums, dv, dm and dh; 0 for B < 1, a refused C or R.
+ * fpc_se_bwd (k_se_bwd_reduce, k_se_excite_bwd, k_se_param_grad, k_se_bwd_apply): the whole backward of
+ *   y = relu(x gate + res) with gate = sigmoid(w2 hidden + b2), hidden = relu(w1 mean + b1), mean = mean_hw(x), from the output
+ *   gradient gy and the forward's y, gate, mean, hidden.  With d = gy where y > 0 and 0 elsewhere:
+ *     dg[b][c] = sum_hw d x (per slab of pixels, the slabs in slab order), dv = dg gate (1 - gate),
+ *     dh[b][j] = (hidden > 0) sum_c dv[c] w2[c][j] (c ascending per thread slice, the slices in order),
+ *     dm[b][c] = sum_j dh[j] w1[j][c] (j ascending),
+ *     dx = d gate + dm (1 / (H W)),  dres = d (skipped when dres is NULL),
+ *     dw2[c][j] = sum_b dv[b][c] hidden[b][j], db2[c] = sum_b dv[b][c], dw1[j][c] = sum_b dh[b][j] mean[b][c],
+ *     db1[j] = sum_b dh[b][j] (the batch in batch order).
+ *   x, y, gy, dx, dres [B][H][W][C]; dw1 [C / R][C], db1 [C / R], dw2 [C][C / R], db2 [C]: every element of every output is
+ *   written exactly once (nothing needs zeroing), gy is only read, dx and dres are distinct from every input and from one another. */
+int fpc_se_gate_train(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, float* gate, float* mean,
+                      float* hidden, float* scratch, int B, int H, int W, int C, int R, fpc_stream_t stream);
+size_t fpc_se_bwd_scratch_floats(int B, int H, int W, int C, int R);
+int fpc_se_bwd(const float* x, const float* y, const float* gy, const float* gate, const float* mean, const float* hidden,
+               const float* w1, const float* w2, float* dx, float* dres, float* dw1, float* db1, float* dw2, float* db2, float* scratch,
+               int B, int H, int W, int C, int R, fpc_stream_t stream);
 
 /* Weight gradient of a convolution for the training step (BASELINE.json configs[4]; the reference leaves the
  * convolutions' backward to cuDNN through autograd, F/lib/pose_regressor.py:709-743 under Lightning's backward).
