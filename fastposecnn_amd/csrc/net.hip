@@ -297,6 +297,7 @@ struct fpc_net {
     int gn_P[7];
     Act a_low[4];                 // low-res logits
     Act a_lsum[4];                // two-pass merge + head: the head of the three upsampled branches' sum at their own resolution
+    int up4_wide = 1;             // 0: FPC_UP4_WIDE=0, plans of 9 to 32 classes keep k_up4_compress<32>
     int merge_split = -1;         // -1: two passes unless FPC_MERGE_SPLIT=0, 0: k_merge_head (one pass), 1: two passes
     size_t splitk_off = 0, splitk_floats = 0;
     size_t se_gate_off = 0, se_part_off = 0;      // SE plans: gate [B][2048] and the slab partials of the stage that needs most (k_se_pool / k_se_excite)
@@ -413,7 +414,7 @@ extern "C" int fpc_net_create_encoder(int block, const int* layers4, int classes
 // groups > 1 on BasicBlock, a width other than 64 without groups, channels per group outside k_conv3x3_grouped's set at any stage.
 extern "C" int fpc_net_create_encoder_ex(int block, const int* layers4, int groups, int width_per_group, int classes, int B, int H,
                                          int W, fpc_net_t** out) {
-    if (!layers4 || !out || (block != 1 && block != 4) || classes < 2 || classes > 8 || B < 1 || H < 32 || W < 32 || H % 32 ||
+    if (!layers4 || !out || (block != 1 && block != 4) || classes < 2 || classes > 32 || B < 1 || H < 32 || W < 32 || H % 32 ||
         W % 32)
         return FPC_EINVAL;
     for (int L = 0; L < 4; ++L)
@@ -436,7 +437,7 @@ extern "C" int fpc_net_create_encoder_ex(int block, const int* layers4, int grou
 // scale + residual + ReLU pass; parameters named as pretrainedmodels' (encoder.layer0.conv1.weight, encoder.layerN.i.se_module.fc1.bias).
 // Refused: a reduction that does not divide 256 (the narrowest stage output).
 extern "C" int fpc_net_create_encoder_se(const int* layers4, int reduction, int classes, int B, int H, int W, fpc_net_t** out) {
-    if (!layers4 || !out || classes < 2 || classes > 8 || B < 1 || H < 32 || W < 32 || H % 32 || W % 32) return FPC_EINVAL;
+    if (!layers4 || !out || classes < 2 || classes > 32 || B < 1 || H < 32 || W < 32 || H % 32 || W % 32) return FPC_EINVAL;
     for (int L = 0; L < 4; ++L)
         if (layers4[L] < 1 || layers4[L] > 64) return FPC_EINVAL;
     if (reduction < 1 || 256 % reduction) return FPC_EINVAL;
@@ -452,6 +453,9 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
     {   // merge + head in two passes (merge_split.hip) unless FPC_MERGE_SPLIT=0; read once, here
         const char* e = getenv("FPC_MERGE_SPLIT");
         n->merge_split = e ? (atoi(e) != 0) : 1;      // (one frame: 27 us in two passes against 32.5 us in one)
+        // 9 to 32 classes: the four-pixel x4 upsample + compression (k_up4_compress_wide) unless FPC_UP4_WIDE=0 (k_up4_compress<32>)
+        const char* u = getenv("FPC_UP4_WIDE");
+        n->up4_wide = u ? (atoi(u) != 0) : 1;
     }
     char buf[256];
 
@@ -535,6 +539,9 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
         dc.head_chp = (head_ch[d] + 3) / 4 * 4;
         dc.p_head_w = n->add_param(std::string(kHeadNames[d]) + ".0.weight", (int64_t)head_ch[d] * 128);
         dc.p_head_b = n->add_param(std::string(kHeadNames[d]) + ".0.bias", head_ch[d]);
+        // a head past one 32-channel matrix tile (10 classes and more) has the two-pass form only: k_merge_head is not widened, and
+        // FPC_MERGE_SPLIT=0 does not apply to such a plan
+        if (dc.head_chp > 32) n->merge_split = 1;
     }
     n->fold_ok = e == 1;
     if (n->fold_ok)
@@ -1468,7 +1475,7 @@ static int forward_bits(fpc_net_t* n, const float* x, float* logits_mask, float*
         u.B = B; u.hl = n->a_low[0].H; u.wl = n->a_low[0].W; u.H = H; u.W = W; u.C = n->classes;
         u.fg_bits = reinterpret_cast<unsigned long long*>(fg_bits); u.fg_stride = (size_t)((H * W + 4095) / 4096) * 64;
         if (u.hl * 4 != H || u.wl * 4 != W) return FPC_EINVAL;
-        FPC_TRY(launch_up4_compress(u, s));
+        FPC_TRY(launch_up4_compress(u, s, n->up4_wide != 0));
     }
     if (n->tuning) { n->tuning = false; n->tuned = true; }
     return FPC_OK;

@@ -579,7 +579,7 @@ int launch_merge_head(const MergeHeadArgs& a, int groups, hipStream_t s) {
     return check_launch();
 }
 
-int launch_up4_compress(const Up4Args& a, hipStream_t s) {
+int launch_up4_compress(const Up4Args& a, hipStream_t s, bool allow_wide) {
     if (a.C < 2 || a.C > 32 || a.H > 65535 || a.B > 65535) return FPC_EINVAL;
     if (a.fg_bits && a.W % 64 != 0) return FPC_EINVAL;
     dim3 grid(cdiv(a.W, 256), a.H, a.B);
@@ -591,6 +591,12 @@ int launch_up4_compress(const Up4Args& a, hipStream_t s) {
     else if (seven)
         hipLaunchKernelGGL(k_up4_compress7, dim3(cdiv(a.W, 128), a.H, a.B), dim3(128), 0, s, a);
     else if (a.C <= 8) hipLaunchKernelGGL(k_up4_compress<8>, grid, dim3(256), 0, s, a);
+    // 9 to 32 classes: four pixels per thread (up4.hip) on a plan's own channel strides and a x4 map whose rows hold whole
+    // thread quads and whose frames hold whole waves; any other shape, and FPC_UP4_WIDE=0, keep the one-pixel kernel
+    else if (allow_wide && a.pm == (a.C + 3) / 4 * 4 && a.pq == 4 * (a.C - 1) && a.pt == (3 * (a.C - 1) + 3) / 4 * 4 && a.ps == a.pt &&
+             a.H == 4 * a.hl && a.W == 4 * a.wl && ((long long)a.H * a.W) % 256 == 0 && (long long)a.H * a.W < (1LL << 31) &&
+             (long long)a.hl * a.wl * a.pq < (1LL << 32) && all_or_none)
+        launch_up4_compress_wide(a, s);
     else hipLaunchKernelGGL(k_up4_compress<32>, grid, dim3(256), 0, s, a);
     return check_launch();
 }

@@ -327,8 +327,9 @@ inline bool se_shape_ok(int B, int H, int W, int C) {
 int launch_gn_finalize(const GnFinArgs& a, int groups, hipStream_t s);
 int launch_gn_relu_up2(const GnUpArgs& a, int groups, hipStream_t s);
 int launch_merge_head(const MergeHeadArgs& a, int groups, hipStream_t s);
-int launch_up4_compress(const Up4Args& a, hipStream_t s);
+int launch_up4_compress(const Up4Args& a, hipStream_t s, bool allow_wide = true);      // allow_wide = false: 9 to 32 classes keep k_up4_compress<32>
 void launch_up4_compress7x4(const Up4Args& a, hipStream_t s);   // up4.hip; preconditions checked by launch_up4_compress
+void launch_up4_compress_wide(const Up4Args& a, hipStream_t s);  // up4.hip, 9 to 32 classes; preconditions checked by launch_up4_compress
 
 // bilinear source coordinate, align_corners=True, torch's arithmetic (UpSample.cuh):
 // src = dst * (in-1)/(out-1) in f32; i0 = (int)src; l1 = src - i0; i1 = i0 + (i0 < in-1)

@@ -4,6 +4,9 @@ A `NetEngine` binds one PoseRegressor's parameters to a native plan for a fixed 
 side repacks the weights once (OHWI, padded; BatchNorm folded), then every `forward` is a single C
 call that enqueues the whole frame's kernels on torch's current stream.  torch only owns the
 memory: parameters, the workspace and the output tensors.
+
+A plan takes 2 to 32 classes (background included), like every later stage; the library refuses more
+(`fpc_net_create*` -> FPC_EINVAL, raised by `nat.check`).
 """
 import ctypes
 import operator

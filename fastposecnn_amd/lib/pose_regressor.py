@@ -238,7 +238,8 @@ class PoseRegressor(Model, torch.nn.Module):
     # ---- native engine (inference) -------------------------------------------------------
     def _engine_for(self, x):
         """The native plan for this input, or None when the torch modules must run: training /
-        autograd (the engine has no backward), CPU tensors (config 1 plumbing), odd sizes."""
+        autograd (the engine has no backward), CPU tensors (config 1 plumbing), odd sizes.  The engine plans 2 to 32
+        classes (background included), the bound of the class compression and the metrics; a model of more raises here."""
         if (self.training or torch.is_grad_enabled() or not x.is_cuda or x.dim() != 4 or x.shape[1] != 3
                 or x.shape[2] % 32 or x.shape[3] % 32 or not getattr(self.HPARAM, 'USE_NATIVE_ENGINE', True)):
             return None

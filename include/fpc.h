@@ -517,7 +517,14 @@ int fpc_lookahead_radam_step(float* p, const float* g, float* m, float* v, float
  * (f32 matrix-core FMAs).  BatchNorm uses running statistics and Dropout2d is the identity
  * (eval mode).
  *
- * fpc_net_create     host-side plan for a fixed (encoder, classes, B, H, W); H, W multiples of 32.
+ * fpc_net_create     host-side plan for a fixed (encoder, classes, B, H, W); H, W multiples of 32;
+ *                    2 <= classes <= 32 (background included: the bound of fpc_class_compress and
+ *                    fpc_confusion), FPC_EINVAL outside — the same for every fpc_net_create_* below.
+ *                    The heads have classes / 4G / 3G / 3G channels (G = classes - 1).  A plan with a
+ *                    head wider than 32 channels (10 classes and more) always runs the merge + head in
+ *                    two passes: FPC_MERGE_SPLIT=0 (the one-pass kernel, heads of at most 32 channels)
+ *                    does not apply to it.  FPC_UP4_WIDE=0 (read at create) keeps plans of 9 to 32
+ *                    classes on the one-pixel-per-thread x4 upsample + class compression kernel.
  * fpc_net_param_*    the parameter tensors the plan needs, by state-dict name (smp naming,
  *                    e.g. "encoder.layer1.0.conv1.weight", "mask_decoder.p4.skip_conv.bias",
  *                    "rotation_decoder.seg_blocks.0.block.1.block.1.weight", "scales_head.0.weight"),
