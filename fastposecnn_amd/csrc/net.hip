@@ -14,254 +14,64 @@
 // 4 lateral 1x1 convs (FPN top-down add in the epilogue), 7 3x3 convs (GroupNorm partial sums in
 // the epilogue), 7 GroupNorm finalisations, 3 GN+ReLU+x2-upsample passes, 1 merge+head kernel,
 // 1 x4-upsample + class-compression kernel.
-#include <math.h>
+//
+// This file keeps fpc_net: building it, loading, tuning, guarding, the forward and the fpc_net_* entry points.  What is not the
+// network lives beside it: conv_plan.hpp (the host-only convolution planner: sites, plans, predicates, Winograd forms, plan codes),
+// conv_launch.hip (a plan's launch, whichever kernel it names) and conv2d.hip (the stand-alone fpc_conv2d* and geometry entry points).
 #include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
 
 #include <initializer_list>
 #include <string>
 #include <utility>
-#include <vector>
 
-#include "net_kernels.hpp"
-
-namespace fpc {
-
-struct PackedConv {
-    int Cin = 0, Cinp = 0, Cout = 0, Kh = 1, Kw = 1, stride = 1, pad = 0;   // Cinp: channels of the input LAYOUT
-    int Kwp = 1;             // taps per kernel row in the packed layout (= Kw; 8 for the stem's row-per-K-step form)
-    int K = 0, Kpad = 0, Npad = 0;
-    int p_w = -1;            // parameter index of the OIHW weight
-    int p_bn = -1;           // first of (weight, bias, running_mean, running_var) or -1
-    int p_bias = -1;         // conv bias or -1
-    size_t w_off = 0, scale_off = 0, shift_off = 0;   // float offsets into the workspace
-    size_t wino_off = 0;     // Winograd-packed copy (eligible convs only)
-    bool wino_ok = false;    // 3x3, stride 1, pad 1, Cin % 8 == 0, Cout % 64 == 0
-    size_t h3_off = 0;       // k_pack_weight_h3's image (h3_ok sites only)
-    bool h3_ok = false;      // a candidate of k_conv_igemm's three-product form: the direct sites of ResNet-18/34 plans that do not
-                             // run on Winograd — the stride-2 3x3 and 1x1 convolutions and the p5 / p4 / p3 laterals
-    int cg = 0;              // > 0: a grouped 3x3 site (conv_grouped.hip) of Cin = Cout channels in groups of cg; K = 9 cg.  It has
-    size_t grp_off = 0;      // k_pack_grouped's image only (no implicit-GEMM, Winograd or h3 image)
-};
-
-struct Act { size_t off = 0; int H = 0, W = 0, C = 0; };
-
-struct ConvPlan {
-    int bm = 64, bn = 64, nsplit = 1, mtiles = 1, ntiles = 1, wino = 0, bf3 = 0, fused = 0;
-    int lat = 0;             // > 0: k_lateral1x1 with this many workgroups per 128-pixel tile (lateral.hip) instead of k_conv_igemm
-    int stem = 0;            // > 0: k_stem7x7 (stem.hip), a persistent grid of this many workgroups (one per CU: 256)
-    int pw = 0;              // > 0: k_conv1x1 (pointwise.hip), variant pw - 1 (net_kernels.hpp: PwArgs::variant)
-    int fold = 0;            // s2.0 with wino 9 only: the FPN p2 level folded into the launch (wino_h3.hip, FOLD); no p2 lateral runs
-    int h3 = 0;              // k_conv_igemm on two fp16 pieces, three piece products (ConvArgs::h3; PackedConv::h3_ok sites)
-    int pool = 0;            // the stem site only (with stem > 0): k_stem_pool_h3 writes the pooled tensor, no stem output, no max-pool launch
-    int grp = 0;             // > 0: k_conv3x3_grouped (conv_grouped.hip), form grp - 1; the only plans of a PackedConv::cg site
-};
-
-// the 7x7 / stride-2 / pad-3 stem in its row-per-K-step layout (NHWC4 image, 8 taps x 4 channels per kernel row, K = 224) with a
-// BatchNorm / bias-only epilogue and an output row that divides into 64-pixel segments
-static bool stem_ok(const ConvArgs& a) {
-    return a.lanepx == 1 && a.generic == 0 && a.Kh == 7 && a.stride == 2 && a.pad == 3 && a.Cout == 64 && a.Kpad == 224 &&
-           a.Wo % 64 == 0 && !a.p[0].res && !a.p[0].up && !a.p[0].gn_part && a.in_sc == 1 && a.in_sw == 4 &&
-           a.in_sh == (long long)4 * a.Wi && a.in_sb == (long long)4 * a.Hi * a.Wi;
-}
-
-// a grouped 1x1 / stride-1 site with K = 64 or 128, bias-only epilogue and one input shared by the groups: the FPN laterals
-// of the stride-4 and stride-8 maps (and fpc_conv2d's test hook)
-static bool lateral_ok(const ConvArgs& a, int groups) {
-    if (a.Kh != 1 || a.Kw != 1 || a.stride != 1 || a.pad != 0 || a.generic != 0 || (a.Cin != 64 && a.Cin != 128) || a.Kpad != a.Cin ||
-        a.Cout % 32 != 0 || a.in_sc != 1 || a.in_sw != a.Cin || a.in_sh != (long long)a.Wi * a.Cin ||
-        a.in_sb != (long long)a.Hi * a.Wi * a.Cin || a.lanepx)
-        return false;
-    for (int g = 0; g < groups; ++g)
-        if (a.p[g].in != a.p[0].in || a.p[g].scale || a.p[g].res || a.p[g].gn_part || ((a.p[g].up != nullptr) != (a.p[0].up != nullptr)))
-            return false;
-    return !(a.p[0].up && ((a.Ho | a.Wo) & 1));
-}
-
-// a 1x1 site k_conv1x1 takes: K a multiple of 64, Cout of 64, stride 1 or 2, channel-contiguous input shared by the groups,
-// no GroupNorm partials and the same epilogue operands in every group
-static bool pw_ok(const ConvArgs& a, int groups) {
-    if (a.Kh != 1 || a.Kw != 1 || a.pad != 0 || (a.stride != 1 && a.stride != 2) || a.generic != 0 || a.lanepx || a.Cin % 64 != 0 ||
-        a.Kpad != a.Cin || a.Cout % 64 != 0 || a.in_sc != 1)
-        return false;
-    for (int g = 0; g < groups; ++g)
-        if (a.p[g].in != a.p[0].in || a.p[g].gn_part || (a.p[g].scale != nullptr) != (a.p[0].scale != nullptr) ||
-            (a.p[g].shift != nullptr) != (a.p[0].shift != nullptr) || (a.p[g].res != nullptr) != (a.p[0].res != nullptr) ||
-            (a.p[g].up != nullptr) != (a.p[0].up != nullptr))
-            return false;
-    return !(a.p[0].up && ((a.Ho | a.Wo) & 1));
-}
-
-// fused split-K (ConvArgs::fused) needs one arrival counter per output tile
-static bool can_fuse(const ConvPlan& p, int groups, int B) {
-    return p.nsplit > 1 && (long long)groups * B * p.mtiles * p.ntiles <= kConvTickets;
-}
-
-static ConvPlan plan_conv(int HoWo, int B, int Cout, int ksteps, int groups, int force_bm = 0, int force_bn = 0,
-                          int force_split = 0) {
-    ConvPlan best;
-    double best_t = 1e300;
-    const int bms[2] = {64, 128}, bns[2] = {64, 128};
-    for (int bi = 0; bi < 2; ++bi)
-        for (int bj = 0; bj < 2; ++bj) {
-            int bm = bms[bi], bn = bns[bj];
-            if (force_bm && bm != force_bm) continue;
-            if (force_bn && bn != force_bn) continue;
-            if (!force_bn && bn == 128 && Cout <= 64) continue;
-            int mt = cdiv(HoWo, bm), nt = cdiv(Cout, bn);
-            for (int ns = 1; ns <= 32; ++ns) {
-                if (force_split && ns != force_split) continue;
-                int per = cdiv(ksteps, ns);
-                if ((ns - 1) * per >= ksteps) continue;
-                if (ns > 1 && (Cout % 4 != 0)) continue;
-                double nblk = (double)groups * B * mt * nt * ns;
-                double work = (double)(bm / 64) * (bn / 64) * per * 16.0 * 64.0 + 4000.0;
-                double t = ceil(nblk / 256.0) * work + (ns > 1 ? 10000.0 + 200.0 * ns : 0.0);
-                if (t < best_t) { best_t = t; best = ConvPlan{bm, bn, ns, mt, nt, 0}; }
-            }
-        }
-    best.fused = can_fuse(best, groups, B) ? 1 : 0;
-    return best;
-}
-
-// Tilings the autotuner may try for one convolution site (the heuristic plan is always among them).
-static std::vector<ConvPlan> conv_candidates(int HoWo, int B, int Cout, int ksteps, int groups) {
-    std::vector<ConvPlan> out;
-    const int splits[] = {1, 2, 3, 4, 6, 8, 12, 16, 24};
-    for (int bm = 64; bm <= 128; bm += 64)
-        for (int bn = 64; bn <= 128; bn += 64) {
-            if (bn == 128 && Cout <= 64) continue;
-            int mt = cdiv(HoWo, bm), nt = cdiv(Cout, bn);
-            long long base = (long long)groups * B * mt * nt;
-            for (int ns : splits) {
-                int per = cdiv(ksteps, ns);
-                if (ns > 1 && (per < 2 || (ns - 1) * per >= ksteps || Cout % 4 != 0)) continue;
-                if (ns > 1 && base * ns > 4096) continue;          // already plenty of workgroups
-                out.push_back(ConvPlan{bm, bn, ns, mt, nt, 0});
-                if (can_fuse(out.back(), groups, B)) { ConvPlan f = out.back(); f.fused = 1; out.push_back(f); }
-            }
-        }
-    return out;
-}
-
-static size_t splitk_floats_for(const ConvPlan& p, int groups, int B, int Npad) {
-    return p.nsplit > 1 ? (size_t)groups * p.nsplit * B * p.mtiles * p.bm * Npad : 0;
-}
-
-// ---- the Winograd forms (ConvPlan::wino = 1..9, reported and requested as -form) and the weight images they read.
-// A new form adds: one row of kWinoForms, one entry of kWinoImages if it reads an image of its own, and its launcher.
-// A site's image region holds the images in the order of kWinoImages, each `units` x Cout x Cin floats followed by `tail` floats; the
-// 128-channel form's image is there only where Cout % 128 == 0.  Behind the last image the region keeps kWinoSlack floats.
-enum WinoImage { kImgF32, kImgBf3, kImgC128, kImgH2, kImgH3, kWinoImageCount };
-struct WinoImageDesc { int units, tail; int (*pack)(const float* w_oihw, float* packed, int Cout, int Cin, hipStream_t s); };
-static int pack_h3_plain(const float* w_oihw, float* packed, int Cout, int Cin, hipStream_t s) { return launch_wino_pack_h3(w_oihw, packed, Cout, Cin, false, s); }
-constexpr WinoImageDesc kWinoImages[kWinoImageCount] = {
-    {16, 0, launch_wino_pack},            // f32
-    {24, 0, launch_wino_pack_bf3},        // split precision: three bf16 planes
-    {24, 0, launch_wino_pack_c128},       // ... in the 128-channel form's fragment order (wino128.hip)
-    {16, 8, launch_wino_pack_h2},         // two fp16 pieces in fragment order (wino_h2.hip); the tail: its two scale floats, kept 32-byte aligned
-    {16, 8, pack_h3_plain},               // ... in pair order (wino_h3.hip), with the same tail; a transposed site's: pack_wino_h3_image
-};
-constexpr size_t kWinoSlack = 128;      // a 64-float line for the tails + 64 zero floats (fpc_conv2d's zero page where the code object has none)
-
-constexpr int kWinoFormCount = 10;      // forms 1..9; row 0 is "not Winograd"
-constexpr int kWinoBf3 = 5, kWinoW4 = 7;     // the range-free split-precision forms a guarded site falls back to (-7 where offered, else -5)
-constexpr int kWinoH2 = 8, kWinoH3 = 9;      // the fp16 x 2 form and its three-product form: the one launch that may pack frames or fold p2 in
-struct WinoForm {
-    int waves;               // 4: 8 x 4 tile patch per workgroup, 8: 8 x 8
-    int bn, ck;              // output channels per workgroup; input channels per K-loop step: Cout and Cin are multiples of these
-    int variant;             // WinoArgs::variant
-    WinoImage image;
-    int wg_per_cu;           // workgroups of the form that share a CU (the tuner's occupancy share)
-    int min_split;           // lowest fpc_net_set_split_precision level at which the tuner offers the form
-    bool zeros;              // reads the zero page (WinoArgs::zeros)
-    bool range_limited;      // two fp16 pieces per operand: the activation envelope of fpc.h (fpc_net_guard_ranges demotes such a site)
-    int (*launch)(const WinoArgs& a, int groups, hipStream_t s);
-};
-constexpr WinoForm kWinoForms[kWinoFormCount] = {
-    {},
-    {4, 64, 8, 0, kImgF32, 2, 0, false, false, launch_conv_wino},      // -1: 4 waves
-    {8, 64, 8, 0, kImgF32, 1, 0, false, false, launch_conv_wino},      // -2: 8 waves
-    {4, 64, 8, 1, kImgF32, 2, 0, false, false, launch_conv_wino},      // -3: wave-private K loop
-    {8, 64, 8, 2, kImgF32, 1, 0, true, false, launch_conv_wino},       // -4: all-DMA 3-stage
-    {8, 64, 8, 3, kImgBf3, 1, 1, true, false, launch_conv_wino},       // -5: split-precision products, 8 waves
-    {4, 128, 8, 0, kImgC128, 1, 1, false, false, launch_conv_wino_c128},      // -6: ... 8 x 4 tiles x 128 channels per workgroup, 4 waves (wino128.hip)
-    {8, 64, 8, 0, kImgBf3, 1, 1, false, false, launch_conv_wino_w4},   // -7: ... 64 channels, four waves of 512 registers, weights direct (wino_w4.hip)
-    {8, 64, 8, 0, kImgH2, 1, 2, false, true, launch_conv_wino_h2},     // -8: the -7 form on two fp16 pieces per operand (range-limited: fpc.h; wino_h2.hip)
-    {8, 64, 16, 0, kImgH3, 1, 3, false, true, launch_conv_wino_h3},    // -9: three of the four piece products of -8, over pairs of K-steps (wino_h3.hip)
-};
-// the shape rules of a form, on top of PackedConv::wino_ok
-static bool wino_form_ok(int form, int Cin, int Cout) {
-    return form >= 1 && form < kWinoFormCount && Cout % kWinoForms[form].bn == 0 && Cin % kWinoForms[form].ck == 0;
-}
-// units and tail floats of the images in front of image `end`; c128: the region has the 128-channel form's image
-struct WinoSpan { size_t units, tails; };
-static WinoSpan wino_span(int end, bool c128) {
-    WinoSpan sp{0, 0};
-    for (int i = 0; i < end; ++i)
-        if (i != kImgC128 || c128) { sp.units += kWinoImages[i].units; sp.tails += kWinoImages[i].tail; }
-    return sp;
-}
-static_assert(kWinoImages[kImgH2].tail + kWinoImages[kImgH3].tail <= 64, "kWinoSlack keeps one 64-float line for all tails");
-// float offset of image `img` in a site's region
-static size_t wino_image_offset(WinoImage img, int Cout, int Cin) {
-    const WinoSpan sp = wino_span(img, Cout % 128 == 0);
-    return sp.units * Cout * Cin + sp.tails;
-}
-// floats of a region that ends with image `last`: what one form needs (fpc_conv2d's exact workspace), and with the last image of
-// all what a site needs (fpc_net::add_conv); c128 = true bounds both (fpc_conv2d_workspace_bytes)
-static size_t wino_region_floats(WinoImage last, int Cout, int Cin, bool c128) { return (wino_span(last, c128).units + kWinoImages[last].units) * Cout * Cin + kWinoSlack; }
-// a plan whose matrix products run on two fp16 pieces per operand, i.e. under the activation envelope: the range-limited Winograd
-// forms (packed or not, with or without the p2 fold), the three-product direct and lateral forms, the stem fused with its max-pool
-static bool plan_range_limited(const ConvPlan& p) {
-    return p.h3 || p.fold || p.pool || (p.wino && kWinoForms[p.wino].range_limited);
-}
-// tile patches of one frame: tbx x tby workgroups per (frame, channel block, group)
-struct WinoGrid { int tbx, tby; int patches() const { return tbx * tby; } };
-static WinoGrid wino_grid(int form, int H, int W) { return {cdiv(cdiv(W, 2), 8), cdiv(cdiv(H, 2), kWinoForms[form].waves)}; }
-
-// ---- the integer a plan is reported by (fpc_net_conv_plan's out5[2]) and requested by (fpc_conv2d's `nsplit`): fpc.h, FPC_PLAN_*.
-// What a request asks for (nsplit: the split-K factor, 0 = the planner's, or -form; wino: the form or 0):
-struct Conv2dRequest { int nsplit; bool bf3, two_launch; int wino, lat; bool stem; int pw; bool h3, pool, pack, orient; int grp; };
-static Conv2dRequest decode_plan(int code) {
-    Conv2dRequest r{code, false, false, 0, 0, false, 0, false, false, false, false, 0};
-    if (code >= FPC_PLAN_GROUPED && code < FPC_PLAN_GROUPED + 1000) { r.grp = code - FPC_PLAN_GROUPED + 1; r.nsplit = 1; return r; }      // + form = k_conv3x3_grouped (fpc_conv2d_grouped's request; fpc_conv2d has no groups and refuses it)
-    if (code == FPC_PLAN_WINO_ORIENT) { r.orient = true; r.nsplit = -kWinoH3; }      // form -9 in the orientation its shape asks for (wino_orient_rule), transposed sites packed along y
-    if (code == FPC_PLAN_WINO_PACKED) { r.pack = true; r.nsplit = -kWinoH3; }      // form -9 with its patches cut out of canvas rows of several frames (wino_pack_geometry)
-    if (r.nsplit >= FPC_PLAN_LATERAL_H3 && r.nsplit < FPC_PLAN_LATERAL_H3 + 1000) { r.lat = r.nsplit - FPC_PLAN_LATERAL_H3; r.h3 = true; r.nsplit = 1; return r; }      // + parts = k_lateral1x1 on two fp16 pieces
-    if (r.nsplit >= FPC_PLAN_H3 && r.nsplit < FPC_PLAN_H3 + 200) { r.h3 = true; r.nsplit -= FPC_PLAN_H3; }      // + split = k_conv_igemm's three-product form; what is left (< 200) reaches the two-launch line only
-    if (r.nsplit >= FPC_PLAN_POINTWISE) { r.pw = r.nsplit - FPC_PLAN_POINTWISE + 1; r.bf3 = true; r.nsplit = 1; return r; }   // + variant = k_conv1x1 (pointwise.hip)
-    if (r.nsplit == FPC_PLAN_STEM_POOL) { r.stem = true; r.pool = true; r.h3 = true; r.nsplit = 1; return r; }     // k_stem_pool_h3: NHWC4 input, `out` = the POOLED tensor
-    if (r.nsplit == FPC_PLAN_STEM) { r.stem = true; r.bf3 = true; r.nsplit = 1; return r; }                   // k_stem7x7 (stem.hip): NHWC4 input
-    if (r.nsplit >= FPC_PLAN_LATERAL) { r.lat = r.nsplit - FPC_PLAN_LATERAL; r.bf3 = true; r.nsplit = 1; return r; }      // + parts = k_lateral1x1 (lateral.hip)
-    if (r.nsplit >= FPC_PLAN_BF3) { r.bf3 = true; r.nsplit -= FPC_PLAN_BF3; }          // + split = split-precision matrix products
-    if (r.nsplit >= FPC_PLAN_TWO_LAUNCH) { r.two_launch = true; r.nsplit -= FPC_PLAN_TWO_LAUNCH; }      // + split = split-K summed by k_conv_splitk_epilogue
-    if (r.nsplit <= -1 && r.nsplit > -kWinoFormCount) r.wino = -r.nsplit;      // -form: kWinoForms
-    return r;
-}
-// What a plan reports; folded_away: the p2 lateral site while s2.0 runs with that level folded in (never a request)
-static int encode_plan(const ConvPlan& p, bool folded_away) {
-    if (folded_away) return FPC_PLAN_FOLDED;
-    if (p.grp) return FPC_PLAN_GROUPED + p.grp - 1;
-    // the three-product form: k_conv_igemm + split (fused or not, as the plain tilings), k_lateral1x1 + parts
-    if (p.h3) return p.lat ? FPC_PLAN_LATERAL_H3 + p.lat : FPC_PLAN_H3 + p.nsplit;
-    if (p.pw) return FPC_PLAN_POINTWISE + p.pw - 1;
-    if (p.stem) return p.pool ? FPC_PLAN_STEM_POOL : FPC_PLAN_STEM;
-    if (p.lat) return FPC_PLAN_LATERAL + p.lat;
-    return p.wino ? -p.wino : p.nsplit;
-}
-
-}  // namespace fpc
+#include "conv_plan.hpp"
 
 using namespace fpc;
 
-struct fpc_net {
-    int layers[4];
-    int classes, B, H, W;
+// ---- the encoder block kinds, each stated once.  A block is up to three convolution sites with BatchNorm in PARAMETER order
+// (encoder.layerN.i.conv1 / bn1, conv2 / bn2, conv3 / bn3), each between two of the block's buffers, then — SE only — the four
+// se_module parameters, then the downsample (1x1 with the block's stride and BatchNorm, In -> D) where the block's stride is not 1 or
+// its channels change.  Channels follow from the buffers: In has the predecessor's, T1 and T2 planes * width / 64 * groups, D and Y
+// planes * expansion.  net_build turns this statement into the parameter table, the activation buffers and the encoder tape.
+enum Buf { kBufNone, kBufIn, kBufT1, kBufT2, kBufD, kBufY, kBufRes, kBufCount };      // Res: D where the block has a downsample, else In
+// k: 3 = 3x3 / pad 1, 1 = 1x1 / pad 0; strided: the site that carries the block's stride; grouped: a grouped 3x3 (add_grouped_conv) in
+// an encoder with groups, dense in every other; res: the residual added in the epilogue, or kBufNone
+struct BlockSite { int k; bool strided, grouped; Buf in, out; bool relu; Buf res; };
+struct BlockKind {
+    int nsites;
+    BlockSite site[3];
+    int ds_before;           // LAUNCH order: the downsample runs in front of this site, whose epilogue (or whose gate) consumes it
+    bool se_gate;            // se_module.fc1 / fc2 (weight, bias) behind the last site's parameters; behind its launch the gate step: Y's
+                             // channel means, the two fc layers, then Y = relu(Y * gate + Res) in place (se.hip: three launches)
+    bool shared;             // true: a stage's blocks share T1 (block 0's, the largest), T2, D and two outputs in turn — only a block's
+                             // output feeds the next block, which reads it as input and residual; false: every block has its own T1, Y, D
+};
+// BasicBlock: 3x3 (stride) -> 3x3 + residual
+constexpr BlockKind kBasicBlock = {2, {{3, true, false, kBufIn, kBufT1, true, kBufNone}, {3, false, false, kBufT1, kBufY, true, kBufRes}}, 1, false, false};
+// torchvision's Bottleneck: 1x1 -> 3x3 (stride; grouped in the ResNeXt encoders) -> 1x1 x 4 + residual
+constexpr BlockKind kBottleneck = {3, {{1, false, false, kBufIn, kBufT1, true, kBufNone}, {3, true, true, kBufT1, kBufT2, true, kBufNone}, {1, false, false, kBufT2, kBufY, true, kBufRes}}, 2, false, true};
+// pretrainedmodels' SEResNetBottleneck: 1x1 (stride) -> 3x3 (a Winograd site at every stage) -> 1x1 x 4 with BatchNorm only -> gate
+constexpr BlockKind kSEBottleneck = {3, {{1, true, false, kBufIn, kBufT1, true, kBufNone}, {3, false, false, kBufT1, kBufT2, true, kBufNone}, {1, false, false, kBufT2, kBufY, false, kBufNone}}, 2, true, true};
+
+// The encoder descriptor: all that tells one encoder from another.  Beside the block statements above it is the only place that
+// knows a block kind; the rest of the engine walks the tape.
+struct EncoderDesc {
     int expansion = 1;            // 1: BasicBlock encoder, 4: Bottleneck (1x1, 3x3 with the stride, 1x1 x 4)
     int groups = 1, width = 64;   // Bottleneck: conv2's groups and torchvision's width_per_group (ResNeXt: 32 and 4 / 8); (1, 64) = ResNet
     int se = 0;                   // > 0: the SE-ResNet Bottleneck (pretrainedmodels.senet) with this reduction; expansion is 4 then
+    int layers[4] = {};           // blocks per stage
+    const BlockKind& kind() const { return se ? kSEBottleneck : expansion == 4 ? kBottleneck : kBasicBlock; }
+    const char* stem_prefix() const { return se ? "encoder.layer0." : "encoder."; }      // torchvision's stem names, pretrainedmodels'
+    // the SE-ResNet stem pool: no padding, ceil_mode (other windows, the same size on the even maps every plan has): its own max-pool launch, never the fused stem + pool
+    bool ceil_pool() const { return se != 0; }
+    bool basic() const { return expansion == 1; }         // c2 has 64 channels: s2.0 may fold the FPN p2 level in, and the direct sites have three-product images
+    bool pointwise() const { return expansion == 4; }     // the autotuner offers k_conv1x1 to the 1x1 sites
+};
+
+struct fpc_net {
+    EncoderDesc enc;
+    int classes, B, H, W;
     std::vector<std::string> pnames;
     std::vector<int64_t> pnumel;
     std::vector<const float*> pptr;
@@ -276,8 +86,10 @@ struct fpc_net {
 
     // conv indices
     int c_stem = -1;
-    struct Block { int conv1, conv2, ds, conv3 = -1; int p_se = -1; };      // conv3: Bottleneck only; p_se: first of se_module's (fc1.weight, fc1.bias, fc2.weight, fc2.bias)
-    std::vector<Block> blocks[4];
+    // The encoder tape: every launch between the max-pool and the decoders, in launch order.  conv >= 0: that site from `in` to `out` with BatchNorm, `res`
+    // (C > 0) and ReLU in its epilogue; conv < 0: an SE block's gate step on `out` in place, with the residual `res` and se_module's four parameters from p_se
+    struct Step { int conv; Act in, out; bool relu; Act res; int p_se; };
+    std::vector<Step> tape;
     struct Dec {
         int lat[4];               // p5, p4, p3, p2 (1x1, bias)
         int seg[7];               // s5.0 s5.1 s5.2 s4.0 s4.1 s3.0 s2.0
@@ -288,8 +100,7 @@ struct fpc_net {
 
     // activations (float offsets)
     Act a_img4, a_stem, a_pool;
-    std::vector<Act> a_blk_t[4], a_blk_y[4], a_blk_d[4];
-    std::vector<Act> a_blk_t2[4];  // Bottleneck: conv2's output (a_blk_t: conv1's); a stage's blocks share T1, T2 and two outputs
+    Act a_feat[4];                // c2 .. c5: the output of each stage's last block
     Act a_p[4][4];                // [decoder][p5,p4,p3,p2]
     Act a_seg[4][7];              // pre-GroupNorm conv outputs
     Act a_up[4][3];               // s5.0 -> up, s5.1 -> up, s4.0 -> up
@@ -333,6 +144,10 @@ struct fpc_net {
     size_t alloc(size_t n) { size_t o = bump; bump += (n + 63) / 64 * 64; return o; }
     Act alloc_act(int h, int w, int c) { Act a; a.H = h; a.W = w; a.C = c; a.off = alloc((size_t)B * h * w * c); return a; }
     int add_param(const std::string& n, int64_t numel) { pnames.push_back(n); pnumel.push_back(numel); return (int)pnames.size() - 1; }
+    int add_bn(const std::string& p, int C) {      // BatchNorm's four -> the index of the first
+        add_param(p + ".weight", C); add_param(p + ".bias", C); add_param(p + ".running_mean", C);
+        return add_param(p + ".running_var", C) - 3;
+    }
 
     int add_conv(const std::string& wname, int Cin, int Cout, int k, int stride, int pad, const char* bn_prefix,
                  const char* bias_name, int Cinp = 0, int Kwp = 0) {
@@ -341,13 +156,7 @@ struct fpc_net {
         c.Kwp = Kwp ? Kwp : k;
         c.K = c.Cinp * k * c.Kwp; c.Kpad = cdiv(c.K, kConvBK) * kConvBK; c.Npad = cdiv(Cout, kConvNAlign) * kConvNAlign;
         c.p_w = add_param(wname, (int64_t)Cout * Cin * k * k);
-        if (bn_prefix) {
-            std::string p(bn_prefix);
-            c.p_bn = add_param(p + ".weight", Cout);
-            add_param(p + ".bias", Cout);
-            add_param(p + ".running_mean", Cout);
-            add_param(p + ".running_var", Cout);
-        }
+        if (bn_prefix) c.p_bn = add_bn(bn_prefix, Cout);
         if (bias_name) c.p_bias = add_param(bias_name, Cout);
         c.w_off = alloc(conv_packed_floats(c.Npad, c.Kpad));      // f32 image + its three bf16 planes
         if (bn_prefix) { c.scale_off = alloc(Cout); c.shift_off = alloc(Cout); }
@@ -362,11 +171,7 @@ struct fpc_net {
         c.Cin = c.Cinp = c.Cout = C; c.Kh = c.Kw = c.Kwp = 3; c.stride = stride; c.pad = 1; c.cg = cg;
         c.K = cg * 9; c.Kpad = cdiv(c.K, kConvBK) * kConvBK; c.Npad = cdiv(C, kConvNAlign) * kConvNAlign;
         c.p_w = add_param(wname, (int64_t)C * cg * 9);
-        std::string p(bn_prefix);
-        c.p_bn = add_param(p + ".weight", C);
-        add_param(p + ".bias", C);
-        add_param(p + ".running_mean", C);
-        add_param(p + ".running_var", C);
+        c.p_bn = add_bn(bn_prefix, C);
         c.grp_off = alloc((size_t)C * cg * 9);
         c.scale_off = alloc(C); c.shift_off = alloc(C);
         convs.push_back(c);
@@ -382,25 +187,35 @@ static void drop_graph(fpc_net* n) {
 static const char* kDecNames[4] = {"mask_decoder", "rotation_decoder", "translation_decoder", "scales_decoder"};
 static const char* kHeadNames[4] = {"segmentation_head", "rotation_head", "translation_head", "scales_head"};
 
-static int conv_out(int x, int k, int s, int p) { return (x + 2 * p - k) / s + 1; }
-
-// the plan of `n` (layers and expansion set) for (classes, B, H, W); owns `n` (deleted on failure)
+// the plan of `n` (its encoder descriptor set) for (classes, B, H, W); owns `n` (deleted on failure)
 static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** out);
 
-extern "C" int fpc_net_create(const char* encoder, int classes, int B, int H, int W, fpc_net_t** out) {
-    const int r18[4] = {2, 2, 2, 2}, r34[4] = {3, 4, 6, 3}, r101[4] = {3, 4, 23, 3};
-    if (!encoder) return FPC_EINVAL;
+// The one creation path: the checks every entry shares, then the plan.  A wrapper keeps only the refusals of its own arguments.
+static int create(EncoderDesc d, const int* layers4, int classes, int B, int H, int W, fpc_net_t** out) {
+    if (!layers4 || !out || classes < 2 || classes > 32 || B < 1 || H < 32 || W < 32 || H % 32 || W % 32) return FPC_EINVAL;
+    for (int L = 0; L < 4; ++L)
+        if (layers4[L] < 1 || layers4[L] > 64) return FPC_EINVAL;
+    memcpy(d.layers, layers4, sizeof(d.layers));
+    return net_build(new fpc_net{d}, classes, B, H, W, out);
+}
+
+// the encoders fpc_net_create knows by name: {expansion, groups, width, se reduction, layers}
+static const struct { const char* name; EncoderDesc desc; } kEncoders[] = {
+    {"resnet18", {1, 1, 64, 0, {2, 2, 2, 2}}}, {"resnet34", {1, 1, 64, 0, {3, 4, 6, 3}}},
     // the ResNeXt encoders: Bottleneck x {3,4,6,3} / {3,4,23,3} with 32 groups of width 4 (8) on conv2
-    if (!strcmp(encoder, "resnext50_32x4d")) return fpc_net_create_encoder_ex(4, r34, 32, 4, classes, B, H, W, out);
-    if (!strcmp(encoder, "resnext101_32x4d")) return fpc_net_create_encoder_ex(4, r101, 32, 4, classes, B, H, W, out);
-    if (!strcmp(encoder, "resnext101_32x8d")) return fpc_net_create_encoder_ex(4, r101, 32, 8, classes, B, H, W, out);
+    {"resnext50_32x4d", {4, 32, 4, 0, {3, 4, 6, 3}}},
+    {"resnext101_32x4d", {4, 32, 4, 0, {3, 4, 23, 3}}},
+    {"resnext101_32x8d", {4, 32, 8, 0, {3, 4, 23, 3}}},
     // the SE-ResNets: pretrainedmodels' SEResNetBottleneck x {3,4,6,3} / {3,4,23,3} / {3,8,36,3}, reduction 16
-    const int r152[4] = {3, 8, 36, 3};
-    if (!strcmp(encoder, "se_resnet50")) return fpc_net_create_encoder_se(r34, 16, classes, B, H, W, out);
-    if (!strcmp(encoder, "se_resnet101")) return fpc_net_create_encoder_se(r101, 16, classes, B, H, W, out);
-    if (!strcmp(encoder, "se_resnet152")) return fpc_net_create_encoder_se(r152, 16, classes, B, H, W, out);
-    if (strcmp(encoder, "resnet18") && strcmp(encoder, "resnet34")) return FPC_EINVAL;
-    return fpc_net_create_encoder(1, strcmp(encoder, "resnet18") ? r34 : r18, classes, B, H, W, out);
+    {"se_resnet50", {4, 1, 64, 16, {3, 4, 6, 3}}},
+    {"se_resnet101", {4, 1, 64, 16, {3, 4, 23, 3}}},
+    {"se_resnet152", {4, 1, 64, 16, {3, 8, 36, 3}}},
+};
+
+extern "C" int fpc_net_create(const char* encoder, int classes, int B, int H, int W, fpc_net_t** out) {
+    for (const auto& e : kEncoders)
+        if (encoder && !strcmp(encoder, e.name)) return create(e.desc, e.desc.layers, classes, B, H, W, out);
+    return FPC_EINVAL;
 }
 
 // An encoder by its descriptor: block 1 = BasicBlock, 4 = Bottleneck (torchvision's: the stride on the 3x3), layers4 = blocks per
@@ -414,22 +229,14 @@ extern "C" int fpc_net_create_encoder(int block, const int* layers4, int classes
 // groups > 1 on BasicBlock, a width other than 64 without groups, channels per group outside k_conv3x3_grouped's set at any stage.
 extern "C" int fpc_net_create_encoder_ex(int block, const int* layers4, int groups, int width_per_group, int classes, int B, int H,
                                          int W, fpc_net_t** out) {
-    if (!layers4 || !out || (block != 1 && block != 4) || classes < 2 || classes > 32 || B < 1 || H < 32 || W < 32 || H % 32 ||
-        W % 32)
-        return FPC_EINVAL;
-    for (int L = 0; L < 4; ++L)
-        if (layers4[L] < 1 || layers4[L] > 64) return FPC_EINVAL;
+    if (block != 1 && block != 4) return FPC_EINVAL;
     if (groups < 1 || width_per_group < 1 || (groups == 1 && width_per_group != 64) || (groups > 1 && block != 4)) return FPC_EINVAL;
     if (groups > 1)
         for (int planes = 64; planes <= 512; planes *= 2) {
             const int cg = planes * width_per_group / 64;      // torchvision: width = int(planes * base_width / 64) * groups
             if (!grouped_cg_ok(cg) || (long long)cg * groups > 8192 || (cg * groups) % 64) return FPC_EINVAL;
         }
-    fpc_net* n = new fpc_net();
-    memcpy(n->layers, layers4, sizeof(n->layers));
-    n->expansion = block;
-    n->groups = groups; n->width = width_per_group;
-    return net_build(n, classes, B, H, W, out);
+    return create({block, groups, width_per_group}, layers4, classes, B, H, W, out);
 }
 
 // The SE-ResNet encoders: SEResNetBottleneck x layers4 — conv1 1x1 WITH the stride, conv2 a dense 3x3 / stride 1 (a Winograd site at
@@ -437,15 +244,8 @@ extern "C" int fpc_net_create_encoder_ex(int block, const int* layers4, int grou
 // scale + residual + ReLU pass; parameters named as pretrainedmodels' (encoder.layer0.conv1.weight, encoder.layerN.i.se_module.fc1.bias).
 // Refused: a reduction that does not divide 256 (the narrowest stage output).
 extern "C" int fpc_net_create_encoder_se(const int* layers4, int reduction, int classes, int B, int H, int W, fpc_net_t** out) {
-    if (!layers4 || !out || classes < 2 || classes > 32 || B < 1 || H < 32 || W < 32 || H % 32 || W % 32) return FPC_EINVAL;
-    for (int L = 0; L < 4; ++L)
-        if (layers4[L] < 1 || layers4[L] > 64) return FPC_EINVAL;
     if (reduction < 1 || 256 % reduction) return FPC_EINVAL;
-    fpc_net* n = new fpc_net();
-    memcpy(n->layers, layers4, sizeof(n->layers));
-    n->expansion = 4;
-    n->se = reduction;
-    return net_build(n, classes, B, H, W, out);
+    return create({4, 1, 64, reduction}, layers4, classes, B, H, W, out);
 }
 
 static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** out) {
@@ -460,54 +260,40 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
     char buf[256];
 
     // ---- parameters + packed storage (persistent region first)
-    n->c_stem = n->se ? n->add_conv("encoder.layer0.conv1.weight", 3, 64, 7, 2, 3, "encoder.layer0.bn1", nullptr, 4, 8)
-                      : n->add_conv("encoder.conv1.weight", 3, 64, 7, 2, 3, "encoder.bn1", nullptr, 4, 8);     // NHWC4 pixels, 8 taps per row
+    const EncoderDesc& enc = n->enc;
+    const BlockKind& kind = enc.kind();
+    const std::string stem(enc.stem_prefix());
+    n->c_stem = n->add_conv(stem + "conv1.weight", 3, 64, 7, 2, 3, (stem + "bn1").c_str(), nullptr, 4, 8);     // NHWC4 pixels, 8 taps per row
     const int planes[4] = {64, 128, 256, 512};
-    const int e = n->expansion;
+    const int e = enc.expansion;
+    struct Block { int conv[3], ds, p_se, stride, ch[kBufCount]; };      // a block's sites as created here, for the buffers and the tape below
+    std::vector<Block> blocks[4];
     int inpl = 64;
     for (int L = 0; L < 4; ++L)
-        for (int bi = 0; bi < n->layers[L]; ++bi) {
-            int stride = (bi == 0 && L > 0) ? 2 : 1;
-            fpc_net::Block blk;
+        for (int bi = 0; bi < enc.layers[L]; ++bi) {
+            const int mid = planes[L] * enc.width / 64 * enc.groups, C = e * planes[L];      // (mid: planes[L] but in the ResNeXt encoders)
+            Block blk{{-1, -1, -1}, -1, -1, (bi == 0 && L > 0) ? 2 : 1, {0, inpl, mid, mid, C, C, C}};      // (channels by Buf)
+            const int* ch = blk.ch;
             snprintf(buf, sizeof(buf), "encoder.layer%d.%d", L + 1, bi);
-            std::string p(buf);
-            if (n->se) {      // SE Bottleneck: 1x1 (stride) -> 3x3 -> 1x1 x 4 -> gate, pretrainedmodels' parameter order
-                const int C = 4 * planes[L], Cr = C / n->se;
-                blk.conv1 = n->add_conv(p + ".conv1.weight", inpl, planes[L], 1, stride, 0, (p + ".bn1").c_str(), nullptr);
-                blk.conv2 = n->add_conv(p + ".conv2.weight", planes[L], planes[L], 3, 1, 1, (p + ".bn2").c_str(), nullptr);
-                blk.conv3 = n->add_conv(p + ".conv3.weight", planes[L], C, 1, 1, 0, (p + ".bn3").c_str(), nullptr);
-                blk.p_se = n->add_param(p + ".se_module.fc1.weight", (int64_t)Cr * C);      // plain parameters, read in place
+            const std::string p(buf);
+            for (int i = 0; i < kind.nsites; ++i) {
+                const BlockSite& st = kind.site[i];
+                const std::string w = p + ".conv" + std::to_string(i + 1) + ".weight", bn = p + ".bn" + std::to_string(i + 1);
+                const int stride = st.strided ? blk.stride : 1;
+                blk.conv[i] = st.grouped && enc.groups > 1 ? n->add_grouped_conv(w, ch[st.out], ch[st.out] / enc.groups, stride, bn.c_str())
+                                                           : n->add_conv(w, ch[st.in], ch[st.out], st.k, stride, st.k / 2, bn.c_str(), nullptr);
+            }
+            if (kind.se_gate) {      // plain parameters, read in place
+                const int Cr = C / enc.se;
+                blk.p_se = n->add_param(p + ".se_module.fc1.weight", (int64_t)Cr * C);
                 n->add_param(p + ".se_module.fc1.bias", Cr);
                 n->add_param(p + ".se_module.fc2.weight", (int64_t)C * Cr);
                 n->add_param(p + ".se_module.fc2.bias", C);
-                blk.ds = -1;
-                if (stride != 1 || inpl != C)
-                    blk.ds = n->add_conv(p + ".downsample.0.weight", inpl, C, 1, stride, 0, (p + ".downsample.1").c_str(), nullptr);
-                inpl = C;
-                n->blocks[L].push_back(blk);
-                continue;
             }
-            if (e == 4) {      // Bottleneck: 1x1 -> 3x3 (stride) -> 1x1 x 4, torchvision's parameter order
-                const int C = 4 * planes[L];
-                const int mid = planes[L] * n->width / 64 * n->groups;      // ResNet: planes[L]
-                blk.conv1 = n->add_conv(p + ".conv1.weight", inpl, mid, 1, 1, 0, (p + ".bn1").c_str(), nullptr);
-                blk.conv2 = n->groups > 1 ? n->add_grouped_conv(p + ".conv2.weight", mid, mid / n->groups, stride, (p + ".bn2").c_str())
-                                          : n->add_conv(p + ".conv2.weight", mid, mid, 3, stride, 1, (p + ".bn2").c_str(), nullptr);
-                blk.conv3 = n->add_conv(p + ".conv3.weight", mid, C, 1, 1, 0, (p + ".bn3").c_str(), nullptr);
-                blk.ds = -1;
-                if (stride != 1 || inpl != C)
-                    blk.ds = n->add_conv(p + ".downsample.0.weight", inpl, C, 1, stride, 0, (p + ".downsample.1").c_str(), nullptr);
-                inpl = C;
-                n->blocks[L].push_back(blk);
-                continue;
-            }
-            blk.conv1 = n->add_conv(p + ".conv1.weight", inpl, planes[L], 3, stride, 1, (p + ".bn1").c_str(), nullptr);
-            blk.conv2 = n->add_conv(p + ".conv2.weight", planes[L], planes[L], 3, 1, 1, (p + ".bn2").c_str(), nullptr);
-            blk.ds = -1;
-            if (stride != 1 || inpl != planes[L])
-                blk.ds = n->add_conv(p + ".downsample.0.weight", inpl, planes[L], 1, stride, 0, (p + ".downsample.1").c_str(), nullptr);
-            inpl = planes[L];
-            n->blocks[L].push_back(blk);
+            if (blk.stride != 1 || inpl != C)
+                blk.ds = n->add_conv(p + ".downsample.0.weight", inpl, C, 1, blk.stride, 0, (p + ".downsample.1").c_str(), nullptr);
+            inpl = C;
+            blocks[L].push_back(blk);
         }
     const int G = classes - 1;
     const int head_ch[4] = {classes, 4 * G, 3 * G, 3 * G};
@@ -543,7 +329,7 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
         // FPC_MERGE_SPLIT=0 does not apply to such a plan
         if (dc.head_chp > 32) n->merge_split = 1;
     }
-    n->fold_ok = e == 1;
+    n->fold_ok = enc.basic();
     if (n->fold_ok)
         for (int d = 0; d < 4; ++d) {
             n->fold_wc_off[d] = n->alloc((size_t)128 * 64 * 9);
@@ -551,9 +337,9 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
             n->fold_img2_off[d] = n->alloc((size_t)16 * 128 * 256 + 2);
             n->fold_tab_off[d] = n->alloc((size_t)16 * 128);
         }
-    if (e == 1) {      // the three-product direct form's weight images, only where it is a candidate (not the p2 lateral: folded away)
+    if (enc.basic()) {      // the three-product direct form's weight images, only where it is a candidate (not the p2 lateral: folded away)
         std::vector<int> sites;
-        for (int L = 1; L < 4; ++L) { sites.push_back(n->blocks[L][0].conv1); if (n->blocks[L][0].ds >= 0) sites.push_back(n->blocks[L][0].ds); }
+        for (int L = 1; L < 4; ++L) { sites.push_back(blocks[L][0].conv[0]); if (blocks[L][0].ds >= 0) sites.push_back(blocks[L][0].ds); }
         for (int d = 0; d < 4; ++d)
             for (int i = 0; i < 3; ++i) sites.push_back(n->dec[d].lat[i]);
         for (int ci : sites) {
@@ -572,48 +358,48 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
     int h1 = conv_out(H, 7, 2, 3), w1 = conv_out(W, 7, 2, 3);
     n->a_img4 = n->alloc_act(H, W, 4);
     n->a_stem = n->alloc_act(h1, w1, 64);
-    // (the SE-ResNet stem pool has no padding and ceil_mode: h1 / 2 — the same size for the even h1 every plan has, other windows)
-    int hp = n->se ? h1 / 2 : conv_out(h1, 3, 2, 1), wp = n->se ? w1 / 2 : conv_out(w1, 3, 2, 1);
+    int hp = enc.ceil_pool() ? h1 / 2 : conv_out(h1, 3, 2, 1), wp = enc.ceil_pool() ? w1 / 2 : conv_out(w1, 3, 2, 1);
     n->a_pool = n->alloc_act(hp, wp, 64);
-    int fh[4], fw[4];
-    {
-        int h = hp, w = wp;
-        for (int L = 0; L < 4; ++L) {
-            const int hin = h, win = w;
-            if (L > 0) { h = conv_out(h, 3, 2, 1); w = conv_out(w, 3, 2, 1); }
-            fh[L] = h; fw[L] = w;
-            if (e == 4) {
-                // only a block's output feeds the next block: the stage's blocks share conv1's output (block 0's, at the stage's
-                // input resolution, is the largest), conv2's, the downsample's and two outputs in turn (a block reads its
-                // predecessor's as input and residual); the last block's is the stage's feature map
-                const int C = 4 * planes[L];
-                const int mid = planes[L] * n->width / 64 * n->groups;
-                // (SE: conv1 carries the stride, so its output is at the stage's OUTPUT resolution in every block; conv3 writes the
-                // pre-gate tensor into the block's own output, which the scale pass then rewrites in place)
-                const Act t1 = n->se ? n->alloc_act(h, w, mid) : n->alloc_act(hin, win, mid), t2 = n->alloc_act(h, w, mid);
-                const Act y[2] = {n->alloc_act(h, w, C), n->alloc_act(h, w, C)};
-                const Act dd = n->alloc_act(h, w, C);
-                for (int bi = 0; bi < n->layers[L]; ++bi) {
-                    Act t = t1;
-                    if (bi > 0) { t.H = h; t.W = w; }
-                    n->a_blk_t[L].push_back(t);
-                    n->a_blk_t2[L].push_back(t2);
-                    n->a_blk_y[L].push_back(y[bi & 1]);
-                    n->a_blk_d[L].push_back(n->blocks[L][bi].ds >= 0 ? dd : Act());
-                }
-                continue;
+    // the blocks' buffers and the encoder tape
+    Act cur = n->a_pool;
+    for (int L = 0; L < 4; ++L) {
+        Act b[kBufCount], y[2];
+        for (size_t bi = 0; bi < blocks[L].size(); ++bi) {
+            const Block& blk = blocks[L][bi];
+            // sizes by role: the input's in front of the strided site, the block's output size (h, w) from it on
+            const int h = conv_out(cur.H, 3, blk.stride, 1), w = conv_out(cur.W, 3, blk.stride, 1);
+            Act sz[kBufCount]; bool past = false;
+            for (int i = 0; i < kind.nsites; ++i) {
+                past = past || kind.site[i].strided;
+                sz[kind.site[i].out] = Act{0, past ? h : cur.H, past ? w : cur.W, blk.ch[kind.site[i].out]};
             }
-            for (int bi = 0; bi < n->layers[L]; ++bi) {
-                n->a_blk_t[L].push_back(n->alloc_act(h, w, planes[L]));
-                n->a_blk_y[L].push_back(n->alloc_act(h, w, planes[L]));
-                n->a_blk_d[L].push_back(n->blocks[L][bi].ds >= 0 ? n->alloc_act(h, w, planes[L]) : Act());
+            // storage, in this order: T1, T2, the output(s), D.  A shared stage allocates once, at block 0, whose T1 is the largest
+            // (a Bottleneck's conv1 there runs at the stage's INPUT resolution), and D whether or not a later block needs it
+            if (!kind.shared || bi == 0) {
+                auto alloc_like = [&](const Act& t) { return n->alloc_act(t.H, t.W, t.C); };
+                b[kBufT1] = alloc_like(sz[kBufT1]); if (kind.nsites == 3) b[kBufT2] = alloc_like(sz[kBufT2]);
+                y[0] = alloc_like(sz[kBufY]); if (kind.shared) y[1] = alloc_like(sz[kBufY]);
+                if (kind.shared || blk.ds >= 0) b[kBufD] = alloc_like(sz[kBufY]);
             }
+            b[kBufT1].H = sz[kBufT1].H; b[kBufT1].W = sz[kBufT1].W;      // (a later block's view of a shared T1)
+            b[kBufIn] = cur; b[kBufY] = y[kind.shared ? bi & 1 : 0]; b[kBufRes] = blk.ds >= 0 ? b[kBufD] : cur;
+            // steps, in launch order
+            for (int i = 0; i < kind.nsites; ++i) {
+                const BlockSite& st = kind.site[i];
+                if (i == kind.ds_before && blk.ds >= 0) n->tape.push_back({blk.ds, cur, b[kBufD], false, Act(), -1});
+                n->tape.push_back({blk.conv[i], b[st.in], b[st.out], st.relu, b[st.res], -1});
+            }
+            if (kind.se_gate) n->tape.push_back({-1, b[kBufY], b[kBufY], true, b[kBufRes], blk.p_se});
+            cur = b[kBufY];
         }
+        n->a_feat[L] = cur;
     }
-    if (n->se) {      // the gate of one block at a time: [B][C] and the slab partials of the stage with the most
+    int fh[4], fw[4];
+    for (int L = 0; L < 4; ++L) { fh[L] = n->a_feat[L].H; fw[L] = n->a_feat[L].W; }
+    if (kind.se_gate) {      // the gate of one block at a time: [B][C] and the slab partials of the stage with the most
         size_t part = 0;
-        for (int L = 0; L < 4; ++L) part = std::max(part, (size_t)se_pool_slabs(fh[L], fw[L], 4 * planes[L]) * 4 * planes[L]);
-        n->se_gate_off = n->alloc((size_t)B * 4 * planes[3]);
+        for (int L = 0; L < 4; ++L) part = std::max(part, (size_t)se_pool_slabs(fh[L], fw[L], n->a_feat[L].C) * n->a_feat[L].C);
+        n->se_gate_off = n->alloc((size_t)B * n->a_feat[3].C);
         n->se_part_off = n->alloc((size_t)B * part);
     }
     // FPN needs exact x2 relations between levels
@@ -641,8 +427,6 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
     n->c_groups.assign(n->convs.size(), 0);
     n->c_tr.assign(n->convs.size(), 0);
     auto oriented = [&](int ci, int h, int w) { if (ci >= 0 && n->convs[ci].wino_ok) n->c_tr[ci] = wino_orient_rule(h, w) ? 1 : 0; };
-    for (int L = 0; L < 4; ++L)
-        for (const fpc_net::Block& blk : n->blocks[L]) { oriented(blk.conv1, fh[L], fw[L]); oriented(blk.conv2, fh[L], fw[L]); }
     auto plan = [&](int ci, int HoWo, int groups) {
         const PackedConv& c = n->convs[ci];
         n->c_howo[ci] = HoWo; n->c_groups[ci] = groups;
@@ -656,14 +440,10 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
         if (need > n->splitk_floats) n->splitk_floats = need;
     };
     plan(n->c_stem, h1 * w1, 1);
-    for (int L = 0; L < 4; ++L)
-        for (size_t bi = 0; bi < n->blocks[L].size(); ++bi) {
-            const fpc_net::Block& blk = n->blocks[L][bi];
-            plan(blk.conv1, n->a_blk_t[L][bi].H * n->a_blk_t[L][bi].W, 1);      // (a Bottleneck's first conv1 of a stage: the stage's input resolution)
-            plan(blk.conv2, fh[L] * fw[L], 1);
-            if (blk.conv3 >= 0) plan(blk.conv3, fh[L] * fw[L], 1);
-            if (blk.ds >= 0) plan(blk.ds, fh[L] * fw[L], 1);
-        }
+    // (the orientation rule is asked with the step's own output size.  A Winograd site has stride 1 (PackedConv::wino_ok), so that is
+    // the stage's output size at every site the mark matters for: a strided conv1, whose input is larger, is never one)
+    for (const fpc_net::Step& st : n->tape)
+        if (st.conv >= 0) { plan(st.conv, st.out.H * st.out.W, 1); oriented(st.conv, st.out.H, st.out.W); }
     for (int i = 0; i < 4; ++i) plan(n->dec[0].lat[i], fh[3 - i] * fw[3 - i], 4);
     for (int i = 0; i < 7; ++i) {
         int HoWo = fh[seg_level[i]] * fw[seg_level[i]];
@@ -693,12 +473,6 @@ extern "C" void fpc_net_destroy(fpc_net_t* n) {
     delete n;
 }
 
-// 1: after autotuning, the ~57 launches of a frame that only touch the plan's workspace are captured once and
-// replayed with one hipGraphLaunch per frame (the first and the last kernel take the caller's tensors and stay
-// ordinary launches).  Changing the tilings (fpc_net_autotune_next) or the parameters drops the recorded graph.
-// 1: the next autotuning pass also times the split-precision (bf16 x 3, f32 accumulation) form of every direct
-// fast-path convolution and keeps it where it is faster.  Opt-in: the results then differ from the f32 product chain
-// by rounding (about 2^-24 relative per product, like a different f32 summation order), not bit for bit.
 // The three-product direct form's weight images (PackedConv::h3_ok): their room is reserved when the plan is built (the workspace
 // size is fixed before the split level is known), but they are packed only at level 3 — by fpc_net_load_params, or by raising the
 // level on a loaded plan (on the stream of the last load).
@@ -715,6 +489,9 @@ static int pack_h3_images(fpc_net* n, hipStream_t s) {
     return FPC_OK;
 }
 
+// 1: the next autotuning pass also times the split-precision (bf16 x 3, f32 accumulation) form of every direct
+// fast-path convolution and keeps it where it is faster.  Opt-in: the results then differ from the f32 product chain
+// by rounding (about 2^-24 relative per product, like a different f32 summation order), not bit for bit.
 extern "C" int fpc_net_set_split_precision(fpc_net_t* n, int on) {
     if (!n) return FPC_EINVAL;
     n->split_precision = on < 0 ? 0 : (on > 3 ? 3 : on);      // 0: f32 products only, 1: + bf16 x 3 forms, 2: + the fp16 x 2 Winograd form, 3: + its three-product form
@@ -772,6 +549,9 @@ extern "C" int fpc_net_set_wino_orient(fpc_net_t* n, int on) {
 // workgroups of all form-9 launches of the last forward that launched (or captured) its kernels; -1 without a plan
 extern "C" int64_t fpc_net_wino_blocks(const fpc_net_t* n) { return n ? (int64_t)n->wino_blocks : -1; }
 
+// 1: after autotuning, the ~57 launches of a frame that only touch the plan's workspace are captured once and
+// replayed with one hipGraphLaunch per frame (the first and the last kernel take the caller's tensors and stay
+// ordinary launches).  Changing the tilings (fpc_net_autotune_next) or the parameters drops the recorded graph.
 extern "C" int fpc_net_set_graph(fpc_net_t* n, int on) {
     if (!n) return FPC_EINVAL;
     n->use_graph = on ? 1 : 0;
@@ -848,143 +628,14 @@ struct ConvIO {
     const float* res; const float* up; float* gn_part;
 };
 
-// fills the shared part of ConvArgs from conv `c` + plan `p`
+// fills the shared part of ConvArgs from conv `c` + plan `p` and the plan's workspace
 void fill_conv_args(const fpc_net* n, ConvArgs& a, const PackedConv& c, const ConvPlan& p, int Hi, int Wi, int Ho,
                     int Wo, long long sb, long long sh, long long sw, long long sc, bool relu, int mode) {
-    memset(&a, 0, sizeof(a));
-    a.B = n->B; a.Hi = Hi; a.Wi = Wi; a.Cin = c.Cin; a.Ho = Ho; a.Wo = Wo; a.Cout = c.Cout; a.Npad = c.Npad;
-    a.Kh = c.Kh; a.Kw = c.Kw; a.stride = c.stride; a.pad = c.pad; a.K = c.K; a.Kpad = c.Kpad;
-    a.in_sb = sb; a.in_sh = sh; a.in_sw = sw; a.in_sc = sc;
-    a.relu = relu ? 1 : 0; a.nsplit = p.nsplit; a.mtiles = p.mtiles; a.ntiles = p.ntiles; a.ksteps = c.Kpad / kConvBK;
-    a.bm = p.bm; a.bn = p.bn; a.generic = mode;
-    a.splitk_ws = n->ws + n->splitk_off;
-    a.zeros = n->ws + n->zeros_off;
-    a.tickets = (int*)(n->ws + n->tickets_off);
-    a.fused = p.fused;
-    a.wino_pack = n->wino_pack;
-    a.wino_orient = n->wino_orient;
+    fill_conv_shape(a, n->B, c, p, Hi, Wi, Ho, Wo, sb, sh, sw, sc, relu, mode);
+    a.splitk_ws = n->ws + n->splitk_off; a.zeros = n->ws + n->zeros_off; a.tickets = (int*)(n->ws + n->tickets_off);
+    a.wino_pack = n->wino_pack; a.wino_orient = n->wino_orient;
 }
 
-int launch_conv_plan(ConvArgs& a, const ConvPlan& p, int groups, hipStream_t s) {
-    if (p.grp || a.cg) {      // a grouped site runs on k_conv3x3_grouped and on nothing else
-        if (!p.grp || p.grp > kGroupedForms || !a.cg || !a.grp_w || groups != 1 || a.in_sc != 1 || a.Kh != 3 || a.pad != 1 ||
-            a.Cin != a.Cout || a.p[0].res || a.p[0].up || a.p[0].gn_part)
-            return FPC_EINVAL;
-        GroupedArgs g;
-        memset(&g, 0, sizeof(g));
-        g.in = a.p[0].in; g.w = a.grp_w; g.out = a.p[0].out; g.scale = a.p[0].scale; g.shift = a.p[0].shift;
-        g.in_sb = a.in_sb; g.in_sh = a.in_sh; g.in_sw = a.in_sw;
-        g.B = a.B; g.Hi = a.Hi; g.Wi = a.Wi; g.Ho = a.Ho; g.Wo = a.Wo; g.C = a.Cout; g.CG = a.cg; g.stride = a.stride; g.relu = a.relu;
-        g.form = p.grp - 1;
-        return launch_conv3x3_grouped(g, s);
-    }
-    if (p.stem) {
-        if (groups != 1 || !stem_ok(a)) return FPC_EINVAL;
-        StemArgs t;
-        memset(&t, 0, sizeof(t));
-        t.in = a.p[0].in;
-        t.wpl = reinterpret_cast<const unsigned short*>(a.p[0].w + (size_t)a.Npad * a.Kpad);      // the bf16 planes behind the f32 image
-        t.out = a.p[0].out; t.scale = a.p[0].scale; t.shift = a.p[0].shift;
-        t.B = a.B; t.Hi = a.Hi; t.Wi = a.Wi; t.Ho = a.Ho; t.Wo = a.Wo; t.Cout = a.Cout; t.Npad = a.Npad; t.Kpad = a.Kpad; t.relu = a.relu;
-        t.grid = p.stem;
-        return launch_stem7x7(t, s);
-    }
-    if (p.pw) {
-        if (!pw_ok(a, groups)) return FPC_EINVAL;
-        PwArgs w;
-        memset(&w, 0, sizeof(w));
-        w.in = a.p[0].in;
-        for (int g = 0; g < groups; ++g) {
-            // the three bf16 planes sit behind the f32 image (k_pack_weight_bf3)
-            w.wpl[g] = reinterpret_cast<const unsigned short*>(a.p[g].w + (size_t)a.Npad * a.Kpad);
-            w.out[g] = a.p[g].out; w.scale[g] = a.p[g].scale; w.shift[g] = a.p[g].shift; w.res[g] = a.p[g].res; w.up[g] = a.p[g].up;
-        }
-        w.in_sb = a.in_sb; w.in_sh = a.in_sh; w.in_sw = a.in_sw;
-        w.B = a.B; w.Ho = a.Ho; w.Wo = a.Wo; w.Cin = a.Cin; w.Cout = a.Cout; w.Npad = a.Npad; w.Kpad = a.Kpad; w.stride = a.stride;
-        w.groups = groups; w.relu = a.relu;
-        w.has_scale = a.p[0].scale != nullptr; w.has_shift = a.p[0].shift != nullptr;
-        w.has_res = a.p[0].res != nullptr; w.has_up = a.p[0].up != nullptr;
-        w.variant = p.pw - 1;
-        return launch_conv1x1(w, s);
-    }
-    if (p.lat) {
-        if (!lateral_ok(a, groups)) return FPC_EINVAL;
-        LatArgs l;
-        memset(&l, 0, sizeof(l));
-        l.in = a.p[0].in;
-        for (int g = 0; g < groups; ++g) {
-            // the three bf16 planes sit behind the f32 image (k_pack_weight_bf3); h3: the site's k_pack_weight_h3 image
-            if (p.h3 && !a.h3_w[g]) return FPC_EINVAL;
-            l.wpl[g] = reinterpret_cast<const unsigned short*>(p.h3 ? a.h3_w[g] : a.p[g].w + (size_t)a.Npad * a.Kpad);
-            l.out[g] = a.p[g].out; l.shift[g] = a.p[g].shift; l.up[g] = a.p[g].up;
-        }
-        l.B = a.B; l.Ho = a.Ho; l.Wo = a.Wo; l.Cout = a.Cout; l.Npad = a.Npad; l.Kpad = a.Kpad; l.groups = groups; l.relu = a.relu;
-        l.parts = p.lat;
-        l.h3 = p.h3;
-        return launch_lateral1x1(l, s);
-    }
-    if (p.wino) {
-        if (!wino_form_ok(p.wino, a.Cin, a.Cout)) return FPC_EINVAL;
-        const WinoForm& f = kWinoForms[p.wino];
-        WinoArgs w;
-        memset(&w, 0, sizeof(w));
-        for (int g = 0; g < groups; ++g) {
-            if (!a.wino_w[g] || a.p[g].up) return FPC_EINVAL;
-            w.p[g] = a.p[g];
-            w.p[g].w = a.wino_w[g] + wino_image_offset(f.image, a.Cout, a.Cin);
-        }
-        w.variant = f.variant;
-        w.zeros = a.zeros;
-        w.dbg = (long long*)a.dbg;
-        w.groups = groups;
-        w.B = a.B; w.H = a.Ho; w.W = a.Wo; w.Cin = a.Cin; w.Cout = a.Cout; w.relu = a.relu;
-        w.waves = f.waves;
-        const WinoGrid wg = wino_grid(p.wino, a.Ho, a.Wo);
-        w.tbx = wg.tbx; w.tby = wg.tby;
-        if (p.wino == kWinoH3) {      // packing and orientation: the same workgroups, fewer of them — properties of the launch, not of the plan
-            bool tr;
-            const WinoPackGeom q = wino_launch_geometry(a.Ho, a.Wo, a.B, a.Cin, a.wino_orient, a.wino_pack && !p.fold, &tr);
-            if (q.G > 1 || tr) { w.pack = q.G; w.tbx = q.tbx; w.tby = q.tby; w.pack_rx = q.rx; }
-            w.orient = tr ? 1 : 0;
-            a.wino_blocks = q.patches * (a.Cout / 64) * groups;
-        }
-        if (p.fold) {      // c2 on Wc's image + up2(p3) on W's (the p2 input of .p[g] is not read)
-            if (p.wino != kWinoH3 || !a.fold_in) return FPC_EINVAL;
-            for (int g = 0; g < groups; ++g) {
-                w.in2[g] = a.fold_up[g]; w.w2[g] = a.fold_w2[g];
-                w.btab[g] = a.fold_tab[g];
-                w.p[g].in = a.fold_in; w.p[g].w = a.fold_w[g];
-            }
-            w.fold = 1; w.Cin2 = a.Cin; w.Cin = a.fold_cin;
-        }
-        return f.launch(w, groups, s);
-    }
-    a.bm = p.bm; a.bn = p.bn; a.nsplit = p.nsplit; a.mtiles = p.mtiles; a.ntiles = p.ntiles; a.groups = groups;
-    a.bf3 = (p.bf3 && a.generic == 0) ? 1 : 0;
-    a.fused = (p.fused && p.nsplit > 1) ? 1 : 0;
-    a.h3 = 0;
-    ConvArgs h;
-    if (p.h3) {      // the same launch on the site's k_pack_weight_h3 images (a is left as it was: the tuner reuses it)
-        if (a.generic != 0) return FPC_EINVAL;
-        h = a;
-        h.bf3 = 0; h.h3 = 1;
-        for (int g = 0; g < groups; ++g) {
-            if (!a.h3_w[g]) return FPC_EINVAL;
-            h.p[g].w = a.h3_w[g];
-        }
-    }
-    const ConvArgs& l = p.h3 ? h : a;
-    int rc = launch_conv(l, groups, s);
-    if (!rc && l.nsplit > 1 && !l.fused) rc = launch_conv_splitk_epilogue(l, groups, s);
-    return rc;
-}
-
-// number of GroupNorm partial rows per image a plan writes
-int plan_gn_rows(const ConvPlan& p, int Ho, int Wo, int B, int Cin, int pack, int orient) {
-    bool tr;
-    if (p.wino == kWinoH3) return wino_launch_geometry(Ho, Wo, B, Cin, orient, pack && !p.fold, &tr).gn_rows;
-    return p.wino ? wino_grid(p.wino, Ho, Wo).patches() : p.mtiles * p.bm / 32;
-}
 
 // Minimum elapsed time (ms) of `reps` runs of `run` (-> FPC_OK) on stream `s`, synchronising after each; 1e30 if it could not be
 // timed: such a candidate is never chosen.  The autotuner's clock; its events are gone on return.
@@ -1004,8 +655,8 @@ template <class F> float min_ms(hipStream_t s, int reps, F run) {
 }
 
 // The plans the autotuner times for the site `a` describes, in the order it times them (the first of equal scores is kept):
-// `split` = the plan's split-precision level, `expansion` = its encoder's block kind.
-std::vector<ConvPlan> tune_candidates(const ConvArgs& a, int groups, int split, int expansion) {
+// `split` = the plan's split-precision level, `pointwise` = its encoder offers k_conv1x1 (EncoderDesc::pointwise).
+std::vector<ConvPlan> tune_candidates(const ConvArgs& a, int groups, int split, bool pointwise) {
     if (a.cg) {      // a grouped site: the forms of k_conv3x3_grouped that are built
         std::vector<ConvPlan> gc;
         for (int f = 0; f < kGroupedForms; ++f) { ConvPlan q; q.grp = f + 1; gc.push_back(q); }
@@ -1030,7 +681,7 @@ std::vector<ConvPlan> tune_candidates(const ConvArgs& a, int groups, int split, 
                 if (split >= 3 && a.h3_w[0]) { lq.h3 = 1; cands.push_back(lq); }      // ... on two fp16 pieces
             }
     }
-    if (split && expansion == 4 && pw_ok(a, groups)) {      // the 1x1 GEMM (bf16 x 3 planes), Bottleneck plans only
+    if (split && pointwise && pw_ok(a, groups)) {      // the 1x1 GEMM (bf16 x 3 planes), Bottleneck plans only
         ConvPlan pq;
         pq.pw = 1; cands.push_back(pq);
         pq.pw = 2; cands.push_back(pq);
@@ -1092,11 +743,11 @@ int survey_site(const fpc_net* n, const ConvArgs& a, const ConvPlan& p, int grou
 // Runs conv site `ci` with its current plan; in tuning mode first times every candidate (HIP events on the stream,
 // synchronising — only ever inside fpc_net_autotune): candidates, time each, keep the best, the fold challenger, launch.
 int run_conv(fpc_net* n, ConvArgs& a, int groups, int ci, hipStream_t s) {
-    if (n && n->tuning) {
+    if (n->tuning) {
         float best_ms = 1e30f, free_ms = 1e30f;
         ConvPlan best = n->cplan[ci];
         n->has_free[ci] = 0;
-        for (const ConvPlan& q : tune_candidates(a, groups, n->split_precision, n->expansion)) {
+        for (const ConvPlan& q : tune_candidates(a, groups, n->split_precision, n->enc.pointwise())) {
             if (splitk_floats_for(q, groups, a.B, a.Npad) > n->splitk_floats) continue;
             if (n->guarded[ci] && plan_range_limited(q)) continue;      // a demoted site stays range-free
             int rc = launch_conv_plan(a, q, groups, s);     // warm-up (also validates the launch)
@@ -1126,29 +777,15 @@ int run_conv(fpc_net* n, ConvArgs& a, int groups, int ci, hipStream_t s) {
         }
         n->cplan[ci] = best;
     }
-    ConvPlan p = n ? n->cplan[ci] : ConvPlan{a.bm, a.bn, a.nsplit, a.mtiles, a.ntiles, 0, a.bf3, a.fused};
-    if (n && n->survey) { const int rs = survey_site(n, a, p, groups, ci, s); if (rs) return rs; }
+    const ConvPlan p = n->cplan[ci];
+    if (n->survey) { const int rs = survey_site(n, a, p, groups, ci, s); if (rs) return rs; }
     const int rc = launch_conv_plan(a, p, groups, s);
-    if (n && !rc && p.wino == kWinoH3) n->wino_blocks += a.wino_blocks;
+    if (!rc && p.wino == kWinoH3) n->wino_blocks += a.wino_blocks;
     return rc;
 }
 
 }  // namespace
 
-#define FPC_TRY(x) do { int rc__ = (x); if (rc__) return rc__; } while (0)
-
-// the stem site's fused launch: image -> pooled tensor (k_stem_pool_h3).  `a` as the stem site fills it; FPC_EINVAL where the shape
-// is not eligible (launch_stem_pool_h3) or the h3 image is not there
-static int launch_stem_pool(const ConvArgs& a, const float* h3_image, float* pool, int Hp, int Wp, hipStream_t s) {
-    if (!h3_image || !stem_ok(a)) return FPC_EINVAL;
-    StemPoolArgs t;
-    memset(&t, 0, sizeof(t));
-    t.in = a.p[0].in; t.wpl = reinterpret_cast<const unsigned short*>(h3_image); t.out = pool;
-    t.scale = a.p[0].scale; t.shift = a.p[0].shift;
-    t.B = a.B; t.Hi = a.Hi; t.Wi = a.Wi; t.Ho = a.Ho; t.Wo = a.Wo; t.Hp = Hp; t.Wp = Wp; t.Npad = a.Npad; t.Kpad = a.Kpad; t.relu = a.relu;
-    t.band = kStemPoolBand; t.grid = 256;
-    return launch_stem_pool_h3(t, s);
-}
 
 // Everything between the NCHW -> NHWC4 conversion of the caller's image and the final upsample / class
 // compression into the caller's tensors: ~57 launches that touch only the plan's workspace and parameters, i.e.
@@ -1172,14 +809,12 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
         a.Cin = 8 * c.Cinp; a.Kw = 1; a.K = c.K; a.lanepx = 1;
         a.p[0] = ConvPtrs{ws + n->a_img4.off, ws + c.w_off, ws + n->a_stem.off, ws + c.scale_off, ws + c.shift_off, nullptr, nullptr, nullptr};
         const float* h3img = n->h3_packed ? ws + n->stem_h3_off : nullptr;
+        const bool ceil = n->enc.ceil_pool();      // the SE-ResNet stem: its pool has no padding (k_stem_pool_h3 is a pad-1 kernel: neither tuned nor forced there)
         auto pool_launch = [&]() {
-            return launch_maxpool3x3s2(ws + n->a_stem.off, ws + n->a_pool.off, B, n->a_stem.H, n->a_stem.W, 64, n->a_pool.H, n->a_pool.W, s);
+            return ceil ? launch_maxpool3x3s2_ceil(ws + n->a_stem.off, ws + n->a_pool.off, B, n->a_stem.H, n->a_stem.W, 64, s)
+                        : launch_maxpool3x3s2(ws + n->a_stem.off, ws + n->a_pool.off, B, n->a_stem.H, n->a_stem.W, 64, n->a_pool.H, n->a_pool.W, s);
         };
-        if (n->se) {      // the SE-ResNet stem: its pool has no padding (k_stem_pool_h3 is a pad-1 kernel: neither tuned nor forced here)
-            n->cplan[n->c_stem].pool = 0;
-            FPC_TRY(run_conv(n, a, 1, n->c_stem, s));
-            FPC_TRY(launch_maxpool3x3s2_ceil(ws + n->a_stem.off, ws + n->a_pool.off, B, n->a_stem.H, n->a_stem.W, 64, s));
-        } else if (n->cplan[n->c_stem].pool && !n->tuning) {      // one launch to the pooled tensor: a_stem is not written
+        if (n->cplan[n->c_stem].pool && !n->tuning && !ceil) {      // one launch to the pooled tensor: a_stem is not written
             if (n->survey) FPC_TRY(survey_site(n, a, n->cplan[n->c_stem], 1, n->c_stem, s));      // (not through run_conv: the image)
             FPC_TRY(launch_stem_pool(a, h3img, ws + n->a_pool.off, n->a_pool.H, n->a_pool.W, s));
         } else {
@@ -1188,7 +823,7 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
             FPC_TRY(pool_launch());
             // level 3: the fused launch against the site's best plan AND the max-pool together (it replaces both), timed as the p2
             // fold is; the whole chip: score = ms.  Kept only when it beats them
-            if (n->tuning && n->split_precision >= 3 && !n->guarded[n->c_stem] && launch_stem_pool(a, h3img, ws + n->a_pool.off, n->a_pool.H, n->a_pool.W, s) == FPC_OK) {
+            if (n->tuning && !ceil && n->split_precision >= 3 && !n->guarded[n->c_stem] && launch_stem_pool(a, h3img, ws + n->a_pool.off, n->a_pool.H, n->a_pool.W, s) == FPC_OK) {
                 const ConvPlan cur = n->cplan[n->c_stem];
                 float ms_pair = 1e30f, ms_fused = 1e30f;
                 for (int rep = 0; rep < 3; ++rep) {      // six runs, the two sides in turn
@@ -1212,56 +847,17 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
         if (c.cg) { a.cg = c.cg; a.grp_w = ws + c.grp_off; }
         return run_conv(n, a, 1, ci, s);
     };
-    Act cur = n->a_pool;
-    Act feat[4];
-    for (int L = 0; L < 4; ++L) {
-        for (size_t bi = 0; bi < n->blocks[L].size(); ++bi) {
-            const fpc_net::Block& blk = n->blocks[L][bi];
-            const Act& T = n->a_blk_t[L][bi];
-            const Act& Y = n->a_blk_y[L][bi];
-            const float* res = ws + cur.off;
-            if (n->se) {
-                // SE Bottleneck: conv1 (1x1 with the stride, BN + ReLU) -> conv2 (3x3, BN + ReLU), the downsample (1x1, stride, BN),
-                // conv3 (1x1, BN only) into Y, the gate from Y's channel means, then Y = relu(Y * gate + residual) in place
-                const Act& T2 = n->a_blk_t2[L][bi];
-                FPC_TRY(enc_conv(blk.conv1, cur, T, true, nullptr));
-                FPC_TRY(enc_conv(blk.conv2, T, T2, true, nullptr));
-                if (blk.ds >= 0) {
-                    FPC_TRY(enc_conv(blk.ds, cur, n->a_blk_d[L][bi], false, nullptr));
-                    res = ws + n->a_blk_d[L][bi].off;
-                }
-                FPC_TRY(enc_conv(blk.conv3, T2, Y, false, nullptr));
-                FPC_TRY(launch_se_pool(ws + Y.off, ws + n->se_part_off, B, Y.H, Y.W, Y.C, s));
-                FPC_TRY(launch_se_excite(ws + n->se_part_off, n->pptr[blk.p_se], n->pptr[blk.p_se + 1], n->pptr[blk.p_se + 2],
-                                         n->pptr[blk.p_se + 3], ws + n->se_gate_off, B, Y.H, Y.W, Y.C, n->se, s));
-                FPC_TRY(launch_se_scale_add_relu(ws + Y.off, ws + n->se_gate_off, res, ws + Y.off, B, Y.H, Y.W, Y.C, s));
-                cur = Y;
-                continue;
-            }
-            if (n->expansion == 4) {
-                // Bottleneck: conv1 (1x1, BN + ReLU) -> conv2 (3x3 with the stride, BN + ReLU), the downsample (1x1, stride, BN),
-                // conv3 (1x1, BN + residual + ReLU)
-                const Act& T2 = n->a_blk_t2[L][bi];
-                FPC_TRY(enc_conv(blk.conv1, cur, T, true, nullptr));
-                FPC_TRY(enc_conv(blk.conv2, T, T2, true, nullptr));
-                if (blk.ds >= 0) {
-                    FPC_TRY(enc_conv(blk.ds, cur, n->a_blk_d[L][bi], false, nullptr));
-                    res = ws + n->a_blk_d[L][bi].off;
-                }
-                FPC_TRY(enc_conv(blk.conv3, T2, Y, true, res));
-                cur = Y;
-                continue;
-            }
-            FPC_TRY(enc_conv(blk.conv1, cur, T, true, nullptr));
-            if (blk.ds >= 0) {
-                FPC_TRY(enc_conv(blk.ds, cur, n->a_blk_d[L][bi], false, nullptr));
-                res = ws + n->a_blk_d[L][bi].off;
-            }
-            FPC_TRY(enc_conv(blk.conv2, T, Y, true, res));
-            cur = Y;
-        }
-        feat[L] = cur;
+    for (const fpc_net::Step& st : n->tape) {
+        const float* res = st.res.C ? ws + st.res.off : nullptr;
+        if (st.conv >= 0) { FPC_TRY(enc_conv(st.conv, st.in, st.out, st.relu, res)); continue; }
+        // the gate of an SE block: from Y's channel means, then Y = relu(Y * gate + residual) in place
+        const Act& Y = st.out;
+        FPC_TRY(launch_se_pool(ws + Y.off, ws + n->se_part_off, B, Y.H, Y.W, Y.C, s));
+        FPC_TRY(launch_se_excite(ws + n->se_part_off, n->pptr[st.p_se], n->pptr[st.p_se + 1], n->pptr[st.p_se + 2], n->pptr[st.p_se + 3],
+                                 ws + n->se_gate_off, B, Y.H, Y.W, Y.C, n->enc.se, s));
+        FPC_TRY(launch_se_scale_add_relu(ws + Y.off, ws + n->se_gate_off, res, ws + Y.off, B, Y.H, Y.W, Y.C, s));
     }
+    const Act* feat = n->a_feat;
 
     // ---- four decoders, grouped
     // laterals: p5 = conv(c5); p4 = up2_nearest(p5) + conv(c4); p3; p2 (not where s2.0 folds it in, outside an autotuning pass)
@@ -1656,7 +1252,7 @@ extern "C" int fpc_net_force_direct_h3(fpc_net_t* n, int on) {
 // when the plan changed, 0 when it was already so, or a negative code.  Drops the recorded graph.
 extern "C" int fpc_net_force_stem_pool(fpc_net_t* n, int on) {
     if (!n || on < 0 || on > 1 || (on && !n->h3_packed)) return FPC_EINVAL;
-    if (on && n->se) return FPC_EINVAL;      // the SE-ResNet stem pool has no padding: the fused launch computes another pool
+    if (on && n->enc.ceil_pool()) return FPC_EINVAL;      // the SE-ResNet stem pool has no padding: the fused launch computes another pool
     if (on && ((n->a_stem.H & 1) || (n->a_stem.W & 63) || (long long)n->H * n->W * 16 >= (1LL << 31))) return FPC_EINVAL;
     ConvPlan& p = n->cplan[n->c_stem];
     if (p.pool == on) return 0;
@@ -1733,7 +1329,7 @@ extern "C" int fpc_net_tensor(const fpc_net_t* n, const char* name, const float*
         t = n->a_stem; ok = true;
     }
     else if (!strcmp(name, "pool")) { t = n->a_pool; ok = true; }
-    else if (name[0] == 'c' && name[1] >= '2' && name[1] <= '5' && !name[2]) { t = n->a_blk_y[name[1] - '2'].back(); ok = true; }
+    else if (name[0] == 'c' && name[1] >= '2' && name[1] <= '5' && !name[2]) { t = n->a_feat[name[1] - '2']; ok = true; }
     else if (name[0] == 'd' && name[1] >= '0' && name[1] <= '3' && name[2] == '.') {
         int d = name[1] - '0';
         const char* r = name + 3;
@@ -1749,236 +1345,3 @@ extern "C" int fpc_net_tensor(const fpc_net_t* n, const char* name, const float*
     return FPC_OK;
 }
 
-// k_stem_pool_h3's wave tasks for a conv output of Ho x Wo (host arithmetic, no device): out4 = bands, strips per frame, conv outputs
-// computed per frame (band overlap rows and halo tiles included), conv outputs that exist.  FPC_EINVAL for a shape the launcher refuses.
-extern "C" int fpc_stem_pool_tasks(int Ho, int Wo, int64_t* out4) {
-    if (!out4 || Ho < 2 || (Ho & 1) || Wo < 64 || (Wo & 63)) return FPC_EINVAL;
-    long long o[4];
-    stem_pool_tasks(Ho, Wo, kStemPoolBand, o);
-    for (int i = 0; i < 4; ++i) out4[i] = o[i];
-    return FPC_OK;
-}
-
-// k_conv_wino_h3's launch geometry for a 3x3 / stride-1 site with output H x W, batch B and Cin input channels (host arithmetic, no
-// device; fold = 1: the folded s2.0, which never packs): out8 = frames per canvas row G (1: plain), patches per full canvas row,
-// patch rows, launched patches per (64-channel block, decoder), their tile slots, tiles that exist, GroupNorm records per frame,
-// GroupNorm records per frame and patch row.
-extern "C" int fpc_wino_pack_geometry(int H, int W, int B, int Cin, int fold, int64_t* out8) {
-    if (!out8 || H < 1 || W < 1 || B < 1 || Cin < 1) return FPC_EINVAL;
-    const WinoPackGeom q = wino_pack_geometry(H, W, B, Cin, !fold);
-    out8[0] = q.G; out8[1] = q.tbx; out8[2] = q.tby; out8[3] = q.patches; out8[4] = q.slots; out8[5] = q.tiles; out8[6] = q.gn_rows;
-    out8[7] = q.rx;
-    return FPC_OK;
-}
-
-// The same for a site under the orientation rule (wino_orient_rule / wino_launch_geometry; host arithmetic): out9[0] = 1 where the
-// launch runs transposed — then out9[1..8] is fpc_wino_pack_geometry's out8 of the virtual image W x H, packed whatever `pack` says
-// and with or without the fold — else 0 and out9[1..8] = the plain site's geometry with packing as `pack` (0 / 1) allows.
-extern "C" int fpc_wino_orient_geometry(int H, int W, int B, int Cin, int fold, int pack, int64_t* out9) {
-    if (!out9 || H < 1 || W < 1 || B < 1 || Cin < 1) return FPC_EINVAL;
-    bool tr;
-    const WinoPackGeom q = wino_launch_geometry(H, W, B, Cin, true, pack && !fold, &tr);
-    out9[0] = tr ? 1 : 0;
-    out9[1] = q.G; out9[2] = q.tbx; out9[3] = q.tby; out9[4] = q.patches; out9[5] = q.slots; out9[6] = q.tiles; out9[7] = q.gn_rows;
-    out9[8] = q.rx;
-    return FPC_OK;
-}
-
-// The reciprocals of the four-wave Winograd kernels' workgroup-id decode (wino_recip, wino_decode: host arithmetic), as the
-// launchers compute them.
-extern "C" int fpc_wino_recip(uint32_t d, int64_t* out2) {
-    if (!out2 || d < 1 || d > (1u << 31)) return FPC_EINVAL;
-    const WinoRecip r = wino_recip(d);
-    out2[0] = r.m; out2[1] = r.sh;
-    return FPC_OK;
-}
-extern "C" int fpc_wino_decode(int Cout, int groups, int tbx, int tby, int W, int B, int pack, int64_t* out14) {
-    if (!out14 || Cout < 64 || groups < 1 || tbx < 1 || tby < 1 || W < 1 || B < 1 || pack < 0) return FPC_EINVAL;
-    const WinoDecode d = wino_decode(Cout, groups, tbx, tby, W, B, pack);
-    const WinoRecip r[7] = {d.nnb, d.groups, d.tbx, d.tby, d.per, d.tbxl, d.tcw};
-    for (int i = 0; i < 7; ++i) { out14[2 * i] = r[i].m; out14[2 * i + 1] = r[i].sh; }
-    return FPC_OK;
-}
-
-// ---- stand-alone convolution (unit tests / micro-benchmarks of k_conv_igemm) -----------------
-extern "C" size_t fpc_conv2d_workspace_bytes(int B, int Ho, int Wo, int Cin, int Cout, int Kh, int Kw) {
-    int K = Cin * Kh * Kw, Kpad = cdiv(K, kConvBK) * kConvBK, Npad = cdiv(Cout, kConvNAlign) * kConvNAlign;
-    size_t packed = conv_packed_floats(Npad, Kpad);
-    size_t splitk = (size_t)32 * B * (cdiv(Ho * Wo, 128) * 128) * Npad;
-    size_t wino = wino_region_floats(kImgH3, Cout, Cin, true);      // every Winograd image + a zero page for the all-DMA form
-    return (packed + splitk + wino + kConvTickets) * sizeof(float);
-}
-
-namespace {
-// workspace of ONE fpc_conv2d call (floats): [packed weights | split-K partials of this plan | Winograd images + zero page |
-// arrival counters]; regions a plan does not use are empty
-struct Conv2dLayout { size_t packed, splitk, wino, tickets, total; };
-Conv2dLayout conv2d_layout(int B, int Cin, int Cout, int Kh, int Kw, const ConvPlan& p, const Conv2dRequest& r) {
-    const int K = Cin * Kh * Kw, Kpad = cdiv(K, kConvBK) * kConvBK, Npad = cdiv(Cout, kConvNAlign) * kConvNAlign;
-    Conv2dLayout L;
-    L.packed = r.wino ? 0 : conv_packed_floats(Npad, Kpad);
-    L.splitk = r.wino ? 0 : (splitk_floats_for(p, 1, B, Npad) + 63) / 64 * 64;
-    L.wino = r.wino ? wino_region_floats(kWinoForms[r.wino].image, Cout, Cin, Cout % 128 == 0) : 0;      // up to the image the form reads
-    L.tickets = (!r.wino && p.fused && p.nsplit > 1) ? kConvTickets : 0;
-    L.total = L.packed + L.splitk + L.wino + L.tickets;
-    return L;
-}
-ConvPlan conv2d_plan_for(int B, int Ho, int Wo, int Cin, int Cout, int Kh, int Kw, int bm, int bn, const Conv2dRequest& r) {
-    const int Kpad = cdiv(Cin * Kh * Kw, kConvBK) * kConvBK;
-    ConvPlan p = plan_conv(Ho * Wo, B, Cout, Kpad / kConvBK, 1, r.wino ? 0 : bm, bn, r.wino ? 1 : r.nsplit);
-    p.bf3 = r.bf3 ? 1 : 0;
-    p.h3 = r.h3 ? 1 : 0;
-    if (r.two_launch) p.fused = 0;
-    p.lat = r.lat;
-    p.stem = r.stem ? 256 : 0;
-    p.pool = r.pool ? 1 : 0;
-    p.pw = r.pw;
-    p.wino = r.wino;
-    return p;
-}
-}  // namespace
-
-extern "C" int fpc_conv2d_plan(int B, int Ho, int Wo, int Cin, int Cout, int Kh, int Kw, int bm, int bn, int nsplit,
-                               int* out4) {
-    if (!out4) return FPC_EINVAL;
-    const int Kpad = cdiv(Cin * Kh * Kw, kConvBK) * kConvBK;
-    // whatever kernel or product the request selects, the tiling reported is k_conv_igemm's with the request's split-K factor (no
-    // GroupNorm rows of its own for k_lateral1x1 / k_stem7x7 / k_conv1x1); a Winograd request: 64 x 64, the request, the form's rows
-    const Conv2dRequest r = decode_plan(nsplit);
-    ConvPlan p = plan_conv(Ho * Wo, B, Cout, Kpad / kConvBK, 1, bm, bn, r.nsplit);
-    p.wino = r.wino;
-    out4[0] = p.bm; out4[1] = p.bn; out4[2] = r.wino ? nsplit : p.nsplit; out4[3] = plan_gn_rows(p, Ho, Wo, B, Cin, r.pack, r.orient);
-    return FPC_OK;
-}
-
-// Exact workspace of fpc_conv2d for ONE request (same bm / bn / nsplit): at most fpc_conv2d_workspace_bytes, usually far
-// less (that bound reserves 32 split-K slices of the whole output).  fpc_conv2d accepts either.
-extern "C" size_t fpc_conv2d_workspace_bytes_for(int B, int Ho, int Wo, int Cin, int Cout, int Kh, int Kw, int bm, int bn,
-                                                 int nsplit) {
-    if (B < 1 || Ho < 1 || Wo < 1 || Cin < 1 || Cout < 1 || Kh < 1 || Kw < 1) return 0;
-    const Conv2dRequest r = decode_plan(nsplit);
-    const ConvPlan p = conv2d_plan_for(B, Ho, Wo, Cin, Cout, Kh, Kw, bm, bn, r);
-    return std::max<size_t>(conv2d_layout(B, Cin, Cout, Kh, Kw, p, r).total * sizeof(float), 256);
-}
-
-extern "C" int fpc_conv2d(const float* in, int64_t sb, int64_t sh, int64_t sw, int64_t sc, const float* w_oihw,
-                          const float* scale, const float* shift, const float* res, const float* up, float* out,
-                          float* gn_part, int B, int Hi, int Wi, int Cin, int Cout, int Kh, int Kw, int stride, int pad,
-                          int relu, int bm, int bn, int nsplit, void* ws, size_t ws_bytes, fpc_stream_t stream) {
-    if (!in || !w_oihw || !out || !ws || B < 1 || Kh != Kw) return FPC_EINVAL;
-    int Ho = conv_out(Hi, Kh, stride, pad), Wo = conv_out(Wi, Kw, stride, pad);
-    if (Ho < 1 || Wo < 1) return FPC_EINVAL;
-    const Conv2dRequest rq = decode_plan(nsplit);
-    if (rq.grp) return FPC_EINVAL;      // this entry has no groups: fpc_conv2d_grouped
-    const int wino = rq.wino;
-    ConvPlan p = conv2d_plan_for(B, Ho, Wo, Cin, Cout, Kh, Kw, bm, bn, rq);
-    const Conv2dLayout lay = conv2d_layout(B, Cin, Cout, Kh, Kw, p, rq);
-    if (ws_bytes < lay.total * sizeof(float) || ((uintptr_t)ws & 255)) return FPC_EWORKSPACE;
-    PackedConv c;
-    c.Cin = c.Cinp = Cin; c.Cout = Cout; c.Kh = Kh; c.Kw = Kw; c.stride = stride; c.pad = pad;
-    c.K = Cin * Kh * Kw; c.Kpad = cdiv(c.K, kConvBK) * kConvBK; c.Npad = cdiv(Cout, kConvNAlign) * kConvNAlign;
-    hipStream_t s = (hipStream_t)stream;
-    float* packed = (float*)ws;
-    if (rq.stem) {      // the engine's stem layout: NHWC4 input, 8 taps x 4 channels per kernel row (K = 224), bf16 planes only
-        if (Cin != 4 || Kh != 7 || stride != 2 || pad != 3 || Cout != 64 || sc != 1 || sw != 4 || sh != (int64_t)4 * Wi ||
-            sb != (int64_t)4 * Hi * Wi || res || up || gn_part)
-            return FPC_EINVAL;
-        c.Kwp = 8; c.K = 4 * 7 * 8; c.Kpad = 224;
-        // pool: conv + BN + ReLU + max-pool 3x3 / 2 / 1 in one launch on the h3 image: out is [B][Ho / 2][Wo / 2][64]
-        FPC_TRY((rq.pool ? launch_pack_weight_h3 : launch_pack_weight_bf3)(w_oihw, packed, Cout, Cin, Cin, Kh, Kw, c.Kwp, c.Npad, c.Kpad, s));
-        fpc_net tmp0;
-        tmp0.B = B; tmp0.ws = packed; tmp0.splitk_off = lay.packed;
-        ConvArgs a0;
-        fill_conv_args(&tmp0, a0, c, p, Hi, Wi, Ho, Wo, sb, sh, sw, sc, relu != 0, 0);
-        a0.Cin = 8 * c.Cinp; a0.Kw = 1; a0.K = c.K; a0.lanepx = 1;
-        a0.p[0] = ConvPtrs{in, packed, out, scale, shift, nullptr, nullptr, nullptr};
-        return rq.pool ? launch_stem_pool(a0, packed, out, Ho / 2, Wo / 2, s) : launch_conv_plan(a0, p, 1, s);
-    }
-    // (the split-precision forms — bf16 x 3 tiles, k_lateral1x1 — read only the planes behind the f32 image: it is not packed for them)
-    static_assert(FPC_IGEMM_DMA_B, "the split-precision direct form stages its B rows from the bf16 planes by LDS-DMA; a build that loads "
-                                   "them from the f32 image must pack that image here as well");
-    // (the three-product form reads its own image at the start of the packed region: conv_packed_floats() > h3_packed_floats())
-    if (!wino) FPC_TRY((p.h3 ? launch_pack_weight_h3 : p.bf3 ? launch_pack_weight_bf3 : launch_pack_weight)(w_oihw, packed, Cout, Cin, Cin, Kh, Kw, Kw, c.Npad, c.Kpad, s));
-    int mode = (sc == 1 && Cin % kConvBK == 0 && Kh * Kw <= 32 && ((int64_t)Hi + 2 * pad) * sh * 4 < ((int64_t)1 << 31)) ? 0
-               : (sc == 1 && Cin % 4 == 0 && sw % 4 == 0 && sh % 4 == 0 && sb % 4 == 0 && ((uintptr_t)in & 15) == 0) ? 2 : 1;
-    fpc_net tmp;
-    tmp.B = B;
-    tmp.wino_pack = rq.pack ? 1 : 0;      // (-9 itself stays on the plain geometry
-    tmp.wino_orient = rq.orient ? 1 : 0;  // and in the stored orientation)
-    tmp.ws = packed;
-    tmp.splitk_off = lay.packed;
-    ConvArgs a;
-    fill_conv_args(&tmp, a, c, p, Hi, Wi, Ho, Wo, sb, sh, sw, sc, relu != 0, mode);
-    a.p[0] = ConvPtrs{in, packed, out, scale, shift, res, up, gn_part};
-    a.zeros = nullptr;
-    a.tickets = nullptr;
-    if (lay.tickets) {   // arrival counters of the fused split-K form, zeroed per call
-        float* tk = packed + lay.packed + lay.splitk + lay.wino;
-        a.tickets = (int*)tk;
-        if (hipMemsetAsync(tk, 0, kConvTickets * sizeof(int), s) != hipSuccess) return FPC_ELAUNCH;
-    }
-#ifdef FPC_STAMP_WINO      // diagnostic builds only: relu = 77 turns ReLU off and hands gn_part to the kernel as its stamp buffer
-    if (wino && relu == 77) { a.dbg = gn_part; a.p[0].gn_part = nullptr; a.relu = 0; }
-#endif
-#ifdef FPC_STAMP_IGEMM
-    if (!wino && relu == 77) { a.dbg = gn_part; a.p[0].gn_part = nullptr; a.relu = 0; }
-#endif
-    if (wino) {
-        if (Kh != 3 || stride != 1 || pad != 1 || Cin % 8 || Cout % 64 || sc != 1 || up || sw != Cin ||
-            sh != (int64_t)Wi * Cin || sb != (int64_t)Hi * Wi * Cin)
-            return FPC_EINVAL;
-        float* wp = packed + lay.packed + lay.splitk;
-        // (a form reads only its own image: the f32 image is not packed for a split-precision form — 78 launches of a training step)
-        if (!wino_form_ok(wino, Cin, Cout)) return FPC_EINVAL;
-        const WinoImage img = kWinoForms[wino].image;
-        if (rq.orient && wino_orient_rule(Ho, Wo)) FPC_TRY(launch_wino_pack_h3(w_oihw, wp + wino_image_offset(img, Cout, Cin), Cout, Cin, true, s));
-        else FPC_TRY(kWinoImages[img].pack(w_oihw, wp + wino_image_offset(img, Cout, Cin), Cout, Cin, s));
-        a.wino_w[0] = wp;
-        a.zeros = zero_page();       // (the workspace's last 64 floats stay reserved for it: fpc_conv2d_workspace_bytes is unchanged)
-        if (!a.zeros) {
-            float* zp = wp + lay.wino - 64;
-            if (hipMemsetAsync(zp, 0, 64 * sizeof(float), s) != hipSuccess) return FPC_ELAUNCH;
-            a.zeros = zp;
-        }
-        return launch_conv_plan(a, p, 1, s);
-    }
-    if (p.h3) {
-        if (mode != 0) return FPC_EINVAL;
-        a.h3_w[0] = packed;
-        return launch_conv_plan(a, p, 1, s);
-    }
-    a.bf3 = (p.bf3 && mode == 0) ? 1 : 0;
-    if (p.bf3 && mode != 0) return FPC_EINVAL;
-    if (p.lat || p.pw) return launch_conv_plan(a, p, 1, s);
-    return run_conv(nullptr, a, 1, 0, s);
-}
-
-// ---- stand-alone grouped 3x3 convolution (unit tests / micro-benchmarks of k_conv3x3_grouped) -----------------
-// workspace: k_pack_grouped's image, C * (C / groups) * 9 floats (0: a shape fpc_conv2d_grouped refuses)
-extern "C" size_t fpc_conv2d_grouped_workspace_bytes(int C, int groups) {
-    if (C < 32 || C % 32 || groups < 1 || C % groups || !grouped_cg_ok(C / groups)) return 0;
-    return std::max<size_t>(align_up((size_t)C * (C / groups) * 9 * sizeof(float), 256), 256);
-}
-
-extern "C" int fpc_conv2d_grouped(const float* in, int64_t sb, int64_t sh, int64_t sw, int64_t sc, const float* w_oihw,
-                                  const float* scale, const float* shift, float* out, int B, int Hi, int Wi, int C, int groups,
-                                  int stride, int relu, int form, void* ws, size_t ws_bytes, fpc_stream_t stream) {
-    if (!in || !w_oihw || !out || !ws || B < 1 || Hi < 1 || Wi < 1 || C < 32 || C % 32 || groups < 1 || C % groups ||
-        !grouped_cg_ok(C / groups) || (stride != 1 && stride != 2) || sc != 1 || form < 0 || form >= 1000)
-        return FPC_EINVAL;
-    const Conv2dRequest rq = decode_plan(FPC_PLAN_GROUPED + form);
-    if (!rq.grp || rq.grp > kGroupedForms) return FPC_EINVAL;
-    if (ws_bytes < fpc_conv2d_grouped_workspace_bytes(C, groups) || ((uintptr_t)ws & 255)) return FPC_EWORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    GroupedArgs g;
-    memset(&g, 0, sizeof(g));
-    g.in = in; g.w = (const float*)ws; g.out = out; g.scale = scale; g.shift = shift;
-    g.in_sb = sb; g.in_sh = sh; g.in_sw = sw;
-    g.B = B; g.Hi = Hi; g.Wi = Wi; g.Ho = conv_out(Hi, 3, stride, 1); g.Wo = conv_out(Wi, 3, stride, 1);
-    g.C = C; g.CG = C / groups; g.stride = stride; g.relu = relu ? 1 : 0; g.form = rq.grp - 1;
-    // (every refusal of the launcher is tested here first, on a null stream-free path: nothing is packed for a refused request)
-    if (((uintptr_t)in | (uintptr_t)out | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)w_oihw) & 15) return FPC_EINVAL;
-    if ((sb | sh | sw) % 4 || sw < C) return FPC_EINVAL;
-    FPC_TRY(launch_pack_grouped(w_oihw, (float*)ws, C, g.CG, s));
-    return launch_conv3x3_grouped(g, s);
-}
