@@ -28,20 +28,19 @@ class NetEngine:
         self.classes = model.classes
         h = ctypes.c_void_p()
         from fastposecnn_amd.lib import backbone
-        block, layers = backbone.encoder_layout(model.encoder.name)
-        groups, width = backbone.encoder_groups(model.encoder.name)
-        reduction = backbone.encoder_reduction(model.encoder.name)
+        name = model.encoder.name
+        block, layers = backbone.encoder_layout(name)
+        groups, width = backbone.encoder_groups(name)
+        reduction = backbone.encoder_reduction(name)
+        arr, tail = (ctypes.c_int * 4)(*layers), (self.classes, B, H, W, ctypes.byref(h))
         if reduction:       # SE-ResNet: the Bottleneck with the stride on conv1 and the squeeze-and-excitation gate
-            nat.check(L.fpc_net_create_encoder_se((ctypes.c_int * 4)(*layers), reduction, self.classes, B, H, W, ctypes.byref(h)),
-                      "fpc_net_create_encoder_se")
+            nat.check(L.fpc_net_create_encoder_se(arr, reduction, *tail), "fpc_net_create_encoder_se")
         elif groups > 1:    # ResNeXt: Bottleneck with a grouped conv2
-            nat.check(L.fpc_net_create_encoder_ex(block, (ctypes.c_int * 4)(*layers), groups, width, self.classes, B, H, W,
-                                                  ctypes.byref(h)), "fpc_net_create_encoder_ex")
+            nat.check(L.fpc_net_create_encoder_ex(block, arr, groups, width, *tail), "fpc_net_create_encoder_ex")
         elif block == 1:    # the named nets, as always
-            nat.check(L.fpc_net_create(model.encoder.name.encode(), self.classes, B, H, W, ctypes.byref(h)), "fpc_net_create")
+            nat.check(L.fpc_net_create(name.encode(), *tail), "fpc_net_create")
         else:               # Bottleneck encoders by their descriptor
-            nat.check(L.fpc_net_create_encoder(block, (ctypes.c_int * 4)(*layers), self.classes, B, H, W, ctypes.byref(h)),
-                      "fpc_net_create_encoder")
+            nat.check(L.fpc_net_create_encoder(block, arr, *tail), "fpc_net_create_encoder")
         self._h = h
         self._names = [L.fpc_net_param_name(h, i).decode() for i in range(L.fpc_net_param_count(h))]
         nbytes = L.fpc_net_workspace_bytes(h)

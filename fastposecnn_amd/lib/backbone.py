@@ -27,27 +27,37 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 
+def _train_conv():
+    """lib/train_conv.py, imported when a training step first needs it."""
+    from fastposecnn_amd.lib import train_conv
+    return train_conv
+
+
+def _train_native(ok, front_end, *args, **kw):
+    """The one dispatch of the training step's native ops: while `ok` — the caller's own pre-conditions — holds, the front end
+    lib/train_conv.<front_end>(*args), an attribute of the module looked up at call time; None when `ok` fails or the front end
+    refuses its operands, and the caller runs torch's modules."""
+    return getattr(_train_conv(), front_end)(*args, **kw) if ok else None
+
+
 class Conv2d(nn.Conv2d):
     """nn.Conv2d whose TRAINING-mode forward on a GPU runs on the native kernels, forward and backward
     (lib/train_conv.py); evaluation goes through the engine's plan (or torch, on CPU) as before.  Same parameters and
     state_dict names as nn.Conv2d."""
 
     def forward(self, x):
-        if self.training and x.is_cuda and self.dilation == (1, 1) and self.padding_mode == "zeros" \
-                and self.stride[0] == self.stride[1] and self.padding[0] == self.padding[1] and not isinstance(self.padding, str):
-            from fastposecnn_amd.lib import train_conv
-            if train_conv.ENABLED:      # (groups > 1: torch's grouped convolution on the channel-last tensor)
-                return train_conv.conv2d(x, self.weight, self.bias, self.stride[0], self.padding[0], self.groups)
-        return super().forward(x)
+        ok = self.training and x.is_cuda and self.dilation == (1, 1) and self.padding_mode == "zeros" \
+            and self.stride[0] == self.stride[1] and self.padding[0] == self.padding[1] and not isinstance(self.padding, str) \
+            and _train_conv().ENABLED      # (groups > 1: torch's grouped convolution on the channel-last tensor)
+        y = _train_native(ok, "conv2d", x, self.weight, self.bias, self.stride[0], self.padding[0], self.groups)
+        return super().forward(x) if y is None else y
 
 
 def _upsample_bilinear(x, scale, out_nchw=False):
     """Bilinear, align_corners=True.  Under autograd on a GPU (the training step) the native forward / backward kernels of
     lib/train_conv.py; plain torch otherwise (inference goes through the engine's plan and never gets here)."""
-    if x.is_cuda and torch.is_grad_enabled() and x.requires_grad:
-        from fastposecnn_amd.lib import train_conv
-        return train_conv.upsample_bilinear(x, scale, out_nchw)
-    return F.interpolate(x, scale_factor=scale, mode="bilinear", align_corners=True)
+    y = _train_native(x.is_cuda and torch.is_grad_enabled() and x.requires_grad, "upsample_bilinear", x, scale, out_nchw)
+    return F.interpolate(x, scale_factor=scale, mode="bilinear", align_corners=True) if y is None else y
 
 
 class UpsamplingBilinear2d(nn.UpsamplingBilinear2d):
@@ -66,12 +76,8 @@ class BatchNorm2d(nn.BatchNorm2d):
     the engine folds it at plan build like any nn.BatchNorm2d."""
 
     def forward(self, x):
-        if x.is_cuda and torch.is_grad_enabled():
-            from fastposecnn_amd.lib import train_conv
-            y = train_conv.batchnorm_act(x, self, relu=False)
-            if y is not None:
-                return y
-        return super().forward(x)
+        y = _train_native(x.is_cuda and torch.is_grad_enabled(), "batchnorm_act", x, self, relu=False)
+        return super().forward(x) if y is None else y
 
 
 class MaxPool2d(nn.MaxPool2d):
@@ -81,25 +87,21 @@ class MaxPool2d(nn.MaxPool2d):
     is nn.MaxPool2d's own forward.  No parameters: state_dicts are untouched."""
 
     def forward(self, x):
-        if x.is_cuda and torch.is_grad_enabled() and x.requires_grad and not self.return_indices and not self.ceil_mode \
-                and self.kernel_size in (3, (3, 3)) and self.stride in (2, (2, 2)) and self.padding in (1, (1, 1)) \
-                and self.dilation in (1, (1, 1)):
-            from fastposecnn_amd.lib import train_conv
-            y = train_conv.maxpool3x3s2(x)
-            if y is not None:
-                return y
-        return super().forward(x)
+        ok = x.is_cuda and torch.is_grad_enabled() and x.requires_grad and not self.return_indices and not self.ceil_mode \
+            and self.kernel_size in (3, (3, 3)) and self.stride in (2, (2, 2)) and self.padding in (1, (1, 1)) \
+            and self.dilation in (1, (1, 1))
+        y = _train_native(ok, "maxpool3x3s2", x)
+        return super().forward(x) if y is None else y
 
 
 def _bn_act(x, bn, act, res=None):
     """act(bn(x) + res) at a block's BatchNorm.  In the training step BatchNorm, the add and the ReLU are one native op; the
     ReLU (and with it the add) is fused only while `act` is an nn.ReLU — a test may have swapped it for a smooth activation,
     and then the BatchNorm runs native and plain (its own forward), the add and the activation stay torch."""
-    if isinstance(act, nn.ReLU) and isinstance(bn, BatchNorm2d) and bn.training and x.is_cuda and torch.is_grad_enabled():
-        from fastposecnn_amd.lib import train_conv
-        y = train_conv.batchnorm_act(x, bn, res, relu=True, count_refusal=False)      # (refused: bn(x) below asks again, plain)
-        if y is not None:
-            return y
+    ok = isinstance(act, nn.ReLU) and isinstance(bn, BatchNorm2d) and bn.training and x.is_cuda and torch.is_grad_enabled()
+    y = _train_native(ok, "batchnorm_act", x, bn, res, relu=True, count_refusal=False)      # (refused: bn(x) below asks again, plain)
+    if y is not None:
+        return y
     y = bn(x)
     if res is not None:
         y = y + res
@@ -197,132 +199,71 @@ class SEResNetBottleneck(nn.Module):
         out = _bn_act(self.conv2(out), self.bn2, self.relu)
         out = self.bn3(self.conv3(out))
         residual = x if self.downsample is None else self.downsample(x)
-        if out.is_cuda and torch.is_grad_enabled():
-            from fastposecnn_amd.lib import train_conv
-            y = train_conv.se_gate_add_relu(out, self.se_module, residual, self.relu)
-            if y is not None:
-                return y
-        return self.relu(self.se_module(out) + residual)
+        y = _train_native(out.is_cuda and torch.is_grad_enabled(), "se_gate_add_relu", out, self.se_module, residual, self.relu)
+        return self.relu(self.se_module(out) + residual) if y is None else y
 
 
-# name -> (block, blocks per stage), as torchvision / smp
-_RESNET_LAYERS = {"resnet18": (BasicBlock, [2, 2, 2, 2]), "resnet34": (BasicBlock, [3, 4, 6, 3]),
-                  "resnet50": (Bottleneck, [3, 4, 6, 3]), "resnet101": (Bottleneck, [3, 4, 23, 3]),
-                  "resnet152": (Bottleneck, [3, 8, 36, 3]),
-                  "resnext50_32x4d": (Bottleneck, [3, 4, 6, 3]), "resnext101_32x4d": (Bottleneck, [3, 4, 23, 3]),
-                  "resnext101_32x8d": (Bottleneck, [3, 4, 23, 3])}
-# name -> (groups, width per group) of the ResNeXt encoders; every other encoder is (1, 64)
-_RESNEXT_WIDTHS = {"resnext50_32x4d": (32, 4), "resnext101_32x4d": (32, 4), "resnext101_32x8d": (32, 8)}
-# the squeeze-and-excitation ResNets (smp's SENetEncoder over pretrainedmodels.senet): name -> (block, blocks per stage, reduction)
-_SENET_LAYERS = {"se_resnet50": (SEResNetBottleneck, [3, 4, 6, 3], 16), "se_resnet101": (SEResNetBottleneck, [3, 4, 23, 3], 16),
-                 "se_resnet152": (SEResNetBottleneck, [3, 8, 36, 3], 16)}
+# name -> (block, blocks per stage, groups, width per group, squeeze-and-excitation reduction: 0 without the gate), as torchvision /
+# smp for the ResNets and ResNeXts, smp's SENetEncoder over pretrainedmodels.senet for the SE-ResNets
+_ENCODERS = {"resnet18": (BasicBlock, [2, 2, 2, 2], 1, 64, 0), "resnet34": (BasicBlock, [3, 4, 6, 3], 1, 64, 0),
+             "resnet50": (Bottleneck, [3, 4, 6, 3], 1, 64, 0), "resnet101": (Bottleneck, [3, 4, 23, 3], 1, 64, 0),
+             "resnet152": (Bottleneck, [3, 8, 36, 3], 1, 64, 0),
+             "resnext50_32x4d": (Bottleneck, [3, 4, 6, 3], 32, 4, 0), "resnext101_32x4d": (Bottleneck, [3, 4, 23, 3], 32, 4, 0),
+             "resnext101_32x8d": (Bottleneck, [3, 4, 23, 3], 32, 8, 0),
+             "se_resnet50": (SEResNetBottleneck, [3, 4, 6, 3], 1, 64, 16), "se_resnet101": (SEResNetBottleneck, [3, 4, 23, 3], 1, 64, 16),
+             "se_resnet152": (SEResNetBottleneck, [3, 8, 36, 3], 1, 64, 16)}
 
 
 def encoder_layout(name):
     """(block expansion, blocks per stage) of encoder `name`: the descriptor fpc_net_create_encoder takes."""
-    block, layers = _SENET_LAYERS[name][:2] if name in _SENET_LAYERS else _RESNET_LAYERS[name]
+    block, layers = _ENCODERS[name][:2]
     return block.expansion, list(layers)
 
 
 def encoder_groups(name):
     """(groups, width per group) of encoder `name`: what fpc_net_create_encoder_ex takes beside encoder_layout's pair."""
-    if name not in _RESNET_LAYERS and name not in _SENET_LAYERS:
-        raise KeyError(name)
-    return _RESNEXT_WIDTHS.get(name, (1, 64))
+    return _ENCODERS[name][2:4]
 
 
 def encoder_reduction(name):
     """The squeeze-and-excitation reduction of encoder `name` (16 for the SE-ResNets: what fpc_net_create_encoder_se takes), 0 for
     every encoder without the gate."""
-    if name not in _RESNET_LAYERS and name not in _SENET_LAYERS:
-        raise KeyError(name)
-    return _SENET_LAYERS[name][2] if name in _SENET_LAYERS else 0
+    return _ENCODERS[name][4]
 
 
-class ResNetEncoder(nn.Module):
-    """torchvision-style ResNet (BasicBlock or Bottleneck) without avgpool/fc, returning 6 feature levels."""
+def _make_stage(block, inplanes, planes, blocks, stride, **kw):
+    """One stage: `blocks` blocks of `planes`, the first with the stride and, where the shape changes, a 1x1 downsample."""
+    downsample = None
+    if stride != 1 or inplanes != planes * block.expansion:
+        downsample = nn.Sequential(Conv2d(inplanes, planes * block.expansion, 1, stride, bias=False),
+                                   BatchNorm2d(planes * block.expansion))
+    layers = [block(inplanes, planes, stride=stride, downsample=downsample, **kw)]
+    layers += [block(planes * block.expansion, planes, **kw) for _ in range(1, blocks)]
+    return nn.Sequential(*layers)
 
-    def __init__(self, name="resnet18", in_channels=3, depth=5):
+
+class _Encoder(nn.Module):
+    """What the encoder classes share: the descriptor look-up, the four stages, the initialisation and the walk over the six
+    feature levels.  A subclass says which descriptors are its own (`_gated`), builds its stem and names the stem's four modules."""
+
+    def __init__(self, name, in_channels, depth):
         super().__init__()
-        if name not in _RESNET_LAYERS:
-            raise KeyError(f"encoder {name!r} not available (have {sorted(_RESNET_LAYERS) + sorted(_SENET_LAYERS)})")
-        block, layers = _RESNET_LAYERS[name]
+        if name not in _ENCODERS or bool(_ENCODERS[name][4]) != self._gated:
+            raise KeyError(f"encoder {name!r} not available (have {sorted(_ENCODERS)})")
+        block, layers, groups, width, reduction = _ENCODERS[name]
         self.name = name
         self._depth = depth
-        self._block = block
-        self._groups, self._base_width = encoder_groups(name)
         e = block.expansion
         self.out_channels = (in_channels, 64, 64 * e, 128 * e, 256 * e, 512 * e)
-        self.inplanes = 64
-        self.conv1 = Conv2d(in_channels, 64, 7, 2, 3, bias=False)
-        self.bn1 = BatchNorm2d(64)
-        self.relu = nn.ReLU(inplace=True)
-        self.maxpool = MaxPool2d(3, 2, 1)
-        self.layer1 = self._make_layer(64, layers[0])
-        self.layer2 = self._make_layer(128, layers[1], stride=2)
-        self.layer3 = self._make_layer(256, layers[2], stride=2)
-        self.layer4 = self._make_layer(512, layers[3], stride=2)
-        for m in self.modules():
-            if isinstance(m, nn.Conv2d):
-                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
-            elif isinstance(m, nn.BatchNorm2d):
-                nn.init.constant_(m.weight, 1)
-                nn.init.constant_(m.bias, 0)
-
-    def _make_layer(self, planes, blocks, stride=1):
-        block = self._block
-        downsample = None
-        if stride != 1 or self.inplanes != planes * block.expansion:
-            downsample = nn.Sequential(Conv2d(self.inplanes, planes * block.expansion, 1, stride, bias=False),
-                                       BatchNorm2d(planes * block.expansion))
-        kw = dict(groups=self._groups, base_width=self._base_width) if self._groups > 1 else {}
-        layers = [block(self.inplanes, planes, stride, downsample, **kw)]
-        self.inplanes = planes * block.expansion
-        for _ in range(1, blocks):
-            layers.append(block(self.inplanes, planes, **kw))
-        return nn.Sequential(*layers)
-
-    def forward(self, x):
-        feats = [x]
-        x = _bn_act(self.conv1(x), self.bn1, self.relu)
-        feats.append(x)
-        x = self.layer1(self.maxpool(x))
-        feats.append(x)
-        x = self.layer2(x)
-        feats.append(x)
-        x = self.layer3(x)
-        feats.append(x)
-        x = self.layer4(x)
-        feats.append(x)
-        return feats
-
-
-class SENetEncoder(nn.Module):
-    """smp's SENetEncoder for the SE-ResNets (pretrainedmodels.senet.SENet with groups = 1, inplanes = 64, a 7x7 stem and 1x1
-    downsamples, without avg_pool / last_linear), returning 6 feature levels.  layer0 is the stem as a Sequential of named
-    children; its pool is MaxPool2d(3, stride=2, ceil_mode=True) WITHOUT padding (windows start at 0, the last one is clipped),
-    a plain nn.MaxPool2d in every mode: the native training pool kernels are pad-1 kernels."""
-
-    def __init__(self, name="se_resnet50", in_channels=3, depth=5):
-        super().__init__()
-        if name not in _SENET_LAYERS:
-            raise KeyError(f"encoder {name!r} not available (have {sorted(_RESNET_LAYERS) + sorted(_SENET_LAYERS)})")
-        from collections import OrderedDict
-        block, layers, reduction = _SENET_LAYERS[name]
-        self.name = name
-        self._depth = depth
-        self._reduction = reduction
-        self.out_channels = (in_channels, 64, 256, 512, 1024, 2048)
-        self.inplanes = 64
-        self.layer0 = nn.Sequential(OrderedDict([
-            ("conv1", Conv2d(in_channels, 64, 7, 2, 3, bias=False)), ("bn1", BatchNorm2d(64)), ("relu1", nn.ReLU(inplace=True)),
-            ("pool", nn.MaxPool2d(3, stride=2, ceil_mode=True))]))
-        self.layer1 = self._make_layer(block, 64, layers[0])
-        self.layer2 = self._make_layer(block, 128, layers[1], stride=2)
-        self.layer3 = self._make_layer(block, 256, layers[2], stride=2)
-        self.layer4 = self._make_layer(block, 512, layers[3], stride=2)
-        # (pretrainedmodels leaves torch's default initialisation; the bias-free convolutions and the BatchNorms start as the
-        # ResNet encoders' here, fc1 / fc2 keep nn.Conv2d's default.  A checkpoint or a weights file overwrites all of it.)
+        self._make_stem(in_channels)
+        kw = dict(reduction=reduction) if reduction else dict(groups=groups, base_width=width) if groups > 1 else {}
+        inplanes = 64
+        for i, planes in enumerate((64, 128, 256, 512)):
+            setattr(self, f"layer{i + 1}", _make_stage(block, inplanes, planes, layers[i], 1 if i == 0 else 2, **kw))
+            inplanes = planes * e
+        # (pretrainedmodels leaves torch's default initialisation; the bias-free convolutions and the BatchNorms of the SE-ResNets
+        # start as the ResNet encoders' here, fc1 / fc2 — the only biased ones — keep nn.Conv2d's default.  A checkpoint or a weights
+        # file overwrites all of it.)
         for m in self.modules():
             if isinstance(m, nn.Conv2d) and m.bias is None:
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
@@ -330,30 +271,53 @@ class SENetEncoder(nn.Module):
                 nn.init.constant_(m.weight, 1)
                 nn.init.constant_(m.bias, 0)
 
-    def _make_layer(self, block, planes, blocks, stride=1):
-        downsample = None
-        if stride != 1 or self.inplanes != planes * block.expansion:
-            downsample = nn.Sequential(Conv2d(self.inplanes, planes * block.expansion, 1, stride, bias=False),
-                                       BatchNorm2d(planes * block.expansion))
-        layers = [block(self.inplanes, planes, self._reduction, stride, downsample)]
-        self.inplanes = planes * block.expansion
-        for _ in range(1, blocks):
-            layers.append(block(self.inplanes, planes, self._reduction))
-        return nn.Sequential(*layers)
-
     def forward(self, x):
+        conv1, bn1, relu, pool = self._stem()
         feats = [x]
-        x = _bn_act(self.layer0.conv1(x), self.layer0.bn1, self.layer0.relu1)
+        x = _bn_act(conv1(x), bn1, relu)
         feats.append(x)
-        x = self.layer1(self.layer0.pool(x))
-        feats.append(x)
-        x = self.layer2(x)
-        feats.append(x)
-        x = self.layer3(x)
-        feats.append(x)
-        x = self.layer4(x)
-        feats.append(x)
+        x = pool(x)
+        for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
+            x = layer(x)
+            feats.append(x)
         return feats
+
+
+class ResNetEncoder(_Encoder):
+    """torchvision-style ResNet (BasicBlock or Bottleneck) without avgpool/fc, returning 6 feature levels."""
+    _gated = False
+
+    def __init__(self, name="resnet18", in_channels=3, depth=5):
+        super().__init__(name, in_channels, depth)
+
+    def _make_stem(self, in_channels):
+        self.conv1 = Conv2d(in_channels, 64, 7, 2, 3, bias=False)
+        self.bn1 = BatchNorm2d(64)
+        self.relu = nn.ReLU(inplace=True)
+        self.maxpool = MaxPool2d(3, 2, 1)
+
+    def _stem(self):
+        return self.conv1, self.bn1, self.relu, self.maxpool
+
+
+class SENetEncoder(_Encoder):
+    """smp's SENetEncoder for the SE-ResNets (pretrainedmodels.senet.SENet with groups = 1, inplanes = 64, a 7x7 stem and 1x1
+    downsamples, without avg_pool / last_linear), returning 6 feature levels.  layer0 is the stem as a Sequential of named
+    children; its pool is MaxPool2d(3, stride=2, ceil_mode=True) WITHOUT padding (windows start at 0, the last one is clipped),
+    a plain nn.MaxPool2d in every mode: the native training pool kernels are pad-1 kernels."""
+    _gated = True
+
+    def __init__(self, name="se_resnet50", in_channels=3, depth=5):
+        super().__init__(name, in_channels, depth)
+
+    def _make_stem(self, in_channels):
+        from collections import OrderedDict
+        self.layer0 = nn.Sequential(OrderedDict([
+            ("conv1", Conv2d(in_channels, 64, 7, 2, 3, bias=False)), ("bn1", BatchNorm2d(64)), ("relu1", nn.ReLU(inplace=True)),
+            ("pool", nn.MaxPool2d(3, stride=2, ceil_mode=True))]))
+
+    def _stem(self):
+        return self.layer0.conv1, self.layer0.bn1, self.layer0.relu1, self.layer0.pool
 
 
 _WARNED_WEIGHTS = set()
@@ -371,7 +335,7 @@ def get_encoder(name, in_channels=3, depth=5, weights=None):
     encoder — a checkpoint loaded afterwards (load_from_ckpt) overwrites the encoder anyway."""
     import logging
     import os
-    enc = (SENetEncoder if name in _SENET_LAYERS else ResNetEncoder)(name, in_channels=in_channels, depth=depth)
+    enc = (SENetEncoder if name in _ENCODERS and _ENCODERS[name][4] else ResNetEncoder)(name, in_channels=in_channels, depth=depth)
     enc.requested_weights = weights
     enc.loaded_weights = None
     if weights is not None:
@@ -406,8 +370,7 @@ class Conv3x3GNReLU(nn.Module):
     def forward(self, x):
         if self.training and x.is_cuda and torch.is_grad_enabled() and isinstance(self.block[2], nn.ReLU):
             # the training step: GroupNorm + ReLU as one native channel-last op behind the native convolution
-            from fastposecnn_amd.lib import train_conv
-            x = train_conv.groupnorm_relu(self.block[0](x), self.block[1])
+            x = _train_native(True, "groupnorm_relu", self.block[0](x), self.block[1])
         else:
             x = self.block(x)
         if self.upsample:
@@ -422,11 +385,10 @@ class FPNBlock(nn.Module):
 
     def forward(self, x, skip=None):
         c = self.skip_conv
-        if c.training and x.is_cuda and torch.is_grad_enabled():      # the training step: lateral convolution + merge in one launch
-            from fastposecnn_amd.lib import train_conv
-            y = train_conv.conv2d_up_add(skip, c.weight, c.bias, x, c.padding[0])
-            if y is not None:
-                return y
+        # the training step: lateral convolution + merge in one launch
+        y = _train_native(c.training and x.is_cuda and torch.is_grad_enabled(), "conv2d_up_add", skip, c.weight, c.bias, x, c.padding[0])
+        if y is not None:
+            return y
         x = F.interpolate(x, scale_factor=2, mode="nearest")
         skip = self.skip_conv(skip)
         return x + skip

@@ -42,7 +42,10 @@ ENABLED = bool(int(os.environ.get("FPC_TRAIN_NATIVE_CONV", "1")))
 SPLIT_PRECISION = bool(int(os.environ.get("FPC_SPLIT_PRECISION", "1")))      # the bf16 x 3 product forms may be chosen
 SPLIT_F16 = SPLIT_PRECISION and bool(int(os.environ.get("FPC_SPLIT_F16", "1")))      # ... and, for forward convolutions, the fp16 x 2 Winograd form
 _plan_cache = {}            # (device index, B, Cin, H, W, Cout, k, stride, pad) -> nsplit code of fpc_conv2d
-counters = {"fwd_native": 0, "dgrad_native": 0, "wgrad_native": 0, "dgrad_aten": 0, "wgrad_aten": 0, "wgrad_direct": 0}
+counters = {"fwd_native": 0, "dgrad_native": 0, "wgrad_native": 0, "dgrad_aten": 0, "wgrad_aten": 0, "wgrad_direct": 0,
+            "grouped_fwd_native": 0, "grouped_dgrad_native": 0, "grouped_wgrad_native": 0,
+            "stem_fwd_native": 0, "stem_wgrad_native": 0, "pool_fwd_native": 0, "pool_bwd_native": 0,
+            "bn_native": 0, "bn_torch": 0, "se_fwd_native": 0, "se_bwd_native": 0, "se_torch": 0}
 
 
 # Weight-gradient sinks (round 6): an optimiser that keeps `p.grad` as views of one flat buffer (train_parallel.py) registers
@@ -61,8 +64,56 @@ class GradSink:
 grad_sinks = {}
 
 
+def _take_sink(w, aligned, padded=False):
+    """The registered sink the weight-gradient kernel may write dW of `w` into, or None: no entry, one already written this step, a
+    view of another shape, not contiguous or (where the caller's kernel needs it: `aligned`) not 16-byte aligned, or a gradient
+    taken for a zero-padded copy of the weight (`padded`).  The entry of a dead owner is deleted."""
+    sink = None if padded else grad_sinks.get(w.data_ptr())
+    if sink is not None and sink.owner() is None:        # its optimiser is gone: the address may belong to another tensor now
+        del grad_sinks[w.data_ptr()]
+        return None
+    if sink is None or sink.written or sink.view.shape != w.shape or not sink.view.is_contiguous() or (aligned and sink.view.data_ptr() % 16):
+        return None
+    return sink
+
+
+def _commit_sink(sink):
+    """dW was written in place: nothing is left for autograd to accumulate, the caller returns None for the weight."""
+    sink.written = True
+    sink.callback()
+
+
+def _is_nhwc(t):
+    return t.stride(1) == 1 and t.is_contiguous(memory_format=torch.channels_last)
+
+
 def _channels_last(t):
-    return t if t.stride(1) == 1 and t.is_contiguous(memory_format=torch.channels_last) else t.contiguous(memory_format=torch.channels_last)
+    return t if _is_nhwc(t) else t.contiguous(memory_format=torch.channels_last)
+
+
+def _operand(t, aligned=False, nhwc=True):
+    """An incoming gradient or an input as the kernels read it: channel-last (nhwc=False: contiguous), and a copy of a tensor that
+    is not 16-byte aligned where the caller's kernels need that (`aligned`)."""
+    t = _channels_last(t) if nhwc else t.contiguous()
+    if aligned and t.data_ptr() % 16:
+        t = t.clone(memory_format=torch.channels_last if nhwc else torch.contiguous_format)
+    return t
+
+
+# ---- the conditions the gates share: each gate below is a conjunction of these and its own terms ---------------------------------
+
+def _f32_cuda_4d(x, any_device=False):
+    """f32 CUDA 4-D tensor on the current device (the launches go to its stream); any_device: on whichever"""
+    return x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and (any_device or x.device.index == torch.cuda.current_device())
+
+
+def _dense_nhwc(t):
+    return _is_nhwc(t) and t.data_ptr() % 16 == 0
+
+
+def _f32_param(t, dev):
+    """contiguous 16-byte-aligned f32 parameter on `dev`: the kernels read it as it stands"""
+    return t.dtype == torch.float32 and t.device == dev and t.is_contiguous() and t.data_ptr() % 16 == 0
 
 
 def _run(x, w, bias, stride, pad, code, out, up=None):
@@ -156,7 +207,7 @@ def _dgrad_stride2(gy, w, H, W, pad):
 def _conv_backward(x, w, gy, stride, pad, needs, has_bias):
     """(dx, dW, db) of a convolution whose forward ran on the native kernels; needs = (x, W, bias) wanted."""
     Cout, Cin, Kh, Kw = w.shape
-    gy = _channels_last(gy)
+    gy = _operand(gy)
     need_x, need_w = needs[0], needs[1]
     gx = gw = gb = None
     if has_bias and needs[2]:
@@ -188,12 +239,7 @@ def _conv_backward(x, w, gy, stride, pad, needs, has_bias):
         L = nat.lib()
         B, _, H, W = x.shape
         Ho, Wo = gy.shape[2], gy.shape[3]
-        sink = grad_sinks.get(w.data_ptr()) if Cw == Cout else None
-        if sink is not None and sink.owner() is None:        # its optimiser is gone: the address may belong to another tensor now
-            del grad_sinks[w.data_ptr()]
-            sink = None
-        if sink is not None and (sink.written or sink.view.shape != w.shape or not sink.view.is_contiguous()):
-            sink = None
+        sink = _take_sink(w, aligned=False, padded=Cw != Cout)      # (no alignment check at this site, as before)
         gw = sink.view if sink is not None else torch.empty_like(w)
         sb, sc, sh, sw = x.stride()
         ws = nat.workspace("train_wgrad", x.device, L.fpc_conv2d_wgrad_workspace_bytes(B, Ho, Wo, Cin, Cw, Kh, Kw))
@@ -203,11 +249,10 @@ def _conv_backward(x, w, gy, stride, pad, needs, has_bias):
         if Cw != Cout:
             gw = gw[:Cout].contiguous()
         counters["wgrad_native"] += 1
-        if sink is not None:                # written in place: nothing for autograd to accumulate
-            sink.written = True
-            sink.callback()
+        if sink is not None:
+            _commit_sink(sink)
             gw = None
-            counters["wgrad_direct"] += 1
+            counters["wgrad_direct"] += 1       # (counted at this site alone, as before)
     if aten_x or aten_w:
         ax, aw, _ = torch.ops.aten.convolution_backward(gy[:, :Cout] if Cw != Cout else gy, x, w_full, None, [stride, stride], [pad, pad],
                                                         [1, 1], False, [0, 0], 1, [aten_x, aten_w, False])
@@ -254,7 +299,7 @@ class _ConvUpAddFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         x, w = ctx.saved_tensors
-        gy = _channels_last(gy)
+        gy = _operand(gy)
         gx, gw, gb = _conv_backward(x, w, gy, 1, ctx.pad, ctx.needs_input_grad, ctx.has_bias)
         gt = torch.nn.functional.avg_pool2d(gy, 2, divisor_override=1) if ctx.needs_input_grad[3] else None
         return gx, gw, gb, gt, None
@@ -276,7 +321,6 @@ def conv2d_up_add(x, w, bias, top, pad):
 
 # Off by default: with it off a grouped convolution is torch's own, forward and backward, as before (DESIGN.md 4.2a'').
 NATIVE_GROUPED = bool(int(os.environ.get("FPC_TRAIN_NATIVE_GROUPED", "0")))
-counters.update(grouped_fwd_native=0, grouped_dgrad_native=0, grouped_wgrad_native=0)
 GROUPED_CG = (4, 8, 16, 32, 64)      # channels per group csrc/conv_grouped.hip is built for
 
 
@@ -291,13 +335,11 @@ _GROUPED_KEEP_TORCH = frozenset()
 
 
 def _grouped_ok(x, w, bias, stride, pad, groups):
-    if not (ENABLED and NATIVE_GROUPED and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
-            and w.dtype == torch.float32 and w.device == x.device and x.device.index == torch.cuda.current_device()):
+    if not (ENABLED and NATIVE_GROUPED and torch.is_tensor(x) and _f32_cuda_4d(x) and w.dtype == torch.float32 and w.device == x.device):
         return False
     C = x.shape[1]
-    # the bias is the kernel's `shift`: f32 on the same device, one value per channel, contiguous and 16-byte aligned as it stands
-    if bias is not None and not (bias.dtype == torch.float32 and bias.device == x.device and tuple(bias.shape) == (C,)
-                                 and bias.is_contiguous() and bias.data_ptr() % 16 == 0):
+    # the bias is the kernel's `shift`, read as it stands: one value per channel
+    if bias is not None and not (_f32_param(bias, x.device) and tuple(bias.shape) == (C,)):
         return False
     return (groups >= 1 and C % 32 == 0 and C % groups == 0 and C // groups in GROUPED_CG and tuple(w.shape) == (C, C // groups, 3, 3)
             and pad == 1 and stride in (1, 2) and x.numel() > 0)
@@ -309,9 +351,7 @@ class _GroupedConv2dFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, bias, stride, groups):
-        x = _channels_last(x)
-        if x.data_ptr() % 16:
-            x = x.clone(memory_format=torch.channels_last)
+        x = _operand(x, aligned=True)
         w = w.contiguous()
         B, C, H, W = x.shape
         Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
@@ -333,9 +373,7 @@ class _GroupedConv2dFn(torch.autograd.Function):
         stride, groups = ctx.stride, ctx.groups
         B, C, H, W = x.shape
         cg = C // groups
-        gy = _channels_last(gy)
-        if gy.data_ptr() % 16:
-            gy = gy.clone(memory_format=torch.channels_last)
+        gy = _operand(gy, aligned=True)
         Ho, Wo = gy.shape[2], gy.shape[3]
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         gx = gw = gb = None
@@ -351,22 +389,15 @@ class _GroupedConv2dFn(torch.autograd.Function):
                                                  ws.numel(), nat.stream()), "fpc_conv2d_grouped_dgrad")
             counters["grouped_dgrad_native"] += 1
         if need_w and not aten_w:
-            sink = grad_sinks.get(w.data_ptr())
-            if sink is not None and sink.owner() is None:        # its optimiser is gone: the address may belong to another tensor now
-                del grad_sinks[w.data_ptr()]
-                sink = None
-            if sink is not None and (sink.written or sink.view.shape != w.shape or not sink.view.is_contiguous()
-                                     or sink.view.data_ptr() % 16):
-                sink = None
+            sink = _take_sink(w, aligned=True)
             gw = sink.view if sink is not None else torch.empty_like(w)
             sb, sc, sh, sw = x.stride()
             ws = nat.workspace("train_grouped_wgrad", x.device, L.fpc_conv2d_grouped_wgrad_workspace_bytes(B, Ho, Wo, C, groups))
             nat.check(L.fpc_conv2d_grouped_wgrad(x.data_ptr(), sb, sh, sw, gy.data_ptr(), gw.data_ptr(), B, H, W, C, groups, stride,
                                                  ws.data_ptr(), ws.numel(), nat.stream()), "fpc_conv2d_grouped_wgrad")
             counters["grouped_wgrad_native"] += 1
-            if sink is not None:                # written in place: nothing for autograd to accumulate
-                sink.written = True
-                sink.callback()
+            if sink is not None:
+                _commit_sink(sink)
                 gw = None
         if aten_x or aten_w:
             ax, aw, _ = torch.ops.aten.convolution_backward(gy, x, w, None, [stride, stride], [1, 1], [1, 1], False, [0, 0], groups,
@@ -380,12 +411,10 @@ class _GroupedConv2dFn(torch.autograd.Function):
 
 # Off by default: with it off the stem and the max-pool are torch's own, forward and backward, as before (DESIGN.md 4.2a''').
 NATIVE_STEM = bool(int(os.environ.get("FPC_TRAIN_NATIVE_STEM", "0")))
-counters.update(stem_fwd_native=0, stem_wgrad_native=0, pool_fwd_native=0, pool_bwd_native=0)
 
 
 def _stem_ok(x, w, bias, stride, pad):
-    return (NATIVE_STEM and ENABLED and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
-            and w.dtype == torch.float32 and w.device == x.device and x.device.index == torch.cuda.current_device()
+    return (NATIVE_STEM and ENABLED and torch.is_tensor(x) and _f32_cuda_4d(x) and w.dtype == torch.float32 and w.device == x.device
             and tuple(w.shape) == (64, 3, 7, 7) and stride == 2 and pad == 3 and bias is None and x.shape[1] == 3
             and x.shape[0] >= 1 and x.shape[2] >= 8 and x.shape[3] >= 8 and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0
             and x.numel() < 2 ** 31
@@ -399,9 +428,7 @@ class _StemConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w):
-        x = x.contiguous()
-        if x.data_ptr() % 16:
-            x = x.clone()
+        x = _operand(x, aligned=True, nhwc=False)      # the planar image
         w = w.contiguous()
         B, _, H, W = x.shape
         Ho, Wo = H // 2, W // 2
@@ -428,25 +455,16 @@ class _StemConvFn(torch.autograd.Function):
         if not ctx.needs_input_grad[1]:
             return None, None
         B, H, W, _ = img4.shape
-        gy = _channels_last(gy)
-        if gy.data_ptr() % 16:
-            gy = gy.clone(memory_format=torch.channels_last)
+        gy = _operand(gy, aligned=True)
         L = nat.lib()
-        sink = grad_sinks.get(w.data_ptr())
-        if sink is not None and sink.owner() is None:        # its optimiser is gone: the address may belong to another tensor now
-            del grad_sinks[w.data_ptr()]
-            sink = None
-        if sink is not None and (sink.written or sink.view.shape != w.shape or not sink.view.is_contiguous()
-                                 or sink.view.data_ptr() % 16):
-            sink = None
+        sink = _take_sink(w, aligned=True)
         gw = sink.view if sink is not None else torch.empty((64, 3, 7, 7), dtype=torch.float32, device=gy.device)
         ws = nat.workspace("train_stem_wgrad", gy.device, L.fpc_stem_wgrad_workspace_bytes(B, H, W))
         nat.check(L.fpc_stem_wgrad(img4.data_ptr(), gy.data_ptr(), gw.data_ptr(), B, H, W, ws.data_ptr(), ws.numel(), nat.stream()),
                   "fpc_stem_wgrad")
         counters["stem_wgrad_native"] += 1
-        if sink is not None:                # written in place: nothing for autograd to accumulate
-            sink.written = True
-            sink.callback()
+        if sink is not None:
+            _commit_sink(sink)
             gw = None
         return None, gw
 
@@ -468,9 +486,7 @@ class _MaxPoolFn(torch.autograd.Function):
     def backward(ctx, gy):
         x, = ctx.saved_tensors
         B, C, H, W = x.shape
-        gy = _channels_last(gy)
-        if gy.data_ptr() % 16:
-            gy = gy.clone(memory_format=torch.channels_last)
+        gy = _operand(gy, aligned=True)
         dx = torch.empty_like(x, memory_format=torch.channels_last)
         nat.check(nat.lib().fpc_maxpool3x3s2_bwd(x.data_ptr(), gy.data_ptr(), dx.data_ptr(), B, H, W, C, nat.stream()),
                   "fpc_maxpool3x3s2_bwd")
@@ -481,10 +497,8 @@ class _MaxPoolFn(torch.autograd.Function):
 def maxpool3x3s2(x):
     """max_pool2d(x, 3, 2, 1) on the native kernels, forward and backward, for a dense channel-last f32 GPU tensor that requires
     grad under autograd, with NATIVE_STEM set; None otherwise (the caller keeps torch's module)."""
-    if not (NATIVE_STEM and ENABLED and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
-            and torch.is_grad_enabled() and x.requires_grad and x.device.index == torch.cuda.current_device()
-            and x.shape[1] % 4 == 0 and 0 < x.numel() < 2 ** 32 and x.stride(1) == 1
-            and x.is_contiguous(memory_format=torch.channels_last) and x.data_ptr() % 16 == 0):
+    if not (NATIVE_STEM and ENABLED and torch.is_tensor(x) and _f32_cuda_4d(x) and torch.is_grad_enabled() and x.requires_grad
+            and x.shape[1] % 4 == 0 and 0 < x.numel() < 2 ** 32 and _dense_nhwc(x)):
         return None
     return _MaxPoolFn.apply(x)
 
@@ -499,17 +513,14 @@ def conv2d(x, w, bias, stride, pad, groups=1):
     that needs no gradient: then _StemConvFn, counted in stem_fwd_native / stem_wgrad_native."""
     if groups == 1 and _stem_ok(x, w, bias, stride, pad):
         return _StemConvFn.apply(x, w)
-    if groups != 1:
-        if _grouped_ok(x, w, bias, stride, pad, groups):
-            return _GroupedConv2dFn.apply(x, w, bias, int(stride), int(groups))
-        if ENABLED and x.is_cuda and x.dim() == 4:
-            x = _channels_last(x)
-        return torch.nn.functional.conv2d(x, w, bias, stride, pad, 1, groups)
-    if ENABLED and x.is_cuda and x.dtype == torch.float32 and _native_forward_ok(x, w):
+    if groups != 1 and _grouped_ok(x, w, bias, stride, pad, groups):
+        return _GroupedConv2dFn.apply(x, w, bias, int(stride), int(groups))
+    # (the dense path asks neither for four dimensions nor for the current device, as before)
+    if groups == 1 and ENABLED and x.is_cuda and x.dtype == torch.float32 and _native_forward_ok(x, w):
         return _Conv2dFn.apply(x, w, bias, int(stride), int(pad))
     if ENABLED and x.is_cuda and x.dim() == 4:
-        x = _channels_last(x)        # the stem: keeps the rest of the network channel-last
-    return torch.nn.functional.conv2d(x, w, bias, stride, pad)
+        x = _channels_last(x)        # the stem, a grouped convolution: keeps the rest of the network channel-last
+    return torch.nn.functional.conv2d(x, w, bias, stride, pad, 1, groups)
 
 
 # ---- bilinear upsampling (align_corners = True): the x2 of the segmentation blocks, the x4 of the heads ----------------
@@ -525,7 +536,7 @@ class _UpBilinearFn(torch.autograd.Function):
         nat.check(L.fpc_upsample_bilinear_fwd(x.data_ptr(), sb, sc, sh, sw, out.data_ptr(), B, C, h, w, scale, int(out_nhwc), nat.stream()),
                   "fpc_upsample_bilinear_fwd")
         ctx.scale, ctx.shape = scale, (B, C, h, w)
-        ctx.in_nhwc = C > 1 and x.stride(1) == 1 and x.is_contiguous(memory_format=torch.channels_last)
+        ctx.in_nhwc = C > 1 and _is_nhwc(x)
         return out
 
     @staticmethod
@@ -545,8 +556,8 @@ def upsample_bilinear(x, scale, out_nchw=False):
     """F.interpolate(x, scale_factor=scale, mode='bilinear', align_corners=True) on the native kernels (forward and backward)
     for f32 GPU tensors with scale 2 or 4; torch otherwise.  The result keeps x's memory format unless out_nchw (the heads:
     full-resolution logits in the layout the losses and the post-network kernels read)."""
-    if ENABLED and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and scale in (2, 4) and x.shape[0] * x.shape[1] <= 65535:
-        nhwc = (not out_nchw) and x.shape[1] > 1 and x.stride(1) == 1 and x.is_contiguous(memory_format=torch.channels_last)
+    if ENABLED and _f32_cuda_4d(x, any_device=True) and scale in (2, 4) and x.shape[0] * x.shape[1] <= 65535:
+        nhwc = (not out_nchw) and x.shape[1] > 1 and _is_nhwc(x)
         if any(s < 0 for s in x.stride()) or x.stride(1) == 0:
             x = x.contiguous()
         return _UpBilinearFn.apply(x, int(scale), bool(nhwc))
@@ -575,7 +586,7 @@ class _GroupNormReLUFn(torch.autograd.Function):
         x, gamma, beta, stats = ctx.saved_tensors
         B, C, H, W = x.shape
         L = nat.lib()
-        gy = _channels_last(gy)
+        gy = _operand(gy)
         dx = torch.empty_like(x, memory_format=torch.channels_last)
         chunks = L.fpc_groupnorm4_relu_scratch_floats(B, H * W, C) // (B * C * 2)
         part = torch.empty((B, chunks, C, 2), dtype=torch.float32, device=x.device)
@@ -589,8 +600,8 @@ def groupnorm_relu(x, gn):
     """relu(gn(x)) for a torch.nn.GroupNorm `gn`: native on channel-last f32 GPU tensors whose groups are 4 channels wide
     (the decoder: GroupNorm(32, 128)), torch otherwise."""
     C, G = gn.num_channels, gn.num_groups
-    if (ENABLED and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and gn.affine and C == 4 * G and 256 % G == 0 and G <= 64
-            and x.shape[0] <= 65535 and x.stride(1) == 1 and x.is_contiguous(memory_format=torch.channels_last)):
+    if (ENABLED and _f32_cuda_4d(x, any_device=True) and gn.affine and C == 4 * G and 256 % G == 0 and G <= 64
+            and x.shape[0] <= 65535 and _is_nhwc(x)):      # (channel-last, with no alignment term, as before)
         return _GroupNormReLUFn.apply(x, gn.weight, gn.bias, G, gn.eps)
     return torch.relu(gn(x))
 
@@ -600,11 +611,6 @@ def groupnorm_relu(x, gn):
 # Off by default: on the batch-8 step the native path has fewer launches and less kernel time, but the step time did not move by
 # more than the spread between repeated runs (profiles/train_bn_step_kernels.txt).
 NATIVE_BN = bool(int(os.environ.get("FPC_TRAIN_NATIVE_BN", "0")))
-counters.update(bn_native=0, bn_torch=0)
-
-
-def _dense_nhwc(t):
-    return t.stride(1) == 1 and t.is_contiguous(memory_format=torch.channels_last) and t.data_ptr() % 16 == 0
 
 
 class _BatchNormActFn(torch.autograd.Function):
@@ -633,9 +639,7 @@ class _BatchNormActFn(torch.autograd.Function):
         B, C, H, W = x.shape
         P = B * H * W
         L = nat.lib()
-        gy = _channels_last(gy)
-        if gy.data_ptr() % 16:
-            gy = gy.clone(memory_format=torch.channels_last)
+        gy = _operand(gy, aligned=True)
         dx = torch.empty_like(x, memory_format=torch.channels_last) if ctx.needs_input_grad[0] else None
         dres = torch.empty_like(x, memory_format=torch.channels_last) if ctx.needs_input_grad[1] else None
         dgb = torch.empty((2, C), dtype=torch.float32, device=x.device)
@@ -656,12 +660,11 @@ def batchnorm_act(x, bn, res=None, relu=True, count_refusal=True):
     default) — and the caller runs the torch modules (counted as
     bn_torch unless the caller says it will ask again)."""
     ok = (ENABLED and NATIVE_BN and bn.training and bn.affine and bn.track_running_stats and bn.momentum is not None
-          and bn.running_mean is not None and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+          and bn.running_mean is not None and torch.is_tensor(x) and _f32_cuda_4d(x)
           and x.shape[1] % 4 == 0 and x.shape[1] == bn.num_features and 2 <= x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31 - 256
-          and _dense_nhwc(x) and x.device.index == torch.cuda.current_device()      # (the launches go to the current device's stream)
+          and _dense_nhwc(x)
           and (res is None or (relu and res.shape == x.shape and res.dtype == x.dtype and res.device == x.device and _dense_nhwc(res)))
-          and all(t.dtype == torch.float32 and t.device == x.device and t.is_contiguous() and t.data_ptr() % 16 == 0
-                  for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)))
+          and all(_f32_param(t, x.device) for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)))
     if not ok:
         counters["bn_torch"] += int(count_refusal)
         return None
@@ -675,7 +678,6 @@ def batchnorm_act(x, bn, res=None, relu=True, count_refusal=True):
 # Off by default: with it off the gate is SEModule's chain of torch ops, the add and the ReLU two more, forward and backward, as
 # before (DESIGN.md 4.2a''''').
 NATIVE_SE = bool(int(os.environ.get("FPC_TRAIN_NATIVE_SE", "0")))
-counters.update(se_fwd_native=0, se_bwd_native=0, se_torch=0)
 
 
 class _SEGateAddReLUFn(torch.autograd.Function):
@@ -709,9 +711,7 @@ class _SEGateAddReLUFn(torch.autograd.Function):
         B, C, H, W = x.shape
         Cr = w1.shape[0]
         L = nat.lib()
-        gy = _channels_last(gy)
-        if gy.data_ptr() % 16:
-            gy = gy.clone(memory_format=torch.channels_last)
+        gy = _operand(gy, aligned=True)
         need = ctx.needs_input_grad
         dx = torch.empty_like(x, memory_format=torch.channels_last)
         dres = torch.empty_like(x, memory_format=torch.channels_last) if need[1] else None
@@ -730,8 +730,7 @@ class _SEGateAddReLUFn(torch.autograd.Function):
 def _se_fc_ok(fc, cin, cout, dev):
     return (isinstance(fc, torch.nn.Conv2d) and fc.kernel_size == (1, 1) and fc.stride == (1, 1) and fc.padding == (0, 0)
             and fc.dilation == (1, 1) and fc.groups == 1 and fc.bias is not None and fc.in_channels == cin and fc.out_channels == cout
-            and all(t.dtype == torch.float32 and t.device == dev and t.is_contiguous() and t.data_ptr() % 16 == 0
-                    for t in (fc.weight, fc.bias)))
+            and _f32_param(fc.weight, dev) and _f32_param(fc.bias, dev))
 
 
 def se_gate_add_relu(x, se_module, res, act=None):
@@ -741,9 +740,8 @@ def se_gate_add_relu(x, se_module, res, act=None):
     convolutions with contiguous aligned f32 parameters, and nn.ReLU as BOTH the block's activation (act=None: the caller's is a
     plain ReLU) and the gate's (a test may have swapped either for a smooth activation).  None otherwise — never a layout copy to get here — and the caller runs the
     torch modules (counted in se_torch)."""
-    ok = (ENABLED and NATIVE_SE and torch.is_grad_enabled() and torch.is_tensor(x) and torch.is_tensor(res) and x.is_cuda
-          and x.dtype == torch.float32 and x.dim() == 4 and res.dtype == torch.float32 and res.device == x.device
-          and res.shape == x.shape and x.device.index == torch.cuda.current_device()
+    ok = (ENABLED and NATIVE_SE and torch.is_grad_enabled() and torch.is_tensor(x) and torch.is_tensor(res) and _f32_cuda_4d(x)
+          and res.dtype == torch.float32 and res.device == x.device and res.shape == x.shape
           and x.shape[1] % 64 == 0 and 64 <= x.shape[1] <= 8192 and 1 <= x.shape[0] <= 65535 and x.shape[2] >= 1 and x.shape[3] >= 1
           and x.numel() // 4 < 2 ** 32 - 4096 * 256 - 8 and _dense_nhwc(x) and _dense_nhwc(res)
           and (act is None or isinstance(act, torch.nn.ReLU)) and isinstance(getattr(se_module, "relu", None), torch.nn.ReLU)
