@@ -139,6 +139,10 @@ _SIGNATURES = {
     "fpc_se_gate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "fpc_se_scale_add_relu": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "fpc_maxpool3x3s2_ceil_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "fpc_dwconv3x3": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "fpc_conv1x1_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
+    "fpc_conv1x1_f32_form": (_i, [_i64, _i, _i]),
+    "fpc_stem3x3s2": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "fpc_se_gate_train": (_i, [_vp] * 9 + [_i, _i, _i, _i, _i, _vp]),
     "fpc_se_bwd_scratch_floats": (_sz, [_i, _i, _i, _i, _i]),
     "fpc_se_bwd": (_i, [_vp] * 15 + [_i, _i, _i, _i, _i, _vp]),

@@ -6,7 +6,8 @@
 // (encoder = ResNet BasicBlock x {2,2,2,2} or {3,4,6,3}, or Bottleneck x {3,4,6,3} / {3,4,23,3} / {3,8,36,3} whose 1x1 sites
 // may run on k_conv1x1 (pointwise.hip) and whose conv2, in the ResNeXt encoders, is a grouped 3x3 on k_conv3x3_grouped
 // (conv_grouped.hip), or the SE-ResNet Bottleneck x {3,4,6,3} / {3,4,23,3} / {3,8,36,3}: the stride on conv1, a dense 3x3 conv2 and the
-// squeeze-and-excitation gate of se.hip between bn3 and the residual add; four FPN decoders, merge "add";
+// squeeze-and-excitation gate of se.hip between bn3 and the residual add, or torchvision's MobileNetV2 features on the three kernels of
+// mobilenet.hip (below: "the MobileNetV2 encoder"); four FPN decoders, merge "add";
 // four 1x1 heads + x4 bilinear), see fastposecnn_amd/lib/backbone.py.  The plan owns no device
 // memory: packed weights, activations and split-K scratch live in one caller-provided workspace.
 // Launch order per frame (R18): stem conv, max-pool, 16 encoder convs (+3 downsample 1x1) with
@@ -61,6 +62,7 @@ struct EncoderDesc {
     int groups = 1, width = 64;   // Bottleneck: conv2's groups and torchvision's width_per_group (ResNeXt: 32 and 4 / 8); (1, 64) = ResNet
     int se = 0;                   // > 0: the SE-ResNet Bottleneck (pretrainedmodels.senet) with this reduction; expansion is 4 then
     int layers[4] = {};           // blocks per stage
+    bool mbv2 = false;            // torchvision's MobileNetV2 features (the MobileNetV2 encoder, below): none of the block kinds, expansion 0
     const BlockKind& kind() const { return se ? kSEBottleneck : expansion == 4 ? kBottleneck : kBasicBlock; }
     const char* stem_prefix() const { return se ? "encoder.layer0." : "encoder."; }      // torchvision's stem names, pretrainedmodels'
     // the SE-ResNet stem pool: no padding, ceil_mode (other windows, the same size on the even maps every plan has): its own max-pool launch, never the fused stem + pool
@@ -88,8 +90,20 @@ struct fpc_net {
     int c_stem = -1;
     // The encoder tape: every launch between the max-pool and the decoders, in launch order.  conv >= 0: that site from `in` to `out` with BatchNorm, `res`
     // (C > 0) and ReLU in its epilogue; conv < 0: an SE block's gate step on `out` in place, with the residual `res` and se_module's four parameters from p_se
-    struct Step { int conv; Act in, out; bool relu; Act res; int p_se; };
+    // mb >= 0: that op of the MobileNetV2 encoder (mops) from `in` to `out`, a 1x1 with the residual `res` (C > 0)
+    struct Step { int conv; Act in, out; bool relu; Act res; int p_se; int mb = -1; };
     std::vector<Step> tape;
+    // The MobileNetV2 encoder's ops: the stem, a depthwise 3x3 or a 1x1, each with BatchNorm folded into scale / shift and ReLU6 where
+    // act = 1.  One form each (mobilenet.hip): not PackedConv sites, not tuned, not surveyed; the weights are read in place.
+    enum MbKind { kMbStem, kMbDw, kMbPw };
+    struct MbOp { MbKind kind; int p_w, p_bn, Cin, Cout, stride, act; size_t scale_off, shift_off; long long howo; };
+    std::vector<MbOp> mops;
+    int add_mop(MbKind kind, const std::string& wname, int64_t wnumel, const std::string& bn, int Cin, int Cout, int stride, int act) {
+        MbOp o{kind, add_param(wname, wnumel), add_bn(bn, Cout), Cin, Cout, stride, act, 0, 0, 0};
+        o.scale_off = alloc(Cout); o.shift_off = alloc(Cout);
+        mops.push_back(o);
+        return (int)mops.size() - 1;
+    }
     struct Dec {
         int lat[4];               // p5, p4, p3, p2 (1x1, bias)
         int seg[7];               // s5.0 s5.1 s5.2 s4.0 s4.1 s3.0 s2.0
@@ -187,6 +201,9 @@ static void drop_graph(fpc_net* n) {
 static const char* kDecNames[4] = {"mask_decoder", "rotation_decoder", "translation_decoder", "scales_decoder"};
 static const char* kHeadNames[4] = {"segmentation_head", "rotation_head", "translation_head", "scales_head"};
 
+// the implicit GEMM's loader of a lateral site: 0 = the fast one (Cin a multiple of 32), 2 = Cin % 4 (k_conv_igemm's MODE 2)
+static int lateral_mode(const PackedConv& c) { return c.Cin % kConvBK == 0 ? 0 : 2; }
+
 // the plan of `n` (its encoder descriptor set) for (classes, B, H, W); owns `n` (deleted on failure)
 static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** out);
 
@@ -210,6 +227,8 @@ static const struct { const char* name; EncoderDesc desc; } kEncoders[] = {
     {"se_resnet50", {4, 1, 64, 16, {3, 4, 6, 3}}},
     {"se_resnet101", {4, 1, 64, 16, {3, 4, 23, 3}}},
     {"se_resnet152", {4, 1, 64, 16, {3, 8, 36, 3}}},
+    // the MobileNetV2 encoder (below); layers: the feature modules of smp's four last stages
+    {"mobilenet_v2", {0, 1, 64, 0, {2, 3, 7, 5}, true}},
 };
 
 extern "C" int fpc_net_create(const char* encoder, int classes, int B, int H, int W, fpc_net_t** out) {
@@ -248,6 +267,88 @@ extern "C" int fpc_net_create_encoder_se(const int* layers4, int reduction, int 
     return create({4, 1, 64, reduction}, layers4, classes, B, H, W, out);
 }
 
+// ---- the MobileNetV2 encoder: torchvision's mobilenet_v2().features as smp's MobileNetV2Encoder walks it.  features.0 is the 3x3 /
+// stride-2 stem (3 -> 32, BatchNorm, ReLU6); features.1 .. 17 are InvertedResidual blocks by the (t, c, n, s) table: an expand 1x1
+// inp -> t inp with BatchNorm and ReLU6 (absent where t = 1), a depthwise 3x3 with the block's stride, BatchNorm and ReLU6, a project
+// 1x1 to c channels with BatchNorm only, and the block's input added where the stride is 1 and inp = c (no activation behind it);
+// features.18 is the 1x1 320 -> 1280 with BatchNorm and ReLU6.  smp's stages end behind features.1 / 3 / 6 / 13 / 18: the last four
+// are c2 .. c5 of 24 / 32 / 96 / 1280 channels.  Parameters in state-dict order (conv weight, then BatchNorm's four), read in place.
+static const int kMbTable[7][4] = {{1, 16, 1, 1}, {6, 24, 2, 2}, {6, 32, 3, 2}, {6, 64, 4, 2}, {6, 96, 3, 1}, {6, 160, 3, 2}, {6, 320, 1, 1}};
+struct MbBlock { int expand, dw, proj, stage; };      // ops of fpc_net::mops (-1: the block has none); stage -1: in front of c2's
+
+static void mbv2_params(fpc_net* n, std::vector<MbBlock>& blocks, int featc[4]) {
+    const std::string f("encoder.features.");
+    n->add_mop(fpc_net::kMbStem, f + "0.0.weight", 32 * 27, f + "0.1", 3, 32, 2, 1);
+    int inp = 32, idx = 1;
+    for (const auto& row : kMbTable)
+        for (int i = 0; i < row[2]; ++i, ++idx) {
+            const int t = row[0], oup = row[1], stride = i == 0 ? row[3] : 1, hid = inp * t;
+            const std::string p = f + std::to_string(idx) + ".conv.";
+            MbBlock b{-1, -1, -1, idx < 2 ? -1 : idx < 4 ? 0 : idx < 7 ? 1 : idx < 14 ? 2 : 3};
+            const int k = t != 1 ? 1 : 0;      // the depthwise's place in `conv`
+            if (k) b.expand = n->add_mop(fpc_net::kMbPw, p + "0.0.weight", (int64_t)hid * inp, p + "0.1", inp, hid, 1, 1);
+            b.dw = n->add_mop(fpc_net::kMbDw, p + std::to_string(k) + ".0.weight", (int64_t)hid * 9, p + std::to_string(k) + ".1", hid, hid, stride, 1);
+            b.proj = n->add_mop(fpc_net::kMbPw, p + std::to_string(k + 1) + ".weight", (int64_t)oup * hid, p + std::to_string(k + 2), hid, oup, 1, 0);
+            blocks.push_back(b);
+            inp = oup;
+        }
+    blocks.push_back(MbBlock{-1, -1, n->add_mop(fpc_net::kMbPw, f + "18.0.weight", (int64_t)1280 * inp, f + "18.1", inp, 1280, 1, 1), 3});
+    featc[0] = 24; featc[1] = 32; featc[2] = 96; featc[3] = 1280;
+}
+
+// Its buffers and tape.  Per stage: the largest expanded tensor, the largest depthwise output and two outputs the blocks take in turn
+// (a block's input is its residual, so it never writes over it); a stage's last output stays: a_feat.
+static void mbv2_buffers(fpc_net* n, const std::vector<MbBlock>& blocks) {
+    const size_t B = (size_t)n->B;
+    n->a_stem = n->alloc_act(n->H / 2, n->W / 2, 32);
+    n->mops[0].howo = (long long)n->a_stem.H * n->a_stem.W;
+    n->tape.push_back({-1, n->a_img4, n->a_stem, false, Act(), -1, 0});
+    Act cur = n->a_stem;
+    for (int stage = -1; stage < 4; ++stage) {
+        size_t fe = 0, fd = 0, fy = 0;
+        int h = cur.H, w = cur.W, count = 0;
+        for (const MbBlock& b : blocks) {
+            if (b.stage != stage) continue;
+            ++count;
+            if (b.expand >= 0) fe = std::max(fe, (size_t)h * w * n->mops[b.expand].Cout);
+            if (b.dw >= 0) {
+                h = conv_out(h, 3, n->mops[b.dw].stride, 1); w = conv_out(w, 3, n->mops[b.dw].stride, 1);
+                fd = std::max(fd, (size_t)h * w * n->mops[b.dw].Cout);
+            }
+            fy = std::max(fy, (size_t)h * w * n->mops[b.proj].Cout);
+        }
+        Act E, D, Y[2];
+        if (fe) E.off = n->alloc(B * fe);
+        if (fd) D.off = n->alloc(B * fd);
+        Y[0].off = n->alloc(B * fy);
+        if (count > 1) Y[1].off = n->alloc(B * fy);
+        int turn = 0;
+        auto view = [&](Act t, int th, int tw, int op) {
+            t.H = th; t.W = tw; t.C = n->mops[op].Cout;
+            n->mops[op].howo = (long long)th * tw;
+            return t;
+        };
+        for (const MbBlock& b : blocks) {
+            if (b.stage != stage) continue;
+            const Act in = cur;
+            Act x = cur;
+            if (b.expand >= 0) { const Act e = view(E, x.H, x.W, b.expand); n->tape.push_back({-1, x, e, false, Act(), -1, b.expand}); x = e; }
+            if (b.dw >= 0) {
+                const int st = n->mops[b.dw].stride;
+                const Act d = view(D, conv_out(x.H, 3, st, 1), conv_out(x.W, 3, st, 1), b.dw);
+                n->tape.push_back({-1, x, d, false, Act(), -1, b.dw});
+                x = d;
+            }
+            const Act y = view(Y[turn], x.H, x.W, b.proj);
+            turn = count > 1 ? turn ^ 1 : 0;
+            const bool res = b.dw >= 0 && n->mops[b.dw].stride == 1 && in.C == y.C;
+            n->tape.push_back({-1, x, y, false, res ? in : Act(), -1, b.proj});
+            cur = y;
+        }
+        if (stage >= 0) n->a_feat[stage] = cur;
+    }
+}
+
 static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** out) {
     n->classes = classes; n->B = B; n->H = H; n->W = W;
     {   // merge + head in two passes (merge_split.hip) unless FPC_MERGE_SPLIT=0; read once, here
@@ -263,13 +364,17 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
     const EncoderDesc& enc = n->enc;
     const BlockKind& kind = enc.kind();
     const std::string stem(enc.stem_prefix());
-    n->c_stem = n->add_conv(stem + "conv1.weight", 3, 64, 7, 2, 3, (stem + "bn1").c_str(), nullptr, 4, 8);     // NHWC4 pixels, 8 taps per row
     const int planes[4] = {64, 128, 256, 512};
     const int e = enc.expansion;
+    int featc[4] = {64 * e, 128 * e, 256 * e, 512 * e};      // channels of c2 .. c5
+    const int stages = enc.mbv2 ? 0 : 4;                     // stages of the block kinds above
+    std::vector<MbBlock> mb;
+    if (enc.mbv2) mbv2_params(n, mb, featc);
+    else n->c_stem = n->add_conv(stem + "conv1.weight", 3, 64, 7, 2, 3, (stem + "bn1").c_str(), nullptr, 4, 8);     // NHWC4 pixels, 8 taps per row
     struct Block { int conv[3], ds, p_se, stride, ch[kBufCount]; };      // a block's sites as created here, for the buffers and the tape below
     std::vector<Block> blocks[4];
     int inpl = 64;
-    for (int L = 0; L < 4; ++L)
+    for (int L = 0; L < stages; ++L)
         for (int bi = 0; bi < enc.layers[L]; ++bi) {
             const int mid = planes[L] * enc.width / 64 * enc.groups, C = e * planes[L];      // (mid: planes[L] but in the ResNeXt encoders)
             Block blk{{-1, -1, -1}, -1, -1, (bi == 0 && L > 0) ? 2 : 1, {0, inpl, mid, mid, C, C, C}};      // (channels by Buf)
@@ -300,8 +405,8 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
     for (int d = 0; d < 4; ++d) {
         std::string D(kDecNames[d]);
         fpc_net::Dec& dc = n->dec[d];
-        dc.lat[0] = n->add_conv(D + ".p5.weight", 512 * e, 256, 1, 1, 0, nullptr, (D + ".p5.bias").c_str());
-        const int skipc[3] = {256 * e, 128 * e, 64 * e};
+        dc.lat[0] = n->add_conv(D + ".p5.weight", featc[3], 256, 1, 1, 0, nullptr, (D + ".p5.bias").c_str());
+        const int skipc[3] = {featc[2], featc[1], featc[0]};
         for (int i = 0; i < 3; ++i) {
             snprintf(buf, sizeof(buf), "%s.p%d.skip_conv", kDecNames[d], 4 - i);
             std::string p(buf);
@@ -349,7 +454,7 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
             c.h3_off = n->alloc(h3_packed_floats(c.Npad, c.Kpad));
         }
     }
-    n->stem_h3_off = n->alloc(h3_packed_floats(n->convs[n->c_stem].Npad, n->convs[n->c_stem].Kpad));      // every encoder shares the stem
+    if (n->c_stem >= 0) n->stem_h3_off = n->alloc(h3_packed_floats(n->convs[n->c_stem].Npad, n->convs[n->c_stem].Kpad));      // every encoder with the 7x7 stem shares it
     n->zeros_off = n->alloc(64);
     n->tickets_off = n->alloc(kConvTickets);
     n->packed_floats = n->bump;
@@ -357,12 +462,16 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
     // ---- activations
     int h1 = conv_out(H, 7, 2, 3), w1 = conv_out(W, 7, 2, 3);
     n->a_img4 = n->alloc_act(H, W, 4);
-    n->a_stem = n->alloc_act(h1, w1, 64);
-    int hp = enc.ceil_pool() ? h1 / 2 : conv_out(h1, 3, 2, 1), wp = enc.ceil_pool() ? w1 / 2 : conv_out(w1, 3, 2, 1);
-    n->a_pool = n->alloc_act(hp, wp, 64);
+    if (enc.mbv2) {
+        mbv2_buffers(n, mb);      // (no pooled tensor: a_pool stays empty)
+    } else {
+        n->a_stem = n->alloc_act(h1, w1, 64);
+        int hp = enc.ceil_pool() ? h1 / 2 : conv_out(h1, 3, 2, 1), wp = enc.ceil_pool() ? w1 / 2 : conv_out(w1, 3, 2, 1);
+        n->a_pool = n->alloc_act(hp, wp, 64);
+    }
     // the blocks' buffers and the encoder tape
     Act cur = n->a_pool;
-    for (int L = 0; L < 4; ++L) {
+    for (int L = 0; L < stages; ++L) {
         Act b[kBufCount], y[2];
         for (size_t bi = 0; bi < blocks[L].size(); ++bi) {
             const Block& blk = blocks[L][bi];
@@ -439,12 +548,17 @@ static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** o
         }
         if (need > n->splitk_floats) n->splitk_floats = need;
     };
-    plan(n->c_stem, h1 * w1, 1);
+    if (n->c_stem >= 0) plan(n->c_stem, h1 * w1, 1);
     // (the orientation rule is asked with the step's own output size.  A Winograd site has stride 1 (PackedConv::wino_ok), so that is
     // the stage's output size at every site the mark matters for: a strided conv1, whose input is larger, is never one)
     for (const fpc_net::Step& st : n->tape)
         if (st.conv >= 0) { plan(st.conv, st.out.H * st.out.W, 1); oriented(st.conv, st.out.H, st.out.W); }
-    for (int i = 0; i < 4; ++i) plan(n->dec[0].lat[i], fh[3 - i] * fw[3 - i], 4);
+    for (int i = 0; i < 4; ++i) {
+        plan(n->dec[0].lat[i], fh[3 - i] * fw[3 - i], 4);
+        // a lateral whose channels the fast loader does not take (c2 of the MobileNetV2 encoder: 24) runs on the Cin % 4 loader
+        // (lateral_mode), through the same grouped launch with the top-down addend: what that loader asks of the site, checked here
+        if (lateral_mode(n->convs[n->dec[0].lat[i]]) == 2 && (featc[3 - i] % 4 != 0 || ((fh[3 - i] | fw[3 - i]) & 1))) { delete n; return FPC_EINVAL; }
+    }
     for (int i = 0; i < 7; ++i) {
         int HoWo = fh[seg_level[i]] * fw[seg_level[i]];
         plan(n->dec[0].seg[i], HoWo, 4);
@@ -482,9 +596,11 @@ static int pack_h3_images(fpc_net* n, hipStream_t s) {
             int rc = launch_pack_weight_h3(n->pptr[c.p_w], n->ws + c.h3_off, c.Cout, c.Cin, c.Cinp, c.Kh, c.Kw, c.Kwp, c.Npad, c.Kpad, s);
             if (rc) return rc;
         }
-    const PackedConv& st = n->convs[n->c_stem];
-    int rc = launch_pack_weight_h3(n->pptr[st.p_w], n->ws + n->stem_h3_off, st.Cout, st.Cin, st.Cinp, st.Kh, st.Kw, st.Kwp, st.Npad, st.Kpad, s);
-    if (rc) return rc;
+    if (n->c_stem >= 0) {
+        const PackedConv& st = n->convs[n->c_stem];
+        int rc = launch_pack_weight_h3(n->pptr[st.p_w], n->ws + n->stem_h3_off, st.Cout, st.Cin, st.Cinp, st.Kh, st.Kw, st.Kwp, st.Npad, st.Kpad, s);
+        if (rc) return rc;
+    }
     n->h3_packed = true;
     return FPC_OK;
 }
@@ -616,6 +732,11 @@ extern "C" int fpc_net_load_params(fpc_net_t* n, const float* const* params, int
             const int rc = pack_fold_images(n, d, s);
             if (rc) return rc;
         }
+    for (const fpc_net::MbOp& o : n->mops) {      // the MobileNetV2 encoder's ops: the folded BatchNorm (the weights are read in place)
+        const int rc = launch_fold_bn(n->pptr[o.p_bn], n->pptr[o.p_bn + 1], n->pptr[o.p_bn + 2], n->pptr[o.p_bn + 3], 1e-5f, o.Cout,
+                                      n->ws + o.scale_off, n->ws + o.shift_off, s);
+        if (rc) return rc;
+    }
     n->loaded = true;
     return FPC_OK;
 }
@@ -798,7 +919,7 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
     auto nhwc = [&](const Act& t, long long& sb, long long& sh, long long& sw, long long& sc) {
         sc = 1; sw = t.C; sh = (long long)t.W * t.C; sb = (long long)t.H * sh;
     };
-    {
+    if (n->c_stem >= 0) {
         const PackedConv& c = n->convs[n->c_stem];
         // The 7x7/2 stem as a 7x1 convolution over "pixels" of 8 x 4 channels: one K-step = one kernel row = the 8
         // consecutive 16-byte pixels starting at wi0, which are 128 contiguous bytes of the NHWC4 image — the fast
@@ -849,6 +970,14 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
     };
     for (const fpc_net::Step& st : n->tape) {
         const float* res = st.res.C ? ws + st.res.off : nullptr;
+        if (st.mb >= 0) {      // an op of the MobileNetV2 encoder
+            const fpc_net::MbOp& o = n->mops[st.mb];
+            const float *w = n->pptr[o.p_w], *sc = ws + o.scale_off, *sh = ws + o.shift_off;
+            if (o.kind == fpc_net::kMbStem) FPC_TRY(launch_stem3x3s2(ws + st.in.off, w, sc, sh, ws + st.out.off, B, st.in.H, st.in.W, s));
+            else if (o.kind == fpc_net::kMbDw) FPC_TRY(launch_dwconv3x3(ws + st.in.off, w, sc, sh, ws + st.out.off, B, st.in.H, st.in.W, st.in.C, o.stride, o.act, s));
+            else FPC_TRY(launch_conv1x1_f32(ws + st.in.off, w, sc, sh, res, ws + st.out.off, (long long)B * st.in.H * st.in.W, o.Cin, o.Cout, o.act, s));
+            continue;
+        }
         if (st.conv >= 0) { FPC_TRY(enc_conv(st.conv, st.in, st.out, st.relu, res)); continue; }
         // the gate of an SE block: from Y's channel means, then Y = relu(Y * gate + residual) in place
         const Act& Y = st.out;
@@ -868,7 +997,7 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
         long long sb, sh, sw, sc;
         nhwc(src, sb, sh, sw, sc);
         int ci0 = n->dec[0].lat[i];
-        fill_conv_args(n, a, n->convs[ci0], n->cplan[ci0], src.H, src.W, src.H, src.W, sb, sh, sw, sc, false, 0);
+        fill_conv_args(n, a, n->convs[ci0], n->cplan[ci0], src.H, src.W, src.H, src.W, sb, sh, sw, sc, false, lateral_mode(n->convs[ci0]));
         for (int d = 0; d < 4; ++d) {
             const PackedConv& c = n->convs[n->dec[d].lat[i]];
             a.p[d] = ConvPtrs{ws + src.off, ws + c.w_off, ws + n->a_p[d][i].off, nullptr, n->pptr[c.p_bias], nullptr,
@@ -1252,6 +1381,7 @@ extern "C" int fpc_net_force_direct_h3(fpc_net_t* n, int on) {
 // when the plan changed, 0 when it was already so, or a negative code.  Drops the recorded graph.
 extern "C" int fpc_net_force_stem_pool(fpc_net_t* n, int on) {
     if (!n || on < 0 || on > 1 || (on && !n->h3_packed)) return FPC_EINVAL;
+    if (n->c_stem < 0) return FPC_EINVAL;      // the MobileNetV2 encoder: no 7x7 stem and no max-pool, whatever `on` is
     if (on && n->enc.ceil_pool()) return FPC_EINVAL;      // the SE-ResNet stem pool has no padding: the fused launch computes another pool
     if (on && ((n->a_stem.H & 1) || (n->a_stem.W & 63) || (long long)n->H * n->W * 16 >= (1LL << 31))) return FPC_EINVAL;
     ConvPlan& p = n->cplan[n->c_stem];
@@ -1311,6 +1441,10 @@ extern "C" int fpc_net_flops(const fpc_net_t* n, double* out3) {
         direct += f;
         if (n->cplan[i].wino) { executed += f / 2.25; wino += f; } else executed += f;
     }
+    for (const fpc_net::MbOp& o : n->mops) {      // the MobileNetV2 encoder's ops: 27 (stem), 9 (depthwise) or Cin products per output
+        const double f = 2.0 * n->B * (double)o.howo * o.Cout * (o.kind == fpc_net::kMbStem ? 27 : o.kind == fpc_net::kMbDw ? 9 : o.Cin);
+        direct += f; executed += f;
+    }
     for (int d = 0; d < 4; ++d)      // the 1x1 heads run inside k_merge_head
         direct += 2.0 * n->B * (double)n->a_low[d].H * n->a_low[d].W * 128.0 * n->dec[d].head_ch,
         executed += 2.0 * n->B * (double)n->a_low[d].H * n->a_low[d].W * 128.0 * n->dec[d].head_ch;
@@ -1325,10 +1459,10 @@ extern "C" int fpc_net_tensor(const fpc_net_t* n, const char* name, const float*
     Act t;
     bool ok = false;
     if (!strcmp(name, "stem")) {
-        if (n->cplan[n->c_stem].pool) return FPC_EINVAL;      // fused with the max-pool: never written
+        if (n->c_stem >= 0 && n->cplan[n->c_stem].pool) return FPC_EINVAL;      // fused with the max-pool: never written
         t = n->a_stem; ok = true;
     }
-    else if (!strcmp(name, "pool")) { t = n->a_pool; ok = true; }
+    else if (!strcmp(name, "pool")) { t = n->a_pool; ok = n->a_pool.C > 0; }      // (the MobileNetV2 encoder has none)
     else if (name[0] == 'c' && name[1] >= '2' && name[1] <= '5' && !name[2]) { t = n->a_feat[name[1] - '2']; ok = true; }
     else if (name[0] == 'd' && name[1] >= '0' && name[1] <= '3' && name[2] == '.') {
         int d = name[1] - '0';

@@ -324,6 +324,17 @@ inline bool se_shape_ok(int B, int H, int W, int C) {
     return B >= 1 && B <= 65535 && H >= 1 && W >= 1 && C >= 64 && C % 64 == 0 && C <= kSeMaxC && (long long)H * W < (1LL << 31) &&
            (long long)B * H * W * (C / 4) < (1LL << 32) - 4096LL * 256 - 8;      // (xcd_walk's 32-bit walk: launch_maxpool3x3s2's bound)
 }
+// mobilenet.hip: the MobileNetV2 encoder's kernels.  Dense channel-last f32, BatchNorm folded into scale / shift, act 1 = ReLU6.
+// stem: in4 [B][Hi][Wi][4] -> out [B][(Hi - 1) / 2 + 1][(Wi - 1) / 2 + 1][32] with w [32][3][3][3] and ReLU6; depthwise: w [C][1][3][3],
+// C % 4 == 0, stride 1 or 2; 1x1: out [M][Cout] = act(scale . in [M][Cin] w[Cout][Cin]^T + shift) (+ res, only with act 0) on exact
+// f32 matrix products, Cin % 8 == 0 (<= 1024), Cout % 8 == 0 (<= 2048)
+int launch_stem3x3s2(const float* in4, const float* w, const float* scale, const float* shift, float* out, int B, int Hi, int Wi,
+                     hipStream_t s);
+int launch_dwconv3x3(const float* in, const float* w, const float* scale, const float* shift, float* out, int B, int Hi, int Wi, int C,
+                     int stride, int act, hipStream_t s);
+int launch_conv1x1_f32(const float* in, const float* w, const float* scale, const float* shift, const float* res, float* out, long long M,
+                       int Cin, int Cout, int act, hipStream_t s);
+int conv1x1_f32_tiles(long long M, int Cout);      // 0: 16 x 16 tiles (few rows), else channel tiles of 32 per wave: a function of the shape alone
 int launch_gn_finalize(const GnFinArgs& a, int groups, hipStream_t s);
 int launch_gn_relu_up2(const GnUpArgs& a, int groups, hipStream_t s);
 int launch_merge_head(const MergeHeadArgs& a, int groups, hipStream_t s);

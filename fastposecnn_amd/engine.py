@@ -29,11 +29,14 @@ class NetEngine:
         h = ctypes.c_void_p()
         from fastposecnn_amd.lib import backbone
         name = model.encoder.name
-        block, layers = backbone.encoder_layout(name)
-        groups, width = backbone.encoder_groups(name)
-        reduction = backbone.encoder_reduction(name)
+        mobilenet = backbone.encoder_family(name) == "mobilenet_v2"      # a plan fpc_net_create builds by name, no descriptor
+        block, layers = (0, [0] * 4) if mobilenet else backbone.encoder_layout(name)
+        groups, width = (1, 64) if mobilenet else backbone.encoder_groups(name)
+        reduction = 0 if mobilenet else backbone.encoder_reduction(name)
         arr, tail = (ctypes.c_int * 4)(*layers), (self.classes, B, H, W, ctypes.byref(h))
-        if reduction:       # SE-ResNet: the Bottleneck with the stride on conv1 and the squeeze-and-excitation gate
+        if mobilenet:
+            nat.check(L.fpc_net_create(name.encode(), *tail), "fpc_net_create")
+        elif reduction:     # SE-ResNet: the Bottleneck with the stride on conv1 and the squeeze-and-excitation gate
             nat.check(L.fpc_net_create_encoder_se(arr, reduction, *tail), "fpc_net_create_encoder_se")
         elif groups > 1:    # ResNeXt: Bottleneck with a grouped conv2
             nat.check(L.fpc_net_create_encoder_ex(block, arr, groups, width, *tail), "fpc_net_create_encoder_ex")

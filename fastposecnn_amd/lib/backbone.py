@@ -18,6 +18,9 @@ Structure (encoder_depth = 5, FPN, merge "add"):
 The SE-ResNet encoders (se_resnet50 / 101 / 152) are smp's SENetEncoder over pretrainedmodels.senet, restated the same way
 (neither package is here: parity unpinned): encoder.layer0.{conv1,bn1,relu1,pool}, SEResNetBottleneck blocks with
 se_module.fc1 / fc2, the same six feature levels.
+The MobileNetV2 encoder (mobilenet_v2) is smp's MobileNetV2Encoder over torchvision.models.mobilenet_v2, restated the same way
+(neither package is here: parity unpinned): encoder.features.0 .. 18 without the classifier, InvertedResidual blocks with a `conv`
+Sequential, ReLU6, the six feature levels behind the input, features.1 / 3 / 6 / 13 / 18.
 state_dict names follow smp: encoder.conv1.weight, encoder.layer1.0.conv1.weight, ...,
 <dec>.p5.weight, <dec>.p4.skip_conv.weight, <dec>.seg_blocks.0.block.0.block.0.weight (conv),
 ...block.1.weight (GroupNorm), <head>.0.weight.
@@ -214,6 +217,15 @@ _ENCODERS = {"resnet18": (BasicBlock, [2, 2, 2, 2], 1, 64, 0), "resnet34": (Basi
              "se_resnet152": (SEResNetBottleneck, [3, 8, 36, 3], 1, 64, 16)}
 
 
+def encoder_family(name):
+    """The one look-up the engine switches on: "mobilenet_v2" for the encoder fpc_net_create builds by that name, "resnet" for every
+    encoder that encoder_layout / encoder_groups / encoder_reduction describe; KeyError for a name this package does not build."""
+    if name == MobileNetV2Encoder.NAME:
+        return "mobilenet_v2"
+    _ENCODERS[name]
+    return "resnet"
+
+
 def encoder_layout(name):
     """(block expansion, blocks per stage) of encoder `name`: the descriptor fpc_net_create_encoder takes."""
     block, layers = _ENCODERS[name][:2]
@@ -249,7 +261,7 @@ class _Encoder(nn.Module):
     def __init__(self, name, in_channels, depth):
         super().__init__()
         if name not in _ENCODERS or bool(_ENCODERS[name][4]) != self._gated:
-            raise KeyError(f"encoder {name!r} not available (have {sorted(_ENCODERS)})")
+            raise KeyError(f"encoder {name!r} not available (have {sorted(_ENCODERS) + ['mobilenet_v2']})")
         block, layers, groups, width, reduction = _ENCODERS[name]
         self.name = name
         self._depth = depth
@@ -320,6 +332,80 @@ class SENetEncoder(_Encoder):
         return self.layer0.conv1, self.layer0.bn1, self.layer0.relu1, self.layer0.pool
 
 
+class ConvBNReLU6(nn.Sequential):
+    """torchvision's ConvBNReLU / Conv2dNormActivation as MobileNetV2 uses it: conv (no bias, padding (k - 1) / 2) -> BatchNorm ->
+    ReLU6, children 0 / 1 / 2.  The activation is a child module: a test may swap it."""
+
+    def __init__(self, inp, oup, kernel_size=3, stride=1, groups=1):
+        super().__init__(Conv2d(inp, oup, kernel_size, stride, (kernel_size - 1) // 2, groups=groups, bias=False),
+                         BatchNorm2d(oup), nn.ReLU6(inplace=True))
+
+
+class InvertedResidual(nn.Module):
+    """torchvision.models.mobilenetv2.InvertedResidual: `conv` = [expand 1x1 + BN + ReLU6 (absent where expand_ratio = 1)], the
+    depthwise 3x3 with the stride (groups = hidden) + BN + ReLU6, the project 1x1 without bias, its BN; the input is added where the
+    stride is 1 and inp = oup, with no activation behind the add.  In the training step the dense 1x1 sites and the BatchNorms run
+    on the native kernels lib/train_conv.py already has (Conv2d / BatchNorm2d above); the depthwise convolution and ReLU6 are torch's."""
+
+    def __init__(self, inp, oup, stride, expand_ratio):
+        super().__init__()
+        if stride not in (1, 2):
+            raise ValueError(f"stride should be 1 or 2 instead of {stride}")
+        self.stride = stride
+        hidden = int(round(inp * expand_ratio))
+        self.use_res_connect = stride == 1 and inp == oup
+        layers = []
+        if expand_ratio != 1:
+            layers.append(ConvBNReLU6(inp, hidden, kernel_size=1))
+        layers += [ConvBNReLU6(hidden, hidden, stride=stride, groups=hidden), Conv2d(hidden, oup, 1, 1, 0, bias=False), BatchNorm2d(oup)]
+        self.conv = nn.Sequential(*layers)
+        self.out_channels = oup
+
+    def forward(self, x):
+        return x + self.conv(x) if self.use_res_connect else self.conv(x)
+
+
+class MobileNetV2Encoder(nn.Module):
+    """smp's MobileNetV2Encoder: torchvision's MobileNetV2 (width 1.0, round_nearest 8) without its classifier, returning 6 feature
+    levels: the input and the outputs of features[:2], [2:4], [4:7], [7:14], [14:].  state_dict names are torchvision's
+    (features.0.0.weight, features.2.conv.1.1.running_var, features.18.1.bias)."""
+    NAME = "mobilenet_v2"
+    # (t, c, n, s): expansion, output channels, blocks, stride of the first block
+    SETTING = ((1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1), (6, 160, 3, 2), (6, 320, 1, 1))
+    STAGES = (2, 4, 7, 14, 19)      # smp: the feature level i + 1 is the output of features[STAGES[i] - 1]
+
+    def __init__(self, name="mobilenet_v2", in_channels=3, depth=5):
+        super().__init__()
+        if name != self.NAME:
+            raise KeyError(f"encoder {name!r} not available (have {sorted(_ENCODERS) + [self.NAME]})")
+        self.name = name
+        self._depth = depth
+        self.out_channels = (in_channels, 16, 24, 32, 96, 1280)
+        features = [ConvBNReLU6(in_channels, 32, stride=2)]
+        inp = 32
+        for t, c, n, s in self.SETTING:
+            for i in range(n):
+                features.append(InvertedResidual(inp, c, s if i == 0 else 1, t))
+                inp = c
+        features.append(ConvBNReLU6(inp, 1280, kernel_size=1))
+        self.features = nn.Sequential(*features)
+        # torchvision's initialisation (a checkpoint or a weights file overwrites it)
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out")
+            elif isinstance(m, nn.BatchNorm2d):
+                nn.init.ones_(m.weight)
+                nn.init.zeros_(m.bias)
+
+    def forward(self, x):
+        feats = [x]
+        for i, f in enumerate(self.features):
+            x = f(x)
+            if i + 1 in self.STAGES:
+                feats.append(x)
+        return feats
+
+
 _WARNED_WEIGHTS = set()
 
 
@@ -330,12 +416,14 @@ def get_encoder(name, in_channels=3, depth=5, weights=None):
     F/config.py).  There is no network here, so pretrained weights come from a local file:
     `FPC_ENCODER_WEIGHTS_DIR/<name>.pth` (or `FPC_ENCODER_WEIGHTS=<file>`) holding the torchvision ResNet state
     dict (keys conv1.weight, bn1.*, layer1.0.conv1.weight, ...; fc.* is dropped, as smp does) or, for an SE-ResNet, the
-    pretrainedmodels one (layer0.conv1.weight, ..., layerN.i.se_module.fc1.bias; last_linear.* is dropped).  When `weights` is
+    pretrainedmodels one (layer0.conv1.weight, ..., layerN.i.se_module.fc1.bias; last_linear.* is dropped) or, for mobilenet_v2,
+    torchvision's (features.0.0.weight, ..., features.18.1.running_var; classifier.* is dropped).  When `weights` is
     requested and no file is configured the encoder stays randomly initialised and a warning says so once per
     encoder — a checkpoint loaded afterwards (load_from_ckpt) overwrites the encoder anyway."""
     import logging
     import os
-    enc = (SENetEncoder if name in _ENCODERS and _ENCODERS[name][4] else ResNetEncoder)(name, in_channels=in_channels, depth=depth)
+    cls = MobileNetV2Encoder if name == MobileNetV2Encoder.NAME else SENetEncoder if name in _ENCODERS and _ENCODERS[name][4] else ResNetEncoder
+    enc = cls(name, in_channels=in_channels, depth=depth)
     enc.requested_weights = weights
     enc.loaded_weights = None
     if weights is not None:
@@ -345,7 +433,7 @@ def get_encoder(name, in_channels=3, depth=5, weights=None):
         if path:
             import torch
             sd = torch.load(path, map_location="cpu")
-            sd = {k: v for k, v in sd.items() if not k.startswith(("fc.", "last_linear."))}
+            sd = {k: v for k, v in sd.items() if not k.startswith(("fc.", "last_linear.", "classifier."))}
             enc.load_state_dict(sd)                  # strict: a wrong file fails loudly
             enc.loaded_weights = path
         elif (name, weights) not in _WARNED_WEIGHTS:

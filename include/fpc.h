@@ -59,6 +59,7 @@ extern "C" {
  * and the device PNG decode (fpc_inflate_host, fpc_png_pack_bytes, fpc_png_pack_batch, fpc_png_decode_device and its _workspace_bytes):
  * and the SE-ResNet encoders (fpc_net_create_encoder_se, fpc_se_pool_slabs, fpc_se_scratch_floats, fpc_se_gate, fpc_se_scale_add_relu, fpc_maxpool3x3s2_ceil_fwd):
  * and their gate in the training step (fpc_se_gate_train, fpc_se_bwd_scratch_floats, fpc_se_bwd):
+ * and the MobileNetV2 encoder (fpc_net_create's "mobilenet_v2", fpc_dwconv3x3, fpc_conv1x1_f32, fpc_conv1x1_f32_form, fpc_stem3x3s2):
  * additions only, every earlier entry point keeps its behaviour. */
 #define FPC_ABI_VERSION 11
 
@@ -858,6 +859,34 @@ int fpc_se_gate(const float* x, const float* w1, const float* b1, const float* w
 int fpc_se_scale_add_relu(const float* x, const float* gate, const float* res, float* y, int B, int H, int W, int C,
                           fpc_stream_t stream);
 int fpc_maxpool3x3s2_ceil_fwd(const float* x, float* y, int B, int Hi, int Wi, int C, fpc_stream_t stream);
+
+/* ---- The MobileNetV2 encoder's kernels (csrc/mobilenet.hip), stand-alone.  fpc_net_create("mobilenet_v2", ...) builds the plan that
+ * runs them: torchvision's MobileNetV2 features as smp wraps it (F/lib/pose_regressor.py:608-613 through smp.encoders.get_encoder),
+ * replacing cuDNN's depthwise and 1x1 convolutions and aten's BatchNorm / ReLU6 at inference.  Such a plan's encoder is the stem,
+ * 17 depthwise, 16 expand, 17 project launches and the last 1x1; these ops have one form each: they are not convolution sites
+ * (fpc_net_conv_count counts the decoders' alone), are not autotuned, and the activation-range survey and guard cover only the
+ * decoder sites of such a plan — the three kernels take any finite f32.  fpc_net_force_stem_pool is refused on it,
+ * fpc_net_force_fold(net, 1) too, fpc_net_force_direct_h3 changes 0 sites; the p2 lateral (24 channels) runs on the implicit GEMM's
+ * Cin % 4 loader with the top-down addend in its epilogue.
+ * All three: dense channel-last f32, every pointer non-NULL and 16-byte aligned (FPC_EINVAL otherwise), per-channel scale / shift =
+ * the folded BatchNorm, act 0 = none, 1 = ReLU6 min(max(v, 0), 6); fixed summation order, no atomics: bit-identical run to run.
+ * fpc_dwconv3x3 (k_dwconv3x3): depthwise 3x3, pad 1, stride 1 or 2: in [B][Hi][Wi][C], w torch's [C][1][3][3] read in place,
+ *   out [B][(Hi - 1) / stride + 1][(Wi - 1) / stride + 1][C].  Refused: B < 1, C < 4 or C % 4 != 0, any other stride or act.
+ * fpc_conv1x1_f32 (k_conv1x1_f32): out[m][n] = act(scale[n] sum_k in[m][k] w[n][k] + shift[n]) (+ res[m][n]) over M pixel rows,
+ *   w torch's [Cout][Cin][1][1], exact f32 products on v_mfma_f32_32x32x2_f32 with f32 accumulation.  Cin % 8 == 0, 8 .. 1024;
+ *   Cout % 8 == 0, 8 .. 2048; res may be NULL and is added behind the affine, with no activation: res with act != 0 is refused.
+ *   fpc_conv1x1_f32_form: the form a shape runs on (host arithmetic; FPC_EINVAL for a refused shape): 0 = 16 x 16 tiles on
+ *   v_mfma_f32_16x16x4_f32 where M / 32 x Cout / 32 (rounded up) is below 1024, else 1 / 2 / 3 / 5 = that many 32-channel tiles per
+ *   wave on 32 x 32 tiles.  The summation order depends on the form, i.e. on the shape alone.
+ * fpc_stem3x3s2 (k_stem3x3s2): the dense 3x3 / stride 2 / pad 1 stem over fpc_image_nhwc4's image [B][Hi][Wi][4] with w [32][3][3][3]
+ *   and ReLU6: out [B][(Hi - 1) / 2 + 1][(Wi - 1) / 2 + 1][32].  Cout must be 32. */
+int fpc_dwconv3x3(const float* in, const float* w, const float* scale, const float* shift, float* out, int B, int Hi, int Wi, int C,
+                  int stride, int act, fpc_stream_t stream);
+int fpc_conv1x1_f32(const float* in, const float* w, const float* scale, const float* shift, const float* res, float* out, int64_t M,
+                    int Cin, int Cout, int act, fpc_stream_t stream);
+int fpc_conv1x1_f32_form(int64_t M, int Cin, int Cout);
+int fpc_stem3x3s2(const float* in4, const float* w, const float* scale, const float* shift, float* out, int B, int Hi, int Wi, int Cout,
+                  fpc_stream_t stream);
 
 /* ---- The same gate in the training step (csrc/se_train.hip; lib/train_conv.se_gate_add_relu behind FPC_TRAIN_NATIVE_SE=1).  They
  * replace autograd through pretrainedmodels.senet.SEModule and through the add / ReLU of SEResNetBottleneck.forward (aten forward
