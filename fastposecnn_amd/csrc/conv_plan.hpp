@@ -1,6 +1,6 @@
 // conv_plan.hpp — the convolution planner of the backbone engine, host arithmetic only: what a packed convolution site and a launch plan are, which
 // kernel forms a site may run on, the heuristic plan and the tilings the autotuner may try, the Winograd forms with the weight images they read, the plan
-// codes (fpc.h, FPC_PLAN_*).  Shared by net.hip (the engine), conv_launch.hip (a plan's launch) and conv2d.hip (the stand-alone fpc_conv2d* entries).
+// codes (fpc.h, FPC_PLAN_*).  Shared by the engine (net_plan.hpp: net_build.hip, net.hip), conv_launch.hip (a plan's launch) and conv2d.hip (the stand-alone fpc_conv2d* entries).
 #pragma once
 #include <math.h>
 #include <string.h>

@@ -2,583 +2,30 @@
 // PoseRegressor.pure_model_forward + Model.class_compression
 // (F/lib/pose_regressor.py:709-743, 445-457) for inference.
 //
-// The graph is the one segmentation_models_pytorch builds for FastPoseCNN
-// (encoder = ResNet BasicBlock x {2,2,2,2} or {3,4,6,3}, or Bottleneck x {3,4,6,3} / {3,4,23,3} / {3,8,36,3} whose 1x1 sites
-// may run on k_conv1x1 (pointwise.hip) and whose conv2, in the ResNeXt encoders, is a grouped 3x3 on k_conv3x3_grouped
-// (conv_grouped.hip), or the SE-ResNet Bottleneck x {3,4,6,3} / {3,4,23,3} / {3,8,36,3}: the stride on conv1, a dense 3x3 conv2 and the
-// squeeze-and-excitation gate of se.hip between bn3 and the residual add, or torchvision's MobileNetV2 features on the three kernels of
-// mobilenet.hip (below: "the MobileNetV2 encoder"); four FPN decoders, merge "add";
-// four 1x1 heads + x4 bilinear), see fastposecnn_amd/lib/backbone.py.  The plan owns no device
-// memory: packed weights, activations and split-K scratch live in one caller-provided workspace.
+// The graph is the one segmentation_models_pytorch builds for FastPoseCNN: an encoder, four FPN decoders with merge "add", four
+// 1x1 heads and the x4 bilinear upsample (fastposecnn_amd/lib/backbone.py).  Which encoders there are, and what each is made of, is
+// stated in net_plan.hpp (the block kinds, the encoder descriptor) and built in net_build.hip (one builder per encoder family).
+// This file knows an encoder only as its tape: a list of steps, each of one kind, which the forward walks.
+// The plan owns no device memory: packed weights, activations and split-K scratch live in one caller-provided workspace.
 // Launch order per frame (R18): stem conv, max-pool, 16 encoder convs (+3 downsample 1x1) with
 // BatchNorm / residual / ReLU in their epilogues, then the FOUR decoders as grouped launches:
 // 4 lateral 1x1 convs (FPN top-down add in the epilogue), 7 3x3 convs (GroupNorm partial sums in
 // the epilogue), 7 GroupNorm finalisations, 3 GN+ReLU+x2-upsample passes, 1 merge+head kernel,
 // 1 x4-upsample + class-compression kernel.
 //
-// This file keeps fpc_net: building it, loading, tuning, guarding, the forward and the fpc_net_* entry points.  What is not the
-// network lives beside it: conv_plan.hpp (the host-only convolution planner: sites, plans, predicates, Winograd forms, plan codes),
-// conv_launch.hip (a plan's launch, whichever kernel it names) and conv2d.hip (the stand-alone fpc_conv2d* and geometry entry points).
-#include <stdio.h>
-#include <stdlib.h>
-
+// This file keeps what is done WITH a plan: loading, tuning, guarding, the forward and the fpc_net_* entry points but the creating
+// ones.  Beside it: net_plan.hpp (what a plan is: struct fpc_net, the tape's steps, the encoder descriptor), net_build.hip (how one is
+// built, and the fpc_net_create* entries), conv_plan.hpp (the host-only convolution planner: sites, plans, predicates, Winograd forms,
+// plan codes), conv_launch.hip (a plan's launch, whichever kernel it names) and conv2d.hip (the stand-alone fpc_conv2d* and geometry
+// entry points).
 #include <initializer_list>
-#include <string>
 #include <utility>
 
-#include "conv_plan.hpp"
-
-using namespace fpc;
-
-// ---- the encoder block kinds, each stated once.  A block is up to three convolution sites with BatchNorm in PARAMETER order
-// (encoder.layerN.i.conv1 / bn1, conv2 / bn2, conv3 / bn3), each between two of the block's buffers, then — SE only — the four
-// se_module parameters, then the downsample (1x1 with the block's stride and BatchNorm, In -> D) where the block's stride is not 1 or
-// its channels change.  Channels follow from the buffers: In has the predecessor's, T1 and T2 planes * width / 64 * groups, D and Y
-// planes * expansion.  net_build turns this statement into the parameter table, the activation buffers and the encoder tape.
-enum Buf { kBufNone, kBufIn, kBufT1, kBufT2, kBufD, kBufY, kBufRes, kBufCount };      // Res: D where the block has a downsample, else In
-// k: 3 = 3x3 / pad 1, 1 = 1x1 / pad 0; strided: the site that carries the block's stride; grouped: a grouped 3x3 (add_grouped_conv) in
-// an encoder with groups, dense in every other; res: the residual added in the epilogue, or kBufNone
-struct BlockSite { int k; bool strided, grouped; Buf in, out; bool relu; Buf res; };
-struct BlockKind {
-    int nsites;
-    BlockSite site[3];
-    int ds_before;           // LAUNCH order: the downsample runs in front of this site, whose epilogue (or whose gate) consumes it
-    bool se_gate;            // se_module.fc1 / fc2 (weight, bias) behind the last site's parameters; behind its launch the gate step: Y's
-                             // channel means, the two fc layers, then Y = relu(Y * gate + Res) in place (se.hip: three launches)
-    bool shared;             // true: a stage's blocks share T1 (block 0's, the largest), T2, D and two outputs in turn — only a block's
-                             // output feeds the next block, which reads it as input and residual; false: every block has its own T1, Y, D
-};
-// BasicBlock: 3x3 (stride) -> 3x3 + residual
-constexpr BlockKind kBasicBlock = {2, {{3, true, false, kBufIn, kBufT1, true, kBufNone}, {3, false, false, kBufT1, kBufY, true, kBufRes}}, 1, false, false};
-// torchvision's Bottleneck: 1x1 -> 3x3 (stride; grouped in the ResNeXt encoders) -> 1x1 x 4 + residual
-constexpr BlockKind kBottleneck = {3, {{1, false, false, kBufIn, kBufT1, true, kBufNone}, {3, true, true, kBufT1, kBufT2, true, kBufNone}, {1, false, false, kBufT2, kBufY, true, kBufRes}}, 2, false, true};
-// pretrainedmodels' SEResNetBottleneck: 1x1 (stride) -> 3x3 (a Winograd site at every stage) -> 1x1 x 4 with BatchNorm only -> gate
-constexpr BlockKind kSEBottleneck = {3, {{1, true, false, kBufIn, kBufT1, true, kBufNone}, {3, false, false, kBufT1, kBufT2, true, kBufNone}, {1, false, false, kBufT2, kBufY, false, kBufNone}}, 2, true, true};
-
-// The encoder descriptor: all that tells one encoder from another.  Beside the block statements above it is the only place that
-// knows a block kind; the rest of the engine walks the tape.
-struct EncoderDesc {
-    int expansion = 1;            // 1: BasicBlock encoder, 4: Bottleneck (1x1, 3x3 with the stride, 1x1 x 4)
-    int groups = 1, width = 64;   // Bottleneck: conv2's groups and torchvision's width_per_group (ResNeXt: 32 and 4 / 8); (1, 64) = ResNet
-    int se = 0;                   // > 0: the SE-ResNet Bottleneck (pretrainedmodels.senet) with this reduction; expansion is 4 then
-    int layers[4] = {};           // blocks per stage
-    bool mbv2 = false;            // torchvision's MobileNetV2 features (the MobileNetV2 encoder, below): none of the block kinds, expansion 0
-    const BlockKind& kind() const { return se ? kSEBottleneck : expansion == 4 ? kBottleneck : kBasicBlock; }
-    const char* stem_prefix() const { return se ? "encoder.layer0." : "encoder."; }      // torchvision's stem names, pretrainedmodels'
-    // the SE-ResNet stem pool: no padding, ceil_mode (other windows, the same size on the even maps every plan has): its own max-pool launch, never the fused stem + pool
-    bool ceil_pool() const { return se != 0; }
-    bool basic() const { return expansion == 1; }         // c2 has 64 channels: s2.0 may fold the FPN p2 level in, and the direct sites have three-product images
-    bool pointwise() const { return expansion == 4; }     // the autotuner offers k_conv1x1 to the 1x1 sites
-};
-
-struct fpc_net {
-    EncoderDesc enc;
-    int classes, B, H, W;
-    std::vector<std::string> pnames;
-    std::vector<int64_t> pnumel;
-    std::vector<const float*> pptr;
-    std::vector<PackedConv> convs;
-    size_t packed_floats = 0;     // packed weights + folded BN region (persistent across forwards)
-    size_t total_floats = 0;      // + activations and scratch
-    float* ws = nullptr;
-    bool loaded = false;
-    bool tuning = false;          // next forward times every candidate tiling per conv site and keeps the best
-    bool tuned = false;
-    int tune_mode = 0;            // 0: minimise latency, 1: latency x sqrt(share of the chip occupied)
-
-    // conv indices
-    int c_stem = -1;
-    // The encoder tape: every launch between the max-pool and the decoders, in launch order.  conv >= 0: that site from `in` to `out` with BatchNorm, `res`
-    // (C > 0) and ReLU in its epilogue; conv < 0: an SE block's gate step on `out` in place, with the residual `res` and se_module's four parameters from p_se
-    // mb >= 0: that op of the MobileNetV2 encoder (mops) from `in` to `out`, a 1x1 with the residual `res` (C > 0)
-    struct Step { int conv; Act in, out; bool relu; Act res; int p_se; int mb = -1; };
-    std::vector<Step> tape;
-    // The MobileNetV2 encoder's ops: the stem, a depthwise 3x3 or a 1x1, each with BatchNorm folded into scale / shift and ReLU6 where
-    // act = 1.  One form each (mobilenet.hip): not PackedConv sites, not tuned, not surveyed; the weights are read in place.
-    enum MbKind { kMbStem, kMbDw, kMbPw };
-    struct MbOp { MbKind kind; int p_w, p_bn, Cin, Cout, stride, act; size_t scale_off, shift_off; long long howo; };
-    std::vector<MbOp> mops;
-    int add_mop(MbKind kind, const std::string& wname, int64_t wnumel, const std::string& bn, int Cin, int Cout, int stride, int act) {
-        MbOp o{kind, add_param(wname, wnumel), add_bn(bn, Cout), Cin, Cout, stride, act, 0, 0, 0};
-        o.scale_off = alloc(Cout); o.shift_off = alloc(Cout);
-        mops.push_back(o);
-        return (int)mops.size() - 1;
-    }
-    struct Dec {
-        int lat[4];               // p5, p4, p3, p2 (1x1, bias)
-        int seg[7];               // s5.0 s5.1 s5.2 s4.0 s4.1 s3.0 s2.0
-        int p_gn[7];              // param index of GN weight (bias = +1)
-        int p_head_w, p_head_b;
-        int head_ch, head_chp;
-    } dec[4];
-
-    // activations (float offsets)
-    Act a_img4, a_stem, a_pool;
-    Act a_feat[4];                // c2 .. c5: the output of each stage's last block
-    Act a_p[4][4];                // [decoder][p5,p4,p3,p2]
-    Act a_seg[4][7];              // pre-GroupNorm conv outputs
-    Act a_up[4][3];               // s5.0 -> up, s5.1 -> up, s4.0 -> up
-    size_t gn_part_off[4][7], gn_aff_off[4][7];
-    int gn_P[7];
-    Act a_low[4];                 // low-res logits
-    Act a_lsum[4];                // two-pass merge + head: the head of the three upsampled branches' sum at their own resolution
-    int up4_wide = 1;             // 0: FPC_UP4_WIDE=0, plans of 9 to 32 classes keep k_up4_compress<32>
-    int merge_split = -1;         // -1: two passes unless FPC_MERGE_SPLIT=0, 0: k_merge_head (one pass), 1: two passes
-    size_t splitk_off = 0, splitk_floats = 0;
-    size_t se_gate_off = 0, se_part_off = 0;      // SE plans: gate [B][2048] and the slab partials of the stage that needs most (k_se_pool / k_se_excite)
-    int use_graph = 0;            // replay the frame-invariant launches as a HIP graph (fpc_net_set_graph)
-    long long wino_blocks = 0;    // workgroups of the form-9 launches of the last forward that launched its kernels (fpc_net_wino_blocks)
-    int wino_pack = 1;            // form-9 launches cut their patches out of canvas rows of several frames where that saves patches (fpc_net_set_wino_pack)
-    int wino_orient = 1;          // form-9 launches run transposed at the sites wino_orient_rule names (fpc_net_set_wino_orient)
-    std::vector<char> c_tr;       // 1: the conv is a form-9 candidate at a shape the rule transposes (every decoder's; its h3 image follows wino_orient)
-    int split_precision = 0;      // autotuning may pick the bf16 x 3 form of a direct convolution (fpc_net_set_split_precision)
-    hipGraphExec_t graph_exec = nullptr;
-    size_t zeros_off = 0;         // 64 zero floats (DMA source for out-of-image positions)
-    size_t tickets_off = 0;       // kConvTickets zero ints: arrival counters of the fused split-K convolutions
-
-    // the FPN p2 fold of s2.0 (BasicBlock encoders: c2 has 64 channels): per decoder Wc = W L (OIHW), the h3 images of Wc and of W on
-    // one scale (wino_h3.hip: launch_wino_pack_h3_pair) and the border-class bias table
-    bool h3_packed = false;               // the PackedConv::h3_ok images hold the current weights (split level 3, pack_h3_images)
-    hipStream_t load_stream = nullptr;    // stream of the last fpc_net_load_params
-    size_t stem_h3_off = 0;               // the stem's k_pack_weight_h3 image (k_stem_pool_h3; packed with the h3_ok images)
-    bool fold_ok = false;
-    size_t fold_wc_off[4] = {}, fold_img1_off[4] = {}, fold_img2_off[4] = {}, fold_tab_off[4] = {};
-
-    // per-conv launch plans (index = conv id of decoder 0 for grouped ones)
-    std::vector<ConvPlan> cplan;
-    std::vector<float> tune_score;       // the autotuner's best score per site (ms, or its throughput objective)
-    // the activation-range guard (fpc_net_survey_next / fpc_net_guard_ranges)
-    unsigned* survey = nullptr;          // device records [convs][4] the NEXT forward fills (k_act_range in front of every site's launch)
-    std::vector<ConvPlan> free_plan;     // the autotuner's best-scoring candidate that is not range-limited, kept beside the best ...
-    std::vector<char> has_free;          // ... 1 where the site was autotuned and had one
-    std::vector<char> guarded;           // 1: the site stands demoted to a range-free plan (sticky: the tuner offers it no fp16-piece form)
-    std::vector<int> c_howo, c_groups;   // output pixels per image and launch multiplicity of every planned conv site (0: not a site)
-
-    size_t bump = 0;
-    size_t alloc(size_t n) { size_t o = bump; bump += (n + 63) / 64 * 64; return o; }
-    Act alloc_act(int h, int w, int c) { Act a; a.H = h; a.W = w; a.C = c; a.off = alloc((size_t)B * h * w * c); return a; }
-    int add_param(const std::string& n, int64_t numel) { pnames.push_back(n); pnumel.push_back(numel); return (int)pnames.size() - 1; }
-    int add_bn(const std::string& p, int C) {      // BatchNorm's four -> the index of the first
-        add_param(p + ".weight", C); add_param(p + ".bias", C); add_param(p + ".running_mean", C);
-        return add_param(p + ".running_var", C) - 3;
-    }
-
-    int add_conv(const std::string& wname, int Cin, int Cout, int k, int stride, int pad, const char* bn_prefix,
-                 const char* bias_name, int Cinp = 0, int Kwp = 0) {
-        PackedConv c;
-        c.Cin = Cin; c.Cinp = Cinp ? Cinp : Cin; c.Cout = Cout; c.Kh = c.Kw = k; c.stride = stride; c.pad = pad;
-        c.Kwp = Kwp ? Kwp : k;
-        c.K = c.Cinp * k * c.Kwp; c.Kpad = cdiv(c.K, kConvBK) * kConvBK; c.Npad = cdiv(Cout, kConvNAlign) * kConvNAlign;
-        c.p_w = add_param(wname, (int64_t)Cout * Cin * k * k);
-        if (bn_prefix) c.p_bn = add_bn(bn_prefix, Cout);
-        if (bias_name) c.p_bias = add_param(bias_name, Cout);
-        c.w_off = alloc(conv_packed_floats(c.Npad, c.Kpad));      // f32 image + its three bf16 planes
-        if (bn_prefix) { c.scale_off = alloc(Cout); c.shift_off = alloc(Cout); }
-        c.wino_ok = (k == 3 && stride == 1 && pad == 1 && c.Cinp == Cin && Cin % 8 == 0 && Cout % 64 == 0);
-        if (c.wino_ok) c.wino_off = alloc(wino_region_floats(kImgH3, Cout, Cin, Cout % 128 == 0));      // every image (kWinoImages)
-        convs.push_back(c);
-        return (int)convs.size() - 1;
-    }
-    // a grouped 3x3 / pad-1 site of C channels in groups of cg, with BatchNorm: its packed image is k_pack_grouped's alone
-    int add_grouped_conv(const std::string& wname, int C, int cg, int stride, const char* bn_prefix) {
-        PackedConv c;
-        c.Cin = c.Cinp = c.Cout = C; c.Kh = c.Kw = c.Kwp = 3; c.stride = stride; c.pad = 1; c.cg = cg;
-        c.K = cg * 9; c.Kpad = cdiv(c.K, kConvBK) * kConvBK; c.Npad = cdiv(C, kConvNAlign) * kConvNAlign;
-        c.p_w = add_param(wname, (int64_t)C * cg * 9);
-        c.p_bn = add_bn(bn_prefix, C);
-        c.grp_off = alloc((size_t)C * cg * 9);
-        c.scale_off = alloc(C); c.shift_off = alloc(C);
-        convs.push_back(c);
-        return (int)convs.size() - 1;
-    }
-};
+#include "net_plan.hpp"
 
 // the recorded graph no longer matches the plans, the parameters or the launch geometry
 static void drop_graph(fpc_net* n) {
     if (n->graph_exec) { (void)hipGraphExecDestroy(n->graph_exec); n->graph_exec = nullptr; }
-}
-
-static const char* kDecNames[4] = {"mask_decoder", "rotation_decoder", "translation_decoder", "scales_decoder"};
-static const char* kHeadNames[4] = {"segmentation_head", "rotation_head", "translation_head", "scales_head"};
-
-// the implicit GEMM's loader of a lateral site: 0 = the fast one (Cin a multiple of 32), 2 = Cin % 4 (k_conv_igemm's MODE 2)
-static int lateral_mode(const PackedConv& c) { return c.Cin % kConvBK == 0 ? 0 : 2; }
-
-// the plan of `n` (its encoder descriptor set) for (classes, B, H, W); owns `n` (deleted on failure)
-static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** out);
-
-// The one creation path: the checks every entry shares, then the plan.  A wrapper keeps only the refusals of its own arguments.
-static int create(EncoderDesc d, const int* layers4, int classes, int B, int H, int W, fpc_net_t** out) {
-    if (!layers4 || !out || classes < 2 || classes > 32 || B < 1 || H < 32 || W < 32 || H % 32 || W % 32) return FPC_EINVAL;
-    for (int L = 0; L < 4; ++L)
-        if (layers4[L] < 1 || layers4[L] > 64) return FPC_EINVAL;
-    memcpy(d.layers, layers4, sizeof(d.layers));
-    return net_build(new fpc_net{d}, classes, B, H, W, out);
-}
-
-// the encoders fpc_net_create knows by name: {expansion, groups, width, se reduction, layers}
-static const struct { const char* name; EncoderDesc desc; } kEncoders[] = {
-    {"resnet18", {1, 1, 64, 0, {2, 2, 2, 2}}}, {"resnet34", {1, 1, 64, 0, {3, 4, 6, 3}}},
-    // the ResNeXt encoders: Bottleneck x {3,4,6,3} / {3,4,23,3} with 32 groups of width 4 (8) on conv2
-    {"resnext50_32x4d", {4, 32, 4, 0, {3, 4, 6, 3}}},
-    {"resnext101_32x4d", {4, 32, 4, 0, {3, 4, 23, 3}}},
-    {"resnext101_32x8d", {4, 32, 8, 0, {3, 4, 23, 3}}},
-    // the SE-ResNets: pretrainedmodels' SEResNetBottleneck x {3,4,6,3} / {3,4,23,3} / {3,8,36,3}, reduction 16
-    {"se_resnet50", {4, 1, 64, 16, {3, 4, 6, 3}}},
-    {"se_resnet101", {4, 1, 64, 16, {3, 4, 23, 3}}},
-    {"se_resnet152", {4, 1, 64, 16, {3, 8, 36, 3}}},
-    // the MobileNetV2 encoder (below); layers: the feature modules of smp's four last stages
-    {"mobilenet_v2", {0, 1, 64, 0, {2, 3, 7, 5}, true}},
-};
-
-extern "C" int fpc_net_create(const char* encoder, int classes, int B, int H, int W, fpc_net_t** out) {
-    for (const auto& e : kEncoders)
-        if (encoder && !strcmp(encoder, e.name)) return create(e.desc, e.desc.layers, classes, B, H, W, out);
-    return FPC_EINVAL;
-}
-
-// An encoder by its descriptor: block 1 = BasicBlock, 4 = Bottleneck (torchvision's: the stride on the 3x3), layers4 = blocks per
-// stage.  (1, {2,2,2,2}) and (1, {3,4,6,3}) are the plans fpc_net_create builds for "resnet18" / "resnet34".
-extern "C" int fpc_net_create_encoder(int block, const int* layers4, int classes, int B, int H, int W, fpc_net_t** out) {
-    return fpc_net_create_encoder_ex(block, layers4, 1, 64, classes, B, H, W, out);
-}
-
-// ... with torchvision's `groups` and `width_per_group`: a Bottleneck's conv2 is then a grouped 3x3 of planes * width / 64 * groups
-// channels (k_conv3x3_grouped) between 1x1 sites of that width; (groups, width) = (1, 64) is fpc_net_create_encoder.  Refused:
-// groups > 1 on BasicBlock, a width other than 64 without groups, channels per group outside k_conv3x3_grouped's set at any stage.
-extern "C" int fpc_net_create_encoder_ex(int block, const int* layers4, int groups, int width_per_group, int classes, int B, int H,
-                                         int W, fpc_net_t** out) {
-    if (block != 1 && block != 4) return FPC_EINVAL;
-    if (groups < 1 || width_per_group < 1 || (groups == 1 && width_per_group != 64) || (groups > 1 && block != 4)) return FPC_EINVAL;
-    if (groups > 1)
-        for (int planes = 64; planes <= 512; planes *= 2) {
-            const int cg = planes * width_per_group / 64;      // torchvision: width = int(planes * base_width / 64) * groups
-            if (!grouped_cg_ok(cg) || (long long)cg * groups > 8192 || (cg * groups) % 64) return FPC_EINVAL;
-        }
-    return create({block, groups, width_per_group}, layers4, classes, B, H, W, out);
-}
-
-// The SE-ResNet encoders: SEResNetBottleneck x layers4 — conv1 1x1 WITH the stride, conv2 a dense 3x3 / stride 1 (a Winograd site at
-// every stage), conv3 1x1 x 4 with BatchNorm only, then the gate of se.hip (fc1 C -> C / reduction, fc2 back, both with bias) and the
-// scale + residual + ReLU pass; parameters named as pretrainedmodels' (encoder.layer0.conv1.weight, encoder.layerN.i.se_module.fc1.bias).
-// Refused: a reduction that does not divide 256 (the narrowest stage output).
-extern "C" int fpc_net_create_encoder_se(const int* layers4, int reduction, int classes, int B, int H, int W, fpc_net_t** out) {
-    if (reduction < 1 || 256 % reduction) return FPC_EINVAL;
-    return create({4, 1, 64, reduction}, layers4, classes, B, H, W, out);
-}
-
-// ---- the MobileNetV2 encoder: torchvision's mobilenet_v2().features as smp's MobileNetV2Encoder walks it.  features.0 is the 3x3 /
-// stride-2 stem (3 -> 32, BatchNorm, ReLU6); features.1 .. 17 are InvertedResidual blocks by the (t, c, n, s) table: an expand 1x1
-// inp -> t inp with BatchNorm and ReLU6 (absent where t = 1), a depthwise 3x3 with the block's stride, BatchNorm and ReLU6, a project
-// 1x1 to c channels with BatchNorm only, and the block's input added where the stride is 1 and inp = c (no activation behind it);
-// features.18 is the 1x1 320 -> 1280 with BatchNorm and ReLU6.  smp's stages end behind features.1 / 3 / 6 / 13 / 18: the last four
-// are c2 .. c5 of 24 / 32 / 96 / 1280 channels.  Parameters in state-dict order (conv weight, then BatchNorm's four), read in place.
-static const int kMbTable[7][4] = {{1, 16, 1, 1}, {6, 24, 2, 2}, {6, 32, 3, 2}, {6, 64, 4, 2}, {6, 96, 3, 1}, {6, 160, 3, 2}, {6, 320, 1, 1}};
-struct MbBlock { int expand, dw, proj, stage; };      // ops of fpc_net::mops (-1: the block has none); stage -1: in front of c2's
-
-static void mbv2_params(fpc_net* n, std::vector<MbBlock>& blocks, int featc[4]) {
-    const std::string f("encoder.features.");
-    n->add_mop(fpc_net::kMbStem, f + "0.0.weight", 32 * 27, f + "0.1", 3, 32, 2, 1);
-    int inp = 32, idx = 1;
-    for (const auto& row : kMbTable)
-        for (int i = 0; i < row[2]; ++i, ++idx) {
-            const int t = row[0], oup = row[1], stride = i == 0 ? row[3] : 1, hid = inp * t;
-            const std::string p = f + std::to_string(idx) + ".conv.";
-            MbBlock b{-1, -1, -1, idx < 2 ? -1 : idx < 4 ? 0 : idx < 7 ? 1 : idx < 14 ? 2 : 3};
-            const int k = t != 1 ? 1 : 0;      // the depthwise's place in `conv`
-            if (k) b.expand = n->add_mop(fpc_net::kMbPw, p + "0.0.weight", (int64_t)hid * inp, p + "0.1", inp, hid, 1, 1);
-            b.dw = n->add_mop(fpc_net::kMbDw, p + std::to_string(k) + ".0.weight", (int64_t)hid * 9, p + std::to_string(k) + ".1", hid, hid, stride, 1);
-            b.proj = n->add_mop(fpc_net::kMbPw, p + std::to_string(k + 1) + ".weight", (int64_t)oup * hid, p + std::to_string(k + 2), hid, oup, 1, 0);
-            blocks.push_back(b);
-            inp = oup;
-        }
-    blocks.push_back(MbBlock{-1, -1, n->add_mop(fpc_net::kMbPw, f + "18.0.weight", (int64_t)1280 * inp, f + "18.1", inp, 1280, 1, 1), 3});
-    featc[0] = 24; featc[1] = 32; featc[2] = 96; featc[3] = 1280;
-}
-
-// Its buffers and tape.  Per stage: the largest expanded tensor, the largest depthwise output and two outputs the blocks take in turn
-// (a block's input is its residual, so it never writes over it); a stage's last output stays: a_feat.
-static void mbv2_buffers(fpc_net* n, const std::vector<MbBlock>& blocks) {
-    const size_t B = (size_t)n->B;
-    n->a_stem = n->alloc_act(n->H / 2, n->W / 2, 32);
-    n->mops[0].howo = (long long)n->a_stem.H * n->a_stem.W;
-    n->tape.push_back({-1, n->a_img4, n->a_stem, false, Act(), -1, 0});
-    Act cur = n->a_stem;
-    for (int stage = -1; stage < 4; ++stage) {
-        size_t fe = 0, fd = 0, fy = 0;
-        int h = cur.H, w = cur.W, count = 0;
-        for (const MbBlock& b : blocks) {
-            if (b.stage != stage) continue;
-            ++count;
-            if (b.expand >= 0) fe = std::max(fe, (size_t)h * w * n->mops[b.expand].Cout);
-            if (b.dw >= 0) {
-                h = conv_out(h, 3, n->mops[b.dw].stride, 1); w = conv_out(w, 3, n->mops[b.dw].stride, 1);
-                fd = std::max(fd, (size_t)h * w * n->mops[b.dw].Cout);
-            }
-            fy = std::max(fy, (size_t)h * w * n->mops[b.proj].Cout);
-        }
-        Act E, D, Y[2];
-        if (fe) E.off = n->alloc(B * fe);
-        if (fd) D.off = n->alloc(B * fd);
-        Y[0].off = n->alloc(B * fy);
-        if (count > 1) Y[1].off = n->alloc(B * fy);
-        int turn = 0;
-        auto view = [&](Act t, int th, int tw, int op) {
-            t.H = th; t.W = tw; t.C = n->mops[op].Cout;
-            n->mops[op].howo = (long long)th * tw;
-            return t;
-        };
-        for (const MbBlock& b : blocks) {
-            if (b.stage != stage) continue;
-            const Act in = cur;
-            Act x = cur;
-            if (b.expand >= 0) { const Act e = view(E, x.H, x.W, b.expand); n->tape.push_back({-1, x, e, false, Act(), -1, b.expand}); x = e; }
-            if (b.dw >= 0) {
-                const int st = n->mops[b.dw].stride;
-                const Act d = view(D, conv_out(x.H, 3, st, 1), conv_out(x.W, 3, st, 1), b.dw);
-                n->tape.push_back({-1, x, d, false, Act(), -1, b.dw});
-                x = d;
-            }
-            const Act y = view(Y[turn], x.H, x.W, b.proj);
-            turn = count > 1 ? turn ^ 1 : 0;
-            const bool res = b.dw >= 0 && n->mops[b.dw].stride == 1 && in.C == y.C;
-            n->tape.push_back({-1, x, y, false, res ? in : Act(), -1, b.proj});
-            cur = y;
-        }
-        if (stage >= 0) n->a_feat[stage] = cur;
-    }
-}
-
-static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** out) {
-    n->classes = classes; n->B = B; n->H = H; n->W = W;
-    {   // merge + head in two passes (merge_split.hip) unless FPC_MERGE_SPLIT=0; read once, here
-        const char* e = getenv("FPC_MERGE_SPLIT");
-        n->merge_split = e ? (atoi(e) != 0) : 1;      // (one frame: 27 us in two passes against 32.5 us in one)
-        // 9 to 32 classes: the four-pixel x4 upsample + compression (k_up4_compress_wide) unless FPC_UP4_WIDE=0 (k_up4_compress<32>)
-        const char* u = getenv("FPC_UP4_WIDE");
-        n->up4_wide = u ? (atoi(u) != 0) : 1;
-    }
-    char buf[256];
-
-    // ---- parameters + packed storage (persistent region first)
-    const EncoderDesc& enc = n->enc;
-    const BlockKind& kind = enc.kind();
-    const std::string stem(enc.stem_prefix());
-    const int planes[4] = {64, 128, 256, 512};
-    const int e = enc.expansion;
-    int featc[4] = {64 * e, 128 * e, 256 * e, 512 * e};      // channels of c2 .. c5
-    const int stages = enc.mbv2 ? 0 : 4;                     // stages of the block kinds above
-    std::vector<MbBlock> mb;
-    if (enc.mbv2) mbv2_params(n, mb, featc);
-    else n->c_stem = n->add_conv(stem + "conv1.weight", 3, 64, 7, 2, 3, (stem + "bn1").c_str(), nullptr, 4, 8);     // NHWC4 pixels, 8 taps per row
-    struct Block { int conv[3], ds, p_se, stride, ch[kBufCount]; };      // a block's sites as created here, for the buffers and the tape below
-    std::vector<Block> blocks[4];
-    int inpl = 64;
-    for (int L = 0; L < stages; ++L)
-        for (int bi = 0; bi < enc.layers[L]; ++bi) {
-            const int mid = planes[L] * enc.width / 64 * enc.groups, C = e * planes[L];      // (mid: planes[L] but in the ResNeXt encoders)
-            Block blk{{-1, -1, -1}, -1, -1, (bi == 0 && L > 0) ? 2 : 1, {0, inpl, mid, mid, C, C, C}};      // (channels by Buf)
-            const int* ch = blk.ch;
-            snprintf(buf, sizeof(buf), "encoder.layer%d.%d", L + 1, bi);
-            const std::string p(buf);
-            for (int i = 0; i < kind.nsites; ++i) {
-                const BlockSite& st = kind.site[i];
-                const std::string w = p + ".conv" + std::to_string(i + 1) + ".weight", bn = p + ".bn" + std::to_string(i + 1);
-                const int stride = st.strided ? blk.stride : 1;
-                blk.conv[i] = st.grouped && enc.groups > 1 ? n->add_grouped_conv(w, ch[st.out], ch[st.out] / enc.groups, stride, bn.c_str())
-                                                           : n->add_conv(w, ch[st.in], ch[st.out], st.k, stride, st.k / 2, bn.c_str(), nullptr);
-            }
-            if (kind.se_gate) {      // plain parameters, read in place
-                const int Cr = C / enc.se;
-                blk.p_se = n->add_param(p + ".se_module.fc1.weight", (int64_t)Cr * C);
-                n->add_param(p + ".se_module.fc1.bias", Cr);
-                n->add_param(p + ".se_module.fc2.weight", (int64_t)C * Cr);
-                n->add_param(p + ".se_module.fc2.bias", C);
-            }
-            if (blk.stride != 1 || inpl != C)
-                blk.ds = n->add_conv(p + ".downsample.0.weight", inpl, C, 1, blk.stride, 0, (p + ".downsample.1").c_str(), nullptr);
-            inpl = C;
-            blocks[L].push_back(blk);
-        }
-    const int G = classes - 1;
-    const int head_ch[4] = {classes, 4 * G, 3 * G, 3 * G};
-    for (int d = 0; d < 4; ++d) {
-        std::string D(kDecNames[d]);
-        fpc_net::Dec& dc = n->dec[d];
-        dc.lat[0] = n->add_conv(D + ".p5.weight", featc[3], 256, 1, 1, 0, nullptr, (D + ".p5.bias").c_str());
-        const int skipc[3] = {featc[2], featc[1], featc[0]};
-        for (int i = 0; i < 3; ++i) {
-            snprintf(buf, sizeof(buf), "%s.p%d.skip_conv", kDecNames[d], 4 - i);
-            std::string p(buf);
-            dc.lat[1 + i] = n->add_conv(p + ".weight", skipc[i], 256, 1, 1, 0, nullptr, (p + ".bias").c_str());
-        }
-        const int nconv[4] = {3, 2, 1, 1};
-        int si = 0;
-        for (int sb = 0; sb < 4; ++sb)
-            for (int j = 0; j < nconv[sb]; ++j) {
-                snprintf(buf, sizeof(buf), "%s.seg_blocks.%d.block.%d.block", kDecNames[d], sb, j);
-                std::string p(buf);
-                dc.seg[si] = n->add_conv(p + ".0.weight", j == 0 ? 256 : 128, 128, 3, 1, 1, nullptr, nullptr);
-                dc.p_gn[si] = n->add_param(p + ".1.weight", 128);
-                n->add_param(p + ".1.bias", 128);
-                ++si;
-            }
-    }
-    for (int d = 0; d < 4; ++d) {
-        fpc_net::Dec& dc = n->dec[d];
-        dc.head_ch = head_ch[d];
-        dc.head_chp = (head_ch[d] + 3) / 4 * 4;
-        dc.p_head_w = n->add_param(std::string(kHeadNames[d]) + ".0.weight", (int64_t)head_ch[d] * 128);
-        dc.p_head_b = n->add_param(std::string(kHeadNames[d]) + ".0.bias", head_ch[d]);
-        // a head past one 32-channel matrix tile (10 classes and more) has the two-pass form only: k_merge_head is not widened, and
-        // FPC_MERGE_SPLIT=0 does not apply to such a plan
-        if (dc.head_chp > 32) n->merge_split = 1;
-    }
-    n->fold_ok = enc.basic();
-    if (n->fold_ok)
-        for (int d = 0; d < 4; ++d) {
-            n->fold_wc_off[d] = n->alloc((size_t)128 * 64 * 9);
-            n->fold_img1_off[d] = n->alloc((size_t)16 * 128 * 64 + 2);
-            n->fold_img2_off[d] = n->alloc((size_t)16 * 128 * 256 + 2);
-            n->fold_tab_off[d] = n->alloc((size_t)16 * 128);
-        }
-    if (enc.basic()) {      // the three-product direct form's weight images, only where it is a candidate (not the p2 lateral: folded away)
-        std::vector<int> sites;
-        for (int L = 1; L < 4; ++L) { sites.push_back(blocks[L][0].conv[0]); if (blocks[L][0].ds >= 0) sites.push_back(blocks[L][0].ds); }
-        for (int d = 0; d < 4; ++d)
-            for (int i = 0; i < 3; ++i) sites.push_back(n->dec[d].lat[i]);
-        for (int ci : sites) {
-            PackedConv& c = n->convs[ci];
-            if (c.wino_ok || c.Cin % kConvBK != 0 || c.Cinp != c.Cin || c.Kh * c.Kw > 32) continue;
-            c.h3_ok = true;
-            c.h3_off = n->alloc(h3_packed_floats(c.Npad, c.Kpad));
-        }
-    }
-    if (n->c_stem >= 0) n->stem_h3_off = n->alloc(h3_packed_floats(n->convs[n->c_stem].Npad, n->convs[n->c_stem].Kpad));      // every encoder with the 7x7 stem shares it
-    n->zeros_off = n->alloc(64);
-    n->tickets_off = n->alloc(kConvTickets);
-    n->packed_floats = n->bump;
-
-    // ---- activations
-    int h1 = conv_out(H, 7, 2, 3), w1 = conv_out(W, 7, 2, 3);
-    n->a_img4 = n->alloc_act(H, W, 4);
-    if (enc.mbv2) {
-        mbv2_buffers(n, mb);      // (no pooled tensor: a_pool stays empty)
-    } else {
-        n->a_stem = n->alloc_act(h1, w1, 64);
-        int hp = enc.ceil_pool() ? h1 / 2 : conv_out(h1, 3, 2, 1), wp = enc.ceil_pool() ? w1 / 2 : conv_out(w1, 3, 2, 1);
-        n->a_pool = n->alloc_act(hp, wp, 64);
-    }
-    // the blocks' buffers and the encoder tape
-    Act cur = n->a_pool;
-    for (int L = 0; L < stages; ++L) {
-        Act b[kBufCount], y[2];
-        for (size_t bi = 0; bi < blocks[L].size(); ++bi) {
-            const Block& blk = blocks[L][bi];
-            // sizes by role: the input's in front of the strided site, the block's output size (h, w) from it on
-            const int h = conv_out(cur.H, 3, blk.stride, 1), w = conv_out(cur.W, 3, blk.stride, 1);
-            Act sz[kBufCount]; bool past = false;
-            for (int i = 0; i < kind.nsites; ++i) {
-                past = past || kind.site[i].strided;
-                sz[kind.site[i].out] = Act{0, past ? h : cur.H, past ? w : cur.W, blk.ch[kind.site[i].out]};
-            }
-            // storage, in this order: T1, T2, the output(s), D.  A shared stage allocates once, at block 0, whose T1 is the largest
-            // (a Bottleneck's conv1 there runs at the stage's INPUT resolution), and D whether or not a later block needs it
-            if (!kind.shared || bi == 0) {
-                auto alloc_like = [&](const Act& t) { return n->alloc_act(t.H, t.W, t.C); };
-                b[kBufT1] = alloc_like(sz[kBufT1]); if (kind.nsites == 3) b[kBufT2] = alloc_like(sz[kBufT2]);
-                y[0] = alloc_like(sz[kBufY]); if (kind.shared) y[1] = alloc_like(sz[kBufY]);
-                if (kind.shared || blk.ds >= 0) b[kBufD] = alloc_like(sz[kBufY]);
-            }
-            b[kBufT1].H = sz[kBufT1].H; b[kBufT1].W = sz[kBufT1].W;      // (a later block's view of a shared T1)
-            b[kBufIn] = cur; b[kBufY] = y[kind.shared ? bi & 1 : 0]; b[kBufRes] = blk.ds >= 0 ? b[kBufD] : cur;
-            // steps, in launch order
-            for (int i = 0; i < kind.nsites; ++i) {
-                const BlockSite& st = kind.site[i];
-                if (i == kind.ds_before && blk.ds >= 0) n->tape.push_back({blk.ds, cur, b[kBufD], false, Act(), -1});
-                n->tape.push_back({blk.conv[i], b[st.in], b[st.out], st.relu, b[st.res], -1});
-            }
-            if (kind.se_gate) n->tape.push_back({-1, b[kBufY], b[kBufY], true, b[kBufRes], blk.p_se});
-            cur = b[kBufY];
-        }
-        n->a_feat[L] = cur;
-    }
-    int fh[4], fw[4];
-    for (int L = 0; L < 4; ++L) { fh[L] = n->a_feat[L].H; fw[L] = n->a_feat[L].W; }
-    if (kind.se_gate) {      // the gate of one block at a time: [B][C] and the slab partials of the stage with the most
-        size_t part = 0;
-        for (int L = 0; L < 4; ++L) part = std::max(part, (size_t)se_pool_slabs(fh[L], fw[L], n->a_feat[L].C) * n->a_feat[L].C);
-        n->se_gate_off = n->alloc((size_t)B * n->a_feat[3].C);
-        n->se_part_off = n->alloc((size_t)B * part);
-    }
-    // FPN needs exact x2 relations between levels
-    for (int L = 1; L < 4; ++L)
-        if (fh[L - 1] != 2 * fh[L] || fw[L - 1] != 2 * fw[L]) { delete n; return FPC_EINVAL; }
-    // seg conv geometry: index -> (resolution level): s5.0@L3, s5.1@L2, s5.2@L1, s4.0@L2, s4.1@L1, s3.0@L1, s2.0@L0
-    const int seg_level[7] = {3, 2, 1, 2, 1, 1, 0};
-    for (int d = 0; d < 4; ++d) {
-        for (int i = 0; i < 4; ++i) n->a_p[d][i] = n->alloc_act(fh[3 - i], fw[3 - i], 256);
-        for (int i = 0; i < 7; ++i) n->a_seg[d][i] = n->alloc_act(fh[seg_level[i]], fw[seg_level[i]], 128);
-        n->a_up[d][0] = n->alloc_act(fh[2], fw[2], 128);   // up2(s5.0)
-        n->a_up[d][1] = n->alloc_act(fh[1], fw[1], 128);   // up2(s5.1)
-        n->a_up[d][2] = n->alloc_act(fh[1], fw[1], 128);   // up2(s4.0)
-        n->a_low[d] = n->alloc_act(fh[0], fw[0], n->dec[d].head_chp);
-        n->a_lsum[d] = n->alloc_act(fh[1], fw[1], n->dec[d].head_chp);
-    }
-
-    // ---- conv plans (+ split-K scratch for the worst candidate, GroupNorm partials for the largest P32)
-    n->cplan.resize(n->convs.size());
-    n->tune_score.assign(n->convs.size(), 0.f);
-    n->free_plan.assign(n->convs.size(), ConvPlan());
-    n->has_free.assign(n->convs.size(), 0);
-    n->guarded.assign(n->convs.size(), 0);
-    n->c_howo.assign(n->convs.size(), 0);
-    n->c_groups.assign(n->convs.size(), 0);
-    n->c_tr.assign(n->convs.size(), 0);
-    auto oriented = [&](int ci, int h, int w) { if (ci >= 0 && n->convs[ci].wino_ok) n->c_tr[ci] = wino_orient_rule(h, w) ? 1 : 0; };
-    auto plan = [&](int ci, int HoWo, int groups) {
-        const PackedConv& c = n->convs[ci];
-        n->c_howo[ci] = HoWo; n->c_groups[ci] = groups;
-        if (c.cg) { ConvPlan q; q.grp = 1; n->cplan[ci] = q; return; }      // a grouped site: k_conv3x3_grouped's form 0, no split-K scratch
-        n->cplan[ci] = plan_conv(HoWo, B, c.Cout, c.Kpad / kConvBK, groups);
-        size_t need = splitk_floats_for(n->cplan[ci], groups, B, c.Npad);
-        for (const ConvPlan& q : conv_candidates(HoWo, B, c.Cout, c.Kpad / kConvBK, groups)) {
-            size_t f = splitk_floats_for(q, groups, B, c.Npad);
-            if (f * sizeof(float) <= ((size_t)256 << 20) && f > need) need = f;
-        }
-        if (need > n->splitk_floats) n->splitk_floats = need;
-    };
-    if (n->c_stem >= 0) plan(n->c_stem, h1 * w1, 1);
-    // (the orientation rule is asked with the step's own output size.  A Winograd site has stride 1 (PackedConv::wino_ok), so that is
-    // the stage's output size at every site the mark matters for: a strided conv1, whose input is larger, is never one)
-    for (const fpc_net::Step& st : n->tape)
-        if (st.conv >= 0) { plan(st.conv, st.out.H * st.out.W, 1); oriented(st.conv, st.out.H, st.out.W); }
-    for (int i = 0; i < 4; ++i) {
-        plan(n->dec[0].lat[i], fh[3 - i] * fw[3 - i], 4);
-        // a lateral whose channels the fast loader does not take (c2 of the MobileNetV2 encoder: 24) runs on the Cin % 4 loader
-        // (lateral_mode), through the same grouped launch with the top-down addend: what that loader asks of the site, checked here
-        if (lateral_mode(n->convs[n->dec[0].lat[i]]) == 2 && (featc[3 - i] % 4 != 0 || ((fh[3 - i] | fw[3 - i]) & 1))) { delete n; return FPC_EINVAL; }
-    }
-    for (int i = 0; i < 7; ++i) {
-        int HoWo = fh[seg_level[i]] * fw[seg_level[i]];
-        plan(n->dec[0].seg[i], HoWo, 4);
-        n->gn_P[i] = cdiv(HoWo, 128) * 4;      // upper bound of mtiles*bm/32 over the tilings
-        // ... and of the packed form-9 launch's records per frame (a seam patch writes one per frame it touches)
-        n->gn_P[i] = std::max(n->gn_P[i], wino_pack_geometry(fh[seg_level[i]], fw[seg_level[i]], B, n->convs[n->dec[0].seg[i]].Cin, true).gn_rows);
-        // a transposed launch's records lie inside that reservation (the rule asks for 8 tile rows: wino_orient_rule); it does not grow
-        bool tr;
-        if (wino_launch_geometry(fh[seg_level[i]], fw[seg_level[i]], B, n->convs[n->dec[0].seg[i]].Cin, true, true, &tr).gn_rows > n->gn_P[i]) { delete n; return FPC_EINVAL; }
-        for (int d = 0; d < 4; ++d) oriented(n->dec[d].seg[i], fh[seg_level[i]], fw[seg_level[i]]);
-        for (int d = 0; d < 4; ++d) {
-            n->gn_part_off[d][i] = n->alloc((size_t)B * n->gn_P[i] * 128 * 2);
-            n->gn_aff_off[d][i] = n->alloc((size_t)B * 128 * 2);
-        }
-    }
-    n->splitk_off = n->alloc(n->splitk_floats);
-    n->total_floats = n->bump;
-    n->pptr.assign(n->pnames.size(), nullptr);
-    *out = n;
-    return FPC_OK;
 }
 
 extern "C" void fpc_net_destroy(fpc_net_t* n) {
@@ -683,6 +130,11 @@ extern "C" int64_t fpc_net_param_numel(const fpc_net_t* n, int i) {
 }
 extern "C" size_t fpc_net_workspace_bytes(const fpc_net_t* n) { return n ? n->total_floats * sizeof(float) : 0; }
 
+// BatchNorm's four parameters from p_bn on, over C channels (eps 1e-5), folded into the scale / shift the epilogues read
+static int fold_bn_of(const fpc_net* n, int p_bn, int C, size_t scale_off, size_t shift_off, hipStream_t s) {
+    return launch_fold_bn(n->pptr[p_bn], n->pptr[p_bn + 1], n->pptr[p_bn + 2], n->pptr[p_bn + 3], 1e-5f, C, n->ws + scale_off, n->ws + shift_off, s);
+}
+
 extern "C" int fpc_net_load_params(fpc_net_t* n, const float* const* params, int count, void* ws, size_t ws_bytes,
                                    fpc_stream_t stream) {
     if (!n || !params || count != (int)n->pnames.size() || !ws) return FPC_EINVAL;
@@ -702,8 +154,7 @@ extern "C" int fpc_net_load_params(fpc_net_t* n, const float* const* params, int
         const PackedConv& c = n->convs[ci];
         if (c.cg) {      // a grouped site: its own image and the folded BatchNorm
             int rg = launch_pack_grouped(n->pptr[c.p_w], n->ws + c.grp_off, c.Cout, c.cg, s);
-            if (!rg) rg = launch_fold_bn(n->pptr[c.p_bn], n->pptr[c.p_bn + 1], n->pptr[c.p_bn + 2], n->pptr[c.p_bn + 3], 1e-5f, c.Cout,
-                                         n->ws + c.scale_off, n->ws + c.shift_off, s);
+            if (!rg) rg = fold_bn_of(n, c.p_bn, c.Cout, c.scale_off, c.shift_off, s);
             if (rg) return rg;
             continue;
         }
@@ -722,8 +173,7 @@ extern "C" int fpc_net_load_params(fpc_net_t* n, const float* const* params, int
             }
         }
         if (c.p_bn >= 0) {
-            rc = launch_fold_bn(n->pptr[c.p_bn], n->pptr[c.p_bn + 1], n->pptr[c.p_bn + 2], n->pptr[c.p_bn + 3], 1e-5f,
-                                c.Cout, n->ws + c.scale_off, n->ws + c.shift_off, s);
+            rc = fold_bn_of(n, c.p_bn, c.Cout, c.scale_off, c.shift_off, s);
             if (rc) return rc;
         }
     }
@@ -733,8 +183,7 @@ extern "C" int fpc_net_load_params(fpc_net_t* n, const float* const* params, int
             if (rc) return rc;
         }
     for (const fpc_net::MbOp& o : n->mops) {      // the MobileNetV2 encoder's ops: the folded BatchNorm (the weights are read in place)
-        const int rc = launch_fold_bn(n->pptr[o.p_bn], n->pptr[o.p_bn + 1], n->pptr[o.p_bn + 2], n->pptr[o.p_bn + 3], 1e-5f, o.Cout,
-                                      n->ws + o.scale_off, n->ws + o.shift_off, s);
+        const int rc = fold_bn_of(n, o.p_bn, o.Cout, o.scale_off, o.shift_off, s);
         if (rc) return rc;
     }
     n->loaded = true;
@@ -930,7 +379,7 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
         a.Cin = 8 * c.Cinp; a.Kw = 1; a.K = c.K; a.lanepx = 1;
         a.p[0] = ConvPtrs{ws + n->a_img4.off, ws + c.w_off, ws + n->a_stem.off, ws + c.scale_off, ws + c.shift_off, nullptr, nullptr, nullptr};
         const float* h3img = n->h3_packed ? ws + n->stem_h3_off : nullptr;
-        const bool ceil = n->enc.ceil_pool();      // the SE-ResNet stem: its pool has no padding (k_stem_pool_h3 is a pad-1 kernel: neither tuned nor forced there)
+        const bool ceil = n->enc.resnet.ceil_pool();      // the SE-ResNet stem: its pool has no padding (k_stem_pool_h3 is a pad-1 kernel: neither tuned nor forced there)
         auto pool_launch = [&]() {
             return ceil ? launch_maxpool3x3s2_ceil(ws + n->a_stem.off, ws + n->a_pool.off, B, n->a_stem.H, n->a_stem.W, 64, s)
                         : launch_maxpool3x3s2(ws + n->a_stem.off, ws + n->a_pool.off, B, n->a_stem.H, n->a_stem.W, 64, n->a_pool.H, n->a_pool.W, s);
@@ -955,7 +404,7 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
             }
         }
     }
-    // encoder stages.  One site: conv `ci` from `in` to `out` with BatchNorm, the residual and ReLU in its epilogue, on whichever
+    // the encoder tape.  One site: conv `ci` from `in` to `out` with BatchNorm, the residual and ReLU in its epilogue, on whichever
     // images the site has
     auto enc_conv = [&](int ci, const Act& in, const Act& out, bool relu, const float* res) -> int {
         long long sb, sh, sw, sc;
@@ -968,23 +417,32 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
         if (c.cg) { a.cg = c.cg; a.grp_w = ws + c.grp_off; }
         return run_conv(n, a, 1, ci, s);
     };
-    for (const fpc_net::Step& st : n->tape) {
-        const float* res = st.res.C ? ws + st.res.off : nullptr;
-        if (st.mb >= 0) {      // an op of the MobileNetV2 encoder
-            const fpc_net::MbOp& o = n->mops[st.mb];
-            const float *w = n->pptr[o.p_w], *sc = ws + o.scale_off, *sh = ws + o.shift_off;
-            if (o.kind == fpc_net::kMbStem) FPC_TRY(launch_stem3x3s2(ws + st.in.off, w, sc, sh, ws + st.out.off, B, st.in.H, st.in.W, s));
-            else if (o.kind == fpc_net::kMbDw) FPC_TRY(launch_dwconv3x3(ws + st.in.off, w, sc, sh, ws + st.out.off, B, st.in.H, st.in.W, st.in.C, o.stride, o.act, s));
-            else FPC_TRY(launch_conv1x1_f32(ws + st.in.off, w, sc, sh, res, ws + st.out.off, (long long)B * st.in.H * st.in.W, o.Cin, o.Cout, o.act, s));
-            continue;
-        }
-        if (st.conv >= 0) { FPC_TRY(enc_conv(st.conv, st.in, st.out, st.relu, res)); continue; }
-        // the gate of an SE block: from Y's channel means, then Y = relu(Y * gate + residual) in place
-        const Act& Y = st.out;
+    // the gate of an SE block: from Y's channel means, then Y = relu(Y * gate + residual) in place.  Refused on a plan built
+    // without the gate's scratch, which lies behind the persistent region where it exists: never at offset 0
+    auto se_gate = [&](int p_se, const Act& Y, const float* res) -> int {
+        if (!n->se_part_off) return FPC_EINVAL;
         FPC_TRY(launch_se_pool(ws + Y.off, ws + n->se_part_off, B, Y.H, Y.W, Y.C, s));
-        FPC_TRY(launch_se_excite(ws + n->se_part_off, n->pptr[st.p_se], n->pptr[st.p_se + 1], n->pptr[st.p_se + 2], n->pptr[st.p_se + 3],
-                                 ws + n->se_gate_off, B, Y.H, Y.W, Y.C, n->enc.se, s));
-        FPC_TRY(launch_se_scale_add_relu(ws + Y.off, ws + n->se_gate_off, res, ws + Y.off, B, Y.H, Y.W, Y.C, s));
+        FPC_TRY(launch_se_excite(ws + n->se_part_off, n->pptr[p_se], n->pptr[p_se + 1], n->pptr[p_se + 2], n->pptr[p_se + 3],
+                                 ws + n->se_gate_off, B, Y.H, Y.W, Y.C, n->enc.resnet.se, s));
+        return launch_se_scale_add_relu(ws + Y.off, ws + n->se_gate_off, res, ws + Y.off, B, Y.H, Y.W, Y.C, s);
+    };
+    // an op of the MobileNetV2 encoder, on the one kernel of its kind
+    auto mb_op = [&](const fpc_net::MbOp& o, const Act& in, const Act& out, const float* res) -> int {
+        const float *w = n->pptr[o.p_w], *sc = ws + o.scale_off, *sh = ws + o.shift_off;
+        switch (o.kind) {
+        case fpc_net::kMbStem: return launch_stem3x3s2(ws + in.off, w, sc, sh, ws + out.off, B, in.H, in.W, s);
+        case fpc_net::kMbDw: return launch_dwconv3x3(ws + in.off, w, sc, sh, ws + out.off, B, in.H, in.W, in.C, o.stride, o.act, s);
+        case fpc_net::kMbPw: return launch_conv1x1_f32(ws + in.off, w, sc, sh, res, ws + out.off, (long long)B * in.H * in.W, o.Cin, o.Cout, o.act, s);
+        }
+        return FPC_EINVAL;
+    };
+    for (const Step& st : n->tape) {
+        const float* res = st.res.C ? ws + st.res.off : nullptr;
+        switch (st.kind) {
+        case kStepConv: FPC_TRY(enc_conv(st.op, st.in, st.out, st.relu, res)); break;
+        case kStepSeGate: FPC_TRY(se_gate(st.op, st.out, res)); break;
+        case kStepMb: FPC_TRY(mb_op(n->mops[st.op], st.in, st.out, res)); break;
+        }
     }
     const Act* feat = n->a_feat;
 
@@ -1382,7 +840,7 @@ extern "C" int fpc_net_force_direct_h3(fpc_net_t* n, int on) {
 extern "C" int fpc_net_force_stem_pool(fpc_net_t* n, int on) {
     if (!n || on < 0 || on > 1 || (on && !n->h3_packed)) return FPC_EINVAL;
     if (n->c_stem < 0) return FPC_EINVAL;      // the MobileNetV2 encoder: no 7x7 stem and no max-pool, whatever `on` is
-    if (on && n->enc.ceil_pool()) return FPC_EINVAL;      // the SE-ResNet stem pool has no padding: the fused launch computes another pool
+    if (on && n->enc.resnet.ceil_pool()) return FPC_EINVAL;      // the SE-ResNet stem pool has no padding: the fused launch computes another pool
     if (on && ((n->a_stem.H & 1) || (n->a_stem.W & 63) || (long long)n->H * n->W * 16 >= (1LL << 31))) return FPC_EINVAL;
     ConvPlan& p = n->cplan[n->c_stem];
     if (p.pool == on) return 0;

@@ -1,0 +1,424 @@
+// net_build.hip — how a plan of the backbone engine (net_plan.hpp: fpc_net) is built, host arithmetic only: the encoders
+// fpc_net_create knows by name, the four creation entry points, the two encoder families' builders and net_build, which puts a
+// family's encoder in front of the four FPN decoders and heads and plans every convolution site.  The graph is the one
+// segmentation_models_pytorch builds for FastPoseCNN (fastposecnn_amd/lib/backbone.py).  Nothing here launches a kernel.
+#include <stdio.h>
+#include <stdlib.h>
+
+#include "net_plan.hpp"
+
+static const char* kDecNames[4] = {"mask_decoder", "rotation_decoder", "translation_decoder", "scales_decoder"};
+static const char* kHeadNames[4] = {"segmentation_head", "rotation_head", "translation_head", "scales_head"};
+
+// ---- An encoder family is two functions (kFamilies, below).  `params` adds the stem and every encoder site and parameter to the
+// persistent region, in state-dict order; `buffers`, called once the persistent region is complete, allocates the stem and stage
+// activations and any scratch of its own and writes the tape and a_feat.  What the first leaves for the second, and for net_build:
+struct ResBlock { int conv[3], ds, p_se, stride, ch[kBufCount]; };      // a block kind's block: its sites as created, its stride, channels by Buf
+struct MbBlock { int expand, dw, proj, stage; };      // ops of fpc_net::mops (-1: the block has none); stage -1: in front of c2's
+struct EncoderBuild {
+    int featc[4];                     // channels of c2 .. c5
+    std::vector<int> h3_sites;        // the encoder sites that are candidates for the three-product direct form (PackedConv::h3_ok)
+    std::vector<ResBlock> res[4];     // the ResNet family's blocks by stage
+    std::vector<MbBlock> mb;          // the MobileNetV2 encoder's blocks
+};
+
+// ---- the ResNet family: the 7x7 / stride-2 stem (3 -> 64, BatchNorm, ReLU) and its 3x3 / stride-2 max-pool, then for L = 0 .. 3
+// a stage of enc.layers[L] blocks of the encoder's BlockKind on 64 << L planes, the first block of every stage but the first with stride 2.
+static void resnet_params(fpc_net* n, EncoderBuild& eb) {
+    const EncoderDesc& enc = n->enc;
+    const ResNetDesc& rd = enc.resnet;
+    const BlockKind& kind = rd.kind();
+    const std::string stem(rd.stem_prefix());
+    n->c_stem = n->add_conv(stem + "conv1.weight", 3, 64, 7, 2, 3, (stem + "bn1").c_str(), nullptr, 4, 8);     // NHWC4 pixels, 8 taps per row
+    int inpl = 64;
+    for (int L = 0; L < 4; ++L) {
+        const int planes = 64 << L;
+        const int mid = planes * rd.width / 64 * rd.groups, C = rd.expansion * planes;      // (mid: planes but in the ResNeXt encoders)
+        for (int bi = 0; bi < enc.layers[L]; ++bi) {
+            ResBlock blk{{-1, -1, -1}, -1, -1, (bi == 0 && L > 0) ? 2 : 1, {0, inpl, mid, mid, C, C, C}};      // (channels by Buf)
+            const int* ch = blk.ch;
+            const std::string p = "encoder.layer" + std::to_string(L + 1) + "." + std::to_string(bi);
+            for (int i = 0; i < kind.nsites; ++i) {
+                const BlockSite& st = kind.site[i];
+                const std::string w = p + ".conv" + std::to_string(i + 1) + ".weight", bn = p + ".bn" + std::to_string(i + 1);
+                const int stride = st.strided ? blk.stride : 1;
+                blk.conv[i] = st.grouped && rd.groups > 1 ? n->add_grouped_conv(w, ch[st.out], ch[st.out] / rd.groups, stride, bn.c_str())
+                                                          : n->add_conv(w, ch[st.in], ch[st.out], st.k, stride, st.k / 2, bn.c_str(), nullptr);
+            }
+            if (kind.se_gate) {      // plain parameters, read in place
+                const int Cr = C / rd.se;
+                blk.p_se = n->add_param(p + ".se_module.fc1.weight", (int64_t)Cr * C);
+                n->add_param(p + ".se_module.fc1.bias", Cr);
+                n->add_param(p + ".se_module.fc2.weight", (int64_t)C * Cr);
+                n->add_param(p + ".se_module.fc2.bias", C);
+            }
+            if (blk.stride != 1 || inpl != C)
+                blk.ds = n->add_conv(p + ".downsample.0.weight", inpl, C, 1, blk.stride, 0, (p + ".downsample.1").c_str(), nullptr);
+            inpl = C;
+            eb.res[L].push_back(blk);
+        }
+        eb.featc[L] = C;
+    }
+    if (enc.basic())      // the three-product direct form's candidates: the strided first site and the downsample of every stage but the first
+        for (int L = 1; L < 4; ++L) {
+            eb.h3_sites.push_back(eb.res[L][0].conv[0]);
+            if (eb.res[L][0].ds >= 0) eb.h3_sites.push_back(eb.res[L][0].ds);
+        }
+}
+
+static void resnet_buffers(fpc_net* n, const EncoderBuild& eb) {
+    const ResNetDesc& rd = n->enc.resnet;
+    const BlockKind& kind = rd.kind();
+    const int h1 = conv_out(n->H, 7, 2, 3), w1 = conv_out(n->W, 7, 2, 3);
+    n->a_stem = n->alloc_act(h1, w1, 64);
+    n->a_pool = rd.ceil_pool() ? n->alloc_act(h1 / 2, w1 / 2, 64) : n->alloc_act(conv_out(h1, 3, 2, 1), conv_out(w1, 3, 2, 1), 64);
+    // the blocks' buffers and the encoder tape
+    Act cur = n->a_pool;
+    for (int L = 0; L < 4; ++L) {
+        Act b[kBufCount], y[2];
+        for (size_t bi = 0; bi < eb.res[L].size(); ++bi) {
+            const ResBlock& blk = eb.res[L][bi];
+            // sizes by role: the input's in front of the strided site, the block's output size (h, w) from it on
+            const int h = conv_out(cur.H, 3, blk.stride, 1), w = conv_out(cur.W, 3, blk.stride, 1);
+            Act sz[kBufCount]; bool past = false;
+            for (int i = 0; i < kind.nsites; ++i) {
+                past = past || kind.site[i].strided;
+                sz[kind.site[i].out] = Act{0, past ? h : cur.H, past ? w : cur.W, blk.ch[kind.site[i].out]};
+            }
+            // storage, in this order: T1, T2, the output(s), D.  A shared stage allocates once, at block 0, whose T1 is the largest
+            // (a Bottleneck's conv1 there runs at the stage's INPUT resolution), and D whether or not a later block needs it
+            if (!kind.shared || bi == 0) {
+                auto alloc_like = [&](const Act& t) { return n->alloc_act(t.H, t.W, t.C); };
+                b[kBufT1] = alloc_like(sz[kBufT1]); if (kind.nsites == 3) b[kBufT2] = alloc_like(sz[kBufT2]);
+                y[0] = alloc_like(sz[kBufY]); if (kind.shared) y[1] = alloc_like(sz[kBufY]);
+                if (kind.shared || blk.ds >= 0) b[kBufD] = alloc_like(sz[kBufY]);
+            }
+            b[kBufT1].H = sz[kBufT1].H; b[kBufT1].W = sz[kBufT1].W;      // (a later block's view of a shared T1)
+            b[kBufIn] = cur; b[kBufY] = y[kind.shared ? bi & 1 : 0]; b[kBufRes] = blk.ds >= 0 ? b[kBufD] : cur;
+            // steps, in launch order
+            for (int i = 0; i < kind.nsites; ++i) {
+                const BlockSite& st = kind.site[i];
+                if (i == kind.ds_before && blk.ds >= 0) n->tape.push_back(conv_step(blk.ds, cur, b[kBufD], false));
+                n->tape.push_back(conv_step(blk.conv[i], b[st.in], b[st.out], st.relu, b[st.res]));
+            }
+            if (kind.se_gate) n->tape.push_back(se_gate_step(blk.p_se, b[kBufY], b[kBufRes]));
+            cur = b[kBufY];
+        }
+        n->a_feat[L] = cur;
+    }
+    if (kind.se_gate) {      // the gate of one block at a time: [B][C] and the slab partials of the stage with the most
+        size_t part = 0;
+        for (const Act& f : n->a_feat) part = std::max(part, (size_t)se_pool_slabs(f.H, f.W, f.C) * f.C);
+        n->se_gate_off = n->alloc((size_t)n->B * n->a_feat[3].C);
+        n->se_part_off = n->alloc((size_t)n->B * part);
+    }
+}
+
+// ---- the MobileNetV2 encoder: torchvision's mobilenet_v2().features as smp's MobileNetV2Encoder walks it.  features.0 is the 3x3 /
+// stride-2 stem (3 -> 32, BatchNorm, ReLU6); features.1 .. 17 are InvertedResidual blocks by the (t, c, n, s) table: an expand 1x1
+// inp -> t inp with BatchNorm and ReLU6 (absent where t = 1), a depthwise 3x3 with the block's stride, BatchNorm and ReLU6, a project
+// 1x1 to c channels with BatchNorm only, and the block's input added where the stride is 1 and inp = c (no activation behind it);
+// features.18 is the 1x1 320 -> 1280 with BatchNorm and ReLU6.  smp's first stage ends behind features.1; the four behind it, of
+// enc.layers = {2, 3, 7, 5} feature modules (they end behind features.3 / 6 / 13 / 18), give c2 .. c5 of 24 / 32 / 96 / 1280
+// channels.  Parameters in state-dict order (conv weight, then BatchNorm's four), read in place.
+static const int kMbTable[7][4] = {{1, 16, 1, 1}, {6, 24, 2, 2}, {6, 32, 3, 2}, {6, 64, 4, 2}, {6, 96, 3, 1}, {6, 160, 3, 2}, {6, 320, 1, 1}};
+
+// the stage (-1: in front of c2's) of feature module idx >= 1
+static int mbv2_stage(const EncoderDesc& enc, int idx) {
+    int stage = -1;
+    for (int end = 1; stage < 3 && idx > end; end += enc.layers[stage]) ++stage;
+    return stage;
+}
+
+static void mbv2_params(fpc_net* n, EncoderBuild& eb) {
+    const std::string f("encoder.features.");
+    n->add_mop(fpc_net::kMbStem, f + "0.0.weight", 32 * 27, f + "0.1", 3, 32, 2, 1);
+    int inp = 32, idx = 1;
+    for (const auto& row : kMbTable)
+        for (int i = 0; i < row[2]; ++i, ++idx) {
+            const int t = row[0], oup = row[1], stride = i == 0 ? row[3] : 1, hid = inp * t;
+            const std::string p = f + std::to_string(idx) + ".conv.";
+            MbBlock b{-1, -1, -1, mbv2_stage(n->enc, idx)};
+            const int k = t != 1 ? 1 : 0;      // the depthwise's place in `conv`
+            if (k) b.expand = n->add_mop(fpc_net::kMbPw, p + "0.0.weight", (int64_t)hid * inp, p + "0.1", inp, hid, 1, 1);
+            b.dw = n->add_mop(fpc_net::kMbDw, p + std::to_string(k) + ".0.weight", (int64_t)hid * 9, p + std::to_string(k) + ".1", hid, hid, stride, 1);
+            b.proj = n->add_mop(fpc_net::kMbPw, p + std::to_string(k + 1) + ".weight", (int64_t)oup * hid, p + std::to_string(k + 2), hid, oup, 1, 0);
+            eb.mb.push_back(b);
+            inp = oup;
+        }
+    eb.mb.push_back(MbBlock{-1, -1, n->add_mop(fpc_net::kMbPw, f + "18.0.weight", (int64_t)1280 * inp, f + "18.1", inp, 1280, 1, 1), mbv2_stage(n->enc, idx)});
+    for (const MbBlock& b : eb.mb)      // (a stage's channels: its last block's)
+        if (b.stage >= 0) eb.featc[b.stage] = n->mops[b.proj].Cout;
+}
+
+// Its buffers and tape.  Per stage: the largest expanded tensor, the largest depthwise output and two outputs the blocks take in turn
+// (a block's input is its residual, so it never writes over it); a stage's last output stays: a_feat.  No pooled tensor: a_pool
+// stays empty.
+static void mbv2_buffers(fpc_net* n, const EncoderBuild& eb) {
+    const size_t B = (size_t)n->B;
+    n->a_stem = n->alloc_act(n->H / 2, n->W / 2, 32);
+    n->mops[0].howo = (long long)n->a_stem.H * n->a_stem.W;
+    n->tape.push_back(mb_step(0, n->a_img4, n->a_stem));
+    Act cur = n->a_stem;
+    for (int stage = -1; stage < 4; ++stage) {
+        size_t fe = 0, fd = 0, fy = 0;
+        int h = cur.H, w = cur.W, count = 0;
+        for (const MbBlock& b : eb.mb) {
+            if (b.stage != stage) continue;
+            ++count;
+            if (b.expand >= 0) fe = std::max(fe, (size_t)h * w * n->mops[b.expand].Cout);
+            if (b.dw >= 0) {
+                h = conv_out(h, 3, n->mops[b.dw].stride, 1); w = conv_out(w, 3, n->mops[b.dw].stride, 1);
+                fd = std::max(fd, (size_t)h * w * n->mops[b.dw].Cout);
+            }
+            fy = std::max(fy, (size_t)h * w * n->mops[b.proj].Cout);
+        }
+        Act E, D, Y[2];
+        if (fe) E.off = n->alloc(B * fe);
+        if (fd) D.off = n->alloc(B * fd);
+        Y[0].off = n->alloc(B * fy);
+        if (count > 1) Y[1].off = n->alloc(B * fy);
+        int turn = 0;
+        auto view = [&](Act t, int th, int tw, int op) {
+            t.H = th; t.W = tw; t.C = n->mops[op].Cout;
+            n->mops[op].howo = (long long)th * tw;
+            return t;
+        };
+        for (const MbBlock& b : eb.mb) {
+            if (b.stage != stage) continue;
+            const Act in = cur;
+            Act x = cur;
+            if (b.expand >= 0) { const Act e = view(E, x.H, x.W, b.expand); n->tape.push_back(mb_step(b.expand, x, e)); x = e; }
+            if (b.dw >= 0) {
+                const int st = n->mops[b.dw].stride;
+                const Act d = view(D, conv_out(x.H, 3, st, 1), conv_out(x.W, 3, st, 1), b.dw);
+                n->tape.push_back(mb_step(b.dw, x, d));
+                x = d;
+            }
+            const Act y = view(Y[turn], x.H, x.W, b.proj);
+            turn = count > 1 ? turn ^ 1 : 0;
+            const bool res = b.dw >= 0 && n->mops[b.dw].stride == 1 && in.C == y.C;
+            n->tape.push_back(mb_step(b.proj, x, y, res ? in : Act()));
+            cur = y;
+        }
+        if (stage >= 0) n->a_feat[stage] = cur;
+    }
+}
+
+static const struct {
+    void (*params)(fpc_net* n, EncoderBuild& eb);
+    void (*buffers)(fpc_net* n, const EncoderBuild& eb);
+} kFamilies[kFamilyCount] = {{resnet_params, resnet_buffers}, {mbv2_params, mbv2_buffers}};      // by EncoderFamily
+
+// The plan of `n` (its encoder descriptor set) for (classes, B, H, W); owns `n` (deleted on failure).  The persistent region (packed
+// weights, folded BatchNorm, weight images) comes first, then the activations and scratch.
+static int net_build(fpc_net* n, int classes, int B, int H, int W, fpc_net_t** out) {
+    n->classes = classes; n->B = B; n->H = H; n->W = W;
+    {   // merge + head in two passes (merge_split.hip) unless FPC_MERGE_SPLIT=0; read once, here
+        const char* e = getenv("FPC_MERGE_SPLIT");
+        n->merge_split = e ? (atoi(e) != 0) : 1;      // (one frame: 27 us in two passes against 32.5 us in one)
+        // 9 to 32 classes: the four-pixel x4 upsample + compression (k_up4_compress_wide) unless FPC_UP4_WIDE=0 (k_up4_compress<32>)
+        const char* u = getenv("FPC_UP4_WIDE");
+        n->up4_wide = u ? (atoi(u) != 0) : 1;
+    }
+    char buf[256];
+
+    // ---- parameters + packed storage
+    const EncoderDesc& enc = n->enc;
+    const auto& family = kFamilies[enc.family];
+    EncoderBuild eb;
+    family.params(n, eb);
+    const int* featc = eb.featc;
+    const int G = classes - 1;
+    const int head_ch[4] = {classes, 4 * G, 3 * G, 3 * G};
+    for (int d = 0; d < 4; ++d) {
+        std::string D(kDecNames[d]);
+        fpc_net::Dec& dc = n->dec[d];
+        dc.lat[0] = n->add_conv(D + ".p5.weight", featc[3], 256, 1, 1, 0, nullptr, (D + ".p5.bias").c_str());
+        const int skipc[3] = {featc[2], featc[1], featc[0]};
+        for (int i = 0; i < 3; ++i) {
+            snprintf(buf, sizeof(buf), "%s.p%d.skip_conv", kDecNames[d], 4 - i);
+            std::string p(buf);
+            dc.lat[1 + i] = n->add_conv(p + ".weight", skipc[i], 256, 1, 1, 0, nullptr, (p + ".bias").c_str());
+        }
+        const int nconv[4] = {3, 2, 1, 1};
+        int si = 0;
+        for (int sb = 0; sb < 4; ++sb)
+            for (int j = 0; j < nconv[sb]; ++j) {
+                snprintf(buf, sizeof(buf), "%s.seg_blocks.%d.block.%d.block", kDecNames[d], sb, j);
+                std::string p(buf);
+                dc.seg[si] = n->add_conv(p + ".0.weight", j == 0 ? 256 : 128, 128, 3, 1, 1, nullptr, nullptr);
+                dc.p_gn[si] = n->add_param(p + ".1.weight", 128);
+                n->add_param(p + ".1.bias", 128);
+                ++si;
+            }
+    }
+    for (int d = 0; d < 4; ++d) {
+        fpc_net::Dec& dc = n->dec[d];
+        dc.head_ch = head_ch[d];
+        dc.head_chp = (head_ch[d] + 3) / 4 * 4;
+        dc.p_head_w = n->add_param(std::string(kHeadNames[d]) + ".0.weight", (int64_t)head_ch[d] * 128);
+        dc.p_head_b = n->add_param(std::string(kHeadNames[d]) + ".0.bias", head_ch[d]);
+        // a head past one 32-channel matrix tile (10 classes and more) has the two-pass form only: k_merge_head is not widened, and
+        // FPC_MERGE_SPLIT=0 does not apply to such a plan
+        if (dc.head_chp > 32) n->merge_split = 1;
+    }
+    n->fold_ok = enc.basic();
+    if (n->fold_ok)
+        for (int d = 0; d < 4; ++d) {
+            n->fold_wc_off[d] = n->alloc((size_t)128 * 64 * 9);
+            n->fold_img1_off[d] = n->alloc((size_t)16 * 128 * 64 + 2);
+            n->fold_img2_off[d] = n->alloc((size_t)16 * 128 * 256 + 2);
+            n->fold_tab_off[d] = n->alloc((size_t)16 * 128);
+        }
+    // the three-product direct form's weight images, only where it is a candidate: the sites the encoder names and, behind a
+    // BasicBlock encoder, the laterals (not the p2 lateral: folded away)
+    std::vector<int> h3_sites = eb.h3_sites;
+    if (enc.basic())
+        for (int d = 0; d < 4; ++d)
+            for (int i = 0; i < 3; ++i) h3_sites.push_back(n->dec[d].lat[i]);
+    for (int ci : h3_sites) {
+        PackedConv& c = n->convs[ci];
+        if (c.wino_ok || c.Cin % kConvBK != 0 || c.Cinp != c.Cin || c.Kh * c.Kw > 32) continue;
+        c.h3_ok = true;
+        c.h3_off = n->alloc(h3_packed_floats(c.Npad, c.Kpad));
+    }
+    if (n->c_stem >= 0) n->stem_h3_off = n->alloc(h3_packed_floats(n->convs[n->c_stem].Npad, n->convs[n->c_stem].Kpad));      // every encoder with the 7x7 stem shares it
+    n->zeros_off = n->alloc(64);
+    n->tickets_off = n->alloc(kConvTickets);
+    n->packed_floats = n->bump;
+
+    // ---- activations
+    n->a_img4 = n->alloc_act(H, W, 4);
+    family.buffers(n, eb);
+    int fh[4], fw[4];
+    for (int L = 0; L < 4; ++L) { fh[L] = n->a_feat[L].H; fw[L] = n->a_feat[L].W; }
+    // FPN needs exact x2 relations between levels
+    for (int L = 1; L < 4; ++L)
+        if (fh[L - 1] != 2 * fh[L] || fw[L - 1] != 2 * fw[L]) { delete n; return FPC_EINVAL; }
+    // seg conv geometry: index -> (resolution level): s5.0@L3, s5.1@L2, s5.2@L1, s4.0@L2, s4.1@L1, s3.0@L1, s2.0@L0
+    const int seg_level[7] = {3, 2, 1, 2, 1, 1, 0};
+    for (int d = 0; d < 4; ++d) {
+        for (int i = 0; i < 4; ++i) n->a_p[d][i] = n->alloc_act(fh[3 - i], fw[3 - i], 256);
+        for (int i = 0; i < 7; ++i) n->a_seg[d][i] = n->alloc_act(fh[seg_level[i]], fw[seg_level[i]], 128);
+        n->a_up[d][0] = n->alloc_act(fh[2], fw[2], 128);   // up2(s5.0)
+        n->a_up[d][1] = n->alloc_act(fh[1], fw[1], 128);   // up2(s5.1)
+        n->a_up[d][2] = n->alloc_act(fh[1], fw[1], 128);   // up2(s4.0)
+        n->a_low[d] = n->alloc_act(fh[0], fw[0], n->dec[d].head_chp);
+        n->a_lsum[d] = n->alloc_act(fh[1], fw[1], n->dec[d].head_chp);
+    }
+
+    // ---- conv plans (+ split-K scratch for the worst candidate, GroupNorm partials for the largest P32)
+    n->cplan.resize(n->convs.size());
+    n->tune_score.assign(n->convs.size(), 0.f);
+    n->free_plan.assign(n->convs.size(), ConvPlan());
+    n->has_free.assign(n->convs.size(), 0);
+    n->guarded.assign(n->convs.size(), 0);
+    n->c_howo.assign(n->convs.size(), 0);
+    n->c_groups.assign(n->convs.size(), 0);
+    n->c_tr.assign(n->convs.size(), 0);
+    auto oriented = [&](int ci, int h, int w) { if (ci >= 0 && n->convs[ci].wino_ok) n->c_tr[ci] = wino_orient_rule(h, w) ? 1 : 0; };
+    auto plan = [&](int ci, int HoWo, int groups) {
+        const PackedConv& c = n->convs[ci];
+        n->c_howo[ci] = HoWo; n->c_groups[ci] = groups;
+        if (c.cg) { ConvPlan q; q.grp = 1; n->cplan[ci] = q; return; }      // a grouped site: k_conv3x3_grouped's form 0, no split-K scratch
+        n->cplan[ci] = plan_conv(HoWo, B, c.Cout, c.Kpad / kConvBK, groups);
+        size_t need = splitk_floats_for(n->cplan[ci], groups, B, c.Npad);
+        for (const ConvPlan& q : conv_candidates(HoWo, B, c.Cout, c.Kpad / kConvBK, groups)) {
+            size_t f = splitk_floats_for(q, groups, B, c.Npad);
+            if (f * sizeof(float) <= ((size_t)256 << 20) && f > need) need = f;
+        }
+        if (need > n->splitk_floats) n->splitk_floats = need;
+    };
+    if (n->c_stem >= 0) plan(n->c_stem, n->a_stem.H * n->a_stem.W, 1);
+    // (the orientation rule is asked with the step's own output size.  A Winograd site has stride 1 (PackedConv::wino_ok), so that is
+    // the stage's output size at every site the mark matters for: a strided conv1, whose input is larger, is never one)
+    for (const Step& st : n->tape)
+        if (st.kind == kStepConv) { plan(st.op, st.out.H * st.out.W, 1); oriented(st.op, st.out.H, st.out.W); }
+    for (int i = 0; i < 4; ++i) {
+        plan(n->dec[0].lat[i], fh[3 - i] * fw[3 - i], 4);
+        // a lateral whose channels the fast loader does not take (c2 of the MobileNetV2 encoder: 24) runs on the Cin % 4 loader
+        // (lateral_mode), through the same grouped launch with the top-down addend: what that loader asks of the site, checked here
+        if (lateral_mode(n->convs[n->dec[0].lat[i]]) == 2 && (featc[3 - i] % 4 != 0 || ((fh[3 - i] | fw[3 - i]) & 1))) { delete n; return FPC_EINVAL; }
+    }
+    for (int i = 0; i < 7; ++i) {
+        int HoWo = fh[seg_level[i]] * fw[seg_level[i]];
+        plan(n->dec[0].seg[i], HoWo, 4);
+        n->gn_P[i] = cdiv(HoWo, 128) * 4;      // upper bound of mtiles*bm/32 over the tilings
+        // ... and of the packed form-9 launch's records per frame (a seam patch writes one per frame it touches)
+        n->gn_P[i] = std::max(n->gn_P[i], wino_pack_geometry(fh[seg_level[i]], fw[seg_level[i]], B, n->convs[n->dec[0].seg[i]].Cin, true).gn_rows);
+        // a transposed launch's records lie inside that reservation (the rule asks for 8 tile rows: wino_orient_rule); it does not grow
+        bool tr;
+        if (wino_launch_geometry(fh[seg_level[i]], fw[seg_level[i]], B, n->convs[n->dec[0].seg[i]].Cin, true, true, &tr).gn_rows > n->gn_P[i]) { delete n; return FPC_EINVAL; }
+        for (int d = 0; d < 4; ++d) oriented(n->dec[d].seg[i], fh[seg_level[i]], fw[seg_level[i]]);
+        for (int d = 0; d < 4; ++d) {
+            n->gn_part_off[d][i] = n->alloc((size_t)B * n->gn_P[i] * 128 * 2);
+            n->gn_aff_off[d][i] = n->alloc((size_t)B * 128 * 2);
+        }
+    }
+    n->splitk_off = n->alloc(n->splitk_floats);
+    n->total_floats = n->bump;
+    n->pptr.assign(n->pnames.size(), nullptr);
+    *out = n;
+    return FPC_OK;
+}
+
+// The one creation path: the checks every entry shares, then the plan.  A wrapper keeps only the refusals of its own arguments.
+static int create(EncoderDesc d, const int* layers4, int classes, int B, int H, int W, fpc_net_t** out) {
+    if (!layers4 || !out || classes < 2 || classes > 32 || B < 1 || H < 32 || W < 32 || H % 32 || W % 32) return FPC_EINVAL;
+    for (int L = 0; L < 4; ++L)
+        if (layers4[L] < 1 || layers4[L] > 64) return FPC_EINVAL;
+    memcpy(d.layers, layers4, sizeof(d.layers));
+    return net_build(new fpc_net{d}, classes, B, H, W, out);
+}
+
+// the encoders fpc_net_create knows by name: {family, {expansion, groups, width, se reduction}, layers}
+static const struct { const char* name; EncoderDesc desc; } kEncoders[] = {
+    {"resnet18", {kFamilyResNet, {1, 1, 64, 0}, {2, 2, 2, 2}}}, {"resnet34", {kFamilyResNet, {1, 1, 64, 0}, {3, 4, 6, 3}}},
+    // the ResNeXt encoders: Bottleneck x {3,4,6,3} / {3,4,23,3} with 32 groups of width 4 (8) on conv2
+    {"resnext50_32x4d", {kFamilyResNet, {4, 32, 4, 0}, {3, 4, 6, 3}}},
+    {"resnext101_32x4d", {kFamilyResNet, {4, 32, 4, 0}, {3, 4, 23, 3}}},
+    {"resnext101_32x8d", {kFamilyResNet, {4, 32, 8, 0}, {3, 4, 23, 3}}},
+    // the SE-ResNets: pretrainedmodels' SEResNetBottleneck x {3,4,6,3} / {3,4,23,3} / {3,8,36,3}, reduction 16
+    {"se_resnet50", {kFamilyResNet, {4, 1, 64, 16}, {3, 4, 6, 3}}},
+    {"se_resnet101", {kFamilyResNet, {4, 1, 64, 16}, {3, 4, 23, 3}}},
+    {"se_resnet152", {kFamilyResNet, {4, 1, 64, 16}, {3, 8, 36, 3}}},
+    // the MobileNetV2 encoder (above); layers: the feature modules in each stage of smp's last four
+    {"mobilenet_v2", {kFamilyMobileNetV2, {}, {2, 3, 7, 5}}},
+};
+
+extern "C" int fpc_net_create(const char* encoder, int classes, int B, int H, int W, fpc_net_t** out) {
+    for (const auto& e : kEncoders)
+        if (encoder && !strcmp(encoder, e.name)) return create(e.desc, e.desc.layers, classes, B, H, W, out);
+    return FPC_EINVAL;
+}
+
+// An encoder by its descriptor: block 1 = BasicBlock, 4 = Bottleneck (torchvision's: the stride on the 3x3), layers4 = blocks per
+// stage.  (1, {2,2,2,2}) and (1, {3,4,6,3}) are the plans fpc_net_create builds for "resnet18" / "resnet34".
+extern "C" int fpc_net_create_encoder(int block, const int* layers4, int classes, int B, int H, int W, fpc_net_t** out) {
+    return fpc_net_create_encoder_ex(block, layers4, 1, 64, classes, B, H, W, out);
+}
+
+// ... with torchvision's `groups` and `width_per_group`: a Bottleneck's conv2 is then a grouped 3x3 of planes * width / 64 * groups
+// channels (k_conv3x3_grouped) between 1x1 sites of that width; (groups, width) = (1, 64) is fpc_net_create_encoder.  Refused:
+// groups > 1 on BasicBlock, a width other than 64 without groups, channels per group outside k_conv3x3_grouped's set at any stage.
+extern "C" int fpc_net_create_encoder_ex(int block, const int* layers4, int groups, int width_per_group, int classes, int B, int H,
+                                         int W, fpc_net_t** out) {
+    if (block != 1 && block != 4) return FPC_EINVAL;
+    if (groups < 1 || width_per_group < 1 || (groups == 1 && width_per_group != 64) || (groups > 1 && block != 4)) return FPC_EINVAL;
+    if (groups > 1)
+        for (int planes = 64; planes <= 512; planes *= 2) {
+            const int cg = planes * width_per_group / 64;      // torchvision: width = int(planes * base_width / 64) * groups
+            if (!grouped_cg_ok(cg) || (long long)cg * groups > 8192 || (cg * groups) % 64) return FPC_EINVAL;
+        }
+    return create({kFamilyResNet, {block, groups, width_per_group}}, layers4, classes, B, H, W, out);
+}
+
+// The SE-ResNet encoders: SEResNetBottleneck x layers4 — conv1 1x1 WITH the stride, conv2 a dense 3x3 / stride 1 (a Winograd site at
+// every stage), conv3 1x1 x 4 with BatchNorm only, then the gate of se.hip (fc1 C -> C / reduction, fc2 back, both with bias) and the
+// scale + residual + ReLU pass; parameters named as pretrainedmodels' (encoder.layer0.conv1.weight, encoder.layerN.i.se_module.fc1.bias).
+// Refused: a reduction that does not divide 256 (the narrowest stage output).
+extern "C" int fpc_net_create_encoder_se(const int* layers4, int reduction, int classes, int B, int H, int W, fpc_net_t** out) {
+    if (reduction < 1 || 256 % reduction) return FPC_EINVAL;
+    return create({kFamilyResNet, {4, 1, 64, reduction}}, layers4, classes, B, H, W, out);
+}
