@@ -143,6 +143,9 @@ _SIGNATURES = {
     "fpc_conv1x1_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
     "fpc_conv1x1_f32_form": (_i, [_i64, _i, _i]),
     "fpc_stem3x3s2": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "fpc_dwconv3x3_dgrad": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "fpc_dwconv3x3_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "fpc_dwconv3x3_wgrad": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "fpc_se_gate_train": (_i, [_vp] * 9 + [_i, _i, _i, _i, _i, _vp]),
     "fpc_se_bwd_scratch_floats": (_sz, [_i, _i, _i, _i, _i]),
     "fpc_se_bwd": (_i, [_vp] * 15 + [_i, _i, _i, _i, _i, _vp]),
@@ -156,6 +159,8 @@ _SIGNATURES = {
     "fpc_batchnorm_scratch_floats": (_sz, [_i, _i]),
     "fpc_batchnorm_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _i, _vp]),
     "fpc_batchnorm_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "fpc_batchnorm_act_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _i, _vp]),
+    "fpc_batchnorm_act_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "fpc_conv2d_wgrad": (_i, [_vp, _i64, _i64, _i64, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "fpc_conv2d_wgrad_split": (_i, [_vp, _i64, _i64, _i64, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
 }

@@ -1,12 +1,12 @@
 // batchnorm.hip — training-mode BatchNorm2d on channel-last activations, fused with the residual add and the ReLU that follow
-// it in a ResNet block, forward and backward, for the training step (BASELINE.json configs[4]).  The reference's encoder is
+// it in a ResNet block — or with the ReLU6 behind it in a MobileNetV2 block —, forward and backward, for the training step (BASELINE.json configs[4]).  The reference's encoder is
 // the smp / torchvision ResNet built at F/lib/pose_regressor.py:608: conv -> BatchNorm2d -> ReLU, and at a block's end
 // conv -> BatchNorm2d -> (+ identity) -> ReLU, under autograd; torch runs that as three MIOpen kernels plus an aten add and
 // ReLU each way.
 //
 // Activations are [P, C] f32, P = B H W pixels, C a multiple of 4; the statistics of a channel run over all P pixels:
-//   forward   mean, var (biased) per channel; z = (x - mean) rstd gamma + beta (+ res); y = relu(z) or z
-//   backward  g = dy [y > 0] (the mask from the SAVED output: bit-consistent with the forward) or dy;
+//   forward   mean, var (biased) per channel; z = (x - mean) rstd gamma + beta (+ res); y = relu(z), min(max(z, 0), 6) or z
+//   backward  g = dy [y > 0], dy [0 < y < 6] (the mask from the SAVED output: bit-consistent with the forward) or dy;
 //             dbeta = sum g, dgamma = sum g xhat;  dx = gamma rstd (g - dbeta / P - xhat dgamma / P);  dres = g
 // Three launches each way: per-chunk partial sums (f32 per thread over <= 8 values, combined in double), one fold of the
 // partials per channel quad (double, a fixed tree: deterministic; no atomics), then the elementwise pass.  A workgroup of the
@@ -31,7 +31,7 @@ struct BnArgs {
     float* part;          // [chunks][C][2]: forward {sum, centred sum of squares}, backward {sum g, sum g xhat}
     float* stats;         // [C][2] mean, rstd (written by the forward, read by the backward)
     float* dgamma; float* dbeta;      // [C]
-    int P, C, Q, chunks, relu;
+    int P, C, Q, chunks, act;      // act: 0 none, 1 ReLU, 2 ReLU6
     float eps, momentum;
 };
 
@@ -157,7 +157,7 @@ __global__ __launch_bounds__(256) void k_bn_finalize(const BnArgs a) {
     }
 }
 
-// MODE 0: y = z;  1: y = relu(z);  2: y = relu(z + res)
+// MODE 0: y = z;  1: y = relu(z);  2: y = relu(z + res);  3: y = min(max(z, 0), 6)
 template <int MODE>
 __global__ __launch_bounds__(256) void k_bn_apply(const BnArgs a) {
     const int t = threadIdx.x, q = t % kBnQuads, r = t / kBnQuads;
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(256) void k_bn_apply(const BnArgs a) {
         if (MODE == 2) z += *reinterpret_cast<const f32x4*>(a.res + o);
         if (MODE >= 1) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) z[e] = fmaxf(z[e], 0.f);
+            for (int e = 0; e < 4; ++e) z[e] = MODE == 3 ? fminf(fmaxf(z[e], 0.f), 6.f) : fmaxf(z[e], 0.f);
         }
         *reinterpret_cast<f32x4*>(a.out + o) = z;
     }
@@ -195,10 +195,10 @@ __global__ __launch_bounds__(256) void k_bn_bwd_reduce(const BnArgs a) {
         for (int p = p0 + r; p < p1; p += kBnRows) {
             const size_t o = (size_t)p * a.C + 4 * (size_t)qg;
             f32x4 g = *reinterpret_cast<const f32x4*>(a.dy + o);
-            if (a.relu) {
+            if (a.act) {
                 const f32x4 y = *reinterpret_cast<const f32x4*>(a.y + o);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) g[e] = y[e] > 0.f ? g[e] : 0.f;
+                for (int e = 0; e < 4; ++e) g[e] = (y[e] > 0.f && (a.act == 1 || y[e] < 6.f)) ? g[e] : 0.f;
             }
             const f32x4 xh = (*reinterpret_cast<const f32x4*>(a.x + o) - mean) * rstd;
             sa += g; sb += g * xh;
@@ -254,10 +254,10 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(const BnArgs a) {
     for (int p = p0 + r; p < p1; p += kBnRows) {
         const size_t o = (size_t)p * a.C + 4 * (size_t)qg;
         f32x4 g = *reinterpret_cast<const f32x4*>(a.dy + o);
-        if (a.relu) {
+        if (a.act) {
             const f32x4 y = *reinterpret_cast<const f32x4*>(a.y + o);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) g[e] = y[e] > 0.f ? g[e] : 0.f;
+            for (int e = 0; e < 4; ++e) g[e] = (y[e] > 0.f && (a.act == 1 || y[e] < 6.f)) ? g[e] : 0.f;
         }
         if (a.dres) *reinterpret_cast<f32x4*>(a.dres + o) = g;
         if (a.out) {
@@ -287,16 +287,18 @@ extern "C" size_t fpc_batchnorm_scratch_floats(int P, int C) {
     return (P < 1 || C < 4) ? 0 : (size_t)cdiv(P, kBnChunk) * C * 2;
 }
 
-extern "C" int fpc_batchnorm_fwd(const float* x, const float* res, const float* gamma, const float* beta, float* running_mean,
-                                 float* running_var, float* y, float* stats, float* part, int P, int C, float eps, float momentum,
-                                 int relu, fpc_stream_t stream) {
+// act: 0 none, 1 ReLU, 2 ReLU6 (a residual goes with ReLU alone)
+extern "C" int fpc_batchnorm_act_fwd(const float* x, const float* res, const float* gamma, const float* beta, float* running_mean,
+                                     float* running_var, float* y, float* stats, float* part, int P, int C, float eps, float momentum,
+                                     int act, fpc_stream_t stream) {
+    if (act < 0 || act > 2) return FPC_EINVAL;
     BnArgs a{};
     int rc = bn_args(a, x, gamma, part, stats, P, C);
     if (rc) return rc;
-    if (bn_bad16(beta) || bn_bad16(y) || (res && (((uintptr_t)res & 15) || !relu))) return FPC_EINVAL;
+    if (bn_bad16(beta) || bn_bad16(y) || (res && (((uintptr_t)res & 15) || act != 1))) return FPC_EINVAL;
     if (!running_mean != !running_var || ((uintptr_t)running_mean & 3) || ((uintptr_t)running_var & 3)) return FPC_EINVAL;
     a.res = res; a.beta = beta; a.out = y; a.running_mean = running_mean; a.running_var = running_var;
-    a.eps = eps; a.momentum = momentum; a.relu = relu != 0;
+    a.eps = eps; a.momentum = momentum; a.act = act;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(a.chunks, cdiv(a.Q, kBnQuads));
     hipLaunchKernelGGL(k_bn_stats, grid, dim3(256), 0, s, a);
@@ -306,19 +308,27 @@ extern "C" int fpc_batchnorm_fwd(const float* x, const float* res, const float* 
     rc = check_launch();
     if (rc) return rc;
     if (res) hipLaunchKernelGGL(k_bn_apply<2>, grid, dim3(256), 0, s, a);
-    else if (relu) hipLaunchKernelGGL(k_bn_apply<1>, grid, dim3(256), 0, s, a);
+    else if (act == 2) hipLaunchKernelGGL(k_bn_apply<3>, grid, dim3(256), 0, s, a);
+    else if (act) hipLaunchKernelGGL(k_bn_apply<1>, grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(k_bn_apply<0>, grid, dim3(256), 0, s, a);
     return check_launch();
 }
 
-extern "C" int fpc_batchnorm_bwd(const float* x, const float* y, const float* dy, const float* gamma, const float* stats, float* dx,
-                                 float* dres, float* dgamma, float* dbeta, float* part, int P, int C, int relu, fpc_stream_t stream) {
+extern "C" int fpc_batchnorm_fwd(const float* x, const float* res, const float* gamma, const float* beta, float* running_mean,
+                                 float* running_var, float* y, float* stats, float* part, int P, int C, float eps, float momentum,
+                                 int relu, fpc_stream_t stream) {
+    return fpc_batchnorm_act_fwd(x, res, gamma, beta, running_mean, running_var, y, stats, part, P, C, eps, momentum, relu != 0, stream);
+}
+
+extern "C" int fpc_batchnorm_act_bwd(const float* x, const float* y, const float* dy, const float* gamma, const float* stats, float* dx,
+                                     float* dres, float* dgamma, float* dbeta, float* part, int P, int C, int act, fpc_stream_t stream) {
+    if (act < 0 || act > 2) return FPC_EINVAL;
     BnArgs a{};
     int rc = bn_args(a, x, gamma, part, const_cast<float*>(stats), P, C);
     if (rc) return rc;
-    if (bn_bad16(dy) || bn_bad16(dgamma) || bn_bad16(dbeta) || (relu && bn_bad16(y))) return FPC_EINVAL;
-    if (((uintptr_t)dx & 15) || ((uintptr_t)dres & 15) || (dres && !relu)) return FPC_EINVAL;
-    a.y = y; a.dy = dy; a.out = dx; a.dres = dres; a.dgamma = dgamma; a.dbeta = dbeta; a.relu = relu != 0;
+    if (bn_bad16(dy) || bn_bad16(dgamma) || bn_bad16(dbeta) || (act && bn_bad16(y))) return FPC_EINVAL;
+    if (((uintptr_t)dx & 15) || ((uintptr_t)dres & 15) || (dres && act != 1)) return FPC_EINVAL;
+    a.y = y; a.dy = dy; a.out = dx; a.dres = dres; a.dgamma = dgamma; a.dbeta = dbeta; a.act = act;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(a.chunks, cdiv(a.Q, kBnQuads));
     hipLaunchKernelGGL(k_bn_bwd_reduce, grid, dim3(256), 0, s, a);
@@ -329,4 +339,9 @@ extern "C" int fpc_batchnorm_bwd(const float* x, const float* y, const float* dy
     if (rc || (!dx && !dres)) return rc;
     hipLaunchKernelGGL(k_bn_bwd_apply, grid, dim3(256), 0, s, a);
     return check_launch();
+}
+
+extern "C" int fpc_batchnorm_bwd(const float* x, const float* y, const float* dy, const float* gamma, const float* stats, float* dx,
+                                 float* dres, float* dgamma, float* dbeta, float* part, int P, int C, int relu, fpc_stream_t stream) {
+    return fpc_batchnorm_act_bwd(x, y, dy, gamma, stats, dx, dres, dgamma, dbeta, part, P, C, relu != 0, stream);
 }

@@ -334,18 +334,34 @@ class SENetEncoder(_Encoder):
 
 class ConvBNReLU6(nn.Sequential):
     """torchvision's ConvBNReLU / Conv2dNormActivation as MobileNetV2 uses it: conv (no bias, padding (k - 1) / 2) -> BatchNorm ->
-    ReLU6, children 0 / 1 / 2.  The activation is a child module: a test may swap it."""
+    ReLU6, children 0 / 1 / 2.  The activation is a child module: a test may swap it.  In the training step, with
+    FPC_TRAIN_NATIVE_MBV2=1 and FPC_TRAIN_NATIVE_BN=1 both set, the BatchNorm and the ReLU6 are one native op each way
+    (lib/train_conv.batchnorm_act(relu6=True)) while child 1 is a training BatchNorm2d and child 2 an nn.ReLU6; whatever the front end
+    refuses, and every other case, is nn.Sequential's own forward, child by child."""
 
     def __init__(self, inp, oup, kernel_size=3, stride=1, groups=1):
         super().__init__(Conv2d(inp, oup, kernel_size, stride, (kernel_size - 1) // 2, groups=groups, bias=False),
                          BatchNorm2d(oup), nn.ReLU6(inplace=True))
+
+    def forward(self, x):
+        if len(self) == 3 and x.is_cuda and torch.is_grad_enabled():
+            conv, bn, act = self[0], self[1], self[2]
+            tc = _train_conv()
+            if isinstance(act, nn.ReLU6) and isinstance(bn, BatchNorm2d) and bn.training and tc.NATIVE_MBV2 and tc.NATIVE_BN:
+                x = conv(x)
+                y = _train_native(True, "batchnorm_act", x, bn, relu=False, relu6=True, count_refusal=False)      # (refused: bn(x) asks again, plain)
+                return act(bn(x)) if y is None else y
+        return super().forward(x)
 
 
 class InvertedResidual(nn.Module):
     """torchvision.models.mobilenetv2.InvertedResidual: `conv` = [expand 1x1 + BN + ReLU6 (absent where expand_ratio = 1)], the
     depthwise 3x3 with the stride (groups = hidden) + BN + ReLU6, the project 1x1 without bias, its BN; the input is added where the
     stride is 1 and inp = oup, with no activation behind the add.  In the training step the dense 1x1 sites and the BatchNorms run
-    on the native kernels lib/train_conv.py already has (Conv2d / BatchNorm2d above); the depthwise convolution and ReLU6 are torch's."""
+    on the native kernels lib/train_conv.py already has (Conv2d / BatchNorm2d above); the depthwise convolution and ReLU6 are torch's
+    by default and, with FPC_TRAIN_NATIVE_MBV2=1, native too: the convolution on k_dwconv3x3 and csrc/dwconv_train.hip (Conv2d above
+    reaches lib/train_conv._DepthwiseConv2dFn), ReLU6 as the activation of the native BatchNorm (ConvBNReLU6.forward, with
+    FPC_TRAIN_NATIVE_BN=1)."""
 
     def __init__(self, inp, oup, stride, expand_ratio):
         super().__init__()

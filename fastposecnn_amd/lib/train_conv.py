@@ -26,6 +26,11 @@ The squeeze-and-excitation gate of the SE-ResNet blocks, the residual add and th
 pool, two 1x1 convolutions, sigmoid and multiply, then an add and a ReLU); with FPC_TRAIN_NATIVE_SE=1 they are _SEGateAddReLUFn: the
 forward on k_se_pool / k_se_excite / k_se_scale_add_relu (csrc/se.hip), the whole backward on csrc/se_train.hip, counted in
 se_fwd_native / se_bwd_native (a refused block in se_torch).
+The DEPTHWISE 3x3 convolution of the MobileNetV2 blocks and the ReLU6 behind their BatchNorms are torch's own by default (the grouped
+MIOpen / aten kernels forward and both gradients, aten's hardtanh each way); with FPC_TRAIN_NATIVE_MBV2=1 the convolution is
+_DepthwiseConv2dFn — the forward on the inference kernel k_dwconv3x3 (act 0, scale 1, shift 0), the data and weight gradients on
+csrc/dwconv_train.hip, counted in dw_fwd_native / dw_dgrad_native / dw_wgrad_native — and, with FPC_TRAIN_NATIVE_BN=1 as well,
+ConvBNReLU6's BatchNorm and ReLU6 are one native op each way (batchnorm_act(relu6=True), counted in bn_relu6_native beside bn_native).
 
 The tiling / Winograd form of a shape is chosen once, by timing the candidates on the first call with that shape (this
 synchronises: it happens in the warm-up steps).  f32 operands, accumulation and results, products in plain f32 or as the
@@ -45,7 +50,8 @@ _plan_cache = {}            # (device index, B, Cin, H, W, Cout, k, stride, pad)
 counters = {"fwd_native": 0, "dgrad_native": 0, "wgrad_native": 0, "dgrad_aten": 0, "wgrad_aten": 0, "wgrad_direct": 0,
             "grouped_fwd_native": 0, "grouped_dgrad_native": 0, "grouped_wgrad_native": 0,
             "stem_fwd_native": 0, "stem_wgrad_native": 0, "pool_fwd_native": 0, "pool_bwd_native": 0,
-            "bn_native": 0, "bn_torch": 0, "se_fwd_native": 0, "se_bwd_native": 0, "se_torch": 0}
+            "bn_native": 0, "bn_torch": 0, "se_fwd_native": 0, "se_bwd_native": 0, "se_torch": 0,
+            "dw_fwd_native": 0, "dw_dgrad_native": 0, "dw_wgrad_native": 0, "bn_relu6_native": 0}
 
 
 # Weight-gradient sinks (round 6): an optimiser that keeps `p.grad` as views of one flat buffer (train_parallel.py) registers
@@ -407,6 +413,93 @@ class _GroupedConv2dFn(torch.autograd.Function):
         return gx, gw, gb, None, None
 
 
+# ---- the depthwise 3x3 convolution (the MobileNetV2 blocks) -------------------------------------------------------------------
+
+# Off by default: with it off a depthwise convolution is torch's own, forward and backward, and ReLU6 is never fused into the
+# native BatchNorm, as before (DESIGN.md 4.2a''''''').
+NATIVE_MBV2 = bool(int(os.environ.get("FPC_TRAIN_NATIVE_MBV2", "0")))
+_DW_WALK_LIMIT = 2 ** 32 - 4096 * 256 - 8      # channel quads of a tensor: the 32-bit walks of csrc/mobilenet.hip
+
+
+def _dw_native_op(op, stride):
+    """Whether `op` ("dgrad" / "wgrad") of a depthwise convolution of this stride runs native.  A combination whose native kernel
+    measured slower than torch's on the training shapes is listed here and keeps torch's kernel (DESIGN.md 4.2a''''''', the
+    per-site table); the forward always runs native."""
+    return (op, stride) not in _DW_KEEP_TORCH
+
+
+_DW_KEEP_TORCH = frozenset()
+_dw_identity = {}      # device index -> (ones, zeros): the forward kernel's scale / shift, grow-only
+
+
+def _dw_scale_shift(dev, C):
+    have = _dw_identity.get(dev.index)
+    if have is None or have[0].numel() < C:
+        have = _dw_identity[dev.index] = (torch.ones(C, dtype=torch.float32, device=dev), torch.zeros(C, dtype=torch.float32, device=dev))
+    return have
+
+
+def _depthwise_ok(x, w, bias, stride, pad, groups):
+    return (ENABLED and NATIVE_MBV2 and torch.is_tensor(x) and _f32_cuda_4d(x) and torch.is_grad_enabled()
+            and w.dtype == torch.float32 and w.device == x.device
+            and groups == x.shape[1] and tuple(w.shape) == (x.shape[1], 1, 3, 3) and x.shape[1] % 4 == 0 and pad == 1
+            and stride in (1, 2) and bias is None and 0 < x.numel() // 4 < _DW_WALK_LIMIT)
+
+
+class _DepthwiseConv2dFn(torch.autograd.Function):
+    """The depthwise 3x3 / pad-1 convolution without bias on the native kernels: forward k_dwconv3x3 through fpc_dwconv3x3 with the
+    identity scale / shift and no activation, backward fpc_dwconv3x3_dgrad / _wgrad (csrc/dwconv_train.hip).  One form: nothing is tuned."""
+
+    @staticmethod
+    def forward(ctx, x, w, stride):
+        x = _operand(x, aligned=True)
+        w = _operand(w, aligned=True, nhwc=False)
+        B, C, H, W = x.shape
+        Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+        out = torch.empty((B, C, Ho, Wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        ones, zeros = _dw_scale_shift(x.device, C)
+        nat.check(nat.lib().fpc_dwconv3x3(x.data_ptr(), w.data_ptr(), ones.data_ptr(), zeros.data_ptr(), out.data_ptr(), B, H, W, C, stride,
+                                          0, nat.stream()), "fpc_dwconv3x3 (training)")
+        ctx.stride = stride
+        ctx.save_for_backward(x, w)
+        counters["dw_fwd_native"] += 1
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        stride = ctx.stride
+        B, C, H, W = x.shape
+        gy = _operand(gy, aligned=True)
+        Ho, Wo = gy.shape[2], gy.shape[3]
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gx = gw = None
+        L = nat.lib()
+        aten_x = need_x and not _dw_native_op("dgrad", stride)
+        aten_w = need_w and not _dw_native_op("wgrad", stride)
+        if need_x and not aten_x:
+            gx = torch.empty((B, C, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+            nat.check(L.fpc_dwconv3x3_dgrad(gy.data_ptr(), w.data_ptr(), gx.data_ptr(), B, H, W, C, stride, nat.stream()),
+                      "fpc_dwconv3x3_dgrad")
+            counters["dw_dgrad_native"] += 1
+        if need_w and not aten_w:
+            sink = _take_sink(w, aligned=True)
+            gw = sink.view if sink is not None else torch.empty_like(w)
+            ws = nat.workspace("train_dw_wgrad", x.device, L.fpc_dwconv3x3_wgrad_workspace_bytes(B, Ho, Wo, C))
+            nat.check(L.fpc_dwconv3x3_wgrad(x.data_ptr(), gy.data_ptr(), gw.data_ptr(), B, H, W, C, stride, ws.data_ptr(), ws.numel(),
+                                            nat.stream()), "fpc_dwconv3x3_wgrad")
+            counters["dw_wgrad_native"] += 1
+            if sink is not None:
+                _commit_sink(sink)
+                gw = None
+        if aten_x or aten_w:
+            ax, aw, _ = torch.ops.aten.convolution_backward(gy, x, w, None, [stride, stride], [1, 1], [1, 1], False, [0, 0], C,
+                                                            [aten_x, aten_w, False])
+            gx = ax if aten_x else gx
+            gw = aw if aten_w else gw
+        return gx, gw, None
+
+
 # ---- the 7x7 / stride-2 stem (Cin = 3) and the 3x3 / stride-2 max-pool behind it -------------------------------------------
 
 # Off by default: with it off the stem and the max-pool are torch's own, forward and backward, as before (DESIGN.md 4.2a''').
@@ -510,9 +603,13 @@ def conv2d(x, w, bias, stride, pad, groups=1):
     a 3x3 / pad-1 / stride-1 or -2 convolution of the class csrc/conv_grouped.hip takes: then _GroupedConv2dFn, counted in
     grouped_fwd_native / grouped_dgrad_native / grouped_wgrad_native.  The 7x7 stem likewise: torch's own unless NATIVE_STEM
     (FPC_TRAIN_NATIVE_STEM=1) is set and it is the 3 -> 64 / stride-2 / pad-3 convolution without bias of an even-sized image
-    that needs no gradient: then _StemConvFn, counted in stem_fwd_native / stem_wgrad_native."""
+    that needs no gradient: then _StemConvFn, counted in stem_fwd_native / stem_wgrad_native.  A DEPTHWISE 3x3 / pad-1 / stride-1 or
+    -2 convolution without bias (groups = C, C % 4 == 0) under autograd is _DepthwiseConv2dFn when NATIVE_MBV2
+    (FPC_TRAIN_NATIVE_MBV2=1) is set, counted in dw_fwd_native / dw_dgrad_native / dw_wgrad_native; it is asked first."""
     if groups == 1 and _stem_ok(x, w, bias, stride, pad):
         return _StemConvFn.apply(x, w)
+    if groups != 1 and _depthwise_ok(x, w, bias, stride, pad, groups):
+        return _DepthwiseConv2dFn.apply(x, w, int(stride))
     if groups != 1 and _grouped_ok(x, w, bias, stride, pad, groups):
         return _GroupedConv2dFn.apply(x, w, bias, int(stride), int(groups))
     # (the dense path asks neither for four dimensions nor for the current device, as before)
@@ -614,28 +711,28 @@ NATIVE_BN = bool(int(os.environ.get("FPC_TRAIN_NATIVE_BN", "0")))
 
 
 class _BatchNormActFn(torch.autograd.Function):
-    """y = bn(x) over the batch statistics, + res, relu (csrc/batchnorm.hip).  running_mean / running_var are rewritten through
-    their raw pointers: their version counters do not move (PoseRegressor.note_unversioned_write)."""
+    """y = act(bn(x) + res) over the batch statistics, act 0 none / 1 ReLU / 2 ReLU6 (csrc/batchnorm.hip).  running_mean /
+    running_var are rewritten through their raw pointers: their version counters do not move (PoseRegressor.note_unversioned_write)."""
 
     @staticmethod
-    def forward(ctx, x, res, gamma, beta, running_mean, running_var, eps, momentum, relu):
+    def forward(ctx, x, res, gamma, beta, running_mean, running_var, eps, momentum, act):
         B, C, H, W = x.shape
         P = B * H * W
         L = nat.lib()
         y = torch.empty_like(x, memory_format=torch.channels_last)
         stats = torch.empty((C, 2), dtype=torch.float32, device=x.device)
         part = nat.workspace("train_bn", x.device, 4 * L.fpc_batchnorm_scratch_floats(P, C))
-        nat.check(L.fpc_batchnorm_fwd(x.data_ptr(), nat.ptr(res), gamma.data_ptr(), beta.data_ptr(), running_mean.data_ptr(),
-                                      running_var.data_ptr(), y.data_ptr(), stats.data_ptr(), part.data_ptr(), P, C, float(eps),
-                                      float(momentum), int(relu), nat.stream()), "fpc_batchnorm_fwd")
-        ctx.save_for_backward(x, gamma, stats, *((y,) if relu else ()))
-        ctx.relu = relu
+        nat.check(L.fpc_batchnorm_act_fwd(x.data_ptr(), nat.ptr(res), gamma.data_ptr(), beta.data_ptr(), running_mean.data_ptr(),
+                                          running_var.data_ptr(), y.data_ptr(), stats.data_ptr(), part.data_ptr(), P, C, float(eps),
+                                          float(momentum), act, nat.stream()), "fpc_batchnorm_act_fwd")
+        ctx.save_for_backward(x, gamma, stats, *((y,) if act else ()))
+        ctx.act = act
         return y
 
     @staticmethod
     def backward(ctx, gy):
         x, gamma, stats = ctx.saved_tensors[:3]
-        y = ctx.saved_tensors[3] if ctx.relu else None
+        y = ctx.saved_tensors[3] if ctx.act else None
         B, C, H, W = x.shape
         P = B * H * W
         L = nat.lib()
@@ -644,15 +741,16 @@ class _BatchNormActFn(torch.autograd.Function):
         dres = torch.empty_like(x, memory_format=torch.channels_last) if ctx.needs_input_grad[1] else None
         dgb = torch.empty((2, C), dtype=torch.float32, device=x.device)
         part = nat.workspace("train_bn", x.device, 4 * L.fpc_batchnorm_scratch_floats(P, C))
-        nat.check(L.fpc_batchnorm_bwd(x.data_ptr(), nat.ptr(y), gy.data_ptr(), gamma.data_ptr(), stats.data_ptr(), nat.ptr(dx),
-                                      nat.ptr(dres), dgb.data_ptr(), dgb.data_ptr() + 4 * C, part.data_ptr(), P, C, int(ctx.relu),
-                                      nat.stream()), "fpc_batchnorm_bwd")
+        nat.check(L.fpc_batchnorm_act_bwd(x.data_ptr(), nat.ptr(y), gy.data_ptr(), gamma.data_ptr(), stats.data_ptr(), nat.ptr(dx),
+                                          nat.ptr(dres), dgb.data_ptr(), dgb.data_ptr() + 4 * C, part.data_ptr(), P, C, ctx.act,
+                                          nat.stream()), "fpc_batchnorm_act_bwd")
         return (dx, dres, dgb[0] if ctx.needs_input_grad[2] else None, dgb[1] if ctx.needs_input_grad[3] else None,
                 None, None, None, None, None)
 
 
-def batchnorm_act(x, bn, res=None, relu=True, count_refusal=True):
-    """relu(bn(x) + res) (res and relu optional; a residual needs relu) for a torch.nn.BatchNorm2d `bn` in TRAINING mode, as one
+def batchnorm_act(x, bn, res=None, relu=True, count_refusal=True, relu6=False):
+    """relu(bn(x) + res) (res and relu optional; a residual needs relu; relu6=True: min(max(bn(x), 0), 6) in place of the ReLU, with
+    no residual — a MobileNetV2 block has none there —, counted in bn_relu6_native too) for a torch.nn.BatchNorm2d `bn` in TRAINING mode, as one
     native op each way on dense channel-last f32 GPU tensors: batch statistics, the module's running statistics and
     num_batches_tracked updated as torch does.  None when the native path does not apply — evaluation mode, no affine parameters,
     no running statistics, momentum=None (torch's cumulative average), another layout (never a layout copy to get here) or
@@ -662,7 +760,7 @@ def batchnorm_act(x, bn, res=None, relu=True, count_refusal=True):
     ok = (ENABLED and NATIVE_BN and bn.training and bn.affine and bn.track_running_stats and bn.momentum is not None
           and bn.running_mean is not None and torch.is_tensor(x) and _f32_cuda_4d(x)
           and x.shape[1] % 4 == 0 and x.shape[1] == bn.num_features and 2 <= x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31 - 256
-          and _dense_nhwc(x)
+          and _dense_nhwc(x) and not (relu6 and res is not None)
           and (res is None or (relu and res.shape == x.shape and res.dtype == x.dtype and res.device == x.device and _dense_nhwc(res)))
           and all(_f32_param(t, x.device) for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)))
     if not ok:
@@ -670,7 +768,9 @@ def batchnorm_act(x, bn, res=None, relu=True, count_refusal=True):
         return None
     bn.num_batches_tracked.add_(1)
     counters["bn_native"] += 1
-    return _BatchNormActFn.apply(x, res, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum, bool(relu))
+    counters["bn_relu6_native"] += int(bool(relu6))
+    return _BatchNormActFn.apply(x, res, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum,
+                                 2 if relu6 else int(bool(relu)))
 
 
 # ---- the squeeze-and-excitation gate + residual add + ReLU of the SE-ResNet blocks (behind bn3) ------------------------------

@@ -9,6 +9,8 @@ What runs where (stated in the JSON line as well):
     bilinear upsampling forward / backward on csrc/upsample.hip; the decoder's GroupNorm + ReLU on csrc/groupnorm.hip; the
     encoder's BatchNorm + residual add + ReLU: torch's modules, or csrc/batchnorm.hip with FPC_TRAIN_NATIVE_BN=1
     the SE-ResNet blocks' gate + add + ReLU: torch's modules, or csrc/se.hip + csrc/se_train.hip with FPC_TRAIN_NATIVE_SE=1
+    the MobileNetV2 blocks' depthwise 3x3 and ReLU6: torch's modules, or csrc/mobilenet.hip + csrc/dwconv_train.hip (and, with
+    FPC_TRAIN_NATIVE_BN=1, ReLU6 inside csrc/batchnorm.hip) with FPC_TRAIN_NATIVE_MBV2=1
     (FPC_TRAIN_NATIVE_CONV=0 returns every convolution and upsampling to torch: the A/B this file's numbers come with);
   * everything after the logits, forward: the inference kernels (class compression, connected components, aggregation,
     RANSAC vote, RT); backward: csrc/train.hip through lib/train_functions.py;
@@ -72,11 +74,14 @@ def _conv_note():
              "behind it fpc_maxpool3x3s2_fwd/bwd (stem_fwd_native / stem_wgrad_native / pool_fwd_native / pool_bwd_native); "
              if train_conv.NATIVE_STEM else
              "torch for the 7x7 stem alone (Cin = 3: outside these counters; FPC_TRAIN_NATIVE_STEM=1: native); ") + "the encoder's "
-            "BatchNorm + add + ReLU " + ("fpc_batchnorm_fwd/bwd (bn_native; bn_torch: left to torch) "
+            "BatchNorm + add + ReLU " + ("fpc_batchnorm_act_fwd/bwd (bn_native; bn_torch: left to torch) "
                                          if train_conv.NATIVE_BN else "torch (FPC_TRAIN_NATIVE_BN=1: native) ") +
             ("; the SE-ResNet blocks' gate + add + ReLU fpc_se_gate_train / fpc_se_scale_add_relu forward, fpc_se_bwd backward "
              "(se_fwd_native / se_bwd_native; se_torch: left to torch) "
              if train_conv.NATIVE_SE else "; the SE-ResNet blocks' gate + add + ReLU torch (FPC_TRAIN_NATIVE_SE=1: native) ") +
+            ("; the MobileNetV2 blocks' depthwise 3x3 fpc_dwconv3x3 forward, fpc_dwconv3x3_dgrad / _wgrad backward (dw_fwd_native / "
+             "dw_dgrad_native / dw_wgrad_native), ReLU6 inside the native BatchNorm where that runs (bn_relu6_native) "
+             if train_conv.NATIVE_MBV2 else "; the MobileNetV2 blocks' depthwise 3x3 and ReLU6 torch (FPC_TRAIN_NATIVE_MBV2=1: native) ") +
             f"(calls so far: {dict(c)})")
 
 

@@ -60,6 +60,8 @@ extern "C" {
  * and the SE-ResNet encoders (fpc_net_create_encoder_se, fpc_se_pool_slabs, fpc_se_scratch_floats, fpc_se_gate, fpc_se_scale_add_relu, fpc_maxpool3x3s2_ceil_fwd):
  * and their gate in the training step (fpc_se_gate_train, fpc_se_bwd_scratch_floats, fpc_se_bwd):
  * and the MobileNetV2 encoder (fpc_net_create's "mobilenet_v2", fpc_dwconv3x3, fpc_conv1x1_f32, fpc_conv1x1_f32_form, fpc_stem3x3s2):
+ * and its depthwise convolution and ReLU6 in the training step (fpc_dwconv3x3_dgrad, fpc_dwconv3x3_wgrad and its _workspace_bytes,
+ *   fpc_batchnorm_act_fwd, fpc_batchnorm_act_bwd):
  * additions only, every earlier entry point keeps its behaviour. */
 #define FPC_ABI_VERSION 11
 
@@ -888,6 +890,34 @@ int fpc_conv1x1_f32_form(int64_t M, int Cin, int Cout);
 int fpc_stem3x3s2(const float* in4, const float* w, const float* scale, const float* shift, float* out, int B, int Hi, int Wi, int Cout,
                   fpc_stream_t stream);
 
+/* ---- The depthwise 3x3 convolution and the ReLU6 of the MobileNetV2 encoder in the training step (csrc/dwconv_train.hip,
+ * csrc/batchnorm.hip; lib/train_conv.py: _DepthwiseConv2dFn and batchnorm_act(relu6=True) behind FPC_TRAIN_NATIVE_MBV2=1).  They
+ * replace autograd through torch.nn.Conv2d(groups = C) and nn.ReLU6 inside smp's MobileNetV2 encoder (cuDNN's grouped kernels and
+ * aten's hardtanh, forward and backward, in the reference; reached from F/lib/pose_regressor.py:608-613).  The FORWARD of the
+ * convolution in training is fpc_dwconv3x3 above with act 0, scale 1 and shift 0 (v * 1 + 0 is exact).  Conventions of the entries
+ * above: dense channel-last f32, w / dw torch's [C][1][3][3] read / written in place, pad 1, plain f32 FMAs in an order the shape
+ * alone fixes, no atomics: bit-identical run to run.  FPC_EINVAL before any launch: a NULL or not 16-byte-aligned pointer, B < 1,
+ * C < 4 or C % 4 != 0, a stride other than 1 or 2, Hi < 1 or Wi < 1, B Hi Wi C / 4 >= 2^32 - 2^20 - 8 (the 32-bit walk limit of
+ * fpc_dwconv3x3).
+ *
+ * fpc_dwconv3x3_dgrad (k_dwconv3x3_dgrad_s1 / _s2): dx [B][Hi][Wi][C] from dy [B][(Hi - 1) / stride + 1][(Wi - 1) / stride + 1][C],
+ *   every element written exactly once: dx[h][w] = sum over kh, kw of dy[(h + 1 - kh) / stride][(w + 1 - kw) / stride] w[kh][kw] where
+ *   the divisions are exact and the index is inside dy.  Stride 2 is evaluated per output parity (dx[2a] = dy[a] w[1],
+ *   dx[2a + 1] = dy[a] w[2] + dy[a + 1] w[0] per axis): nine products per 2 x 2 block of dx and channel, no zero insertion.
+ * fpc_dwconv3x3_wgrad (k_dwconv3x3_wgrad + k_dwconv3x3_wgrad_reduce): dw[c][kh][kw] = sum over b, ho, wo of
+ *   dy[b][ho][wo][c] x[b][stride ho + kh - 1][stride wo + kw - 1][c], zero outside x; every element of dw is overwritten, a tap no
+ *   pixel reaches (a 1 x 1 map: all but the centre) with an exact zero.  The list of the B Ho (frame, output row) pairs is cut into
+ *       slices = max(1, min(max(1, 1024 / ceil(C / 32)), B Ho ceil(Wo / 8) / 32, B Ho))      (integer divisions)
+ *   contiguous slices, slice i = rows [i B Ho / slices, (i + 1) B Ho / slices): a function of (B, Ho, Wo, C) alone.  One f32
+ *   partial [C][9] per slice (inside a slice: 32 pixel slots over its (row, 8-column segment) units in turn, added in a fixed
+ *   tree), the slices added in double in sixteen contiguous ranges, each ascending, the ranges ascending.
+ *   ws: fpc_dwconv3x3_wgrad_workspace_bytes(B, Ho, Wo, C) = slices * C * 9 * 4 bytes (0 for a refused shape), 256-byte aligned;
+ *   too small or misaligned: FPC_EWORKSPACE (a NULL ws: FPC_EINVAL). */
+int fpc_dwconv3x3_dgrad(const float* dy, const float* w, float* dx, int B, int Hi, int Wi, int C, int stride, fpc_stream_t stream);
+size_t fpc_dwconv3x3_wgrad_workspace_bytes(int B, int Ho, int Wo, int C);
+int fpc_dwconv3x3_wgrad(const float* x, const float* dy, float* dw, int B, int Hi, int Wi, int C, int stride, void* ws,
+                        size_t ws_bytes, fpc_stream_t stream);
+
 /* ---- The same gate in the training step (csrc/se_train.hip; lib/train_conv.se_gate_add_relu behind FPC_TRAIN_NATIVE_SE=1).  They
  * replace autograd through pretrainedmodels.senet.SEModule and through the add / ReLU of SEResNetBottleneck.forward (aten forward
  * and backward kernels in the reference, reached from F/lib/pose_regressor.py:608-613).  Conventions, shape class and refusals of
@@ -979,6 +1009,16 @@ int fpc_batchnorm_fwd(const float* x, const float* res, const float* gamma, cons
                       fpc_stream_t stream);
 int fpc_batchnorm_bwd(const float* x, const float* y, const float* dy, const float* gamma, const float* stats, float* dx,
                       float* dres, float* dgamma, float* dbeta, float* part, int P, int C, int relu, fpc_stream_t stream);
+/* The two entries above with an activation code in place of `relu`: act 0 none, 1 ReLU, 2 ReLU6 (the activation behind every
+ * BatchNorm but the last of a MobileNetV2 block: nn.ReLU6 in the reference's encoder, aten's hardtanh forward and backward).
+ * act 2: y = min(max(z, 0), 6) forward, g = dy [0 < y < 6] on the saved output backward — torch's hardtanh rule on the
+ * pre-activation.  Statistics, running buffers and the partial sums are those of the entries above, which are these with
+ * act = (relu != 0).  FPC_EINVAL besides theirs: any other act, and a residual (res, dres) with act 2 — no block has it. */
+int fpc_batchnorm_act_fwd(const float* x, const float* res, const float* gamma, const float* beta, float* running_mean,
+                          float* running_var, float* y, float* stats, float* part, int P, int C, float eps, float momentum, int act,
+                          fpc_stream_t stream);
+int fpc_batchnorm_act_bwd(const float* x, const float* y, const float* dy, const float* gamma, const float* stats, float* dx,
+                          float* dres, float* dgamma, float* dbeta, float* part, int P, int C, int act, fpc_stream_t stream);
 
 #ifdef __cplusplus
 }
