@@ -110,6 +110,12 @@ _SIGNATURES = {
     "fpc_net_set_wino_pack": (_i, [_vp, _i]),
     "fpc_net_set_wino_orient": (_i, [_vp, _i]),
     "fpc_wino_orient_geometry": (_i, [_i, _i, _i, _i, _i, _i, ctypes.POINTER(_i64)]),
+    "fpc_wino_xshare_rule": (_i, [_i]),
+    "fpc_net_set_wino_xshare": (_i, [_vp, _i]),
+    "fpc_wino_tile_frag": (_i, [_i, _i, _i, _i, ctypes.POINTER(_i64)]),
+    "fpc_wino_tile_slot": (_i, [_i] * 11 + [ctypes.POINTER(_i64)]),
+    "fpc_wino_tile_zrun": (_i, [_i, _i, _i, _i, _i, _i, ctypes.POINTER(_i64)]),
+    "fpc_wino_tile_zread": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(_i64)]),
     "fpc_wino_recip": (_i, [ctypes.c_uint32, ctypes.POINTER(_i64)]),
     "fpc_wino_decode": (_i, [_i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(_i64)]),
     "fpc_net_wino_blocks": (_i64, [_vp]),

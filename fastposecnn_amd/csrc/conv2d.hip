@@ -1,6 +1,6 @@
 // conv2d.hip — the stand-alone convolution entry points of include/fpc.h, outside any network: fpc_conv2d* (one convolution on any plan code, for unit
 // tests, micro-benchmarks and the training path), fpc_conv2d_grouped*, and the host-arithmetic exports of the launch geometry (fpc_stem_pool_tasks,
-// fpc_wino_pack_geometry, fpc_wino_orient_geometry, fpc_wino_recip, fpc_wino_decode).  They plan with conv_plan.hpp and launch through conv_launch.hip.
+// fpc_wino_pack_geometry, fpc_wino_orient_geometry, fpc_wino_recip, fpc_wino_decode, fpc_wino_xshare_rule, fpc_wino_tile_*).  They plan with conv_plan.hpp and launch through conv_launch.hip.
 #include <algorithm>
 
 #include "conv_plan.hpp"
@@ -55,6 +55,35 @@ extern "C" int fpc_wino_decode(int Cout, int groups, int tbx, int tby, int W, in
     const WinoDecode d = wino_decode(Cout, groups, tbx, tby, W, B, pack);
     const WinoRecip r[7] = {d.nnb, d.groups, d.tbx, d.tby, d.per, d.tbxl, d.tcw};
     for (int i = 0; i < 7; ++i) { out14[2 * i] = r[i].m; out14[2 * i + 1] = r[i].sh; }
+    return FPC_OK;
+}
+
+// The tile maps of the four-wave Winograd kernels as the kernels compute them (host arithmetic; xshare = 1: the x-shared map of
+// packed form-9 launches, fpc_wino_xshare_rule; 0: the row-split map).  See fpc.h.
+extern "C" int fpc_wino_xshare_rule(int W) { return W >= 1 && wino_xshare_rule(W) ? 1 : 0; }
+extern "C" int fpc_wino_tile_frag(int xshare, int wi, int lane, int pk_ks, int64_t* out17) {
+    long long o[17] = {0};
+    if (!out17 || wino_tile_frag(xshare != 0, wi, lane, pk_ks, o)) return FPC_EINVAL;
+    for (int i = 0; i < 17; ++i) out17[i] = o[i];
+    return FPC_OK;
+}
+extern "C" int fpc_wino_tile_slot(int xshare, int tr, int slot, int y_in0, int x_in0, int H, int W, int Cs, int up, int pk_ks, int pk_two,
+                                  int64_t* out6) {
+    long long o[6];
+    if (!out6 || wino_tile_slot(xshare != 0, tr != 0, slot, y_in0, x_in0, H, W, Cs, up, pk_ks, pk_two, o)) return FPC_EINVAL;
+    for (int i = 0; i < 6; ++i) out6[i] = o[i];
+    return FPC_OK;
+}
+extern "C" int fpc_wino_tile_zrun(int xshare, int wi, int mt, int r, int nt, int cc, int64_t* out3) {
+    long long o[3];
+    if (!out3 || wino_tile_zrun(xshare != 0, wi, mt, r, nt, cc, o)) return FPC_EINVAL;
+    for (int i = 0; i < 3; ++i) out3[i] = o[i];
+    return FPC_OK;
+}
+extern "C" int fpc_wino_tile_zread(int xshare, int t_e, int tp, int cc, int i, int64_t* out1) {
+    long long o[1];
+    if (!out1 || wino_tile_zread(xshare != 0, t_e, tp, cc, i, o)) return FPC_EINVAL;
+    out1[0] = o[0];
     return FPC_OK;
 }
 
@@ -161,6 +190,7 @@ extern "C" int fpc_conv2d(const float* in, int64_t sb, int64_t sh, int64_t sw, i
     fill_conv_shape(a, B, c, p, Hi, Wi, Ho, Wo, sb, sh, sw, sc, relu != 0, mode);
     a.wino_pack = rq.pack ? 1 : 0;      // (-9 itself stays on the plain geometry
     a.wino_orient = rq.orient ? 1 : 0;  // and in the stored orientation)
+    a.wino_rowsplit = rq.rowsplit ? 1 : 0;
     a.splitk_ws = packed + lay.packed;
     a.p[0] = ConvPtrs{in, packed, out, scale, shift, res, up, gn_part};
     if (lay.tickets) {   // arrival counters of the fused split-K form, zeroed per call

@@ -86,6 +86,7 @@ int launch_conv_plan(ConvArgs& a, const ConvPlan& p, int groups, hipStream_t s) 
             const WinoPackGeom q = wino_launch_geometry(a.Ho, a.Wo, a.B, a.Cin, a.wino_orient, a.wino_pack && !p.fold, &tr);
             if (q.G > 1 || tr) { w.pack = q.G; w.tbx = q.tbx; w.tby = q.tby; w.pack_rx = q.rx; }
             w.orient = tr ? 1 : 0;
+            w.xshare = ((q.G > 1 || tr) && !a.wino_rowsplit && wino_xshare_rule(tr ? a.Ho : a.Wo)) ? 1 : 0;
             a.wino_blocks = q.patches * (a.Cout / 64) * groups;
         }
         if (p.fold) {      // c2 on Wc's image + up2(p3) on W's (the p2 input of .p[g] is not read)

@@ -206,11 +206,20 @@ inline bool plan_range_limited(const ConvPlan& p) {
 struct WinoGrid { int tbx, tby; int patches() const { return tbx * tby; } };
 inline WinoGrid wino_grid(int form, int H, int W) { return {cdiv(cdiv(W, 2), 8), cdiv(cdiv(H, 2), kWinoForms[form].waves)}; }
 
+// The X-SHARE RULE of a packed form-9 launch (pack > 1 or transposed) on a (virtual) image W pixels wide: the x-shared tile map
+// (wino_tile.hpp, XS: a lane's two tiles are the neighbours 2k, 2k + 1 of one tile row and share half their input columns) iff the
+// frame has an EVEN number of tile columns tcw.  A packed patch's seam lies after tcw (f + 1) - 8 bx tile columns: with tcw even it
+// is even, falls between two lanes' pairs, and both tiles of a lane lie on one side of it.  Otherwise the row-split map, as ever.
+inline bool wino_xshare_rule(int W) { return (((W + 1) >> 1) & 1) == 0; }
+
 // ---- the integer a plan is reported by (fpc_net_conv_plan's out5[2]) and requested by (fpc_conv2d's `nsplit`): fpc.h, FPC_PLAN_*.
 // What a request asks for (nsplit: the split-K factor, 0 = the planner's, or -form; wino: the form or 0):
-struct Conv2dRequest { int nsplit; bool bf3, two_launch; int wino, lat; bool stem; int pw; bool h3, pool, pack, orient; int grp; };
+struct Conv2dRequest { int nsplit; bool bf3, two_launch; int wino, lat; bool stem; int pw; bool h3, pool, pack, orient; int grp; bool rowsplit; };
 inline Conv2dRequest decode_plan(int code) {
-    Conv2dRequest r{code, false, false, 0, 0, false, 0, false, false, false, false, 0};
+    Conv2dRequest r{code, false, false, 0, 0, false, 0, false, false, false, false, 0, false};
+    // -12 / -13: -10 / -11 on the row-split tile map even where wino_xshare_rule offers the x-shared one (the two maps' A/B)
+    if (code == FPC_PLAN_WINO_PACKED_ROWSPLIT) { r.rowsplit = true; code = FPC_PLAN_WINO_PACKED; }
+    if (code == FPC_PLAN_WINO_ORIENT_ROWSPLIT) { r.rowsplit = true; code = FPC_PLAN_WINO_ORIENT; }
     if (code >= FPC_PLAN_GROUPED && code < FPC_PLAN_GROUPED + 1000) { r.grp = code - FPC_PLAN_GROUPED + 1; r.nsplit = 1; return r; }      // + form = k_conv3x3_grouped (fpc_conv2d_grouped's request; fpc_conv2d has no groups and refuses it)
     if (code == FPC_PLAN_WINO_ORIENT) { r.orient = true; r.nsplit = -kWinoH3; }      // form -9 in the orientation its shape asks for (wino_orient_rule), transposed sites packed along y
     if (code == FPC_PLAN_WINO_PACKED) { r.pack = true; r.nsplit = -kWinoH3; }      // form -9 with its patches cut out of canvas rows of several frames (wino_pack_geometry)

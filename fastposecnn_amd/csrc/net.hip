@@ -75,6 +75,16 @@ extern "C" int fpc_net_set_wino_pack(fpc_net_t* n, int on) {
     return FPC_OK;
 }
 
+// on = 1 (the default): a packed form-9 launch (several frames per canvas row, or transposed) whose frame has an even number of tile
+// columns runs on the x-shared tile map (conv_plan.hpp: wino_xshare_rule; wino_tile.hpp, XS); on = 0: every launch on the row-split
+// map.  The same outputs and GroupNorm records bit for bit; plans, images and the workspace do not change; the recorded graph is dropped.
+extern "C" int fpc_net_set_wino_xshare(fpc_net_t* n, int on) {
+    if (!n || on < 0 || on > 1) return FPC_EINVAL;
+    if (n->wino_xshare != on) drop_graph(n);
+    n->wino_xshare = on;
+    return FPC_OK;
+}
+
 // The h3 image of conv `ci` in the orientation the site runs in, and decoder d's fold images and bias table in s2.0's.
 static int pack_wino_h3_image(const fpc_net* n, int ci, hipStream_t s) {
     const PackedConv& c = n->convs[ci];
@@ -203,7 +213,7 @@ void fill_conv_args(const fpc_net* n, ConvArgs& a, const PackedConv& c, const Co
                     int Wo, long long sb, long long sh, long long sw, long long sc, bool relu, int mode) {
     fill_conv_shape(a, n->B, c, p, Hi, Wi, Ho, Wo, sb, sh, sw, sc, relu, mode);
     a.splitk_ws = n->ws + n->splitk_off; a.zeros = n->ws + n->zeros_off; a.tickets = (int*)(n->ws + n->tickets_off);
-    a.wino_pack = n->wino_pack; a.wino_orient = n->wino_orient;
+    a.wino_pack = n->wino_pack; a.wino_orient = n->wino_orient; a.wino_rowsplit = n->wino_xshare ? 0 : 1;
 }
 
 

@@ -55,6 +55,7 @@ struct ConvArgs {
     long long wino_blocks;            // host side only, written by a form-9 launch: its workgroups
     int wino_pack;                    // host side only: a form-9 launch may use the packed patch geometry (wino_pack_geometry)
     int wino_orient;                  // host side only: a form-9 launch runs transposed where wino_orient_rule says so (wino_launch_geometry)
+    int wino_rowsplit;                // host side only: 1 = a packed form-9 launch keeps the row-split tile map where wino_xshare_rule offers the x-shared one
     int cg;                           // host side only: > 0 = a grouped 3x3 site of Cin = Cout channels in groups of cg (conv_grouped.hip) ...
     const float* grp_w;               // ... and its k_pack_grouped image
 };
@@ -255,6 +256,9 @@ struct WinoArgs {
     // for the kernel; tbx / tby / pack / pack_rx are wino_pack_geometry's on the swapped sizes (pack >= 1), the images were packed
     // from the transposed taps
     int orient;
+    // k_conv_wino_h3 only: 1 = the x-shared tile map (a lane's two tiles are neighbours in x: wino_tile.hpp, XS).  Packed launches
+    // (pack > 1 or orient) whose (virtual) width has an even tile-column count only: conv_plan.hpp's wino_xshare_rule
+    int xshare;
     // wino_w4.hip, wino_h2.hip, wino_h3.hip: the reciprocals of the workgroup-id decode; the launchers fill them (callers leave them zero)
     WinoDecode dec;
 };
@@ -291,6 +295,11 @@ WinoPackGeom wino_pack_geometry(int H, int W, int B, int Cin, bool allow);
 bool wino_orient_rule(int H, int W);
 WinoPackGeom wino_launch_geometry(int H, int W, int B, int Cin, bool orient, bool pack_allow, bool* transposed);
 int launch_wino_pack_h3(const float* w_oihw, float* packed, int Cout, int Cin, bool transpose, hipStream_t s);
+// host views of the four-wave kernels' tile maps (xs: the x-shared one), for tests: fragment reads, staging plan, Z image (wino_h3.hip)
+int wino_tile_frag(bool xs, int wi, int lane, int pk_ks, long long* out17);
+int wino_tile_slot(bool xs, bool tr, int slot, int y_in0, int x_in0, int H, int W, int Cs, int up, int pk_ks, int pk_two, long long* out6);
+int wino_tile_zrun(bool xs, int wi, int mt, int r, int nt, int cc, long long* out3);
+int wino_tile_zread(bool xs, int t_e, int tp, int cc, int i, long long* out1);
 // the fold's weights: wc = W . L (OIHW [Cout][Cmid -> Cin][3][3], f64 sums) and the bias table conv3x3(W, bias . 1_inside) per border
 // class (WinoArgs::btab); W [Cout][Cmid][3][3], L the 1x1 lateral [Cmid][Cin], bias [Cmid]
 int launch_wino_pack_h3_pair(const float* w1, float* packed1, int Cin1, const float* w2, float* packed2, int Cin2, int Cout, bool transpose,

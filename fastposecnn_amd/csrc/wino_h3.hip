@@ -33,6 +33,7 @@
 #include <cstdlib>
 #endif
 #include <type_traits>
+#include "conv_plan.hpp"      // wino_xshare_rule
 #include "wino_tile.hpp"
 
 namespace fpc {
@@ -70,8 +71,16 @@ __device__ __forceinline__ const float* sgpr_ptr(const float* p) {
 // TR: the launch runs TRANSPOSED (wino_orient_rule): a.H x a.W is the virtual image H' = W, W' = H whose pixel (y, x) is the stored
 // pixel (x, y), the weight image was packed from the transposed taps.  The staging plan's byte offsets and the epilogue's output and
 // residual offsets know; nothing else does.  Always with PACK (a single frame per canvas row is pack = 1).
-template <int VAR, bool FOLD, bool PACK, bool TR = false>
+//
+// XS: the X-SHARED tile map (wino_tile.hpp: wino_frag, wino_slot, z_run; packed launches whose tile-column count is even,
+// wino_xshare_rule).  A lane's two tiles are neighbours in x and share two of their four region columns: a K-step reads six columns
+// of two rows (12 fragment reads, not 16) and row-transforms six (not 8); the column transforms, the splits, the operands and the
+// matrix instructions are the plain ones, on the same numbers: every output is the plain map's, bit for bit.
+template <int VAR, bool FOLD, bool PACK, bool TR = false, bool XS = false>
 __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
+    static_assert(PACK || !XS, "the x-shared map needs the packed decode's even seams");
+    constexpr int kNC = XS ? 6 : 8;      // region columns a lane reads per row and K-step; tile half mt transforms columns kNC - 4 apart
+    constexpr int kNR = 2 * kNC / 4;     // fragment reads per slot 0-3 of phase O
     __shared__ __attribute__((aligned(16))) float lds[kLdsFloats];
     long long* const dbg = kWinoStamp ? a.dbg : nullptr;      // a constant in the product build: the stamp code below folds away
     const long long t_entry = dbg ? clock64() : 0;
@@ -125,10 +134,16 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
     const float* isb = sgpr_ptr(src + (size_t)pt.b * (H >> up) * (W >> up) * Cs);      // image base, + 8 floats per step
     unsigned ivo[5];
     unsigned long long imask[5];
-    wino_stage_plan<PACK, TR>(ivo, imask, wi, lane, y_in0, x_in0, H, W, Cs, up, pk_ks, pt.pk_two);
+    wino_stage_plan<PACK, TR, XS>(ivo, imask, wi, lane, y_in0, x_in0, H, W, Cs, up, pk_ks, pt.pk_two);
 #define FPC_H3_ISSUE_IN(BUF, PTR) wino_issue_in(lds + (BUF) * kInFloats, wi, ivo, imask, PTR)
     int in_a[2], in_b[2];
-    const float sgn = wino_frag<PACK>(in_a, in_b, wi, li, lh, pk_ks);
+    const float sgn = wino_frag<PACK, XS>(in_a, in_b, wi, li, lh, pk_ks);
+    // fragment read x = 0 .. kNC - 1 of row a / b: column x of the lane's six (XS), else column x & 3 of tile half x >> 2
+#define FPC_H3_FA(X) wino_frag_at<XS>(in_a, (X) >> 2, XS ? (X) : (X) & 3)
+#define FPC_H3_FB(X) wino_frag_at<XS>(in_b, (X) >> 2, XS ? (X) : (X) & 3)
+    // tile half MT's column transform of the row-transformed columns E[]
+#define FPC_H3_COLUMN(E, MT, JX) ((JX) == 0 ? sub_s4(E[(MT) * (kNC - 4)], E[(MT) * (kNC - 4) + 2]) : (JX) == 1 ? add_s4(E[(MT) * (kNC - 4) + 1], E[(MT) * (kNC - 4) + 2]) : \
+                                  (JX) == 2 ? sub_s4(E[(MT) * (kNC - 4) + 2], E[(MT) * (kNC - 4) + 1]) : sub_s4(E[(MT) * (kNC - 4) + 1], E[(MT) * (kNC - 4) + 3]))
     if (PH == 0) t_plan = fine ? clock64() : 0;
     wino_zero_ring(lds, t, kRing, y_in0, x_in0, H, W, PACK && pk_ks < kTX);
     if (PH == 0) t_zero = fine ? clock64() : 0;
@@ -184,14 +199,14 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) { TA1[j][mt] = u32x4{0u, 0u, 0u, 0u}; TA2[j][mt] = u32x4{0u, 0u, 0u, 0u}; }
     {      // step 0 -> the even halves of xi 0-2; xi 3 stays in vn for E of pair 0
+        f32x4 e[kNC];
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
-            f32x4 e[4];
 #pragma unroll
-            for (int c = 0; c < 4; ++c)
-                e[c] = fma_s4(sgn, *reinterpret_cast<const f32x4*>(lds + in_b[c >> 1] + (c & 1) * in_cs + mt * in_ms),
-                              *reinterpret_cast<const f32x4*>(lds + in_a[c >> 1] + (c & 1) * in_cs + mt * in_ms));
-            vn[mt][0] = sub_s4(e[0], e[2]); vn[mt][1] = add_s4(e[1], e[2]); vn[mt][2] = sub_s4(e[2], e[1]); vn[mt][3] = sub_s4(e[1], e[3]);
+            for (int x = mt * 4; x < (mt ? kNC : 4); ++x)      // (XS: half 1 adds columns 4 and 5 to half 0's four)
+                e[x] = fma_s4(sgn, *reinterpret_cast<const f32x4*>(lds + FPC_H3_FB(x)), *reinterpret_cast<const f32x4*>(lds + FPC_H3_FA(x)));
+#pragma unroll
+            for (int j = 0; j < 4; ++j) vn[mt][j] = FPC_H3_COLUMN(e, mt, j);
 #pragma unroll
             for (int j = 0; j < 3; ++j) { FPC_H3_SPLIT_PAIR(j, mt, 0, 0); FPC_H3_SPLIT_PAIR(j, mt, 1, 0); }
         }
@@ -210,14 +225,12 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
         {
             // the sixteen fragment reads first: 64 KB per workgroup = 512 cycles of the LDS pipe, under the staging burst and xi 3's split
             const float* InE = lds + ((2 * p + 1) & 3) * kInFloats;
-            f32x4 ea[2][4], eb[2][4];
+            f32x4 ea[kNC], eb[kNC];
 #pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    ea[mt][c] = *reinterpret_cast<const f32x4*>(InE + in_a[c >> 1] + (c & 1) * in_cs + mt * in_ms);
-                    eb[mt][c] = *reinterpret_cast<const f32x4*>(InE + in_b[c >> 1] + (c & 1) * in_cs + mt * in_ms);
-                }
+            for (int x = 0; x < kNC; ++x) {
+                ea[x] = *reinterpret_cast<const f32x4*>(InE + FPC_H3_FA(x));
+                eb[x] = *reinterpret_cast<const f32x4*>(InE + FPC_H3_FB(x));
+            }
             __builtin_amdgcn_sched_barrier(0);
             // inputs of steps 2p + 3 and 2p + 4 -> the buffers steps 2p - 1 and 2p were read from before the last barrier
             // (a step past the last is not staged: the end-of-pair wait counts the sixteen weight loads BEHIND the pieces, so fewer
@@ -228,24 +241,26 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) FPC_H3_SPLIT_Q(3, q, 0);      // xi 3 of step 2p: its operands were in use until the end of O
             __builtin_amdgcn_sched_barrier(0);
+            f32x4 e[kNC];
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt) {
-                f32x4 e[4];
 #pragma unroll
-                for (int c = 0; c < 4; ++c) e[c] = fma_s4(sgn, eb[mt][c], ea[mt][c]);
-                vn[mt][0] = sub_s4(e[0], e[2]); vn[mt][1] = add_s4(e[1], e[2]); vn[mt][2] = sub_s4(e[2], e[1]); vn[mt][3] = sub_s4(e[1], e[3]);
+                for (int x = mt * 4; x < (mt ? kNC : 4); ++x) e[x] = fma_s4(sgn, eb[x], ea[x]);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) vn[mt][j] = FPC_H3_COLUMN(e, mt, j);
                 FPC_H3_SPLIT_PAIR(0, mt, 0, 1); FPC_H3_SPLIT_PAIR(0, mt, 1, 1);
             }
         }
         __builtin_amdgcn_sched_barrier(0);
         // ---- O: the pair's 48 matrix instructions; slot sl = 12 j + 4 g + 2 mt + nt, g = 0: A1 B1, 1: A2 B1, 2: A1 B2.  One item per slot:
-        //   sl  0- 3  fragment reads of step 2p + 2       sl  4-11  row transform e       sl 12-19  column transform vn
+        //   sl  0- 3  fragment reads of step 2p + 2       sl  4-11  row transform e (XS: 6-11)       sl 12-19  column transform vn
         //   sl  0- 3 / 4-7 / 8-11  ALSO the split of xi 1 / 2 / 3 of step 2p + 1 into the odd halves (before xi 1's first matrix instruction, slot 12,
         //             and before slot 12 overwrites vn)
         //   sl 20-23 / 24-27 / 36-39  split of xi 0 / 1 / 2 of step 2p + 2 into the even halves (xi j's last matrix instruction: slot 12 j + 11)
         // A weight fragment's last matrix instruction is followed by its reload for the next pair.
         const float* In = lds + ((2 * p + 2) & 3) * kInFloats;
-        f32x4 da[2][4], db[2][4], e[2][4];
+        // XS: three reads per slot 0-3 (read q = 3 sl ..: column q >> 1, row a / b = q & 1), the six row transforms in slots 6-11
+        f32x4 da[kNC], db[kNC], e[kNC];
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -267,25 +282,22 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
                         }
                         if (sl < 4) {
 #pragma unroll
-                            for (int c = 2 * (sl & 1); c < 2 * (sl & 1) + 2; ++c) {
-                                da[sl >> 1][c] = *reinterpret_cast<const f32x4*>(In + in_a[c >> 1] + (c & 1) * in_cs + (sl >> 1) * in_ms);
-                                db[sl >> 1][c] = *reinterpret_cast<const f32x4*>(In + in_b[c >> 1] + (c & 1) * in_cs + (sl >> 1) * in_ms);
+                            for (int q = kNR * sl; q < kNR * sl + kNR; ++q) {
+                                if ((q & 1) == 0) da[q >> 1] = *reinterpret_cast<const f32x4*>(In + FPC_H3_FA(q >> 1));
+                                if ((q & 1) == 1) db[q >> 1] = *reinterpret_cast<const f32x4*>(In + FPC_H3_FB(q >> 1));
                             }
                         }
-                        if (sl >= 4 && sl < 12) {
-                            const int m_ = (sl - 4) >> 2, c = (sl - 4) & 3;
-                            e[m_][c] = fma_s4(sgn, db[m_][c], da[m_][c]);
-                            FPC_H3_PIN4(e[m_][c]);
+                        if (sl >= 12 - kNC && sl < 12) {
+                            const int x = sl - (12 - kNC);
+                            e[x] = fma_s4(sgn, db[x], da[x]);
+                            FPC_H3_PIN4(e[x]);
                         }
                         if (sl < 4) FPC_H3_SPLIT_Q(1, sl, 1);
                         if (sl >= 4 && sl < 8) FPC_H3_SPLIT_Q(2, sl - 4, 1);
                         if (sl >= 8 && sl < 12) FPC_H3_SPLIT_Q(3, sl - 8, 1);
                         if (sl >= 12 && sl < 20 && !(SKIPC && ((sl - 12) & 3) == 2)) {
                             const int m_ = (sl - 12) >> 2, jx = (sl - 12) & 3;
-                            if (jx == 0) vn[m_][0] = sub_s4(e[m_][0], e[m_][2]);
-                            if (jx == 1) vn[m_][1] = add_s4(e[m_][1], e[m_][2]);
-                            if (jx == 2) vn[m_][2] = sub_s4(e[m_][2], e[m_][1]);
-                            if (jx == 3) vn[m_][3] = sub_s4(e[m_][1], e[m_][3]);
+                            vn[m_][jx] = FPC_H3_COLUMN(e, m_, jx);
                             FPC_H3_PIN4(vn[m_][jx]);
                         }
                         if (sl >= 20 && sl < 24) FPC_H3_SPLIT_Q(0, sl - 20, 0);
@@ -311,6 +323,9 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
 #undef FPC_H3_LOAD_U1_AT
 #undef FPC_H3_LOAD_U2_AT
 #undef FPC_H3_XI_LIVE
+#undef FPC_H3_FA
+#undef FPC_H3_FB
+#undef FPC_H3_COLUMN
     };      // kloop
 
     if (!FOLD) {
@@ -331,7 +346,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
     }
     long long* const fdbg = (!(FOLD && PACK) && fine) ? dbg + (size_t)gridDim.x * 32 + ((size_t)blockIdx.x * 4 + wi) * 16 : nullptr;
     if (fdbg && lane == 0) { fdbg[0] = t_dec - t_entry; fdbg[1] = t_wld - t_entry; fdbg[2] = t_plan - t_entry; fdbg[3] = t_zero - t_entry; fdbg[4] = t_issued - t_entry; }
-    wino_output<PACK, FOLD, TR>(lds, acc, P, pt, WinoEpi{H, W, Cout, a.relu, a.tbx, a.tby, a.pack_rx}, inv_s,
+    wino_output<PACK, FOLD, TR, XS>(lds, acc, P, pt, WinoEpi{H, W, Cout, a.relu, a.tbx, a.tby, a.pack_rx}, inv_s,
                             wino_group(a.btab[0], a.btab[1], a.btab[2], a.btab[3], grp), dbg, t_kend, t, wi, fdbg);
 }
 
@@ -358,6 +373,53 @@ WinoPackGeom wino_pack_geometry(int H, int W, int B, int Cin, bool allow) {
     q.tiles = (long long)B * tch * tcw;
     q.gn_rows = q.tby * q.rx;
     return q;
+}
+
+// ---- host views of the two tile maps (wino_tile.hpp), through the very functions the kernels call (fpc_wino_tile_*, conv2d.hip)
+// fragment reads of (wave wi, lane) in a patch with seam pk_ks (>= 8: none): out[0] = n columns, then per column x the byte offsets
+// of its row-a and row-b read in an input buffer
+int wino_tile_frag(bool xs, int wi, int lane, int pk_ks, long long* out17) {
+    if (wi < 0 || wi > 3 || lane < 0 || lane > 63 || pk_ks < 0) return FPC_EINVAL;
+    int in_a[2], in_b[2];
+    if (xs) wino_frag<true, true>(in_a, in_b, wi, lane & 31, lane >> 5, pk_ks);
+    else wino_frag<true, false>(in_a, in_b, wi, lane & 31, lane >> 5, pk_ks);
+    const int n = xs ? 6 : 8;
+    out17[0] = n;
+    for (int x = 0; x < n; ++x) {
+        out17[1 + 2 * x] = 4 * (xs ? wino_frag_at<true>(in_a, 0, x) : wino_frag_at<false>(in_a, x >> 2, x & 3));
+        out17[2 + 2 * x] = 4 * (xs ? wino_frag_at<true>(in_b, 0, x) : wino_frag_at<false>(in_b, x >> 2, x & 3));
+    }
+    return 0;
+}
+// the staging plan's view of 16-byte unit `slot` (= 64 piece + lane) of a packed patch whose region starts at pixel (y_in0, x_in0) of
+// a (virtual) H x W image of Cs channels (up, tr: wino_stage_plan): out6 = {region row, region column, channel half of the unit,
+// behind the seam, staged, byte offset of its source from the K-step's channels of frame b}
+int wino_tile_slot(bool xs, bool tr, int slot, int y_in0, int x_in0, int H, int W, int Cs, int up, int pk_ks, int pk_two, long long* out6) {
+    if (slot < 0 || slot >= 5 * 4 * 64 || pk_ks < 0 || H < 1 || W < 1 || Cs < 8 || up < 0 || up > 1) return FPC_EINVAL;
+    const WinoSlot u = xs ? wino_slot<true>(slot, pk_ks) : wino_slot<false>(slot, pk_ks);
+    const WinoSrc q = xs ? (tr ? wino_stage_src<true, true, true>(slot, y_in0, x_in0, H, W, Cs, up, pk_ks, pk_two != 0)
+                               : wino_stage_src<true, false, true>(slot, y_in0, x_in0, H, W, Cs, up, pk_ks, pk_two != 0))
+                         : (tr ? wino_stage_src<true, true, false>(slot, y_in0, x_in0, H, W, Cs, up, pk_ks, pk_two != 0)
+                               : wino_stage_src<true, false, false>(slot, y_in0, x_in0, H, W, Cs, up, pk_ks, pk_two != 0));
+    out6[0] = 2 * u.ah + ((u.block >> 2) & 1); out6[1] = 2 * u.qh + ((u.block >> 1) & 1); out6[2] = u.block & 1;
+    out6[3] = u.qh > pk_ks; out6[4] = q.ok; out6[5] = q.off;
+    return 0;
+}
+// the Z image.  Writer: out3 = {byte offset of the run of (wave wi, half mt, register r, channel tile nt, column cc), the tile
+// (8 ty + tx) of its lanes 0-31, of its lanes 32-63}.  Reader: the byte offset of thread t_e's read of pass tp, column cc, row i.
+int wino_tile_zrun(bool xs, int wi, int mt, int r, int nt, int cc, long long* out3) {
+    if (wi < 0 || wi > 3 || (mt | nt | cc) < 0 || (mt | nt | cc) > 1 || r < 0 || r > 15) return FPC_EINVAL;
+    out3[0] = z_run(cc, mt, r, nt, xs) + 256 * wi;
+    for (int hb = 0; hb < 2; ++hb) {
+        const int li = (r & 3) + 8 * (r >> 2) + 4 * hb;      // the matrix instruction's row of this register and lane half
+        out3[1 + hb] = xs ? 8 * (li >> 2) + 2 * (li & 3) + mt : 32 * mt + li;
+    }
+    return 0;
+}
+int wino_tile_zread(bool xs, int t_e, int tp, int cc, int i, long long* out1) {
+    if (t_e < 0 || t_e > 255 || tp < 0 || tp > 3 || cc < 0 || cc > 1 || i < 0 || i > 3) return FPC_EINVAL;
+    out1[0] = z_read_base(t_e >> 4, t_e & 15, xs) + z_read_step(tp, cc, i, xs);
+    return 0;
 }
 
 // what the fold's launch needs on top of wino_tile_check (wino_output<PACK, true> RELIES on these refusals)
@@ -402,22 +464,27 @@ int launch_conv_wino_h3(const WinoArgs& a_in, int groups, hipStream_t s) {
         // the transposed taps (launch_wino_pack_h3 / _pair, launch_fold_compose with transpose = true)
         WinoArgs t = a;
         std::swap(t.H, t.W);
-        if (a.pack < 1 || a.dbg) return FPC_EINVAL;
+        if (a.pack < 1) return FPC_EINVAL;      // (a stamp buffer: the plain records only, and never with the fold — wino_fold_check)
         if (const int rc = wino_tile_check(t, groups, 16, kPairBytes, true, &nblk)) return rc;
         t.dec = wino_decode(t.Cout, groups, t.tbx, t.tby, t.W, t.B, t.pack);
+        if (a.xshare && !wino_xshare_rule(t.W)) return FPC_EINVAL;      // (an odd seam would part a lane's tile pair)
         if (a.fold) {
             if (const int rc = wino_fold_check(a, groups)) return rc;
-            hipLaunchKernelGGL((k_conv_wino_h3<0, true, true, true>), dim3((unsigned)nblk), dim3(256), 0, s, t);
+            if (a.xshare) hipLaunchKernelGGL((k_conv_wino_h3<0, true, true, true, true>), dim3((unsigned)nblk), dim3(256), 0, s, t);
+            else hipLaunchKernelGGL((k_conv_wino_h3<0, true, true, true>), dim3((unsigned)nblk), dim3(256), 0, s, t);
         } else {
-            hipLaunchKernelGGL((k_conv_wino_h3<0, false, true, true>), dim3((unsigned)nblk), dim3(256), 0, s, t);
+            if (a.xshare) hipLaunchKernelGGL((k_conv_wino_h3<0, false, true, true, true>), dim3((unsigned)nblk), dim3(256), 0, s, t);
+            else hipLaunchKernelGGL((k_conv_wino_h3<0, false, true, true>), dim3((unsigned)nblk), dim3(256), 0, s, t);
         }
         return check_launch();
     }
     if (const int rc = wino_tile_check(a_in, groups, 16, kPairBytes, a_in.pack > 1, &nblk)) return rc;
     WinoArgs a = a_in;      // + the reciprocals of the workgroup-id decode (wino_patch)
     a.dec = wino_decode(a.Cout, groups, a.tbx, a.tby, a.W, a.B, a.pack > 1 ? a.pack : 0);
+    if (a.xshare && (a.pack <= 1 || a.fold || !wino_xshare_rule(a.W))) return FPC_EINVAL;      // packed launches only
     if (a.pack > 1) {
-        hipLaunchKernelGGL((k_conv_wino_h3<0, false, true>), dim3((unsigned)nblk), dim3(256), 0, s, a);
+        if (a.xshare) hipLaunchKernelGGL((k_conv_wino_h3<0, false, true, false, true>), dim3((unsigned)nblk), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_conv_wino_h3<0, false, true>), dim3((unsigned)nblk), dim3(256), 0, s, a);
         return check_launch();
     }
     // c2 + up2(p3): both phases pairs of K-steps, p2 exactly 2 x p3, the bias table and nothing else in the epilogue.  wino_output<PACK, true>

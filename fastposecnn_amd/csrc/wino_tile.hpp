@@ -33,13 +33,26 @@ constexpr int kPairBytes = 16 * 2 * 2 * 64 * 16; // k_wino_pack_fp16<true>'s ima
 // 64 KB region that starts HALF a 256-byte bank row late: a ds_read_b128 lane group of the output stage holds eight quads of an even
 // tile and eight of the odd tile beside it, all from the same half of their runs (lane bit 5 of the writer = tile bit 2, the same for
 // a whole reading wave) — the shift puts the odd tile's on the other 128 bytes of the bank row, 16 different 16-byte slots per group.
+// xs (the x-shared tile map, wino_frag<PACK, true>): register r of half mt holds tile row 2 (r >> 2) + (lane >> 5), tile column
+// 2 (r & 3) + mt, and the even / odd tile pair of a reading lane group differs in mt: there the runs of mt = 1 live in the late region
+// and r's low bit takes mt's place in the index.  The same bytes, the same two M0 bases, the same reach.
 constexpr int kZOdd = 64 * 1024 + 128;           // byte offset of the odd runs' region
-constexpr int z_run(int cc, int mt, int r, int nt) { return ((((cc * 2 + mt) * 8 + (r >> 1)) * 2 + nt) * 4) * 256 + (r & 1) * kZOdd; }
+constexpr int z_run(int cc, int mt, int r, int nt, bool xs = false) {
+    return ((((cc * 2 + (xs ? (r & 1) : mt)) * 8 + (r >> 1)) * 2 + nt) * 4) * 256 + (xs ? mt : (r & 1)) * kZOdd;
+}
+// byte offset of the output stage's first read of thread (tile otl of a 16-tile pass, channel quad oq): its tile of pass 0, row 0, cc 0
+// (pass tp, column cc, row i: + z_run(cc, tp >> 1, 8 (tp & 1), 0) + 256 i; xs: + z_run(cc, 0, 4 tp, 0, true) + 256 i)
+constexpr int z_read_base(int otl, int oq, bool xs = false) {
+    return xs ? z_run(0, otl & 1, (otl >> 1) & 3, oq >> 3, true) + (otl >> 3) * 128 + (oq & 7) * 16
+              : z_run(0, 0, (otl & 3) + 4 * (otl >> 3), oq >> 3) + ((otl >> 2) & 1) * 128 + (oq & 7) * 16;
+}
+constexpr int z_read_step(int tp, int cc, int i, bool xs = false) { return (xs ? z_run(cc, 0, 4 * tp, 0, true) : z_run(cc, tp >> 1, 8 * (tp & 1), 0)) + 256 * i; }
 // ds_write_addtid_b32 adds M0's low 16 bits and a 16-bit immediate: the even runs from M0 = image + 256 wi (immediates up to 63 KB),
 // the odd ones from that + kZOddM0 (immediates 960 .. 65 472); both fit while the image starts in the first kZM0Slack bytes of LDS
 constexpr int kZOddM0 = 64704;
 constexpr int kZM0Slack = 65535 - 3 * 256 - kZOddM0;
 static_assert(z_run(1, 1, 15, 1) - kZOddM0 < 65536 && z_run(0, 0, 1, 0) >= kZOddM0 && kZM0Slack >= 0, "ds_write_addtid_b32's reach");
+static_assert(z_run(1, 1, 15, 1, true) == z_run(1, 1, 15, 1) && z_run(0, 1, 0, 0, true) == z_run(0, 0, 1, 0) && z_run(1, 0, 15, 1, true) < 65536 - 3 * 256, "... and the x-shared map's");
 constexpr int kLdsFloats = 4 * 2 * kNT * kBN + 32;      // the Z image = 128 KB + the odd region's shift; the K loop's input buffers live in its space
 static_assert(z_run(1, 1, 15, 1) + 3 * 256 + 256 == kLdsFloats * 4, "the last run ends the image");
 
@@ -122,26 +135,58 @@ __device__ __forceinline__ T wino_group(const T v0, const T v1, const T v2, cons
 // ks holds frame f's last pixel (and the zero of x = W), column ks + 1 the zero of x = -1 and frame f + 1's first pixel.
 // TR: H x W is the VIRTUAL image of a transposed launch (wino_orient_rule): its pixel (y, x) is the stored image's pixel (x, y), whose
 // rows are H pixels long.  Only the lane's byte offset knows; a frame is as large either way.
-template <bool PACK, bool TR = false>
+// XS (the x-shared tile map, wino_frag): a lane reads the column pairs qh = 2k + s .. 2k + s + 2 of its tile pair k = 0..3 (s = 1 behind
+// a seam; the seam ks is EVEN: wino_xshare_rule), so the bank slot takes the pair index, not the column's: with the LOGICAL column
+// u = qh - (qh > ks), unit = ((ah >> 2) * 3 + col) * 8 + block) * 16 + 4 * ((u >> 1) & 3) + (ah & 3), col = u & 1 — the three reads of a
+// lane then sit in slots 4 k, 4 k, 4 (k + 1) + (ah & 3) whatever the seam, and column pair 1 is column pair 0's unit + one cell.
+// Column 2 of the cells holds what is left: u = 8 in slot group 0, and frame f's last column pair qh = ks (whose u the first pair
+// behind the seam has too) in slot group ks / 2 = that of the lane that reads it as its third.  The same 9 x 8 x 16 units.
+struct WinoSlot { int ah, qh, block; bool ok; };      // of a 16-byte unit: region row pair, column pair, (ry & 1) * 4 + (rx & 1) * 2 + channel half
+template <bool XS>
+constexpr WinoSlot wino_slot(int slot, int ks) {
+    const int blk = slot >> 4, res = slot & 15, cell = blk >> 3;
+    const int ah = (cell / 3) * 4 + (res & 3);
+    if (!XS) return WinoSlot{ah, (cell % 3) * 4 + (res >> 2), blk & 7, true};
+    const int col = cell % 3, g = res >> 2;
+    const bool seam = ks < kTX;
+    if (col < 2) return WinoSlot{ah, 2 * g + col + ((seam && 2 * g + col >= ks) ? 1 : 0), blk & 7, true};
+    if (seam && ks > 0 && g == (ks >> 1)) return WinoSlot{ah, ks, blk & 7, true};
+    return WinoSlot{ah, kTX + (seam ? 1 : 0), blk & 7, g == 0};
+}
+// the unit of (row pair ah, column pair qh, block) in the x-shared image (a seam patch with ks = 0 has no tile in front of the seam
+// and stages nothing there: its qh = 0 has no unit)
+constexpr int wino_xs_unit(int ah, int qh, int block, int ks) {
+    const bool seam = ks < kTX;
+    const int u = qh - ((seam && qh > ks) ? 1 : 0);
+    const bool last = seam && qh == ks;      // frame f's last column pair
+    const int col = (last || u == kTX) ? 2 : (u & 1), g = last ? (ks >> 1) : ((u >> 1) & 3);
+    return (((ah >> 2) * 3 + col) * 8 + block) * 16 + 4 * g + (ah & 3);
+}
+// what unit `slot` (= 64 piece + lane) of an input buffer is filled from: whether it is staged at all, and its byte offset from the
+// K-step's channels of frame b
+struct WinoSrc { bool ok; unsigned off; };
+template <bool PACK, bool TR = false, bool XS = false>
+constexpr WinoSrc wino_stage_src(int slot, int y_in0, int x_in0, int H, int W, int Cs, int up, int pk_ks, bool pk_two) {
+    const int Hs = H >> up, Ws = W >> up;                      // the source image's own size
+    const WinoSlot us = wino_slot<XS>(slot, pk_ks);
+    const int blk = us.block, ah = us.ah, qh = us.qh;
+    const int hf = blk & 1;
+    const int ry = 2 * ah + ((blk >> 2) & 1), rx = 2 * qh + ((blk >> 1) & 1);
+    const bool far = PACK && qh > pk_ks;      // behind the seam: frame b + 1, one gap column in between
+    const int y = y_in0 + ry, x = far ? rx - 2 * pk_ks - 3 : x_in0 + rx;
+    const int qmax = (PACK && pk_ks < kTX) ? kTX + 1 : kTX;
+    const bool iok = slot < kInPieces * 64 && us.ok && ah <= kTY && qh <= qmax && y >= 0 && y < H && x >= 0 && x < W && (!far || pk_two);
+    const size_t px = TR ? (size_t)(x >> up) * Hs + (y >> up) : (size_t)(y >> up) * Ws + (x >> up);
+    return WinoSrc{iok, iok ? (unsigned)((px * Cs + 4 * hf) * sizeof(float)) + (far ? (unsigned)((size_t)Hs * Ws * Cs * sizeof(float)) : 0u) : 0u};
+}
+template <bool PACK, bool TR = false, bool XS = false>
 __device__ __forceinline__ void wino_stage_plan(unsigned (&ivo)[5], unsigned long long (&imask)[5], int wi, int lane, int y_in0, int x_in0, int H,
                                                 int W, int Cs, int up, int pk_ks, bool pk_two) {
-    const int Hs = H >> up, Ws = W >> up;                      // the source image's own size
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
-        const int slot = (wi + 4 * i) * 64 + lane;
-        const int blk = slot >> 4, res = slot & 15, cell = blk >> 3;
-        const int ah = (cell / 3) * 4 + (res & 3), qh = (cell % 3) * 4 + (res >> 2);
-        const int hf = blk & 1;
-        const int ry = 2 * ah + ((blk >> 2) & 1), rx = 2 * qh + ((blk >> 1) & 1);
-        const bool far = PACK && qh > pk_ks;      // behind the seam: frame b + 1, one gap column in between
-        const int y = y_in0 + ry, x = far ? rx - 2 * pk_ks - 3 : x_in0 + rx;
-        const int qmax = (PACK && pk_ks < kTX) ? kTX + 1 : kTX;
-        const bool iok = wi + 4 * i < kInPieces && ah <= kTY && qh <= qmax && y >= 0 && y < H && x >= 0 && x < W && (!far || pk_two);
-        const size_t px = TR ? (size_t)(x >> up) * Hs + (y >> up) : (size_t)(y >> up) * Ws + (x >> up);
-        ivo[i] = iok ? (unsigned)((px * Cs + 4 * hf) * sizeof(float)) +
-                              (far ? (unsigned)((size_t)Hs * Ws * Cs * sizeof(float)) : 0u)
-                        : 0u;
-        imask[i] = __ballot(iok);
+        const WinoSrc q = wino_stage_src<PACK, TR, XS>((wi + 4 * i) * 64 + lane, y_in0, x_in0, H, W, Cs, up, pk_ks, pk_two);
+        ivo[i] = q.off;
+        imask[i] = __ballot(q.ok);
     }
 }
 // One K-step's pieces -> the input buffer at `buf` from the image at `src` (wave-uniform).  One asm block, no branch: EXEC is set to
@@ -172,20 +217,31 @@ __device__ __forceinline__ void wino_issue_in(const float* buf, int wi, const un
 // ---- fragment addressing: this lane's tile of half 0 (half 1 = four tile rows further down = + 3 cells), the two region rows of
 // transform row wi, columns 2 txl + c.  in_a[ch] / in_b[ch]: float offsets of rows ra / rb at column 2 (txl + ch) in an input buffer;
 // returns the sign.  Row pair (ra, rb) and sign of B^T row wi:  0: d0-d2   1: d1+d2   2: d2-d1   3: d1-d3.  PACK: columns behind the seam lie one further.
+// XS, the x-shared map: a lane's two tiles are NEIGHBOURS in x — lane li holds tiles 2k and 2k + 1, k = li & 3, of tile row li >> 2 (half
+// mt = the tile column's low bit) — and share two of their four region columns: six columns c = 0..5 at 2 (2k + s) + c, tile mt
+// transforms columns 2 mt .. 2 mt + 3.  in_a[0] / in_b[0]: column pair 0 (pair 1: + in_xc), in_a[1] / in_b[1]: column pair 2.
 constexpr int in_cs = 2 * 16 * 4;          // + 1 column: the (rx & 1) block bit
 constexpr int in_ms = 3 * 8 * 16 * 4;      // + 4 tile rows (tile half 1): the next row of cells
-template <bool PACK>
-__device__ __forceinline__ float wino_frag(int (&in_a)[2], int (&in_b)[2], int wi, int li, int lh, int pk_ks) {
-    const int tyl = li >> 3, txl = (li & 7) + ((PACK && (li & 7) >= pk_ks) ? 1 : 0);
+constexpr int in_xc = 8 * 16 * 4;          // XS: + 1 column pair from a lane's first: the next cell
+template <bool PACK, bool XS = false>
+__host__ __device__ __forceinline__ float wino_frag(int (&in_a)[2], int (&in_b)[2], int wi, int li, int lh, int pk_ks) {
+    const int tyl = XS ? li >> 2 : li >> 3;
+    const int txl = XS ? 2 * (li & 3) + ((PACK && 2 * (li & 3) >= pk_ks) ? 1 : 0) : (li & 7) + ((PACK && (li & 7) >= pk_ks) ? 1 : 0);
     const int ra = (wi == 0) ? 0 : (wi == 2 ? 2 : 1);
     const int rb = (wi == 0) ? 2 : (wi == 1 ? 2 : (wi == 2 ? 1 : 3));
     auto unit = [&](int r, int ch) {      // float offset of row 2 tyl + r, column 2 (txl + ch), this lane's channel half
         const int ah = tyl + (r >> 1), qh = txl + ch;
+        if (XS) return wino_xs_unit(ah, qh, (r & 1) * 4 + lh, PACK ? pk_ks : 99) * 4;
         return ((((ah >> 2) * 3 + (qh >> 2)) * 8 + (r & 1) * 4 + lh) * 16 + 4 * (qh & 3) + (ah & 3)) * 4;
     };
-    in_a[0] = unit(ra, 0); in_a[1] = unit(ra, 1);
-    in_b[0] = unit(rb, 0); in_b[1] = unit(rb, 1);
+    in_a[0] = unit(ra, 0); in_a[1] = unit(ra, XS ? 2 : 1);
+    in_b[0] = unit(rb, 0); in_b[1] = unit(rb, XS ? 2 : 1);
     return (wi == 1) ? 1.f : -1.f;
+}
+// float offset of one fragment read from the pair above.  XS: column c = 0..5; else column c = 0..3 of tile half mt
+template <bool XS>
+__host__ __device__ __forceinline__ int wino_frag_at(const int (&in_x)[2], int mt, int c) {
+    return XS ? ((c >> 1) == 2 ? in_x[1] : in_x[0] + (c >> 1) * in_xc) + (c & 1) * in_cs : in_x[c >> 1] + (c & 1) * in_cs + mt * in_ms;
 }
 // a patch that reaches over the image border zeroes its nbuf input buffers once (inactive DMA lanes leave them alone); an interior
 // patch rewrites every unit the fragment reads touch with every step's DMA.  (A seam patch zeroes too: the units of x = W and
@@ -214,7 +270,7 @@ __device__ __forceinline__ void wino_zero_ring(float* lds, int t, int nbuf, int 
 struct WinoEpi { int H, W, Cout, relu, tbx, tby, pack_rx; };
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm"      // (the Z stores name m0 as clobbered)
-template <bool PACK, bool FOLD, bool TR = false>
+template <bool PACK, bool FOLD, bool TR = false, bool XS = false>
 __device__ __forceinline__ void wino_output(float* lds, const f32x16 (&acc)[4][2][2], const ConvPtrs P, const WinoPatch pt, const WinoEpi e,
                                             const float inv_s, const float* btab, long long* dbg, const long long t_kend, const int t,
                                             const int wi, long long* fdbg = nullptr) {
@@ -261,6 +317,7 @@ __device__ __forceinline__ void wino_output(float* lds, const f32x16 (&acc)[4][2
                 for (int cc = 0; cc < 2; ++cc)
 #pragma unroll
                     for (int odd = 0; odd < 2; ++odd) {
+                        const int late = XS ? mt : odd;      // the run lies in the late region, reached from the second base
                         float z[8];
 #pragma unroll
                         for (int h = 0; h < 8; ++h) {
@@ -268,14 +325,14 @@ __device__ __forceinline__ void wino_output(float* lds, const f32x16 (&acc)[4][2
                             const float m0 = acc[0][mt][nt][r], m1 = acc[1][mt][nt][r], m2 = acc[2][mt][nt][r], m3 = acc[3][mt][nt][r];
                             z[h] = cc == 0 ? m0 + m1 + m2 : m1 - m2 - m3;
                         }
-#define FPC_Z_IMM(H) "i"(z_run(cc, mt, 2 * (H) + odd, nt) - odd * kZOddM0)
+#define FPC_Z_IMM(H) "i"(z_run(cc, mt, 2 * (H) + odd, nt, XS) - late * kZOddM0)
                         asm volatile("s_mov_b32 m0, %8\n s_nop 0\n"
                                      "ds_write_addtid_b32 %0 offset:%9\n ds_write_addtid_b32 %1 offset:%10\n"
                                      "ds_write_addtid_b32 %2 offset:%11\n ds_write_addtid_b32 %3 offset:%12\n"
                                      "ds_write_addtid_b32 %4 offset:%13\n ds_write_addtid_b32 %5 offset:%14\n"
                                      "ds_write_addtid_b32 %6 offset:%15\n ds_write_addtid_b32 %7 offset:%16\n"
                                      :: "v"(z[0]), "v"(z[1]), "v"(z[2]), "v"(z[3]), "v"(z[4]), "v"(z[5]), "v"(z[6]), "v"(z[7]),
-                                        "s"(zm0 + odd * kZOddM0), FPC_Z_IMM(0), FPC_Z_IMM(1), FPC_Z_IMM(2), FPC_Z_IMM(3), FPC_Z_IMM(4),
+                                        "s"(zm0 + late * kZOddM0), FPC_Z_IMM(0), FPC_Z_IMM(1), FPC_Z_IMM(2), FPC_Z_IMM(3), FPC_Z_IMM(4),
                                         FPC_Z_IMM(5), FPC_Z_IMM(6), FPC_Z_IMM(7)
                                      : "memory", "m0");
 #undef FPC_Z_IMM
@@ -287,18 +344,18 @@ __device__ __forceinline__ void wino_output(float* lds, const f32x16 (&acc)[4][2
     if (kWinoStamp && fdbg && (t & 63) == 0) fdbg[10] = clock64() - t_kend;      // barrier
     f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
     // this thread's quad of its tile of pass 0, row 0, cc 0
-    const float* const zr = lds + z_run(0, 0, (otl & 3) + 4 * (otl >> 3), oq >> 3) / 4 +
-                            ((otl >> 2) & 1) * 32 + (oq & 7) * 4;
+    const float* const zr = lds + z_read_base(otl, oq, XS) / 4;
 #pragma unroll
     for (int tp = 0; tp < 4; ++tp) {
         const int ot = otl + 16 * tp;
         const int oty = pt.ty0 + (ot >> 3);
         f32x4 z[4][2];
         // tile ot = otl + 16 tp of the Z image: mt = tp >> 1, r = (otl & 3) + 4 ((otl >> 3) + 2 (tp & 1)), writer half (otl >> 2) & 1
+        // (XS: mt = otl & 1, r = ((otl >> 1) & 3) + 4 tp, writer half otl >> 3)
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int cc = 0; cc < 2; ++cc) z[i][cc] = *reinterpret_cast<const f32x4*>(zr + (z_run(cc, tp >> 1, 8 * (tp & 1), 0) + 256 * i) / 4);
+            for (int cc = 0; cc < 2; ++cc) z[i][cc] = *reinterpret_cast<const f32x4*>(zr + z_read_step(tp, cc, i, XS) / 4);
 #pragma unroll
         for (int rr = 0; rr < 2; ++rr)
 #pragma unroll

@@ -200,6 +200,11 @@ class NetEngine:
         the workspace do not change."""
         nat.check(self._lib.fpc_net_set_wino_orient(self._h, int(on)), "fpc_net_set_wino_orient")
 
+    def set_wino_xshare(self, on):
+        """Packed form-9 Winograd launches use the x-shared tile map where the frame's tile-column count is even (on = 1, the
+        library's default) or the row-split map everywhere (on = 0).  The same results bit for bit; plans and images do not change."""
+        nat.check(self._lib.fpc_net_set_wino_xshare(self._h, int(on)), "fpc_net_set_wino_xshare")
+
     def wino_blocks(self):
         """Workgroups of all form-9 launches of the last forward that launched its kernels."""
         return int(self._lib.fpc_net_wino_blocks(self._h))

@@ -729,6 +729,27 @@ int fpc_wino_orient_geometry(int H, int W, int B, int Cin, int fold, int pack, i
  * groups, tbx, tby, tbx * tby, the patches per row of a ragged last canvas row (tbx where there is none), ceil(W / 2). */
 int fpc_wino_recip(uint32_t d, int64_t* out2);
 int fpc_wino_decode(int Cout, int groups, int tbx, int tby, int W, int B, int pack, int64_t* out14);
+/* The TILE MAP of a packed form-9 launch (several frames per canvas row, or transposed).  Row-split: a lane's two tiles lie four tile
+ * rows apart.  X-shared: they are the neighbours 2k, 2k + 1 of one tile row and share half their input columns (12 fragment reads
+ * and 6 row transforms per K-step and wave instead of 16 and 8); taken iff the frame's tile-column count ceil(W / 2) of the launch's
+ * (virtual) width is even — fpc_wino_xshare_rule(W) = 1 — since every seam of a packed patch is then even.  Outputs and GroupNorm
+ * records are the same bit for bit.  fpc_net_set_wino_xshare: on = 1 (default) / 0 = every launch row-split; drops the recorded
+ * graph.  fpc_conv2d's -12 / -13 are -10 / -11 on the row-split map.
+ * fpc_wino_tile_*: the maps as the kernels compute them (host only; xshare 0 / 1).  _frag: out17 = {n, then per region column
+ * x < n of (wave wi, lane) in a patch with its seam after pk_ks tile columns (>= 8: none) the byte offsets of the two fragment reads
+ * in an input buffer}.  _slot: the staging plan's view of the buffer's 16-byte unit `slot` in a packed patch whose 18 x 18 region
+ * starts at pixel (y_in0, x_in0) of the launch's (virtual; tr = 1: transposed) H x W image of Cs channels, read as its nearest-x2
+ * upsample where up = 1, pk_two: the frame behind the seam exists: out6 = {region row, region column, channel half, behind the seam,
+ * staged, byte offset of the source from the K-step's first channel of the patch's frame}.
+ * _zrun: out3 = {byte offset in the output transform image of the run of (wave wi, tile half mt, accumulator register r, channel
+ * tile nt, column cc), tile 8 ty + tx of its lanes 0-31, of its lanes 32-63}.  _zread: byte offset of the output stage's read of
+ * thread t_e, tile pass tp, column cc, row i. */
+int fpc_wino_xshare_rule(int W);
+int fpc_net_set_wino_xshare(fpc_net_t* net, int on);
+int fpc_wino_tile_frag(int xshare, int wi, int lane, int pk_ks, int64_t* out17);
+int fpc_wino_tile_slot(int xshare, int tr, int slot, int y_in0, int x_in0, int H, int W, int Cs, int up, int pk_ks, int pk_two, int64_t* out6);
+int fpc_wino_tile_zrun(int xshare, int wi, int mt, int r, int nt, int cc, int64_t* out3);
+int fpc_wino_tile_zread(int xshare, int t_e, int tp, int cc, int i, int64_t* out1);
 /* Workgroups of all form-9 launches of the last forward that launched (or captured) its kernels: what the switch above changes. */
 int64_t fpc_net_wino_blocks(const fpc_net_t* net);
 /* FLOP of one forward over the batch under the current plans: out3 = {2 x MACs of the direct convolutions (what the
@@ -755,6 +776,7 @@ int fpc_net_tensor(const fpc_net_t* net, const char* name, const float** ptr, in
  * implicit GEMM with split-K factor k on two fp16 pieces per operand and three piece products (channel stride 1, Cin a multiple
  * of 32; 6100 + k: split-K summed by a second launch), 7000 + parts the pixel-resident FPN lateral product on the same two pieces.  5000 is never a request: fpc_net_conv_plan's "folded away". */
 enum {      /* the bases of those codes, as fpc_net_conv_plan reports them and fpc_conv2d takes them (a Winograd form: -form) */
+    FPC_PLAN_WINO_ORIENT_ROWSPLIT = -13, FPC_PLAN_WINO_PACKED_ROWSPLIT = -12,      /* -11 / -10 on the row-split tile map (fpc_wino_xshare_rule) */
     FPC_PLAN_WINO_ORIENT = -11, FPC_PLAN_WINO_PACKED = -10, FPC_PLAN_TWO_LAUNCH = 100, FPC_PLAN_BF3 = 1000, FPC_PLAN_LATERAL = 2000, FPC_PLAN_STEM = 3000,
     FPC_PLAN_STEM_POOL = 3100, FPC_PLAN_POINTWISE = 4000, FPC_PLAN_FOLDED = 5000, FPC_PLAN_H3 = 6000, FPC_PLAN_LATERAL_H3 = 7000,
     FPC_PLAN_GROUPED = 8000      /* + form: the grouped 3x3 kernel (fpc_conv2d_grouped; fpc_conv2d itself refuses the code) */
