@@ -149,6 +149,13 @@ _SIGNATURES = {
     "fpc_conv1x1_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
     "fpc_conv1x1_f32_form": (_i, [_i64, _i, _i]),
     "fpc_stem3x3s2": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "fpc_mbconv_dw": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "fpc_mbconv_gate_slabs": (_i, [_i, _i, _i]),
+    "fpc_mbconv_gate_scratch_floats": (_sz, [_i, _i, _i, _i]),
+    "fpc_mbconv_gate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "fpc_mbconv_pw": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _vp]),
+    "fpc_mbconv_pw_form": (_i, [_i, _i64, _i, _i]),
+    "fpc_mbconv_stem": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "fpc_dwconv3x3_dgrad": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "fpc_dwconv3x3_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "fpc_dwconv3x3_wgrad": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),

@@ -79,6 +79,11 @@ __device__ __forceinline__ f32x4 fma_s4(float s, f32x4 b, f32x4 a) {      // s *
     return r;
 }
 
+// sigmoid and swish (v * sigmoid(v)) of the EfficientNet epilogues as one correctly rounded division each (common.hpp: div_ieee, never
+// a compiler-expanded `/`).  v = 100: exp(-v) underflows, the results are 1 and v; v = -100: exp(-v) = inf, the results are 0 and -0.
+__device__ __forceinline__ float sigmoid(float v) { return div_ieee(1.0f, 1.0f + expf(-v)); }
+__device__ __forceinline__ float swish(float v) { return div_ieee(v, 1.0f + expf(-v)); }
+
 // LDS operand rows are 32 floats (128 B) with NO padding: the 16-byte chunk c of row r lives in slot c ^ (r & 7), which
 // keeps both the staging writes and the fragment reads conflict-free (8 consecutive rows hit 8 distinct slots of
 // each half of the 64-bank window).  32 KB for the 64x64 tiling, 48 KB for 64x128 / 128x64 (36-float padded rows:

@@ -22,6 +22,10 @@
 //                  that still leaves the chip two waves per SIMD and wastes no tile.  The sum over k runs in ascending K-steps whatever NT is.
 //   k_conv1x1_f32_small  the same product on 16 x 16 tiles (v_mfma_f32_16x16x4_f32) for the sites with too few pixel rows to fill
 //                  the chip with 32 x 32 tiles: see the kernel.
+// The stem and the two 1x1 kernels carry a template parameter MB.  Its true instantiations are the EfficientNet encoder's
+// (efficientnet.hip holds that encoder's other kernels and the entries): the stem's window starts at (2 ho, 2 wo) and ends in swish;
+// the 1x1 kernels know act 2 = swish and multiply a per-frame, per-channel gate into the in operand.  MB = false compiles to what
+// these kernels were before the parameter: no gate pointer is read, the activation is the two-way select.
 #include <initializer_list>
 
 #include "conv_device.hpp"
@@ -40,12 +44,20 @@ __device__ __forceinline__ RowWalk xcd_rows(unsigned total, unsigned rpb, unsign
 }
 
 __device__ __forceinline__ float act_apply(float v, int act) { return act ? fminf(fmaxf(v, 0.f), 6.f) : v; }
+// ... and with code 2, swish v / (1 + exp(-v)): the EfficientNet instantiations (MB) alone, so the others keep their two-way select
+template <bool MB>
+__device__ __forceinline__ float act_apply(float v, int act) {
+    if constexpr (MB) return act == 2 ? swish(v) : act_apply(v, act);
+    else return act_apply(v, act);
+}
 
 constexpr long long kWalkLimit = (1LL << 32) - 4096LL * 256 - 8;      // the 32-bit walks keep a grid stride of headroom
 
 }  // namespace
 
-// in4 [B][Hi][Wi][4] (the fourth channel is not read), w [32][3][3][3], out [B][Ho][Wo][32]; npix = B Ho Wo
+// in4 [B][Hi][Wi][4] (the fourth channel is not read), w [32][3][3][3], out [B][Ho][Wo][32]; npix = B Ho Wo.  MB: EfficientNet's stem,
+// the same sum with the window starting at (2 ho, 2 wo) (pads 0 before and 1 after) and swish in place of ReLU6
+template <bool MB>
 __global__ __launch_bounds__(256) void k_stem3x3s2(const float* __restrict__ in4, const float* __restrict__ w,
                                                    const float* __restrict__ scale, const float* __restrict__ shift,
                                                    float* __restrict__ out, unsigned npix, int Hi, int Wi, int Ho, int Wo) {
@@ -63,10 +75,10 @@ __global__ __launch_bounds__(256) void k_stem3x3s2(const float* __restrict__ in4
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kh = 0; kh < 3; ++kh) {
-            const int hi = 2 * (int)ho - 1 + kh;
+            const int hi = 2 * (int)ho - (MB ? 0 : 1) + kh;
 #pragma unroll
             for (int kw = 0; kw < 3; ++kw) {
-                const int wi = 2 * (int)wo - 1 + kw;
+                const int wi = 2 * (int)wo - (MB ? 0 : 1) + kw;
                 f32x4 x = f32x4{0.f, 0.f, 0.f, 0.f};
                 if (hi >= 0 && hi < Hi && wi >= 0 && wi < Wi) x = *reinterpret_cast<const f32x4*>(in4 + (((size_t)b * Hi + hi) * Wi + wi) * 4);
 #pragma unroll
@@ -77,7 +89,7 @@ __global__ __launch_bounds__(256) void k_stem3x3s2(const float* __restrict__ in4
         }
         f32x4 o;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = fminf(fmaxf(acc[j] * sc[j] + sh[j], 0.f), 6.f);
+        for (int j = 0; j < 4; ++j) o[j] = act_apply<MB>(acc[j] * sc[j] + sh[j], MB ? 2 : 1);
         *reinterpret_cast<f32x4*>(out + (size_t)p * 32 + 4 * q) = o;
     }
 }
@@ -140,11 +152,14 @@ __global__ __launch_bounds__(256) void k_dwconv3x3(const float* __restrict__ in,
 // in [M][Cin], w [Cout][Cin], out / res [M][Cout]; waves = mtiles * nchunks, the chunk index fastest.  U K-steps of 8 per loop
 // iteration: their loads are issued together, one iteration ahead of the MFMAs that read them; the K-steps past the last full
 // iteration (fewer than U) load together behind the loop.  Ascending K-steps whatever NT and U are.
-template <int NT, int U>
+// MB (the EfficientNet 1x1 sites): act 2 is swish, and where `gate` [M / HW][Cin] is not NULL the in operand is in[m][k] gate[m / HW][k],
+// rounded to f32 before it enters the matrix instruction; the frame m / HW is a lane's own (a tile may straddle frames).  The
+// instantiations without MB never read gate and HW.
+template <int NT, int U, bool MB>
 __global__ __launch_bounds__(256) void k_conv1x1_f32(const float* __restrict__ in, const float* __restrict__ w,
                                                      const float* __restrict__ scale, const float* __restrict__ shift,
                                                      const float* __restrict__ res, float* __restrict__ out, unsigned M, int Cin, int Cout,
-                                                     int act, unsigned mtiles, unsigned nchunks) {
+                                                     int act, unsigned mtiles, unsigned nchunks, const float* __restrict__ gate, unsigned HW) {
     // workgroups go to the XCDs round-robin: XCD x takes the x-th contiguous eighth of the logical workgroups (launch: a multiple of 8)
     unsigned bid = blockIdx.x;
     if ((gridDim.x & 7) == 0) bid = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
@@ -155,6 +170,8 @@ __global__ __launch_bounds__(256) void k_conv1x1_f32(const float* __restrict__ i
     const unsigned m0 = mt * 32, n0 = chunk * (NT * 32);
     // rows past M and channels past Cout load the last valid row instead; their results are never written
     const float* pa = in + (size_t)min(m0 + li, M - 1) * Cin + 4 * lh;
+    const float* pg = nullptr;
+    if constexpr (MB) pg = gate ? gate + (size_t)(min(m0 + li, M - 1) / HW) * Cin + 4 * lh : nullptr;
     const float* pb[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) pb[t] = w + (size_t)min(n0 + 32 * t + li, (unsigned)Cout - 1) * Cin + 4 * lh;
@@ -172,6 +189,7 @@ __global__ __launch_bounds__(256) void k_conv1x1_f32(const float* __restrict__ i
 #pragma unroll
         for (int j = 0; j < U; ++j) {
             A[j] = *reinterpret_cast<const f32x4*>(pa + k + 8 * j);
+            if constexpr (MB) { if (pg) A[j] = A[j] * *reinterpret_cast<const f32x4*>(pg + k + 8 * j); }
 #pragma unroll
             for (int t = 0; t < NT; ++t) Bq[t][j] = *reinterpret_cast<const f32x4*>(pb[t] + k + 8 * j);
         }
@@ -203,6 +221,7 @@ __global__ __launch_bounds__(256) void k_conv1x1_f32(const float* __restrict__ i
         for (int j = 0; j < U - 1; ++j)
             if (j < ntail) {
                 a[j] = *reinterpret_cast<const f32x4*>(pa + kmain + 8 * j);
+                if constexpr (MB) { if (pg) a[j] = a[j] * *reinterpret_cast<const f32x4*>(pg + kmain + 8 * j); }
 #pragma unroll
                 for (int t = 0; t < NT; ++t) bq[t][j] = *reinterpret_cast<const f32x4*>(pb[t] + kmain + 8 * j);
             }
@@ -232,7 +251,7 @@ __global__ __launch_bounds__(256) void k_conv1x1_f32(const float* __restrict__ i
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const unsigned m = m0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            const float v = act_apply(acc[t][r] * sc + sh, act) + rv[r];
+            const float v = act_apply<MB>(acc[t][r] * sc + sh, act) + rv[r];
             if (m < M) out[(size_t)m * Cout + nn] = v;
         }
     }
@@ -244,11 +263,13 @@ __global__ __launch_bounds__(256) void k_conv1x1_f32(const float* __restrict__ i
 // feeds four instructions, instruction e sums k0 + 4 g + e over g.  Four K-steps per operand set, two sets in turn as above; two
 // accumulators take the K-steps in turn (the instruction's dependent latency is longer than its issue interval) and are added at
 // the end: an order the shape alone fixes.  Where Cin is not a multiple of 16 the last K-step is half one: the lanes of g >= 2 read
-// eight floats earlier (inside their row) and contribute zeros.
+// eight floats earlier (inside their row) and contribute zeros.  MB: as k_conv1x1_f32's.
+template <bool MB>
 __global__ __launch_bounds__(256) void k_conv1x1_f32_small(const float* __restrict__ in, const float* __restrict__ w,
                                                            const float* __restrict__ scale, const float* __restrict__ shift,
                                                            const float* __restrict__ res, float* __restrict__ out, unsigned M, int Cin,
-                                                           int Cout, int act, unsigned mtiles, unsigned ntiles) {
+                                                           int Cout, int act, unsigned mtiles, unsigned ntiles,
+                                                           const float* __restrict__ gate, unsigned HW) {
     unsigned bid = blockIdx.x;
     if ((gridDim.x & 7) == 0) bid = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
     const unsigned lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
@@ -257,6 +278,8 @@ __global__ __launch_bounds__(256) void k_conv1x1_f32_small(const float* __restri
     const unsigned nt = wid % ntiles, mt = wid / ntiles;
     const unsigned m0 = mt * 16, n0 = nt * 16;
     const float* pa = in + (size_t)min(m0 + li, M - 1) * Cin + 4 * g;
+    const float* pg = nullptr;
+    if constexpr (MB) pg = gate ? gate + (size_t)(min(m0 + li, M - 1) / HW) * Cin + 4 * g : nullptr;
     const float* pb = w + (size_t)min(n0 + li, (unsigned)Cout - 1) * Cin + 4 * g;
     constexpr int U = 4, KU = 16 * U;
     const int iters = Cin / KU, kmain = iters * KU;
@@ -264,7 +287,10 @@ __global__ __launch_bounds__(256) void k_conv1x1_f32_small(const float* __restri
     f32x4 a[U], b[U], a1[U], b1[U];
     auto load_set = [&](f32x4 (&A)[U], f32x4 (&Bq)[U], int k) {
 #pragma unroll
-        for (int j = 0; j < U; ++j) { A[j] = *reinterpret_cast<const f32x4*>(pa + k + 16 * j); Bq[j] = *reinterpret_cast<const f32x4*>(pb + k + 16 * j); }
+        for (int j = 0; j < U; ++j) {
+            A[j] = *reinterpret_cast<const f32x4*>(pa + k + 16 * j); Bq[j] = *reinterpret_cast<const f32x4*>(pb + k + 16 * j);
+            if constexpr (MB) { if (pg) A[j] = A[j] * *reinterpret_cast<const f32x4*>(pg + k + 16 * j); }
+        }
     };
     auto mma_set = [&](const f32x4 (&A)[U], const f32x4 (&Bq)[U]) {
 #pragma unroll
@@ -293,6 +319,7 @@ __global__ __launch_bounds__(256) void k_conv1x1_f32_small(const float* __restri
                 const int back = (j == whole && g >= 2) ? 8 : 0;      // the half step's upper lanes stay inside the row
                 a[j] = *reinterpret_cast<const f32x4*>(pa + kmain + 16 * j - back);
                 b[j] = *reinterpret_cast<const f32x4*>(pb + kmain + 16 * j - back);
+                if constexpr (MB) { if (pg) a[j] = a[j] * *reinterpret_cast<const f32x4*>(pg + kmain + 16 * j - back); }
                 if (back) { a[j] = f32x4{0.f, 0.f, 0.f, 0.f}; b[j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
             }
 #pragma unroll
@@ -314,7 +341,7 @@ __global__ __launch_bounds__(256) void k_conv1x1_f32_small(const float* __restri
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const unsigned m = m0 + 4 * g + r;
-        const float v = act_apply((acc[0][r] + acc[1][r]) * sc + sh, act) + rv[r];
+        const float v = act_apply<MB>((acc[0][r] + acc[1][r]) * sc + sh, act) + rv[r];
         if (m < M) out[(size_t)m * Cout + nn] = v;
     }
 }
@@ -326,7 +353,18 @@ int launch_stem3x3s2(const float* in4, const float* w, const float* scale, const
     const long long npix = (long long)B * Ho * Wo;
     if (npix * 8 >= kWalkLimit) return FPC_EINVAL;
     // (a thread loads its 108 weights once: a grid of npix / 256 workgroups gives it eight pixels to spend them on)
-    hipLaunchKernelGGL(k_stem3x3s2, dim3(stream_grid(npix)), dim3(256), 0, s, in4, w, scale, shift, out, (unsigned)npix, Hi, Wi, Ho, Wo);
+    hipLaunchKernelGGL(k_stem3x3s2<false>, dim3(stream_grid(npix)), dim3(256), 0, s, in4, w, scale, shift, out, (unsigned)npix, Hi, Wi, Ho, Wo);
+    return check_launch();
+}
+
+// EfficientNet's stem: pads 0 before and 1 after, swish; even extents only (an odd one would read a second padded row or column)
+int launch_mb_stem3x3s2(const float* in4, const float* w, const float* scale, const float* shift, float* out, int B, int Hi, int Wi,
+                        hipStream_t s) {
+    if (B < 1 || Hi < 2 || Wi < 2 || (Hi & 1) || (Wi & 1)) return FPC_EINVAL;
+    const int Ho = Hi / 2, Wo = Wi / 2;
+    const long long npix = (long long)B * Ho * Wo;
+    if (npix * 8 >= kWalkLimit) return FPC_EINVAL;
+    hipLaunchKernelGGL(k_stem3x3s2<true>, dim3(stream_grid(npix)), dim3(256), 0, s, in4, w, scale, shift, out, (unsigned)npix, Hi, Wi, Ho, Wo);
     return check_launch();
 }
 
@@ -355,18 +393,17 @@ int conv1x1_f32_tiles(long long M, int Cout) {
     return 1;
 }
 
-int launch_conv1x1_f32(const float* in, const float* w, const float* scale, const float* shift, const float* res, float* out, long long M,
-                       int Cin, int Cout, int act, hipStream_t s) {
-    if (M < 1 || M >= (1LL << 31) - 64 || Cin < 8 || Cin > 1024 || Cin % 8 || Cout < 8 || Cout > 2048 || Cout % 8 || act < 0 || act > 1 ||
-        (res && act))
-        return FPC_EINVAL;
+// the launch of a checked 1x1 site on the form its shape names; MB: the EfficientNet instantiations (gate may be NULL)
+template <bool MB>
+static int launch_pw(const float* in, const float* w, const float* scale, const float* shift, const float* res, float* out, long long M,
+                     int Cin, int Cout, int act, const float* gate, long long HW, hipStream_t s) {
     const int nt = conv1x1_f32_tiles(M, Cout);
     if (nt == 0) {
         const long long mt16 = (M + 15) / 16, nt16 = (Cout + 15) / 16;
         long long grid = (mt16 * nt16 + 3) / 4;
         if (grid >= 8) grid = (grid + 7) / 8 * 8;
-        hipLaunchKernelGGL(k_conv1x1_f32_small, dim3((unsigned)grid), dim3(256), 0, s, in, w, scale, shift, res, out, (unsigned)M, Cin, Cout, act,
-                           (unsigned)mt16, (unsigned)nt16);
+        hipLaunchKernelGGL(k_conv1x1_f32_small<MB>, dim3((unsigned)grid), dim3(256), 0, s, in, w, scale, shift, res, out, (unsigned)M, Cin, Cout, act,
+                           (unsigned)mt16, (unsigned)nt16, gate, (unsigned)HW);
         return check_launch();
     }
     const long long mtiles = (M + 31) / 32, nchunks = ((Cout + 31) / 32 + nt - 1) / nt, waves = mtiles * nchunks;
@@ -374,13 +411,34 @@ int launch_conv1x1_f32(const float* in, const float* w, const float* scale, cons
     long long grid = (waves + 3) / 4;
     if (grid >= 8) grid = (grid + 7) / 8 * 8;      // the XCD bands; the workgroups past the last wave leave at once
     const dim3 g((unsigned)grid), b(256);
-#define FPC_PW32(NT, U) hipLaunchKernelGGL((k_conv1x1_f32<NT, U>), g, b, 0, s, in, w, scale, shift, res, out, (unsigned)M, Cin, Cout, act, (unsigned)mtiles, (unsigned)nchunks)
+#define FPC_PW32(NT, U) hipLaunchKernelGGL((k_conv1x1_f32<NT, U, MB>), g, b, 0, s, in, w, scale, shift, res, out, (unsigned)M, Cin, Cout, act, (unsigned)mtiles, (unsigned)nchunks, gate, (unsigned)HW)
     if (nt == 5) FPC_PW32(5, 1);      // (K-steps per iteration: what the registers leave room for)
     else if (nt == 3) FPC_PW32(3, 2);
     else if (nt == 2) FPC_PW32(2, 4);
     else FPC_PW32(1, 4);
 #undef FPC_PW32
     return check_launch();
+}
+
+int launch_conv1x1_f32(const float* in, const float* w, const float* scale, const float* shift, const float* res, float* out, long long M,
+                       int Cin, int Cout, int act, hipStream_t s) {
+    if (M < 1 || M >= (1LL << 31) - 64 || Cin < 8 || Cin > 1024 || Cin % 8 || Cout < 8 || Cout > 2048 || Cout % 8 || act < 0 || act > 1 ||
+        (res && act))
+        return FPC_EINVAL;
+    return launch_pw<false>(in, w, scale, shift, res, out, M, Cin, Cout, act, nullptr, 1, s);
+}
+
+// The EfficientNet 1x1 sites: M = B HW rows, Cin up to kMbMaxCin (a project site's K is 6 x 192 = 1152), act 0 / 1 / 2 (swish), `gate`
+// [B][Cin] or NULL.  The forms and their threshold are conv1x1_f32_tiles' whatever K is: NT and U are set by the registers (NT
+// accumulator tiles of 16 and two operand sets of (NT + 1) U quads; the gate's quad is multiplied into the in operand's as it
+// arrives and keeps no register of its own: the compiler's counts are 124 + 80 / 90 + 48 / 112 + 32 / 80 + 16 vector and accumulator
+// registers for NT = 5 / 3 / 2 / 1, inside the 512 of two waves per SIMD as without the gate), not by the length of the K loop,
+// which K = 1152 only makes longer (36 iterations of 32 at NT = 1, 18 of 64 on the 16 x 16 tiles); a frame's gate row is
+// 4.6 KB at most and comes from L1 / L2.
+int launch_mb_conv1x1(const float* in, const float* gate, const float* w, const float* scale, const float* shift, const float* res,
+                      float* out, int B, long long HW, int Cin, int Cout, int act, hipStream_t s) {
+    if (!mb_conv1x1_ok(B, HW, Cin, Cout) || act < 0 || act > 2 || (res && act)) return FPC_EINVAL;
+    return launch_pw<true>(in, w, scale, shift, res, out, (long long)B * HW, Cin, Cout, act, gate, HW, s);
 }
 
 }  // namespace fpc

@@ -140,9 +140,10 @@ extern "C" int64_t fpc_net_param_numel(const fpc_net_t* n, int i) {
 }
 extern "C" size_t fpc_net_workspace_bytes(const fpc_net_t* n) { return n ? n->total_floats * sizeof(float) : 0; }
 
-// BatchNorm's four parameters from p_bn on, over C channels (eps 1e-5), folded into the scale / shift the epilogues read
-static int fold_bn_of(const fpc_net* n, int p_bn, int C, size_t scale_off, size_t shift_off, hipStream_t s) {
-    return launch_fold_bn(n->pptr[p_bn], n->pptr[p_bn + 1], n->pptr[p_bn + 2], n->pptr[p_bn + 3], 1e-5f, C, n->ws + scale_off, n->ws + shift_off, s);
+// BatchNorm's four parameters from p_bn on, over C channels (eps 1e-5 but for the EfficientNet ops: 1e-3), folded into the scale /
+// shift the epilogues read
+static int fold_bn_of(const fpc_net* n, int p_bn, int C, size_t scale_off, size_t shift_off, hipStream_t s, float eps = 1e-5f) {
+    return launch_fold_bn(n->pptr[p_bn], n->pptr[p_bn + 1], n->pptr[p_bn + 2], n->pptr[p_bn + 3], eps, C, n->ws + scale_off, n->ws + shift_off, s);
 }
 
 extern "C" int fpc_net_load_params(fpc_net_t* n, const float* const* params, int count, void* ws, size_t ws_bytes,
@@ -192,8 +193,8 @@ extern "C" int fpc_net_load_params(fpc_net_t* n, const float* const* params, int
             const int rc = pack_fold_images(n, d, s);
             if (rc) return rc;
         }
-    for (const fpc_net::MbOp& o : n->mops) {      // the MobileNetV2 encoder's ops: the folded BatchNorm (the weights are read in place)
-        const int rc = fold_bn_of(n, o.p_bn, o.Cout, o.scale_off, o.shift_off, s);
+    for (const fpc_net::MbOp& o : n->mops) {      // the MobileNetV2 and EfficientNet encoders' ops: the folded BatchNorm (the weights are read in place)
+        const int rc = fold_bn_of(n, o.p_bn, o.Cout, o.scale_off, o.shift_off, s, o.eps);
         if (rc) return rc;
     }
     n->loaded = true;
@@ -436,15 +437,27 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
                                  ws + n->se_gate_off, B, Y.H, Y.W, Y.C, n->enc.resnet.se, s));
         return launch_se_scale_add_relu(ws + Y.off, ws + n->se_gate_off, res, ws + Y.off, B, Y.H, Y.W, Y.C, s);
     };
-    // an op of the MobileNetV2 encoder, on the one kernel of its kind
+    // an op of the MobileNetV2 or EfficientNet encoder, on the one kernel of its kind
     auto mb_op = [&](const fpc_net::MbOp& o, const Act& in, const Act& out, const float* res) -> int {
         const float *w = n->pptr[o.p_w], *sc = ws + o.scale_off, *sh = ws + o.shift_off;
         switch (o.kind) {
         case fpc_net::kMbStem: return launch_stem3x3s2(ws + in.off, w, sc, sh, ws + out.off, B, in.H, in.W, s);
         case fpc_net::kMbDw: return launch_dwconv3x3(ws + in.off, w, sc, sh, ws + out.off, B, in.H, in.W, in.C, o.stride, o.act, s);
         case fpc_net::kMbPw: return launch_conv1x1_f32(ws + in.off, w, sc, sh, res, ws + out.off, (long long)B * in.H * in.W, o.Cin, o.Cout, o.act, s);
+        case fpc_net::kMbSameStem: return launch_mb_stem3x3s2(ws + in.off, w, sc, sh, ws + out.off, B, in.H, in.W, s);
+        case fpc_net::kMbSameDw: return launch_mb_dwconv(ws + in.off, w, sc, sh, ws + out.off, B, in.H, in.W, in.C, o.k, o.stride, o.act, s);
+        case fpc_net::kMbGatedPw:      // (the gate its block's gate step wrote just before)
+            if (o.gate >= 0 && !n->mb_gate_off) return FPC_EINVAL;
+            return launch_mb_conv1x1(ws + in.off, o.gate >= 0 ? ws + n->mb_gate_off : nullptr, w, sc, sh, res, ws + out.off, B,
+                                     (long long)in.H * in.W, o.Cin, o.Cout, o.act, s);
         }
         return FPC_EINVAL;
+    };
+    // the gate of an MBConv block from its depthwise output.  Refused on a plan built without the gate's scratch, as se_gate is
+    auto mb_gate = [&](const fpc_net::MbGate& g, const Act& x) -> int {
+        if (!n->mb_part_off || g.C != x.C) return FPC_EINVAL;
+        return launch_mb_gate(ws + x.off, n->pptr[g.p], n->pptr[g.p + 1], n->pptr[g.p + 2], n->pptr[g.p + 3], ws + n->mb_gate_off,
+                              ws + n->mb_part_off, B, x.H, x.W, x.C, g.Cs, s);
     };
     for (const Step& st : n->tape) {
         const float* res = st.res.C ? ws + st.res.off : nullptr;
@@ -452,6 +465,7 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
         case kStepConv: FPC_TRY(enc_conv(st.op, st.in, st.out, st.relu, res)); break;
         case kStepSeGate: FPC_TRY(se_gate(st.op, st.out, res)); break;
         case kStepMb: FPC_TRY(mb_op(n->mops[st.op], st.in, st.out, res)); break;
+        case kStepMbGate: FPC_TRY(mb_gate(n->mgates[st.op], st.in)); break;
         }
     }
     const Act* feat = n->a_feat;
@@ -849,7 +863,7 @@ extern "C" int fpc_net_force_direct_h3(fpc_net_t* n, int on) {
 // when the plan changed, 0 when it was already so, or a negative code.  Drops the recorded graph.
 extern "C" int fpc_net_force_stem_pool(fpc_net_t* n, int on) {
     if (!n || on < 0 || on > 1 || (on && !n->h3_packed)) return FPC_EINVAL;
-    if (n->c_stem < 0) return FPC_EINVAL;      // the MobileNetV2 encoder: no 7x7 stem and no max-pool, whatever `on` is
+    if (n->c_stem < 0) return FPC_EINVAL;      // the MobileNetV2 and EfficientNet encoders: no 7x7 stem and no max-pool, whatever `on` is
     if (on && n->enc.resnet.ceil_pool()) return FPC_EINVAL;      // the SE-ResNet stem pool has no padding: the fused launch computes another pool
     if (on && ((n->a_stem.H & 1) || (n->a_stem.W & 63) || (long long)n->H * n->W * 16 >= (1LL << 31))) return FPC_EINVAL;
     ConvPlan& p = n->cplan[n->c_stem];
@@ -909,8 +923,9 @@ extern "C" int fpc_net_flops(const fpc_net_t* n, double* out3) {
         direct += f;
         if (n->cplan[i].wino) { executed += f / 2.25; wino += f; } else executed += f;
     }
-    for (const fpc_net::MbOp& o : n->mops) {      // the MobileNetV2 encoder's ops: 27 (stem), 9 (depthwise) or Cin products per output
-        const double f = 2.0 * n->B * (double)o.howo * o.Cout * (o.kind == fpc_net::kMbStem ? 27 : o.kind == fpc_net::kMbDw ? 9 : o.Cin);
+    for (const fpc_net::MbOp& o : n->mops) {      // the MobileNetV2 and EfficientNet ops: 27 (stem), k k (depthwise) or Cin products per output
+        const bool stem = o.kind == fpc_net::kMbStem || o.kind == fpc_net::kMbSameStem, dw = o.kind == fpc_net::kMbDw || o.kind == fpc_net::kMbSameDw;
+        const double f = 2.0 * n->B * (double)o.howo * o.Cout * (stem ? 27 : dw ? o.k * o.k : o.Cin);
         direct += f; executed += f;
     }
     for (int d = 0; d < 4; ++d)      // the 1x1 heads run inside k_merge_head

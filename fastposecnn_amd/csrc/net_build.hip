@@ -1,5 +1,5 @@
 // net_build.hip — how a plan of the backbone engine (net_plan.hpp: fpc_net) is built, host arithmetic only: the encoders
-// fpc_net_create knows by name, the four creation entry points, the two encoder families' builders and net_build, which puts a
+// fpc_net_create knows by name, the four creation entry points, the three encoder families' builders and net_build, which puts a
 // family's encoder in front of the four FPN decoders and heads and plans every convolution site.  The graph is the one
 // segmentation_models_pytorch builds for FastPoseCNN (fastposecnn_amd/lib/backbone.py).  Nothing here launches a kernel.
 #include <stdio.h>
@@ -14,12 +14,12 @@ static const char* kHeadNames[4] = {"segmentation_head", "rotation_head", "trans
 // persistent region, in state-dict order; `buffers`, called once the persistent region is complete, allocates the stem and stage
 // activations and any scratch of its own and writes the tape and a_feat.  What the first leaves for the second, and for net_build:
 struct ResBlock { int conv[3], ds, p_se, stride, ch[kBufCount]; };      // a block kind's block: its sites as created, its stride, channels by Buf
-struct MbBlock { int expand, dw, proj, stage; };      // ops of fpc_net::mops (-1: the block has none); stage -1: in front of c2's
+struct MbBlock { int expand, dw, proj, stage, gate = -1; };      // ops of fpc_net::mops (-1: the block has none); stage -1: in front of c2's; gate: of fpc_net::mgates, between dw and proj (-1: none)
 struct EncoderBuild {
     int featc[4];                     // channels of c2 .. c5
     std::vector<int> h3_sites;        // the encoder sites that are candidates for the three-product direct form (PackedConv::h3_ok)
     std::vector<ResBlock> res[4];     // the ResNet family's blocks by stage
-    std::vector<MbBlock> mb;          // the MobileNetV2 encoder's blocks
+    std::vector<MbBlock> mb;          // the MobileNetV2 or EfficientNet encoder's blocks
 };
 
 // ---- the ResNet family: the 7x7 / stride-2 stem (3 -> 64, BatchNorm, ReLU) and its 3x3 / stride-2 max-pool, then for L = 0 .. 3
@@ -151,10 +151,11 @@ static void mbv2_params(fpc_net* n, EncoderBuild& eb) {
         if (b.stage >= 0) eb.featc[b.stage] = n->mops[b.proj].Cout;
 }
 
-// Its buffers and tape.  Per stage: the largest expanded tensor, the largest depthwise output and two outputs the blocks take in turn
+// Its buffers and tape, and the EfficientNet encoders' (whose depthwise output sizes Hi / stride are conv_out(Hi, 3, stride, 1) on the even
+// maps every plan has).  Per stage: the largest expanded tensor, the largest depthwise output and two outputs the blocks take in turn
 // (a block's input is its residual, so it never writes over it); a stage's last output stays: a_feat.  No pooled tensor: a_pool
-// stays empty.
-static void mbv2_buffers(fpc_net* n, const EncoderBuild& eb) {
+// stays empty.  A block with a gate has the gate's step between its depthwise and its project op; the gates share one buffer.
+static void mb_buffers(fpc_net* n, const EncoderBuild& eb) {
     const size_t B = (size_t)n->B;
     n->a_stem = n->alloc_act(n->H / 2, n->W / 2, 32);
     n->mops[0].howo = (long long)n->a_stem.H * n->a_stem.W;
@@ -195,6 +196,7 @@ static void mbv2_buffers(fpc_net* n, const EncoderBuild& eb) {
                 n->tape.push_back(mb_step(b.dw, x, d));
                 x = d;
             }
+            if (b.gate >= 0) n->tape.push_back(mb_gate_step(b.gate, x));
             const Act y = view(Y[turn], x.H, x.W, b.proj);
             turn = count > 1 ? turn ^ 1 : 0;
             const bool res = b.dw >= 0 && n->mops[b.dw].stride == 1 && in.C == y.C;
@@ -203,12 +205,54 @@ static void mbv2_buffers(fpc_net* n, const EncoderBuild& eb) {
         }
         if (stage >= 0) n->a_feat[stage] = cur;
     }
+    size_t gate = 0, part = 0;      // one block's gate at a time: [B][C] and the slab partials of the block with the most
+    for (const Step& st : n->tape)
+        if (st.kind == kStepMbGate) {
+            gate = std::max(gate, (size_t)st.in.C);
+            part = std::max(part, (size_t)mb_pool_slabs(st.in.H, st.in.W, st.in.C) * st.in.C);
+        }
+    if (gate) { n->mb_gate_off = n->alloc(B * gate); n->mb_part_off = n->alloc(B * part); }
+}
+
+// ---- the EfficientNet encoders: efficientnet_pytorch's EfficientNet as smp's EfficientNetEncoder walks it, a table of block
+// arguments per variant (B0's is the one here: a later variant is its table, its layers and its pads).  _conv_stem is the 3x3 / stride-2 stem (3 -> 32, BatchNorm, swish); _blocks.N are MBConv blocks by the block arguments
+// (repeat, k, stride, expand, in, out), only a group's first block with its stride and input width: an expand 1x1 with BatchNorm and
+// swish (absent where expand = 1), a depthwise k x k with the block's stride, BatchNorm and swish, the gate (hidden width
+// max(1, in / 4): the block's INPUT), a project 1x1 with BatchNorm only whose input is the depthwise output times the gate, and the
+// block's input added where the stride is 1 and in = out.  Every convolution has the static "same" pads of the variant's declared
+// image size (B0: 224, even at every site, so a stride-2 site pads k - 2 cells: (k - 3) / 2 before, the rest after); BatchNorm's eps
+// is 1e-3.  enc.layers blocks per stage give c2 .. c5 (B0: {3, 2, 4, 7}, 24 / 40 / 112 / 320 channels; the stem alone is level 1).
+// _conv_head and the top-level _bn1 stay in the module and are not run: they are not parameters of the plan.  Parameters in
+// state-dict order, read in place.
+struct EffNetArgs { int repeat, k, stride, expand, in, out; };
+static const EffNetArgs kEffNetB0[7] = {{1, 3, 1, 1, 32, 16}, {2, 3, 2, 6, 16, 24}, {2, 5, 2, 6, 24, 40}, {3, 3, 2, 6, 40, 80},
+                                        {3, 5, 1, 6, 80, 112}, {4, 5, 2, 6, 112, 192}, {1, 3, 1, 6, 192, 320}};
+
+static void effnet_params(fpc_net* n, EncoderBuild& eb) {
+    constexpr float eps = 1e-3f;
+    constexpr int swish = 2;
+    const std::string e("encoder.");
+    n->add_mop(fpc_net::kMbSameStem, e + "_conv_stem.weight", 32 * 27, e + "_bn0", 3, 32, 2, swish, 3, eps);
+    int idx = 0, stage = 0, left = n->enc.layers[0];
+    for (const EffNetArgs& a : kEffNetB0)
+        for (int i = 0; i < a.repeat; ++i, ++idx) {
+            const int inp = i == 0 ? a.in : a.out, stride = i == 0 ? a.stride : 1, hid = inp * a.expand, Cs = std::max(1, inp / 4);
+            const std::string p = e + "_blocks." + std::to_string(idx) + ".";
+            MbBlock b{-1, -1, -1, stage};
+            if (a.expand != 1) b.expand = n->add_mop(fpc_net::kMbGatedPw, p + "_expand_conv.weight", (int64_t)hid * inp, p + "_bn0", inp, hid, 1, swish, 1, eps);
+            b.dw = n->add_mop(fpc_net::kMbSameDw, p + "_depthwise_conv.weight", (int64_t)hid * a.k * a.k, p + "_bn1", hid, hid, stride, swish, a.k, eps);
+            b.gate = n->add_mgate(p, hid, Cs);
+            b.proj = n->add_mop(fpc_net::kMbGatedPw, p + "_project_conv.weight", (int64_t)a.out * hid, p + "_bn2", hid, a.out, 1, 0, 1, eps, b.gate);
+            eb.mb.push_back(b);
+            eb.featc[stage] = a.out;
+            if (--left == 0 && stage < 3) left = n->enc.layers[++stage];
+        }
 }
 
 static const struct {
     void (*params)(fpc_net* n, EncoderBuild& eb);
     void (*buffers)(fpc_net* n, const EncoderBuild& eb);
-} kFamilies[kFamilyCount] = {{resnet_params, resnet_buffers}, {mbv2_params, mbv2_buffers}};      // by EncoderFamily
+} kFamilies[kFamilyCount] = {{resnet_params, resnet_buffers}, {mbv2_params, mb_buffers}, {effnet_params, mb_buffers}};      // by EncoderFamily
 
 // The plan of `n` (its encoder descriptor set) for (classes, B, H, W); owns `n` (deleted on failure).  The persistent region (packed
 // weights, folded BatchNorm, weight images) comes first, then the activations and scratch.
@@ -385,6 +429,8 @@ static const struct { const char* name; EncoderDesc desc; } kEncoders[] = {
     {"se_resnet152", {kFamilyResNet, {4, 1, 64, 16}, {3, 8, 36, 3}}},
     // the MobileNetV2 encoder (above); layers: the feature modules in each stage of smp's last four
     {"mobilenet_v2", {kFamilyMobileNetV2, {}, {2, 3, 7, 5}}},
+    // EfficientNet-B0 (above); layers: the MBConv blocks in each stage of smp's last four (its stage ends 3, 5, 9, 16)
+    {"efficientnet-b0", {kFamilyEfficientNet, {}, {3, 2, 4, 7}}},
 };
 
 extern "C" int fpc_net_create(const char* encoder, int classes, int B, int H, int W, fpc_net_t** out) {

@@ -344,6 +344,34 @@ int launch_dwconv3x3(const float* in, const float* w, const float* scale, const 
 int launch_conv1x1_f32(const float* in, const float* w, const float* scale, const float* shift, const float* res, float* out, long long M,
                        int Cin, int Cout, int act, hipStream_t s);
 int conv1x1_f32_tiles(long long M, int Cout);      // 0: 16 x 16 tiles (few rows), else channel tiles of 32 per wave: a function of the shape alone
+// efficientnet.hip (and the MB instantiations of mobilenet.hip's stem and 1x1 kernels): the EfficientNet encoder's kernels, on the
+// same conventions; act 2 = swish.  The pads are efficientnet_pytorch's static "same" ones: stride 1 (k - 1) / 2 on every side;
+// stride 2 (even extents only) 0 before and 1 after for k = 3, 1 and 2 for k = 5.
+// depthwise: w [C][1][k][k], k 3 or 5, C % 4 == 0, out [B][Hi / stride][Wi / stride][C].  gate: per-channel means of x [B][H][W][C] in
+// mb_pool_slabs(H, W, C) slabs (partial [B][slabs][C]), then gate [B][C] = sigmoid(w2 swish(w1 mean + b1) + b2) with w1 [Cs][C],
+// w2 [C][Cs].  1x1: launch_conv1x1_f32's product over B frames of HW rows with in[m][k] gate[m / HW][k] as the in operand where gate
+// is not NULL, Cin up to kMbMaxCin
+constexpr int kMbMaxC = 2048, kMbMaxCs = 64;      // k_mb_excite keeps one frame's means and hidden activations in LDS
+constexpr int kMbMaxCin = 2048;
+constexpr int kMbRowPixels = 32;                  // pixels one thread row of k_mb_pool adds per slab
+inline int mb_pool_lanes(int C) { return C / 4 < 256 ? C / 4 : 256; }
+inline int mb_pool_slabs(int H, int W, int C) {   // a function of the shape only; 0 for a refused one
+    if (H < 1 || W < 1 || C < 4 || C % 4 || C > kMbMaxC || (long long)H * W >= (1LL << 31)) return 0;
+    const long long per = (long long)(256 / mb_pool_lanes(C)) * kMbRowPixels;
+    return (int)(((long long)H * W + per - 1) / per);
+}
+inline bool mb_conv1x1_ok(int B, long long HW, int Cin, int Cout) {
+    return B >= 1 && HW >= 1 && HW < (1LL << 31) && (long long)B * HW < (1LL << 31) - 64 && Cin >= 8 && Cin <= kMbMaxCin && Cin % 8 == 0 &&
+           Cout >= 8 && Cout <= 2048 && Cout % 8 == 0;
+}
+int launch_mb_stem3x3s2(const float* in4, const float* w, const float* scale, const float* shift, float* out, int B, int Hi, int Wi,
+                        hipStream_t s);
+int launch_mb_dwconv(const float* in, const float* w, const float* scale, const float* shift, float* out, int B, int Hi, int Wi, int C,
+                     int k, int stride, int act, hipStream_t s);
+int launch_mb_gate(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, float* gate, float* partial, int B,
+                   int H, int W, int C, int Cs, hipStream_t s);
+int launch_mb_conv1x1(const float* in, const float* gate, const float* w, const float* scale, const float* shift, const float* res,
+                      float* out, int B, long long HW, int Cin, int Cout, int act, hipStream_t s);
 int launch_gn_finalize(const GnFinArgs& a, int groups, hipStream_t s);
 int launch_gn_relu_up2(const GnUpArgs& a, int groups, hipStream_t s);
 int launch_merge_head(const MergeHeadArgs& a, int groups, hipStream_t s);

@@ -40,6 +40,7 @@ constexpr BlockKind kSEBottleneck = {3, {{1, true, false, kBufIn, kBufT1, true, 
 enum EncoderFamily {
     kFamilyResNet,           // the 7x7 stem, a max-pool, then stage by stage blocks of one of the kinds above
     kFamilyMobileNetV2,      // torchvision's MobileNetV2 features: none of the block kinds (net_build.hip: "the MobileNetV2 encoder")
+    kFamilyEfficientNet,     // efficientnet_pytorch's MBConv blocks by a table of block arguments (net_build.hip: "the EfficientNet encoders")
     kFamilyCount
 };
 // What the ResNet family asks beside the blocks per stage; no other family has one, so no other family is asked these questions.
@@ -55,7 +56,8 @@ struct ResNetDesc {
 struct EncoderDesc {
     EncoderFamily family = kFamilyResNet;
     ResNetDesc resnet;            // read where family == kFamilyResNet only
-    int layers[4] = {};           // ResNet: blocks per stage; MobileNetV2: the feature modules per stage of smp's last four, behind features.1
+    int layers[4] = {};           // ResNet: blocks per stage; MobileNetV2: the feature modules per stage of smp's last four, behind features.1;
+                                  // EfficientNet: the MBConv blocks per stage of smp's last four
     bool basic() const { return family == kFamilyResNet && resnet.expansion == 1; }         // c2 has 64 channels: s2.0 may fold the FPN p2 level in, and the direct sites have three-product images
     bool pointwise() const { return family == kFamilyResNet && resnet.expansion == 4; }     // the autotuner offers k_conv1x1 to the 1x1 sites
 };
@@ -65,7 +67,8 @@ struct EncoderDesc {
 enum StepKind {
     kStepConv,       // op: a conv site (fpc_net::convs) from `in` to `out`, with BatchNorm, the residual `res` (C > 0) and ReLU in its epilogue
     kStepSeGate,     // op: the first of se_module's four parameters; an SE block's gate on `out` in place, with the residual `res`
-    kStepMb          // op: an op of the MobileNetV2 encoder (fpc_net::mops, whose MbOp::kind names the kernel) from `in` to `out`; a 1x1 adds `res` (C > 0)
+    kStepMb,         // op: an op of the MobileNetV2 or EfficientNet encoder (fpc_net::mops, whose MbOp::kind names the kernel) from `in` to `out`; a 1x1 adds `res` (C > 0)
+    kStepMbGate      // op: an MBConv block's gate (fpc_net::mgates) from the depthwise output `in`; writes the plan's gate buffer, which the block's project op reads
 };
 struct Step { StepKind kind; int op; Act in, out; bool relu; Act res; };
 inline Step conv_step(int conv, const Act& in, const Act& out, bool relu, const Act& res = Act()) {
@@ -76,6 +79,9 @@ inline Step se_gate_step(int p_se, const Act& y, const Act& res) {      // Y = r
 }
 inline Step mb_step(int mop, const Act& in, const Act& out, const Act& res = Act()) {      // (the activation is the op's own: MbOp::act)
     Step s; s.kind = kStepMb; s.op = mop; s.in = in; s.out = out; s.relu = false; s.res = res; return s;
+}
+inline Step mb_gate_step(int gate, const Act& x) {      // (`out` is the operand too: the gate itself lies in fpc_net::mb_gate_off)
+    Step s; s.kind = kStepMbGate; s.op = gate; s.in = s.out = x; s.relu = false; return s;
 }
 
 struct fpc_net {
@@ -98,14 +104,30 @@ struct fpc_net {
     std::vector<Step> tape;
     // The MobileNetV2 encoder's ops: the stem, a depthwise 3x3 or a 1x1, each with BatchNorm folded into scale / shift and ReLU6 where
     // act = 1.  One form each (mobilenet.hip): not PackedConv sites, not tuned, not surveyed; the weights are read in place.
-    enum MbKind { kMbStem, kMbDw, kMbPw };
-    struct MbOp { MbKind kind; int p_w, p_bn, Cin, Cout, stride, act; size_t scale_off, shift_off; long long howo; };
+    // The EfficientNet encoder's ops are further kinds of the same list (efficientnet.hip): the stem, a depthwise k x k and a 1x1 with the
+    // static "same" pads, swish where act = 2, BatchNorm's eps 1e-3, and — the project 1x1 — `gate`, the MBConv gate (mgates) whose
+    // values multiply the op's input; -1: none.  The same rules: one form each, not tuned, not surveyed.
+    enum MbKind { kMbStem, kMbDw, kMbPw, kMbSameStem, kMbSameDw, kMbGatedPw };
+    struct MbOp { MbKind kind; int p_w, p_bn, Cin, Cout, stride, act; size_t scale_off, shift_off; long long howo; int k; float eps; int gate; };
     std::vector<MbOp> mops;
-    int add_mop(MbKind kind, const std::string& wname, int64_t wnumel, const std::string& bn, int Cin, int Cout, int stride, int act) {
-        MbOp o{kind, add_param(wname, wnumel), add_bn(bn, Cout), Cin, Cout, stride, act, 0, 0, 0};
+    int add_mop(MbKind kind, const std::string& wname, int64_t wnumel, const std::string& bn, int Cin, int Cout, int stride, int act,
+                int k = 3, float eps = 1e-5f, int gate = -1) {
+        MbOp o{kind, add_param(wname, wnumel), add_bn(bn, Cout), Cin, Cout, stride, act, 0, 0, 0, k, eps, gate};
         o.scale_off = alloc(Cout); o.shift_off = alloc(Cout);
         mops.push_back(o);
         return (int)mops.size() - 1;
+    }
+    // An MBConv block's gate: _se_reduce (weight [Cs][C], bias) and _se_expand (weight [C][Cs], bias), four parameters from p on, read
+    // in place; sigmoid(expand(swish(reduce(mean_hw(x))))) of the depthwise output x [B][H][W][C] -> mb_gate_off [B][C]
+    struct MbGate { int p, C, Cs; };
+    std::vector<MbGate> mgates;
+    int add_mgate(const std::string& prefix, int C, int Cs) {
+        const int p = add_param(prefix + "_se_reduce.weight", (int64_t)Cs * C);
+        add_param(prefix + "_se_reduce.bias", Cs);
+        add_param(prefix + "_se_expand.weight", (int64_t)C * Cs);
+        add_param(prefix + "_se_expand.bias", C);
+        mgates.push_back(MbGate{p, C, Cs});
+        return (int)mgates.size() - 1;
     }
     struct Dec {
         int lat[4];               // p5, p4, p3, p2 (1x1, bias)
@@ -129,6 +151,7 @@ struct fpc_net {
     int merge_split = -1;         // -1: two passes unless FPC_MERGE_SPLIT=0, 0: k_merge_head (one pass), 1: two passes
     size_t splitk_off = 0, splitk_floats = 0;
     size_t se_gate_off = 0, se_part_off = 0;      // SE plans: gate [B][2048] and the slab partials of the stage that needs most (k_se_pool / k_se_excite)
+    size_t mb_gate_off = 0, mb_part_off = 0;      // EfficientNet plans: gate [B][widest C] of one block at a time and the slab partials of the block that needs most (k_mb_pool / k_mb_excite)
     int use_graph = 0;            // replay the frame-invariant launches as a HIP graph (fpc_net_set_graph)
     long long wino_blocks = 0;    // workgroups of the form-9 launches of the last forward that launched its kernels (fpc_net_wino_blocks)
     int wino_pack = 1;            // form-9 launches cut their patches out of canvas rows of several frames where that saves patches (fpc_net_set_wino_pack)

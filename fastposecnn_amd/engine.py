@@ -29,12 +29,12 @@ class NetEngine:
         h = ctypes.c_void_p()
         from fastposecnn_amd.lib import backbone
         name = model.encoder.name
-        mobilenet = backbone.encoder_family(name) == "mobilenet_v2"      # a plan fpc_net_create builds by name, no descriptor
-        block, layers = (0, [0] * 4) if mobilenet else backbone.encoder_layout(name)
-        groups, width = (1, 64) if mobilenet else backbone.encoder_groups(name)
-        reduction = 0 if mobilenet else backbone.encoder_reduction(name)
+        by_name = backbone.encoder_family(name) in ("mobilenet_v2", "efficientnet")      # a plan fpc_net_create builds by name, no descriptor
+        block, layers = (0, [0] * 4) if by_name else backbone.encoder_layout(name)
+        groups, width = (1, 64) if by_name else backbone.encoder_groups(name)
+        reduction = 0 if by_name else backbone.encoder_reduction(name)
         arr, tail = (ctypes.c_int * 4)(*layers), (self.classes, B, H, W, ctypes.byref(h))
-        if mobilenet:
+        if by_name:
             nat.check(L.fpc_net_create(name.encode(), *tail), "fpc_net_create")
         elif reduction:     # SE-ResNet: the Bottleneck with the stride on conv1 and the squeeze-and-excitation gate
             nat.check(L.fpc_net_create_encoder_se(arr, reduction, *tail), "fpc_net_create_encoder_se")

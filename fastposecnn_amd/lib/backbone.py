@@ -21,6 +21,10 @@ se_module.fc1 / fc2, the same six feature levels.
 The MobileNetV2 encoder (mobilenet_v2) is smp's MobileNetV2Encoder over torchvision.models.mobilenet_v2, restated the same way
 (neither package is here: parity unpinned): encoder.features.0 .. 18 without the classifier, InvertedResidual blocks with a `conv`
 Sequential, ReLU6, the six feature levels behind the input, features.1 / 3 / 6 / 13 / 18.
+The EfficientNet-B0 encoder (efficientnet-b0) is smp's EfficientNetEncoder over efficientnet_pytorch.EfficientNet, restated the same
+way (neither package is here: parity unpinned): encoder._conv_stem / _bn0, 16 MBConv blocks encoder._blocks.N with the static "same"
+pads of the declared 224 image, swish and the squeeze-and-excitation gate, _conv_head / _bn1 kept and not run, the feature levels
+behind the stem and blocks 2 / 4 / 8 / 15.
 state_dict names follow smp: encoder.conv1.weight, encoder.layer1.0.conv1.weight, ...,
 <dec>.p5.weight, <dec>.p4.skip_conv.weight, <dec>.seg_blocks.0.block.0.block.0.weight (conv),
 ...block.1.weight (GroupNorm), <head>.0.weight.
@@ -218,10 +222,13 @@ _ENCODERS = {"resnet18": (BasicBlock, [2, 2, 2, 2], 1, 64, 0), "resnet34": (Basi
 
 
 def encoder_family(name):
-    """The one look-up the engine switches on: "mobilenet_v2" for the encoder fpc_net_create builds by that name, "resnet" for every
-    encoder that encoder_layout / encoder_groups / encoder_reduction describe; KeyError for a name this package does not build."""
+    """The one look-up the engine switches on: "mobilenet_v2" and "efficientnet" for the encoders fpc_net_create builds by their
+    names, "resnet" for every encoder that encoder_layout / encoder_groups / encoder_reduction describe; KeyError for a name this
+    package does not build."""
     if name == MobileNetV2Encoder.NAME:
         return "mobilenet_v2"
+    if name in EfficientNetEncoder.VARIANTS:
+        return "efficientnet"
     _ENCODERS[name]
     return "resnet"
 
@@ -243,6 +250,11 @@ def encoder_reduction(name):
     return _ENCODERS[name][4]
 
 
+def _available():
+    """The encoder names this package builds, for the KeyError of an unknown one."""
+    return sorted(_ENCODERS) + [MobileNetV2Encoder.NAME] + sorted(EfficientNetEncoder.VARIANTS)
+
+
 def _make_stage(block, inplanes, planes, blocks, stride, **kw):
     """One stage: `blocks` blocks of `planes`, the first with the stride and, where the shape changes, a 1x1 downsample."""
     downsample = None
@@ -261,7 +273,7 @@ class _Encoder(nn.Module):
     def __init__(self, name, in_channels, depth):
         super().__init__()
         if name not in _ENCODERS or bool(_ENCODERS[name][4]) != self._gated:
-            raise KeyError(f"encoder {name!r} not available (have {sorted(_ENCODERS) + ['mobilenet_v2']})")
+            raise KeyError(f"encoder {name!r} not available (have {_available()})")
         block, layers, groups, width, reduction = _ENCODERS[name]
         self.name = name
         self._depth = depth
@@ -393,7 +405,7 @@ class MobileNetV2Encoder(nn.Module):
     def __init__(self, name="mobilenet_v2", in_channels=3, depth=5):
         super().__init__()
         if name != self.NAME:
-            raise KeyError(f"encoder {name!r} not available (have {sorted(_ENCODERS) + [self.NAME]})")
+            raise KeyError(f"encoder {name!r} not available (have {_available()})")
         self.name = name
         self._depth = depth
         self.out_channels = (in_channels, 16, 24, 32, 96, 1280)
@@ -422,6 +434,130 @@ class MobileNetV2Encoder(nn.Module):
         return feats
 
 
+class Swish(nn.Module):
+    """efficientnet_pytorch's swish, x * sigmoid(x), as a child module without parameters: a test may swap it."""
+
+    def forward(self, x):
+        return x * torch.sigmoid(x)
+
+
+class Conv2dStaticSamePadding(Conv2d):
+    """efficientnet_pytorch's Conv2dStaticSamePadding: a pad-0 convolution behind `static_padding`, the TensorFlow "same" pads worked
+    out once from the DECLARED image size at this site (not from the tensor it gets): per axis max((ceil(i / s) - 1) s + k - i, 0)
+    cells, the smaller half before.  nn.ZeroPad2d where there is any, nn.Identity otherwise; no parameters, so the state_dict is
+    nn.Conv2d's.  Behind the pad the convolution is Conv2d above: in the training step a dense one reaches the native front end
+    where that accepts its shape, a depthwise one (k = 5 included) runs on torch's grouped kernels."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, image_size=None, **kw):
+        super().__init__(in_channels, out_channels, kernel_size, stride, 0, **kw)
+        ih, iw = (image_size, image_size) if isinstance(image_size, int) else image_size
+        k, s = self.kernel_size[0], self.stride[0]
+        pad_h = max((-(-ih // s) - 1) * s + k - ih, 0)
+        pad_w = max((-(-iw // s) - 1) * s + k - iw, 0)
+        if pad_h or pad_w:
+            self.static_padding = nn.ZeroPad2d((pad_w // 2, pad_w - pad_w // 2, pad_h // 2, pad_h - pad_h // 2))
+        else:
+            self.static_padding = nn.Identity()
+
+    def forward(self, x):
+        return super().forward(self.static_padding(x))
+
+
+class MBConvBlock(nn.Module):
+    """efficientnet_pytorch's MBConvBlock with the gate (se_ratio 0.25 of the block's INPUT width) and the identity skip:
+        x1 = swish(bn0(expand(x)))            (absent where expand_ratio = 1: x1 = x)
+        x2 = swish(bn1(depthwise(x1)))        (k x k with the block's stride)
+        g  = sigmoid(se_expand(swish(se_reduce(mean_hw(x2)))))
+        y  = bn2(project(x2 * g));  y = drop_connect(y) + x where the stride is 1 and inp = oup
+    drop_connect runs in training only, at `drop_connect_rate` (the encoder sets it per call).  Every BatchNorm has eps 1e-3 and
+    momentum 0.01.  The native engine runs all of it at inference (csrc/efficientnet.hip); in the training step the dense 1x1
+    sites and the BatchNorms reach the native front ends through Conv2d / BatchNorm2d above, the rest is torch."""
+
+    def __init__(self, inp, oup, kernel_size, stride, expand_ratio, image_size, se_ratio=0.25, bn_mom=0.01, bn_eps=1e-3):
+        super().__init__()
+        hidden = inp * expand_ratio
+        self.stride = stride
+        self.use_skip = stride == 1 and inp == oup
+        self.drop_connect_rate = 0.0
+        if expand_ratio != 1:
+            self._expand_conv = Conv2dStaticSamePadding(inp, hidden, 1, image_size=image_size, bias=False)
+            self._bn0 = BatchNorm2d(hidden, momentum=bn_mom, eps=bn_eps)
+        self._depthwise_conv = Conv2dStaticSamePadding(hidden, hidden, kernel_size, stride, image_size=image_size, groups=hidden, bias=False)
+        self._bn1 = BatchNorm2d(hidden, momentum=bn_mom, eps=bn_eps)
+        squeezed = max(1, int(inp * se_ratio))
+        self._se_reduce = Conv2dStaticSamePadding(hidden, squeezed, 1, image_size=(1, 1))
+        self._se_expand = Conv2dStaticSamePadding(squeezed, hidden, 1, image_size=(1, 1))
+        self._project_conv = Conv2dStaticSamePadding(hidden, oup, 1, image_size=-(-image_size // stride), bias=False)
+        self._bn2 = BatchNorm2d(oup, momentum=bn_mom, eps=bn_eps)
+        self._swish = Swish()
+
+    def forward(self, x):
+        inputs = x
+        if hasattr(self, "_expand_conv"):
+            x = self._swish(self._bn0(self._expand_conv(x)))
+        x = self._swish(self._bn1(self._depthwise_conv(x)))
+        g = self._se_expand(self._swish(self._se_reduce(F.adaptive_avg_pool2d(x, 1))))
+        x = self._bn2(self._project_conv(torch.sigmoid(g) * x))
+        if self.use_skip:
+            p = self.drop_connect_rate
+            if self.training and p:
+                keep = torch.floor(1 - p + torch.rand([x.shape[0], 1, 1, 1], dtype=x.dtype, device=x.device))
+                x = x / (1 - p) * keep
+            x = x + inputs
+        return x
+
+
+class EfficientNetEncoder(nn.Module):
+    """smp's EfficientNetEncoder: efficientnet_pytorch's EfficientNet without _fc, returning 6 feature levels: the input, the stem
+    and the outputs of the blocks in front of smp's stage indices.  `_conv_head` and the top-level `_bn1` stay in the module and in
+    the state_dict, as in smp, and forward does not run them.  One row of VARIANTS per encoder: the declared image size, the block
+    arguments (repeat, kernel, stride, expand ratio, input, output — only a group's first block has the stride and the input width),
+    smp's stage indices and the head width.  Only B0 is here: its declared 224 stays even down to 14, so every stride-2 site pads
+    (0, 1) for k = 3 and (1, 2) for k = 5; B1 and up declare sizes that reach odd extents and need their own pads per site in the
+    native kernels."""
+    VARIANTS = {"efficientnet-b0": dict(
+        image_size=224, stem=32, head=1280, stages=(3, 5, 9, 16), out_channels=(32, 24, 40, 112, 320),
+        blocks=((1, 3, 1, 1, 32, 16), (2, 3, 2, 6, 16, 24), (2, 5, 2, 6, 24, 40), (3, 3, 2, 6, 40, 80), (3, 5, 1, 6, 80, 112),
+                (4, 5, 2, 6, 112, 192), (1, 3, 1, 6, 192, 320)))}
+
+    def __init__(self, name="efficientnet-b0", in_channels=3, depth=5):
+        super().__init__()
+        if name not in self.VARIANTS:
+            raise KeyError(f"encoder {name!r} not available (have {_available()})")
+        v = self.VARIANTS[name]
+        self.name = name
+        self._depth = depth
+        self._stage_idxs = v["stages"]
+        self.out_channels = (in_channels,) + v["out_channels"]
+        self.drop_connect_rate = 0.2
+        size = v["image_size"]
+        self._conv_stem = Conv2dStaticSamePadding(in_channels, v["stem"], 3, 2, image_size=size, bias=False)
+        self._bn0 = BatchNorm2d(v["stem"], momentum=0.01, eps=1e-3)
+        size = -(-size // 2)
+        blocks = []
+        for repeat, k, stride, expand, inp, oup in v["blocks"]:
+            for i in range(repeat):
+                blocks.append(MBConvBlock(inp if i == 0 else oup, oup, k, stride if i == 0 else 1, expand, size))
+                if i == 0:
+                    size = -(-size // stride)
+        self._blocks = nn.ModuleList(blocks)
+        self._conv_head = Conv2dStaticSamePadding(v["blocks"][-1][5], v["head"], 1, image_size=size, bias=False)
+        self._bn1 = BatchNorm2d(v["head"], momentum=0.01, eps=1e-3)
+        self._swish = Swish()
+        # (efficientnet_pytorch leaves torch's default initialisation; a checkpoint or a weights file overwrites it)
+
+    def forward(self, x):
+        feats = [x]
+        x = self._swish(self._bn0(self._conv_stem(x)))
+        feats.append(x)
+        for i, block in enumerate(self._blocks):
+            block.drop_connect_rate = self.drop_connect_rate * i / len(self._blocks)
+            x = block(x)
+            if i + 1 in self._stage_idxs:
+                feats.append(x)
+        return feats
+
+
 _WARNED_WEIGHTS = set()
 
 
@@ -433,12 +569,14 @@ def get_encoder(name, in_channels=3, depth=5, weights=None):
     `FPC_ENCODER_WEIGHTS_DIR/<name>.pth` (or `FPC_ENCODER_WEIGHTS=<file>`) holding the torchvision ResNet state
     dict (keys conv1.weight, bn1.*, layer1.0.conv1.weight, ...; fc.* is dropped, as smp does) or, for an SE-ResNet, the
     pretrainedmodels one (layer0.conv1.weight, ..., layerN.i.se_module.fc1.bias; last_linear.* is dropped) or, for mobilenet_v2,
-    torchvision's (features.0.0.weight, ..., features.18.1.running_var; classifier.* is dropped).  When `weights` is
+    torchvision's (features.0.0.weight, ..., features.18.1.running_var; classifier.* is dropped) or, for efficientnet-b0,
+    efficientnet_pytorch's (_conv_stem.weight, ..., _conv_head.weight, _bn1.*; _fc.* is dropped).  When `weights` is
     requested and no file is configured the encoder stays randomly initialised and a warning says so once per
     encoder — a checkpoint loaded afterwards (load_from_ckpt) overwrites the encoder anyway."""
     import logging
     import os
-    cls = MobileNetV2Encoder if name == MobileNetV2Encoder.NAME else SENetEncoder if name in _ENCODERS and _ENCODERS[name][4] else ResNetEncoder
+    cls = MobileNetV2Encoder if name == MobileNetV2Encoder.NAME else EfficientNetEncoder if name in EfficientNetEncoder.VARIANTS \
+        else SENetEncoder if name in _ENCODERS and _ENCODERS[name][4] else ResNetEncoder
     enc = cls(name, in_channels=in_channels, depth=depth)
     enc.requested_weights = weights
     enc.loaded_weights = None
@@ -449,7 +587,7 @@ def get_encoder(name, in_channels=3, depth=5, weights=None):
         if path:
             import torch
             sd = torch.load(path, map_location="cpu")
-            sd = {k: v for k, v in sd.items() if not k.startswith(("fc.", "last_linear.", "classifier."))}
+            sd = {k: v for k, v in sd.items() if not k.startswith(("fc.", "last_linear.", "classifier.", "_fc."))}
             enc.load_state_dict(sd)                  # strict: a wrong file fails loudly
             enc.loaded_weights = path
         elif (name, weights) not in _WARNED_WEIGHTS:

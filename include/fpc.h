@@ -62,6 +62,8 @@ extern "C" {
  * and the MobileNetV2 encoder (fpc_net_create's "mobilenet_v2", fpc_dwconv3x3, fpc_conv1x1_f32, fpc_conv1x1_f32_form, fpc_stem3x3s2):
  * and its depthwise convolution and ReLU6 in the training step (fpc_dwconv3x3_dgrad, fpc_dwconv3x3_wgrad and its _workspace_bytes,
  *   fpc_batchnorm_act_fwd, fpc_batchnorm_act_bwd):
+ * and the EfficientNet-B0 encoder (fpc_net_create's "efficientnet-b0", fpc_mbconv_dw, fpc_mbconv_gate and its _slabs / _scratch_floats,
+ *   fpc_mbconv_pw, fpc_mbconv_pw_form, fpc_mbconv_stem):
  * additions only, every earlier entry point keeps its behaviour. */
 #define FPC_ABI_VERSION 11
 
@@ -911,6 +913,47 @@ int fpc_conv1x1_f32(const float* in, const float* w, const float* scale, const f
 int fpc_conv1x1_f32_form(int64_t M, int Cin, int Cout);
 int fpc_stem3x3s2(const float* in4, const float* w, const float* scale, const float* shift, float* out, int B, int Hi, int Wi, int Cout,
                   fpc_stream_t stream);
+
+/* ---- The EfficientNet-B0 encoder's kernels (csrc/efficientnet.hip and the gated / swish instantiations of csrc/mobilenet.hip's stem
+ * and 1x1 kernels), stand-alone.  fpc_net_create("efficientnet-b0", ...) builds the plan that runs them: efficientnet_pytorch's
+ * EfficientNet as smp's EfficientNetEncoder wraps it (F/lib/pose_regressor.py:608-613 through smp.encoders.get_encoder), replacing
+ * cuDNN's depthwise and 1x1 convolutions and aten's BatchNorm, swish, mean, sigmoid and multiply at inference.  Such a plan's encoder
+ * is the stem and, for each of the 16 MBConv blocks, an expand 1x1 (not block 0), a depthwise, the gate (two launches) and a project
+ * 1x1 that multiplies its input by the gate: 80 launches.  The ops follow the MobileNetV2 ops' rules: one form each, not convolution
+ * sites (fpc_net_conv_count counts the decoders' alone), not autotuned, not surveyed or guarded; fpc_net_force_stem_pool and
+ * fpc_net_force_fold(net, 1) are refused, fpc_net_force_direct_h3 changes 0 sites; the p2 / p3 / p4 laterals (24 / 40 / 112
+ * channels) run on the implicit GEMM's Cin % 4 loader.  _conv_head and the top-level _bn1 are not parameters of the plan.
+ * All: dense channel-last f32, every pointer non-NULL (but res and gate of fpc_mbconv_pw) and 16-byte aligned (FPC_EINVAL
+ * otherwise), scale / shift = the folded BatchNorm (eps 1e-3 in this encoder), act 0 = none, 1 = ReLU6, 2 = swish v / (1 + exp(-v));
+ * fixed summation orders, no atomics: bit-identical run to run.  The pads are efficientnet_pytorch's static "same" pads for the
+ * declared 224 image: stride 1 (k - 1) / 2 on every side; stride 2 pads 0 before and 1 after for k = 3, 1 and 2 for k = 5.
+ * fpc_mbconv_dw (k_mb_dwconv; replaces _depthwise_conv + _bn1 + swish of MBConvBlock.forward): depthwise k x k, k 3 or 5, stride 1
+ *   or 2: in [B][Hi][Wi][C], w torch's [C][1][k][k] read in place, out [B][Hi / stride][Wi / stride][C].  Refused: B < 1, C < 4 or
+ *   C % 4 != 0, any other k, stride or act, an odd Hi or Wi at stride 2.
+ * fpc_mbconv_gate (k_mb_pool + k_mb_excite; replaces adaptive_avg_pool2d, _se_reduce, swish, _se_expand and sigmoid):
+ *   gate[b][c] = 1 / (1 + exp(-(w2 swish(w1 m_b + b1) + b2)[c])) with m_b the mean of x[b] [H][W][C] over its pixels (slab sums added
+ *   in slab order, divided by H W), w1 [Cs][C], b1 [Cs], w2 [C][Cs], b2 [C]: torch's layouts.  C % 4 == 0, 4 .. 2048; Cs 1 .. 64;
+ *   B <= 65535.  fpc_mbconv_gate_slabs: the slabs one frame is cut into, a function of (H, W, C) only, 0 for a refused shape;
+ *   fpc_mbconv_gate_scratch_floats: floats of `scratch` = B * slabs * C.
+ * fpc_mbconv_pw (k_conv1x1_f32's gated instantiations; replaces `x * gate`, _project_conv + _bn2 + the skip add, and _expand_conv +
+ *   _bn0 + swish): out[m][n] = act(scale[n] sum_k (in[m][k] gate[m / HW][k]) w[n][k] + shift[n]) (+ res[m][n]) over B frames of HW
+ *   rows each, the product in gate rounded to f32 before it enters the exact-f32 matrix instruction; gate [B][Cin] may be NULL (no
+ *   multiply).  Cin % 8 == 0, 8 .. 2048; Cout % 8 == 0, 8 .. 2048; res with act != 0 is refused.  fpc_mbconv_pw_form: the form the
+ *   shape runs on, as fpc_conv1x1_f32_form for M = B HW (0, 1, 2, 3 or 5; FPC_EINVAL for a refused shape).
+ * fpc_mbconv_stem (k_stem3x3s2's instantiation; replaces _conv_stem + _bn0 + swish): the dense 3x3 / stride 2 stem with pads 0 before
+ *   and 1 after over fpc_image_nhwc4's image [B][Hi][Wi][4], w [32][3][3][3], swish: out [B][Hi / 2][Wi / 2][32].  Cout must be 32,
+ *   Hi and Wi even. */
+int fpc_mbconv_dw(const float* in, const float* w, const float* scale, const float* shift, float* out, int B, int Hi, int Wi, int C,
+                  int k, int stride, int act, fpc_stream_t stream);
+int fpc_mbconv_gate_slabs(int H, int W, int C);
+size_t fpc_mbconv_gate_scratch_floats(int B, int H, int W, int C);
+int fpc_mbconv_gate(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, float* gate, float* scratch, int B,
+                    int H, int W, int C, int Cs, fpc_stream_t stream);
+int fpc_mbconv_pw(const float* in, const float* gate, const float* w, const float* scale, const float* shift, const float* res, float* out,
+                  int B, int64_t HW, int Cin, int Cout, int act, fpc_stream_t stream);
+int fpc_mbconv_pw_form(int B, int64_t HW, int Cin, int Cout);
+int fpc_mbconv_stem(const float* in4, const float* w, const float* scale, const float* shift, float* out, int B, int Hi, int Wi, int Cout,
+                    fpc_stream_t stream);
 
 /* ---- The depthwise 3x3 convolution and the ReLU6 of the MobileNetV2 encoder in the training step (csrc/dwconv_train.hip,
  * csrc/batchnorm.hip; lib/train_conv.py: _DepthwiseConv2dFn and batchnorm_act(relu6=True) behind FPC_TRAIN_NATIVE_MBV2=1).  They
