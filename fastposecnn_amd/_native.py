@@ -159,6 +159,9 @@ _SIGNATURES = {
     "fpc_dwconv3x3_dgrad": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "fpc_dwconv3x3_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "fpc_dwconv3x3_wgrad": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "fpc_mbconv_dw_dgrad": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "fpc_mbconv_dw_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "fpc_mbconv_dw_wgrad": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "fpc_se_gate_train": (_i, [_vp] * 9 + [_i, _i, _i, _i, _i, _vp]),
     "fpc_se_bwd_scratch_floats": (_sz, [_i, _i, _i, _i, _i]),
     "fpc_se_bwd": (_i, [_vp] * 15 + [_i, _i, _i, _i, _i, _vp]),

@@ -64,6 +64,7 @@ extern "C" {
  *   fpc_batchnorm_act_fwd, fpc_batchnorm_act_bwd):
  * and the EfficientNet-B0 encoder (fpc_net_create's "efficientnet-b0", fpc_mbconv_dw, fpc_mbconv_gate and its _slabs / _scratch_floats,
  *   fpc_mbconv_pw, fpc_mbconv_pw_form, fpc_mbconv_stem):
+ * and the gradients of its depthwise convolution for the training step (fpc_mbconv_dw_dgrad, fpc_mbconv_dw_wgrad and its _workspace_bytes):
  * additions only, every earlier entry point keeps its behaviour. */
 #define FPC_ABI_VERSION 11
 
@@ -981,6 +982,37 @@ int fpc_mbconv_stem(const float* in4, const float* w, const float* scale, const 
 int fpc_dwconv3x3_dgrad(const float* dy, const float* w, float* dx, int B, int Hi, int Wi, int C, int stride, fpc_stream_t stream);
 size_t fpc_dwconv3x3_wgrad_workspace_bytes(int B, int Ho, int Wo, int C);
 int fpc_dwconv3x3_wgrad(const float* x, const float* dy, float* dw, int B, int Hi, int Wi, int C, int stride, void* ws,
+                        size_t ws_bytes, fpc_stream_t stream);
+
+/* ---- The gradients of the depthwise k x k convolution of the EfficientNet-B0 encoder, for the training step
+ * (csrc/mbconv_train.hip; C entries only, their front end in lib/train_conv.py is DESIGN.md 6b item 8 d).  They replace
+ * the backward of autograd through efficientnet_pytorch's Conv2dStaticSamePadding(groups = C) — nn.ZeroPad2d and cuDNN's grouped
+ * kernels, forward and backward — inside smp's EfficientNetEncoder (reached from F/lib/pose_regressor.py:608-613).  The FORWARD of the convolution in training is fpc_mbconv_dw above with act 0,
+ * scale 1 and shift 0 (v * 1 + 0 is exact).  Conventions of fpc_dwconv3x3_dgrad / _wgrad: dense channel-last f32, w / dw torch's
+ * [C][1][k][k] read / written in place, plain f32 FMAs in an order the shape alone fixes, no atomics: bit-identical run to run.
+ * The pads are fpc_mbconv_dw's: pad-before pb = (k - 1) / 2 at stride 1, 0 for k = 3 and 1 for k = 5 at stride 2; Ho = Hi / stride,
+ * Wo = Wi / stride.  FPC_EINVAL before any launch: a NULL or not 16-byte-aligned pointer, B < 1, C < 4 or C % 4 != 0, k other than
+ * 3 or 5, a stride other than 1 or 2, Hi < 1 or Wi < 1, an odd Hi or Wi at stride 2, B Hi Wi C / 4 >= 2^32 - 2^20 - 8 (the 32-bit
+ * walk limit of fpc_mbconv_dw).  (k, stride) = (3, 1) is pad 1 on every side: both entries hand it to fpc_dwconv3x3_dgrad / _wgrad.
+ *
+ * fpc_mbconv_dw_dgrad (k_mb_dw_dgrad_s1 / _s2): dx [B][Hi][Wi][C] from dy [B][Ho][Wo][C], every element written exactly once:
+ *   dx[h][w] = sum over kh, kw of dy[(h + pb - kh) / stride][(w + pb - kw) / stride] w[kh][kw] where the divisions are exact and
+ *   the index is inside dy.  Stride 2 is evaluated per output parity, no zero insertion: k = 3 per axis dx[2a] = dy[a] w[0] +
+ *   dy[a - 1] w[2], dx[2a + 1] = dy[a] w[1] (9 products per 2 x 2 block and channel); k = 5 dx[2a] = dy[a] w[1] + dy[a - 1] w[3],
+ *   dx[2a + 1] = dy[a + 1] w[0] + dy[a] w[2] + dy[a - 1] w[4] (25 products).
+ * fpc_mbconv_dw_wgrad (k_mb_dw_wgrad + k_mb_dw_wgrad_reduce): dw[c][kh][kw] = sum over b, ho, wo of
+ *   dy[b][ho][wo][c] x[b][stride ho + kh - pb][stride wo + kw - pb][c], zero outside x; every element of dw is overwritten, a tap
+ *   no pixel reaches with an exact zero.  The list of the B Ho (frame, output row) pairs is cut into
+ *       slices = max(1, min(max(1, 1024 / ceil(C / 32)), B Ho ceil(Wo / 8) / slots, B Ho)),  slots = 32 (k = 3) or 8 (k = 5)
+ *   contiguous slices (integer divisions), slice i = rows [i B Ho / slices, (i + 1) B Ho / slices): a function of
+ *   (B, Ho, Wo, C, k) alone, fpc_dwconv3x3_wgrad's count at k = 3.  One f32 partial [C][k k] per slice (inside a slice: `slots`
+ *   pixel slots over its (row, 8-column segment) units in turn, added in a fixed tree; at k = 5 a thread holds one tap row of a
+ *   channel quad), the slices added in double in sixteen contiguous ranges, each ascending, the ranges ascending.
+ *   ws: fpc_mbconv_dw_wgrad_workspace_bytes(B, Ho, Wo, C, k) = slices * C * k * k * 4 bytes (0 for a refused shape), 256-byte
+ *   aligned; too small or misaligned: FPC_EWORKSPACE (a NULL ws: FPC_EINVAL). */
+int fpc_mbconv_dw_dgrad(const float* dy, const float* w, float* dx, int B, int Hi, int Wi, int C, int k, int stride, fpc_stream_t stream);
+size_t fpc_mbconv_dw_wgrad_workspace_bytes(int B, int Ho, int Wo, int C, int k);
+int fpc_mbconv_dw_wgrad(const float* x, const float* dy, float* dw, int B, int Hi, int Wi, int C, int k, int stride, void* ws,
                         size_t ws_bytes, fpc_stream_t stream);
 
 /* ---- The same gate in the training step (csrc/se_train.hip; lib/train_conv.se_gate_add_relu behind FPC_TRAIN_NATIVE_SE=1).  They
