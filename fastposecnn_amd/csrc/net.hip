@@ -197,6 +197,13 @@ extern "C" int fpc_net_load_params(fpc_net_t* n, const float* const* params, int
         const int rc = fold_bn_of(n, o.p_bn, o.Cout, o.scale_off, o.shift_off, s, o.eps);
         if (rc) return rc;
     }
+    for (const fpc_net::DnOp& o : n->dops) {      // the DenseNet encoders' ops: the folded BatchNorms and conv2's re-laid image (conv1 and the transitions' conv are read in place)
+        int rc = FPC_OK;
+        if (o.p_bn1 >= 0) rc = fold_bn_of(n, o.p_bn1, o.K, o.s1_off, o.t1_off, s);
+        if (!rc && o.p_bn2 >= 0) rc = fold_bn_of(n, o.p_bn2, o.Cout, o.s2_off, o.t2_off, s);
+        if (!rc && o.kind == fpc_net::kDnConv3) rc = launch_dense_pack_w(n->pptr[o.p_w], n->ws + o.wt_off, s);
+        if (rc) return rc;
+    }
     n->loaded = true;
     return FPC_OK;
 }
@@ -459,6 +466,22 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
         return launch_mb_gate(ws + x.off, n->pptr[g.p], n->pptr[g.p + 1], n->pptr[g.p + 2], n->pptr[g.p + 3], ws + n->mb_gate_off,
                               ws + n->mb_part_off, B, x.H, x.W, x.C, g.Cs, s);
     };
+    // an op of a DenseNet encoder, on the one kernel of its kind and the form its shape names
+    auto dense_op = [&](const fpc_net::DnOp& o) -> int {
+        const long long M = (long long)B * o.H * o.W;
+        switch (o.kind) {
+        case fpc_net::kDnPlace: return launch_dense_place(ws + o.in_off, ws + o.out_off, M, o.K, o.ldo, s);
+        case fpc_net::kDnPw:
+            return launch_dense_pw(ws + o.in_off, o.p_bn1 >= 0 ? ws + o.s1_off : nullptr, o.p_bn1 >= 0 ? ws + o.t1_off : nullptr, n->pptr[o.p_w],
+                                   o.p_bn2 >= 0 ? ws + o.s2_off : nullptr, o.p_bn2 >= 0 ? ws + o.t2_off : nullptr, ws + o.out_off, M, o.K, o.Cout,
+                                   o.ldi, o.ldo, o.act, -1, s);
+        case fpc_net::kDnConv3: return launch_dense_conv3(ws + o.in_off, ws + o.wt_off, ws + o.out_off, B, o.H, o.W, o.c0, o.ldo, -1, s);
+        case fpc_net::kDnNormPool:
+            return launch_dense_norm_pool(ws + o.in_off, ws + o.s1_off, ws + o.t1_off, ws + o.out_off, o.out2 ? ws + o.out2_off : nullptr, B, o.H,
+                                          o.W, o.K, o.act, s);
+        }
+        return FPC_EINVAL;
+    };
     for (const Step& st : n->tape) {
         const float* res = st.res.C ? ws + st.res.off : nullptr;
         switch (st.kind) {
@@ -466,6 +489,7 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
         case kStepSeGate: FPC_TRY(se_gate(st.op, st.out, res)); break;
         case kStepMb: FPC_TRY(mb_op(n->mops[st.op], st.in, st.out, res)); break;
         case kStepMbGate: FPC_TRY(mb_gate(n->mgates[st.op], st.in)); break;
+        case kStepDense: FPC_TRY(dense_op(n->dops[st.op])); break;
         }
     }
     const Act* feat = n->a_feat;
@@ -926,6 +950,11 @@ extern "C" int fpc_net_flops(const fpc_net_t* n, double* out3) {
     for (const fpc_net::MbOp& o : n->mops) {      // the MobileNetV2 and EfficientNet ops: 27 (stem), k k (depthwise) or Cin products per output
         const bool stem = o.kind == fpc_net::kMbStem || o.kind == fpc_net::kMbSameStem, dw = o.kind == fpc_net::kMbDw || o.kind == fpc_net::kMbSameDw;
         const double f = 2.0 * n->B * (double)o.howo * o.Cout * (stem ? 27 : dw ? o.k * o.k : o.Cin);
+        direct += f; executed += f;
+    }
+    for (const fpc_net::DnOp& o : n->dops) {      // the DenseNet ops' products: K per output of a 1x1, 9 x 128 of a 3x3
+        if (o.kind != fpc_net::kDnPw && o.kind != fpc_net::kDnConv3) continue;
+        const double f = 2.0 * n->B * (double)o.H * o.W * o.Cout * (o.kind == fpc_net::kDnConv3 ? 9 * 128 : o.K);
         direct += f; executed += f;
     }
     for (int d = 0; d < 4; ++d)      // the 1x1 heads run inside k_merge_head

@@ -1,5 +1,5 @@
 // net_build.hip — how a plan of the backbone engine (net_plan.hpp: fpc_net) is built, host arithmetic only: the encoders
-// fpc_net_create knows by name, the four creation entry points, the three encoder families' builders and net_build, which puts a
+// fpc_net_create knows by name, the four creation entry points, the four encoder families' builders and net_build, which puts a
 // family's encoder in front of the four FPN decoders and heads and plans every convolution site.  The graph is the one
 // segmentation_models_pytorch builds for FastPoseCNN (fastposecnn_amd/lib/backbone.py).  Nothing here launches a kernel.
 #include <stdio.h>
@@ -249,10 +249,89 @@ static void effnet_params(fpc_net* n, EncoderBuild& eb) {
         }
 }
 
+// ---- the DenseNet encoders: torchvision's DenseNet.features as smp's DenseNetEncoder walks it, stem 64, growth 32, bn_size 4
+// (densenet121 / 169 / 201; densenet161's stem 96 and growth 48 are not built).  features.conv0 / norm0 / relu0 / pool0 are the ResNet
+// family's stem site and max-pool.  denseblockN has enc.layers[N - 1] layers: layer j reads the C = C0 + 32 j channels in front of
+// it, norm1 + relu1 + conv1 (1x1, C -> 128) + norm2 + relu2 + conv2 (3x3, 128 -> 32), and appends its 32.  transitionN (N = 1 .. 3) is
+// norm + relu (the stage's skip tensor: c2 .. c4) + conv (1x1, C -> C / 2) + a 2 x 2 average pool; the plan pools FIRST (the conv is
+// 1x1: the same linear map at a quarter of the products) and the conv writes into the next block's buffer.  norm5 without ReLU is
+// c5.  Parameters in state-dict order; every BatchNorm is folded at load, every conv2 re-laid (k_dense_pack_w), conv1 read in place.
+static void dn_params(fpc_net* n, EncoderBuild& eb) {
+    const std::string f("encoder.features.");
+    n->c_stem = n->add_conv(f + "conv0.weight", 3, 64, 7, 2, 3, (f + "norm0").c_str(), nullptr, 4, 8);      // (as resnet_params)
+    typedef fpc_net::DnOp DnOp;
+    {   DnOp o; o.kind = fpc_net::kDnPlace; o.block = 0; o.K = 64; n->dops.push_back(o); }
+    int C = 64;
+    for (int blk = 0; blk < 4; ++blk) {
+        for (int j = 0; j < n->enc.layers[blk]; ++j, C += 32) {
+            const std::string p = f + "denseblock" + std::to_string(blk + 1) + ".denselayer" + std::to_string(j + 1) + ".";
+            DnOp pw; pw.kind = fpc_net::kDnPw; pw.block = blk; pw.K = C; pw.Cout = 128; pw.act = 1;
+            pw.p_bn1 = n->add_bn(p + "norm1", C);
+            pw.p_w = n->add_param(p + "conv1.weight", (int64_t)128 * C);
+            pw.p_bn2 = n->add_bn(p + "norm2", 128);
+            pw.s1_off = n->alloc(C); pw.t1_off = n->alloc(C); pw.s2_off = n->alloc(128); pw.t2_off = n->alloc(128);
+            DnOp cv; cv.kind = fpc_net::kDnConv3; cv.block = blk; cv.K = 128; cv.Cout = 32; cv.c0 = C;
+            cv.p_w = n->add_param(p + "conv2.weight", (int64_t)32 * 128 * 9);
+            cv.wt_off = n->alloc(kDenseWtFloats);
+            n->dops.push_back(pw); n->dops.push_back(cv);
+        }
+        eb.featc[blk] = C;
+        DnOp np; np.kind = fpc_net::kDnNormPool; np.block = blk; np.K = C;
+        if (blk < 3) {
+            const std::string p = f + "transition" + std::to_string(blk + 1) + ".";
+            np.p_bn1 = n->add_bn(p + "norm", C); np.act = 1; np.out2 = 1;
+            np.s1_off = n->alloc(C); np.t1_off = n->alloc(C);
+            DnOp pw; pw.kind = fpc_net::kDnPw; pw.block = blk; pw.K = C; pw.Cout = C / 2; pw.out2 = 1;      // (out2: into the next block's buffer)
+            pw.p_w = n->add_param(p + "conv.weight", (int64_t)(C / 2) * C);
+            n->dops.push_back(np); n->dops.push_back(pw);
+            C /= 2;
+        } else {
+            np.p_bn1 = n->add_bn(f + "norm5", C);
+            np.s1_off = n->alloc(C); np.t1_off = n->alloc(C);
+            n->dops.push_back(np);
+        }
+    }
+}
+
+// Per block: the concatenation buffer [B][h][w][C_end], the 128-channel bottleneck, the stage's a_feat (the skip tensor; block 4's:
+// norm5's output) and, for blocks 1 .. 3, the pooled skip tensor.  Then every op's offsets and pitches, and the tape.
+static void dn_buffers(fpc_net* n, const EncoderBuild& eb) {
+    const int h1 = conv_out(n->H, 7, 2, 3), w1 = conv_out(n->W, 7, 2, 3);
+    n->a_stem = n->alloc_act(h1, w1, 64);
+    n->a_pool = n->alloc_act(conv_out(h1, 3, 2, 1), conv_out(w1, 3, 2, 1), 64);
+    Act cat[4], mid[4], pooled[4];
+    for (int blk = 0, h = n->a_pool.H, w = n->a_pool.W; blk < 4; ++blk, h /= 2, w /= 2) {
+        cat[blk] = n->alloc_act(h, w, eb.featc[blk]);
+        mid[blk] = n->alloc_act(h, w, 128);
+        n->a_feat[blk] = n->alloc_act(h, w, eb.featc[blk]);
+        if (blk < 3) pooled[blk] = n->alloc_act(h / 2, w / 2, eb.featc[blk]);
+    }
+    for (size_t i = 0; i < n->dops.size(); ++i) {
+        fpc_net::DnOp& o = n->dops[i];
+        const Act& c = cat[o.block];
+        Act in = c, out = c;
+        o.H = c.H; o.W = c.W;
+        switch (o.kind) {
+        case fpc_net::kDnPlace: in = n->a_pool; o.ldi = 64; o.ldo = c.C; break;
+        case fpc_net::kDnPw:
+            if (o.out2) { in = pooled[o.block]; out = cat[o.block + 1]; o.H = in.H; o.W = in.W; o.ldi = in.C; o.ldo = out.C; }
+            else { out = mid[o.block]; o.ldi = c.C; o.ldo = 128; }
+            break;
+        case fpc_net::kDnConv3: in = mid[o.block]; o.ldi = 128; o.ldo = c.C; break;
+        case fpc_net::kDnNormPool:
+            out = n->a_feat[o.block]; o.ldi = o.ldo = c.C;
+            if (o.out2) o.out2_off = pooled[o.block].off;
+            break;
+        }
+        o.in_off = in.off; o.out_off = out.off;
+        n->tape.push_back(dense_step((int)i, in, out));
+    }
+}
+
 static const struct {
     void (*params)(fpc_net* n, EncoderBuild& eb);
     void (*buffers)(fpc_net* n, const EncoderBuild& eb);
-} kFamilies[kFamilyCount] = {{resnet_params, resnet_buffers}, {mbv2_params, mb_buffers}, {effnet_params, mb_buffers}};      // by EncoderFamily
+} kFamilies[kFamilyCount] = {{resnet_params, resnet_buffers}, {mbv2_params, mb_buffers}, {effnet_params, mb_buffers}, {dn_params, dn_buffers}};      // by EncoderFamily
 
 // The plan of `n` (its encoder descriptor set) for (classes, B, H, W); owns `n` (deleted on failure).  The persistent region (packed
 // weights, folded BatchNorm, weight images) comes first, then the activations and scratch.
@@ -431,6 +510,10 @@ static const struct { const char* name; EncoderDesc desc; } kEncoders[] = {
     {"mobilenet_v2", {kFamilyMobileNetV2, {}, {2, 3, 7, 5}}},
     // EfficientNet-B0 (above); layers: the MBConv blocks in each stage of smp's last four (its stage ends 3, 5, 9, 16)
     {"efficientnet-b0", {kFamilyEfficientNet, {}, {3, 2, 4, 7}}},
+    // DenseNet-121 / 169 / 201 (above); layers: the dense layers of each block
+    {"densenet121", {kFamilyDenseNet, {}, {6, 12, 24, 16}}},
+    {"densenet169", {kFamilyDenseNet, {}, {6, 12, 32, 32}}},
+    {"densenet201", {kFamilyDenseNet, {}, {6, 12, 48, 32}}},
 };
 
 extern "C" int fpc_net_create(const char* encoder, int classes, int B, int H, int W, fpc_net_t** out) {

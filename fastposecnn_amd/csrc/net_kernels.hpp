@@ -372,6 +372,21 @@ int launch_mb_gate(const float* x, const float* w1, const float* b1, const float
                    int H, int W, int C, int Cs, hipStream_t s);
 int launch_mb_conv1x1(const float* in, const float* gate, const float* w, const float* scale, const float* shift, const float* res,
                       float* out, int B, long long HW, int Cin, int Cout, int act, hipStream_t s);
+// densenet.hip: the DenseNet encoders' kernels.  Channel-last f32 with row pitches: the 1x1 reads channels [0, K) of rows ldi apart
+// and writes [0, Cout) of rows ldo apart, pre(v) = max(s1[k] v + t1[k], 0) on its operand where s1 is not NULL, s2 / t2 (or NULL)
+// and act 1 = ReLU behind the sum; the 3x3 (128 -> 32, pad 1) reads dense [B][H][W][128] and the [9][32][128] image of
+// launch_dense_pack_w and writes channels [c0, c0 + 32) of rows ldo apart.  form: -1 = the shape's own (dense_*_form), 0 / 1 forced.
+constexpr int kDenseWtFloats = 9 * 32 * 128;
+bool dense_pw_ok(long long M, int K, int Cout, int ldi, int ldo);
+int dense_pw_form(long long M, int Cout);
+int launch_dense_pw(const float* in, const float* s1, const float* t1, const float* w, const float* s2, const float* t2, float* out,
+                    long long M, int K, int Cout, int ldi, int ldo, int act, int form, hipStream_t s);
+int launch_dense_pack_w(const float* w, float* wt, hipStream_t s);
+int dense_conv3_form(long long M);
+int launch_dense_conv3(const float* in, const float* wt, float* out, int B, int H, int W, int c0, int ldo, int form, hipStream_t s);
+int launch_dense_norm_pool(const float* x, const float* sc, const float* sh, float* skip, float* pooled, int B, int H, int W, int C, int act,
+                           hipStream_t s);
+int launch_dense_place(const float* in, float* out, long long M, int C, int ld, hipStream_t s);
 int launch_gn_finalize(const GnFinArgs& a, int groups, hipStream_t s);
 int launch_gn_relu_up2(const GnUpArgs& a, int groups, hipStream_t s);
 int launch_merge_head(const MergeHeadArgs& a, int groups, hipStream_t s);

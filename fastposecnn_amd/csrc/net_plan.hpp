@@ -41,6 +41,7 @@ enum EncoderFamily {
     kFamilyResNet,           // the 7x7 stem, a max-pool, then stage by stage blocks of one of the kinds above
     kFamilyMobileNetV2,      // torchvision's MobileNetV2 features: none of the block kinds (net_build.hip: "the MobileNetV2 encoder")
     kFamilyEfficientNet,     // efficientnet_pytorch's MBConv blocks by a table of block arguments (net_build.hip: "the EfficientNet encoders")
+    kFamilyDenseNet,         // torchvision's DenseNet features: the ResNet family's stem, then dense blocks and transitions (net_build.hip: "the DenseNet encoders")
     kFamilyCount
 };
 // What the ResNet family asks beside the blocks per stage; no other family has one, so no other family is asked these questions.
@@ -57,7 +58,7 @@ struct EncoderDesc {
     EncoderFamily family = kFamilyResNet;
     ResNetDesc resnet;            // read where family == kFamilyResNet only
     int layers[4] = {};           // ResNet: blocks per stage; MobileNetV2: the feature modules per stage of smp's last four, behind features.1;
-                                  // EfficientNet: the MBConv blocks per stage of smp's last four
+                                  // EfficientNet: the MBConv blocks per stage of smp's last four; DenseNet: the dense layers per block
     bool basic() const { return family == kFamilyResNet && resnet.expansion == 1; }         // c2 has 64 channels: s2.0 may fold the FPN p2 level in, and the direct sites have three-product images
     bool pointwise() const { return family == kFamilyResNet && resnet.expansion == 4; }     // the autotuner offers k_conv1x1 to the 1x1 sites
 };
@@ -68,7 +69,8 @@ enum StepKind {
     kStepConv,       // op: a conv site (fpc_net::convs) from `in` to `out`, with BatchNorm, the residual `res` (C > 0) and ReLU in its epilogue
     kStepSeGate,     // op: the first of se_module's four parameters; an SE block's gate on `out` in place, with the residual `res`
     kStepMb,         // op: an op of the MobileNetV2 or EfficientNet encoder (fpc_net::mops, whose MbOp::kind names the kernel) from `in` to `out`; a 1x1 adds `res` (C > 0)
-    kStepMbGate      // op: an MBConv block's gate (fpc_net::mgates) from the depthwise output `in`; writes the plan's gate buffer, which the block's project op reads
+    kStepMbGate,     // op: an MBConv block's gate (fpc_net::mgates) from the depthwise output `in`; writes the plan's gate buffer, which the block's project op reads
+    kStepDense       // op: an op of a DenseNet encoder (fpc_net::dops, whose DnOp::kind names the kernel); the op itself carries its buffer offsets, pitches and c0: `in` / `out` say which tensors it reads and writes
 };
 struct Step { StepKind kind; int op; Act in, out; bool relu; Act res; };
 inline Step conv_step(int conv, const Act& in, const Act& out, bool relu, const Act& res = Act()) {
@@ -82,6 +84,9 @@ inline Step mb_step(int mop, const Act& in, const Act& out, const Act& res = Act
 }
 inline Step mb_gate_step(int gate, const Act& x) {      // (`out` is the operand too: the gate itself lies in fpc_net::mb_gate_off)
     Step s; s.kind = kStepMbGate; s.op = gate; s.in = s.out = x; s.relu = false; return s;
+}
+inline Step dense_step(int dop, const Act& in, const Act& out) {
+    Step s; s.kind = kStepDense; s.op = dop; s.in = in; s.out = out; s.relu = false; return s;
 }
 
 struct fpc_net {
@@ -129,6 +134,27 @@ struct fpc_net {
         mgates.push_back(MbGate{p, C, Cs});
         return (int)mgates.size() - 1;
     }
+    // The DenseNet encoders' ops behind the stem and its max-pool (densenet.hip), in launch order.  Activations live in per-block
+    // concatenation buffers [B][h][w][C_end] that every layer of the block reads a channel prefix of and appends 32 channels to, so
+    // an op carries float offsets and row pitches of its own instead of Acts:
+    //   kDnPlace     the pooled stem [M][64] (in_off) into channels [0, 64) of block 1's buffer (out_off, ldo)
+    //   kDnPw        a dense layer's norm1 + relu1 + conv1 + norm2 + relu2 (pre = 1: s1 / t1 of p_bn1 over K channels, s2 / t2 of p_bn2,
+    //                act 1) from the prefix [0, K) of the buffer (ldi) to the 128-channel bottleneck; or a transition's conv on the pooled
+    //                tensor (pre = 0, no affine, act 0) into channels [0, Cout) of the NEXT block's buffer (ldo)
+    //   kDnConv3     a dense layer's conv2: the bottleneck [M][128] to channels [c0, c0 + 32) of the buffer (ldo); wt_off: its re-laid image
+    //   kDnNormPool  a transition's norm + relu to the stage's skip tensor (out_off, dense, K channels) and its 2 x 2 mean (out2_off);
+    //                or norm5 (act 0, no pooled tensor: out2 = 0)
+    // One form per shape each: not convolution sites, not tuned, not surveyed, not guarded.
+    enum DnKind { kDnPlace, kDnPw, kDnConv3, kDnNormPool };
+    struct DnOp {
+        DnKind kind; int block;
+        int p_w = -1, p_bn1 = -1, p_bn2 = -1;
+        int K = 0, Cout = 0, ldi = 0, ldo = 0, c0 = 0, act = 0, out2 = 0;
+        size_t s1_off = 0, t1_off = 0, s2_off = 0, t2_off = 0, wt_off = 0;
+        size_t in_off = 0, out_off = 0, out2_off = 0;
+        int H = 0, W = 0;      // the op's INPUT map
+    };
+    std::vector<DnOp> dops;
     struct Dec {
         int lat[4];               // p5, p4, p3, p2 (1x1, bias)
         int seg[7];               // s5.0 s5.1 s5.2 s4.0 s4.1 s3.0 s2.0
@@ -138,7 +164,7 @@ struct fpc_net {
     } dec[4];
 
     // activations (float offsets)
-    Act a_img4, a_stem, a_pool;   // (a_pool: the ResNet family's alone)
+    Act a_img4, a_stem, a_pool;   // (a_pool: the ResNet and DenseNet families' alone)
     Act a_feat[4];                // c2 .. c5: the output of each stage's last block
     Act a_p[4][4];                // [decoder][p5,p4,p3,p2]
     Act a_seg[4][7];              // pre-GroupNorm conv outputs

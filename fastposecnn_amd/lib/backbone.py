@@ -25,6 +25,9 @@ The EfficientNet-B0 encoder (efficientnet-b0) is smp's EfficientNetEncoder over 
 way (neither package is here: parity unpinned): encoder._conv_stem / _bn0, 16 MBConv blocks encoder._blocks.N with the static "same"
 pads of the declared 224 image, swish and the squeeze-and-excitation gate, _conv_head / _bn1 kept and not run, the feature levels
 behind the stem and blocks 2 / 4 / 8 / 15.
+The DenseNet encoders (densenet121 / 169 / 201) are smp's DenseNetEncoder over torchvision.models.densenet, restated the same way
+(parity unpinned): encoder.features.conv0 / norm0 / relu0 / pool0, dense blocks of pre-activated 1x1 + 3x3 layers whose outputs are
+concatenated, transitions whose post-ReLU tensor is the feature level, norm5 without a ReLU as the last level.  densenet161 is not built.
 state_dict names follow smp: encoder.conv1.weight, encoder.layer1.0.conv1.weight, ...,
 <dec>.p5.weight, <dec>.p4.skip_conv.weight, <dec>.seg_blocks.0.block.0.block.0.weight (conv),
 ...block.1.weight (GroupNorm), <head>.0.weight.
@@ -222,13 +225,15 @@ _ENCODERS = {"resnet18": (BasicBlock, [2, 2, 2, 2], 1, 64, 0), "resnet34": (Basi
 
 
 def encoder_family(name):
-    """The one look-up the engine switches on: "mobilenet_v2" and "efficientnet" for the encoders fpc_net_create builds by their
-    names, "resnet" for every encoder that encoder_layout / encoder_groups / encoder_reduction describe; KeyError for a name this
+    """The one look-up the engine switches on: "mobilenet_v2", "efficientnet" and "densenet" for the encoders fpc_net_create builds by
+    their names, "resnet" for every encoder that encoder_layout / encoder_groups / encoder_reduction describe; KeyError for a name this
     package does not build."""
     if name == MobileNetV2Encoder.NAME:
         return "mobilenet_v2"
     if name in EfficientNetEncoder.VARIANTS:
         return "efficientnet"
+    if name in DenseNetEncoder.VARIANTS:
+        return "densenet"
     _ENCODERS[name]
     return "resnet"
 
@@ -252,7 +257,7 @@ def encoder_reduction(name):
 
 def _available():
     """The encoder names this package builds, for the KeyError of an unknown one."""
-    return sorted(_ENCODERS) + [MobileNetV2Encoder.NAME] + sorted(EfficientNetEncoder.VARIANTS)
+    return sorted(_ENCODERS) + [MobileNetV2Encoder.NAME] + sorted(EfficientNetEncoder.VARIANTS) + sorted(DenseNetEncoder.VARIANTS)
 
 
 def _make_stage(block, inplanes, planes, blocks, stride, **kw):
@@ -558,6 +563,120 @@ class EfficientNetEncoder(nn.Module):
         return feats
 
 
+class DenseLayer(nn.Module):
+    """torchvision.models.densenet._DenseLayer: conv2(relu2(norm2(conv1(relu1(norm1(x)))))) of the concatenated input, conv1 a 1x1
+    to bn_size * growth channels, conv2 a 3x3 / pad 1 to `growth`; no dropout (drop_rate 0).  Both ReLUs are named children: a test
+    may swap them."""
+
+    def __init__(self, inp, growth, bn_size):
+        super().__init__()
+        self.norm1 = BatchNorm2d(inp)
+        self.relu1 = nn.ReLU(inplace=True)
+        self.conv1 = Conv2d(inp, bn_size * growth, 1, bias=False)
+        self.norm2 = BatchNorm2d(bn_size * growth)
+        self.relu2 = nn.ReLU(inplace=True)
+        self.conv2 = Conv2d(bn_size * growth, growth, 3, 1, 1, bias=False)
+
+    def forward(self, x):
+        y = self.conv1(_bn_act(x, self.norm1, self.relu1))
+        return self.conv2(_bn_act(y, self.norm2, self.relu2))
+
+
+class DenseBlock(nn.ModuleDict):
+    """torchvision's _DenseBlock: children denselayer1 .. N; every layer's output is concatenated behind its input."""
+
+    def __init__(self, layers, inp, growth, bn_size):
+        super().__init__()
+        for j in range(layers):
+            self["denselayer%d" % (j + 1)] = DenseLayer(inp + j * growth, growth, bn_size)
+
+    def forward(self, x):
+        for layer in self.values():
+            x = torch.cat([x, layer(x)], 1)
+        return x
+
+
+class Transition(nn.Sequential):
+    """torchvision's _Transition (norm, relu, conv 1x1 to half the channels, AvgPool2d(2, 2)) as smp's TransitionWithSkip walks it:
+    returns the pooled tensor and the tensor behind the ReLU, which is the stage's feature level."""
+
+    def __init__(self, inp, oup):
+        super().__init__()
+        self.norm = BatchNorm2d(inp)
+        self.relu = nn.ReLU(inplace=True)
+        self.conv = Conv2d(inp, oup, 1, bias=False)
+        self.pool = nn.AvgPool2d(kernel_size=2, stride=2)
+
+    def forward(self, x):
+        skip = _bn_act(x, self.norm, self.relu)
+        return self.pool(self.conv(skip)), skip
+
+
+class DenseNetEncoder(nn.Module):
+    """smp's DenseNetEncoder: torchvision's DenseNet.features without the classifier, restated the same way as the other encoders
+    (neither package is here: parity unpinned), returning 6 feature levels: the input, relu0's output, the tensor behind the ReLU
+    of transitions 1 .. 3 (in front of their conv) and norm5's output WITHOUT a ReLU.  state_dict names and order are torchvision's
+    (features.conv0.weight, features.denseblock1.denselayer1.norm1.weight, features.transition1.conv.weight, features.norm5.bias).
+    VARIANTS: the dense layers per block; all three have a 64-channel stem, growth 32 and bn_size 4.  densenet161 (stem 96, growth
+    48) is NOT built: the native 7x7 stem and the native 3x3 are made for 64 and 32 channels; it raises KeyError like any unknown
+    name.  In the training step the convolutions and BatchNorms reach the native front ends through Conv2d / BatchNorm2d / _bn_act
+    above where those accept the shape; the concatenation and the average pool are torch's."""
+    VARIANTS = {"densenet121": (6, 12, 24, 16), "densenet169": (6, 12, 32, 32), "densenet201": (6, 12, 48, 32)}
+    STEM, GROWTH, BN_SIZE = 64, 32, 4
+
+    def __init__(self, name="densenet121", in_channels=3, depth=5):
+        super().__init__()
+        if name not in self.VARIANTS:
+            raise KeyError(f"encoder {name!r} not available (have {_available()})")
+        from collections import OrderedDict
+        self.name = name
+        self._depth = depth
+        f = OrderedDict([("conv0", Conv2d(in_channels, self.STEM, 7, 2, 3, bias=False)), ("norm0", BatchNorm2d(self.STEM)),
+                         ("relu0", nn.ReLU(inplace=True)), ("pool0", MaxPool2d(3, 2, 1))])
+        c, skips = self.STEM, []
+        for i, layers in enumerate(self.VARIANTS[name]):
+            f["denseblock%d" % (i + 1)] = DenseBlock(layers, c, self.GROWTH, self.BN_SIZE)
+            c += layers * self.GROWTH
+            if i < 3:
+                skips.append(c)
+                f["transition%d" % (i + 1)] = Transition(c, c // 2)
+                c //= 2
+        f["norm5"] = BatchNorm2d(c)
+        self.features = nn.Sequential(f)
+        self.out_channels = (in_channels, self.STEM, *skips, c)
+        # torchvision's initialisation (a checkpoint or a weights file overwrites it)
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight)
+            elif isinstance(m, nn.BatchNorm2d):
+                nn.init.constant_(m.weight, 1)
+                nn.init.constant_(m.bias, 0)
+
+    def forward(self, x):
+        f = self.features
+        feats = [x]
+        x = _bn_act(f.conv0(x), f.norm0, f.relu0)
+        feats.append(x)
+        x = f.pool0(x)
+        for i in (1, 2, 3):
+            x, skip = getattr(f, "transition%d" % i)(getattr(f, "denseblock%d" % i)(x))
+            feats.append(skip)
+        feats.append(f.norm5(f.denseblock4(x)))
+        return feats
+
+    @staticmethod
+    def remap_legacy_keys(sd):
+        """torchvision's released DenseNet checkpoints name a dense layer's children norm.1 / relu.1 / conv.1 / norm.2 ...; smp's
+        DenseNetEncoder.load_state_dict rewrites them to norm1 / conv1 ... before loading.  The same rewrite."""
+        import re
+        pat = re.compile(r"^(.*denselayer\d+\.(?:norm|relu|conv))\.((?:[12])\.(?:weight|bias|running_mean|running_var|num_batches_tracked))$")
+        out = type(sd)()
+        for k, v in sd.items():
+            m = pat.match(k)
+            out[m.group(1) + m.group(2) if m else k] = v
+        return out
+
+
 _WARNED_WEIGHTS = set()
 
 
@@ -570,13 +689,15 @@ def get_encoder(name, in_channels=3, depth=5, weights=None):
     dict (keys conv1.weight, bn1.*, layer1.0.conv1.weight, ...; fc.* is dropped, as smp does) or, for an SE-ResNet, the
     pretrainedmodels one (layer0.conv1.weight, ..., layerN.i.se_module.fc1.bias; last_linear.* is dropped) or, for mobilenet_v2,
     torchvision's (features.0.0.weight, ..., features.18.1.running_var; classifier.* is dropped) or, for efficientnet-b0,
-    efficientnet_pytorch's (_conv_stem.weight, ..., _conv_head.weight, _bn1.*; _fc.* is dropped).  When `weights` is
+    efficientnet_pytorch's (_conv_stem.weight, ..., _conv_head.weight, _bn1.*; _fc.* is dropped) or, for densenet121 / 169 / 201,
+    torchvision's (features.conv0.weight, ..., features.norm5.running_var, with the released files' legacy norm.1 / conv.2 keys
+    rewritten; classifier.* is dropped).  When `weights` is
     requested and no file is configured the encoder stays randomly initialised and a warning says so once per
     encoder — a checkpoint loaded afterwards (load_from_ckpt) overwrites the encoder anyway."""
     import logging
     import os
     cls = MobileNetV2Encoder if name == MobileNetV2Encoder.NAME else EfficientNetEncoder if name in EfficientNetEncoder.VARIANTS \
-        else SENetEncoder if name in _ENCODERS and _ENCODERS[name][4] else ResNetEncoder
+        else DenseNetEncoder if name in DenseNetEncoder.VARIANTS else SENetEncoder if name in _ENCODERS and _ENCODERS[name][4] else ResNetEncoder
     enc = cls(name, in_channels=in_channels, depth=depth)
     enc.requested_weights = weights
     enc.loaded_weights = None
@@ -588,6 +709,8 @@ def get_encoder(name, in_channels=3, depth=5, weights=None):
             import torch
             sd = torch.load(path, map_location="cpu")
             sd = {k: v for k, v in sd.items() if not k.startswith(("fc.", "last_linear.", "classifier.", "_fc."))}
+            if cls is DenseNetEncoder:
+                sd = DenseNetEncoder.remap_legacy_keys(sd)      # (norm.1 -> norm1 ...: as smp's load_state_dict)
             enc.load_state_dict(sd)                  # strict: a wrong file fails loudly
             enc.loaded_weights = path
         elif (name, weights) not in _WARNED_WEIGHTS:

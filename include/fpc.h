@@ -65,6 +65,8 @@ extern "C" {
  * and the EfficientNet-B0 encoder (fpc_net_create's "efficientnet-b0", fpc_mbconv_dw, fpc_mbconv_gate and its _slabs / _scratch_floats,
  *   fpc_mbconv_pw, fpc_mbconv_pw_form, fpc_mbconv_stem):
  * and the gradients of its depthwise convolution for the training step (fpc_mbconv_dw_dgrad, fpc_mbconv_dw_wgrad and its _workspace_bytes):
+ * and the DenseNet-121 / 169 / 201 encoders (fpc_net_create's "densenet121" / "densenet169" / "densenet201", fpc_dense_pw, fpc_dense_pw_form,
+ *   fpc_dense_conv3x3, fpc_dense_conv3x3_pack, fpc_dense_conv3x3_form, fpc_dense_norm_pool, fpc_dense_place):
  * additions only, every earlier entry point keeps its behaviour. */
 #define FPC_ABI_VERSION 11
 
@@ -955,6 +957,48 @@ int fpc_mbconv_pw(const float* in, const float* gate, const float* w, const floa
 int fpc_mbconv_pw_form(int B, int64_t HW, int Cin, int Cout);
 int fpc_mbconv_stem(const float* in4, const float* w, const float* scale, const float* shift, float* out, int B, int Hi, int Wi, int Cout,
                     fpc_stream_t stream);
+
+/* ---- The DenseNet encoders' kernels (csrc/densenet.hip), stand-alone.  fpc_net_create("densenet121" | "densenet169" | "densenet201", ...)
+ * builds the plan that runs them: torchvision's DenseNet.features as smp's DenseNetEncoder wraps it (F/lib/pose_regressor.py:608-613
+ * through smp.encoders.get_encoder), replacing cuDNN's 1x1 and 3x3 convolutions and aten's BatchNorm, ReLU, cat and avg_pool2d at
+ * inference.  densenet161 (stem 96, growth 48) is not built: FPC_EINVAL.  Such a plan's encoder is the ResNet family's 7x7 stem
+ * site (tuned, surveyed and guarded like theirs; fpc_net_force_stem_pool applies) and its max-pool, the place step, two launches per
+ * dense layer (58 / 82 / 98 layers), two per transition and norm5.  A block's layers share one concatenation buffer
+ * [B][h][w][C_end]: torch.cat is never executed, a layer reads the channel prefix in front of it and appends its 32 channels.  A
+ * transition runs as conv(pool(relu(norm(x)))): the module's pool(conv(.)) is the same linear map, at four times the products; the
+ * two orders differ by rounding only.  The dense ops are not convolution sites (fpc_net_conv_count counts the stem's and the
+ * decoders' alone), are not autotuned, surveyed or guarded; fpc_net_force_fold(net, 1) is refused, fpc_net_force_direct_h3 changes
+ * 0 sites; the laterals see 256 / 512 / 1024 .. channels, all on the fast loader.
+ * All: channel-last f32, every pointer 16-byte aligned (FPC_EINVAL otherwise; NULL only where stated), exact f32 products on
+ * v_mfma_f32_32x32x2_f32 / v_mfma_f32_16x16x4_f32 with f32 accumulation, a summation order the shape and the form alone fix, no
+ * atomics: bit-identical run to run.  `form` -1 runs the form the shape names (the _form function), 0 / 1 force one.
+ * fpc_dense_pw (k_dense_pw32 / k_dense_pw16; replaces norm1 + relu1 + conv1 + norm2 + relu2 of _DenseLayer, and a _Transition's conv):
+ *   out[m ldo + n] = act(s2[n] sum_{k < K} pre(in[m ldi + k]) w[n][k] + t2[n]) with pre(v) = max(s1[k] v + t1[k], 0) rounded to f32
+ *   before the matrix instruction; s1 / t1 both NULL: pre is the identity; s2 / t2 both NULL: no affine.  w torch's [Cout][K][1][1]
+ *   read in place.  Nothing at or behind channel K of an input row is read, only [0, Cout) of an output row is written.  K % 32 == 0,
+ *   32 .. 2048; Cout % 32 == 0, 32 .. 1024; ldi >= K, ldi % 4 == 0; ldo >= Cout; 1 <= M < 2^31 - 64; act 0 or 1 (ReLU).
+ *   fpc_dense_pw_form: 1 = 32 x 32 tiles, a wave each, where M / 32 (rounded up) x Cout / 32 reaches 1024, else 0 = 16 x 16 tiles, a
+ *   workgroup each: its four waves take the K-steps of 32 in turn and are added through LDS as ((w0 + w1) + w2) + w3.
+ * fpc_dense_conv3x3 (k_dense_conv3_tile / k_dense_conv3_split; replaces conv2 of _DenseLayer and the torch.cat behind it): 3x3, pad 1,
+ *   stride 1, 128 -> 32 channels, no affine, no activation: out[((b H + h) W + w) ldo + c0 + n] = sum in[b][h + kh - 1][w + kw - 1][c]
+ *   w[n][c][kh][kw] over in dense [B][H][W][128]; only channels [c0, c0 + 32) of a pixel are written.  c0 % 32 == 0, c0 + 32 <= ldo,
+ *   B H W < 2^31 - 64.  wt is the image fpc_dense_conv3x3_pack makes of torch's w [32][128][3][3]: 9 x 32 x 128 floats, [tap][n][c].
+ *   fpc_dense_conv3x3_form: 1 = one wave per 64 pixels where that gives 1024 waves (B H W > 65472), else 0 = a workgroup of nine waves
+ *   per 16 pixels, a tap each, added through LDS in tap order.
+ * fpc_dense_norm_pool (k_dense_norm_pool; replaces a _Transition's norm + relu + pool, and norm5): skip = act(s x + t) over dense
+ *   [B][H][W][C] and, where pooled is not NULL (H and W even), pooled[b][h / 2][w / 2][c] = 0.25f ((skip00 + skip01) + (skip10 + skip11)).
+ *   C % 4 == 0; B H W C / 4 < 2^32 - 2^20 - 8.
+ * fpc_dense_place (k_dense_place; the pooled stem into block 1's buffer): out[m ld + c] = in[m C + c] for c < C, bit for bit; C % 4 == 0,
+ *   ld >= C, ld % 4 == 0, M C / 4 < 2^32 - 2^20 - 8. */
+int fpc_dense_pw(const float* in, const float* s1, const float* t1, const float* w, const float* s2, const float* t2, float* out, int64_t M,
+                 int K, int Cout, int ldi, int ldo, int act, int form, fpc_stream_t stream);
+int fpc_dense_pw_form(int64_t M, int K, int Cout);
+int fpc_dense_conv3x3_pack(const float* w, float* wt, fpc_stream_t stream);
+int fpc_dense_conv3x3(const float* in, const float* wt, float* out, int B, int H, int W, int c0, int ldo, int form, fpc_stream_t stream);
+int fpc_dense_conv3x3_form(int B, int H, int W);
+int fpc_dense_norm_pool(const float* x, const float* s, const float* t, float* skip, float* pooled, int B, int H, int W, int C, int act,
+                        fpc_stream_t stream);
+int fpc_dense_place(const float* in, float* out, int64_t M, int C, int ld, fpc_stream_t stream);
 
 /* ---- The depthwise 3x3 convolution and the ReLU6 of the MobileNetV2 encoder in the training step (csrc/dwconv_train.hip,
  * csrc/batchnorm.hip; lib/train_conv.py: _DepthwiseConv2dFn and batchnorm_act(relu6=True) behind FPC_TRAIN_NATIVE_MBV2=1).  They
