@@ -4,7 +4,6 @@ manifests, feature levels, BatchNorm constants, a dense layer and a transition a
 orders), encoder-weights loading with the legacy keys, the preprocessing parameters, the engine's host-side plan
 (fpc_net_create("densenet121" ...): parameter table, refusals), the host-side refusals of the stand-alone kernel entries, and the
 condition the GPU engine test puts on its own inputs.  No compute calls into the HIP library."""
-import copy
 import ctypes
 import os
 
@@ -12,6 +11,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _batch_forms as BF
 import _densenet_model as D
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -334,15 +334,14 @@ def test_the_engine_tests_draw_is_well_conditioned(B, H, W):
     forward of the module stays within a quarter of the network bar 1e-4 max(1, |ref|max) of float64 on c2 .. c5 and every logit, so
     the bar measures the engine and not the conditioning of the draw."""
     import fastposecnn_amd.lib as L
-    m, hp = D.model(L, "densenet121")
-    hp.USE_NATIVE_ENGINE = False
-    x = D.images(B, H, W)
-    m64 = copy.deepcopy(m).double()
-    m64.HPARAM = hp
-    with torch.no_grad():
-        got = list(m.encoder(x)[2:]) + list(m.pure_model_forward(x).values())
-        ref = list(m64.encoder(x.double())[2:]) + list(m64.pure_model_forward(x.double()).values())
-    assert len(ref) == 9
-    for a, r in zip(got, ref):
-        err = (a.double() - r).abs().max().item()
-        assert err <= 0.25 * 1e-4 * max(1.0, r.abs().max().item()), err
+    for err, scale in BF.f32_errors(L, "densenet121", D.images(B, H, W)):
+        assert err <= 0.25 * 1e-4 * max(1.0, scale), err
+
+
+def test_the_batch_tests_frames_are_well_conditioned():
+    """The same condition on what tests/test_gpu_batch_forms.py compares: frames 0, 17 and 31 of its batch at 352 x 416."""
+    import fastposecnn_amd.lib as L
+    x = BF.frames("densenet121")
+    assert tuple(x.shape) == (3, 3, 352, 416)
+    for err, scale in BF.f32_errors(L, "densenet121", x):
+        assert err <= 0.25 * 1e-4 * max(1.0, scale), err

@@ -12,10 +12,10 @@ import torch
 import torch.nn.functional as F
 
 import _densenet_model as D
+from _densenet_kernels import NAN, _bar, _conv_run, _pitched, _pw_operands, _pw_ref, _twice
 
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
 PW_M = [1, 30, 33, 300]                                  # one row; under / over one 32-row tile; 19 tiles of 16 with a ragged last one
 PW_K = [(64, 64), (96, 256), (160, 512), (1024, 1024), (1920, 1920)]      # (K, ldi): dense, and prefixes of a wider row
 CONV_SHAPES = [(1, 1, 1), (2, 2, 2), (1, 3, 5), (2, 7, 9), (1, 15, 20), (1, 8, 40)]
@@ -36,70 +36,7 @@ def lib(dev):
     return L
 
 
-def _twice(dev, prefill, launch):
-    """Two launches into fresh buffers: 64 NaN canaries, `prefill` (CPU f32, NaN wherever the kernel must write, a pattern wherever it
-    must not), 64 NaN canaries.  The canaries intact, the pattern intact bit for bit, nothing left unwritten, both runs the same
-    bits.  Returns the first run's body (CPU, flat)."""
-    n = prefill.numel()
-    keep = ~torch.isnan(prefill.view(-1))
-    outs = []
-    for _ in range(2):
-        buf = torch.full((n + 128,), NAN)
-        buf[64:64 + n] = prefill.view(-1)
-        buf = buf.to(dev)
-        y = buf[64:64 + n]
-        assert y.data_ptr() % 16 == 0
-        assert launch(y.data_ptr()) == 0
-        torch.cuda.synchronize()
-        host = buf.cpu()
-        assert torch.isnan(host[:64]).all() and torch.isnan(host[64 + n:]).all(), "a canary was overwritten"
-        body = host[64:64 + n]
-        assert torch.equal(body[keep].view(torch.int32), prefill.view(-1)[keep].view(torch.int32)), "wrote outside its slice"
-        assert not torch.isnan(body[~keep]).any(), "unwritten outputs"
-        outs.append(body)
-    assert torch.equal(outs[0].view(torch.int32), outs[1].view(torch.int32))
-    return outs[0]
-
-
-def _pitched(M, ld, lo, hi):
-    """[M][ld] pre-fill: NaN in columns [lo, hi), a pattern of finite values (no two neighbours alike) elsewhere."""
-    t = (torch.arange(M * ld, dtype=torch.float32) % 977 - 400.0).view(M, ld) * 0.25
-    t[:, lo:hi] = NAN
-    return t
-
-
-def _bar(out, ref, what):
-    err = (out.double() - ref).abs().max().item()
-    print(what, "err", err, "ref max", ref.abs().max().item())
-    assert err <= 2e-5 * max(1.0, ref.abs().max().item()), (what, err)
-
-
 # ---------------------------------------------------------------------------------------------------------------- fpc_dense_pw
-
-def _pw_operands(g, M, K, ldi, whole):
-    """in [M][ldi] with NaN behind channel K, s1 / t1 [K], w [128][K], s2 / t2 [128] (a narrower Cout takes their first rows)."""
-    if whole:
-        x = torch.randint(-4, 5, (M, K), generator=g).float()
-        s1, t1 = torch.randint(1, 3, (K,), generator=g).float(), torch.randint(-3, 4, (K,), generator=g).float()
-        w = torch.randint(-2, 3, (128, K), generator=g).float()
-        s2, t2 = torch.randint(1, 4, (128,), generator=g).float(), torch.randint(-5, 6, (128,), generator=g).float()
-    else:
-        x = torch.randn((M, K), generator=g)
-        s1, t1 = (torch.rand(K, generator=g) + 0.5), torch.randn(K, generator=g) * 0.5
-        w = torch.randn((128, K), generator=g) * 2.0 / K ** 0.5
-        s2, t2 = (torch.rand(128, generator=g) + 0.5) * 2.0, torch.randn(128, generator=g)
-    xin = torch.full((M, ldi), NAN)
-    xin[:, :K] = x
-    return x, xin, s1, t1, w, s2, t2
-
-
-def _pw_ref(x, s1, t1, w, s2, t2, Cout, pre, act):
-    a = x.double()
-    if pre:
-        a = (a * s1.double() + t1.double()).clamp_min(0.0)
-    v = a @ w[:Cout].double().t() * s2[:Cout].double() + t2[:Cout].double()
-    return v.clamp_min(0.0) if act else v
-
 
 def _pw_sweep(dev, M, K, ldi, whole, seed):
     from fastposecnn_amd import _native as nat
@@ -158,21 +95,6 @@ def test_pw_forms_by_shape(lib, dev):
 
 
 # ----------------------------------------------------------------------------------------------------------- fpc_dense_conv3x3
-
-def _conv_run(dev, x, w, c0, ldo, form):
-    from fastposecnn_amd import _native as nat
-    L = nat.lib()
-    B, _, H, W = x.shape
-    xd = x.permute(0, 2, 3, 1).contiguous().to(dev)
-    wd = w.contiguous().to(dev)
-    wt = torch.full((9 * 32 * 128 + 64,), NAN, device=dev)
-    assert L.fpc_dense_conv3x3_pack(wd.data_ptr(), wt.data_ptr(), nat.stream()) == 0
-    assert torch.isnan(wt[9 * 32 * 128:]).all() and not torch.isnan(wt[:9 * 32 * 128]).any()
-    assert torch.equal(wt[:9 * 32 * 128].view(9, 32, 128).cpu(), w.permute(2, 3, 0, 1).reshape(9, 32, 128))
-    out = _twice(dev, _pitched(B * H * W, ldo, c0, c0 + 32), lambda y: L.fpc_dense_conv3x3(xd.data_ptr(), wt.data_ptr(), y, B, H, W, c0, ldo,
-                                                                                          form, nat.stream()))
-    return out.view(B, H, W, ldo)[..., c0:c0 + 32].permute(0, 3, 1, 2)
-
 
 @pytest.mark.parametrize("form", [0, 1], ids=["split", "tile"])
 @pytest.mark.parametrize("c0,ldo", CONV_SLICES)
