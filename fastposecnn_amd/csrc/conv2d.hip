@@ -86,6 +86,19 @@ extern "C" int fpc_wino_tile_zread(int xshare, int t_e, int tp, int cc, int i, i
     out1[0] = o[0];
     return FPC_OK;
 }
+// the exit of those kernels: the patch decode with its fast-exit verdict, a thread's 16 output offsets.  See fpc.h.
+extern "C" int fpc_wino_tile_patch(int packed, int H, int W, int B, int tbx, int tby, int pack, int patch, int64_t* out8) {
+    long long o[8];
+    if (!out8 || wino_tile_patch(packed != 0, H, W, B, tbx, tby, pack, patch, o)) return FPC_EINVAL;
+    for (int i = 0; i < 8; ++i) out8[i] = o[i];
+    return FPC_OK;
+}
+extern "C" int fpc_wino_tile_out(int tr, int H, int W, int Cout, int nb, int b, int ty0, int tx0, int pk_ks, int t_e, int64_t* out16) {
+    long long o[16];
+    if (!out16 || wino_tile_out(tr != 0, H, W, Cout, nb, b, ty0, tx0, pk_ks, t_e, o)) return FPC_EINVAL;
+    for (int i = 0; i < 16; ++i) out16[i] = o[i];
+    return FPC_OK;
+}
 
 // ---- stand-alone convolution (unit tests / micro-benchmarks of k_conv_igemm) -----------------
 extern "C" size_t fpc_conv2d_workspace_bytes(int B, int Ho, int Wo, int Cin, int Cout, int Kh, int Kw) {
@@ -191,6 +204,7 @@ extern "C" int fpc_conv2d(const float* in, int64_t sb, int64_t sh, int64_t sw, i
     a.wino_pack = rq.pack ? 1 : 0;      // (-9 itself stays on the plain geometry
     a.wino_orient = rq.orient ? 1 : 0;  // and in the stored orientation)
     a.wino_rowsplit = rq.rowsplit ? 1 : 0;
+    a.wino_exit_general = rq.exit_general ? 1 : 0;
     a.splitk_ws = packed + lay.packed;
     a.p[0] = ConvPtrs{in, packed, out, scale, shift, res, up, gn_part};
     if (lay.tickets) {   // arrival counters of the fused split-K form, zeroed per call

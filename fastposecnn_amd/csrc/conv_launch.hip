@@ -79,6 +79,7 @@ int launch_conv_plan(ConvArgs& a, const ConvPlan& p, int groups, hipStream_t s) 
         w.groups = groups;
         w.B = a.B; w.H = a.Ho; w.W = a.Wo; w.Cin = a.Cin; w.Cout = a.Cout; w.relu = a.relu;
         w.waves = f.waves;
+        w.exit_general = a.wino_exit_general ? 1 : 0;
         const WinoGrid wg = wino_grid(p.wino, a.Ho, a.Wo);
         w.tbx = wg.tbx; w.tby = wg.tby;
         if (p.wino == kWinoH3) {      // packing and orientation: the same workgroups, fewer of them — properties of the launch, not of the plan

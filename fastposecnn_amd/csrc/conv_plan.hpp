@@ -214,9 +214,15 @@ inline bool wino_xshare_rule(int W) { return (((W + 1) >> 1) & 1) == 0; }
 
 // ---- the integer a plan is reported by (fpc_net_conv_plan's out5[2]) and requested by (fpc_conv2d's `nsplit`): fpc.h, FPC_PLAN_*.
 // What a request asks for (nsplit: the split-K factor, 0 = the planner's, or -form; wino: the form or 0):
-struct Conv2dRequest { int nsplit; bool bf3, two_launch; int wino, lat; bool stem; int pw; bool h3, pool, pack, orient; int grp; bool rowsplit; };
+struct Conv2dRequest { int nsplit; bool bf3, two_launch; int wino, lat; bool stem; int pw; bool h3, pool, pack, orient; int grp; bool rowsplit, exit_general; };
 inline Conv2dRequest decode_plan(int code) {
-    Conv2dRequest r{code, false, false, 0, 0, false, 0, false, false, false, false, 0, false};
+    Conv2dRequest r{code, false, false, 0, 0, false, 0, false, false, false, false, 0, false, false};
+    // -107 .. -113: the four-wave forms -7 .. -13 with every workgroup on the general exit (the two exits' A/B)
+    if (code <= FPC_PLAN_WINO_GENERAL_EXIT - kWinoW4 && code >= FPC_PLAN_WINO_GENERAL_EXIT + FPC_PLAN_WINO_ORIENT_ROWSPLIT) {
+        r.exit_general = true;
+        code -= FPC_PLAN_WINO_GENERAL_EXIT;
+        r.nsplit = code;
+    }
     // -12 / -13: -10 / -11 on the row-split tile map even where wino_xshare_rule offers the x-shared one (the two maps' A/B)
     if (code == FPC_PLAN_WINO_PACKED_ROWSPLIT) { r.rowsplit = true; code = FPC_PLAN_WINO_PACKED; }
     if (code == FPC_PLAN_WINO_ORIENT_ROWSPLIT) { r.rowsplit = true; code = FPC_PLAN_WINO_ORIENT; }

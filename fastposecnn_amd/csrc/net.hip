@@ -85,6 +85,16 @@ extern "C" int fpc_net_set_wino_xshare(fpc_net_t* n, int on) {
     return FPC_OK;
 }
 
+// on = 1 (the default): a workgroup of the four-wave Winograd kernels whose patch lies wholly inside its frame(s) leaves through the
+// fast exit, which tests no pixel (wino_tile.hpp: wino_exit_fast, wino_output); on = 0: every workgroup takes the general exit.  The
+// same outputs and GroupNorm records bit for bit; plans, images and the workspace do not change; the recorded graph is dropped.
+extern "C" int fpc_net_set_wino_fast_exit(fpc_net_t* n, int on) {
+    if (!n || on < 0 || on > 1) return FPC_EINVAL;
+    if (n->wino_fast_exit != on) drop_graph(n);
+    n->wino_fast_exit = on;
+    return FPC_OK;
+}
+
 // The h3 image of conv `ci` in the orientation the site runs in, and decoder d's fold images and bias table in s2.0's.
 static int pack_wino_h3_image(const fpc_net* n, int ci, hipStream_t s) {
     const PackedConv& c = n->convs[ci];
@@ -221,7 +231,7 @@ void fill_conv_args(const fpc_net* n, ConvArgs& a, const PackedConv& c, const Co
                     int Wo, long long sb, long long sh, long long sw, long long sc, bool relu, int mode) {
     fill_conv_shape(a, n->B, c, p, Hi, Wi, Ho, Wo, sb, sh, sw, sc, relu, mode);
     a.splitk_ws = n->ws + n->splitk_off; a.zeros = n->ws + n->zeros_off; a.tickets = (int*)(n->ws + n->tickets_off);
-    a.wino_pack = n->wino_pack; a.wino_orient = n->wino_orient; a.wino_rowsplit = n->wino_xshare ? 0 : 1;
+    a.wino_pack = n->wino_pack; a.wino_orient = n->wino_orient; a.wino_rowsplit = n->wino_xshare ? 0 : 1; a.wino_exit_general = n->wino_fast_exit ? 0 : 1;
 }
 
 

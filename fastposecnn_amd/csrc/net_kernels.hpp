@@ -56,6 +56,7 @@ struct ConvArgs {
     int wino_pack;                    // host side only: a form-9 launch may use the packed patch geometry (wino_pack_geometry)
     int wino_orient;                  // host side only: a form-9 launch runs transposed where wino_orient_rule says so (wino_launch_geometry)
     int wino_rowsplit;                // host side only: 1 = a packed form-9 launch keeps the row-split tile map where wino_xshare_rule offers the x-shared one
+    int wino_exit_general;            // host side only: 1 = every workgroup of a four-wave Winograd launch takes the general exit (wino_tile.hpp: wino_output)
     int cg;                           // host side only: > 0 = a grouped 3x3 site of Cin = Cout channels in groups of cg (conv_grouped.hip) ...
     const float* grp_w;               // ... and its k_pack_grouped image
 };
@@ -259,6 +260,9 @@ struct WinoArgs {
     // k_conv_wino_h3 only: 1 = the x-shared tile map (a lane's two tiles are neighbours in x: wino_tile.hpp, XS).  Packed launches
     // (pack > 1 or orient) whose (virtual) width has an even tile-column count only: conv_plan.hpp's wino_xshare_rule
     int xshare;
+    // wino_w4.hip, wino_h2.hip, wino_h3.hip: 1 = every workgroup takes the general exit, which tests each pixel against its frame
+    // (0: a workgroup whose patch lies wholly inside takes the fast one; the same results bit for bit: wino_tile.hpp, wino_output)
+    int exit_general;
     // wino_w4.hip, wino_h2.hip, wino_h3.hip: the reciprocals of the workgroup-id decode; the launchers fill them (callers leave them zero)
     WinoDecode dec;
 };
@@ -300,6 +304,9 @@ int wino_tile_frag(bool xs, int wi, int lane, int pk_ks, long long* out17);
 int wino_tile_slot(bool xs, bool tr, int slot, int y_in0, int x_in0, int H, int W, int Cs, int up, int pk_ks, int pk_two, long long* out6);
 int wino_tile_zrun(bool xs, int wi, int mt, int r, int nt, int cc, long long* out3);
 int wino_tile_zread(bool xs, int t_e, int tp, int cc, int i, long long* out1);
+// the exit: the patch decode with its fast-exit verdict, and a thread's 16 output offsets (fpc.h: fpc_wino_tile_patch, fpc_wino_tile_out)
+int wino_tile_patch(bool packed, int H, int W, int B, int tbx, int tby, int pack, int patch, long long* out8);
+int wino_tile_out(bool tr, int H, int W, int Cout, int nb, int b, int ty0, int tx0, int pk_ks, int t_e, long long* out16);
 // the fold's weights: wc = W . L (OIHW [Cout][Cmid -> Cin][3][3], f64 sums) and the bias table conv3x3(W, bias . 1_inside) per border
 // class (WinoArgs::btab); W [Cout][Cmid][3][3], L the 1x1 lateral [Cmid][Cin], bias [Cmid]
 int launch_wino_pack_h3_pair(const float* w1, float* packed1, int Cin1, const float* w2, float* packed2, int Cin2, int Cout, bool transpose,

@@ -346,7 +346,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
     }
     long long* const fdbg = (!(FOLD && PACK) && fine) ? dbg + (size_t)gridDim.x * 32 + ((size_t)blockIdx.x * 4 + wi) * 16 : nullptr;
     if (fdbg && lane == 0) { fdbg[0] = t_dec - t_entry; fdbg[1] = t_wld - t_entry; fdbg[2] = t_plan - t_entry; fdbg[3] = t_zero - t_entry; fdbg[4] = t_issued - t_entry; }
-    wino_output<PACK, FOLD, TR, XS>(lds, acc, P, pt, WinoEpi{H, W, Cout, a.relu, a.tbx, a.tby, a.pack_rx}, inv_s,
+    wino_output<PACK, FOLD, TR, XS>(lds, acc, P, pt, WinoEpi{H, W, Cout, a.relu, a.tbx, a.tby, a.pack_rx, a.exit_general}, inv_s,
                             wino_group(a.btab[0], a.btab[1], a.btab[2], a.btab[3], grp), dbg, t_kend, t, wi, fdbg);
 }
 
@@ -419,6 +419,27 @@ int wino_tile_zrun(bool xs, int wi, int mt, int r, int nt, int cc, long long* ou
 int wino_tile_zread(bool xs, int t_e, int tp, int cc, int i, long long* out1) {
     if (t_e < 0 || t_e > 255 || tp < 0 || tp > 3 || cc < 0 || cc > 1 || i < 0 || i > 3) return FPC_EINVAL;
     out1[0] = z_read_base(t_e >> 4, t_e & 15, xs) + z_read_step(tp, cc, i, xs);
+    return 0;
+}
+
+// the exit.  The patch decode of workgroup `patch` of a launch with one 64-channel block and one group, through wino_patch and the
+// launchers' own reciprocals, and whether it takes the fast exit
+int wino_tile_patch(bool packed, int H, int W, int B, int tbx, int tby, int pack, int patch, long long* out8) {
+    if (H < 1 || W < 1 || B < 1 || tbx < 1 || tby < 1 || patch < 0 || (packed && (pack < 1 || pack > B))) return FPC_EINVAL;
+    const WinoDecode dc = wino_decode(kBN, 1, tbx, tby, W, B, packed ? pack : 0);
+    const WinoPatch q = packed ? wino_patch<true>(patch, 1, 1, tbx, tby, pack, W, B, dc) : wino_patch<false>(patch, 1, 1, tbx, tby, 0, W, B, dc);
+    if (q.b >= B || q.by >= tby) return FPC_EINVAL;
+    const long long o[8] = {q.b, q.ty0, q.tx0, q.pk_ks, q.pk_two, q.by, q.bx, wino_exit_fast(H, W, q.ty0, q.tx0, q.pk_ks, q.pk_two)};
+    std::copy(o, o + 8, out8);
+    return 0;
+}
+// thread t_e's 16 output (and residual) element offsets, summed as wino_output sums them
+int wino_tile_out(bool tr, int H, int W, int Cout, int nb, int b, int ty0, int tx0, int pk_ks, int t_e, long long* out16) {
+    if (H < 1 || W < 1 || Cout < kBN || nb < 0 || b < 0 || ty0 < 0 || tx0 < 0 || pk_ks < 0 || t_e < 0 || t_e > 255) return FPC_EINVAL;
+    const WinoOut o = tr ? wino_out_base<true, true>(H, W, Cout, nb, b, ty0, tx0, pk_ks, t_e >> 4, t_e & 15)
+                         : wino_out_base<true, false>(H, W, Cout, nb, b, ty0, tx0, pk_ks, t_e >> 4, t_e & 15);
+    for (int tp = 0; tp < 4; ++tp)
+        for (int q = 0; q < 4; ++q) out16[4 * tp + q] = o.base + wino_out_step(o, tp, q >> 1, q & 1);
     return 0;
 }
 

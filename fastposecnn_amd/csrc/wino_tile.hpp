@@ -10,6 +10,7 @@
 // argument in scratch): the kernels sit at 512 registers, and their listings are the test of a change here (tools_dev/isa_stats.py).
 #pragma once
 #include <algorithm>
+#include <type_traits>
 #include "net_kernels.hpp"
 
 namespace fpc {
@@ -82,9 +83,9 @@ struct WinoPatch {
 };
 // Every divisor is a launch constant and every quotient is taken by the launch's reciprocals (dc, WinoRecip: n / d = (n * m) >> sh,
 // exact for 0 <= n < 2^31): the decode stands in front of the first load of the kernel, where nothing hides it.
-__device__ __forceinline__ int wino_div(int n, const WinoRecip r) { return (int)(((unsigned long long)(unsigned)n * r.m) >> r.sh); }
+__host__ __device__ __forceinline__ int wino_div(int n, const WinoRecip r) { return (int)(((unsigned long long)(unsigned)n * r.m) >> r.sh); }
 template <bool PACK>
-__device__ __forceinline__ WinoPatch wino_patch(int bid, int nnb, int groups, int tbx, int tby, int pack, int W, int B, const WinoDecode dc) {
+__host__ __device__ __forceinline__ WinoPatch wino_patch(int bid, int nnb, int groups, int tbx, int tby, int pack, int W, int B, const WinoDecode dc) {
     WinoPatch q;
     q.pk_ks = 99; q.pk_raw = 99; q.pk_slot = 0; q.pk_two = false;
     int up = wino_div(bid, dc.nnb);
@@ -100,8 +101,9 @@ __device__ __forceinline__ WinoPatch wino_patch(int bid, int nnb, int groups, in
     } else {
         const int G = pack, tcw = (W + 1) >> 1, per = tbx * tby;
         const int g = wino_div(bid, dc.per), rem = bid - g * per;
-        const int nf = min(G, B - g * G);                      // frames of this canvas row (a ragged last group has fewer,
-        const int tbxg = min(tbx, (nf * tcw + kTX - 1) / kTX); // and only the patches that reach them: dc.tbxl's divisor)
+        const int nf = G < B - g * G ? G : B - g * G;          // frames of this canvas row (a ragged last group has fewer,
+        const int tbxr = (nf * tcw + kTX - 1) / kTX;           // and only the patches that reach them: dc.tbxl's divisor)
+        const int tbxg = tbx < tbxr ? tbx : tbxr;
         q.by = wino_div(rem, tbxg == tbx ? dc.tbx : dc.tbxl); q.bx = rem - q.by * tbxg;
         const int f = wino_div(kTX * q.bx, dc.tcw);
         q.tx0 = kTX * q.bx - f * tcw;
@@ -267,38 +269,74 @@ __device__ __forceinline__ void wino_zero_ring(float* lds, int t, int nbuf, int 
 // ints, the fold kernel kept the struct in memory.)
 // TR: y, x, H, W below are the virtual image's (wino_stage_plan); the output and the residual are stored images: pixel (x, y), rows
 // of H pixels.  (The fold's border classes are the virtual image's too: k_fold_compose wrote the table for the transposed taps.)
-struct WinoEpi { int H, W, Cout, relu, tbx, tby, pack_rx; };
+// ADDRESSES.  A thread's 16 quads (tile pass tp, output row rr and column cc of its tile) differ by wave-uniform strides: one output
+// row (sy elements), one output column (sx), four tile rows = eight output rows per pass.  ONE 64-bit element offset per thread —
+// its tile of pass 0, row 0, column 0 — and quad (tp, rr, cc) lies (4 tp + rr) sy + cc sx further (wino_out_step: a scalar sum); the
+// residual's offset is the output's.  A seam patch has two frames and so two wave-uniform bases — frame b from tile column tx0, frame
+// b + 1 from tile column -ks — of which a thread selects its side's once.  64-bit sums throughout: no size limit of its own.
+struct WinoOut { long long base, sy, sx; };
+template <bool PACK, bool TR>
+__host__ __device__ __forceinline__ WinoOut wino_out_base(int H, int W, int Cout, int nb, int b, int ty0, int tx0, int pk_ks, int otl, int oq) {
+    const long long sy = (long long)(TR ? 1 : W) * Cout, sx = (long long)(TR ? H : 1) * Cout, frame = (long long)H * W * Cout;
+    const long long row = b * frame + 2 * ty0 * sy;
+    const long long s_near = row + 2 * tx0 * sx, s_far = row + frame - 2 * pk_ks * sx;
+    const bool far = PACK && (otl & 7) >= pk_ks;
+    return WinoOut{(far ? s_far : s_near) + (otl & 7) * (2 * sx) + (otl >> 3) * (2 * sy) + nb * kBN + oq * 4, sy, sx};
+}
+__host__ __device__ __forceinline__ long long wino_out_step(const WinoOut o, int tp, int rr, int cc) { return (4 * tp + rr) * o.sy + cc * o.sx; }
+// THE FAST EXIT is taken by a workgroup whose every pixel lies inside its frame in both axes (of the virtual image where the launch
+// is transposed), a seam patch's in both frames, the second of which exists: no quad of it is tested.  pk_ks >= 8: no seam.
+__host__ __device__ __forceinline__ bool wino_exit_fast(int H, int W, int ty0, int tx0, int pk_ks, bool pk_two) {
+    if (2 * (ty0 + kTY) > H) return false;
+    if (pk_ks >= kTX) return 2 * (tx0 + kTX) <= W;
+    return (pk_ks <= 0 || 2 * (tx0 + pk_ks) <= W) && pk_two && 2 * (kTX - pk_ks) <= W;
+}
+// general: every workgroup takes the general exit (fpc_net_set_wino_fast_exit, fpc_conv2d's FPC_PLAN_WINO_GENERAL_EXIT requests)
+struct WinoEpi { int H, W, Cout, relu, tbx, tby, pack_rx, general; };
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm"      // (the Z stores name m0 as clobbered)
 template <bool PACK, bool FOLD, bool TR = false, bool XS = false>
 __device__ __forceinline__ void wino_output(float* lds, const f32x16 (&acc)[4][2][2], const ConvPtrs P, const WinoPatch pt, const WinoEpi e,
                                             const float inv_s, const float* btab, long long* dbg, const long long t_kend, const int t,
                                             const int wi, long long* fdbg = nullptr) {
-    const int H = e.H, W = e.W, Cout = e.Cout, HW = H * W;
-    // (PACK: the thread's indices are rebuilt from the lane counter here instead of being carried over the K loop: the packed
-    // set-up needs a few registers more, and the allocator otherwise parks these in scratch from the set-up to the epilogue)
-    const int lane = PACK ? (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) : t & 63;
-    const int t_e = PACK ? wi * 64 + lane : t;
+    const int H = e.H, W = e.W, Cout = e.Cout;
+    // (the thread's indices are rebuilt from the lane counter here instead of being carried over the K loop: the allocator otherwise
+    // parks them, and whatever of the exit's addressing it can compute from them ahead of the loop, in scratch until the epilogue)
+    const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const int t_e = wi * 64 + lane;
     const int oq = t_e & 15, otl = t_e >> 4;                  // quad 0..15, tile 0..15 (+ 16 per tile pass)
     // (ot & 7 is the same in all four tile passes of a thread: it lies wholly on one side of a seam)
     const bool o_far = PACK && (otl & 7) >= pt.pk_ks;
-    const int ob = o_far ? pt.b + 1 : pt.b, otx = o_far ? (otl & 7) - pt.pk_ks : pt.tx0 + (otl & 7);
+    const int otx = o_far ? (otl & 7) - pt.pk_ks : pt.tx0 + (otl & 7);
     const bool o_ok = !o_far || pt.pk_two;
     const int n = pt.nb * kBN + oq * 4;
     const f32x4 e_sc = (!FOLD && P.scale) ? *reinterpret_cast<const f32x4*>(P.scale + n) : f32x4{1.f, 1.f, 1.f, 1.f};
     const f32x4 e_sh = (!FOLD && P.shift) ? *reinterpret_cast<const f32x4*>(P.shift + n) : f32x4{0.f, 0.f, 0.f, 0.f};
     // the residual of this thread's 4 x 4 outputs is requested BEFORE the output transform's barriers (one workgroup per CU: nothing
     // else hides that latency; k_conv_wino does the same)
+    // (wave-uniform, all of them: the epilogue's parts and the exit path are chosen by scalar branches, once per workgroup)
+    const bool has_sc = !FOLD && P.scale, has_res = !FOLD && P.res, has_relu = !FOLD && e.relu, has_gn = P.gn_part != nullptr;
+    const bool fastp = !e.general && wino_exit_fast(H, W, pt.ty0, pt.tx0, PACK ? pt.pk_ks : 99, pt.pk_two);
+    const WinoOut oa = wino_out_base<PACK, TR>(H, W, Cout, pt.nb, pt.b, pt.ty0, pt.tx0, pt.pk_ks, otl, oq);
+    const int oy0 = 2 * (pt.ty0 + (otl >> 3)), ox0 = 2 * otx;      // quad (tp, rr, cc): pixel (oy0 + 4 tp + rr, ox0 + cc)
     f32x4 e_res[4][4];
+    if (has_res && fastp) {
+        const float* const rp = P.res + oa.base;
 #pragma unroll
-    for (int tp = 0; tp < 4; ++tp)
+        for (int tp = 0; tp < 4; ++tp) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int ot = otl + 16 * tp;
-            const int y = 2 * (pt.ty0 + (ot >> 3)) + (q >> 1), x = 2 * otx + (q & 1);
-            e_res[tp][q] = (!FOLD && P.res && o_ok && y < H && x < W) ? *reinterpret_cast<const f32x4*>(P.res + ((size_t)ob * HW + (TR ? (size_t)x * H + y : (size_t)y * W + x)) * Cout + n)
-                                                             : f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int q = 0; q < 4; ++q) e_res[tp][q] = *reinterpret_cast<const f32x4*>(rp + wino_out_step(oa, tp, q >> 1, q & 1));
+            __builtin_amdgcn_sched_barrier(0);      // (a pass's four sums at a time: all 16 ahead of the loads cost 32 registers the accumulators need)
         }
+    } else if (!fastp) {
+        const float* const rp = P.res + oa.base;
+#pragma unroll
+        for (int tp = 0; tp < 4; ++tp)
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                e_res[tp][q] = (has_res && o_ok && oy0 + 4 * tp + (q >> 1) < H && ox0 + (q & 1) < W) ? *reinterpret_cast<const f32x4*>(rp + wino_out_step(oa, tp, q >> 1, q & 1))
+                                                                                                 : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
     __syncthreads();
     // (fdbg: the exit's phases in a diagnostic build, ticks since the K loop's end: words 8 .. 12 of the wave's 16-word record)
     if (kWinoStamp && fdbg && (t & 63) == 0) fdbg[8] = clock64() - t_kend;      // first barrier passed
@@ -345,10 +383,21 @@ __device__ __forceinline__ void wino_output(float* lds, const f32x16 (&acc)[4][2
     f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
     // this thread's quad of its tile of pass 0, row 0, cc 0
     const float* const zr = lds + z_read_base(otl, oq, XS) / 4;
+    // (the base through an empty asm: the compiler otherwise keeps the residual prefetch's 16 sums, 32 registers, for the stores
+    // across the Z stores, where the accumulators leave it none to spare)
+    long long obase = oa.base;
+    asm volatile("" : "+v"(obase));
+    float* const op = P.out + obase;
+    // The 16 quads.  FAST: the workgroup's fast exit — no test of a pixel, and the epilogue's parts are compile-time (the caller has
+    // branched on them); otherwise the general exit, every quad tested against its frame, the parts by their run-time flags.  Either
+    // way every value is the same sum of the same terms in the same order, and so are the GroupNorm sums (quads in (tp, rr, cc)
+    // order; a launch without records accumulates none).
+    auto quads = [&](auto fast_c, auto sc_c, auto res_c, auto relu_c, auto gn_c) __attribute__((always_inline)) {
+    constexpr bool FAST = decltype(fast_c)::value;
+    const bool do_sc = FAST ? decltype(sc_c)::value : has_sc, do_res = FAST ? decltype(res_c)::value : has_res;
+    const bool do_relu = FAST ? decltype(relu_c)::value : has_relu, do_gn = FAST ? decltype(gn_c)::value : has_gn;
 #pragma unroll
     for (int tp = 0; tp < 4; ++tp) {
-        const int ot = otl + 16 * tp;
-        const int oty = pt.ty0 + (ot >> 3);
         f32x4 z[4][2];
         // tile ot = otl + 16 tp of the Z image: mt = tp >> 1, r = (otl & 3) + 4 ((otl >> 3) + 2 (tp & 1)), writer half (otl >> 2) & 1
         // (XS: mt = otl & 1, r = ((otl >> 1) & 3) + 4 tp, writer half otl >> 3)
@@ -360,22 +409,37 @@ __device__ __forceinline__ void wino_output(float* lds, const f32x16 (&acc)[4][2
         for (int rr = 0; rr < 2; ++rr)
 #pragma unroll
             for (int cc = 0; cc < 2; ++cc) {
-                const int y = 2 * oty + rr, x = 2 * otx + cc;
-                if (y >= H || x >= W || !o_ok) continue;
+                const int y = oy0 + 4 * tp + rr, x = ox0 + cc;
+                if (!FAST && (y >= H || x >= W || !o_ok)) continue;
                 f32x4 val = (rr == 0 ? z[0][cc] + z[1][cc] + z[2][cc] : z[1][cc] - z[2][cc] - z[3][cc]) * inv_s;      // (a power of two: exact)
                 if (FOLD) {
                     const int cls = (((y == 0) | ((y == H - 1) << 1)) << 2) | (x == 0) | ((x == W - 1) << 1);
                     val += *reinterpret_cast<const f32x4*>(btab + (size_t)cls * Cout + n);
                 }
-                if (!FOLD && P.scale) val = val * e_sc;
+                if (do_sc) val = val * e_sc;
                 val = val + e_sh;
-                const size_t o = ((size_t)ob * HW + (TR ? (size_t)x * H + y : (size_t)y * W + x)) * Cout + n;
-                if (!FOLD && P.res) val += e_res[tp][2 * rr + cc];
-                if (!FOLD && e.relu) { val[0] = fmaxf(val[0], 0.f); val[1] = fmaxf(val[1], 0.f); val[2] = fmaxf(val[2], 0.f); val[3] = fmaxf(val[3], 0.f); }
-                *reinterpret_cast<f32x4*>(P.out + o) = val;
-                s1 += val;
-                s2 += val * val;
+                if (do_res) val += e_res[tp][2 * rr + cc];
+                if (do_relu) { val[0] = fmaxf(val[0], 0.f); val[1] = fmaxf(val[1], 0.f); val[2] = fmaxf(val[2], 0.f); val[3] = fmaxf(val[3], 0.f); }
+                *reinterpret_cast<f32x4*>(op + wino_out_step(oa, tp, rr, cc)) = val;
+                if (do_gn) { s1 += val; s2 += val * val; }
             }
+    }
+    };      // quads
+    {
+        const std::true_type yes;
+        const std::false_type no;
+        // one scalar branch per part, outside the 16 quads (the fold has no part but the records: launch_conv_wino_h3)
+        auto part = [](bool c, auto f) __attribute__((always_inline)) { if (c) f(std::true_type()); else f(std::false_type()); };
+        if (!fastp) quads(no, no, no, no, no);
+        else if constexpr (FOLD) part(has_gn, [&](auto gn_c) __attribute__((always_inline)) { quads(yes, no, no, no, gn_c); });
+        else
+            part(has_sc, [&](auto sc_c) __attribute__((always_inline)) {
+                part(has_res, [&](auto res_c) __attribute__((always_inline)) {
+                    part(has_relu, [&](auto relu_c) __attribute__((always_inline)) {
+                        part(has_gn, [&](auto gn_c) __attribute__((always_inline)) { quads(yes, sc_c, res_c, relu_c, gn_c); });
+                    });
+                });
+            });
     }
     if (kWinoStamp && fdbg && (t & 63) == 0) fdbg[11] = clock64() - t_kend;      // reads, epilogue, last store issued
     if (PACK && P.gn_part) {

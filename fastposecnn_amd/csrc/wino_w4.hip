@@ -245,7 +245,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_w4(const WinoArgs a) {
         o[0] = 0; o[1] = 0; o[2] = 0;
         o[3] = t_kend - c_begin; o[4] = wall_clock64() - r_begin; o[5] = nkb; o[6] = c_begin - t_entry;
     }
-    wino_output<false, false>(lds, acc, P, pt, WinoEpi{H, W, Cout, a.relu, a.tbx, a.tby, 0}, 1.0f, nullptr, dbg, t_kend, t, wi);
+    wino_output<false, false>(lds, acc, P, pt, WinoEpi{H, W, Cout, a.relu, a.tbx, a.tby, 0, a.exit_general}, 1.0f, nullptr, dbg, t_kend, t, wi);
 }
 
 // .w = the k_wino_pack_bf3 image (as variant 3 of launch_conv_wino), .waves = 8 (tby = ceil(ceil(H / 2) / 8): 8 x 8 tile patches)

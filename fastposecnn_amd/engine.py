@@ -205,6 +205,11 @@ class NetEngine:
         library's default) or the row-split map everywhere (on = 0).  The same results bit for bit; plans and images do not change."""
         nat.check(self._lib.fpc_net_set_wino_xshare(self._h, int(on)), "fpc_net_set_wino_xshare")
 
+    def set_wino_fast_exit(self, on):
+        """Workgroups of the four-wave Winograd kernels whose patch lies wholly inside its frame leave through the fast exit, which
+        tests no pixel (on = 1, the library's default), or all through the general one (on = 0).  The same results bit for bit."""
+        nat.check(self._lib.fpc_net_set_wino_fast_exit(self._h, int(on)), "fpc_net_set_wino_fast_exit")
+
     def wino_blocks(self):
         """Workgroups of all form-9 launches of the last forward that launched its kernels."""
         return int(self._lib.fpc_net_wino_blocks(self._h))

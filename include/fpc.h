@@ -67,6 +67,7 @@ extern "C" {
  * and the gradients of its depthwise convolution for the training step (fpc_mbconv_dw_dgrad, fpc_mbconv_dw_wgrad and its _workspace_bytes):
  * and the DenseNet-121 / 169 / 201 encoders (fpc_net_create's "densenet121" / "densenet169" / "densenet201", fpc_dense_pw, fpc_dense_pw_form,
  *   fpc_dense_conv3x3, fpc_dense_conv3x3_pack, fpc_dense_conv3x3_form, fpc_dense_norm_pool, fpc_dense_place):
+ * and the exit of the four-wave Winograd kernels (fpc_net_set_wino_fast_exit, fpc_wino_tile_patch, fpc_wino_tile_out, fpc_conv2d's -107 .. -113):
  * additions only, every earlier entry point keeps its behaviour. */
 #define FPC_ABI_VERSION 11
 
@@ -755,6 +756,22 @@ int fpc_wino_tile_frag(int xshare, int wi, int lane, int pk_ks, int64_t* out17);
 int fpc_wino_tile_slot(int xshare, int tr, int slot, int y_in0, int x_in0, int H, int W, int Cs, int up, int pk_ks, int pk_two, int64_t* out6);
 int fpc_wino_tile_zrun(int xshare, int wi, int mt, int r, int nt, int cc, int64_t* out3);
 int fpc_wino_tile_zread(int xshare, int t_e, int tp, int cc, int i, int64_t* out1);
+/* The EXIT of the four-wave Winograd kernels (forms -7, -8, -9 and what -10 .. -13 make of -9).  A thread addresses its 16 output
+ * quads (and the residual's, the same) from ONE 64-bit element offset — its tile of pass 0, row 0, column 0; a seam patch has one
+ * base per frame, of which a thread takes its side's — plus wave-uniform strides: quad (tp, rr, cc) lies (4 tp + rr) rows and cc
+ * columns further.  A workgroup whose patch lies wholly inside its frame in both axes (a seam patch: inside both frames, the second
+ * of which exists) takes the FAST exit, which tests no pixel; every other the general one.  Outputs and GroupNorm records are the
+ * same bit for bit.  fpc_net_set_wino_fast_exit: on = 1 (default) / 0 = every workgroup takes the general exit; drops the recorded
+ * graph.  fpc_conv2d's FPC_PLAN_WINO_GENERAL_EXIT + r (-107 .. -113) is request r = -7 .. -13 with every workgroup on the general exit.
+ * fpc_wino_tile_patch (host only): patch `patch` (the workgroup id of a launch of one 64-channel block and one group) of a launch on a
+ * (virtual) H x W image of B frames with tbx x tby patches per canvas row, `pack` frames per canvas row (packed = 0: the plain
+ * decode, one frame per patch row; pack is then ignored): out8 = {frame b, first tile row ty0, first tile column tx0, seam after
+ * that many tile columns (99: none), the frame behind the seam exists, patch row, patch column, takes the fast exit}.
+ * fpc_wino_tile_out (host only): the element offsets of thread t_e's 16 quads, out16[4 tp + 2 rr + cc], as the kernels add them up,
+ * for the patch (b, ty0, tx0, pk_ks) of 64-channel block nb on a (virtual; tr = 1: transposed) H x W image of Cout channels. */
+int fpc_net_set_wino_fast_exit(fpc_net_t* net, int on);
+int fpc_wino_tile_patch(int packed, int H, int W, int B, int tbx, int tby, int pack, int patch, int64_t* out8);
+int fpc_wino_tile_out(int tr, int H, int W, int Cout, int nb, int b, int ty0, int tx0, int pk_ks, int t_e, int64_t* out16);
 /* Workgroups of all form-9 launches of the last forward that launched (or captured) its kernels: what the switch above changes. */
 int64_t fpc_net_wino_blocks(const fpc_net_t* net);
 /* FLOP of one forward over the batch under the current plans: out3 = {2 x MACs of the direct convolutions (what the
@@ -781,6 +798,7 @@ int fpc_net_tensor(const fpc_net_t* net, const char* name, const float** ptr, in
  * implicit GEMM with split-K factor k on two fp16 pieces per operand and three piece products (channel stride 1, Cin a multiple
  * of 32; 6100 + k: split-K summed by a second launch), 7000 + parts the pixel-resident FPN lateral product on the same two pieces.  5000 is never a request: fpc_net_conv_plan's "folded away". */
 enum {      /* the bases of those codes, as fpc_net_conv_plan reports them and fpc_conv2d takes them (a Winograd form: -form) */
+    FPC_PLAN_WINO_GENERAL_EXIT = -100,      /* + r, r = -7 .. -13: request r with every workgroup on the general exit (never reported) */
     FPC_PLAN_WINO_ORIENT_ROWSPLIT = -13, FPC_PLAN_WINO_PACKED_ROWSPLIT = -12,      /* -11 / -10 on the row-split tile map (fpc_wino_xshare_rule) */
     FPC_PLAN_WINO_ORIENT = -11, FPC_PLAN_WINO_PACKED = -10, FPC_PLAN_TWO_LAUNCH = 100, FPC_PLAN_BF3 = 1000, FPC_PLAN_LATERAL = 2000, FPC_PLAN_STEM = 3000,
     FPC_PLAN_STEM_POOL = 3100, FPC_PLAN_POINTWISE = 4000, FPC_PLAN_FOLDED = 5000, FPC_PLAN_H3 = 6000, FPC_PLAN_LATERAL_H3 = 7000,
