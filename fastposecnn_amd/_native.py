@@ -113,6 +113,7 @@ _SIGNATURES = {
     "fpc_wino_xshare_rule": (_i, [_i]),
     "fpc_net_set_wino_xshare": (_i, [_vp, _i]),
     "fpc_net_set_wino_fast_exit": (_i, [_vp, _i]),
+    "fpc_net_set_fold_idle_row": (_i, [_vp, _i]),
     "fpc_wino_tile_patch": (_i, [_i] * 8 + [ctypes.POINTER(_i64)]),
     "fpc_wino_tile_out": (_i, [_i] * 10 + [ctypes.POINTER(_i64)]),
     "fpc_wino_tile_frag":(_i, [_i, _i, _i, _i, ctypes.POINTER(_i64)]),

@@ -98,6 +98,7 @@ int launch_conv_plan(ConvArgs& a, const ConvPlan& p, int groups, hipStream_t s) 
                 w.p[g].in = a.fold_in; w.p[g].w = a.fold_w[g];
             }
             w.fold = 1; w.Cin2 = a.Cin; w.Cin = a.fold_cin;
+            w.all_rows = a.wino_fold_all_rows ? 1 : 0;
         }
         return f.launch(w, groups, s);
     }

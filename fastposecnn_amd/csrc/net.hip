@@ -95,6 +95,16 @@ extern "C" int fpc_net_set_wino_fast_exit(fpc_net_t* n, int on) {
     return FPC_OK;
 }
 
+// on = 1 (the default): in phase 2 of the folded s2.0 (wino_h3.hip, FOLD) the wave of the zero transform row only stages its pieces;
+// on = 0: every wave runs the phase.  The same outputs and GroupNorm records bit for bit on finite operands; plans, images and the
+// workspace do not change; the recorded graph is dropped.
+extern "C" int fpc_net_set_fold_idle_row(fpc_net_t* n, int on) {
+    if (!n || on < 0 || on > 1) return FPC_EINVAL;
+    if (n->fold_idle_row != on) drop_graph(n);
+    n->fold_idle_row = on;
+    return FPC_OK;
+}
+
 // The h3 image of conv `ci` in the orientation the site runs in, and decoder d's fold images and bias table in s2.0's.
 static int pack_wino_h3_image(const fpc_net* n, int ci, hipStream_t s) {
     const PackedConv& c = n->convs[ci];
@@ -232,6 +242,7 @@ void fill_conv_args(const fpc_net* n, ConvArgs& a, const PackedConv& c, const Co
     fill_conv_shape(a, n->B, c, p, Hi, Wi, Ho, Wo, sb, sh, sw, sc, relu, mode);
     a.splitk_ws = n->ws + n->splitk_off; a.zeros = n->ws + n->zeros_off; a.tickets = (int*)(n->ws + n->tickets_off);
     a.wino_pack = n->wino_pack; a.wino_orient = n->wino_orient; a.wino_rowsplit = n->wino_xshare ? 0 : 1; a.wino_exit_general = n->wino_fast_exit ? 0 : 1;
+    a.wino_fold_all_rows = n->fold_idle_row ? 0 : 1;
 }
 
 

@@ -57,6 +57,7 @@ struct ConvArgs {
     int wino_orient;                  // host side only: a form-9 launch runs transposed where wino_orient_rule says so (wino_launch_geometry)
     int wino_rowsplit;                // host side only: 1 = a packed form-9 launch keeps the row-split tile map where wino_xshare_rule offers the x-shared one
     int wino_exit_general;            // host side only: 1 = every workgroup of a four-wave Winograd launch takes the general exit (wino_tile.hpp: wino_output)
+    int wino_fold_all_rows;           // host side only: 1 = every wave of the folded s2.0 runs phase 2 (0: the wave of the zero transform row only stages there, wino_h3.hip)
     int cg;                           // host side only: > 0 = a grouped 3x3 site of Cin = Cout channels in groups of cg (conv_grouped.hip) ...
     const float* grp_w;               // ... and its k_pack_grouped image
 };
@@ -265,6 +266,9 @@ struct WinoArgs {
     int exit_general;
     // wino_w4.hip, wino_h2.hip, wino_h3.hip: the reciprocals of the workgroup-id decode; the launchers fill them (callers leave them zero)
     WinoDecode dec;
+    // k_conv_wino_h3 only, fold = 1: 1 = every wave runs phase 2 (0: the wave of the zero transform row only stages there; the same
+    // results bit for bit on finite operands: wino_h3.hip)
+    int all_rows;
 };
 int launch_conv_wino(const WinoArgs& a, int groups, hipStream_t s);
 const float* zero_page();      // 64 zero floats in the code object (per device context), or null

@@ -184,6 +184,7 @@ struct fpc_net {
     int wino_orient = 1;          // form-9 launches run transposed at the sites wino_orient_rule names (fpc_net_set_wino_orient)
     int wino_xshare = 1;          // packed form-9 launches use the x-shared tile map where wino_xshare_rule offers it (fpc_net_set_wino_xshare)
     int wino_fast_exit = 1;       // workgroups of the four-wave Winograd kernels take the fast exit where their patch lies inside (fpc_net_set_wino_fast_exit)
+    int fold_idle_row = 1;        // the wave of the zero transform row only stages in phase 2 of the folded s2.0 (fpc_net_set_fold_idle_row)
     std::vector<char> c_tr;       // 1: the conv is a form-9 candidate at a shape the rule transposes (every decoder's; its h3 image follows wino_orient)
     int split_precision = 0;      // autotuning may pick the bf16 x 3 form of a direct convolution (fpc_net_set_split_precision)
     hipGraphExec_t graph_exec = nullptr;

@@ -62,8 +62,22 @@ __device__ __forceinline__ const float* sgpr_ptr(const float* p) {
 // UPSAMPLED image straight from p3 (each lane's DMA address is its low-resolution pixel): a tile's input rows 2i-1 .. 2i+2 are then
 // the low-resolution rows [a, b, b, c], and B^T [a, b, b, c] = [a-b, 2b, 0, b-c] with an exact 0 in floating point.  Transform row 2
 // and column 2 are zero: every wave skips its xi column 2 in phase 2 (operands, weight loads, matrix instructions), 36 of 48 matrix
-// instructions per pair.  Wave 2's row is zero too, but it still runs the loop (its products add exact zeros): a branch that gave it
-// only the staging made the compiler spill ~1 KB per wave at the phase boundary.
+// instructions per pair.  Row 2 is wave 2's: in phase 2 that wave only STAGES (its share of the ring zeroing, its five pieces per
+// K-step, the waits for them, every barrier) and loads no weights, reads no fragments, transforms, splits and multiplies nothing
+// (a.all_rows = 1: it runs the phase on its zeros as before; fpc_net_set_fold_idle_row).  Its accumulators keep phase 1's sums: the
+// dropped products were +-0, and an accumulator that started from +0 is never -0, so no bit of any output changes for finite p3 (a
+// non-finite p3 value made NaN in that row, inf - inf, and no longer does).  How the branch is written matters at 512 registers:
+//   - ONE instance of the loop, the condition made inside it from an opaque scalar: unswitched, the second instance spilled
+//     ~1 KB per wave at the phase boundary;
+//   - if-then only, never if-else: the structuriser turns a diamond, uniform or not, into Flow blocks whose phis carry every
+//     loop-carried register on a poison edge, the coalescer gives up and ~300 scratch instructions land in the loop;
+//   - one guarded block per pair, so phase 2 issues its staging burst IN FRONT of the fragment reads (phase 1 and the other
+//     kernels keep it behind them): with the reads guarded apart from the rest, 5 to 8 accumulator registers are spilled across
+//     the phase;
+//   - the entry's weight loads pinned in program order in the fold kernels: the counted waits in front of the loop's matrix
+//     instructions merge the entry's order with the loop's, and a scheduler that moves the first load behind eight others makes
+//     vmcnt(11) a vmcnt(3), which waits for staging pieces issued a moment ago (+4 % on the kernel).
+// profiles/fold_idle_row_ledger.md has the listings and the measurements.
 //
 // PACK: the patches are cut out of a canvas of a.pack frames side by side and a patch may carry a SEAM (wino_tile.hpp: wino_patch,
 // wino_stage_plan).  Only the set-up and the epilogue know about it; the K loop is the plain one.
@@ -101,6 +115,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
     float inv_s = 1.f;        // 1 / (the power of two the weights of the LAST phase were scaled by)
     long long t_issued = 0, t_landed = 0, t_synced = 0, c_begin = 0, r_begin = 0;
     const bool stamp = dbg != nullptr;      // (the loop below never names `a`: a reference to the kernel argument puts it in scratch)
+    const int all_rows = a.all_rows;
 
     // The K loop over one input image `src` (Cs channels; up = 1: read as its nearest-x2 upsample) on the weight image `wimg`.
     // PH 0: the whole loop (acc zeroed first); 1: fold phase 2 (xi column 2 skipped).  Every phase ends after a barrier with no
@@ -108,6 +123,11 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
     auto kloop = [&](auto ph, const float* src, const float* wimg, const int Cs, const int up) __attribute__((always_inline)) {
     constexpr int PH = decltype(ph)::value;
     constexpr bool SKIPC = PH == 1;
+    // fold phase 2: transform row 2 is zero like column 2, and row 2 is wave 2's.  That wave only stages (its pieces wi + 4 i have no
+    // other owner) and keeps every barrier; it loads no weights, reads no fragments and issues no transform, split or matrix
+    // instruction — its accumulators keep phase 1's sums, to which the dropped products would have added +-0 (a.all_rows: it runs)
+    int live = 1;
+    if constexpr (PH == 1) live = __builtin_amdgcn_readfirstlane(all_rows | (wi ^ 2));
     const int nkb = Cs >> 3;
     const int npair = nkb >> 1;      // (the launcher refuses an odd number of K-steps)
     // ---- weights: buffer loads of this wave's fragments, per pair of K-steps one 16-byte B1 = {g1 even, g1 odd} and one B2 = {g2 even,
@@ -117,6 +137,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
     const int vo_u = lane * 16;
     int so_u = wi * 4 * 4096;      // this wave's four xi; + kPairBytes per pair
     u32x4 U1[4][2], U2[4][2];
+    if (live) {
     // (a fold phase 2 loads no fragment of xi column 2: 12 weight loads per pair instead of 16)
 #define FPC_H3_XI_LIVE(J) (!(SKIPC && (J) == 2))
 #define FPC_H3_LOAD_U1_AT(SO, J, NT) do { if (FPC_H3_XI_LIVE(J)) U1[J][NT] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_w, vo_u, (SO) + (J) * 4096 + (NT) * 2048, 0)); } while (0)
@@ -126,8 +147,15 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
-        for (int nt = 0; nt < 2; ++nt) { FPC_H3_LOAD_U1(j, nt); FPC_H3_LOAD_U2(j, nt); }
+        for (int nt = 0; nt < 2; ++nt) {
+            FPC_H3_LOAD_U1(j, nt); FPC_H3_LOAD_U2(j, nt);
+            // (the fold kernels: the loads keep this order, the oldest first in the loop's order of use — the counted waits in front of
+            // the loop's matrix instructions are made from it; one moved behind eight others turns vmcnt(11) into vmcnt(3), which
+            // waits for the staging pieces issued a moment ago)
+            if constexpr (FOLD) __builtin_amdgcn_sched_barrier(0);
+        }
     if (npair > 1) so_u += kPairBytes;
+    }
     if (PH == 0) t_wld = fine ? clock64() : 0;
 
     // ---- input staging and fragment addressing (wino_tile.hpp)
@@ -166,7 +194,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
                     if (PH == 0) acc[j][mt][nt][r] = 0.f;
 
     t_issued = stamp ? clock64() : 0;
-    asm volatile("s_waitcnt vmcnt(10)" ::: "memory");      // the weight fragments and step 0 (steps 1, 2 land under step 0's transform)
+    asm volatile("s_waitcnt vmcnt(10)" ::: "memory");      // the weight fragments and step 0 (steps 1, 2 land under step 0's transform; the weights are issued first: right without them too)
     t_landed = stamp ? clock64() : 0;
     __syncthreads();
     t_synced = stamp ? clock64() : 0;
@@ -194,6 +222,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
         asm volatile("" :: "v"(k1_), "v"(k2_));                                                               \
         TA1[J][MT][2 * (HALF) + (PAIR)] = k1_; TA2[J][MT][2 * (HALF) + (PAIR)] = k2_;                         \
     } while (0)
+    if (live) {
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -211,6 +240,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
             for (int j = 0; j < 3; ++j) { FPC_H3_SPLIT_PAIR(j, mt, 0, 0); FPC_H3_SPLIT_PAIR(j, mt, 1, 0); }
         }
     }
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // steps 1 and 2
     __syncthreads();       // everybody's have landed; buffer 0 is refilled by the pieces of step 4, issued at the top of pair 0
 
@@ -220,12 +250,25 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
     c_begin = stamp ? clock64() : 0; r_begin = stamp ? wall_clock64() : 0;
 #pragma unroll 1
     for (int p = 0; p < npair; ++p) {
+        // `live` again, made inside the loop from a scalar the compiler cannot see through: ONE instance of the loop serves both kinds
+        // of wave (unswitched, the second instance spilled ~1 KB per wave at the phase boundary)
+        bool lv = true;
+        if constexpr (PH == 1) {
+            int lv_;
+            asm volatile("s_mov_b32 %0, %1" : "=s"(lv_) : "s"(live));
+            lv = lv_ != 0;
+        }
         // ---- E: step 2p + 1's fragment reads and transform; the odd halves of xi 0 (xi 1-3 follow behind O's first matrix instructions).
         // No matrix instruction is in flight behind the barrier: plain code, the sixteen fragment reads issued together.
         {
             // the sixteen fragment reads first: 64 KB per workgroup = 512 cycles of the LDS pipe, under the staging burst and xi 3's split
             const float* InE = lds + ((2 * p + 1) & 3) * kInFloats;
             f32x4 ea[kNC], eb[kNC];
+#define FPC_H3_STAGE_PAIR() do { if (sn < nkb) { FPC_H3_ISSUE_IN((sn & 3), isb); isb += 8; }                  \
+                                 if (sn + 1 < nkb) { FPC_H3_ISSUE_IN(((sn + 1) & 3), isb); isb += 8; }        \
+                                 sn += 2; } while (0)
+            if constexpr (PH == 1) FPC_H3_STAGE_PAIR();
+            if (lv) {      // (to the end of O)
 #pragma unroll
             for (int x = 0; x < kNC; ++x) {
                 ea[x] = *reinterpret_cast<const f32x4*>(InE + FPC_H3_FA(x));
@@ -235,12 +278,11 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
             // inputs of steps 2p + 3 and 2p + 4 -> the buffers steps 2p - 1 and 2p were read from before the last barrier
             // (a step past the last is not staged: the end-of-pair wait counts the sixteen weight loads BEHIND the pieces, so fewer
             // pieces in front of them keep it exact)
-            if (sn < nkb) { FPC_H3_ISSUE_IN((sn & 3), isb); isb += 8; }
-            if (sn + 1 < nkb) { FPC_H3_ISSUE_IN(((sn + 1) & 3), isb); isb += 8; }
-            sn += 2;
+            if constexpr (PH == 0) FPC_H3_STAGE_PAIR();
 #pragma unroll
             for (int q = 0; q < 4; ++q) FPC_H3_SPLIT_Q(3, q, 0);      // xi 3 of step 2p: its operands were in use until the end of O
             __builtin_amdgcn_sched_barrier(0);
+            {
             f32x4 e[kNC];
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt) {
@@ -250,7 +292,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
                 for (int j = 0; j < 4; ++j) vn[mt][j] = FPC_H3_COLUMN(e, mt, j);
                 FPC_H3_SPLIT_PAIR(0, mt, 0, 1); FPC_H3_SPLIT_PAIR(0, mt, 1, 1);
             }
-        }
+            }
         __builtin_amdgcn_sched_barrier(0);
         // ---- O: the pair's 48 matrix instructions; slot sl = 12 j + 4 g + 2 mt + nt, g = 0: A1 B1, 1: A2 B1, 2: A1 B2.  One item per slot:
         //   sl  0- 3  fragment reads of step 2p + 2       sl  4-11  row transform e (XS: 6-11)       sl 12-19  column transform vn
@@ -310,6 +352,9 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
         // this wave's ten pieces (issued before the pair's 16 weight loads, which stay in flight) have landed
         if (PH == 0) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
         if (PH == 1) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+        }
+        }
+        if (!lv) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (a wave that loads no weights has only its pieces in flight)
         __syncthreads();                                       // everybody's have; this pair's fragment reads are done
     }
 #undef FPC_H3_MFMA
@@ -317,6 +362,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
 #undef FPC_H3_SPLIT_PAIR_V
 #undef FPC_H3_SPLIT_Q
 #undef FPC_H3_PIN4
+#undef FPC_H3_STAGE_PAIR
 #undef FPC_H3_ISSUE_IN
 #undef FPC_H3_LOAD_U1
 #undef FPC_H3_LOAD_U2

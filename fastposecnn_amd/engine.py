@@ -210,6 +210,11 @@ class NetEngine:
         tests no pixel (on = 1, the library's default), or all through the general one (on = 0).  The same results bit for bit."""
         nat.check(self._lib.fpc_net_set_wino_fast_exit(self._h, int(on)), "fpc_net_set_wino_fast_exit")
 
+    def set_fold_idle_row(self, on):
+        """In the p3 phase of the folded s2.0 the wave of the zero transform row only stages its share of the input (on = 1, the
+        library's default), or runs the phase on its zeros like the other three (on = 0).  The same results bit for bit."""
+        nat.check(self._lib.fpc_net_set_fold_idle_row(self._h, int(on)), "fpc_net_set_fold_idle_row")
+
     def wino_blocks(self):
         """Workgroups of all form-9 launches of the last forward that launched its kernels."""
         return int(self._lib.fpc_net_wino_blocks(self._h))

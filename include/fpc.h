@@ -68,6 +68,7 @@ extern "C" {
  * and the DenseNet-121 / 169 / 201 encoders (fpc_net_create's "densenet121" / "densenet169" / "densenet201", fpc_dense_pw, fpc_dense_pw_form,
  *   fpc_dense_conv3x3, fpc_dense_conv3x3_pack, fpc_dense_conv3x3_form, fpc_dense_norm_pool, fpc_dense_place):
  * and the exit of the four-wave Winograd kernels (fpc_net_set_wino_fast_exit, fpc_wino_tile_patch, fpc_wino_tile_out, fpc_conv2d's -107 .. -113):
+ * and the idle wave of the folded s2.0's second phase (fpc_net_set_fold_idle_row):
  * additions only, every earlier entry point keeps its behaviour. */
 #define FPC_ABI_VERSION 11
 
@@ -770,6 +771,13 @@ int fpc_wino_tile_zread(int xshare, int t_e, int tp, int cc, int i, int64_t* out
  * fpc_wino_tile_out (host only): the element offsets of thread t_e's 16 quads, out16[4 tp + 2 rr + cc], as the kernels add them up,
  * for the patch (b, ty0, tx0, pk_ks) of 64-channel block nb on a (virtual; tr = 1: transposed) H x W image of Cout channels. */
 int fpc_net_set_wino_fast_exit(fpc_net_t* net, int on);
+/* The folded s2.0 (form 9 with the FPN p2 level folded in) reads p3 in its second phase as its nearest x2 upsample: a tile's input
+ * rows are the low-resolution rows [a, b, b, c], whose transform B^T [a, b, b, c] = [a - b, 2b, 0, b - c] has an exact zero in row
+ * 2, the row of one of the workgroup's four waves.  on = 1 (default): that wave only stages its share of the input in that phase;
+ * on = 0: it runs the phase on its zeros as the other three do on their rows.  Outputs and GroupNorm records are the same bit for
+ * bit for finite p3 (a non-finite value times the zero row made NaN with on = 0 and does not with on = 1); plans, images and the
+ * workspace do not change; drops the recorded graph. */
+int fpc_net_set_fold_idle_row(fpc_net_t* net, int on);
 int fpc_wino_tile_patch(int packed, int H, int W, int B, int tbx, int tby, int pack, int patch, int64_t* out8);
 int fpc_wino_tile_out(int tr, int H, int W, int Cout, int nb, int b, int ty0, int tx0, int pk_ks, int t_e, int64_t* out16);
 /* Workgroups of all form-9 launches of the last forward that launched (or captured) its kernels: what the switch above changes. */
