@@ -25,6 +25,11 @@ inline int check_launch() {
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }      // the 16-byte loads and stores of the entries' operands
+
+// Bound of the 32-bit grid-stride walks (conv_device.hpp: xcd_walk): an item count below it leaves a whole grid stride (4096
+// workgroups of 256) of headroom under 2^32, so the walk's index never wraps
+constexpr long long kWalkLimit = (1LL << 32) - 4096LL * 256 - 8;
 
 // (double)x < 1e-6 for a float x, without leaving fp32: the nearest float to 1e-6 is
 // 9.99999997e-7 < 1e-6, so the double comparison of the reference

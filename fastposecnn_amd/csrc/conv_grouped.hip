@@ -169,8 +169,6 @@ int launch_grouped_t(GroupedArgs a, hipStream_t s) {
     return check_launch();
 }
 
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 bool grouped_cg_ok(int cg) { return cg == 4 || cg == 8 || cg == 16 || cg == 32 || cg == 64; }

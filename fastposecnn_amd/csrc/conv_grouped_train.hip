@@ -333,8 +333,6 @@ int launch_wgrad_t(GrpWgradArgs a, float* dw, hipStream_t s) {
     return check_launch();
 }
 
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 inline bool grouped_shape_ok(int C, int groups) {
     return C >= 32 && C % 32 == 0 && groups >= 1 && C % groups == 0 && grouped_cg_ok(C / groups);
 }

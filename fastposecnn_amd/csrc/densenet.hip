@@ -29,8 +29,6 @@ namespace fpc {
 
 namespace {
 
-constexpr long long kWalkLimit = (1LL << 32) - 4096LL * 256 - 8;      // the 32-bit walks keep a grid stride of headroom
-
 // logical workgroup of a launch whose grid is a multiple of 8: XCD x takes the x-th contiguous eighth
 __device__ __forceinline__ unsigned xcd_block() {
     return (gridDim.x & 7) == 0 ? (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
@@ -434,8 +432,6 @@ int launch_dense_place(const float* in, float* out, long long M, int C, int ld, 
 }  // namespace fpc
 
 using namespace fpc;
-
-static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 extern "C" int fpc_dense_pw(const float* in, const float* s1, const float* t1, const float* w, const float* s2, const float* t2, float* out,
                             int64_t M, int K, int Cout, int ldi, int ldo, int act, int form, fpc_stream_t stream) {

@@ -1,101 +1,21 @@
-// efficientnet.hip — the kernels of the EfficientNet-B0 encoder (smp's EfficientNetEncoder over efficientnet_pytorch, restated in
-// lib/backbone.py EfficientNetEncoder), for inference, on mobilenet.hip's conventions: dense channel-last f32, BatchNorm folded to
+// efficientnet.hip — the gate kernels and the entries of the EfficientNet-B0 encoder (smp's EfficientNetEncoder over
+// efficientnet_pytorch, restated in lib/backbone.py EfficientNetEncoder), for inference, on mobilenet.hip's conventions: dense channel-last f32, BatchNorm folded to
 // per-channel scale / shift, no atomics and no split over K — every sum runs in an order the shape alone fixes, so two launches agree
 // bit for bit —, the XCD-banded walks of conv_device.hpp.  act 0 is none, 1 ReLU6, 2 swish v / (1 + exp(-v)); every division is
 // div_ieee's (conv_device.hpp: sigmoid, swish).  The pads are efficientnet_pytorch's static "same" ones for the declared 224 image,
 // fixed numbers: stride 1 (k - 1) / 2 on every side; stride 2 pads 0 before and 1 after for k = 3, 1 and 2 for k = 5.
 //
-//   k_mb_dwconv<K, S>  the depthwise K x K (3 or 5), stride S, as k_dwconv3x3: one thread per (row, strip of 4 (S = 1) or 2 (S = 2)
-//                  output columns, channel quad), lanes along the channels.  A 5x5 strip at stride 1 reads 5 x 8 input quads for 4 outputs
-//                  instead of 25 each.  The weights are torch's [C][1][K][K] read in place (see the kernel for how).  K K FMAs per
-//                  output in (kh, kw) order.
 //   k_mb_pool      per-channel partial sums of the gate's operand: one workgroup per (slab of pixels, frame), lanes along the channel
 //                  quads, the slab's pixels dealt to thread rows, a fixed-order LDS reduction over the rows; partial[b][slab][C].
 //   k_mb_excite    one workgroup per frame: the slabs added in slab order and divided by H W; the reduce 1x1 (a wave per four hidden
 //                  units: a lane adds its channel quads in ascending order, xor butterfly), bias, swish; the expand 1x1 (16 lanes
 //                  per channel: a lane adds its hidden units in ascending order, xor butterfly), bias, sigmoid; gate[b][C].
 // The stem (3x3 / stride 2, pads 0 and 1, swish) and the 1x1 sites (swish, the gated in operand, K up to 2048) are the MB
-// instantiations of mobilenet.hip's k_stem3x3s2, k_conv1x1_f32 and k_conv1x1_f32_small; their stand-alone entries are here.
+// instantiations of mobilenet.hip's k_stem3x3s2, k_conv1x1_f32 and k_conv1x1_f32_small; their stand-alone entries are here.  The
+// depthwise K x K convolution (fpc_mbconv_dw) is depthwise.hip's k_dw_fwd<K, S, same pad, true>.
 #include "conv_device.hpp"
 
 namespace fpc {
-
-namespace {
-
-constexpr long long kWalkLimit = (1LL << 32) - 4096LL * 256 - 8;      // the 32-bit walks keep a grid stride of headroom
-
-__device__ __forceinline__ float mb_act(float v, int act) { return act == 2 ? swish(v) : act == 1 ? fminf(fmaxf(v, 0.f), 6.f) : v; }
-
-}  // namespace
-
-// in [B][Hi][Wi][C], w [C][1][K][K], out [B][Ho][Wo][C]; total = B Ho WT CQ items with WT strips of TW output columns per row
-template <int K, int S>
-__global__ __launch_bounds__(256) void k_mb_dwconv(const float* __restrict__ in, const float* __restrict__ w,
-                                                   const float* __restrict__ scale, const float* __restrict__ shift,
-                                                   float* __restrict__ out, unsigned total, int Hi, int Wi, int Ho, int Wo, int WT, int CQ,
-                                                   int act) {
-    constexpr int TW = S == 1 ? 4 : 2, NC = (TW - 1) * S + K, PB = S == 1 ? (K - 1) / 2 : (K - 3) / 2;      // PB: the pad before
-    const int C = 4 * CQ;
-    const XcdWalk wk = xcd_walk(total);
-    for (unsigned g = wk.first; g < wk.end; g += wk.step) {
-        const unsigned cq = g % (unsigned)CQ;
-        unsigned t = g / (unsigned)CQ;
-        const unsigned wt = t % (unsigned)WT;
-        t /= (unsigned)WT;
-        const unsigned ho = t % (unsigned)Ho, b = t / (unsigned)Ho;
-        // K = 3: the quad's 36 weights [channel][kh][kw] in registers and the three rows unrolled, as k_dwconv3x3.  K = 5: 100 weights
-        // and the 5 x NC quads of a window hoisted above the FMAs do not fit the registers of a 256-thread workgroup, so the rows
-        // stay a loop and each takes its own 4 x 5 weights [channel][kw] (one float at a time: a row of 5 is not 16-byte aligned)
-        constexpr bool ROWS = K == 5;
-        constexpr int KH_UNROLL = ROWS ? 1 : K;
-        float wf[ROWS ? 4 * K : 4 * K * K];
-        const float* wq = w + 4 * K * K * (size_t)cq;
-        if constexpr (!ROWS) {
-#pragma unroll
-            for (int i = 0; i < K * K; ++i) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(wq + 4 * i);
-                wf[4 * i] = v[0]; wf[4 * i + 1] = v[1]; wf[4 * i + 2] = v[2]; wf[4 * i + 3] = v[3];
-            }
-        }
-        f32x4 acc[TW];
-#pragma unroll
-        for (int o = 0; o < TW; ++o) acc[o] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const int wo0 = (int)wt * TW, wi0 = wo0 * S - PB;
-#pragma unroll KH_UNROLL
-        for (int kh = 0; kh < K; ++kh) {
-            if constexpr (ROWS) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int kw = 0; kw < K; ++kw) wf[K * j + kw] = wq[K * K * j + K * kh + kw];
-            }
-            const int hi = (int)ho * S - PB + kh;
-            const bool rowok = hi >= 0 && hi < Hi;
-            f32x4 x[NC];
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                const int wi = wi0 + c;
-                x[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (rowok && wi >= 0 && wi < Wi) x[c] = *reinterpret_cast<const f32x4*>(in + (((size_t)b * Hi + hi) * Wi + wi) * C + 4 * cq);
-            }
-#pragma unroll
-            for (int o = 0; o < TW; ++o)
-#pragma unroll
-                for (int kw = 0; kw < K; ++kw)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[o][j] = fmaf(x[o * S + kw][j], wf[ROWS ? K * j + kw : K * K * j + K * kh + kw], acc[o][j]);
-        }
-        const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + 4 * cq), sh = *reinterpret_cast<const f32x4*>(shift + 4 * cq);
-#pragma unroll
-        for (int o = 0; o < TW; ++o) {
-            if (wo0 + o >= Wo) continue;
-            f32x4 v;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = mb_act(acc[o][j] * sc[j] + sh[j], act);
-            *reinterpret_cast<f32x4*>(out + (((size_t)b * Ho + ho) * Wo + wo0 + o) * C + 4 * cq) = v;
-        }
-    }
-}
 
 // grid (slabs, B).  x [B][HW][C]; partial [B][slabs][C], every element written once.  lanes = min(C / 4, 256) threads take the channel
 // quads of a pixel, rows = 256 / lanes thread rows take the slab's pixels in turn (the threads behind rows * lanes only keep the
@@ -223,22 +143,6 @@ __global__ __launch_bounds__(kMbExciteThreads) void k_mb_excite(const float* __r
     }
 }
 
-int launch_mb_dwconv(const float* in, const float* w, const float* scale, const float* shift, float* out, int B, int Hi, int Wi, int C,
-                     int k, int stride, int act, hipStream_t s) {
-    if (B < 1 || Hi < 1 || Wi < 1 || C < 4 || C % 4 || (k != 3 && k != 5) || (stride != 1 && stride != 2) || act < 0 || act > 2) return FPC_EINVAL;
-    if (stride == 2 && ((Hi | Wi) & 1)) return FPC_EINVAL;      // (an odd extent would need another pad table)
-    const int Ho = Hi / stride, Wo = Wi / stride, TW = stride == 1 ? 4 : 2, WT = (Wo + TW - 1) / TW;
-    const long long total = (long long)B * Ho * WT * (C / 4);
-    if (total >= kWalkLimit) return FPC_EINVAL;
-#define FPC_MB_DW(K, S) hipLaunchKernelGGL((k_mb_dwconv<K, S>), dim3(stream_grid(total)), dim3(256), 0, s, in, w, scale, shift, out, (unsigned)total, Hi, Wi, Ho, Wo, WT, C / 4, act)
-    if (k == 3 && stride == 1) FPC_MB_DW(3, 1);
-    else if (k == 3) FPC_MB_DW(3, 2);
-    else if (stride == 1) FPC_MB_DW(5, 1);
-    else FPC_MB_DW(5, 2);
-#undef FPC_MB_DW
-    return check_launch();
-}
-
 int launch_mb_gate(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, float* gate, float* partial, int B,
                    int H, int W, int C, int Cs, hipStream_t s) {
     const int slabs = mb_pool_slabs(H, W, C);
@@ -254,14 +158,6 @@ int launch_mb_gate(const float* x, const float* w1, const float* b1, const float
 }  // namespace fpc
 
 using namespace fpc;
-
-static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-extern "C" int fpc_mbconv_dw(const float* in, const float* w, const float* scale, const float* shift, float* out, int B, int Hi, int Wi,
-                             int C, int k, int stride, int act, fpc_stream_t stream) {
-    if (!in || !w || !scale || !shift || !out || !al16(in) || !al16(w) || !al16(scale) || !al16(shift) || !al16(out)) return FPC_EINVAL;
-    return launch_mb_dwconv(in, w, scale, shift, out, B, Hi, Wi, C, k, stride, act, (hipStream_t)stream);
-}
 
 extern "C" int fpc_mbconv_gate_slabs(int H, int W, int C) { return mb_pool_slabs(H, W, C); }
 

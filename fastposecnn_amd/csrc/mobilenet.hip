@@ -1,17 +1,12 @@
-// mobilenet.hip — the three kernels of the MobileNetV2 encoder (torchvision's, as smp wraps it: lib/backbone.py MobileNetV2Encoder),
-// for inference.  Activations are dense channel-last f32; BatchNorm arrives folded as per-channel scale / shift; act 1 is ReLU6,
-// min(max(v, 0), 6).  No atomics and no split over K: every sum runs in an order the shape alone fixes, so two launches agree bit
+// mobilenet.hip — the stem and the 1x1 kernels of the MobileNetV2 encoder (torchvision's, as smp wraps it: lib/backbone.py
+// MobileNetV2Encoder), for inference; its depthwise 3x3 is depthwise.hip's k_dw_fwd<3, S, 1, false>.  Activations are dense
+// channel-last f32; BatchNorm arrives folded as per-channel scale / shift; act 1 is ReLU6, min(max(v, 0), 6).  No atomics and no split over K: every sum runs in an order the shape alone fixes, so two launches agree bit
 // for bit.  No kernel divides a float.  Workgroups walk their items in the XCD-banded order of the other streaming kernels
 // (conv_device.hpp: xcd_walk), so neighbouring rows are fetched by one L2.
 //
 //   k_stem3x3s2    features.0: dense 3x3 / stride 2 / pad 1 over the NHWC4 image to 32 channels.  Eight threads per output pixel, each
 //                  with the 4 x 27 weights of its channel quad in registers for the whole launch; the nine 16-byte pixels of a window
 //                  are the same addresses for those eight lanes (one fetch).  27 FMAs per channel in (kh, kw, ci) order.
-//   k_dwconv3x3<S> the depthwise 3x3 / pad 1, stride S: one thread per (row, strip of 4 (S = 1) or 2 (S = 2) output columns, channel
-//                  quad), lanes along the channels.  A strip reads 3 x 6 (3 x 5) input quads for 4 (2) outputs instead of 9 each,
-//                  the rows above and below come from the L2 the band belongs to: the input is read from memory once plus the
-//                  band borders.  The weights are torch's [C][1][3][3] read in place: a quad's 36 floats are nine 16-byte loads.
-//                  Nine FMAs per output in (kh, kw) order.
 //   k_conv1x1_f32<NT>  the 1x1 sites as out[m][n] = act(scale[n] sum_k in[m][k] w[n][k] + shift[n]) (+ res[m][n]) on
 //                  v_mfma_f32_32x32x2_f32 (exact f32 products, f32 accumulation).  One wave per (32 pixel rows, NT tiles of 32
 //                  output channels), both operands straight from memory in the instruction's own lane layout (lane l: row l & 31,
@@ -51,8 +46,6 @@ __device__ __forceinline__ float act_apply(float v, int act) {
     else return act_apply(v, act);
 }
 
-constexpr long long kWalkLimit = (1LL << 32) - 4096LL * 256 - 8;      // the 32-bit walks keep a grid stride of headroom
-
 }  // namespace
 
 // in4 [B][Hi][Wi][4] (the fourth channel is not read), w [32][3][3][3], out [B][Ho][Wo][32]; npix = B Ho Wo.  MB: EfficientNet's stem,
@@ -91,61 +84,6 @@ __global__ __launch_bounds__(256) void k_stem3x3s2(const float* __restrict__ in4
 #pragma unroll
         for (int j = 0; j < 4; ++j) o[j] = act_apply<MB>(acc[j] * sc[j] + sh[j], MB ? 2 : 1);
         *reinterpret_cast<f32x4*>(out + (size_t)p * 32 + 4 * q) = o;
-    }
-}
-
-// in [B][Hi][Wi][C], w [C][1][3][3], out [B][Ho][Wo][C]; total = B Ho WT CQ items with WT strips of TW output columns per row
-template <int S>
-__global__ __launch_bounds__(256) void k_dwconv3x3(const float* __restrict__ in, const float* __restrict__ w,
-                                                   const float* __restrict__ scale, const float* __restrict__ shift,
-                                                   float* __restrict__ out, unsigned total, int Hi, int Wi, int Ho, int Wo, int WT, int CQ,
-                                                   int act) {
-    constexpr int TW = S == 1 ? 4 : 2, NC = (TW - 1) * S + 3;
-    const int C = 4 * CQ;
-    const XcdWalk wk = xcd_walk(total);
-    for (unsigned g = wk.first; g < wk.end; g += wk.step) {
-        const unsigned cq = g % (unsigned)CQ;
-        unsigned t = g / (unsigned)CQ;
-        const unsigned wt = t % (unsigned)WT;
-        t /= (unsigned)WT;
-        const unsigned ho = t % (unsigned)Ho, b = t / (unsigned)Ho;
-        float wf[36];      // [channel of the quad][kh][kw]
-#pragma unroll
-        for (int i = 0; i < 9; ++i) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(w + 36 * (size_t)cq + 4 * i);
-            wf[4 * i] = v[0]; wf[4 * i + 1] = v[1]; wf[4 * i + 2] = v[2]; wf[4 * i + 3] = v[3];
-        }
-        f32x4 acc[TW];
-#pragma unroll
-        for (int o = 0; o < TW; ++o) acc[o] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const int wo0 = (int)wt * TW, wi0 = wo0 * S - 1;
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
-            const int hi = (int)ho * S - 1 + kh;
-            const bool rowok = hi >= 0 && hi < Hi;
-            f32x4 x[NC];
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                const int wi = wi0 + c;
-                x[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (rowok && wi >= 0 && wi < Wi) x[c] = *reinterpret_cast<const f32x4*>(in + (((size_t)b * Hi + hi) * Wi + wi) * C + 4 * cq);
-            }
-#pragma unroll
-            for (int o = 0; o < TW; ++o)
-#pragma unroll
-                for (int kw = 0; kw < 3; ++kw)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[o][j] = fmaf(x[o * S + kw][j], wf[9 * j + 3 * kh + kw], acc[o][j]);
-        }
-        const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + 4 * cq), sh = *reinterpret_cast<const f32x4*>(shift + 4 * cq);
-#pragma unroll
-        for (int o = 0; o < TW; ++o) {
-            if (wo0 + o >= Wo) continue;
-            f32x4 v;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = act_apply(acc[o][j] * sc[j] + sh[j], act);
-            *reinterpret_cast<f32x4*>(out + (((size_t)b * Ho + ho) * Wo + wo0 + o) * C + 4 * cq) = v;
-        }
     }
 }
 
@@ -368,19 +306,6 @@ int launch_mb_stem3x3s2(const float* in4, const float* w, const float* scale, co
     return check_launch();
 }
 
-int launch_dwconv3x3(const float* in, const float* w, const float* scale, const float* shift, float* out, int B, int Hi, int Wi, int C,
-                     int stride, int act, hipStream_t s) {
-    if (B < 1 || Hi < 1 || Wi < 1 || C < 4 || C % 4 || (stride != 1 && stride != 2) || act < 0 || act > 1) return FPC_EINVAL;
-    const int Ho = (Hi - 1) / stride + 1, Wo = (Wi - 1) / stride + 1, TW = stride == 1 ? 4 : 2, WT = (Wo + TW - 1) / TW;
-    const long long total = (long long)B * Ho * WT * (C / 4);
-    if (total >= kWalkLimit) return FPC_EINVAL;
-    if (stride == 1)
-        hipLaunchKernelGGL(k_dwconv3x3<1>, dim3(stream_grid(total)), dim3(256), 0, s, in, w, scale, shift, out, (unsigned)total, Hi, Wi, Ho, Wo, WT, C / 4, act);
-    else
-        hipLaunchKernelGGL(k_dwconv3x3<2>, dim3(stream_grid(total)), dim3(256), 0, s, in, w, scale, shift, out, (unsigned)total, Hi, Wi, Ho, Wo, WT, C / 4, act);
-    return check_launch();
-}
-
 // The form of a site of M rows and Cout channels, a function of the shape alone: 0 = k_conv1x1_f32_small (16 x 16 tiles) where tiles
 // of 32 x 32 would not give every SIMD of the chip a wave (fewer than 1024); else the channel tiles of 32 per wave of
 // k_conv1x1_f32: the most of 5, 3, 2 that divides the site's tiles and still leaves 2048 waves (two per SIMD), else 1.
@@ -444,14 +369,6 @@ int launch_mb_conv1x1(const float* in, const float* gate, const float* w, const 
 }  // namespace fpc
 
 using namespace fpc;
-
-static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-extern "C" int fpc_dwconv3x3(const float* in, const float* w, const float* scale, const float* shift, float* out, int B, int Hi, int Wi,
-                             int C, int stride, int act, fpc_stream_t stream) {
-    if (!in || !w || !scale || !shift || !out || !al16(in) || !al16(w) || !al16(scale) || !al16(shift) || !al16(out)) return FPC_EINVAL;
-    return launch_dwconv3x3(in, w, scale, shift, out, B, Hi, Wi, C, stride, act, (hipStream_t)stream);
-}
 
 extern "C" int fpc_conv1x1_f32(const float* in, const float* w, const float* scale, const float* shift, const float* res, float* out,
                                int64_t M, int Cin, int Cout, int act, fpc_stream_t stream) {

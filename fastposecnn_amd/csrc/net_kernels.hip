@@ -539,7 +539,7 @@ __global__ void k_fold_bn(const float* __restrict__ gamma, const float* __restri
 
 int launch_maxpool3x3s2(const float* in, float* out, int B, int Hi, int Wi, int C, int Ho, int Wo, hipStream_t s) {
     // (xcd_walk's 32-bit `first + k * step` must not wrap: one grid stride — at most 4096 x 256 items — of headroom below 2^32)
-    if (C % 4 != 0 || (long long)B * Ho * Wo * (C / 4) >= (1LL << 32) - 4096LL * 256 - 8) return FPC_EINVAL;
+    if (C % 4 != 0 || (long long)B * Ho * Wo * (C / 4) >= kWalkLimit) return FPC_EINVAL;
     hipLaunchKernelGGL(k_maxpool3x3s2<1>, dim3(stream_grid((long long)B * Ho * Wo * (C / 4))), dim3(256), 0, s, in, out, B,
                        Hi, Wi, C, Ho, Wo);
     return check_launch();
@@ -548,7 +548,7 @@ int launch_maxpool3x3s2(const float* in, float* out, int B, int Hi, int Wi, int 
 // the pad-0 ceil-mode form: out [B][Hi / 2][Wi / 2][C] (torch's output size for every Hi, Wi >= 2: no window starts outside)
 int launch_maxpool3x3s2_ceil(const float* in, float* out, int B, int Hi, int Wi, int C, hipStream_t s) {
     const int Ho = Hi / 2, Wo = Wi / 2;
-    if (C % 4 != 0 || Hi < 2 || Wi < 2 || (long long)B * Ho * Wo * (C / 4) >= (1LL << 32) - 4096LL * 256 - 8) return FPC_EINVAL;
+    if (C % 4 != 0 || Hi < 2 || Wi < 2 || (long long)B * Ho * Wo * (C / 4) >= kWalkLimit) return FPC_EINVAL;
     hipLaunchKernelGGL(k_maxpool3x3s2<0>, dim3(stream_grid((long long)B * Ho * Wo * (C / 4))), dim3(256), 0, s, in, out, B,
                        Hi, Wi, C, Ho, Wo);
     return check_launch();

@@ -342,7 +342,7 @@ inline int se_lanes(int C) { return C / 4 < kSeThreads ? C / 4 : kSeThreads; }
 inline int se_rows(int C) { return kSeThreads / se_lanes(C); }
 inline bool se_shape_ok(int B, int H, int W, int C) {
     return B >= 1 && B <= 65535 && H >= 1 && W >= 1 && C >= 64 && C % 64 == 0 && C <= kSeMaxC && (long long)H * W < (1LL << 31) &&
-           (long long)B * H * W * (C / 4) < (1LL << 32) - 4096LL * 256 - 8;      // (xcd_walk's 32-bit walk: launch_maxpool3x3s2's bound)
+           (long long)B * H * W * (C / 4) < kWalkLimit;      // (xcd_walk's 32-bit walk: launch_maxpool3x3s2's bound)
 }
 // mobilenet.hip: the MobileNetV2 encoder's kernels.  Dense channel-last f32, BatchNorm folded into scale / shift, act 1 = ReLU6.
 // stem: in4 [B][Hi][Wi][4] -> out [B][(Hi - 1) / 2 + 1][(Wi - 1) / 2 + 1][32] with w [32][3][3][3] and ReLU6; depthwise: w [C][1][3][3],

@@ -148,8 +148,6 @@ __global__ __launch_bounds__(128 * WM) void k_conv1x1(const PwArgs a) {
 #undef FPC_GLOBAL
 #undef FPC_LOCAL
 
-bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 int launch_conv1x1(const PwArgs& a, hipStream_t s) {

@@ -201,8 +201,6 @@ int launch_se_scale_add_relu(const float* x, const float* gate, const float* res
 
 using namespace fpc;
 
-static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 extern "C" int fpc_se_pool_slabs(int H, int W, int C) { return se_pool_slabs(H, W, C); }
 
 extern "C" size_t fpc_se_scratch_floats(int B, int H, int W, int C) {

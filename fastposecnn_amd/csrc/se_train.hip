@@ -262,8 +262,6 @@ static int launch_se_bwd(const float* x, const float* y, const float* gy, const 
 
 using namespace fpc;
 
-static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 extern "C" int fpc_se_gate_train(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, float* gate,
                                  float* mean, float* hidden, float* scratch, int B, int H, int W, int C, int R, fpc_stream_t stream) {
     if (!x || !w1 || !b1 || !w2 || !b2 || !gate || !mean || !hidden || !scratch) return FPC_EINVAL;

@@ -224,8 +224,6 @@ __global__ __launch_bounds__(256) void k_maxpool3x3s2_bwd(const float* __restric
     }
 }
 
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 inline bool stem_shape_ok(int B, int Hi, int Wi) {
     return B >= 1 && Hi >= 8 && Wi >= 8 && Hi % 2 == 0 && Wi % 2 == 0 && (long long)B * Hi * Wi < (1LL << 31);
 }

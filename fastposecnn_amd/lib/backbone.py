@@ -376,7 +376,7 @@ class InvertedResidual(nn.Module):
     depthwise 3x3 with the stride (groups = hidden) + BN + ReLU6, the project 1x1 without bias, its BN; the input is added where the
     stride is 1 and inp = oup, with no activation behind the add.  In the training step the dense 1x1 sites and the BatchNorms run
     on the native kernels lib/train_conv.py already has (Conv2d / BatchNorm2d above); the depthwise convolution and ReLU6 are torch's
-    by default and, with FPC_TRAIN_NATIVE_MBV2=1, native too: the convolution on k_dwconv3x3 and csrc/dwconv_train.hip (Conv2d above
+    by default and, with FPC_TRAIN_NATIVE_MBV2=1, native too: the convolution on csrc/depthwise.hip, forward and backward (Conv2d above
     reaches lib/train_conv._DepthwiseConv2dFn), ReLU6 as the activation of the native BatchNorm (ConvBNReLU6.forward, with
     FPC_TRAIN_NATIVE_BN=1)."""
 

@@ -28,8 +28,8 @@ forward on k_se_pool / k_se_excite / k_se_scale_add_relu (csrc/se.hip), the whol
 se_fwd_native / se_bwd_native (a refused block in se_torch).
 The DEPTHWISE 3x3 convolution of the MobileNetV2 blocks and the ReLU6 behind their BatchNorms are torch's own by default (the grouped
 MIOpen / aten kernels forward and both gradients, aten's hardtanh each way); with FPC_TRAIN_NATIVE_MBV2=1 the convolution is
-_DepthwiseConv2dFn — the forward on the inference kernel k_dwconv3x3 (act 0, scale 1, shift 0), the data and weight gradients on
-csrc/dwconv_train.hip, counted in dw_fwd_native / dw_dgrad_native / dw_wgrad_native — and, with FPC_TRAIN_NATIVE_BN=1 as well,
+_DepthwiseConv2dFn — the forward on the inference kernel k_dw_fwd (act 0, scale 1, shift 0), the data and weight gradients
+beside it in csrc/depthwise.hip, counted in dw_fwd_native / dw_dgrad_native / dw_wgrad_native — and, with FPC_TRAIN_NATIVE_BN=1 as well,
 ConvBNReLU6's BatchNorm and ReLU6 are one native op each way (batchnorm_act(relu6=True), counted in bn_relu6_native beside bn_native).
 
 The tiling / Winograd form of a shape is chosen once, by timing the candidates on the first call with that shape (this
@@ -418,7 +418,7 @@ class _GroupedConv2dFn(torch.autograd.Function):
 # Off by default: with it off a depthwise convolution is torch's own, forward and backward, and ReLU6 is never fused into the
 # native BatchNorm, as before (DESIGN.md 4.2a''''''').
 NATIVE_MBV2 = bool(int(os.environ.get("FPC_TRAIN_NATIVE_MBV2", "0")))
-_DW_WALK_LIMIT = 2 ** 32 - 4096 * 256 - 8      # channel quads of a tensor: the 32-bit walks of csrc/mobilenet.hip
+_DW_WALK_LIMIT = 2 ** 32 - 4096 * 256 - 8      # channel quads of a tensor: csrc/common.hpp's kWalkLimit
 
 
 def _dw_native_op(op, stride):
@@ -447,8 +447,8 @@ def _depthwise_ok(x, w, bias, stride, pad, groups):
 
 
 class _DepthwiseConv2dFn(torch.autograd.Function):
-    """The depthwise 3x3 / pad-1 convolution without bias on the native kernels: forward k_dwconv3x3 through fpc_dwconv3x3 with the
-    identity scale / shift and no activation, backward fpc_dwconv3x3_dgrad / _wgrad (csrc/dwconv_train.hip).  One form: nothing is tuned."""
+    """The depthwise 3x3 / pad-1 convolution without bias on the native kernels: forward k_dw_fwd through fpc_dwconv3x3 with the
+    identity scale / shift and no activation, backward fpc_dwconv3x3_dgrad / _wgrad (csrc/depthwise.hip).  One form: nothing is tuned."""
 
     @staticmethod
     def forward(ctx, x, w, stride):

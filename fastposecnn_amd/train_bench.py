@@ -9,7 +9,7 @@ What runs where (stated in the JSON line as well):
     bilinear upsampling forward / backward on csrc/upsample.hip; the decoder's GroupNorm + ReLU on csrc/groupnorm.hip; the
     encoder's BatchNorm + residual add + ReLU: torch's modules, or csrc/batchnorm.hip with FPC_TRAIN_NATIVE_BN=1
     the SE-ResNet blocks' gate + add + ReLU: torch's modules, or csrc/se.hip + csrc/se_train.hip with FPC_TRAIN_NATIVE_SE=1
-    the MobileNetV2 blocks' depthwise 3x3 and ReLU6: torch's modules, or csrc/mobilenet.hip + csrc/dwconv_train.hip (and, with
+    the MobileNetV2 blocks' depthwise 3x3 and ReLU6: torch's modules, or csrc/depthwise.hip (and, with
     FPC_TRAIN_NATIVE_BN=1, ReLU6 inside csrc/batchnorm.hip) with FPC_TRAIN_NATIVE_MBV2=1
     (FPC_TRAIN_NATIVE_CONV=0 returns every convolution and upsampling to torch: the A/B this file's numbers come with);
   * everything after the logits, forward: the inference kernels (class compression, connected components, aggregation,

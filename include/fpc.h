@@ -925,7 +925,7 @@ int fpc_maxpool3x3s2_ceil_fwd(const float* x, float* y, int B, int Hi, int Wi, i
  * Cin % 4 loader with the top-down addend in its epilogue.
  * All three: dense channel-last f32, every pointer non-NULL and 16-byte aligned (FPC_EINVAL otherwise), per-channel scale / shift =
  * the folded BatchNorm, act 0 = none, 1 = ReLU6 min(max(v, 0), 6); fixed summation order, no atomics: bit-identical run to run.
- * fpc_dwconv3x3 (k_dwconv3x3): depthwise 3x3, pad 1, stride 1 or 2: in [B][Hi][Wi][C], w torch's [C][1][3][3] read in place,
+ * fpc_dwconv3x3 (csrc/depthwise.hip: k_dw_fwd): depthwise 3x3, pad 1, stride 1 or 2: in [B][Hi][Wi][C], w torch's [C][1][3][3] read in place,
  *   out [B][(Hi - 1) / stride + 1][(Wi - 1) / stride + 1][C].  Refused: B < 1, C < 4 or C % 4 != 0, any other stride or act.
  * fpc_conv1x1_f32 (k_conv1x1_f32): out[m][n] = act(scale[n] sum_k in[m][k] w[n][k] + shift[n]) (+ res[m][n]) over M pixel rows,
  *   w torch's [Cout][Cin][1][1], exact f32 products on v_mfma_f32_32x32x2_f32 with f32 accumulation.  Cin % 8 == 0, 8 .. 1024;
@@ -956,7 +956,7 @@ int fpc_stem3x3s2(const float* in4, const float* w, const float* scale, const fl
  * otherwise), scale / shift = the folded BatchNorm (eps 1e-3 in this encoder), act 0 = none, 1 = ReLU6, 2 = swish v / (1 + exp(-v));
  * fixed summation orders, no atomics: bit-identical run to run.  The pads are efficientnet_pytorch's static "same" pads for the
  * declared 224 image: stride 1 (k - 1) / 2 on every side; stride 2 pads 0 before and 1 after for k = 3, 1 and 2 for k = 5.
- * fpc_mbconv_dw (k_mb_dwconv; replaces _depthwise_conv + _bn1 + swish of MBConvBlock.forward): depthwise k x k, k 3 or 5, stride 1
+ * fpc_mbconv_dw (csrc/depthwise.hip: k_dw_fwd; replaces _depthwise_conv + _bn1 + swish of MBConvBlock.forward): depthwise k x k, k 3 or 5, stride 1
  *   or 2: in [B][Hi][Wi][C], w torch's [C][1][k][k] read in place, out [B][Hi / stride][Wi / stride][C].  Refused: B < 1, C < 4 or
  *   C % 4 != 0, any other k, stride or act, an odd Hi or Wi at stride 2.
  * fpc_mbconv_gate (k_mb_pool + k_mb_excite; replaces adaptive_avg_pool2d, _se_reduce, swish, _se_expand and sigmoid):
@@ -1026,7 +1026,7 @@ int fpc_dense_norm_pool(const float* x, const float* s, const float* t, float* s
                         fpc_stream_t stream);
 int fpc_dense_place(const float* in, float* out, int64_t M, int C, int ld, fpc_stream_t stream);
 
-/* ---- The depthwise 3x3 convolution and the ReLU6 of the MobileNetV2 encoder in the training step (csrc/dwconv_train.hip,
+/* ---- The depthwise 3x3 convolution and the ReLU6 of the MobileNetV2 encoder in the training step (csrc/depthwise.hip,
  * csrc/batchnorm.hip; lib/train_conv.py: _DepthwiseConv2dFn and batchnorm_act(relu6=True) behind FPC_TRAIN_NATIVE_MBV2=1).  They
  * replace autograd through torch.nn.Conv2d(groups = C) and nn.ReLU6 inside smp's MobileNetV2 encoder (cuDNN's grouped kernels and
  * aten's hardtanh, forward and backward, in the reference; reached from F/lib/pose_regressor.py:608-613).  The FORWARD of the
@@ -1036,11 +1036,11 @@ int fpc_dense_place(const float* in, float* out, int64_t M, int C, int ld, fpc_s
  * C < 4 or C % 4 != 0, a stride other than 1 or 2, Hi < 1 or Wi < 1, B Hi Wi C / 4 >= 2^32 - 2^20 - 8 (the 32-bit walk limit of
  * fpc_dwconv3x3).
  *
- * fpc_dwconv3x3_dgrad (k_dwconv3x3_dgrad_s1 / _s2): dx [B][Hi][Wi][C] from dy [B][(Hi - 1) / stride + 1][(Wi - 1) / stride + 1][C],
+ * fpc_dwconv3x3_dgrad (k_dw_dgrad_s1 / _s2): dx [B][Hi][Wi][C] from dy [B][(Hi - 1) / stride + 1][(Wi - 1) / stride + 1][C],
  *   every element written exactly once: dx[h][w] = sum over kh, kw of dy[(h + 1 - kh) / stride][(w + 1 - kw) / stride] w[kh][kw] where
  *   the divisions are exact and the index is inside dy.  Stride 2 is evaluated per output parity (dx[2a] = dy[a] w[1],
  *   dx[2a + 1] = dy[a] w[2] + dy[a + 1] w[0] per axis): nine products per 2 x 2 block of dx and channel, no zero insertion.
- * fpc_dwconv3x3_wgrad (k_dwconv3x3_wgrad + k_dwconv3x3_wgrad_reduce): dw[c][kh][kw] = sum over b, ho, wo of
+ * fpc_dwconv3x3_wgrad (k_dw_wgrad + k_dw_wgrad_reduce): dw[c][kh][kw] = sum over b, ho, wo of
  *   dy[b][ho][wo][c] x[b][stride ho + kh - 1][stride wo + kw - 1][c], zero outside x; every element of dw is overwritten, a tap no
  *   pixel reaches (a 1 x 1 map: all but the centre) with an exact zero.  The list of the B Ho (frame, output row) pairs is cut into
  *       slices = max(1, min(max(1, 1024 / ceil(C / 32)), B Ho ceil(Wo / 8) / 32, B Ho))      (integer divisions)
@@ -1055,27 +1055,28 @@ int fpc_dwconv3x3_wgrad(const float* x, const float* dy, float* dw, int B, int H
                         size_t ws_bytes, fpc_stream_t stream);
 
 /* ---- The gradients of the depthwise k x k convolution of the EfficientNet-B0 encoder, for the training step
- * (csrc/mbconv_train.hip; C entries only, their front end in lib/train_conv.py is DESIGN.md 6b item 8 d).  They replace
+ * (csrc/depthwise.hip; C entries only, their front end in lib/train_conv.py is DESIGN.md 6b item 8 d).  They replace
  * the backward of autograd through efficientnet_pytorch's Conv2dStaticSamePadding(groups = C) — nn.ZeroPad2d and cuDNN's grouped
- * kernels, forward and backward — inside smp's EfficientNetEncoder (reached from F/lib/pose_regressor.py:608-613).  The FORWARD of the convolution in training is fpc_mbconv_dw above with act 0,
- * scale 1 and shift 0 (v * 1 + 0 is exact).  Conventions of fpc_dwconv3x3_dgrad / _wgrad: dense channel-last f32, w / dw torch's
+ * kernels, forward and backward — inside smp's EfficientNetEncoder (reached from F/lib/pose_regressor.py:608-613).  The FORWARD of
+ * the convolution in training is fpc_mbconv_dw above with act 0, scale 1 and shift 0 (v * 1 + 0 is exact).  Conventions of fpc_dwconv3x3_dgrad / _wgrad: dense channel-last f32, w / dw torch's
  * [C][1][k][k] read / written in place, plain f32 FMAs in an order the shape alone fixes, no atomics: bit-identical run to run.
  * The pads are fpc_mbconv_dw's: pad-before pb = (k - 1) / 2 at stride 1, 0 for k = 3 and 1 for k = 5 at stride 2; Ho = Hi / stride,
  * Wo = Wi / stride.  FPC_EINVAL before any launch: a NULL or not 16-byte-aligned pointer, B < 1, C < 4 or C % 4 != 0, k other than
  * 3 or 5, a stride other than 1 or 2, Hi < 1 or Wi < 1, an odd Hi or Wi at stride 2, B Hi Wi C / 4 >= 2^32 - 2^20 - 8 (the 32-bit
- * walk limit of fpc_mbconv_dw).  (k, stride) = (3, 1) is pad 1 on every side: both entries hand it to fpc_dwconv3x3_dgrad / _wgrad.
+ * walk limit of fpc_mbconv_dw).  (k, stride) = (3, 1) is pad 1 on every side: both entries run fpc_dwconv3x3_dgrad / _wgrad's
+ * kernels of stride 1 there.
  *
- * fpc_mbconv_dw_dgrad (k_mb_dw_dgrad_s1 / _s2): dx [B][Hi][Wi][C] from dy [B][Ho][Wo][C], every element written exactly once:
+ * fpc_mbconv_dw_dgrad (k_dw_dgrad_s1 / _s2): dx [B][Hi][Wi][C] from dy [B][Ho][Wo][C], every element written exactly once:
  *   dx[h][w] = sum over kh, kw of dy[(h + pb - kh) / stride][(w + pb - kw) / stride] w[kh][kw] where the divisions are exact and
  *   the index is inside dy.  Stride 2 is evaluated per output parity, no zero insertion: k = 3 per axis dx[2a] = dy[a] w[0] +
  *   dy[a - 1] w[2], dx[2a + 1] = dy[a] w[1] (9 products per 2 x 2 block and channel); k = 5 dx[2a] = dy[a] w[1] + dy[a - 1] w[3],
  *   dx[2a + 1] = dy[a + 1] w[0] + dy[a] w[2] + dy[a - 1] w[4] (25 products).
- * fpc_mbconv_dw_wgrad (k_mb_dw_wgrad + k_mb_dw_wgrad_reduce): dw[c][kh][kw] = sum over b, ho, wo of
+ * fpc_mbconv_dw_wgrad (k_dw_wgrad + k_dw_wgrad_reduce): dw[c][kh][kw] = sum over b, ho, wo of
  *   dy[b][ho][wo][c] x[b][stride ho + kh - pb][stride wo + kw - pb][c], zero outside x; every element of dw is overwritten, a tap
- *   no pixel reaches with an exact zero.  The list of the B Ho (frame, output row) pairs is cut into
+ *   no pixel reaches with an exact zero.  The list of the B Ho (frame, output row) pairs is cut as fpc_dwconv3x3_wgrad's, its
+ *   formula with `slots` in place of 32:
  *       slices = max(1, min(max(1, 1024 / ceil(C / 32)), B Ho ceil(Wo / 8) / slots, B Ho)),  slots = 32 (k = 3) or 8 (k = 5)
- *   contiguous slices (integer divisions), slice i = rows [i B Ho / slices, (i + 1) B Ho / slices): a function of
- *   (B, Ho, Wo, C, k) alone, fpc_dwconv3x3_wgrad's count at k = 3.  One f32 partial [C][k k] per slice (inside a slice: `slots`
+ *   a function of (B, Ho, Wo, C, k) alone, fpc_dwconv3x3_wgrad's count at k = 3.  One f32 partial [C][k k] per slice (inside a slice: `slots`
  *   pixel slots over its (row, 8-column segment) units in turn, added in a fixed tree; at k = 5 a thread holds one tap row of a
  *   channel quad), the slices added in double in sixteen contiguous ranges, each ascending, the ranges ascending.
  *   ws: fpc_mbconv_dw_wgrad_workspace_bytes(B, Ho, Wo, C, k) = slices * C * k * k * 4 bytes (0 for a refused shape), 256-byte

@@ -1,4 +1,4 @@
-"""What tests/test_gpu_dwconv_train.py holds the depthwise training kernels to (csrc/dwconv_train.hip): the cases, the operands and
+"""What tests/test_gpu_dwconv_train.py holds the depthwise training kernels to (csrc/depthwise.hip): the cases, the operands and
 the kernels' formulas written out in float64 — the stride-1 flipped form and the stride-2 parity form of the data gradient, the
 nine sums of the weight gradient — which tests/test_dwconv_train_host.py shows to BE float64 autograd through
 F.conv2d(groups = C).  Also include/fpc.h's slice count of the weight gradient, so that a test can say where the seams fall."""

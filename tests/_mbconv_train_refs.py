@@ -1,4 +1,4 @@
-"""What tests/test_gpu_mbconv_train.py holds the EfficientNet depthwise gradient kernels to (csrc/mbconv_train.hip): the
+"""What tests/test_gpu_mbconv_train.py holds the EfficientNet depthwise gradient kernels to (csrc/depthwise.hip): the
 cases, the operands and the kernels' formulas written out in float64 — the flipped stride-1 form and the per-parity stride-2 form of
 the data gradient, the k k sums of the weight gradient — which tests/test_mbconv_train_host.py shows to BE float64 autograd through
 F.conv2d(F.pad(x, static pads), w, groups = C).  Also include/fpc.h's slice count of the weight gradient, restated."""

@@ -1,4 +1,4 @@
-"""The MobileNetV2 encoder's training step on the native depthwise kernels (csrc/dwconv_train.hip) and with ReLU6 as an activation
+"""The MobileNetV2 encoder's training step on the native depthwise kernels (csrc/depthwise.hip) and with ReLU6 as an activation
 of the native BatchNorm (csrc/batchnorm.hip: fpc_batchnorm_act_fwd / _bwd), behind FPC_TRAIN_NATIVE_MBV2: the kernels against the
 float64 references of _dwconv_train_refs (which tests/test_dwconv_train_host.py shows to be float64 autograd), the front end
 lib/train_conv.conv2d / batchnorm_act(relu6=True), two InvertedResidual blocks and the model.  Bars: dx and y within

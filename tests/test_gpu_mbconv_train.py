@@ -1,4 +1,4 @@
-"""The gradients of the EfficientNet-B0 encoder's depthwise convolution on the native kernels (csrc/mbconv_train.hip), through the C
+"""The gradients of the EfficientNet-B0 encoder's depthwise convolution on the native kernels (csrc/depthwise.hip), through the C
 ABI: fpc_mbconv_dw_dgrad / _wgrad against the float64 references of _mbconv_train_refs (which tests/test_mbconv_train_host.py shows to
 be float64 autograd).  Bars: dx within 2e-5 max(1, |ref|max) of float64, dw within 1e-4 max(1, |ref|max); outputs in NaN-filled
 buffers between 64-float canaries, every launch twice and bit-identical."""

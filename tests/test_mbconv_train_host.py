@@ -37,7 +37,7 @@ def test_the_three_entries_are_declared_listed_and_exported(hiplib):
     hdr = open(os.path.join(REPO, "include", "fpc.h")).read()
     decl = hdr.index("int fpc_mbconv_dw_dgrad")
     cited = hdr[hdr.rindex("/* ----", 0, decl):decl]      # the block's own comment, from its header to the first declaration
-    assert "csrc/mbconv_train.hip" in cited and cited.count("/*") == 1 and cited.rstrip().endswith("*/")
+    assert "csrc/depthwise.hip" in cited and cited.count("/*") == 1 and cited.rstrip().endswith("*/")
     assert "F/lib/pose_regressor.py:608-613" in cited and "Conv2dStaticSamePadding(groups = C)" in cited
     top = hdr[:hdr.index("#define FPC_ABI_VERSION")]
     code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
@@ -133,7 +133,7 @@ def test_depthwise_refusals_come_before_any_launch(hiplib):
 def test_reference_is_autograd_in_float64(ks):
     """The yardstick: the written-out flipped / parity data gradient and the k k sums of the weight gradient against
     torch.autograd.grad through F.conv2d(F.pad(x, static pads), groups = C), float64, on every shape of the GPU file.  It pins the
-    reference, not the kernels: it passes without csrc/mbconv_train.hip too (the entry, refusal, workspace and GPU tests do not)."""
+    reference, not the kernels: it passes without csrc/depthwise.hip too (the entry, refusal, workspace and GPU tests do not)."""
     k, s = ks
     for shape in R.SHAPES_ALL:
         B, Hi, Wi, C = shape
@@ -158,7 +158,7 @@ def test_reference_is_autograd_in_float64(ks):
 
 def test_static_pads_of_b0_are_the_kernels_constants():
     """The module's pads at the 16 depthwise sites against the references' (which are the kernels' compile-time constants).  It
-    pins what the kernels may assume about the module, not the kernels: it passes without csrc/mbconv_train.hip too."""
+    pins what the kernels may assume about the module, not the kernels: it passes without csrc/depthwise.hip too."""
     from fastposecnn_amd.lib import backbone as bb
     enc = bb.get_encoder("efficientnet-b0")
     sites = [b._depthwise_conv for b in enc._blocks]

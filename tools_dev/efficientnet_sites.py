@@ -1,5 +1,6 @@
-"""The EfficientNet-B0 encoder's kernels (csrc/efficientnet.hip and the gated / swish instantiations of csrc/mobilenet.hip) on every
-encoder launch of a 640 x 480 frame, B = 1 and B = 32, and the whole forward beside resnet18's and mobilenet_v2's, in one process:
+"""The EfficientNet-B0 encoder's kernels (csrc/efficientnet.hip, csrc/depthwise.hip and the gated / swish instantiations of
+csrc/mobilenet.hip) on every encoder launch of a 640 x 480 frame, B = 1 and B = 32, and the whole forward beside resnet18's and
+mobilenet_v2's, in one process:
 python tools_dev/efficientnet_sites.py [out.json]
 
 Per launch (the stem and, per MBConv block, expand — not block 0 —, depthwise, gate and project: 1 + 15 + 16 + 16 + 16 = 64 entry
@@ -31,8 +32,8 @@ F32_PEAK_TFLOPS = 157.3
 # (repeat, kernel, stride, expand ratio, input, output)
 BLOCKS = [(1, 3, 1, 1, 32, 16), (2, 3, 2, 6, 16, 24), (2, 5, 2, 6, 24, 40), (3, 3, 2, 6, 40, 80), (3, 5, 1, 6, 80, 112),
           (4, 5, 2, 6, 112, 192), (1, 3, 1, 6, 192, 320)]
-ENCODER_KERNELS = {"efficientnet-b0": ("k_stem3x3s2", "k_mb_dwconv", "k_mb_pool", "k_mb_excite", "k_conv1x1_f32"),
-                   "mobilenet_v2": ("k_stem3x3s2", "k_dwconv3x3", "k_conv1x1_f32")}
+ENCODER_KERNELS = {"efficientnet-b0": ("k_stem3x3s2", "k_dw_fwd", "k_mb_pool", "k_mb_excite", "k_conv1x1_f32"),
+                   "mobilenet_v2": ("k_stem3x3s2", "k_dw_fwd", "k_conv1x1_f32")}
 SWISH = 2
 LINES = []
 

@@ -1,8 +1,8 @@
 """The EfficientNet-B0 encoder's depthwise gradient kernels (and the forward they go with) against torch's own:
 python tools_dev/efficientnet_train_sites.py [out.json]
 
-Every distinct depthwise site of a 640 x 480 frame at the training batch, 8 (csrc/efficientnet.hip's k_mb_dwconv with the identity
-scale / shift forward, csrc/mbconv_train.hip backward, each through its C entry): forward, data gradient and weight gradient each
+Every distinct depthwise site of a 640 x 480 frame at the training batch, 8 (csrc/depthwise.hip: k_dw_fwd with the identity
+scale / shift forward, its gradient kernels backward, each through its C entry): forward, data gradient and weight gradient each
 beside torch's kernel(s) for the same call in the same process — F.conv2d(groups = C) on the ZeroPad2d copy of the channel-last
 tensor (the pad kernel counted: the module's own forward launches it) and aten.convolution_backward on that copy with one output
 asked for (the data gradient's slice back to the unpadded extent counted), which is what the encoder's training step runs today.

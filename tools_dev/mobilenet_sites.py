@@ -1,4 +1,4 @@
-"""The MobileNetV2 encoder's kernels (csrc/mobilenet.hip) on every encoder site of a 640 x 480 frame, B = 1 and B = 32, and the
+"""The MobileNetV2 encoder's kernels (csrc/mobilenet.hip, csrc/depthwise.hip) on every encoder site of a 640 x 480 frame, B = 1 and B = 32, and the
 whole forward beside resnet18's, in one process: python tools_dev/mobilenet_sites.py [out.json]
 
 Per site (the stem, 17 depthwise, 16 expand, 17 project, the last 1x1 = 52 launches): device time per launch, the bytes the launch
@@ -27,7 +27,7 @@ dev = torch.device("cuda:0")
 L = nat.lib()
 F32_PEAK_TFLOPS = 157.3
 SETTING = [(1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1), (6, 160, 3, 2), (6, 320, 1, 1)]
-ENCODER_KERNELS = ("k_stem3x3s2", "k_dwconv3x3", "k_conv1x1_f32")
+ENCODER_KERNELS = ("k_stem3x3s2", "k_dw_fwd", "k_conv1x1_f32")
 LINES = []
 
 

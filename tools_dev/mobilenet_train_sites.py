@@ -1,8 +1,8 @@
 """The MobileNetV2 encoder's depthwise training kernels against torch's own, and the training step with and without them:
 python tools_dev/mobilenet_train_sites.py sites|step [out.json]
 
-sites  every distinct depthwise site of a 640 x 480 frame at the training batch, 8 (csrc/mobilenet.hip's k_dwconv3x3 with the
-       identity scale / shift forward, csrc/dwconv_train.hip backward): forward, data gradient and weight gradient each beside
+sites  every distinct depthwise site of a 640 x 480 frame at the training batch, 8 (csrc/depthwise.hip: k_dw_fwd with the
+       identity scale / shift forward, its gradient kernels backward): forward, data gradient and weight gradient each beside
        torch's kernel(s) for the same call in the same process — F.conv2d(groups = C) on the channel-last tensor and
        aten.convolution_backward with one output asked for, which is what the switch-off path (and the parent commit) runs.  Device
        time per call from torch.profiler's kernel records: the mean (min - max) of 10 calls after 3 warm-up calls, every kernel a call
