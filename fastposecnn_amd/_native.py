@@ -167,6 +167,8 @@ _SIGNATURES = {
     "fpc_dense_conv3x3_form": (_i, [_i, _i, _i]),
     "fpc_dense_norm_pool": (_i, [_vp] * 5 + [_i, _i, _i, _i, _i, _vp]),
     "fpc_dense_place": (_i, [_vp, _vp, _i64, _i, _i, _vp]),
+    "fpc_conv3x3_c3": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "fpc_maxpool2x2_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "fpc_dwconv3x3_dgrad": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "fpc_dwconv3x3_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "fpc_dwconv3x3_wgrad": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),

@@ -205,8 +205,15 @@ extern "C" int fpc_net_load_params(fpc_net_t* n, const float* const* params, int
         }
         if (c.p_bn >= 0) {
             rc = fold_bn_of(n, c.p_bn, c.Cout, c.scale_off, c.shift_off, s);
+            if (!rc && c.p_bias >= 0) rc = launch_fold_conv_bias(n->ws + c.scale_off, n->pptr[c.p_bias], n->ws + c.shift_off, c.Cout, s);      // (a VGG _bn site: the conv bias behind the fold)
             if (rc) return rc;
         }
+    }
+    if (n->vgg0.p_bn >= 0) {      // features.0 of a VGG _bn encoder: the same fold
+        const fpc_net::VggStem& v = n->vgg0;
+        int rc = fold_bn_of(n, v.p_bn, 64, v.scale_off, v.shift_off, s);
+        if (!rc) rc = launch_fold_conv_bias(n->ws + v.scale_off, n->pptr[v.p_bias], n->ws + v.shift_off, 64, s);
+        if (rc) return rc;
     }
     if (n->fold_ok)
         for (int d = 0; d < 4; ++d) {
@@ -450,7 +457,10 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
         nhwc(in, sb, sh, sw, sc);
         const PackedConv& c = n->convs[ci];
         fill_conv_args(n, a, c, n->cplan[ci], in.H, in.W, out.H, out.W, sb, sh, sw, sc, relu, 0);
-        a.p[0] = ConvPtrs{ws + in.off, ws + c.w_off, ws + out.off, ws + c.scale_off, ws + c.shift_off, res, nullptr, nullptr};
+        // (a site without BatchNorm — a VGG encoder's — has its bias, read in place, as the shift and no scale)
+        const float* scale = c.p_bn >= 0 ? ws + c.scale_off : nullptr;
+        const float* shift = c.p_bn >= 0 ? ws + c.shift_off : c.p_bias >= 0 ? n->pptr[c.p_bias] : nullptr;
+        a.p[0] = ConvPtrs{ws + in.off, ws + c.w_off, ws + out.off, scale, shift, res, nullptr, nullptr};
         if (c.wino_ok) a.wino_w[0] = ws + c.wino_off;
         if (c.h3_ok && n->h3_packed) a.h3_w[0] = ws + c.h3_off;
         if (c.cg) { a.cg = c.cg; a.grp_w = ws + c.grp_off; }
@@ -511,6 +521,14 @@ static int forward_middle(fpc_net* n, hipStream_t s) {
         case kStepMb: FPC_TRY(mb_op(n->mops[st.op], st.in, st.out, res)); break;
         case kStepMbGate: FPC_TRY(mb_gate(n->mgates[st.op], st.in)); break;
         case kStepDense: FPC_TRY(dense_op(n->dops[st.op])); break;
+        case kStepVggStem: {      // features.0 of a VGG encoder: the folded BatchNorm, or the bias alone, and ReLU
+            const fpc_net::VggStem& v = n->vgg0;
+            if (v.p_w < 0) return FPC_EINVAL;
+            FPC_TRY(launch_conv3x3_c3(ws + st.in.off, n->pptr[v.p_w], v.p_bn >= 0 ? ws + v.scale_off : nullptr,
+                                      v.p_bn >= 0 ? ws + v.shift_off : n->pptr[v.p_bias], ws + st.out.off, B, st.in.H, st.in.W, 1, s));
+            break;
+        }
+        case kStepPool2: FPC_TRY(launch_maxpool2x2(ws + st.in.off, ws + st.out.off, B, st.in.H, st.in.W, st.in.C, s)); break;
         }
     }
     const Act* feat = n->a_feat;
@@ -908,7 +926,7 @@ extern "C" int fpc_net_force_direct_h3(fpc_net_t* n, int on) {
 // when the plan changed, 0 when it was already so, or a negative code.  Drops the recorded graph.
 extern "C" int fpc_net_force_stem_pool(fpc_net_t* n, int on) {
     if (!n || on < 0 || on > 1 || (on && !n->h3_packed)) return FPC_EINVAL;
-    if (n->c_stem < 0) return FPC_EINVAL;      // the MobileNetV2 and EfficientNet encoders: no 7x7 stem and no max-pool, whatever `on` is
+    if (n->c_stem < 0) return FPC_EINVAL;      // the MobileNetV2, EfficientNet and VGG encoders: no 7x7 stem and no 3x3 max-pool, whatever `on` is
     if (on && n->enc.resnet.ceil_pool()) return FPC_EINVAL;      // the SE-ResNet stem pool has no padding: the fused launch computes another pool
     if (on && ((n->a_stem.H & 1) || (n->a_stem.W & 63) || (long long)n->H * n->W * 16 >= (1LL << 31))) return FPC_EINVAL;
     ConvPlan& p = n->cplan[n->c_stem];
@@ -976,6 +994,10 @@ extern "C" int fpc_net_flops(const fpc_net_t* n, double* out3) {
     for (const fpc_net::DnOp& o : n->dops) {      // the DenseNet ops' products: K per output of a 1x1, 9 x 128 of a 3x3
         if (o.kind != fpc_net::kDnPw && o.kind != fpc_net::kDnConv3) continue;
         const double f = 2.0 * n->B * (double)o.H * o.W * o.Cout * (o.kind == fpc_net::kDnConv3 ? 9 * 128 : o.K);
+        direct += f; executed += f;
+    }
+    if (n->vgg0.p_w >= 0) {      // features.0 of a VGG encoder: 27 products per output
+        const double f = 2.0 * n->B * (double)n->H * n->W * 64 * 27;
         direct += f; executed += f;
     }
     for (int d = 0; d < 4; ++d)      // the 1x1 heads run inside k_merge_head

@@ -1,5 +1,5 @@
 // net_build.hip — how a plan of the backbone engine (net_plan.hpp: fpc_net) is built, host arithmetic only: the encoders
-// fpc_net_create knows by name, the four creation entry points, the four encoder families' builders and net_build, which puts a
+// fpc_net_create knows by name, the four creation entry points, the five encoder families' builders and net_build, which puts a
 // family's encoder in front of the four FPN decoders and heads and plans every convolution site.  The graph is the one
 // segmentation_models_pytorch builds for FastPoseCNN (fastposecnn_amd/lib/backbone.py).  Nothing here launches a kernel.
 #include <stdio.h>
@@ -20,6 +20,7 @@ struct EncoderBuild {
     std::vector<int> h3_sites;        // the encoder sites that are candidates for the three-product direct form (PackedConv::h3_ok)
     std::vector<ResBlock> res[4];     // the ResNet family's blocks by stage
     std::vector<MbBlock> mb;          // the MobileNetV2 or EfficientNet encoder's blocks
+    std::vector<int> vgg[5];          // a VGG encoder's conv sites by block, in order (-1: features.0, which is fpc_net::vgg0 and no site)
 };
 
 // ---- the ResNet family: the 7x7 / stride-2 stem (3 -> 64, BatchNorm, ReLU) and its 3x3 / stride-2 max-pool, then for L = 0 .. 3
@@ -328,10 +329,83 @@ static void dn_buffers(fpc_net* n, const EncoderBuild& eb) {
     }
 }
 
+// ---- the VGG encoders: torchvision's vgg.make_layers as smp's VGGEncoder walks it (vgg11 / 13 / 16 / 19 and each with _bn).  Five
+// blocks of 64 / 128 / 256 / 512 / 512 channels: enc.vgg_block1() convolutions in the first, enc.layers[0 .. 3] in the others, each a
+// 3x3 / stride 1 / pad 1 with a bias, a BatchNorm (vgg_bn) and a ReLU, each block closed by MaxPool2d(2, 2).  encoder.features.N
+// counts every module: a convolution takes 2 indices (3 with BatchNorm), a pool 1.  features.0 (3 -> 64 over the NHWC4 image) is
+// fpc_net::vgg0 on k_conv3x3_c3; every other convolution is an ordinary site (wino_ok holds for all of them) whose BatchNorm is folded
+// at load with the bias folded in behind it, or whose bias alone is the shift.  smp's stages split at the pools, a pool opening the
+// next stage: levels 1 .. 5 are the blocks' outputs in front of their pools, level 6 the last pool alone.  c2 .. c5 = levels 3 .. 6.
+// Parameters in state-dict order.
+static void vgg_params(fpc_net* n, EncoderBuild& eb) {
+    const bool bn = n->enc.vgg_bn();
+    const int chans[5] = {64, 128, 256, 512, 512};
+    int idx = 0, cin = 3;
+    for (int blk = 0; blk < 5; ++blk) {
+        const int convs = blk == 0 ? n->enc.vgg_block1() : n->enc.layers[blk - 1], c = chans[blk];
+        for (int j = 0; j < convs; ++j, idx += bn ? 3 : 2, cin = c) {
+            const std::string p = "encoder.features." + std::to_string(idx), bnp = "encoder.features." + std::to_string(idx + 1);
+            if (idx == 0) {
+                fpc_net::VggStem& v = n->vgg0;
+                v.p_w = n->add_param(p + ".weight", 64 * 27);
+                v.p_bias = n->add_param(p + ".bias", 64);
+                if (bn) { v.p_bn = n->add_bn(bnp, 64); v.scale_off = n->alloc(64); v.shift_off = n->alloc(64); }
+                eb.vgg[blk].push_back(-1);
+            } else {
+                eb.vgg[blk].push_back(n->add_conv(p + ".weight", cin, c, 3, 1, 1, bn ? bnp.c_str() : nullptr, (p + ".bias").c_str(), 0, 0, true));
+            }
+        }
+        ++idx;      // the block's pool
+    }
+    eb.featc[0] = 256; eb.featc[1] = eb.featc[2] = eb.featc[3] = 512;
+}
+
+// The largest (B, H, W) of a VGG plan: the smallest bound of the kernels on it ("the VGG encoders").  Over the
+// batch, features.0's walk of 16 threads per full-resolution pixel, 16 B H W < kWalkLimit (B H W < 2^28 - 2^16: 873 frames of
+// 640 x 480), which is also the first pool's item count times four; per frame, the implicit GEMM's 31-bit lane offsets on the
+// full-resolution 64-channel map, (H + 2) W 256 < 2^31, inside which the Winograd kernels' H W 256 < 2^32 (twice that on a packed
+// canvas) lies.  Everything behind block 1 sees no more elements than block 1 does.
+static bool vgg_size_ok(int B, int H, int W) {
+    return conv3x3_c3_ok(B, H, W) && maxpool2x2_ok(B, H, W, 64) && ((long long)H + 2) * W * 64 * 4 < (1LL << 31);
+}
+
+// Buffers: two full-resolution 64-channel tensors X and Y, reused across the plan, and c2 .. c5.  Block 1 alternates between them and
+// ends in Y (level 1: a_stem).  Block 2, of half their size, alternates between X's halves and ends in the lower (level 2: a_pool);
+// blocks 3 .. 5, of a quarter and less, alternate between the quarters of X's upper half and end in their own a_feat, which the
+// decoders read; the last pool writes a_feat[3].  So levels 1 and 2 outlive the forward (fpc_net_tensor: "stem", "pool").
+static void vgg_buffers(fpc_net* n, const EncoderBuild& eb) {
+    const size_t S = (size_t)n->B * n->H * n->W * 64;
+    const size_t X = n->alloc(S), Y = n->alloc(S);
+    auto view = [](size_t off, int h, int w, int c) { Act a; a.off = off; a.H = h; a.W = w; a.C = c; return a; };
+    const int chans[5] = {64, 128, 256, 512, 512};
+    Act cur = n->a_img4;
+    int h = n->H, w = n->W;
+    for (int blk = 0; blk < 5; ++blk, h /= 2, w /= 2) {
+        const int k = (int)eb.vgg[blk].size(), c = chans[blk];
+        // the slot of the block's tensor i = 0 .. k (0: the pool's output in front of it; block 1 has none)
+        auto slot = [&](int i) {
+            if (blk == 0) return view((k - i) % 2 == 0 ? Y : X, h, w, c);
+            if (blk == 1) return view((k - i) % 2 == 0 ? X : X + S / 2, h, w, c);
+            return view(X + S / 2 + (i % 2 ? S / 4 : 0), h, w, c);
+        };
+        if (blk > 0) { Act t = slot(0); t.C = cur.C; n->tape.push_back(pool2_step(cur, t)); cur = t; }      // (the pooled tensor keeps the previous block's channels)
+        for (int i = 1; i <= k; ++i) {
+            const Act t = (blk >= 2 && i == k) ? n->alloc_act(h, w, c) : slot(i);
+            n->tape.push_back(eb.vgg[blk][i - 1] < 0 ? vgg_stem_step(cur, t) : conv_step(eb.vgg[blk][i - 1], cur, t, true));
+            cur = t;
+        }
+        if (blk == 0) n->a_stem = cur;
+        else if (blk == 1) n->a_pool = cur;
+        else n->a_feat[blk - 2] = cur;
+    }
+    n->a_feat[3] = n->alloc_act(h, w, 512);
+    n->tape.push_back(pool2_step(cur, n->a_feat[3]));
+}
+
 static const struct {
     void (*params)(fpc_net* n, EncoderBuild& eb);
     void (*buffers)(fpc_net* n, const EncoderBuild& eb);
-} kFamilies[kFamilyCount] = {{resnet_params, resnet_buffers}, {mbv2_params, mb_buffers}, {effnet_params, mb_buffers}, {dn_params, dn_buffers}};      // by EncoderFamily
+} kFamilies[kFamilyCount] = {{resnet_params, resnet_buffers}, {mbv2_params, mb_buffers}, {effnet_params, mb_buffers}, {dn_params, dn_buffers}, {vgg_params, vgg_buffers}};      // by EncoderFamily
 
 // The plan of `n` (its encoder descriptor set) for (classes, B, H, W); owns `n` (deleted on failure).  The persistent region (packed
 // weights, folded BatchNorm, weight images) comes first, then the activations and scratch.
@@ -491,6 +565,7 @@ static int create(EncoderDesc d, const int* layers4, int classes, int B, int H, 
     if (!layers4 || !out || classes < 2 || classes > 32 || B < 1 || H < 32 || W < 32 || H % 32 || W % 32) return FPC_EINVAL;
     for (int L = 0; L < 4; ++L)
         if (layers4[L] < 1 || layers4[L] > 64) return FPC_EINVAL;
+    if (d.family == kFamilyVgg && !vgg_size_ok(B, H, W)) return FPC_EINVAL;      // a plan is built and right, or refused
     memcpy(d.layers, layers4, sizeof(d.layers));
     return net_build(new fpc_net{d}, classes, B, H, W, out);
 }
@@ -514,6 +589,11 @@ static const struct { const char* name; EncoderDesc desc; } kEncoders[] = {
     {"densenet121", {kFamilyDenseNet, {}, {6, 12, 24, 16}}},
     {"densenet169", {kFamilyDenseNet, {}, {6, 12, 32, 32}}},
     {"densenet201", {kFamilyDenseNet, {}, {6, 12, 48, 32}}},
+    // VGG configurations A / B / D / E (above): {block 1's convolutions, BatchNorm}, layers: the convolutions of blocks 2 .. 5
+    {"vgg11", {kFamilyVgg, {1, 0}, {1, 2, 2, 2}}}, {"vgg11_bn", {kFamilyVgg, {1, 1}, {1, 2, 2, 2}}},
+    {"vgg13", {kFamilyVgg, {2, 0}, {2, 2, 2, 2}}}, {"vgg13_bn", {kFamilyVgg, {2, 1}, {2, 2, 2, 2}}},
+    {"vgg16", {kFamilyVgg, {2, 0}, {2, 3, 3, 3}}}, {"vgg16_bn", {kFamilyVgg, {2, 1}, {2, 3, 3, 3}}},
+    {"vgg19", {kFamilyVgg, {2, 0}, {2, 4, 4, 4}}}, {"vgg19_bn", {kFamilyVgg, {2, 1}, {2, 4, 4, 4}}},
 };
 
 extern "C" int fpc_net_create(const char* encoder, int classes, int B, int H, int W, fpc_net_t** out) {

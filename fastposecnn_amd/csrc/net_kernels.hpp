@@ -398,6 +398,16 @@ int launch_dense_conv3(const float* in, const float* wt, float* out, int B, int 
 int launch_dense_norm_pool(const float* x, const float* sc, const float* sh, float* skip, float* pooled, int B, int H, int W, int C, int act,
                            hipStream_t s);
 int launch_dense_place(const float* in, float* out, long long M, int C, int ld, hipStream_t s);
+// vgg.hip: the VGG encoders' two kernels.  features.0 — the dense 3x3 / stride 1 / pad 1 of the NHWC4 image [B][H][W][4] to 64 channels,
+// out = act(scale[n] sum + shift[n]), scale NULL: sum + shift[n], act 1 = ReLU — and MaxPool2d(2, 2) over dense [B][H][W][C].  The _ok
+// predicates are the launchers' shape checks (the plan builder asks them before it builds).  launch_fold_conv_bias: shift += scale * bias,
+// a convolution's bias behind its folded BatchNorm.
+bool conv3x3_c3_ok(int B, int H, int W);
+int launch_conv3x3_c3(const float* in4, const float* w, const float* scale, const float* shift, float* out, int B, int H, int W, int act,
+                      hipStream_t s);
+bool maxpool2x2_ok(int B, int H, int W, int C);
+int launch_maxpool2x2(const float* x, float* y, int B, int H, int W, int C, hipStream_t s);
+int launch_fold_conv_bias(const float* scale, const float* bias, float* shift, int C, hipStream_t s);
 int launch_gn_finalize(const GnFinArgs& a, int groups, hipStream_t s);
 int launch_gn_relu_up2(const GnUpArgs& a, int groups, hipStream_t s);
 int launch_merge_head(const MergeHeadArgs& a, int groups, hipStream_t s);

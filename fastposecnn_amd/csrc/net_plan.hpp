@@ -42,6 +42,7 @@ enum EncoderFamily {
     kFamilyMobileNetV2,      // torchvision's MobileNetV2 features: none of the block kinds (net_build.hip: "the MobileNetV2 encoder")
     kFamilyEfficientNet,     // efficientnet_pytorch's MBConv blocks by a table of block arguments (net_build.hip: "the EfficientNet encoders")
     kFamilyDenseNet,         // torchvision's DenseNet features: the ResNet family's stem, then dense blocks and transitions (net_build.hip: "the DenseNet encoders")
+    kFamilyVgg,              // torchvision's VGG features: features.0 on its own kernel, 3x3 conv sites and 2x2 max-pools (net_build.hip: "the VGG encoders")
     kFamilyCount
 };
 // What the ResNet family asks beside the blocks per stage; no other family has one, so no other family is asked these questions.
@@ -56,9 +57,12 @@ struct ResNetDesc {
 };
 struct EncoderDesc {
     EncoderFamily family = kFamilyResNet;
-    ResNetDesc resnet;            // read where family == kFamilyResNet only
+    ResNetDesc resnet;            // read where family == kFamilyResNet only; a VGG row keeps two ints of its own in it (vgg_block1, vgg_bn)
     int layers[4] = {};           // ResNet: blocks per stage; MobileNetV2: the feature modules per stage of smp's last four, behind features.1;
-                                  // EfficientNet: the MBConv blocks per stage of smp's last four; DenseNet: the dense layers per block
+                                  // EfficientNet: the MBConv blocks per stage of smp's last four; DenseNet: the dense layers per block;
+                                  // VGG: the convolutions of blocks 2 .. 5
+    int vgg_block1() const { return resnet.expansion; }      // VGG rows: the convolutions of block 1 (1 or 2) ...
+    bool vgg_bn() const { return resnet.groups != 0; }        // ... and whether a BatchNorm follows every convolution (the _bn variants)
     bool basic() const { return family == kFamilyResNet && resnet.expansion == 1; }         // c2 has 64 channels: s2.0 may fold the FPN p2 level in, and the direct sites have three-product images
     bool pointwise() const { return family == kFamilyResNet && resnet.expansion == 4; }     // the autotuner offers k_conv1x1 to the 1x1 sites
 };
@@ -70,7 +74,9 @@ enum StepKind {
     kStepSeGate,     // op: the first of se_module's four parameters; an SE block's gate on `out` in place, with the residual `res`
     kStepMb,         // op: an op of the MobileNetV2 or EfficientNet encoder (fpc_net::mops, whose MbOp::kind names the kernel) from `in` to `out`; a 1x1 adds `res` (C > 0)
     kStepMbGate,     // op: an MBConv block's gate (fpc_net::mgates) from the depthwise output `in`; writes the plan's gate buffer, which the block's project op reads
-    kStepDense       // op: an op of a DenseNet encoder (fpc_net::dops, whose DnOp::kind names the kernel); the op itself carries its buffer offsets, pitches and c0: `in` / `out` say which tensors it reads and writes
+    kStepDense,      // op: an op of a DenseNet encoder (fpc_net::dops, whose DnOp::kind names the kernel); the op itself carries its buffer offsets, pitches and c0: `in` / `out` say which tensors it reads and writes
+    kStepVggStem,    // features.0 of a VGG encoder (fpc_net::vgg0) from the NHWC4 image `in` to `out`, bias or folded BatchNorm and ReLU in its epilogue
+    kStepPool2       // MaxPool2d(2, 2) from `in` to `out` (vgg.hip: k_maxpool2x2); op unused
 };
 struct Step { StepKind kind; int op; Act in, out; bool relu; Act res; };
 inline Step conv_step(int conv, const Act& in, const Act& out, bool relu, const Act& res = Act()) {
@@ -87,6 +93,12 @@ inline Step mb_gate_step(int gate, const Act& x) {      // (`out` is the operand
 }
 inline Step dense_step(int dop, const Act& in, const Act& out) {
     Step s; s.kind = kStepDense; s.op = dop; s.in = in; s.out = out; s.relu = false; return s;
+}
+inline Step vgg_stem_step(const Act& img, const Act& out) {
+    Step s; s.kind = kStepVggStem; s.op = 0; s.in = img; s.out = out; s.relu = true; return s;
+}
+inline Step pool2_step(const Act& in, const Act& out) {
+    Step s; s.kind = kStepPool2; s.op = 0; s.in = in; s.out = out; s.relu = false; return s;
 }
 
 struct fpc_net {
@@ -155,6 +167,10 @@ struct fpc_net {
         int H = 0, W = 0;      // the op's INPUT map
     };
     std::vector<DnOp> dops;
+    // features.0 of a VGG encoder (vgg.hip: k_conv3x3_c3): the weight [64][3][3][3] and, without BatchNorm, the bias are read in place;
+    // with BatchNorm scale / shift hold the fold, the conv bias folded in behind it.  Not a convolution site: one form, not tuned, not
+    // surveyed (its operand is the image).  p_w -1: the plan has none.
+    struct VggStem { int p_w = -1, p_bias = -1, p_bn = -1; size_t scale_off = 0, shift_off = 0; } vgg0;
     struct Dec {
         int lat[4];               // p5, p4, p3, p2 (1x1, bias)
         int seg[7];               // s5.0 s5.1 s5.2 s4.0 s4.1 s3.0 s2.0
@@ -164,7 +180,7 @@ struct fpc_net {
     } dec[4];
 
     // activations (float offsets)
-    Act a_img4, a_stem, a_pool;   // (a_pool: the ResNet and DenseNet families' alone)
+    Act a_img4, a_stem, a_pool;   // (a_pool: the ResNet and DenseNet families'; a VGG plan: a_stem / a_pool are block 1's / block 2's outputs, smp's feature levels 1 and 2)
     Act a_feat[4];                // c2 .. c5: the output of each stage's last block
     Act a_p[4][4];                // [decoder][p5,p4,p3,p2]
     Act a_seg[4][7];              // pre-GroupNorm conv outputs
@@ -218,15 +234,18 @@ struct fpc_net {
         return add_param(p + ".running_var", C) - 3;
     }
 
+    // (bias_first: the bias parameter stands in front of the BatchNorm's four — a VGG site's state-dict order; a site with both has the
+    // bias folded into its shift at load)
     int add_conv(const std::string& wname, int Cin, int Cout, int k, int stride, int pad, const char* bn_prefix,
-                 const char* bias_name, int Cinp = 0, int Kwp = 0) {
+                 const char* bias_name, int Cinp = 0, int Kwp = 0, bool bias_first = false) {
         PackedConv c;
         c.Cin = Cin; c.Cinp = Cinp ? Cinp : Cin; c.Cout = Cout; c.Kh = c.Kw = k; c.stride = stride; c.pad = pad;
         c.Kwp = Kwp ? Kwp : k;
         c.K = c.Cinp * k * c.Kwp; c.Kpad = cdiv(c.K, kConvBK) * kConvBK; c.Npad = cdiv(Cout, kConvNAlign) * kConvNAlign;
         c.p_w = add_param(wname, (int64_t)Cout * Cin * k * k);
+        if (bias_name && bias_first) c.p_bias = add_param(bias_name, Cout);
         if (bn_prefix) c.p_bn = add_bn(bn_prefix, Cout);
-        if (bias_name) c.p_bias = add_param(bias_name, Cout);
+        if (bias_name && !bias_first) c.p_bias = add_param(bias_name, Cout);
         c.w_off = alloc(conv_packed_floats(c.Npad, c.Kpad));      // f32 image + its three bf16 planes
         if (bn_prefix) { c.scale_off = alloc(Cout); c.shift_off = alloc(Cout); }
         c.wino_ok = (k == 3 && stride == 1 && pad == 1 && c.Cinp == Cin && Cin % 8 == 0 && Cout % 64 == 0);

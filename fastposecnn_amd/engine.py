@@ -29,7 +29,7 @@ class NetEngine:
         h = ctypes.c_void_p()
         from fastposecnn_amd.lib import backbone
         name = model.encoder.name
-        by_name = backbone.encoder_family(name) in ("mobilenet_v2", "efficientnet", "densenet")      # a plan fpc_net_create builds by name, no descriptor
+        by_name = backbone.encoder_family(name) in ("mobilenet_v2", "efficientnet", "densenet", "vgg")      # a plan fpc_net_create builds by name, no descriptor
         block, layers = (0, [0] * 4) if by_name else backbone.encoder_layout(name)
         groups, width = (1, 64) if by_name else backbone.encoder_groups(name)
         reduction = 0 if by_name else backbone.encoder_reduction(name)

@@ -28,6 +28,10 @@ behind the stem and blocks 2 / 4 / 8 / 15.
 The DenseNet encoders (densenet121 / 169 / 201) are smp's DenseNetEncoder over torchvision.models.densenet, restated the same way
 (parity unpinned): encoder.features.conv0 / norm0 / relu0 / pool0, dense blocks of pre-activated 1x1 + 3x3 layers whose outputs are
 concatenated, transitions whose post-ReLU tensor is the feature level, norm5 without a ReLU as the last level.  densenet161 is not built.
+The VGG encoders (vgg11 / 13 / 16 / 19 and each with _bn) are smp's VGGEncoder over torchvision.models.vgg.make_layers, restated the
+same way (neither package is here: parity unpinned): one Sequential encoder.features indexed as torchvision's, 3x3 / pad 1
+convolutions with a bias, [BatchNorm,] ReLU, MaxPool2d(2, 2) behind each of five blocks, no classifier; the six feature levels are
+the five blocks' outputs IN FRONT of their pools and the last pool's output alone (the first level is not the input image).
 state_dict names follow smp: encoder.conv1.weight, encoder.layer1.0.conv1.weight, ...,
 <dec>.p5.weight, <dec>.p4.skip_conv.weight, <dec>.seg_blocks.0.block.0.block.0.weight (conv),
 ...block.1.weight (GroupNorm), <head>.0.weight.
@@ -225,7 +229,7 @@ _ENCODERS = {"resnet18": (BasicBlock, [2, 2, 2, 2], 1, 64, 0), "resnet34": (Basi
 
 
 def encoder_family(name):
-    """The one look-up the engine switches on: "mobilenet_v2", "efficientnet" and "densenet" for the encoders fpc_net_create builds by
+    """The one look-up the engine switches on: "mobilenet_v2", "efficientnet", "densenet" and "vgg" for the encoders fpc_net_create builds by
     their names, "resnet" for every encoder that encoder_layout / encoder_groups / encoder_reduction describe; KeyError for a name this
     package does not build."""
     if name == MobileNetV2Encoder.NAME:
@@ -234,6 +238,8 @@ def encoder_family(name):
         return "efficientnet"
     if name in DenseNetEncoder.VARIANTS:
         return "densenet"
+    if name in VGGEncoder.VARIANTS:
+        return "vgg"
     _ENCODERS[name]
     return "resnet"
 
@@ -257,7 +263,8 @@ def encoder_reduction(name):
 
 def _available():
     """The encoder names this package builds, for the KeyError of an unknown one."""
-    return sorted(_ENCODERS) + [MobileNetV2Encoder.NAME] + sorted(EfficientNetEncoder.VARIANTS) + sorted(DenseNetEncoder.VARIANTS)
+    return sorted(_ENCODERS) + [MobileNetV2Encoder.NAME] + sorted(EfficientNetEncoder.VARIANTS) + sorted(DenseNetEncoder.VARIANTS) \
+        + sorted(VGGEncoder.VARIANTS)
 
 
 def _make_stage(block, inplanes, planes, blocks, stride, **kw):
@@ -677,6 +684,64 @@ class DenseNetEncoder(nn.Module):
         return out
 
 
+class VGGEncoder(nn.Module):
+    """smp's VGGEncoder: torchvision's vgg.make_layers(cfg, batch_norm) without avgpool and classifier, restated the same way as the
+    other encoders (neither package is here: parity unpinned).  `features` is ONE nn.Sequential indexed exactly as torchvision's: per
+    convolution Conv2d(3x3, pad 1, bias=True), [BatchNorm2d,] ReLU(inplace), and MaxPool2d(2, 2) behind each of the five blocks of
+    64 / 128 / 256 / 512 / 512 channels; state_dict names are features.N.weight / .bias (and the BatchNorm's five).  smp splits the
+    Sequential at every max-pool, the pool OPENING the next stage, and returns one tensor per stage: six feature levels, the five
+    blocks' outputs in front of their pools (scales 1/1 .. 1/16; the first is NOT the input image) and the last pool's output alone
+    (1/32).  The FPN reads the last four.  VARIANTS: (convolutions per block, BatchNorm) of configurations A / B / D / E.  In the
+    training step the convolutions and BatchNorms reach the native front ends through Conv2d / BatchNorm2d / _bn_act above where
+    those accept the shape; the 2x2 pools and whatever the front ends refuse are torch's."""
+    CHANNELS = (64, 128, 256, 512, 512)
+    CONFIGS = {"vgg11": (1, 1, 2, 2, 2), "vgg13": (2, 2, 2, 2, 2), "vgg16": (2, 2, 3, 3, 3), "vgg19": (2, 2, 4, 4, 4)}
+    VARIANTS = {n + s: (c, bool(s)) for n, c in CONFIGS.items() for s in ("", "_bn")}
+
+    def __init__(self, name="vgg16", in_channels=3, depth=5):
+        super().__init__()
+        if name not in self.VARIANTS:
+            raise KeyError(f"encoder {name!r} not available (have {_available()})")
+        self.name = name
+        self._depth = depth
+        convs, self.batch_norm = self.VARIANTS[name]
+        self.out_channels = self.CHANNELS + (512,)
+        layers, c = [], in_channels
+        for n, v in zip(convs, self.CHANNELS):
+            for _ in range(n):
+                layers.append(Conv2d(c, v, 3, padding=1))
+                if self.batch_norm:
+                    layers.append(BatchNorm2d(v))
+                layers.append(nn.ReLU(inplace=True))
+                c = v
+            layers.append(nn.MaxPool2d(kernel_size=2, stride=2))
+        self.features = nn.Sequential(*layers)
+        # torchvision's initialisation (a checkpoint or a weights file overwrites it)
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+                nn.init.constant_(m.bias, 0)
+            elif isinstance(m, nn.BatchNorm2d):
+                nn.init.constant_(m.weight, 1)
+                nn.init.constant_(m.bias, 0)
+
+    def forward(self, x):
+        feats, mods, i = [], list(self.features), 0
+        while i < len(mods):
+            m = mods[i]
+            if isinstance(m, nn.MaxPool2d):      # a pool closes a stage and opens the next
+                feats.append(x)
+                x = m(x)
+            elif isinstance(m, nn.BatchNorm2d):  # (BatchNorm + ReLU: one native op in the training step)
+                x = _bn_act(x, m, mods[i + 1])
+                i += 1
+            else:
+                x = m(x)
+            i += 1
+        feats.append(x)
+        return feats
+
+
 _WARNED_WEIGHTS = set()
 
 
@@ -691,13 +756,14 @@ def get_encoder(name, in_channels=3, depth=5, weights=None):
     torchvision's (features.0.0.weight, ..., features.18.1.running_var; classifier.* is dropped) or, for efficientnet-b0,
     efficientnet_pytorch's (_conv_stem.weight, ..., _conv_head.weight, _bn1.*; _fc.* is dropped) or, for densenet121 / 169 / 201,
     torchvision's (features.conv0.weight, ..., features.norm5.running_var, with the released files' legacy norm.1 / conv.2 keys
-    rewritten; classifier.* is dropped).  When `weights` is
+    rewritten; classifier.* is dropped) or, for a VGG, torchvision's (features.0.weight, features.0.bias, ...; classifier.* is
+    dropped).  When `weights` is
     requested and no file is configured the encoder stays randomly initialised and a warning says so once per
     encoder — a checkpoint loaded afterwards (load_from_ckpt) overwrites the encoder anyway."""
     import logging
     import os
     cls = MobileNetV2Encoder if name == MobileNetV2Encoder.NAME else EfficientNetEncoder if name in EfficientNetEncoder.VARIANTS \
-        else DenseNetEncoder if name in DenseNetEncoder.VARIANTS else SENetEncoder if name in _ENCODERS and _ENCODERS[name][4] else ResNetEncoder
+        else DenseNetEncoder if name in DenseNetEncoder.VARIANTS else VGGEncoder if name in VGGEncoder.VARIANTS else SENetEncoder if name in _ENCODERS and _ENCODERS[name][4] else ResNetEncoder
     enc = cls(name, in_channels=in_channels, depth=depth)
     enc.requested_weights = weights
     enc.loaded_weights = None

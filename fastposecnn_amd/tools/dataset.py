@@ -40,15 +40,18 @@ from fastposecnn_amd import _native as nat
 from fastposecnn_amd.tools import data_manipulation as dm
 from fastposecnn_amd.tools import json_tools as jt
 
-# segmentation_models_pytorch's preprocessing parameters for the resnet encoders, mobilenet_v2, efficientnet-b0 and densenet121 / 169 / 201 with "imagenet" weights
+# segmentation_models_pytorch's preprocessing parameters for the resnet encoders, mobilenet_v2, efficientnet-b0, densenet121 / 169 / 201 and the VGGs with "imagenet" weights
 # (smp.encoders.get_preprocessing_params; upstream package, absent from the reference tree): RGB, range [0, 1]
 IMAGENET_PARAMS = {"input_space": "RGB", "input_range": [0, 1], "mean": [0.485, 0.456, 0.406],
                    "std": [0.229, 0.224, 0.225]}
 
+VGG_NAMES = tuple(n + s for n in ("vgg11", "vgg13", "vgg16", "vgg19") for s in ("", "_bn"))      # (exact names: no prefix match)
+
 
 def get_preprocessing_params(encoder_name="resnet18", pretrained="imagenet"):
     """smp.encoders.get_preprocessing_params for the encoders this package builds (lib/backbone.py)."""
-    if pretrained != "imagenet" or not str(encoder_name).startswith(("resnet", "resnext", "se_resnet", "mobilenet_v2", "efficientnet-b0", "densenet121", "densenet169", "densenet201")):
+    if pretrained != "imagenet" or not str(encoder_name).startswith(("resnet", "resnext", "se_resnet", "mobilenet_v2", "efficientnet-b0", "densenet121", "densenet169", "densenet201")) \
+            and str(encoder_name) not in VGG_NAMES:
         raise ValueError("no preprocessing parameters for encoder %r / weights %r" % (encoder_name, pretrained))
     return {k: (list(v) if isinstance(v, list) else v) for k, v in IMAGENET_PARAMS.items()}
 

@@ -69,6 +69,7 @@ extern "C" {
  *   fpc_dense_conv3x3, fpc_dense_conv3x3_pack, fpc_dense_conv3x3_form, fpc_dense_norm_pool, fpc_dense_place):
  * and the exit of the four-wave Winograd kernels (fpc_net_set_wino_fast_exit, fpc_wino_tile_patch, fpc_wino_tile_out, fpc_conv2d's -107 .. -113):
  * and the idle wave of the folded s2.0's second phase (fpc_net_set_fold_idle_row):
+ * and the VGG encoders (fpc_net_create's "vgg11" .. "vgg19_bn", fpc_conv3x3_c3, fpc_maxpool2x2_fwd):
  * additions only, every earlier entry point keeps its behaviour. */
 #define FPC_ABI_VERSION 11
 
@@ -1025,6 +1026,31 @@ int fpc_dense_conv3x3_form(int B, int H, int W);
 int fpc_dense_norm_pool(const float* x, const float* s, const float* t, float* skip, float* pooled, int B, int H, int W, int C, int act,
                         fpc_stream_t stream);
 int fpc_dense_place(const float* in, float* out, int64_t M, int C, int ld, fpc_stream_t stream);
+
+/* ---- The VGG encoders' kernels (csrc/vgg.hip), stand-alone.  fpc_net_create("vgg11" | "vgg13" | "vgg16" | "vgg19", each also with
+ * "_bn", ...) builds the plan that runs them: torchvision's vgg.make_layers as smp's VGGEncoder wraps it (F/lib/pose_regressor.py:608-613
+ * through smp.encoders.get_encoder).  features.0 runs on k_conv3x3_c3, every pool on k_maxpool2x2; every other convolution (3x3 /
+ * stride 1 / pad 1, 64 .. 512 channels) is an ordinary convolution site: tuned, surveyed and range-guarded like a ResNet's, on a
+ * Winograd form or the implicit GEMM, with ReLU and the bias — or the BatchNorm folded at load with the bias folded in behind it — in
+ * its epilogue.  fpc_net_conv_count is the encoder's convolutions minus one plus the decoders' 44 (56 for vgg16).  c2 .. c5 are the
+ * outputs of blocks 3, 4, 5 and of the last pool; fpc_net_tensor's "stem" and "pool" name the outputs of blocks 1 and 2 (smp's
+ * feature levels 1 and 2), which outlive the forward.  fpc_net_force_fold(net, 1) and fpc_net_force_stem_pool are refused (c2 has 256
+ * channels; there is no 7x7 stem).  SIZE: such a plan holds full-resolution 64-channel maps; fpc_net_create returns FPC_EINVAL unless
+ * 16 B H W < 2^32 - 2^20 - 8 (features.0's walk; 873 frames of 640 x 480) and (H + 2) W 256 < 2^31 (the implicit GEMM's lane offsets
+ * inside one frame): the smallest bounds of the kernels on the plan.  32 x 480 x 640 is built.
+ * Both: channel-last f32, every pointer 16-byte aligned (FPC_EINVAL otherwise; NULL only where stated), no atomics, a summation
+ * order the shape alone fixes: bit-identical run to run.
+ * fpc_conv3x3_c3 (k_conv3x3_c3; replaces features.0 with its BatchNorm and ReLU): dense 3x3 / stride 1 / pad 1 over fpc_image_nhwc4's
+ *   image in4 [B][H][W][4] — the fourth channel never enters a product, whatever it holds — with w torch's [64][3][3][3] read in
+ *   place: out[b][h][w][n] = act(scale[n] sum + shift[n]), sum over (kh, kw, ci) in that order by fused multiply-adds from 0; scale
+ *   NULL: sum + shift[n] (the bias alone).  act 0, or 1 = ReLU.  Nothing outside the image is read.  Cout must be 64; B, H, W >= 1;
+ *   16 B H W < 2^32 - 2^20 - 8.
+ * fpc_maxpool2x2_fwd (k_maxpool2x2; replaces MaxPool2d(2, 2)): x [B][H][W][C] -> y [B][H / 2][W / 2][C],
+ *   y = max(max(x00, x01), max(x10, x11)).  H, W even and >= 2, C >= 4 and C % 4 == 0, B (H / 2) (W / 2) (C / 4) < 2^32 - 2^20 - 8.  Inputs
+ *   are finite: NaN is outside the contract, as for fpc_maxpool3x3s2_fwd; of -0 and +0 either may be returned. */
+int fpc_conv3x3_c3(const float* in4, const float* w, const float* scale, const float* shift, float* out, int B, int H, int W, int Cout,
+                   int act, fpc_stream_t stream);
+int fpc_maxpool2x2_fwd(const float* x, float* y, int B, int H, int W, int C, fpc_stream_t stream);
 
 /* ---- The depthwise 3x3 convolution and the ReLU6 of the MobileNetV2 encoder in the training step (csrc/depthwise.hip,
  * csrc/batchnorm.hip; lib/train_conv.py: _DepthwiseConv2dFn and batchnorm_act(relu6=True) behind FPC_TRAIN_NATIVE_MBV2=1).  They
