@@ -169,6 +169,10 @@ _SIGNATURES = {
     "fpc_dense_place": (_i, [_vp, _vp, _i64, _i, _i, _vp]),
     "fpc_conv3x3_c3": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "fpc_maxpool2x2_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "fpc_conv3x3_c3_wgrad_workspace_bytes": (_sz, [_i, _i, _i]),
+    "fpc_conv3x3_c3_wgrad_slices": (_i, [_i, _i, _i]),
+    "fpc_conv3x3_c3_wgrad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    "fpc_maxpool2x2_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "fpc_dwconv3x3_dgrad": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "fpc_dwconv3x3_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "fpc_dwconv3x3_wgrad": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),

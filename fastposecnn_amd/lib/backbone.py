@@ -693,7 +693,9 @@ class VGGEncoder(nn.Module):
     blocks' outputs in front of their pools (scales 1/1 .. 1/16; the first is NOT the input image) and the last pool's output alone
     (1/32).  The FPN reads the last four.  VARIANTS: (convolutions per block, BatchNorm) of configurations A / B / D / E.  In the
     training step the convolutions and BatchNorms reach the native front ends through Conv2d / BatchNorm2d / _bn_act above where
-    those accept the shape; the 2x2 pools and whatever the front ends refuse are torch's."""
+    those accept the shape; features.0 (3 -> 64 channels) and the 2x2 pools are torch's unless FPC_TRAIN_NATIVE_VGG=1 — then
+    lib/train_conv's _VggConv0Fn (through Conv2d) and maxpool2x2 (asked here for a pool that is exactly MaxPool2d(2, 2)), on
+    csrc/vgg.hip and csrc/vgg_train.hip —; whatever the front ends refuse is torch's."""
     CHANNELS = (64, 128, 256, 512, 512)
     CONFIGS = {"vgg11": (1, 1, 2, 2, 2), "vgg13": (2, 2, 2, 2, 2), "vgg16": (2, 2, 3, 3, 3), "vgg19": (2, 2, 4, 4, 4)}
     VARIANTS = {n + s: (c, bool(s)) for n, c in CONFIGS.items() for s in ("", "_bn")}
@@ -731,7 +733,11 @@ class VGGEncoder(nn.Module):
             m = mods[i]
             if isinstance(m, nn.MaxPool2d):      # a pool closes a stage and opens the next
                 feats.append(x)
-                x = m(x)
+                # exactly MaxPool2d(2, 2) in the training step: one native op each way (FPC_TRAIN_NATIVE_VGG=1); refused: the module
+                ok = x.is_cuda and torch.is_grad_enabled() and x.requires_grad and not m.return_indices and not m.ceil_mode \
+                    and m.kernel_size in (2, (2, 2)) and m.stride in (2, (2, 2)) and m.padding in (0, (0, 0)) and m.dilation in (1, (1, 1))
+                y = _train_native(ok, "maxpool2x2", x)
+                x = m(x) if y is None else y
             elif isinstance(m, nn.BatchNorm2d):  # (BatchNorm + ReLU: one native op in the training step)
                 x = _bn_act(x, m, mods[i + 1])
                 i += 1

@@ -31,6 +31,12 @@ MIOpen / aten kernels forward and both gradients, aten's hardtanh each way); wit
 _DepthwiseConv2dFn — the forward on the inference kernel k_dw_fwd (act 0, scale 1, shift 0), the data and weight gradients
 beside it in csrc/depthwise.hip, counted in dw_fwd_native / dw_dgrad_native / dw_wgrad_native — and, with FPC_TRAIN_NATIVE_BN=1 as well,
 ConvBNReLU6's BatchNorm and ReLU6 are one native op each way (batchnorm_act(relu6=True), counted in bn_relu6_native beside bn_native).
+features.0 of the VGG encoders (3 -> 64 channels at full resolution, with a bias) and their five MaxPool2d(2, 2) are torch's own by
+default (MIOpen forward and weight gradient, an aten reduction for the bias gradient, aten's pool with its int64 index plane and
+scatter); with FPC_TRAIN_NATIVE_VGG=1 the convolution is _VggConv0Fn — fpc_image_nhwc4 and the inference kernel k_conv3x3_c3 (shift =
+the bias, no activation) forward, k_c3_wgrad backward: the weight and the bias gradient from one pass over dy — and a pool is
+_MaxPool2x2Fn (k_maxpool2x2 / k_maxpool2x2_bwd, the arg-max recomputed from x; csrc/vgg_train.hip), counted in c3_fwd_native /
+c3_wgrad_native / pool2_fwd_native / pool2_bwd_native: no MIOpen convolution and no aten pooling kernel is left in a VGG step then.
 
 The tiling / Winograd form of a shape is chosen once, by timing the candidates on the first call with that shape (this
 synchronises: it happens in the warm-up steps).  f32 operands, accumulation and results, products in plain f32 or as the
@@ -51,7 +57,8 @@ counters = {"fwd_native": 0, "dgrad_native": 0, "wgrad_native": 0, "dgrad_aten":
             "grouped_fwd_native": 0, "grouped_dgrad_native": 0, "grouped_wgrad_native": 0,
             "stem_fwd_native": 0, "stem_wgrad_native": 0, "pool_fwd_native": 0, "pool_bwd_native": 0,
             "bn_native": 0, "bn_torch": 0, "se_fwd_native": 0, "se_bwd_native": 0, "se_torch": 0,
-            "dw_fwd_native": 0, "dw_dgrad_native": 0, "dw_wgrad_native": 0, "bn_relu6_native": 0}
+            "dw_fwd_native": 0, "dw_dgrad_native": 0, "dw_wgrad_native": 0, "bn_relu6_native": 0,
+            "c3_fwd_native": 0, "c3_wgrad_native": 0, "pool2_fwd_native": 0, "pool2_bwd_native": 0}
 
 
 # Weight-gradient sinks (round 6): an optimiser that keeps `p.grad` as views of one flat buffer (train_parallel.py) registers
@@ -596,6 +603,107 @@ def maxpool3x3s2(x):
     return _MaxPoolFn.apply(x)
 
 
+# ---- features.0 of the VGG encoders (3 -> 64 channels, 3x3 / stride 1 / pad 1) and their 2x2 / stride-2 max-pools ------------------
+
+# Off by default: with it off features.0 and the pools are torch's own, forward and backward, as before (DESIGN.md 4.2a'''''''''''').
+NATIVE_VGG = bool(int(os.environ.get("FPC_TRAIN_NATIVE_VGG", "0")))
+_C3_WALK_LIMIT = 2 ** 32 - 4096 * 256 - 8      # csrc/common.hpp's kWalkLimit: 16 B H W below it (csrc/vgg.hip: conv3x3_c3_ok)
+_c3_zero_shift = {}      # device index -> zeros [64]: the forward kernel's shift for a convolution without bias
+
+
+def _vgg_c3_ok(x, w, bias, stride, pad, groups=1):
+    return (NATIVE_VGG and ENABLED and torch.is_tensor(x) and _f32_cuda_4d(x) and w.dtype == torch.float32 and w.device == x.device
+            and tuple(w.shape) == (64, 3, 3, 3) and stride == 1 and pad == 1 and groups == 1 and x.shape[1] == 3
+            and (bias is None or (_f32_param(bias, x.device) and tuple(bias.shape) == (64,)))
+            and x.shape[0] >= 1 and x.shape[2] >= 1 and x.shape[3] >= 1 and 16 * x.shape[0] * x.shape[2] * x.shape[3] < _C3_WALK_LIMIT
+            and not x.requires_grad             # there is no data gradient here: an input that needs one stays on torch
+            and torch.is_grad_enabled() and (w.requires_grad or (bias is not None and bias.requires_grad)))
+
+
+class _VggConv0Fn(torch.autograd.Function):
+    """features.0 of a VGG encoder on the native kernels: y = conv(x, w) + bias raw (BatchNorm or ReLU follows), channel-last, on
+    k_conv3x3_c3.  The NHWC4 image is saved for the backward, which is the weight and bias gradient from one pass over dy
+    (fpc_conv3x3_c3_wgrad, csrc/vgg_train.hip): x gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias):
+        x = _operand(x, aligned=True, nhwc=False)      # the planar image
+        w = _operand(w, aligned=True, nhwc=False)
+        B, _, H, W = x.shape
+        L = nat.lib()
+        img4 = torch.empty((B, H, W, 4), dtype=torch.float32, device=x.device)
+        nat.check(L.fpc_image_nhwc4(x.data_ptr(), img4.data_ptr(), B, H, W, nat.stream()), "fpc_image_nhwc4")
+        out = torch.empty((B, 64, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        if bias is None:
+            shift = _c3_zero_shift.get(x.device.index)
+            if shift is None:
+                shift = _c3_zero_shift[x.device.index] = torch.zeros(64, dtype=torch.float32, device=x.device)
+        else:
+            shift = bias.detach()
+        nat.check(L.fpc_conv3x3_c3(img4.data_ptr(), w.data_ptr(), None, shift.data_ptr(), out.data_ptr(), B, H, W, 64, 0, nat.stream()),
+                  "fpc_conv3x3_c3 (training)")
+        ctx.has_bias = bias is not None
+        ctx.save_for_backward(img4, w)
+        counters["c3_fwd_native"] += 1
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        img4, w = ctx.saved_tensors
+        need_w, need_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        if not (need_w or need_b):
+            return None, None, None
+        B, H, W, _ = img4.shape
+        gy = _operand(gy, aligned=True)
+        L = nat.lib()
+        sink = _take_sink(w, aligned=True) if need_w else None
+        gw = sink.view if sink is not None else torch.empty((64, 3, 3, 3), dtype=torch.float32, device=gy.device)
+        gb = torch.empty(64, dtype=torch.float32, device=gy.device) if need_b else None
+        ws = nat.workspace("train_c3_wgrad", gy.device, L.fpc_conv3x3_c3_wgrad_workspace_bytes(B, H, W))
+        nat.check(L.fpc_conv3x3_c3_wgrad(img4.data_ptr(), gy.data_ptr(), gw.data_ptr(), nat.ptr(gb), B, H, W, ws.data_ptr(), ws.numel(),
+                                         nat.stream()), "fpc_conv3x3_c3_wgrad")
+        counters["c3_wgrad_native"] += 1
+        if sink is not None:
+            _commit_sink(sink)
+            gw = None
+        return None, gw if need_w else None, gb
+
+
+class _MaxPool2x2Fn(torch.autograd.Function):
+    """max_pool2d(x, 2, 2) on a dense channel-last tensor (k_maxpool2x2).  Only x is saved — it is alive anyway: the ReLU / BatchNorm
+    in front saved it as its output —; the backward finds each window's arg-max again, by torch's rule (the first maximum in row-major
+    order), and writes dy or 0 to every element (csrc/vgg_train.hip: k_maxpool2x2_bwd).  No index plane."""
+
+    @staticmethod
+    def forward(ctx, x):
+        B, C, H, W = x.shape
+        y = torch.empty((B, C, H // 2, W // 2), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        nat.check(nat.lib().fpc_maxpool2x2_fwd(x.data_ptr(), y.data_ptr(), B, H, W, C, nat.stream()), "fpc_maxpool2x2_fwd (training)")
+        ctx.save_for_backward(x)
+        counters["pool2_fwd_native"] += 1
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, = ctx.saved_tensors
+        B, C, H, W = x.shape
+        gy = _operand(gy, aligned=True)
+        dx = torch.empty_like(x, memory_format=torch.channels_last)
+        nat.check(nat.lib().fpc_maxpool2x2_bwd(x.data_ptr(), gy.data_ptr(), dx.data_ptr(), B, H, W, C, nat.stream()), "fpc_maxpool2x2_bwd")
+        counters["pool2_bwd_native"] += 1
+        return dx
+
+
+def maxpool2x2(x):
+    """max_pool2d(x, 2, 2) on the native kernels, forward and backward, for a dense channel-last f32 GPU tensor with even H and W and
+    C % 4 == 0 that requires grad under autograd, with NATIVE_VGG set; None otherwise (the caller keeps torch's module)."""
+    if not (NATIVE_VGG and ENABLED and torch.is_tensor(x) and _f32_cuda_4d(x) and torch.is_grad_enabled() and x.requires_grad
+            and x.shape[0] >= 1 and x.shape[1] >= 4 and x.shape[1] % 4 == 0 and x.shape[2] >= 2 and x.shape[3] >= 2
+            and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and x.numel() // 16 < _C3_WALK_LIMIT and _dense_nhwc(x)):
+        return None
+    return _MaxPool2x2Fn.apply(x)
+
+
 def conv2d(x, w, bias, stride, pad, groups=1):
     """Training-mode convolution: native when the shapes allow it, torch otherwise (same signature either way).  A grouped
     convolution (conv2 of the ResNeXt blocks) is torch's own on the channel-last tensor, forward and backward, and like the stem
@@ -605,9 +713,13 @@ def conv2d(x, w, bias, stride, pad, groups=1):
     (FPC_TRAIN_NATIVE_STEM=1) is set and it is the 3 -> 64 / stride-2 / pad-3 convolution without bias of an even-sized image
     that needs no gradient: then _StemConvFn, counted in stem_fwd_native / stem_wgrad_native.  A DEPTHWISE 3x3 / pad-1 / stride-1 or
     -2 convolution without bias (groups = C, C % 4 == 0) under autograd is _DepthwiseConv2dFn when NATIVE_MBV2
-    (FPC_TRAIN_NATIVE_MBV2=1) is set, counted in dw_fwd_native / dw_dgrad_native / dw_wgrad_native; it is asked first."""
+    (FPC_TRAIN_NATIVE_MBV2=1) is set, counted in dw_fwd_native / dw_dgrad_native / dw_wgrad_native; it is asked first.  features.0 of
+    a VGG encoder (3 -> 64 channels, 3x3 / stride 1 / pad 1, with or without a bias, of an image that needs no gradient) is torch's
+    own unless NATIVE_VGG (FPC_TRAIN_NATIVE_VGG=1) is set: then _VggConv0Fn, counted in c3_fwd_native / c3_wgrad_native."""
     if groups == 1 and _stem_ok(x, w, bias, stride, pad):
         return _StemConvFn.apply(x, w)
+    if groups == 1 and _vgg_c3_ok(x, w, bias, stride, pad):
+        return _VggConv0Fn.apply(x, w, bias)
     if groups != 1 and _depthwise_ok(x, w, bias, stride, pad, groups):
         return _DepthwiseConv2dFn.apply(x, w, int(stride))
     if groups != 1 and _grouped_ok(x, w, bias, stride, pad, groups):

@@ -11,6 +11,8 @@ What runs where (stated in the JSON line as well):
     the SE-ResNet blocks' gate + add + ReLU: torch's modules, or csrc/se.hip + csrc/se_train.hip with FPC_TRAIN_NATIVE_SE=1
     the MobileNetV2 blocks' depthwise 3x3 and ReLU6: torch's modules, or csrc/depthwise.hip (and, with
     FPC_TRAIN_NATIVE_BN=1, ReLU6 inside csrc/batchnorm.hip) with FPC_TRAIN_NATIVE_MBV2=1
+    the VGG encoders' features.0 (3 -> 64 channels) and 2x2 max-pools: torch's modules, or csrc/vgg.hip + csrc/vgg_train.hip with
+    FPC_TRAIN_NATIVE_VGG=1
     (FPC_TRAIN_NATIVE_CONV=0 returns every convolution and upsampling to torch: the A/B this file's numbers come with);
   * everything after the logits, forward: the inference kernels (class compression, connected components, aggregation,
     RANSAC vote, RT); backward: csrc/train.hip through lib/train_functions.py;
@@ -82,6 +84,9 @@ def _conv_note():
             ("; the MobileNetV2 blocks' depthwise 3x3 fpc_dwconv3x3 forward, fpc_dwconv3x3_dgrad / _wgrad backward (dw_fwd_native / "
              "dw_dgrad_native / dw_wgrad_native), ReLU6 inside the native BatchNorm where that runs (bn_relu6_native) "
              if train_conv.NATIVE_MBV2 else "; the MobileNetV2 blocks' depthwise 3x3 and ReLU6 torch (FPC_TRAIN_NATIVE_MBV2=1: native) ") +
+            ("; the VGG encoders' features.0 fpc_image_nhwc4 + fpc_conv3x3_c3 forward, fpc_conv3x3_c3_wgrad backward, their 2x2 max-pools "
+             "fpc_maxpool2x2_fwd/bwd (c3_fwd_native / c3_wgrad_native / pool2_fwd_native / pool2_bwd_native) "
+             if train_conv.NATIVE_VGG else "; the VGG encoders' features.0 and 2x2 max-pools torch (FPC_TRAIN_NATIVE_VGG=1: native) ") +
             f"(calls so far: {dict(c)})")
 
 

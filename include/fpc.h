@@ -1052,6 +1052,31 @@ int fpc_conv3x3_c3(const float* in4, const float* w, const float* scale, const f
                    int act, fpc_stream_t stream);
 int fpc_maxpool2x2_fwd(const float* x, float* y, int B, int H, int W, int C, fpc_stream_t stream);
 
+/* The training step's VGG pieces (csrc/vgg_train.hip, lib/train_conv.py: _VggConv0Fn, _MaxPool2x2Fn, behind FPC_TRAIN_NATIVE_VGG=1;
+ * ABI 11, additive).  They replace the backward of features.0 (cuDNN's weight gradient and aten's bias reduction under autograd in
+ * the reference) and of MaxPool2d(2, 2) (aten's index plane and scatter) inside smp's VGG encoder, reached from
+ * F/lib/pose_regressor.py:608-613; the forwards in training are fpc_image_nhwc4 + fpc_conv3x3_c3 (scale NULL, shift = the bias,
+ * act 0) and fpc_maxpool2x2_fwd above.  f32 throughout; no atomics and a fixed summation order: bit-identical run to run.  Every
+ * entry returns FPC_EINVAL BEFORE any launch for a shape outside its class and for a pointer that is null (db excepted) or not
+ * 16-byte aligned.
+ *
+ * fpc_conv3x3_c3_wgrad (k_c3_wgrad + k_c3_wgrad_reduce): dw OIHW [64][3][3][3] and db [64], every element of both overwritten,
+ *   dw[co][ci][kh][kw] = sum over b, y, x of dy[b][y][x][co] img4[b][y + kh - 1][x + kw - 1][ci], zero outside the image;
+ *   db[co] = sum over b, y, x of dy[b][y][x][co], from the same pass over dy; db NULL: not computed.  img4 [B][H][W][4]
+ *   (fpc_image_nhwc4's; the fourth channel never enters a result, whatever it holds), dy NHWC [B][H][W][64] contiguous.  Shape class:
+ *   fpc_conv3x3_c3's (B, H, W >= 1, 16 B H W < 2^32 - 2^20 - 8).  Exact f32 products on the matrix cores.  The list of (frame, row,
+ *   64-pixel segment) units is cut into fpc_conv3x3_c3_wgrad_slices(B, H, W) contiguous slices — a function of the shape alone —,
+ *   one partial [64][48] per slice, added in slice order in double.  ws: fpc_conv3x3_c3_wgrad_workspace_bytes(B, H, W) = slices *
+ *   64 * 48 * 4 bytes, 16-byte aligned (too small: FPC_EINVAL).  Slices and bytes of a refused shape are 0.
+ * fpc_maxpool2x2_bwd (k_maxpool2x2_bwd): dx [B][H][W][C] from x and dy [B][H / 2][W / 2][C], every element written once: dy of a
+ *   window goes to the window's FIRST maximum in row-major order (torch's rule), 0 to its other three elements.  Shape class:
+ *   fpc_maxpool2x2_fwd's.  Inputs are finite: NaN is outside the contract. */
+size_t fpc_conv3x3_c3_wgrad_workspace_bytes(int B, int H, int W);
+int fpc_conv3x3_c3_wgrad_slices(int B, int H, int W);
+int fpc_conv3x3_c3_wgrad(const float* img4, const float* dy, float* dw, float* db, int B, int H, int W, void* ws, size_t ws_bytes,
+                         fpc_stream_t stream);
+int fpc_maxpool2x2_bwd(const float* x, const float* dy, float* dx, int B, int H, int W, int C, fpc_stream_t stream);
+
 /* ---- The depthwise 3x3 convolution and the ReLU6 of the MobileNetV2 encoder in the training step (csrc/depthwise.hip,
  * csrc/batchnorm.hip; lib/train_conv.py: _DepthwiseConv2dFn and batchnorm_act(relu6=True) behind FPC_TRAIN_NATIVE_MBV2=1).  They
  * replace autograd through torch.nn.Conv2d(groups = C) and nn.ReLU6 inside smp's MobileNetV2 encoder (cuDNN's grouped kernels and
