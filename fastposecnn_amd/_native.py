@@ -106,6 +106,7 @@ _SIGNATURES = {
     "fpc_net_guard_ranges": (_i, [_vp, ctypes.POINTER(ctypes.c_uint32), _i, _f, _f]),
     "fpc_net_guarded": (_i, [_vp, _i]),
     "fpc_stem_pool_tasks": (_i, [_i, _i, ctypes.POINTER(_i64)]),
+    "fpc_xcd_order": (_i, [_i, _i, _i64, _i, _i, ctypes.POINTER(_i64)]),
     "fpc_wino_pack_geometry": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(_i64)]),
     "fpc_net_set_wino_pack": (_i, [_vp, _i]),
     "fpc_net_set_wino_orient": (_i, [_vp, _i]),

@@ -1,8 +1,9 @@
 // conv2d.hip — the stand-alone convolution entry points of include/fpc.h, outside any network: fpc_conv2d* (one convolution on any plan code, for unit
-// tests, micro-benchmarks and the training path), fpc_conv2d_grouped*, and the host-arithmetic exports of the launch geometry (fpc_stem_pool_tasks,
+// tests, micro-benchmarks and the training path), fpc_conv2d_grouped*, and the host-arithmetic exports of the launch geometry (fpc_stem_pool_tasks, fpc_xcd_order,
 // fpc_wino_pack_geometry, fpc_wino_orient_geometry, fpc_wino_recip, fpc_wino_decode, fpc_wino_xshare_rule, fpc_wino_tile_*).  They plan with conv_plan.hpp and launch through conv_launch.hip.
 #include <algorithm>
 
+#include "conv_device.hpp"
 #include "conv_plan.hpp"
 
 using namespace fpc;
@@ -14,6 +15,16 @@ extern "C" int fpc_stem_pool_tasks(int Ho, int Wo, int64_t* out4) {
     long long o[4];
     stem_pool_tasks(Ho, Wo, kStemPoolBand, o);
     for (int i = 0; i < 4; ++i) out4[i] = o[i];
+    return FPC_OK;
+}
+
+// The XCD-banded workgroup order (conv_device.hpp; host arithmetic, no device): out4 = xcd_logical(block, grid), then first, end and
+// step of xcd_span(total, per_block, slot, block, grid).
+extern "C" int fpc_xcd_order(int grid, int block, int64_t total, int per_block, int slot, int64_t* out4) {
+    if (!out4 || grid < 1 || block < 0 || block >= grid || per_block < 1 || slot < 0 || slot >= per_block || total < 0 || total >= kWalkLimit)
+        return FPC_EINVAL;
+    const XcdSpan w = xcd_span((unsigned)total, (unsigned)per_block, (unsigned)slot, (unsigned)block, (unsigned)grid);
+    out4[0] = xcd_logical((unsigned)block, (unsigned)grid); out4[1] = w.first; out4[2] = w.end; out4[3] = w.step;
     return FPC_OK;
 }
 

@@ -91,22 +91,50 @@ __device__ __forceinline__ float swish(float v) { return div_ieee(v, 1.0f + expf
 // squeezed to 96 — did not shorten the 1200-workgroup launches: their workgroups share the matrix pipe.)
 constexpr int kLdsRow = kConvBK;
 
-// XCD-banded grid-stride walk of `total` items in row order (round 5).  Workgroups go to the 8 XCDs round-robin by linear id; a
-// kernel whose items read NEIGHBOURING input rows (pooling windows, bilinear taps) then makes every XCD's L2 fetch every input
-// row.  With a grid that is a multiple of 8, XCD x = blockIdx.x % 8 walks the x-th contiguous eighth of the items with its own
-// blocks, so an input row is fetched by one L2 (two at a band border).  lo / hi / step in items; 32-bit (launchers check).
-struct XcdWalk { unsigned first, end, step; };
-__device__ __forceinline__ XcdWalk xcd_walk(unsigned total) {
-    if ((gridDim.x & 7) != 0) return XcdWalk{blockIdx.x * blockDim.x + threadIdx.x, total, gridDim.x * blockDim.x};
-    const unsigned per = (total + 7) >> 3, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const unsigned lo = xcd * per, hi = min(lo + per, total);
-    return XcdWalk{lo + slot * blockDim.x + threadIdx.x, hi, (gridDim.x >> 3) * blockDim.x};
+// The XCD-banded workgroup order.  Workgroups go to the 8 XCDs round-robin by linear id, and each XCD has its own L2; a kernel whose
+// items read NEIGHBOURING rows (pooling windows, bilinear taps, the channel tiles of one pixel tile) then makes every L2 fetch every
+// row.  With a grid that is a multiple of 8, XCD x = block % 8 works on the x-th contiguous eighth of the tile or item list with its
+// own blocks, so a row is fetched by one L2 (two at a band border).  The contract:
+//   - the grid is a multiple of 8 for the banded order (launchers: xcd_grid); any other grid runs in plain launch order;
+//   - where the launcher rounded the grid up, a remapped id may lie past the list: the kernel compares it with the list's length,
+//   - and such a workgroup leaves before any barrier (a kernel with a barrier and no such test launches its exact count).
+// xcd_logical is a permutation of [0, grid); the spans of xcd_span over all blocks and slots visit [0, total) once each
+// (tests/test_xcd_order_host.py through fpc_xcd_order).  A span is 32-bit: `first + k * step` must not wrap, so launchers keep
+// total below kWalkLimit (common.hpp).
+__host__ __device__ __forceinline__ unsigned xcd_banded(unsigned block, unsigned grid) { return (block & 7) * (grid >> 3) + (block >> 3); }      // grid % 8 == 0
+__host__ __device__ __forceinline__ unsigned xcd_logical(unsigned block, unsigned grid) { return (grid & 7) == 0 ? xcd_banded(block, grid) : block; }
+// The items of slot `slot` (of per_block per workgroup and step) of workgroup `block`: first, first + step, ... below end.  T is the
+// caller's index type (unsigned; int in stem.hip, whose task arithmetic is signed).  The other four keep the caller's types: plain
+// integers on the host, and in a kernel the four below, each READ WHERE IT IS USED, on the taken side of the test, as the hand-written
+// walks read them (as values they are loaded in front of the test, and every walking kernel's instruction list changes).
+struct XcdBlockDim { __device__ __forceinline__ operator unsigned() const { return blockDim.x; } };
+struct XcdThreadIdx { __device__ __forceinline__ operator unsigned() const { return threadIdx.x; } };
+struct XcdBlockIdx { __device__ __forceinline__ operator unsigned() const { return blockIdx.x; } };
+struct XcdGridDim { __device__ __forceinline__ operator unsigned() const { return gridDim.x; } };
+template <class T> struct XcdSpanT { T first, end, step; };
+using XcdSpan = XcdSpanT<unsigned>;
+template <class T, class P, class S, class B, class G>
+__host__ __device__ __forceinline__ XcdSpanT<T> xcd_span(T total, P per_block, S slot, B block, G grid) {
+    if ((grid & 7) != 0) return XcdSpanT<T>{(T)(block * per_block + slot), total, (T)(grid * per_block)};
+    const T per = (total + 7) >> 3;
+    const auto band = block & 7, turn = block >> 3;      // this workgroup's XCD and its place among that XCD's workgroups
+    const T lo = (T)(band * per), hi = lo + per < total ? lo + per : total;      // (no min(): the host has none for unsigned)
+    return XcdSpanT<T>{(T)(lo + turn * per_block + slot), hi, (T)((grid >> 3) * per_block)};
 }
+__device__ __forceinline__ unsigned xcd_block() { return xcd_logical(blockIdx.x, gridDim.x); }
+// ... without the test, for a launcher that rounds EVERY grid up to a multiple of 8 (the grouped 3x3 family: with the test its stride-2
+// sites measured 1 - 2.6 % slower, profiles/xcd_order_ledger.md)
+__device__ __forceinline__ unsigned xcd_block_rounded() { return xcd_banded(blockIdx.x, gridDim.x); }
+__device__ __forceinline__ XcdSpan xcd_walk(unsigned total) { return xcd_span(total, XcdBlockDim{}, XcdThreadIdx{}, XcdBlockIdx{}, XcdGridDim{}); }
+template <class T>      // rpb rows a workgroup and step, this thread on row slot r of them
+__device__ __forceinline__ XcdSpanT<T> xcd_rows(T total, T rpb, T r) { return xcd_span(total, rpb, r, XcdBlockIdx{}, XcdGridDim{}); }
+
+// the launcher half: a grid of at least 8 workgroups rounded up to a multiple of 8, a smaller one as it is (plain order)
+inline long long xcd_grid(long long blocks) { return blocks < 8 ? blocks : (blocks + 7) / 8 * 8; }
 
 inline int stream_grid(long long work_items) {
-    long long g = (work_items + 255) / 256;
-    g = g < 1 ? 1 : (g > 4096 ? 4096 : g);
-    return (int)(g >= 8 ? (g + 7) / 8 * 8 : g);      // a multiple of 8: the XCD-banded walks (xcd_walk) need it, the others do not mind
+    const long long g = (work_items + 255) / 256;
+    return (int)xcd_grid(g < 1 ? 1 : (g > 4096 ? 4096 : g));
 }
 
 }  // namespace fpc

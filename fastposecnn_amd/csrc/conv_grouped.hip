@@ -20,7 +20,7 @@
 // results are bit-identical run to run.  Workgroups run in an XCD-aware order: with the grid a multiple of 8, XCD x takes the
 // x-th contiguous eighth of the (frame, tile row, tile column, channel block) list, so tiles that share halo rows and the
 // channel blocks of one tile meet in one L2.
-#include "net_kernels.hpp"
+#include "conv_device.hpp"
 
 namespace fpc {
 
@@ -73,8 +73,8 @@ __global__ __launch_bounds__((GrpGeom<CG, STRIDE>::THREADS)) void k_conv3x3_grou
     __shared__ __attribute__((aligned(16))) float s_in[G::IN_FLOATS];
     __shared__ __attribute__((aligned(16))) float s_w[G::W_FLOATS];
     const int tid = threadIdx.x;
-    // XCD-aware order (the launcher rounds the grid up to a multiple of 8; the ids past the list leave before any barrier)
-    const int bid = (int)((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3));
+    // XCD-banded order (conv_device.hpp; the launcher rounds every grid), the channel chunk fastest; the ids past the list leave before any barrier
+    const int bid = (int)xcd_block_rounded();
     const int nchunk = a.C / kGrpCC;
     if (bid >= a.B * a.ty * a.tx * nchunk) return;
     const int chunk = bid % nchunk;
@@ -164,7 +164,7 @@ int launch_grouped_t(GroupedArgs a, hipStream_t s) {
     a.ty = cdiv(a.Ho, kGrpTH);
     const long long blocks = (long long)a.B * a.ty * a.tx * (a.C / kGrpCC);
     if (blocks < 1 || blocks > (1LL << 30)) return FPC_EINVAL;
-    const unsigned grid = (unsigned)((blocks + 7) / 8 * 8);
+    const unsigned grid = (unsigned)xcd_grid(blocks < 8 ? 8 : blocks);      // always banded: at least 8 workgroups
     hipLaunchKernelGGL((k_conv3x3_grouped<CG, STRIDE>), dim3(grid), dim3(G::THREADS), 0, s, a);
     return check_launch();
 }

@@ -24,7 +24,7 @@
 
 #include <algorithm>
 
-#include "net_kernels.hpp"
+#include "conv_device.hpp"
 
 #define FPC_TRY(x) do { int rc__ = (x); if (rc__) return rc__; } while (0)
 
@@ -62,8 +62,8 @@ __global__ __launch_bounds__(kGtThreads) void k_conv3x3_grouped_dgrad_s2(const G
     __shared__ __attribute__((aligned(16))) float s_dy[G::IN_FLOATS];
     __shared__ __attribute__((aligned(16))) float s_w[G::W_FLOATS];
     const int tid = threadIdx.x;
-    // XCD-aware order, as k_conv3x3_grouped (the ids past the list leave before any barrier)
-    const int bid = (int)((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3));
+    // XCD-banded order, as k_conv3x3_grouped (the ids past the list leave before any barrier)
+    const int bid = (int)xcd_block_rounded();
     const int nchunk = a.C / kGtCC;
     if (bid >= a.B * a.ty * a.tx * nchunk) return;
     const int chunk = bid % nchunk;
@@ -152,7 +152,7 @@ int launch_dgrad_s2_t(GrpDgradArgs a, hipStream_t s) {
     a.tx = cdiv(a.Wi, 2 * DgGeom<CG>::BW);
     const long long blocks = (long long)a.B * a.ty * a.tx * (a.C / kGtCC);
     if (blocks < 1 || blocks > (1LL << 30)) return FPC_EINVAL;
-    const unsigned grid = (unsigned)((blocks + 7) / 8 * 8);
+    const unsigned grid = (unsigned)xcd_grid(blocks < 8 ? 8 : blocks);      // always banded: at least 8 workgroups
     hipLaunchKernelGGL((k_conv3x3_grouped_dgrad_s2<CG>), dim3(grid), dim3(kGtThreads), 0, s, a);
     return check_launch();
 }

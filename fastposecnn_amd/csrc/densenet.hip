@@ -29,11 +29,6 @@ namespace fpc {
 
 namespace {
 
-// logical workgroup of a launch whose grid is a multiple of 8: XCD x takes the x-th contiguous eighth
-__device__ __forceinline__ unsigned xcd_block() {
-    return (gridDim.x & 7) == 0 ? (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
-}
-
 __device__ __forceinline__ f32x4 pre_act(f32x4 v, f32x4 s, f32x4 t) {
     f32x4 r;
 #pragma unroll
@@ -319,7 +314,7 @@ __global__ __launch_bounds__(256) void k_dense_norm_pool(const float* __restrict
                                                          float* __restrict__ skip, float* __restrict__ pooled, unsigned total, int H, int W,
                                                          int CQ, int act) {
     const int C = 4 * CQ;
-    const XcdWalk wk = xcd_walk(total);
+    const XcdSpan wk = xcd_walk(total);
     for (unsigned i = wk.first; i < wk.end; i += wk.step) {
         const unsigned cq = i % (unsigned)CQ, px = i / (unsigned)CQ;
         const f32x4 sc = *reinterpret_cast<const f32x4*>(s + 4 * cq), sh = *reinterpret_cast<const f32x4*>(t + 4 * cq);
@@ -348,7 +343,7 @@ __global__ __launch_bounds__(256) void k_dense_norm_pool(const float* __restrict
 
 // in [M][C] -> out[m][0 .. C) of rows ld apart
 __global__ __launch_bounds__(256) void k_dense_place(const float* __restrict__ in, float* __restrict__ out, unsigned total, int CQ, int ld) {
-    const XcdWalk wk = xcd_walk(total);
+    const XcdSpan wk = xcd_walk(total);
     for (unsigned i = wk.first; i < wk.end; i += wk.step) {
         const unsigned cq = i % (unsigned)CQ, m = i / (unsigned)CQ;
         *reinterpret_cast<f32x4*>(out + (size_t)m * ld + 4 * cq) = *reinterpret_cast<const f32x4*>(in + (size_t)i * 4);
@@ -372,8 +367,7 @@ int launch_dense_pw(const float* in, const float* s1, const float* t1, const flo
     const int tile = form ? 32 : 16;
     const long long mtiles = (M + tile - 1) / tile, ntiles = Cout / tile, waves = mtiles * ntiles;
     if (waves >= (1LL << 31)) return FPC_EINVAL;
-    long long grid = form ? (waves + 3) / 4 : waves;      // (form 0: a workgroup per tile)
-    if (grid >= 8) grid = (grid + 7) / 8 * 8;      // the XCD bands; the workgroups past the last tile leave at once
+    const long long grid = xcd_grid(form ? (waves + 3) / 4 : waves);      // (form 0: a workgroup per tile); the workgroups past the last tile leave at once
     const dim3 g((unsigned)grid), b(256);
 #define FPC_DENSE_PW(KERNEL) hipLaunchKernelGGL(KERNEL, g, b, 0, s, in, s1, t1, w, s2, t2, out, (unsigned)M, K, ldi, ldo, act, (unsigned)mtiles, (unsigned)ntiles)
     if (form) { if (s1) FPC_DENSE_PW(k_dense_pw32<true>); else FPC_DENSE_PW(k_dense_pw32<false>); }
@@ -400,8 +394,7 @@ int launch_dense_conv3(const float* in, const float* wt, float* out, int B, int 
     if (form < 0) form = dense_conv3_form(M);
     if (form) {
         const long long mtiles = (M + 63) / 64;
-        long long grid = (mtiles + 3) / 4;
-        if (grid >= 8) grid = (grid + 7) / 8 * 8;
+        const long long grid = xcd_grid((mtiles + 3) / 4);
         hipLaunchKernelGGL(k_dense_conv3_tile, dim3((unsigned)grid), dim3(256), 0, s, in, wt, out, (unsigned)M, H, W, c0, ldo, (unsigned)mtiles);
     } else {
         // (exactly one workgroup per 16 pixels: the kernel has a barrier, so no workgroup may be past the last tile; a grid that is

@@ -68,7 +68,7 @@ __global__ __launch_bounds__(256) void k_dw_fwd(const float* __restrict__ in, co
                                                 int act) {
     constexpr int TW = S == 1 ? 4 : 2, NC = (TW - 1) * S + K;
     const int C = 4 * CQ;
-    const XcdWalk wk = xcd_walk(total);
+    const XcdSpan wk = xcd_walk(total);
     for (unsigned g = wk.first; g < wk.end; g += wk.step) {
         const unsigned cq = g % (unsigned)CQ;
         unsigned t = g / (unsigned)CQ;
@@ -136,7 +136,7 @@ __global__ __launch_bounds__(256) void k_dw_dgrad_s1(const float* __restrict__ d
                                                      unsigned total, int H, int W, int WT, int CQ) {
     constexpr int TW = 4, NC = TW + K - 1;
     const int C = 4 * CQ;
-    const XcdWalk wk = xcd_walk(total);
+    const XcdSpan wk = xcd_walk(total);
     for (unsigned g = wk.first; g < wk.end; g += wk.step) {
         const unsigned cq = g % (unsigned)CQ;
         unsigned t = g / (unsigned)CQ;
@@ -244,7 +244,7 @@ template <int K, int PB>
 __global__ __launch_bounds__(256) void k_dw_dgrad_s2(const float* __restrict__ dy, const float* __restrict__ w, float* __restrict__ dx,
                                                      unsigned total, int Hi, int Wi, int Ho, int Wo, int WT, int CQ) {
     const int C = 4 * CQ;
-    const XcdWalk wk = xcd_walk(total);
+    const XcdSpan wk = xcd_walk(total);
     for (unsigned g = wk.first; g < wk.end; g += wk.step) {
         const unsigned cq = g % (unsigned)CQ;
         unsigned t = g / (unsigned)CQ;
@@ -283,10 +283,8 @@ __global__ __launch_bounds__(dw_wgrad_threads(K)) void k_dw_wgrad(const DwWgradA
     constexpr int SLOTS = dw_wgrad_slots(K), HALF = SLOTS / 2 * TPS, NACC = 4 * KHT * K;
     static_assert(SLOTS * TPS == dw_wgrad_threads(K), "threads = slots x quads x tap rows");
     __shared__ float red[NACC * HALF];
-    // XCD-aware order: the workgroups of one XCD take a contiguous eighth of the (slice, chunk) list (the ids past it leave before
-    // any barrier)
-    unsigned bid = blockIdx.x;
-    if ((gridDim.x & 7) == 0) bid = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+    // XCD-banded order (conv_device.hpp) over the (slice, chunk) list, the chunk fastest; the ids past it leave before any barrier
+    const unsigned bid = xcd_block();
     if (bid >= a.blocks) return;
     const int chunk = (int)(bid % (unsigned)a.nchunk), slice = (int)(bid / (unsigned)a.nchunk);
     const int tid = threadIdx.x, q = tid % kDwQuads, kh0 = (tid / kDwQuads) % (K / KHT) * KHT, slot = tid / TPS;
@@ -467,7 +465,7 @@ int launch_dw_wgrad(const float* x, const float* dy, float* dw, int B, int Hi, i
     a.nchunk = cdiv(a.CQ, kDwQuads); a.nslice = dw_wgrad_slices(B, Ho, Wo, C, dw_wgrad_slots(k)); a.nseg = cdiv(Wo, kDwSeg);
     const long long blocks = (long long)a.nchunk * a.nslice;      // (at most max(nchunk, 1024))
     a.blocks = (unsigned)blocks;
-    const unsigned grid = (unsigned)(blocks >= 8 ? (blocks + 7) / 8 * 8 : blocks);
+    const unsigned grid = (unsigned)xcd_grid(blocks);
 #define FPC_DW_WGRAD(K, S, PB) hipLaunchKernelGGL((k_dw_wgrad<K, S, PB>), dim3(grid), dim3(dw_wgrad_threads(K)), 0, s, a)
     if (k == 3 && stride == 1) FPC_DW_WGRAD(3, 1, 1);
     else if (k == 3 && !same) FPC_DW_WGRAD(3, 2, 1);

@@ -17,14 +17,9 @@
 // H3 (LatArgs::h3): k_conv_igemm's three-product form — the A fragments as two fp16 pieces (split_h2: 2/3 of the registers), the
 // weight tiles from k_pack_weight_h3's two planes, three v_mfma_f32_32x32x16_f16 per k-group, 1 / scale (a power of two) applied
 // before the bias.  (K = 256 on two pieces was tried for the p4 lateral: with its top-down addend the build spills 76 registers.)
-#include "net_kernels.hpp"
+#include "conv_device.hpp"
 
 namespace fpc {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 template <int KG /* K / 16 */, bool UP /* top-down addend */, bool H3 = false>
 __global__ __launch_bounds__(256, 2) void k_lateral1x1(const LatArgs a) {
@@ -34,11 +29,9 @@ __global__ __launch_bounds__(256, 2) void k_lateral1x1(const LatArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned char s_w[2][NPL * TILEB];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, col = lane & 31, h = lane >> 5;
     const int HW = a.Ho * a.Wo, mt = (HW + 127) >> 7;
-    // XCD-aware tile order: workgroups go to the 8 XCDs round-robin by id; with the grid a multiple of 8, XCD x = id % 8 takes the
-    // x-th contiguous eighth of the (image, pixel tile, part) list, so the input pixels and the top-down rows two pixel rows share
-    // are fetched by one L2 instead of two to eight
-    int bid = blockIdx.x;
-    if ((gridDim.x & 7) == 0) bid = (int)((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3));
+    // XCD-banded order (conv_device.hpp) over the (image, pixel tile, part) list, the part fastest: the input pixels and the top-down
+    // rows two pixel rows share are fetched by one L2 instead of two to eight
+    int bid = (int)xcd_block();
     const int part = bid % a.parts;
     bid /= a.parts;
     const int m = bid % mt, b = bid / mt;

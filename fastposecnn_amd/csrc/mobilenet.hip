@@ -29,15 +29,6 @@ namespace fpc {
 
 namespace {
 
-// xcd_walk over `total` rows where a workgroup takes `rpb` rows per step and this thread works on row slot `r` of them
-struct RowWalk { unsigned first, end, step; };
-__device__ __forceinline__ RowWalk xcd_rows(unsigned total, unsigned rpb, unsigned r) {
-    if ((gridDim.x & 7) != 0) return RowWalk{blockIdx.x * rpb + r, total, gridDim.x * rpb};
-    const unsigned per = (total + 7) >> 3, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const unsigned lo = xcd * per, hi = min(lo + per, total);
-    return RowWalk{lo + slot * rpb + r, hi, (gridDim.x >> 3) * rpb};
-}
-
 __device__ __forceinline__ float act_apply(float v, int act) { return act ? fminf(fmaxf(v, 0.f), 6.f) : v; }
 // ... and with code 2, swish v / (1 + exp(-v)): the EfficientNet instantiations (MB) alone, so the others keep their two-way select
 template <bool MB>
@@ -62,7 +53,7 @@ __global__ __launch_bounds__(256) void k_stem3x3s2(const float* __restrict__ in4
         wr[4 * i] = v[0]; wr[4 * i + 1] = v[1]; wr[4 * i + 2] = v[2]; wr[4 * i + 3] = v[3];
     }
     const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + 4 * q), sh = *reinterpret_cast<const f32x4*>(shift + 4 * q);
-    const RowWalk wk = xcd_rows(npix, 32, pl);
+    const XcdSpan wk = xcd_rows(npix, 32u, pl);
     for (unsigned p = wk.first; p < wk.end; p += wk.step) {
         const unsigned wo = p % (unsigned)Wo, t = p / (unsigned)Wo, ho = t % (unsigned)Ho, b = t / (unsigned)Ho;
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -98,11 +89,8 @@ __global__ __launch_bounds__(256) void k_conv1x1_f32(const float* __restrict__ i
                                                      const float* __restrict__ scale, const float* __restrict__ shift,
                                                      const float* __restrict__ res, float* __restrict__ out, unsigned M, int Cin, int Cout,
                                                      int act, unsigned mtiles, unsigned nchunks, const float* __restrict__ gate, unsigned HW) {
-    // workgroups go to the XCDs round-robin: XCD x takes the x-th contiguous eighth of the logical workgroups (launch: a multiple of 8)
-    unsigned bid = blockIdx.x;
-    if ((gridDim.x & 7) == 0) bid = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
     const unsigned lane = threadIdx.x & 63, li = lane & 31, lh = lane >> 5;
-    const unsigned wid = bid * 4 + (threadIdx.x >> 6);
+    const unsigned wid = xcd_block() * 4 + (threadIdx.x >> 6);      // the chunk index fastest: a pixel-row tile's chunks share an L2
     if (wid >= mtiles * nchunks) return;      // (no barrier in this kernel)
     const unsigned chunk = wid % nchunks, mt = wid / nchunks;
     const unsigned m0 = mt * 32, n0 = chunk * (NT * 32);
@@ -208,10 +196,8 @@ __global__ __launch_bounds__(256) void k_conv1x1_f32_small(const float* __restri
                                                            const float* __restrict__ res, float* __restrict__ out, unsigned M, int Cin,
                                                            int Cout, int act, unsigned mtiles, unsigned ntiles,
                                                            const float* __restrict__ gate, unsigned HW) {
-    unsigned bid = blockIdx.x;
-    if ((gridDim.x & 7) == 0) bid = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
     const unsigned lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
-    const unsigned wid = bid * 4 + (threadIdx.x >> 6);
+    const unsigned wid = xcd_block() * 4 + (threadIdx.x >> 6);
     if (wid >= mtiles * ntiles) return;      // (no barrier in this kernel)
     const unsigned nt = wid % ntiles, mt = wid / ntiles;
     const unsigned m0 = mt * 16, n0 = nt * 16;
@@ -325,16 +311,14 @@ static int launch_pw(const float* in, const float* w, const float* scale, const 
     const int nt = conv1x1_f32_tiles(M, Cout);
     if (nt == 0) {
         const long long mt16 = (M + 15) / 16, nt16 = (Cout + 15) / 16;
-        long long grid = (mt16 * nt16 + 3) / 4;
-        if (grid >= 8) grid = (grid + 7) / 8 * 8;
+        const long long grid = xcd_grid((mt16 * nt16 + 3) / 4);
         hipLaunchKernelGGL(k_conv1x1_f32_small<MB>, dim3((unsigned)grid), dim3(256), 0, s, in, w, scale, shift, res, out, (unsigned)M, Cin, Cout, act,
                            (unsigned)mt16, (unsigned)nt16, gate, (unsigned)HW);
         return check_launch();
     }
     const long long mtiles = (M + 31) / 32, nchunks = ((Cout + 31) / 32 + nt - 1) / nt, waves = mtiles * nchunks;
     if (waves >= (1LL << 31)) return FPC_EINVAL;
-    long long grid = (waves + 3) / 4;
-    if (grid >= 8) grid = (grid + 7) / 8 * 8;      // the XCD bands; the workgroups past the last wave leave at once
+    const long long grid = xcd_grid((waves + 3) / 4);      // the workgroups past the last wave leave at once
     const dim3 g((unsigned)grid), b(256);
 #define FPC_PW32(NT, U) hipLaunchKernelGGL((k_conv1x1_f32<NT, U, MB>), g, b, 0, s, in, w, scale, shift, res, out, (unsigned)M, Cin, Cout, act, (unsigned)mtiles, (unsigned)nchunks, gate, (unsigned)HW)
     if (nt == 5) FPC_PW32(5, 1);      // (K-steps per iteration: what the registers leave room for)

@@ -18,7 +18,7 @@ template <int PAD>
 __global__ __launch_bounds__(256) void k_maxpool3x3s2(const float* __restrict__ in, float* __restrict__ out, int B,
                                                       int Hi, int Wi, int C, int Ho, int Wo) {
     const unsigned C4 = C >> 2;
-    const XcdWalk wk = xcd_walk((unsigned)B * Ho * Wo * C4);      // < 2^32: launch_maxpool3x3s2
+    const XcdSpan wk = xcd_walk((unsigned)B * Ho * Wo * C4);      // < 2^32: launch_maxpool3x3s2
     for (unsigned g = wk.first; g < wk.end; g += wk.step) {
         int c4 = (int)(g % C4);
         unsigned r = g / C4;
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256) void k_gn_relu_up2(const GnUpArgs a) {
     const int ah = a.h[job], aw = a.w[job];
     const int C4 = a.C >> 2, H2 = 2 * ah, W2 = 2 * aw;
     const float sy = H2 > 1 ? (float)(ah - 1) / (float)(H2 - 1) : 0.f, sx = W2 > 1 ? (float)(aw - 1) / (float)(W2 - 1) : 0.f;
-    const XcdWalk wk = xcd_walk((unsigned)a.B * ah * aw * C4);      // < 2^32: launch_gn_relu_up2; an XCD walks a band of rows
+    const XcdSpan wk = xcd_walk((unsigned)a.B * ah * aw * C4);      // < 2^32: launch_gn_relu_up2; an XCD walks a band of rows
     for (unsigned g = wk.first; g < wk.end; g += wk.step) {
         const unsigned c4 = g % C4;
         unsigned r = g / C4;

@@ -21,15 +21,11 @@
 // per register quad, so the epilogue (folded BatchNorm or bias, residual, nearest-x2 top-down addend, ReLU) loads and stores
 // 16 bytes per lane.  Workgroups run in an XCD-aware order (channel tiles of one pixel tile on one XCD: the activation rows
 // are fetched into one L2).  No atomics, no split over K: the summation order is fixed, results are bit-identical run to run.
-#include "net_kernels.hpp"
+#include "conv_device.hpp"
 
 namespace fpc {
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 #define FPC_GLOBAL(p) ((const __attribute__((address_space(1))) void*)(p))
 #define FPC_LOCAL(p) ((__attribute__((address_space(3))) void*)(p))
@@ -46,10 +42,8 @@ __global__ __launch_bounds__(128 * WM) void k_conv1x1(const PwArgs a) {
     const int wn = wv & 1, wm = wv >> 1;
     const int HoWo = a.Ho * a.Wo, M = a.B * HoWo;
     const int ntg = a.Cout >> 6, nt = a.groups * ntg;
-    // XCD-aware order: with the grid a multiple of 8, XCD x = id % 8 takes the x-th contiguous eighth of the tile list, whose
-    // channel tiles of one pixel tile (the fast index) then share that XCD's L2 for the activation rows
-    int bid = blockIdx.x;
-    if ((gridDim.x & 7) == 0) bid = (int)((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3));
+    // XCD-banded order (conv_device.hpp): the channel tiles of one pixel tile (the fast index) share an L2 for the activation rows
+    const int bid = (int)xcd_block();
     const int tn = bid % nt, tm = bid / nt;
     const int d = tn / ntg, n0 = (tn - d * ntg) * 64, m0 = tm * BM;
 

@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256) void k_se_excite(const float* __restrict__ par
 __global__ __launch_bounds__(256) void k_se_scale_add_relu(const float* x, const float* __restrict__ gate,
                                                            const float* __restrict__ res, float* y, unsigned total, unsigned CQ,
                                                            unsigned frame_items) {
-    const XcdWalk wk = xcd_walk(total);      // < 2^32 with a grid stride of headroom: launch_se_scale_add_relu
+    const XcdSpan wk = xcd_walk(total);      // < 2^32 with a grid stride of headroom: launch_se_scale_add_relu
     for (unsigned g = wk.first; g < wk.end; g += wk.step) {
         const unsigned b = g / frame_items, c4 = g % CQ;
         const float4 v = *reinterpret_cast<const float4*>(x + (size_t)g * 4);

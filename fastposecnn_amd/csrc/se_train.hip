@@ -197,7 +197,7 @@ __global__ __launch_bounds__(256) void k_se_bwd_apply(const float* __restrict__ 
                                                       const float* __restrict__ gate, const float* __restrict__ dm,
                                                       float* __restrict__ dx, float* __restrict__ dres, float inv_hw, unsigned total,
                                                       unsigned CQ, unsigned frame_items) {
-    const XcdWalk wk = xcd_walk(total);      // < 2^32 with a grid stride of headroom: se_shape_ok
+    const XcdSpan wk = xcd_walk(total);      // < 2^32 with a grid stride of headroom: se_shape_ok
     for (unsigned g = wk.first; g < wk.end; g += wk.step) {
         const unsigned b = g / frame_items, c4 = g % CQ;
         const float4 d = relu_mask(*reinterpret_cast<const float4*>(gy + (size_t)g * 4), *reinterpret_cast<const float4*>(y + (size_t)g * 4));

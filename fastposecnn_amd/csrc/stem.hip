@@ -18,15 +18,11 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "net_kernels.hpp"
+#include "conv_device.hpp"
 
 namespace fpc {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x3 __attribute__((ext_vector_type(3)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int kStemKG = 14;                       // 16-deep k-groups: 7 kernel rows x (taps 0-3 | taps 4-7)
 constexpr int kStemLds = kStemKG * 3 * 2 * 1024;  // bytes
@@ -47,15 +43,10 @@ __global__ __launch_bounds__(512, 1) void k_stem7x7(const StemArgs a) {
 
     const int segs = a.Wo >> 6;                     // 64-pixel segments per output row
     const int ntile = a.B * a.Ho * segs;            // < 2^31: launch_stem7x7
-    // XCD-banded walk: workgroups go to the 8 XCDs round-robin; with the grid a multiple of 8, XCD x = blockIdx.x % 8 walks the
-    // x-th contiguous eighth of the tiles (row segments in raster order), so the 3.5 output rows that share an input row are
-    // served by one L2
-    int t_first = blockIdx.x * 8 + wv, t_end = ntile, t_step = gridDim.x * 8;
-    if ((gridDim.x & 7) == 0) {
-        const int per = (ntile + 7) >> 3, lo = (blockIdx.x & 7) * per;
-        t_first = lo + (blockIdx.x >> 3) * 8 + wv; t_end = min(lo + per, ntile); t_step = (gridDim.x >> 3) * 8;
-    }
-    for (int tile = t_first; tile < t_end; tile += t_step) {
+    // XCD-banded walk (conv_device.hpp) of the tiles (row segments in raster order), a tile per wave: the 3.5 output rows that share
+    // an input row are served by one L2
+    const XcdSpanT<int> wk = xcd_rows(ntile, 8, wv);
+    for (int tile = wk.first; tile < wk.end; tile += wk.step) {
         const int t2 = tile / segs, seg = tile - t2 * segs;
         const int b = t2 / a.Ho, oy = t2 - b * a.Ho;
         const int ox0 = seg * 64;
@@ -250,11 +241,7 @@ __global__ __launch_bounds__(512, 1) void k_stem_pool_h3(const StemPoolArgs a) {
 
     const int strips = a.Wo >> 6, bands = (a.Hp + a.band - 1) / a.band;
     const int ntask = a.B * bands * strips;           // < 2^31: launch_stem_pool_h3
-    int t_first = blockIdx.x * 8 + wv, t_end = ntask, t_step = gridDim.x * 8;
-    if ((gridDim.x & 7) == 0) {      // XCD-banded walk, as k_stem7x7
-        const int per = (ntask + 7) >> 3, lo = (blockIdx.x & 7) * per;
-        t_first = lo + (blockIdx.x >> 3) * 8 + wv; t_end = min(lo + per, ntask); t_step = (gridDim.x >> 3) * 8;
-    }
+    const XcdSpanT<int> wk = xcd_rows(ntask, 8, wv);      // XCD-banded walk, as k_stem7x7
     const unsigned rowB = (unsigned)a.Wi * 16u;       // bytes of an image row
     // a pixel is loaded as its three real channels (the fourth of the NHWC4 image is zero: a constant, not a register)
     auto masked = [](f32x3 v, unsigned m) {
@@ -265,7 +252,7 @@ __global__ __launch_bounds__(512, 1) void k_stem_pool_h3(const StemPoolArgs a) {
         return o;
     };
     float* halo = &s_halo[wv][0][0];
-    for (int task = t_first; task < t_end; task += t_step) {
+    for (int task = wk.first; task < wk.end; task += wk.step) {
         const int t2 = task / strips, strip = task - t2 * strips;
         const int b = t2 / bands, band = t2 - b * bands;
         const int r0 = band * a.band, nr = min(a.band, a.Hp - r0);

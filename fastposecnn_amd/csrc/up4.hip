@@ -2,7 +2,7 @@
 // compression (F/lib/pose_regressor.py:729-732, 445-457; F/lib/gpu_tensor_funcs.py:37-99) with four pixels per thread.
 // k_up4_compress_wide (below): the same for 9 to 32 classes, with a mode that interpolates only the winning class's channels.
 // The one-pixel-per-thread forms (any class count, any width) are k_up4_compress / k_up4_compress7 in net_kernels.hip.
-#include "net_kernels.hpp"
+#include "conv_device.hpp"
 
 namespace fpc {
 
@@ -14,16 +14,10 @@ namespace fpc {
 __global__ __launch_bounds__(128, 3) void k_up4_compress7x4(const Up4Args a) {
     constexpr int C = 7, G = 6;
     const int HW = a.H * a.W;
-    // XCD-aware block order.  Workgroups go to the 8 XCDs round-robin by linear id, and every output pixel reads ~100 bytes of
-    // low-resolution taps: in plain order each XCD's L2 (4 MB) saw ALL rows of every frame's low-resolution logits (5.5 MB per
-    // frame) and re-fetched them through the fabric — about 1.4 GB of reads beside 3.1 GB of writes per 32-frame batch.  When the
-    // blocks of a frame divide by 8, XCD x takes the x-th eighth of the frame's rows (0.7 MB of taps): id -> (xcd = id % 8, rest).
-    int b = blockIdx.y, blk = blockIdx.x;
-    if ((gridDim.x & 7) == 0) {
-        const unsigned id = blockIdx.x + gridDim.x * blockIdx.y, per = gridDim.x >> 3, j = id >> 3;
-        b = (int)(j / per);
-        blk = (int)((id & 7) * per + (j - (unsigned)b * per));
-    }
+    // XCD-banded block order (conv_device.hpp) inside a frame.  Every output pixel reads ~100 bytes of low-resolution taps: in plain
+    // order each XCD's L2 (4 MB) saw ALL rows of every frame's low-resolution logits (5.5 MB per frame) and re-fetched them through
+    // the fabric — about 1.4 GB of reads beside 3.1 GB of writes per 32-frame batch; an eighth of a frame's rows is 0.7 MB of taps.
+    const int b = blockIdx.y, blk = (int)xcd_block();
     const int p0 = 4 * (blk * blockDim.x + threadIdx.x);
     if (p0 >= HW) return;                                   // whole waves only: HW % 256 == 0 (launcher)
     const int y = p0 / a.W, x0 = p0 - y * a.W;
@@ -231,12 +225,7 @@ template <int MQ, bool LOGITS>
 __global__ __launch_bounds__(128) void k_up4_compress_wide(const Up4Args a) {
     const int C = a.C, G = C - 1;
     const int HW = a.H * a.W;
-    int b = blockIdx.y, blk = blockIdx.x;                   // XCD-aware block order: see k_up4_compress7x4
-    if ((gridDim.x & 7) == 0) {
-        const unsigned id = blockIdx.x + gridDim.x * blockIdx.y, per = gridDim.x >> 3, j = id >> 3;
-        b = (int)(j / per);
-        blk = (int)((id & 7) * per + (j - (unsigned)b * per));
-    }
+    const int b = blockIdx.y, blk = (int)xcd_block();       // XCD-banded block order inside a frame: see k_up4_compress7x4
     const int p0 = 4 * (blk * blockDim.x + threadIdx.x);
     if (p0 >= HW) return;                                   // whole waves only: HW % 256 == 0 (launcher)
     const int y = p0 / a.W, x0 = p0 - y * a.W;

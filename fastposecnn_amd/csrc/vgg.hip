@@ -18,19 +18,6 @@
 
 namespace fpc {
 
-namespace {
-
-// xcd_walk over `total` rows where a workgroup takes `rpb` rows per step and this thread works on row slot `r` of them
-struct RowWalk { unsigned first, end, step; };
-__device__ __forceinline__ RowWalk xcd_rows(unsigned total, unsigned rpb, unsigned r) {
-    if ((gridDim.x & 7) != 0) return RowWalk{blockIdx.x * rpb + r, total, gridDim.x * rpb};
-    const unsigned per = (total + 7) >> 3, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const unsigned lo = xcd * per, hi = min(lo + per, total);
-    return RowWalk{lo + slot * rpb + r, hi, (gridDim.x >> 3) * rpb};
-}
-
-}  // namespace
-
 // One thread's pixel pair: outputs (y0, x0) and (y0, x0 + 1), x0 even, of its channel quad, from the 3 x 4 window of 16-byte pixels
 // they share.  INTERIOR: the whole window and both outputs lie inside the image — no clamp, no select, two stores.  Otherwise every
 // address is clamped into the image and a tap outside it is a select of zero; the second output is stored where x0 + 1 < W.  Either
@@ -97,7 +84,7 @@ __global__ __launch_bounds__(256) void k_conv3x3_c3(const float* __restrict__ in
     f32x4 sc = f32x4{1.f, 1.f, 1.f, 1.f};
     if (AFF) sc = *reinterpret_cast<const f32x4*>(scale + 4 * q);
     const f32x4 sh = *reinterpret_cast<const f32x4*>(shift + 4 * q);
-    const RowWalk wk = xcd_rows(items, 16, pl);
+    const XcdSpan wk = xcd_rows(items, 16u, pl);
     for (unsigned it = wk.first; it < wk.end; it += wk.step) {
         const unsigned t = div_by(it, rWp), xp = it - t * (unsigned)Wp;      // t = b H + y0: the row of the batch
         const unsigned b = div_by(t, rH);
@@ -113,7 +100,7 @@ __global__ __launch_bounds__(256) void k_conv3x3_c3(const float* __restrict__ in
 // x [B][H][W][C] -> y [B][H / 2][W / 2][C]; H, W even, C % 4 == 0; items = B (H / 2) (W / 2) (C / 4)
 __global__ __launch_bounds__(256) void k_maxpool2x2(const float* __restrict__ x, float* __restrict__ y, unsigned items, int Ho, int Wo, int C) {
     const unsigned C4 = (unsigned)C >> 2;
-    const XcdWalk wk = xcd_walk(items);      // < kWalkLimit: launch_maxpool2x2
+    const XcdSpan wk = xcd_walk(items);      // < kWalkLimit: launch_maxpool2x2
     const size_t row = (size_t)2 * Wo * C;   // one input row
     for (unsigned g = wk.first; g < wk.end; g += wk.step) {
         const unsigned c4 = g % C4;

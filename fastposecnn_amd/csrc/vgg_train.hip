@@ -65,8 +65,8 @@ __global__ __launch_bounds__(kCwThreads) void k_c3_wgrad(const C3WgradArgs a) {
     __shared__ __attribute__((aligned(16))) float s_im[kCwImg4 * 4];
     const int tid = threadIdx.x, lane = tid & 63;
     const int m = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // XCD x = blockIdx.x % 8 takes the x-th contiguous eighth of the slices (neighbouring rows of the image and of dy in one L2)
-    const int slice = (a.nslice & 7) ? (int)blockIdx.x : (int)(blockIdx.x & 7) * (a.nslice >> 3) + (int)(blockIdx.x >> 3);
+    // XCD-banded order (conv_device.hpp) over the slices (the grid is nslice): neighbouring rows of the image and of dy in one L2
+    const int slice = (int)xcd_block();
     const int u0 = (int)((long long)slice * a.nunit / a.nslice), u1 = (int)((long long)(slice + 1) * a.nunit / a.nslice);
     const int per_frame = a.H * a.nseg;
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256) void k_c3_wgrad_reduce(const float* __restrict
 __global__ __launch_bounds__(256) void k_maxpool2x2_bwd(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ dx,
                                                         unsigned items, int Wo, int C) {
     const unsigned C4 = (unsigned)C >> 2;
-    const XcdWalk wk = xcd_walk(items);      // < kWalkLimit: fpc_maxpool2x2_bwd
+    const XcdSpan wk = xcd_walk(items);      // < kWalkLimit: fpc_maxpool2x2_bwd
     const size_t row = (size_t)2 * Wo * C;   // one input row
     for (unsigned g = wk.first; g < wk.end; g += wk.step) {
         const unsigned c4 = g % C4;

@@ -711,6 +711,12 @@ int fpc_net_guarded(const fpc_net_t* net, int i);
  * conv columns, conv outputs one frame's launch computes (the band overlap rows and the halo tiles included), conv outputs that
  * exist (Ho * Wo).  FPC_EINVAL for a shape the fused launch does not take. */
 int fpc_stem_pool_tasks(int Ho, int Wo, int64_t* out4);
+/* The XCD-banded workgroup order of the streaming and tile kernels (host only, no device): for workgroup `block` of a launch of
+ * `grid` workgroups, out4[0] = the logical workgroup it works as (grid % 8 == 0: (block % 8) * (grid / 8) + block / 8, else block);
+ * out4[1..3] = first, end, step of the items that slot `slot` (of `per_block` per workgroup and step) of that workgroup visits out of
+ * `total`: first, first + step, ... below end.  FPC_EINVAL for grid < 1, block outside [0, grid), per_block < 1, slot outside
+ * [0, per_block), total < 0 or total at or above the 32-bit walks' bound (2^32 - 2^20 - 8). */
+int fpc_xcd_order(int grid, int block, int64_t total, int per_block, int slot, int64_t* out4);
 /* Form -9's launch geometry (host arithmetic, no device) for a 3x3 / stride-1 site with output H x W, batch B, Cin input channels.
  * Where the tile columns of a frame do not fill whole 8-column patches, G frames are laid side by side on a canvas row and the
  * patches are cut out of the canvas (G = the smallest count in 1 .. min(B, 8) that minimises ceil(G tcw / 8) / G, tcw = ceil(W / 2);
