@@ -87,7 +87,10 @@ __device__ __forceinline__ float adjoint_weight(float r, int o, int n_in, int i)
     return (i0 == i ? l0 : 0.f) + (i1 == i ? l1 : 0.f);
 }
 
-constexpr int kUpTaps = 12;      // outputs per axis that can touch one input coordinate at scale <= 4 on maps >= 4 wide (2 / r + 3)
+// Candidates per axis the unrolled form of the adjoint holds.  adjoint_range spans hi - lo + 1 of them: at scale 2 never more than
+// 12 (always the unrolled form); at scale 4 up to 14 (hi - lo <= 13) at one to four coordinates per axis of every extent >= 5, the
+// 120- and 160-wide maps included: those coordinates take the rolled loop.  Extents <= 4 fit the unrolled form at either scale.
+constexpr int kUpTaps = 12;
 
 // The adjoint is separable: first along x (dout [.., H, W] -> tmp [.., H, w]), then along y (tmp -> din [.., h, w]); a pass
 // gathers <= 2 scale + 3 values per element instead of the (2 scale + 3)^2 of the one-pass form (x4: 81 loads per element).
@@ -113,7 +116,7 @@ __global__ __launch_bounds__(256) void k_up_bilinear_bwd_1d(const UpArgs a, int 
         }
 #pragma unroll
         for (int k = 0; k < kUpTaps; ++k) acc += wgt[k] * val[k];
-    } else {      // tiny maps (1 / r up to 2 * scale - 1)
+    } else {      // the scale-4 coordinates whose range exceeds kUpTaps (see there): same taps, same order, rolled
         for (int o = lo; o <= hi; ++o) {
             const float wv = adjoint_weight(r, o, n_in, i);
             if (wv != 0.f) acc += wv * p[o * st];
@@ -336,73 +339,132 @@ static int up_args(UpArgs& a, const float* src, int64_t sb, int64_t sc, int64_t 
 }
 
 // grid over dst (Y x X per image), see dst_element
-static bool up_grid(const UpArgs& a, int X, int Y, dim3& g) {
-    const long long zs = a.order_nhwc ? a.B : (long long)a.B * a.C, xs = a.order_nhwc ? (long long)X * a.C : (long long)X * Y;
+static bool up_grid(int order_nhwc, int B, int C, int X, int Y, dim3& g) {
+    const long long zs = order_nhwc ? B : (long long)B * C, xs = order_nhwc ? (long long)X * C : (long long)X * Y;
     if (zs > 65535 || Y > 65535 || xs > 0x7FFFFFFF - 256) return false;
-    g = dim3((unsigned)((xs + 255) / 256), a.order_nhwc ? (unsigned)Y : 1u, (unsigned)zs);
+    g = dim3((unsigned)((xs + 255) / 256), order_nhwc ? (unsigned)Y : 1u, (unsigned)zs);
     return true;
 }
+
+// ---- which kernel a call runs on, stated once.  Host arithmetic on the call's arguments; of the pointers only the low four
+// bits count (`low4`: those of every pointer of the call, or-ed).  The launchers below switch on the result and the C ABI
+// hands it out (fpc_upsample_bilinear_form), so a test can name the kernel a case runs on.
+enum UpFwdForm { kUpFwdScalar = 0, kUpFwdNhwc4 = 1, kUpFwdNhwcToNchw = 2, kUpFwdNchw4 = 3 };
+enum UpBwdForm { kUpBwdScalar = 0, kUpBwdNhwc4 = 1, kUpBwdNchw = 2 };      // pass 1: k_up_bwd_x_nchw, pass 2: k_up_bwd_y_nchw4
+struct UpForm {
+    int fwd;                 // forward: UpFwdForm
+    int pass1, pass2;        // backward: UpBwdForm of the x pass and of the y pass
+    int order;               // backward: thread order of both passes = dout's layout
+};
+
+// FPC_EINVAL for every shape the launchers refuse (they add the null pointers)
+static int up_form(UpForm& f, bool backward, unsigned low4, int64_t sb, int64_t sc, int64_t sh, int64_t sw, int B, int C, int h, int w,
+                   int scale, int dst_nhwc) {
+    if ((scale != 2 && scale != 4) || B < 1 || C < 1 || h < 1 || w < 1) return FPC_EINVAL;
+    const int H = h * scale, W = w * scale;
+    const bool al16 = (low4 & 15) == 0;
+    dim3 g;
+    f = UpForm{};
+    if (!backward) {
+        if (!up_grid(dst_nhwc ? 1 : 0, B, C, W, H, g)) return FPC_EINVAL;
+        if (dst_nhwc && C % 4 == 0 && sc == 1 && al16 && !((sb | sh | sw) & 3)) f.fwd = kUpFwdNhwc4;
+        else if (!dst_nhwc && sc == 1 && sw == C && C <= 32 && (H + 3) / 4 <= 65535 && B <= 65535) f.fwd = kUpFwdNhwcToNchw;
+        else if (!dst_nhwc && W % 4 == 0 && al16 && (H + 3) / 4 <= 65535) f.fwd = kUpFwdNchw4;
+        else f.fwd = kUpFwdScalar;
+        return FPC_OK;
+    }
+    f.order = (C > 1 && sc == 1) ? 1 : 0;      // thread order = dout's layout: its reads are the many
+    if (!up_grid(f.order, B, C, w, H, g)) return FPC_EINVAL;      // pass 1 writes [B, C, H, w]; pass 2's [B, C, h, w] is the smaller
+    const bool vec_c = f.order && C % 4 == 0 && al16 && !((sb | sh | sw) & 3);           // channel-last, four channels per thread
+    const bool vec_x = !f.order && sw == 1 && al16 && w % 4 == 0 && !((sb | sc | sh) & 3) && (H + 15) / 16 <= 65535;   // x fastest
+    f.pass1 = vec_c ? kUpBwdNhwc4 : vec_x ? kUpBwdNchw : kUpBwdScalar;
+    f.pass2 = (vec_c && dst_nhwc) ? kUpBwdNhwc4 : vec_x ? kUpBwdNchw : kUpBwdScalar;
+    return FPC_OK;
+}
+
+// The form of a call: backward = 0: the forward kernel of fpc_upsample_bilinear_fwd (0 = k_up_bilinear_fwd, one element per thread;
+// 1 = k_up_fwd_nhwc4; 2 = k_up_fwd_nhwc_to_nchw, the LDS patch; 3 = k_up_fwd_nchw4); backward = 1: pass 1 in bits 0-3 and pass 2 in
+// bits 4-7 of fpc_upsample_bilinear_bwd (0 = k_up_bilinear_bwd_1d, 1 = k_up_bwd_1d_nhwc4, 2 = k_up_bwd_x_nchw / k_up_bwd_y_nchw4).
+// ptr_low4: the low four bits of the call's pointers (in, out; dout, din, scratch), or-ed.  FPC_EINVAL where the launcher refuses
+// the shape.
+extern "C" int fpc_upsample_bilinear_form(int backward, unsigned ptr_low4, int64_t sb, int64_t sc, int64_t sh, int64_t sw, int B, int C,
+                                          int h, int w, int scale, int dst_nhwc) {
+    UpForm f;
+    const int rc = up_form(f, backward != 0, ptr_low4, sb, sc, sh, sw, B, C, h, w, scale, dst_nhwc);
+    if (rc) return rc;
+    return backward ? (f.pass1 | (f.pass2 << 4)) : f.fwd;
+}
+
+static unsigned low4(const void* p) { return (unsigned)((uintptr_t)p & 15); }
 
 // out [B,C,h*scale,w*scale] (contiguous; channel-last if out_nhwc) = bilinear(in), align_corners = True; scale 2 or 4;
 // `in` through its element strides (any layout).
 extern "C" int fpc_upsample_bilinear_fwd(const float* in, int64_t sb, int64_t sc, int64_t sh, int64_t sw, float* out, int B, int C,
                                          int h, int w, int scale, int out_nhwc, fpc_stream_t stream) {
-    if (scale != 2 && scale != 4) return FPC_EINVAL;
+    UpForm f;
+    int rc = up_form(f, false, low4(in) | low4(out), sb, sc, sh, sw, B, C, h, w, scale, out_nhwc);
+    if (rc) return rc;
     UpArgs a{};
-    int rc = up_args(a, in, sb, sc, sh, sw, out, B, C, h, w, scale, out_nhwc, h * scale, w * scale);
+    rc = up_args(a, in, sb, sc, sh, sw, out, B, C, h, w, scale, out_nhwc, h * scale, w * scale);
     if (rc) return rc;
     a.order_nhwc = out_nhwc ? 1 : 0;
     dim3 g;
-    if (!up_grid(a, a.W, a.H, g)) return FPC_EINVAL;
-    const bool al16 = (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
-    if (out_nhwc && C % 4 == 0 && sc == 1 && al16 && !((sb | sh | sw) & 3)) {
+    if (!up_grid(a.order_nhwc, B, C, a.W, a.H, g)) return FPC_EINVAL;
+    switch (f.fwd) {
+    case kUpFwdNhwc4:
         hipLaunchKernelGGL(k_up_fwd_nhwc4, dim3((unsigned)(((long long)a.W * (C / 4) + 255) / 256), (unsigned)a.H, (unsigned)B), dim3(256), 0,
                            (hipStream_t)stream, a);
-    } else if (!out_nhwc && sc == 1 && sw == C && C <= 32 && (a.H + 3) / 4 <= 65535 && B <= 65535) {
+        break;
+    case kUpFwdNhwcToNchw:
         hipLaunchKernelGGL(k_up_fwd_nhwc_to_nchw, dim3((unsigned)((a.W + 63) / 64), (unsigned)((a.H + 3) / 4), (unsigned)B), dim3(256),
                            sizeof(float) * kUpPatchH * kUpPatchW * C, (hipStream_t)stream, a);
-    } else if (!out_nhwc && a.W % 4 == 0 && al16 && (a.H + 3) / 4 <= 65535) {
+        break;
+    case kUpFwdNchw4:
         hipLaunchKernelGGL(k_up_fwd_nchw4, dim3((unsigned)((a.W / 4 + 63) / 64), (unsigned)((a.H + 3) / 4), g.z), dim3(64, 4), 0,
                            (hipStream_t)stream, a);
-    } else {
+        break;
+    default:
         hipLaunchKernelGGL(k_up_bilinear_fwd, g, dim3(256), 0, (hipStream_t)stream, a);
     }
     return check_launch();
 }
 
-// floats of scratch the backward needs: the x-pass result [B, C, h * scale, w]
+// floats of scratch the backward needs: the x-pass result [B, C, h * scale, w]; 0 for a shape or scale the backward refuses
 extern "C" size_t fpc_upsample_bilinear_bwd_scratch_floats(int B, int C, int h, int w, int scale) {
-    return (B < 1 || C < 1 || h < 1 || w < 1 || scale < 1) ? 0 : (size_t)B * C * h * scale * w;
+    return (B < 1 || C < 1 || h < 1 || w < 1 || (scale != 2 && scale != 4)) ? 0 : (size_t)B * C * h * scale * w;
 }
 
 // din [B,C,h,w] (contiguous; channel-last if din_nhwc, overwritten) = adjoint of the above applied to dout
 // [B,C,h*scale,w*scale] (through its element strides).  scratch: fpc_upsample_bilinear_bwd_scratch_floats floats.
 extern "C" int fpc_upsample_bilinear_bwd(const float* dout, int64_t sb, int64_t sc, int64_t sh, int64_t sw, float* din, float* scratch,
                                          int B, int C, int h, int w, int scale, int din_nhwc, fpc_stream_t stream) {
-    if (!scratch || (scale != 2 && scale != 4) || h < 1 || w < 1) return FPC_EINVAL;
-    const int H = h * scale;
-    const int order = (C > 1 && sc == 1) ? 1 : 0;      // thread order = dout's layout: its reads are the many
+    if (!dout || !din || !scratch) return FPC_EINVAL;      // before pass 1: a refused call writes nothing, the scratch included
+    UpForm f;
+    int rc = up_form(f, true, low4(dout) | low4(din) | low4(scratch), sb, sc, sh, sw, B, C, h, w, scale, din_nhwc);
+    if (rc) return rc;
+    const int H = h * scale, order = f.order;
     // pass 1 (x axis): dout -> tmp [B, C, H, w], laid out like dout
     UpArgs a{};
-    int rc = up_args(a, dout, sb, sc, sh, sw, scratch, B, C, H, w, 1, order, H, w);
+    rc = up_args(a, dout, sb, sc, sh, sw, scratch, B, C, H, w, 1, order, H, w);
     if (rc) return rc;
     UpArgs a1 = a;
     a1.h = H; a1.w = w; a1.order_nhwc = order;
     const float rx = w * scale > 1 ? (float)(w - 1) / (float)(w * scale - 1) : 0.f;
     const float ry = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f;
     dim3 g;
-    if (!up_grid(a1, w, H, g)) return FPC_EINVAL;
-    const bool al16 = (((uintptr_t)dout | (uintptr_t)din | (uintptr_t)scratch) & 15) == 0;
-    const bool vec_c = order && C % 4 == 0 && al16 && !((sb | sh | sw) & 3);           // channel-last, four channels per thread
-    const bool vec_x = !order && sw == 1 && al16 && w % 4 == 0 && !((sb | sc | sh) & 3) && (H + 15) / 16 <= 65535;   // x fastest
-    if (vec_c)
+    if (!up_grid(order, B, C, w, H, g)) return FPC_EINVAL;
+    switch (f.pass1) {
+    case kUpBwdNhwc4:
         hipLaunchKernelGGL(k_up_bwd_1d_nhwc4<0>, dim3((unsigned)(((long long)w * (C / 4) + 255) / 256), (unsigned)H, (unsigned)B), dim3(256), 0,
                            (hipStream_t)stream, a1, w, w * scale, rx);
-    else if (vec_x)
+        break;
+    case kUpBwdNchw:
         hipLaunchKernelGGL(k_up_bwd_x_nchw, dim3((unsigned)((w + 63) / 64), (unsigned)((H + 15) / 16), g.z), dim3(64, 4), 0, (hipStream_t)stream,
                            a1, w, w * scale, rx);
-    else
+        break;
+    default:
         hipLaunchKernelGGL(k_up_bilinear_bwd_1d<0>, g, dim3(256), 0, (hipStream_t)stream, a1, w, w * scale, rx);
+    }
     rc = check_launch();
     if (rc) return rc;
     // pass 2 (y axis): tmp -> din [B, C, h, w]
@@ -412,14 +474,18 @@ extern "C" int fpc_upsample_bilinear_bwd(const float* dout, int64_t sb, int64_t 
     rc = up_args(a2, scratch, t_b, t_c, t_y, t_x, din, B, C, h, w, 1, din_nhwc, h, w);
     if (rc) return rc;
     a2.h = h; a2.w = w; a2.order_nhwc = order;
-    if (!up_grid(a2, w, h, g)) return FPC_EINVAL;
-    if (vec_c && din_nhwc)
+    if (!up_grid(order, B, C, w, h, g)) return FPC_EINVAL;
+    switch (f.pass2) {
+    case kUpBwdNhwc4:
         hipLaunchKernelGGL(k_up_bwd_1d_nhwc4<1>, dim3((unsigned)(((long long)w * (C / 4) + 255) / 256), (unsigned)h, (unsigned)B), dim3(256), 0,
                            (hipStream_t)stream, a2, h, H, ry);
-    else if (vec_x)
+        break;
+    case kUpBwdNchw:
         hipLaunchKernelGGL(k_up_bwd_y_nchw4, dim3((unsigned)((w / 4 + 63) / 64), (unsigned)((h + 3) / 4), g.z), dim3(64, 4), 0, (hipStream_t)stream,
                            a2, h, H, ry);
-    else
+        break;
+    default:
         hipLaunchKernelGGL(k_up_bilinear_bwd_1d<1>, g, dim3(256), 0, (hipStream_t)stream, a2, h, H, ry);
+    }
     return check_launch();
 }

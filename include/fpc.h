@@ -1194,12 +1194,22 @@ int fpc_conv2d_wgrad_split(const float* x, int64_t sb, int64_t sh, int64_t sw, c
  * torch.nn.functional.interpolate / nn.UpsamplingBilinear2d in the reference's network, F/lib/pose_regressor.py:608-666),
  * forward and its exact adjoint, ATen's source-index arithmetic.  scale: 2 or 4.  The tensor that is READ is given by its
  * element strides (any layout); the one WRITTEN is contiguous [B,C,.,.], channel-last when *_nhwc != 0.  The backward runs
- * one axis at a time through `scratch` (fpc_upsample_bilinear_bwd_scratch_floats floats).  Deterministic. */
+ * one axis at a time through `scratch` (fpc_upsample_bilinear_bwd_scratch_floats floats; 0 for a shape or scale the
+ * backward refuses).  A refused call writes nothing, the scratch included.  Deterministic. */
 int fpc_upsample_bilinear_fwd(const float* in, int64_t sb, int64_t sc, int64_t sh, int64_t sw, float* out, int B, int C, int h,
                               int w, int scale, int out_nhwc, fpc_stream_t stream);
 size_t fpc_upsample_bilinear_bwd_scratch_floats(int B, int C, int h, int w, int scale);
 int fpc_upsample_bilinear_bwd(const float* dout, int64_t sb, int64_t sc, int64_t sh, int64_t sw, float* din, float* scratch,
                               int B, int C, int h, int w, int scale, int din_nhwc, fpc_stream_t stream);
+/* The kernel a call of the two above runs on (host arithmetic, the launchers switch on the same result; ABI 11, additive).
+ * ptr_low4: the low four bits of the call's pointers, or-ed (in, out; dout, din, scratch); the strides, shape, scale and
+ * dst_nhwc (out_nhwc / din_nhwc) as in the call.  backward == 0: 0 = one element per thread, 1 = channel-last on both
+ * sides with four channels per thread, 2 = channel-last source -> NCHW through an LDS patch (C <= 32), 3 = NCHW
+ * destination with four columns per thread.  backward != 0: the x pass in bits 0-3 and the y pass in bits 4-7, each
+ * 0 = one element per thread, 1 = channel-last with four channels per thread, 2 = x-fastest (four rows per thread in
+ * the x pass, four columns in the y pass).  FPC_EINVAL where the launcher refuses the shape (null pointers apart). */
+int fpc_upsample_bilinear_form(int backward, unsigned ptr_low4, int64_t sb, int64_t sc, int64_t sh, int64_t sw, int B, int C,
+                               int h, int w, int scale, int dst_nhwc);
 
 /* GroupNorm + ReLU on channel-last activations for the training step (the decoder blocks' GroupNorm(32, 128) -> ReLU,
  * segmentation_models_pytorch Conv3x3GNReLU, call sites F/lib/pose_regressor.py:608-666): x, y, dy, dx are [B, HW, C]
