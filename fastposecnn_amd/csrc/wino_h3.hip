@@ -156,6 +156,20 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
         }
     if (npair > 1) so_u += kPairBytes;
     }
+    // ---- the accumulators start from +0.0 (PH 1 keeps phase 1's sums; the fold kernels: below).  Sixteen matrix instructions on zero operands with the literal 0
+    // as C, each writing the 16 registers of one accumulator (0 * 0 + 0 = +0.0, the bits 256 v_accvgpr_write left at ~1 k issue cycles
+    // of the only wave on the SIMD, in front of the first wait).  Four at a time — xi column J's — behind the weight requests, behind
+    // the staging plan and between the three staging bursts: each group runs in the matrix pipe while the wave issues what follows.
+    // ONE zero operand, declared here and passed through an empty asm per call: written plainly the compiler merges the sixteen into
+    // one instruction and 240 register copies.  profiles/wino_entry_ledger.md.
+    f16x8 zop = {0, 0, 0, 0, 0, 0, 0, 0};
+#define FPC_H3_ZERO_ACC(J) do { if constexpr (PH == 0 && !FOLD) {                                                    \
+        _Pragma("unroll") for (int mt_ = 0; mt_ < 2; ++mt_)                                                   \
+        _Pragma("unroll") for (int nt_ = 0; nt_ < 2; ++nt_) {                                                 \
+            asm volatile("" : "+v"(zop));                                                                     \
+            acc[J][mt_][nt_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(zop, zop, f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, 0, 0, 0); \
+        } } } while (0)
+    FPC_H3_ZERO_ACC(0);
     if (PH == 0) t_wld = fine ? clock64() : 0;
 
     // ---- input staging and fragment addressing (wino_tile.hpp)
@@ -172,26 +186,33 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
     // tile half MT's column transform of the row-transformed columns E[]
 #define FPC_H3_COLUMN(E, MT, JX) ((JX) == 0 ? sub_s4(E[(MT) * (kNC - 4)], E[(MT) * (kNC - 4) + 2]) : (JX) == 1 ? add_s4(E[(MT) * (kNC - 4) + 1], E[(MT) * (kNC - 4) + 2]) : \
                                   (JX) == 2 ? sub_s4(E[(MT) * (kNC - 4) + 2], E[(MT) * (kNC - 4) + 1]) : sub_s4(E[(MT) * (kNC - 4) + 1], E[(MT) * (kNC - 4) + 3]))
+    FPC_H3_ZERO_ACC(1);
     if (PH == 0) t_plan = fine ? clock64() : 0;
     wino_zero_ring(lds, t, kRing, y_in0, x_in0, H, W, PACK && pk_ks < kTX);
     if (PH == 0) t_zero = fine ? clock64() : 0;
     // steps 0, 1, 2 -> buffers 0, 1, 2
     FPC_H3_ISSUE_IN(0, isb);
     isb += 8;                      // (nkb >= 2)
+    FPC_H3_ZERO_ACC(2);
     FPC_H3_ISSUE_IN(1, isb);
     isb += 8;
+    FPC_H3_ZERO_ACC(3);
     FPC_H3_ISSUE_IN(2, nkb > 2 ? isb : isb - 8);      // (nkb = 2: step 1 again — the same count of pieces in front of the first wait)
     isb += 8;
     int sn = 3;                    // the next step to stage
+    // (the fold kernels keep the register writes: with the matrix form the allocator hands phase 1's weight registers, whose last
+    // redundant reloads are still in flight, to phase 2's fragment reads, and the compiler guards them with vmcnt(9) .. vmcnt(1)
+    // inside the loop — waits for staging pieces issued a moment ago, +29 % on the kernel: profiles/wino_entry_ledger.md)
+    if constexpr (PH == 0 && FOLD) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j)
+        for (int j = 0; j < 4; ++j)
 #pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
+            for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
+                for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    if (PH == 0) acc[j][mt][nt][r] = 0.f;
+                    for (int r = 0; r < 16; ++r) acc[j][mt][nt][r] = 0.f;
+    }
 
     t_issued = stamp ? clock64() : 0;
     asm volatile("s_waitcnt vmcnt(10)" ::: "memory");      // the weight fragments and step 0 (steps 1, 2 land under step 0's transform; the weights are issued first: right without them too)
@@ -369,6 +390,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_h3(const WinoArgs a) {
 #undef FPC_H3_LOAD_U1_AT
 #undef FPC_H3_LOAD_U2_AT
 #undef FPC_H3_XI_LIVE
+#undef FPC_H3_ZERO_ACC
 #undef FPC_H3_FA
 #undef FPC_H3_FB
 #undef FPC_H3_COLUMN
